@@ -8,7 +8,12 @@ PCIe-inclusive figure is in DESIGN.md).  N > 1: one process per GPU, every rank 
 independent instance (weak scaling, no data-path collective); the timed region is bracketed by a
 barrier + torch.cuda.synchronize() and the MAX over ranks is reported.
 
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds what takes work of its own:
+verification of the proof, the 3-proofs-in-flight batch figures, the instance-list -> proof leg and the CPU baseline.
+--dump-outputs DIR writes the proof of the last timed step as DIR/proof_words.npy (see dump_outputs()).
+
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -41,10 +46,14 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed", type=int, default=1000)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the proof and measure the batch figures, the instance-list -> proof leg and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proof of the last timed step as DIR/proof_words.npy (rank 0)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend: nccl (= RCCL, default) or gloo (rehearsal)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal only: every rank uses GPU 0 (needs --backend gloo)")
-    ap.add_argument("--no-batch-mode", action="store_true", help="skip the extra 3-proofs-in-flight throughput measurement")
+    ap.add_argument("--no-batch-mode", action="store_true", help="--full: skip the extra 3-proofs-in-flight throughput measurement")
     ap.add_argument("--concurrency", type=int, default=1,
                     help="independent proofs in flight per GPU (batch mode, BASELINE config[2]); 1 = single-proof latency (default)")
     ap.add_argument("--table", choices=["g1", "g2", "fq12"], default="g1",
@@ -182,16 +191,19 @@ def main():
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = max_over_ranks(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof if args.steps > 0 else None)
 
-    # every rank checks its own proof outside the timed region
-    S.verify_stark_proof(stark, proof, cfg)
+    # --full: every rank checks its own proof outside the timed region
+    if args.full:
+        S.verify_stark_proof(stark, proof, cfg)
 
-    # batch mode, reported beside the single-proof line: 3 independent proofs in flight on this GPU (one prover context
+    # batch mode (--full), reported beside the single-proof line: 3 independent proofs in flight on this GPU (one prover context
     # and one host thread each, include/sbn.h sbn_batch_prover_*), which fills the latency-bound tails and the
     # host-transcript gaps of one proof with the kernels of the others.  Units are instance lists: witness generation
     # (on the device) is part of the measured work.  Outside the timed region; rank 0 of a single-GPU run only.
     batch = None
-    if rank == 0 and world == 1 and max(args.concurrency, 1) == 1 and not args.no_batch_mode:
+    if args.full and rank == 0 and world == 1 and max(args.concurrency, 1) == 1 and not args.no_batch_mode:
         inflight, units = 3, 3 * max(4, min(args.steps, 10))
         bp = S.BatchProver(stark, cfg, DEGREE_BITS, inflight)          # C ABI: sbn_batch_prover_*
         ios_units = np.broadcast_to(ios, (units,) + ios.shape)
@@ -228,10 +240,10 @@ def main():
         for p in provers[1:]:
             p.close()
 
-    # instance list -> proof with the witness generated on the device (outside the timed region, reported
+    # --full: instance list -> proof with the witness generated on the device (outside the timed region, reported
     # beside the host-generator + PCIe path): wall clock of generate_trace + prove, 5 repetitions after one warm-up
     e2e = None
-    if rank == 0:
+    if args.full and rank == 0:
         prover.generate_trace(ios)
         t0 = time.perf_counter()
         wall_gen = wall_prove = 0.0
@@ -283,7 +295,7 @@ def main():
         if e2e:
             e2e["ios_to_proof_ms_host_witness"] = (t_tracegen + t_h2d) * 1e3 + ms_per_step / max(args.concurrency, 1) * max(args.concurrency, 1)
             line["end_to_end"] = e2e
-        if world == 1 and not args.skip_cpu_baseline:
+        if args.full and world == 1 and not args.skip_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(trace, pi, args.table)
         emit(line)
     prover.close()
@@ -355,6 +367,8 @@ def bench_batch(args, S, np, torch, dist, rank, world, barrier, max_over_ranks):
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = max_over_ranks(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proofs[-1] if proofs else None)
     local = {int(u): sharding.digest(p.words) for u, p in zip(units, proofs)}
     for p in proofs[:2]:
         S.verify_stark_proof(stark, p, cfg)                              # a sample per rank, outside the timed region
@@ -411,6 +425,8 @@ def bench_split(args, S, np, torch, dist, rank, world, barrier, max_over_ranks):
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = max_over_ranks(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof if args.steps > 0 else None)
     S.verify_stark_proof(stark, proof, cfg)
     digests = sharding_gather({rank: digest_of(proof)}, dist)
     if rank == 0:
@@ -480,6 +496,25 @@ def dry_run_plan(args):
                      "collectives": "none on the data path (barrier, MAX of the timed region)",
                      "ranks": [{"rank": r, "seed": sharding.unit_seed(args.seed, r), "proofs": args.steps} for r in range(world)]})
     return plan
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the proof the caller of the timed path receives (StarkProofWithPublicInputs as the canonical
+    u64 words of include/sbn.h) as DIR/proof_words.npy, float64 of shape (words, 2): column 0 the low and column 1 the
+    high 32 bits of every word, so that the values are exact.  The inputs depend on --seed only, so two builds run with
+    the same arguments can be compared output for output."""
+    import numpy as np
+    if proof is None:
+        raise SystemExit("--dump-outputs needs a timed step (--steps >= 1)")
+    w = np.asarray(proof.words, dtype=np.uint64)
+    arr = np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64)
+    if arr.nbytes > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {arr.nbytes} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof_words.npy"), arr)
 
 
 def digest_of(proof):

@@ -89,3 +89,26 @@ def test_bench_dry_run_plans_for_eight_ranks():
     assert b["ranks"][3]["first_units"] == [3, 11, 19, 27]
     d = _dry_run("--gpus", "4")
     assert d["mode"] == "default" and [r["seed"] for r in d["ranks"]] == [1000, 1001, 1002, 1003] and d["launch"].startswith("python -m torch.distributed.run")
+
+
+def test_bench_dump_outputs_keeps_every_proof_word_exact(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed proof as float64 (low, high) 32-bit halves of every word: the u64
+    words come back bit for bit, and a dump above 64 MB is refused instead of written."""
+    import importlib.util
+    import pytest
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Proof:
+        words = np.array([0, 1, 2**32 - 1, 2**32, 0x31564F5250424E53, 2**64 - 2**32 + 1, 2**64 - 1], dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "out"), Proof())
+    a = np.load(tmp_path / "out" / "proof_words.npy")
+    assert a.dtype == np.float64 and a.shape == (len(Proof.words), 2)
+    assert (a[:, 0].astype(np.uint64) | (a[:, 1].astype(np.uint64) << np.uint64(32)) == Proof.words).all()
+    Proof.words = np.zeros(bench.DUMP_LIMIT_BYTES // 16 + 1, dtype=np.uint64)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), Proof())
+    assert not (tmp_path / "big").exists()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "none"), None)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Are the sponge launches of a proof slower right after device witness generation, and which ones?  Reads a rocprofv3 --kernel-trace
-CSV of `bench.py --steps K --no-batch-mode` (K resident proofs, then 1 + 5 generate_trace + prove pairs), groups the
+CSV of `bench.py --full --steps K --no-batch-mode` (K resident proofs, then 1 + 5 generate_trace + prove pairs), groups the
 leaf_absorb_kernel launches by proof (39 per G1 proof) and prints the mean duration of launch 0..38 for proofs that follow a
 tg::range_check_kernel launch against proofs that do not.
 usage: absorb_after_witness.py <dir with *_kernel_trace.csv>"""

@@ -17,7 +17,6 @@ python bench.py --batch 24 --skip-cpu-baseline > gpurun_out/${TAG}_bench_batch24
 python bench.py --batch 256 --seed 1000 --skip-cpu-baseline > gpurun_out/${TAG}_bench_batch256_seed1000.json 2> gpurun_out/${TAG}_bench_batch256_seed1000.err
 SBN_HOST_THREADS=2 python bench.py --batch 24 --skip-cpu-baseline > gpurun_out/${TAG}_bench_batch24_threads2.json 2> /dev/null
 SBN_HOST_THREADS=2 SBN_NO_AVX512=1 python bench.py --batch 24 --skip-cpu-baseline > gpurun_out/${TAG}_bench_batch24_threads2_no_avx512.json 2> /dev/null
-SBN_TRACE_TIMING=1 python bench.py --steps 3 --warmup 1 --skip-cpu-baseline --no-batch-mode 2>&1 > /dev/null | grep "device tracegen" | tail -6 > gpurun_out/${TAG}_tracegen_timing.txt
 (cd tools/microbench && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../starky_bn254_amd/csrc range_check_phases.hip -o /tmp/range_check_phases 2> /dev/null && /tmp/range_check_phases > ../../gpurun_out/${TAG}_range_check_phases.txt)
 (cd tools/microbench && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../starky_bn254_amd/csrc sponge_rate.hip -o /tmp/sponge_rate && /tmp/sponge_rate 12400 > ../../gpurun_out/${TAG}_sponge_rate.txt)
 # every experiment switch (honoured only with SBN_EXPERIMENTAL=1, csrc/settings.hpp) must give the same proof bytes

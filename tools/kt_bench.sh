@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof_ktb
-rocprofv3 --kernel-trace --stats -d $OUT/prof_ktb -o kt --output-format csv -- python3 $ROOT/bench.py --steps 6 --warmup 1 --skip-cpu-baseline --no-batch-mode "$@" > $OUT/kt_bench.json 2> $OUT/kt_bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/prof_ktb -o kt --output-format csv -- python3 $ROOT/bench.py --full --steps 6 --warmup 1 --skip-cpu-baseline --no-batch-mode "$@" > $OUT/kt_bench.json 2> $OUT/kt_bench.err
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, json
 out = sys.argv[1]

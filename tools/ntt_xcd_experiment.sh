@@ -14,8 +14,8 @@ for cfg in "0 0" "1 0" "0 16" "1 16" "1 8" "1 32"; do
   if [ "$2" = "0" ]; then unset SBN_NTT_SUB; else export SBN_NTT_SUB=$2; fi
   tag="xcd$1_sub$2"
   python3 $ROOT/bench.py --steps 10 --warmup 2 --skip-cpu-baseline --no-batch-mode > $OUT/nx_$tag.json 2> $OUT/nx_$tag.err || { echo "bench failed: $tag"; exit 1; }
-  rocprofv3 --pmc FETCH_SIZE -d $OUT/nx_f_$tag -o f --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 0 --skip-cpu-baseline --no-batch-mode > $OUT/nx_f_$tag.log 2>&1 || { echo "pmc failed: $tag"; exit 1; }
-  rocprofv3 --pmc WRITE_SIZE -d $OUT/nx_w_$tag -o w --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 0 --skip-cpu-baseline --no-batch-mode > $OUT/nx_w_$tag.log 2>&1 || { echo "pmc failed: $tag"; exit 1; }
+  rocprofv3 --pmc FETCH_SIZE -d $OUT/nx_f_$tag -o f --output-format csv -- python3 $ROOT/bench.py --full --steps 2 --warmup 0 --skip-cpu-baseline --no-batch-mode > $OUT/nx_f_$tag.log 2>&1 || { echo "pmc failed: $tag"; exit 1; }
+  rocprofv3 --pmc WRITE_SIZE -d $OUT/nx_w_$tag -o w --output-format csv -- python3 $ROOT/bench.py --full --steps 2 --warmup 0 --skip-cpu-baseline --no-batch-mode > $OUT/nx_w_$tag.log 2>&1 || { echo "pmc failed: $tag"; exit 1; }
   python3 - "$OUT" "$tag" >> $OUT/ntt_xcd_experiment.txt <<'PY'
 import csv, glob, json, sys
 out, tag = sys.argv[1], sys.argv[2]

@@ -9,7 +9,7 @@ i=0
 for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_ANY" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU_MFMA_I8"; do
   i=$((i+1))
-  rocprofv3 --pmc $set -d $OUT/prof_sq$i -o s --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 0 --skip-cpu-baseline --no-batch-mode > $OUT/pmc_sq$i.log 2>&1 || echo "pass $i failed: $set"
+  rocprofv3 --pmc $set -d $OUT/prof_sq$i -o s --output-format csv -- python3 $ROOT/bench.py --full --steps 2 --warmup 0 --skip-cpu-baseline --no-batch-mode > $OUT/pmc_sq$i.log 2>&1 || echo "pass $i failed: $set"
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections, re
