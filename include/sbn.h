@@ -196,7 +196,9 @@ uint64_t* sbn_prover_trace_device_ptr(sbn_prover* p);
  * public inputs, bit for bit, as sbn_generate_trace_{g1,g2,fq12}_exp; afterwards the prover is loaded and
  * sbn_prover_prove can run.  pi_out (optional): [num_public_inputs].  G1_EXP / G2_EXP / FQ_EXP: 2^16 .. 2^18 rows (the
  * reference pads to any power of two >= 128 instances, src/curves/g1/circuit.rs:273-277; SBN_ERR_UNSUPPORTED beyond: use
- * the host generators + sbn_prover_load_trace); FQ12_EXP, FQ12_EXP_U64: any size. */
+ * the host generators + sbn_prover_load_trace); FQ12_EXP, FQ12_EXP_U64: any size.  A call that fails, for whatever reason
+ * (a coordinate >= p, a degenerate instance, a non-canonical exponent), leaves NO trace loaded: sbn_prover_prove then fails
+ * with SBN_ERR_BAD_ARG until a trace is generated or loaded again. */
 int sbn_prover_generate_trace(sbn_prover* p, const uint32_t* ios, size_t num_io, uint64_t* pi_out);
 /* Device -> host copy of the loaded trace, column-major [num_columns][N] (tests, debugging). */
 int sbn_prover_read_trace(sbn_prover* p, uint64_t* trace_out);
@@ -306,6 +308,13 @@ int sbn_poseidon_permute_batch(uint64_t* states, size_t count);
  * canonicalisation; mode 0), or the weak product of the transform passes canonicalised afterwards (mode 1).  a, b: any 64-bit
  * values (non-canonical representatives included: the kernels' intermediate values are); out canonical.  Host in/out. */
 int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int mode);
+/* The BN254 base-field helpers of the witness generators (csrc/bn254w.cuh, csrc/kernels_tracegen.cuh) on `count` elements of four
+ * little-endian u64 words in standard form.  op 0: a*b through the Montgomery product (to_m, mmul, from_m); 1: a+b; 2: a-b;
+ * 3: a^-1 (device: Fermat, host: binary extended GCD); 4: a^-1 by Montgomery's trick over consecutive groups of 8 (count % 8 == 0);
+ * 5: (c0 + c1 i)^-1 in Fq2 through the norm, c0 from a and c1 from b, out [count][2][4].  on_device = 0 runs the host build of
+ * the same functions (no device needed).  SBN_ERR_NON_CANONICAL for an input >= p, SBN_ERR_BAD_ARG for a zero to invert.
+ * Parity tests only; host in/out. */
+int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device);
 /* The host permutation behind the Fiat-Shamir transcript of prove()/verify() (plonky2 Challenger's
  * PoseidonPermutation): sparse partial rounds, or the plain definition when use_definition != 0.  Host only. */
 int sbn_poseidon_permute_host(uint64_t* states, size_t count, int use_definition);

@@ -36,7 +36,7 @@ EXPORTS = [
     "sbn_prover_generate_trace", "sbn_prover_read_trace",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_prove", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
-    "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch",
+    "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
     "sbn_split_prover_load_trace", "sbn_split_prover_prove", "sbn_split_prover_stage_times",
     "sbn_abi_version", "sbn_rccl_unique_id", "sbn_rccl_comm_create", "sbn_rccl_comm_destroy",
@@ -126,6 +126,7 @@ def lib():
         L.sbn_poseidon_permute_batch.argtypes = [vp, sz]
         L.sbn_poseidon_permute_host.argtypes = [vp, sz, C.c_int]
         L.sbn_field_mul_batch.argtypes = [vp, vp, vp, sz, C.c_int]
+        L.sbn_bn254_fq_batch.argtypes = [C.c_int, vp, vp, vp, sz, C.c_int]
         L.sbn_set_device.argtypes = [C.c_int]
         L.sbn_set_thread_device.argtypes = [C.c_int]
         L.sbn_host_curve_chains.argtypes = [C.c_int, vp, sz, vp, vp, C.c_int]
@@ -606,6 +607,23 @@ def field_mul_batch(a, b, mode=0):
     out = np.zeros_like(a)
     _check(lib().sbn_field_mul_batch(_ptr(a), _ptr(b), _ptr(out), a.shape[0], mode))
     return out
+
+
+BN254_FQ_OPS = {"mul": 0, "add": 1, "sub": 2, "inv": 3, "batch_inv": 4, "fq2_inv": 5}   # sbn_bn254_fq_batch (include/sbn.h)
+
+
+def bn254_fq_batch(op, a, b=None, on_device=True):
+    """The BN254 base-field helpers of the witness generators on Python ints below p (test hook): op in BN254_FQ_OPS; a, b lists of
+    ints.  Returns a list of ints, or of (c0, c1) pairs for "fq2_inv" (a = c0, b = c1).  on_device=False runs the host build."""
+    def words(vals):
+        return np.array([[(v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(4)] for v in vals], dtype=np.uint64).reshape(len(vals), 4)
+    code = BN254_FQ_OPS[op]
+    wa = words(a)
+    wb = words(b) if b is not None else None
+    out = np.zeros((len(a), 2 if op == "fq2_inv" else 1, 4), dtype=np.uint64)
+    _check(lib().sbn_bn254_fq_batch(code, _ptr(wa), _ptr(wb), _ptr(out), len(a), 1 if on_device else 0))
+    vals = [[sum(int(w) << (64 * j) for j, w in enumerate(e)) for e in row] for row in out]
+    return [tuple(v) for v in vals] if op == "fq2_inv" else [v[0] for v in vals]
 
 
 def eval_constraints_host(stark, local_row, next_row, public_inputs, alphas, z_last, l_first, l_last):

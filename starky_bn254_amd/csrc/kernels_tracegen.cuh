@@ -22,8 +22,9 @@ namespace tg {
 using namespace bnw;
 
 
-// a^(p-2) with 4-bit fixed windows (252 squarings + <= 64 + 14 products).
-__device__ __noinline__ Fq finv_fermat(const Fq& a) {
+// a^(p-2) with 4-bit fixed windows (252 squarings + <= 64 + 14 products).  The inversion helpers below are host-device only so that
+// sbn_bn254_fq_batch (prover.hip) can run the host build of them as well; the kernels use the device build.
+__host__ __device__ __noinline__ Fq finv_fermat(const Fq& a) {
   constexpr u64 PL[4] = BNW_PL;
   const u64 e[4] = {PL[0] - 2, PL[1], PL[2], PL[3]};
   Fq tab[16];
@@ -43,15 +44,15 @@ __device__ __noinline__ Fq finv_fermat(const Fq& a) {
 // product with one Fermat chain (~330 multiplies) and walks back with two multiplies per value, so an inversion costs ~45
 // multiplies instead of ~330.  A coordinate in Fq2 is inverted through its norm a^2 + b^2 (an Fq value): 1/(a + bi) = (a - bi) / norm.
 static constexpr int TG_INV_BATCH = 8;
-__device__ __forceinline__ Fq cnorm(const Co<1>& a) { return a.c[0]; }
-__device__ __forceinline__ Fq cnorm(const Co<2>& a) { return fadd(mmul(a.c[0], a.c[0]), mmul(a.c[1], a.c[1])); }
-__device__ __forceinline__ Co<1> cinv_from_norm(const Co<1>&, const Fq& ni) { Co<1> r; r.c[0] = ni; return r; }
-__device__ __forceinline__ Co<2> cinv_from_norm(const Co<2>& a, const Fq& ni) {
+GL_HD Fq cnorm(const Co<1>& a) { return a.c[0]; }
+GL_HD Fq cnorm(const Co<2>& a) { return fadd(mmul(a.c[0], a.c[0]), mmul(a.c[1], a.c[1])); }
+GL_HD Co<1> cinv_from_norm(const Co<1>&, const Fq& ni) { Co<1> r; r.c[0] = ni; return r; }
+GL_HD Co<2> cinv_from_norm(const Co<2>& a, const Fq& ni) {
   Co<2> r; r.c[0] = mmul(a.c[0], ni); r.c[1] = fsub(Fq{{0, 0, 0, 0}}, mmul(a.c[1], ni));
   return r;
 }
 // nrm[j] (all non-zero) -> nrm[j]^-1, j < TG_INV_BATCH
-__device__ __forceinline__ void batch_inverse(Fq (&nrm)[TG_INV_BATCH]) {
+GL_HD void batch_inverse(Fq (&nrm)[TG_INV_BATCH]) {
   Fq pre[TG_INV_BATCH];
   pre[0] = nrm[0];
 #pragma unroll
@@ -941,6 +942,45 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
     for (int r = tid; r < KT - c65; r += RC_THREADS) assign_deferred(pooled + r, 65535);
   }
   RC_MARK(8);
+}
+
+// ---- parity hook (sbn_bn254_fq_batch, prover.hip): the field helpers above on standard-form operands, 4 words per element --------------
+enum { FQB_MUL = 0, FQB_ADD = 1, FQB_SUB = 2, FQB_INV = 3, FQB_BATCH_INV = 4, FQB_FQ2_INV = 5 };
+// Item i of op: element i, or group i of TG_INV_BATCH elements for FQB_BATCH_INV.  FQB_INV is finv_fermat on the device and inv_std on
+// the host; FQB_FQ2_INV reads c0 from a and c1 from b and writes out[i] = {c0, c1} (8 words).
+GL_HD void fq_batch_item(int op, const u64* a, const u64* b, u64* out, size_t i) {
+  if (op == FQB_MUL) { from_m(mmul(to_m(a + 4 * i), to_m(b + 4 * i)), out + 4 * i); return; }
+  if (op == FQB_ADD || op == FQB_SUB) {
+    Fq x, y;
+    for (int j = 0; j < 4; j++) { x.l[j] = a[4 * i + j]; y.l[j] = b[4 * i + j]; }
+    const Fq r = op == FQB_ADD ? fadd(x, y) : fsub(x, y);
+    for (int j = 0; j < 4; j++) out[4 * i + j] = r.l[j];
+    return;
+  }
+  if (op == FQB_INV) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    from_m(finv_fermat(to_m(a + 4 * i)), out + 4 * i);
+#else
+    inv_std(a + 4 * i, out + 4 * i);
+#endif
+    return;
+  }
+  if (op == FQB_BATCH_INV) {
+    Fq v[TG_INV_BATCH];
+    for (int j = 0; j < TG_INV_BATCH; j++) v[j] = to_m(a + 4 * (TG_INV_BATCH * i + j));
+    batch_inverse(v);
+    for (int j = 0; j < TG_INV_BATCH; j++) from_m(v[j], out + 4 * (TG_INV_BATCH * i + j));
+    return;
+  }
+  if (op == FQB_FQ2_INV) {
+    Co<2> c; c.c[0] = to_m(a + 4 * i); c.c[1] = to_m(b + 4 * i);
+    const Co<2> r = cinv_from_norm(c, finv_fermat(cnorm(c)));
+    from_m(r.c[0], out + 8 * i); from_m(r.c[1], out + 8 * i + 4);
+  }
+}
+__global__ void fq_batch_kernel(int op, const u64* __restrict__ a, const u64* __restrict__ b, u64* __restrict__ out, size_t items) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < items) fq_batch_item(op, a, b, out, i);
 }
 
 }  // namespace tg

@@ -1025,7 +1025,6 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   HIPC(hipSetDevice(P->device));
   hipStream_t st = P->stream;
   const ExpShape sh = exp_shape(P->air);
-  P->loaded = false;
   // carve the scratch
   u64* const wbase = P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde;   // scratch: the LDE buffer, not yet in use
   u64* w = wbase;
@@ -1167,7 +1166,6 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   HIPC(hipSetDevice(P->device));
   hipStream_t st = P->stream;
   const ExpShape sh = exp_shape(P->air);
-  P->loaded = false;
   u64* const wbase = P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde;   // scratch: the LDE buffer, not yet in use
   u64* w = wbase;
   auto take = [&](size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; };
@@ -1266,7 +1264,6 @@ static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K
   HIPC(hipSetDevice(P->device));
   hipStream_t st = P->stream;
   const ExpShape sh = exp_shape(P->air);
-  P->loaded = false;
   u64* const wbase = P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde;   // scratch: the LDE buffer, not yet in use
   u64* w = wbase;
   auto take = [&](size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; };
@@ -1326,7 +1323,9 @@ static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K
 }
 
 extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
-  if (!P || !ios) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;   // before any check: a refused instance list must not leave the previous trace provable
+  if (!ios) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (!is_exp_air(P->air.kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
   if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
   if (P->n != exp_rows_per_instance(P->air.kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
@@ -1961,6 +1960,42 @@ extern "C" int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_
   }
   (void)hipFree(d);
   if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_field_mul_batch: %s", hipGetErrorString(e));
+  return SBN_OK;
+}
+
+extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
+  using namespace tg;
+  if (op < FQB_MUL || op > FQB_FQ2_INV) return fail(SBN_ERR_BAD_ARG, "unknown op %d", op);
+  const bool binary = op == FQB_MUL || op == FQB_ADD || op == FQB_SUB || op == FQB_FQ2_INV;
+  if (!a || !out || (binary && !b)) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (op == FQB_BATCH_INV && count % TG_INV_BATCH) return fail(SBN_ERR_BAD_ARG, "batch inverse needs a multiple of %d values", TG_INV_BATCH);
+  for (size_t i = 0; i < count; i++) {
+    if (bnw::geq_p(a + 4 * i) || (binary && bnw::geq_p(b + 4 * i))) return fail(SBN_ERR_NON_CANONICAL, "element %zu is not below p", i);
+    const bool za = !(a[4 * i] | a[4 * i + 1] | a[4 * i + 2] | a[4 * i + 3]);
+    const bool zb = !binary || !(b[4 * i] | b[4 * i + 1] | b[4 * i + 2] | b[4 * i + 3]);
+    if ((op == FQB_INV || op == FQB_BATCH_INV) && za) return fail(SBN_ERR_BAD_ARG, "element %zu is zero: no inverse", i);
+    if (op == FQB_FQ2_INV && za && zb) return fail(SBN_ERR_BAD_ARG, "element %zu is zero: no inverse", i);
+  }
+  const size_t items = op == FQB_BATCH_INV ? count / TG_INV_BATCH : count, out_words = 4 * count * (op == FQB_FQ2_INV ? 2 : 1);
+  if (!on_device) {
+    for (size_t i = 0; i < items; i++) fq_batch_item(op, a, b, out, i);
+    return SBN_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
+  HIPC(hipSetDevice(g_device));
+  if (count == 0) return SBN_OK;
+  u64* d = nullptr;
+  HIPC(hipMalloc((void**)&d, (8 * count + out_words) * sizeof(u64)));
+  hipError_t e = hipMemcpy(d, a, 4 * count * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess && binary) e = hipMemcpy(d + 4 * count, b, 4 * count * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fq_batch_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, 0, op, d, d + 4 * count, d + 8 * count, items);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, d + 8 * count, out_words * sizeof(u64), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_bn254_fq_batch: %s", hipGetErrorString(e));
   return SBN_OK;
 }
 
