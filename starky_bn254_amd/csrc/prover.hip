@@ -125,29 +125,15 @@ struct sbn_prover {
   hipEvent_t ev[ST_COUNT + 1];
   float stage_ms[ST_COUNT + EX_COUNT];
   size_t ntt_chunk;
-  size_t ntt_sub = 0;                        // SBN_NTT_SUB: transform the columns of a chunk in sub-chunks of this many (0: whole chunk)
-  bool ntt_xcd = true;                       // (columns, tiles) grid order in the fast passes; SBN_NTT_XCD=0: (tiles, columns)
-  bool fast_ntt = true;                      // SBN_FAST_NTT=0 selects the generic radix-2 pass everywhere
   bool ntt_fused = false;                    // the inverse transform's pass B and the LDE's pass A as ONE kernel (2^16 / 2^17 rows)
   u64* d_tmp2 = nullptr;                     // its output: the fused kernel cannot work in place
-  // EXPERIMENT (SBN_RANGE_ASYNC=1; measured, no gain: profiles/r4_range_async_ab.txt)
-  // u16 range check of the curve witness BEHIND the call that generated it (n <= 2^16 rows): it writes the last columns of the trace
-  // (start_lookups ..), which the trace commitment reaches after ~14 of its 27 chunks; it runs on its own stream, the commitment
-  // joins it before the first chunk that holds such a column, every other reader of the trace joins it first (rc_finish), and its
-  // error word (own allocation: the witness scratch lives in the LDE buffer the commitment overwrites) is checked by prove()
-  hipStream_t rstream = nullptr;
-  hipEvent_t rows_done = nullptr, rc_done = nullptr;
-  int* d_rc_err = nullptr;
-  bool rc_pending = false;
-  size_t rc_first_col = 0;
   u64* d_tmp3 = nullptr;                     // 2^18 rows, two transform streams: the fused kernel's second output buffer (chunks alternate)
-  bool ntt_fused512 = false;                 // 2^18-row tables: kernels_ntt.cuh ntt_fused512_inv_b_lde_a_kernel (SBN_NTT_FUSED=0: separate passes)
+  bool ntt_fused512 = false;                 // 2^18-row tables: kernels_ntt.cuh ntt_fused512_inv_b_lde_a_kernel
   hipStream_t hstream = nullptr;             // sponge absorption / Merkle stream
   hipStream_t nstream = nullptr;             // second transform stream (2^19 LDE rows and up): the LDE of chunk k beside the inverse transform of chunk k+1
   hipEvent_t intt_done[MAX_CHUNKS];          // main -> second transform stream: the coefficients of chunk k are complete
   bool ntt_two_streams = false;
   Settings set;                              // the SBN_* switches this prover was created under (settings.hpp)
-  unsigned gen_calls = 0;                    // generate_trace calls so far (SBN_TRACEGEN_SKIP spares the first)
   int chain_mode = 0;                        // curve witness: 0 host pool, 1 one lane per instance, 2 one wave per instance
   hipEvent_t chunk_ready[MAX_CHUNKS];        // main -> hash: LDE chunk k is complete
   hipEvent_t abs_ev[2 * MAX_CHUNKS];         // hash stream: before/after each absorb launch
@@ -200,17 +186,17 @@ static int ntt_columns(sbn_prover* P, const u64* in, size_t in_cs, u64* out, siz
     size_t la = ((size_t)1 << pa.log_r) * ((1u << pa.log_t) + 1) * 8, lb = ((size_t)1 << pb.log_r) * ((1u << pb.log_t) + 1) * 8;
     const u32 kperm = inverse ? 11u : 5u;  // omega_16 = (2^12)^13, omega_16^-1 = (2^12)^3: 13^-1 = 5, 3^-1 = 11 (mod 16)
     auto launch = [&](NttPassParams q, dim3 grid, size_t lds_bytes) {
-      const bool fast = P->fast_ntt && q.log_t == 4 && (q.log_r == 8 || q.log_r == 9);
-      if (fast && P->ntt_xcd) { q.xcd_order = 1; std::swap(grid.x, grid.y); }
+      const bool fast = q.log_t == 4 && (q.log_r == 8 || q.log_r == 9);
+      if (fast) { q.xcd_order = 1; std::swap(grid.x, grid.y); }   // (columns, tiles) grid order (kernels_ntt.cuh NttPassParams::xcd_order)
       if (fast && q.log_r == 8) hipLaunchKernelGGL(ntt_fast_pass_kernel<0>, grid, dim3(256), 16 * 272 * 8, st, q, kperm);
       else if (fast) hipLaunchKernelGGL(ntt_fast_pass_kernel<1>, grid, dim3(256), 32 * 272 * 8, st, q, kperm);
       else hipLaunchKernelGGL(ntt_pass_kernel, grid, dim3(NTT_THREADS), lds_bytes, st, q);
     };
-    if (P->fast_ntt && pa.log_r == 9 && log_n2 >= 4) pa.log_t = 4;  // the fast kernel always uses 16-wide tiles
-    if (P->fast_ntt && pb.log_r == 9 && log_n1 >= 4) pb.log_t = 4;
+    if (pa.log_r == 9 && log_n2 >= 4) pa.log_t = 4;  // the fast kernel always uses 16-wide tiles
+    if (pb.log_r == 9 && log_n1 >= 4) pb.log_t = 4;
     // 1,024-point first pass over an input whose rows 512.. are zero (the 2^19-point coset LDE): two 512-point fast passes
     // on grid.z (kernels_ntt.cuh NttPassParams::split) instead of the generic radix-2 pass
-    const bool split_a = P->fast_ntt && !inverse && pa.log_r == 10 && log_n2 >= 4 && pa.in_st == 1 && n_in <= (size_t)512 * pa.in_sr && pre == P->d_shift && P->d_shift_odd;
+    const bool split_a = !inverse && pa.log_r == 10 && log_n2 >= 4 && pa.in_st == 1 && n_in <= (size_t)512 * pa.in_sr && pre == P->d_shift && P->d_shift_odd;
     if (split_a) { pa.log_r = 9; pa.log_t = 4; pa.split = 1; pa.pre2 = P->d_shift_odd; }
     ga = dim3((unsigned)(n2 >> pa.log_t), (unsigned)nc, split_a ? 2u : 1u); gb = dim3((unsigned)(n1 >> pb.log_t), (unsigned)nc);
     la = ((size_t)1 << pa.log_r) * ((1u << pa.log_t) + 1) * 8; lb = ((size_t)1 << pb.log_r) * ((1u << pb.log_t) + 1) * 8;
@@ -235,6 +221,14 @@ static int ntt_fast_setup() {  // idempotent, so a race between prover threads i
     done[d].store(true);
   }
   return 0;
+}
+// The transform kernels of a table, a function of its size alone.  create_ctx and sbn_commit_values both pick them here, so the
+// parity tests of sbn_commit_values run the kernels the prover runs.  2^16 / 2^17 rows: the fused middle pass; 2^18 rows (the
+// 2^19-point LDE): its 512-point form, and the LDE's 1,024-point first pass as two 512-point halves -- both read d_shift_odd,
+// which the callers allocate exactly when ntt_fused512 is set.
+static void ntt_plan(sbn_prover* P) {
+  P->ntt_fused = P->degree_bits == 16 || P->degree_bits == 17;
+  P->ntt_fused512 = P->degree_bits == 18 && P->lde_log == 19;
 }
 
 // values [ncols][n] -> coefficients [ncols][n]
@@ -296,19 +290,6 @@ static int intt_lde_cols(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, siz
   if (rc) return rc;
   return ntt_columns(P, cf, P->n, lde_out, P->m, P->d_tmp, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1);
 }
-static int intt_then_lde_chunk(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t c0, size_t nc) {
-  if (!P->ntt_sub) return intt_lde_cols(P, vals + c0 * P->n, coef + c0 * P->n, lde + c0 * P->m, nc);
-  const size_t sub = P->ntt_sub ? P->ntt_sub : nc;
-  for (size_t s0 = 0; s0 < nc; s0 += sub) {   // (sub-chunks reuse the front of d_tmp: an experiment in L2 residency, SBN_NTT_SUB)
-    const size_t a = c0 + s0, k = std::min(sub, nc - s0);
-    int rc = ntt_columns(P, vals + a * P->n, P->n, coef + a * P->n, P->n, P->d_tmp, P->m, k, P->degree_bits, true, P->n, nullptr, nullptr,
-                         host_inv_pow2(P->degree_bits));
-    if (rc) return rc;
-    rc = ntt_columns(P, coef + a * P->n, P->n, lde + a * P->m, P->m, P->d_tmp, P->m, k, P->lde_log, false, P->n, P->d_shift, nullptr, 1);
-    if (rc) return rc;
-  }
-  return 0;
-}
 
 static int tree_alloc(DevTree& t, size_t nleaf, u32 cap_height) {
   t.nleaf = nleaf;
@@ -322,12 +303,11 @@ static int tree_build_inner(sbn_prover* P, DevTree& t, hipStream_t st) {
   // workgroup (one wave per SIMD), one launch per level; the last <= 16 parents finish inside one workgroup.
   // Round 3: the narrow levels (<= 8192 parents) run FIVE levels per launch -- a workgroup owns 32 consecutive nodes and hashes its
   // own 16 -> 8 -> 4 -> 2 -> 1 parents through LDS (merkle_subtree_kernel, 16 lanes per permutation), so a 2^17-leaf tree takes
-  // 3 + 2 launches instead of 3 + 10 and the dependent chain loses eight launch gaps (SBN_MERKLE_FUSE=0: one launch per level, A/B).
-  const bool fuse = P->set.merkle_fuse;
+  // 3 + 2 launches instead of 3 + 10 and the dependent chain loses eight launch gaps.
   u32 l0 = 0;
   while (l0 < t.nlevels) {
     const size_t parents = t.nleaf >> (l0 + 1);
-    if (fuse && parents <= 8192 && parents >= 16 && ((t.nleaf >> l0) % 32) == 0) {
+    if (parents <= 8192 && parents >= 16 && ((t.nleaf >> l0) % 32) == 0) {
       const u32 nlev = std::min<u32>(t.nlevels - l0, 5);
       hipLaunchKernelGGL(merkle_subtree_kernel, dim3((unsigned)((t.nleaf >> l0) / 32)), dim3(MERKLE_SUBTREE_THREADS), 0, st, t.d, t.nleaf, l0, nlev, 32u);
       l0 += nlev;
@@ -358,13 +338,11 @@ static int tree_from_matrix(sbn_prover* P, DevTree& t, const u64* lde, size_t nc
 }
 // PolynomialBatch::from_values for a wide matrix: per column chunk iNTT + coset LDE on the main stream,
 // sponge absorption of that chunk on the hash stream, then the Merkle levels; main waits at the end.
-static int intt_then_lde_chunk(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t c0, size_t nc);
 static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t ncols, DevTree& t, int ex_ms, int ex_launches) {
   size_t ch = P->ntt_chunk;
   size_t nchunks = (ncols + ch - 1) / ch;
   if (nchunks > (size_t)MAX_CHUNKS) return fail(SBN_ERR_UNSUPPORTED, "too many column chunks");
   if (ncols <= 4) {   // hash_or_noop: a leaf of at most 4 elements is its own digest (MyStark's 4 columns and its 2 Z columns)
-    if (P->rc_pending && vals == P->d_trace) HIPC(hipStreamWaitEvent(P->stream, P->rc_done, 0));
     int rc = intt_then_lde(P, vals, coef, lde, ncols);
     if (rc) return rc;
     P->stage_ms[ST_COUNT + ex_launches] = 0;
@@ -375,21 +353,16 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
   // behind the LDE of chunk k -- 28.3 -> 29.6 ms per proof: the stage is bound by the VALU work of sponge + transforms
   // together, not by the latency of the transform stream, and more transform waves in flight only slow the sponge launches
   // (12.3 -> 14.8 ms of sponge kernel time).
-  bool rc_joined = !(P->rc_pending && vals == P->d_trace);
   for (size_t k = 0; k < nchunks; k++) {
     size_t c0 = k * ch, nc = std::min(ch, ncols - c0);
     int rc;
-    if (!rc_joined && c0 + nc > P->rc_first_col) {   // the first chunk with a column the asynchronous range check writes
-      HIPC(hipStreamWaitEvent(P->stream, P->rc_done, 0));
-      rc_joined = true;
-    }
-    if (P->ntt_two_streams && !P->ntt_sub && (P->ntt_fused || P->ntt_fused512) && P->d_tmp3) {
+    if (P->ntt_two_streams && (P->ntt_fused || P->ntt_fused512) && P->d_tmp3) {
       // the fused kernel of chunk k writes buffer k & 1, which the LDE pass B of chunk k - 2 (second stream) must have left
       if (k >= 2) HIPC(hipStreamWaitEvent(P->stream, P->chunk_ready[k - 2], 0));
       rc = intt_lde_cols_fused(P, vals + c0 * P->n, coef + c0 * P->n, lde + c0 * P->m, nc, (k & 1) ? P->d_tmp3 : P->d_tmp2, P->nstream, P->intt_done[k]);
       if (rc) return rc;
       HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
-    } else if (P->ntt_two_streams && !P->ntt_sub && !P->ntt_fused && !P->ntt_fused512) {
+    } else if (P->ntt_two_streams && !P->ntt_fused && !P->ntt_fused512) {
       rc = ntt_columns(P, vals + c0 * P->n, P->n, coef + c0 * P->n, P->n, P->d_tmp, P->m, nc, P->degree_bits, true, P->n, nullptr, nullptr, host_inv_pow2(P->degree_bits));
       if (rc) return rc;
       HIPC(hipEventRecord(P->intt_done[k], P->stream));
@@ -398,7 +371,7 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
       if (rc) return rc;
       HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
     } else {
-      rc = intt_then_lde_chunk(P, vals, coef, lde, c0, nc);
+      rc = intt_lde_cols(P, vals + c0 * P->n, coef + c0 * P->n, lde + c0 * P->m, nc);
       if (rc) return rc;
       HIPC(hipEventRecord(P->chunk_ready[k], P->stream));
     }
@@ -657,12 +630,9 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   }
   const Settings& set = P->set;
   if (set.ntt_chunk) P->ntt_chunk = (size_t)set.ntt_chunk;
-  P->fast_ntt = set.fast_ntt; P->ntt_xcd = set.ntt_xcd;
-  P->ntt_fused = P->fast_ntt && (degree_bits == 16 || degree_bits == 17) && set.ntt_fused;   // SBN_NTT_FUSED=0: four separate passes (A/B)
-  P->ntt_fused512 = P->fast_ntt && degree_bits == 18 && P->lde_log == 19 && set.ntt_split1024 && set.ntt_fused;
+  ntt_plan(P);
   // with the fused middle pass the chunk also crosses the transform's second buffer: 40 columns (0.605 -> 0.589 s, profiles/r4_fused512.txt)
   if (P->ntt_fused512 && !set.ntt_chunk) P->ntt_chunk = 40;
-  P->ntt_sub = (size_t)set.ntt_sub;
   // curve chains of the device witness: the host pool when the CPU has AVX-512 IFMA (eight instances per register: 128 instances
   // are 16 tasks of ~0.15 ms, chains_ifma.hpp) or the pool has the threads for the scalar form (2.2 ms on 16), else one wave per
   // instance on the device (5.2 ms whatever the host share: an 8-rank node may leave a rank two CPUs, where the scalar host chains
@@ -671,17 +641,11 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   acc(ntt_fast_setup());
   hipc(hipStreamCreate(&P->stream), "hipStreamCreate");
   hipc(hipStreamCreate(&P->hstream), "hipStreamCreate");
-  if (is_exp_air(as.kind)) {   // the asynchronous range check of the curve witness (sbn_prover::rstream)
-    hipc(hipStreamCreate(&P->rstream), "hipStreamCreate");
-    hipc(hipEventCreateWithFlags(&P->rows_done, hipEventDisableTiming), "hipEventCreate");
-    hipc(hipEventCreateWithFlags(&P->rc_done, hipEventDisableTiming), "hipEventCreate");
-    hipc(hipMalloc((void**)&P->d_rc_err, 256), "hipMalloc");
-  }
   // From 2^19 LDE rows up the transform stream, not the sum of the instruction streams, bounds the commitments (profiles/
   // r3_v8_fq12_512_kernel_stats.csv: five passes of 410 us per chunk beside a 1.19 ms sponge launch, 1.63 ms of VALU work in a 2.05 ms
-  // period): the LDE passes of chunk k then run on a second stream beside the inverse passes of chunk k+1 (SBN_NTT_STREAMS=1: one
-  // stream, =2: two streams at any size -- at 2^16 rows, where the stage IS at its VALU bound, this was measured slower in round 2).
-  P->ntt_two_streams = set.ntt_streams ? set.ntt_streams == 2 : P->lde_log >= 19;
+  // period): the LDE passes of chunk k then run on a second stream beside the inverse passes of chunk k+1 (two streams at 2^16 rows,
+  // where the stage IS at its VALU bound, were measured slower in round 2).
+  P->ntt_two_streams = P->lde_log >= 19;
   if (P->ntt_two_streams) {
     hipc(hipStreamCreate(&P->nstream), "hipStreamCreate");
     for (auto& e : P->intt_done) hipc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
@@ -752,7 +716,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   acc(dmalloc(&P->d_q, 2 * m)); acc(dmalloc(&P->d_qlde, 4 * m));
   acc(tree_alloc(P->tree_q, m, cfg->cap_height));
   acc(dmalloc(&P->d_tw_f, m)); acc(dmalloc(&P->d_tw_i, m)); acc(dmalloc(&P->d_shift, m)); acc(dmalloc(&P->d_shift_inv, m));
-  if (P->lde_log == 19 && set.ntt_split1024) acc(dmalloc(&P->d_shift_odd, n));   // SBN_NTT_SPLIT1024=0: generic first pass (A/B)
+  if (P->ntt_fused512) acc(dmalloc(&P->d_shift_odd, n));   // (ntt_plan)
   acc(dmalloc(&P->d_xs, m)); acc(dmalloc(&P->d_lag_first, m)); acc(dmalloc(&P->d_lag_last, m));
   P->apow_n = apow_len(as.nconstraints, as.nzs);
   acc(dmalloc(&P->d_apow, (size_t)SBN_NCH * P->apow_n));
@@ -828,7 +792,6 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
 extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (!P) return;
   (void)hipSetDevice(P->device);
-  if (P->rc_pending) (void)hipEventSynchronize(P->rc_done);
   u64* bufs[] = {P->d_trace, P->d_coef, P->d_lde, P->d_tmp, P->d_tmp2, P->d_tmp3, P->d_zval, P->d_zcoef, P->d_zlde, P->d_q, P->d_qlde, P->tree_t.d, P->tree_z.d,
                  P->tree_q.d, P->d_tw_f, P->d_tw_i, P->d_shift, P->d_shift_inv, P->d_xs, P->d_lag_first, P->d_lag_last, P->d_apow, P->d_zpow,
                  P->d_open, P->d_part, P->d_w, P->d_fa, P->d_fcoef, P->d_fcoef2, P->d_pow, P->d_qbuf, P->d_shift_odd};
@@ -857,10 +820,6 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (P->h_open) (void)hipHostFree(P->h_open);
   if (P->h_open2) (void)hipHostFree(P->h_open2);
   if (P->hstream) (void)hipStreamDestroy(P->hstream);
-  if (P->rstream) (void)hipStreamDestroy(P->rstream);
-  if (P->rows_done) (void)hipEventDestroy(P->rows_done);
-  if (P->rc_done) (void)hipEventDestroy(P->rc_done);
-  if (P->d_rc_err) (void)hipFree(P->d_rc_err);
   if (P->nstream) { (void)hipStreamDestroy(P->nstream); for (auto& e : P->intt_done) if (e) (void)hipEventDestroy(e); }
   if (P->stream) (void)hipStreamDestroy(P->stream);
   delete P;
@@ -873,21 +832,9 @@ static int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi) {
   P->pi.assign(pi, pi + n_pi);
   return 0;
 }
-// The asynchronous range check (sbn_prover::rstream): every reader or writer of the trace other than the trace commitment waits
-// for it here and learns its verdict; prove() calls this after the commitment, which joined it on the stream.
-static int rc_finish(sbn_prover* P) {
-  if (!P->rc_pending) return SBN_OK;
-  P->rc_pending = false;
-  int err = 0;
-  HIPC(hipEventSynchronize(P->rc_done));
-  HIPC(hipMemcpy(&err, P->d_rc_err, sizeof(int), hipMemcpyDeviceToHost));
-  if (err) { P->loaded = false; return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16"); }
-  return SBN_OK;
-}
 extern "C" int sbn_prover_load_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi) {
   if (!P || !trace) return fail(SBN_ERR_BAD_ARG, "null argument");
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
-  (void)rc_finish(P);   // (a range check still writing the columns this call overwrites)
   size_t words = P->air.ncols * P->n;
   {  // canonical-form check on several host threads (the copy below is the PCIe-bound part)
     unsigned nt = std::thread::hardware_concurrency(); if (nt == 0) nt = 4; if (nt > 16) nt = 16;
@@ -911,7 +858,6 @@ extern "C" int sbn_prover_load_trace_device(sbn_prover* P, const uint64_t* d_tra
   if (!P || !d_trace) return fail(SBN_ERR_BAD_ARG, "null argument");
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
   HIPC(hipSetDevice(P->device));
-  (void)rc_finish(P);
   if (d_trace != P->d_trace) HIPC(hipMemcpy(P->d_trace, d_trace, P->air.ncols * P->n * sizeof(u64), hipMemcpyDeviceToDevice));
   P->loaded = true;
   return SBN_OK;
@@ -1060,20 +1006,16 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
   auto blocks = [](size_t k, unsigned b) { return dim3((unsigned)((k + b - 1) / b)); };
   mark();
-  const int skip = P->gen_calls++ ? P->set.tracegen_skip : 0;   // measurement only (settings.hpp): the first call of a prover always writes the whole trace
-  if (!(skip & 1)) {
   hipLaunchKernelGGL(tg::flags_kernel, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
   hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
   hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, (u64)65535, P->d_trace);
   hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
-  }
   mark();
   // the two 256-step curve chains per instance: host threads while the device writes the input-independent columns
   // chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx picks by the host pool's size): 2 = one wave per instance walking levels of
   // independent Fq operations (tg::chain_coop_kernel), 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host threads +
   // pinned upload
-  if (skip & 2) {
-  } else if (P->chain_mode == 2) {
+  if (P->chain_mode == 2) {
     static const ChainProgram prog = build_chain_program(E);
     if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
     tg::ChainProgDev cp{};
@@ -1099,25 +1041,14 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
     HIPC(hipMemcpyAsync(jb, P->h_chain + cw, cw * sizeof(u64), hipMemcpyHostToDevice, st));
   }
   mark();
-  if (!(skip & 2))
   hipLaunchKernelGGL(tg::affine_lambda_kernel<E>, blocks((n + tg::TG_ROWS - 1) / tg::TG_ROWS, 64), dim3(64), 0, st, d_ios, K, ja, jb, n, sv, row_op, d_out, d_err);
   mark();
-  if (!(skip & 4))
   hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, sh.gadget_col, P->d_trace, d_err);
   mark();
-  if (skip & 8) {
-  } else if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
+  if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
     HIPC(hipMemsetAsync(d_cnt, 0, (size_t)sh.num_rc * 65536 * sizeof(unsigned int), st));
     hipLaunchKernelGGL(tg::range_count_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, d_cnt, d_err);
     hipLaunchKernelGGL(tg::range_check_kernel<true>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
-  } else if (P->set.range_async && !timing && P->rstream) {
-    // behind this call: on its own stream after the rows are written; the trace commitment joins it (commit_pipeline), prove() reads its verdict
-    HIPC(hipEventRecord(P->rows_done, st));
-    HIPC(hipStreamWaitEvent(P->rstream, P->rows_done, 0));
-    HIPC(hipMemsetAsync(P->d_rc_err, 0, sizeof(int), P->rstream));
-    hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, P->rstream, P->d_trace, n, sh.rc_start, sh.start_lookups, P->d_rc_err, (const unsigned int*)nullptr, P->set.range_check);
-    HIPC(hipEventRecord(P->rc_done, P->rstream));
-    P->rc_pending = true; P->rc_first_col = sh.start_lookups;
   } else {
     hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, (const unsigned int*)nullptr, P->set.range_check);
   }
@@ -1329,7 +1260,6 @@ extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, siz
   if (!is_exp_air(P->air.kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
   if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
   if (P->n != exp_rows_per_instance(P->air.kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  (void)rc_finish(P);   // (the range check of an earlier call that no proof consumed)
   if (P->air.kind == SBN_AIR_FQ12_EXP || P->air.kind == SBN_AIR_FQ12_EXP_U64) return generate_trace_device_fq12(P, ios, num_io, pi_out);
   if (P->n < 65536 || P->n > 262144) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
   if (P->air.kind == SBN_AIR_FQ_EXP) return generate_trace_device_fq(P, ios, num_io, pi_out);
@@ -1340,14 +1270,12 @@ extern "C" int sbn_prover_read_trace(sbn_prover* P, uint64_t* out) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (!P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
   HIPC(hipSetDevice(P->device));
-  { const int rc = rc_finish(P); if (rc) return rc; }
   HIPC(hipMemcpy(out, P->d_trace, P->air.ncols * P->n * sizeof(u64), hipMemcpyDeviceToHost));
   return SBN_OK;
 }
 extern "C" uint64_t* sbn_prover_trace_device_ptr(sbn_prover* P) {
   if (!P) return nullptr;
   (void)hipSetDevice(P->device);
-  (void)rc_finish(P);   // the caller reads or writes the buffer next
   return P->d_trace;
 }
 
@@ -1365,12 +1293,9 @@ template <int KIND>
 static void launch_quotient_kind(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
   const dim3 g1((unsigned)qblocks, 1), g2((unsigned)qblocks, 2);
   if (qp.seg_mask & 12u) hipLaunchKernelGGL((quotient_kernel<KIND, 2>), g2, dim3(256), 0, P->hstream, qp, qp.apow[0], qp.apow[1], qp.pic);
-  // SBN_QUOTIENT_TAIL (A/B): 1 = the tail segment behind the permutation checks on the second stream instead of behind the head;
-  // 2 = the tail IN FRONT of the head on the main stream (it then walks the lookup columns at the same time as the permutation checks)
-  const int tail_mode = P->set.quotient_tail;
-  if (tail_mode == 2 && (qp.seg_mask & 2u)) hipLaunchKernelGGL((quotient_kernel<KIND, 1>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
+  const auto tail = quotient_kernel<KIND, 1>;   // (named before PART 0: the order of first use is the kernels' order in the code object)
   if (qp.seg_mask & 1u) hipLaunchKernelGGL((quotient_kernel<KIND, 0>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
-  if (tail_mode != 2 && (qp.seg_mask & 2u)) hipLaunchKernelGGL((quotient_kernel<KIND, 1>), g1, dim3(256), 0, tail_mode == 1 ? P->hstream : P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
+  if (qp.seg_mask & 2u) hipLaunchKernelGGL(tail, g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
 }
 static int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
   switch (P->air.kind) {
@@ -1420,12 +1345,10 @@ extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) {
   if (!P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
   if (S) {
     S->tev_used = 0;
-    if (P->rc_pending) HIPC(hipStreamWaitEvent(st, P->rc_done, 0));
     if ((rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t))) return rc;
   } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES))) return rc;
   HIPC(hipEventRecord(P->ev[ST_PERM_Z], st));
   if ((rc = S ? split_cap_to_host(P, P->tree_t, trace_cap) : tree_cap_to_host(P, P->tree_t, trace_cap))) return rc;
-  if ((rc = rc_finish(P))) return rc;   // (the commitment joined the asynchronous range check; its verdict)
   ch.observe_words(trace_cap.data(), capw);
 
   // P2 permutation argument -------------------------------------------------------------------------
@@ -1442,10 +1365,10 @@ extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) {
       if (cnt == 0) return;
       const PairCols* pp = pairs + z0; u64* out = P->d_zval + z0 * n;
       // from 2^13 rows up: chunk products, one wave per column for their prefix / suffix, then Z written once -- 5 words per row
-      // instead of 7 (kernels.cuh permz_chunk_*; the chunk products wait in the idle quotient scratch).  SBN_PERM_Z=1 (experiment
-      // switch): the one-workgroup-per-column kernel of rounds 1-3.
+      // instead of 7 (kernels.cuh permz_chunk_*; the chunk products wait in the idle quotient scratch).  Other shapes: the
+      // one-workgroup-per-column kernel of rounds 1-3.
       const size_t chunks = n / 2048;
-      if (n >= 8192 && n % 2048 == 0 && P->set.perm_z != 1 && cnt <= 65535 && cnt * chunks * 4 <= 2 * 32 * n) {
+      if (n >= 8192 && n % 2048 == 0 && cnt <= 65535 && cnt * chunks * 4 <= 2 * 32 * n) {
         u64* tot = P->d_part; u64* pq = P->d_part + cnt * chunks * 2;
         hipLaunchKernelGGL(permz_chunk_products_kernel<8>, dim3((unsigned)chunks, (unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0.v, gamma1.v, tot);
         hipLaunchKernelGGL(permz_chunk_scan_kernel, dim3((unsigned)cnt), dim3(64), 0, s, tot, (u32)chunks, pq);
@@ -1886,17 +1809,13 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
   HIPC(hipSetDevice(g_device));
   { int rc0 = ntt_fast_setup(); if (rc0) return rc0; }
   { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
-  P.fast_ntt = P.set.fast_ntt; P.ntt_xcd = P.set.ntt_xcd;
-  // the transform kernels the prover itself picks at this size (the fused middle passes), so that the parity test of this
-  // entry point covers them
-  P.ntt_fused = P.fast_ntt && (lg == 16 || lg == 17) && P.set.ntt_fused;
-  P.ntt_fused512 = P.fast_ntt && lg == 18 && P.set.ntt_split1024 && P.set.ntt_fused;
+  ntt_plan(&P);   // the transform kernels the prover picks at this size
   HIPC(hipStreamCreate(&P.stream));
   u64 *d_vals = nullptr, *d_coef = nullptr, *d_lde = nullptr;
   int rc = 0;
   rc |= dmalloc(&d_vals, ncols * n); rc |= dmalloc(&d_coef, ncols * n); rc |= dmalloc(&d_lde, ncols * P.m); rc |= dmalloc(&P.d_tmp, 64 * P.m);
   if (P.ntt_fused || P.ntt_fused512) rc |= dmalloc(&P.d_tmp2, 64 * P.m);
-  if (lg == 18 && P.set.ntt_split1024) rc |= dmalloc(&P.d_shift_odd, n);
+  if (P.ntt_fused512) rc |= dmalloc(&P.d_shift_odd, n);
   rc |= dmalloc(&P.d_tw_f, P.m); rc |= dmalloc(&P.d_tw_i, P.m); rc |= dmalloc(&P.d_shift, P.m);
   rc |= tree_alloc(P.tree_t, P.m, cap_height);
   if (!rc) {
@@ -1908,7 +1827,7 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
     if (P.d_shift_odd) hipLaunchKernelGGL(shift_odd_table_kernel, blocks(n), dim3(256), 0, P.stream, P.d_shift_odd, n, P.d_shift, P.d_tw_f, 9u);
     if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess) rc = fail(SBN_ERR_HIP, "H2D failed");
   }
-  for (size_t c0 = 0; !rc && c0 < ncols; c0 += P.ntt_chunk) rc = intt_then_lde_chunk(&P, d_vals, d_coef, d_lde, c0, std::min(P.ntt_chunk, ncols - c0));
+  for (size_t c0 = 0; !rc && c0 < ncols; c0 += P.ntt_chunk) rc = intt_lde_cols(&P, d_vals + c0 * n, d_coef + c0 * n, d_lde + c0 * P.m, std::min(P.ntt_chunk, ncols - c0));
   if (!rc && ncols <= 4) rc = tree_from_matrix(&P, P.tree_t, d_lde, ncols);
   if (!rc && ncols > 4) {  // same chunked sponge as the prover (chunks of 64 columns), on one stream
     rc = dmalloc(&P.d_sponge, 12 * P.m);
@@ -2035,11 +1954,11 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
   const char* chain = P->chain_mode == 0 && tracegen_host_chains_vectorized() ? "host_pool_ifma_x8" : CH[P->chain_mode < 0 || P->chain_mode > 2 ? 0 : P->chain_mode];
   char buf[1024];
   snprintf(buf, sizeof buf,
-           "abi=%d device=%d ntt_chunk=%zu fast_ntt=%d ntt_xcd=%d ntt_fused=%d ntt_sub=%zu ntt_streams=%d ntt_split1024=%d merkle_fuse=%d quotient_tail=%d "
-           "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d range_async=%d perm_z=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d ignored=[%s]",
-           SBN_ABI_VERSION, P->device, P->ntt_chunk, (int)P->fast_ntt, (int)P->ntt_xcd, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_sub, P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0,
-           (int)s.merkle_fuse, s.quotient_tail, chain, tracegen_host_threads(), (int)s.fq12_host_chain,
-           (int)s.fq12_row_kernel, s.range_check, (int)s.range_async, s.perm_z, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, s.ignored.c_str());
+           "abi=%d device=%d ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d "
+           "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d ignored=[%s]",
+           SBN_ABI_VERSION, P->device, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0,
+           chain, tracegen_host_threads(), (int)s.fq12_host_chain,
+           (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, s.ignored.c_str());
   snprintf(out, cap, "%s", buf);
   return SBN_OK;
 }
