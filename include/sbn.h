@@ -173,6 +173,15 @@ int sbn_prover_load_trace(sbn_prover* p, const uint64_t* trace_col_major, const 
 int sbn_prover_load_trace_device(sbn_prover* p, const uint64_t* d_trace_col_major, const uint64_t* public_inputs, size_t n_pi);
 /* prove() on the loaded trace; may be called repeatedly (the loaded trace is preserved). */
 int sbn_prover_prove(sbn_prover* p, sbn_proof** out);
+/* load + prove in one call: the trace crosses PCIe in the commit pipeline's own column chunks while earlier chunks are
+ * transformed and absorbed.  Same proof words as sbn_prover_load_trace followed by sbn_prover_prove.  On success the
+ * trace is resident as after load_trace (prove can be repeated, read_trace returns it).  On any failure NO trace is
+ * loaded.  The caller's matrix is only read (it may be a read-only mapping) and is not needed after the call returns; it
+ * is staged through at most 64 MiB of pinned host memory per prover, allocated on the first call.  The canonical-form
+ * check runs on the device, chunk by chunk behind the copies: a word >= p gives SBN_ERR_NON_CANONICAL naming the smallest
+ * such index, as load_trace does, after the trace commitment instead of in front of it.  Single-GPU provers only; the
+ * trace_commit stage time includes the upload. */
+int sbn_prover_prove_host_trace(sbn_prover* p, const uint64_t* trace_col_major, const uint64_t* public_inputs, size_t n_pi, sbn_proof** out);
 /* Per-stage device times (ms, HIP events on the prover's stream) of the last prove():
  * names via sbn_prover_stage_name(i); returns the number of stages written. */
 int sbn_prover_stage_times(const sbn_prover* p, float* ms_out, int cap);
@@ -204,9 +213,21 @@ int sbn_prover_generate_trace(sbn_prover* p, const uint32_t* ios, size_t num_io,
 int sbn_prover_read_trace(sbn_prover* p, uint64_t* trace_out);
 
 /* One-shot convenience with the reference's argument list:
- * prove(stark, &config, trace_poly_values, public_inputs) (src/curves/g1/exp.rs:818-825). */
+ * prove(stark, &config, trace_poly_values, public_inputs) (src/curves/g1/exp.rs:818-825): a device context, then
+ * sbn_prover_prove_host_trace.  The context is created and destroyed per call unless sbn_prove_cache_configure keeps it. */
 int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* trace_col_major, uint32_t degree_bits,
               const uint64_t* public_inputs, size_t n_pi, sbn_proof** out);
+
+/* sbn_prove keeps the device contexts it creates, keyed by (device, kind, num_io, degree_bits, every sbn_config field),
+ * up to budget_bytes of device memory, least recently used evicted first.  0 (the default) = create and destroy per
+ * call, as before; setting 0 also destroys what is cached.  Thread-safe.  A context is handed to one call at a time: a
+ * concurrent call for the same key works on a temporary context of its own.  A context larger than the whole budget is
+ * never kept, and neither is one whose call failed.  A cached context keeps the SBN_* switches it was created under (they
+ * are read when a context is created, see sbn_prover_describe); configure 0 and the budget again to have them read anew.
+ * Nothing is released at process exit: call this with 0 before unloading the library or resetting the device. */
+int sbn_prove_cache_configure(uint64_t budget_bytes);
+/* out[0..5] = hits, misses, evictions, contexts resident, bytes resident, budget. */
+int sbn_prove_cache_stats(uint64_t out[6]);
 
 /* Batch mode (BASELINE config "batch of independent proofs"): `inflight` prover contexts on the current GPU with one
  * host thread each.  Every unit is one instance list of the table (`num_io` instances, `ios_words_per_unit` u32 words,
@@ -315,6 +336,10 @@ int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* out, siz
  * the same functions (no device needed).  SBN_ERR_NON_CANONICAL for an input >= p, SBN_ERR_BAD_ARG for a zero to invert.
  * Parity tests only; host in/out. */
 int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device);
+/* Index of the first word >= p (the Goldilocks modulus) among words[0 .. count), or count when every word is canonical: the scan
+ * sbn_prover_prove_host_trace runs behind each chunk it uploads (csrc/kernels.cuh first_non_canonical_kernel), host in/out.
+ * on_device = 0 runs a host loop and needs no device. */
+int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out);
 /* The host permutation behind the Fiat-Shamir transcript of prove()/verify() (plonky2 Challenger's
  * PoseidonPermutation): sparse partial rounds, or the plain definition when use_definition != 0.  Host only. */
 int sbn_poseidon_permute_host(uint64_t* states, size_t count, int use_definition);

@@ -65,6 +65,10 @@ extern "C" {
     pub fn sbn_prover_load_trace(p: *mut sbn_prover, trace_col_major: *const u64, public_inputs: *const u64, n_pi: usize) -> i32;
     pub fn sbn_prover_generate_trace(p: *mut sbn_prover, ios: *const u32, num_io: usize, pi_out: *mut u64) -> i32;
     pub fn sbn_prover_prove(p: *mut sbn_prover, out: *mut *mut sbn_proof) -> i32;
+    pub fn sbn_prover_prove_host_trace(p: *mut sbn_prover, trace_col_major: *const u64, public_inputs: *const u64, n_pi: usize, out: *mut *mut sbn_proof) -> i32;
+    pub fn sbn_prove_cache_configure(budget_bytes: u64) -> i32;
+    pub fn sbn_prove_cache_stats(out: *mut u64) -> i32;
+    pub fn sbn_first_non_canonical(words: *const u64, count: usize, on_device: i32, index_out: *mut u64) -> i32;
     pub fn sbn_prover_stage_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
     pub fn sbn_prover_stage_name(i: i32) -> *const c_char;
     pub fn sbn_prover_describe(p: *const sbn_prover, out: *mut c_char, cap: usize) -> i32;

@@ -125,8 +125,15 @@ impl Prover {
         F: RichField + Extendable<D>,
         C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
     {
+        let (flat, pis) = self.flatten(trace, public_inputs)?;
+        check(unsafe { ffi::sbn_prover_load_trace(self.raw, flat.as_ptr(), pis.as_ptr(), pis.len()) }, "sbn_prover_load_trace")?;
+        self.finish::<F, C, D>()
+    }
+
+    /// The trace as the C ABI takes it (column-major, flat) and the public inputs, as canonical u64.  The library reads
+    /// num_columns * 2^degree_bits words and n_pi public inputs: the sizes are checked here, before the FFI call.
+    fn flatten<F: RichField>(&self, trace: Vec<PolynomialValues<F>>, public_inputs: &[F]) -> Result<(Vec<u64>, Vec<u64>)> {
         let n = trace.first().map(|c| c.len()).unwrap_or(0);
-        // sbn_prover_load_trace reads num_columns * 2^degree_bits words and n_pi public inputs: check before the FFI call
         ensure!(trace.len() == self.n_cols, "the table has {} columns, the trace {}", self.n_cols, trace.len());
         ensure!(n == 1usize << self.degree_bits, "the prover was created for 2^{} rows, the trace has {}", self.degree_bits, n);
         ensure!(public_inputs.len() == self.n_pi, "expected {} public inputs, got {}", self.n_pi, public_inputs.len());
@@ -135,10 +142,22 @@ impl Prover {
             ensure!(col.len() == n, "ragged trace");
             flat.extend(col.values.iter().map(|x| x.to_canonical_u64()));
         }
-        drop(trace);
-        let pis: Vec<u64> = public_inputs.iter().map(|x| x.to_canonical_u64()).collect();
-        check(unsafe { ffi::sbn_prover_load_trace(self.raw, flat.as_ptr(), pis.as_ptr(), pis.len()) }, "sbn_prover_load_trace")?;
-        self.finish::<F, C, D>()
+        Ok((flat, public_inputs.iter().map(|x| x.to_canonical_u64()).collect()))
+    }
+
+    /// The same call with the upload INSIDE the proof (sbn_prover_prove_host_trace): the flattened trace crosses PCIe in the
+    /// commit pipeline's column chunks while earlier chunks are transformed and hashed, and the canonical-form check runs on the
+    /// device.  Same proof as `prove`; afterwards the trace is resident on the device.  (Source only, like the rest of this
+    /// crate: no Rust toolchain where the library is built and tested.)
+    pub fn prove_host_trace<F, C, const D: usize>(&mut self, trace: Vec<PolynomialValues<F>>, public_inputs: &[F]) -> Result<StarkProofWithPublicInputs<F, C, D>>
+    where
+        F: RichField + Extendable<D>,
+        C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+    {
+        let (flat, pis) = self.flatten(trace, public_inputs)?;
+        let mut p = ptr::null_mut();
+        check(unsafe { ffi::sbn_prover_prove_host_trace(self.raw, flat.as_ptr(), pis.as_ptr(), pis.len(), &mut p) }, "sbn_prover_prove_host_trace")?;
+        Self::take_proof::<F, C, D>(p)
     }
 
     /// Witness generated on the device from the instance list (`G1ExpIONative` etc. flattened to u32 limbs as
@@ -163,6 +182,15 @@ impl Prover {
     {
         let mut p = ptr::null_mut();
         check(unsafe { ffi::sbn_prover_prove(self.raw, &mut p) }, "sbn_prover_prove")?;
+        Self::take_proof::<F, C, D>(p)
+    }
+
+    /// Converts and frees the library's proof object.
+    fn take_proof<F, C, const D: usize>(p: *mut ffi::sbn_proof) -> Result<StarkProofWithPublicInputs<F, C, D>>
+    where
+        F: RichField + Extendable<D>,
+        C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+    {
         let words = unsafe { std::slice::from_raw_parts(ffi::sbn_proof_words(p), ffi::sbn_proof_num_words(p)) };
         let proof = convert::proof_from_words::<F, C, D>(words);
         unsafe { ffi::sbn_proof_free(p) };
@@ -210,7 +238,7 @@ where
     ensure!(n.is_power_of_two(), "trace height must be a power of two");
     timing.push("sbn prove (MI355X)", log::Level::Debug);
     let mut prover = Prover::new(&stark, config, n.trailing_zeros() as usize)?;
-    let proof = prover.prove::<F, C, D>(trace_poly_values, &public_inputs);
+    let proof = prover.prove_host_trace::<F, C, D>(trace_poly_values, &public_inputs);   // the upload inside the trace commitment
     for (name, ms) in prover.stage_times() {
         log::debug!("sbn stage {name}: {ms:.3} ms");
     }

@@ -32,10 +32,10 @@ EXPORTS = [
     "sbn_generate_trace_g1_exp", "sbn_generate_trace_g2_exp", "sbn_generate_trace_fq12_exp", "sbn_generate_trace_fq_exp", "sbn_generate_trace_fq12_exp_u64",
     "sbn_generate_trace_g1_op", "sbn_generate_trace_modular", "sbn_generate_trace_fq12_mul", "sbn_generate_trace_lookup", "sbn_generate_trace_flags", "sbn_generate_trace_flags_u64",
     "sbn_prover_create", "sbn_prover_destroy", "sbn_prover_load_trace", "sbn_prover_load_trace_device",
-    "sbn_prover_prove", "sbn_prover_stage_times", "sbn_prover_stage_name", "sbn_prover_describe", "sbn_settings_check", "sbn_prover_trace_device_ptr",
+    "sbn_prover_prove", "sbn_prover_prove_host_trace", "sbn_prover_stage_times", "sbn_prover_stage_name", "sbn_prover_describe", "sbn_settings_check", "sbn_prover_trace_device_ptr",
     "sbn_prover_generate_trace", "sbn_prover_read_trace",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
-    "sbn_prove", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
+    "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
     "sbn_split_prover_load_trace", "sbn_split_prover_prove", "sbn_split_prover_stage_times",
@@ -103,6 +103,10 @@ def lib():
         L.sbn_prover_load_trace.argtypes = [vp, vp, vp, sz]
         L.sbn_prover_load_trace_device.argtypes = [vp, vp, vp, sz]
         L.sbn_prover_prove.argtypes = [vp, C.POINTER(vp)]
+        L.sbn_prover_prove_host_trace.argtypes = [vp, vp, vp, sz, C.POINTER(vp)]
+        L.sbn_prove_cache_configure.argtypes = [C.c_uint64]
+        L.sbn_prove_cache_stats.argtypes = [vp]
+        L.sbn_first_non_canonical.argtypes = [vp, sz, C.c_int, vp]
         L.sbn_prover_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
         L.sbn_prover_trace_device_ptr.restype = vp
         L.sbn_prover_trace_device_ptr.argtypes = [vp]
@@ -508,6 +512,18 @@ class Prover:
         _check(lib().sbn_prover_prove(self._h, C.byref(h)))
         return _take_proof(h)
 
+    def prove_host_trace(self, trace, public_inputs):
+        """load_trace + prove in one call: the host trace crosses PCIe inside the trace commitment, chunk by chunk, and is checked for
+        canonical form on the device.  Same proof; afterwards the trace is resident (prove() can be repeated).  A refused call
+        leaves no trace loaded."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if trace.shape != (self.stark.num_columns, 1 << self.degree_bits):
+            raise SbnError(-1, "trace shape does not match the prover")
+        h = C.c_void_p()
+        _check(lib().sbn_prover_prove_host_trace(self._h, _ptr(trace), _ptr(pi), len(pi), C.byref(h)))
+        return _take_proof(h)
+
     def stage_times(self):
         buf = (C.c_float * 32)()
         k = lib().sbn_prover_stage_times(self._h, buf, 32)
@@ -573,6 +589,29 @@ def prove(stark, config, trace_poly_values, public_inputs, timing=None):
     h = C.c_void_p()
     _check(lib().sbn_prove(C.byref(stark._d), C.byref(config._c), _ptr(trace), n.bit_length() - 1, _ptr(pi), len(pi), C.byref(h)))
     return _take_proof(h)
+
+
+def prove_cache_configure(budget_bytes):
+    """Let prove() keep its device contexts, up to budget_bytes of device memory (least recently used evicted first); 0 (the
+    default) creates and destroys one per call and releases what is cached."""
+    _check(lib().sbn_prove_cache_configure(int(budget_bytes)))
+
+
+def prove_cache_stats():
+    out = (C.c_uint64 * 6)()
+    _check(lib().sbn_prove_cache_stats(out))
+    return dict(zip(("hits", "misses", "evictions", "contexts_resident", "bytes_resident", "budget"), (int(v) for v in out)))
+
+
+def first_non_canonical(words, on_device=True):
+    """Index of the first word >= p of a uint64 array, or len(words): the scan of Prover.prove_host_trace (test hook).
+    on_device=False runs a host loop and needs no device."""
+    w = np.asarray(words)
+    if w.dtype != np.uint64 or w.ndim != 1 or not w.flags.c_contiguous:
+        w = np.ascontiguousarray(w, dtype=np.uint64).reshape(-1)
+    out = C.c_uint64(0)
+    _check(lib().sbn_first_non_canonical(_ptr(w), len(w), 1 if on_device else 0, C.byref(out)))
+    return int(out.value)
 
 
 def verify_stark_proof(stark, proof, config):

@@ -8,7 +8,88 @@
 
 using namespace sbn;
 
+// ---- the context cache of the one-shot call (include/sbn.h sbn_prove_cache_configure) ---------------------------------
+// Idle contexts only: a context leaves the list while a call works on it, so two threads never share one, and a thread that
+// finds its key busy creates a temporary context instead of waiting.  bytes = the idle contexts' device memory <= budget at
+// every return; what does not fit when it comes back is destroyed.  The list lives on the heap and is never destroyed by a
+// static destructor (the HIP runtime may be gone by then): sbn_prove_cache_configure(0) releases the contexts.
+namespace {
+struct CacheKey {
+  int device; int32_t kind; uint32_t num_io, degree_bits; sbn_config cfg;
+  bool operator==(const CacheKey& o) const {
+    return device == o.device && kind == o.kind && num_io == o.num_io && degree_bits == o.degree_bits && cfg.security_bits == o.cfg.security_bits &&
+           cfg.num_challenges == o.cfg.num_challenges && cfg.rate_bits == o.cfg.rate_bits && cfg.cap_height == o.cfg.cap_height &&
+           cfg.proof_of_work_bits == o.cfg.proof_of_work_bits && cfg.fri_arity_bits == o.cfg.fri_arity_bits &&
+           cfg.fri_final_poly_bits == o.cfg.fri_final_poly_bits && cfg.num_query_rounds == o.cfg.num_query_rounds && cfg.fri_variant == o.cfg.fri_variant;
+  }
+};
+struct CacheEntry { CacheKey key; sbn_prover* P; uint64_t bytes; };
+struct ProveCache {
+  std::mutex m;
+  std::vector<CacheEntry> idle;   // least recently used first
+  uint64_t budget = 0, bytes = 0, hits = 0, misses = 0, evictions = 0;
+};
+ProveCache& prove_cache() { static ProveCache* c = new ProveCache(); return *c; }
+
+// an idle context of this key, or null (counted as a miss: the caller creates one)
+sbn_prover* cache_take(const CacheKey& key) {
+  ProveCache& c = prove_cache();
+  std::lock_guard<std::mutex> g(c.m);
+  if (c.budget == 0) return nullptr;   // the cache is off: nothing is counted
+  for (size_t i = 0; i < c.idle.size(); i++)
+    if (c.idle[i].key == key) {
+      sbn_prover* P = c.idle[i].P;
+      c.bytes -= c.idle[i].bytes;
+      c.idle.erase(c.idle.begin() + (long)i);
+      c.hits++;
+      return P;
+    }
+  c.misses++;
+  return nullptr;
+}
+// after a successful call: keep the context if the budget allows (evicting the least recently used), else destroy it
+void cache_give(const CacheKey& key, sbn_prover* P) {
+  ProveCache& c = prove_cache();
+  const uint64_t bytes = prover_device_bytes(P);
+  std::vector<sbn_prover*> drop;
+  {
+    std::lock_guard<std::mutex> g(c.m);
+    if (bytes > c.budget) drop.push_back(P);   // (the cache is off, or the context alone exceeds the budget)
+    else {
+      while (c.bytes + bytes > c.budget) {
+        drop.push_back(c.idle.front().P); c.bytes -= c.idle.front().bytes; c.idle.erase(c.idle.begin()); c.evictions++;
+      }
+      c.idle.push_back(CacheEntry{key, P, bytes});
+      c.bytes += bytes;
+    }
+  }
+  for (sbn_prover* q : drop) sbn_prover_destroy(q);   // outside the lock: freeing 6.5 GB takes milliseconds
+}
+}  // namespace
+
 extern "C" {
+
+int sbn_prove_cache_configure(uint64_t budget_bytes) {
+  ProveCache& c = prove_cache();
+  std::vector<sbn_prover*> drop;
+  {
+    std::lock_guard<std::mutex> g(c.m);
+    c.budget = budget_bytes;
+    while (!c.idle.empty() && (budget_bytes == 0 || c.bytes > budget_bytes)) {
+      drop.push_back(c.idle.front().P); c.bytes -= c.idle.front().bytes; c.idle.erase(c.idle.begin());
+      if (budget_bytes) c.evictions++;
+    }
+  }
+  for (sbn_prover* q : drop) sbn_prover_destroy(q);
+  return SBN_OK;
+}
+int sbn_prove_cache_stats(uint64_t out[6]) {
+  if (!out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  ProveCache& c = prove_cache();
+  std::lock_guard<std::mutex> g(c.m);
+  out[0] = c.hits; out[1] = c.misses; out[2] = c.evictions; out[3] = c.idle.size(); out[4] = c.bytes; out[5] = c.budget;
+  return SBN_OK;
+}
 
 const char* sbn_version(void) { return "starky-bn254-amd 0.3 (gfx950)"; }
 int sbn_abi_version(void) { return SBN_ABI_VERSION; }
@@ -43,12 +124,21 @@ int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* tr
               sbn_proof** out) {
   if (!out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
-  sbn_prover* P = nullptr;
-  int rc = sbn_prover_create(air, cfg, degree_bits, &P);
-  if (rc) return rc;
-  rc = sbn_prover_load_trace(P, trace, pi, n_pi);
-  if (!rc) rc = sbn_prover_prove(P, out);
-  sbn_prover_destroy(P);
+  CacheKey key{};
+  const bool keyed = air && cfg;   // (null arguments: sbn_prover_create reports them)
+  if (keyed) { key.device = current_device(); key.kind = air->kind; key.num_io = air->num_io; key.degree_bits = degree_bits; key.cfg = *cfg; }
+  sbn_prover* P = keyed ? cache_take(key) : nullptr;
+  int rc = 0;
+  if (!P && (rc = sbn_prover_create(air, cfg, degree_bits, &P))) return rc;
+  if (!trace) rc = fail(SBN_ERR_BAD_ARG, "null argument");
+  else rc = sbn_prover_prove_host_trace(P, trace, pi, n_pi, out);
+  if (rc) {   // a context whose call failed is not kept (destroy leaves the message of the failure in place)
+    const std::string msg = g_last_error;
+    sbn_prover_destroy(P);
+    g_last_error = msg;
+    return rc;
+  }
+  cache_give(key, P);
   return rc;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
 
 namespace sbn {
 
@@ -116,8 +117,12 @@ int tracegen_host_chains_fq12(const uint32_t* ios, size_t iow, int steps, size_t
 int tracegen_host_chains_fq(const uint32_t* ios, size_t K, u64* ca, u64* cb);
 // tracegen.hip: threads of the host worker pool (the caller's included): SBN_HOST_THREADS, else one per visible CPU (<= 64)
 unsigned tracegen_host_threads();
+// tracegen.hip: f(0) .. f(n - 1) on that pool (the caller's thread takes part; a call from inside a pool task runs serially)
+void host_parallel_for(size_t n, const std::function<void(size_t)>& f);
 // tracegen.hip: the curve chains run eight instances per AVX-512 IFMA register on this CPU (0.15 ms per group of eight)
 bool tracegen_host_chains_vectorized();
+// prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)
+size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)
 int current_device();
 

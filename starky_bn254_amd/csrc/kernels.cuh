@@ -939,3 +939,30 @@ __global__ void gather_fri_leaf_kernel(const u64* va, const u64* vb, u32 log_m, 
   u32 nat = bitrev32((u32)(leaf * arity + (e >> 1)), log_m);
   out[(size_t)q * qstride + off + e] = (e & 1) ? vb[nat] : va[nat];
 }
+
+// Canonical-form scan of a host trace on its way in (prover.hip prove_host_trace; sbn_first_non_canonical): *first_bad =
+// min(*first_bad, base + i) over the words w[i] >= p.  Bandwidth-bound: 16-byte loads, grid-stride; a wave whose lanes all saw
+// canonical words issues no atomic (wave vote), any other wave issues one, after a min over its lanes.  `w` may sit 8 bytes
+// off a 16-byte boundary: lane 0 of the grid takes the word in front of the first whole vector and the one behind the last.
+typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));   // (a load of this type stays ONE global_load_dwordx4)
+__global__ __launch_bounds__(256) void first_non_canonical_kernel(const u64* __restrict__ w, size_t count, u64 base, unsigned long long* first_bad) {
+  const size_t head = (((size_t)w & 8) && count) ? 1 : 0;
+  const u64x2_t* __restrict__ v = reinterpret_cast<const u64x2_t*>(w + head);
+  const size_t nvec = (count - head) >> 1;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  u64 bad = ~(u64)0;
+#pragma unroll 4
+  for (size_t i = tid; i < nvec; i += stride) {
+    const u64x2_t x = v[i];
+    const bool b0 = x.x >= GLP, b1 = x.y >= GLP;
+    if (b0 | b1) { const u64 j = head + 2 * i + (b0 ? 0 : 1); bad = bad < j ? bad : j; }
+  }
+  if (tid == 0) {
+    const size_t last = head + 2 * nvec;   // < count iff one word is left behind the vectors
+    if (last < count && w[last] >= GLP) bad = bad < last ? bad : last;
+    if (head && w[0] >= GLP) bad = 0;
+  }
+  if (!__any(bad != ~(u64)0)) return;
+  for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor((unsigned long long)bad, d, 64); bad = o < bad ? o : bad; }
+  if ((threadIdx.x & 63) == 0) atomicMin(first_bad, (unsigned long long)(base + bad));
+}

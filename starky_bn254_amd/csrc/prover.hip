@@ -12,6 +12,7 @@
 #include <thread>
 #include <atomic>
 #include <chrono>
+#include <functional>
 
 using namespace sbn;
 
@@ -47,6 +48,10 @@ static const char* STAGE_NAMES[ST_COUNT + EX_COUNT] = {
   "trace_absorb_kernels_ms", "trace_absorb_launches", "z_absorb_kernels_ms", "z_absorb_launches", "device_tracegen_ms",
   "split_exchange_ms"};
 static constexpr int MAX_CHUNKS = 512;
+// prove_host_trace: the pinned staging ring of one prover, 4 slots of 16 MiB = 64 MiB of pinned host memory at most, allocated on
+// the first call.  A piece of the trace never spans two column chunks; a chunk larger than a slot crosses in several pieces.
+static constexpr int UPLOAD_SLOTS = 4;
+static constexpr size_t UPLOAD_SLOT_WORDS = (size_t)2 << 20;
 
 struct DevTree {  // Merkle digests, levels concatenated (leaf level first)
   u64* d = nullptr; size_t nleaf = 0; u32 nlevels = 0;  // nlevels = number of levels BELOW the cap
@@ -145,10 +150,21 @@ struct sbn_prover {
   size_t h_io_words = 0;
   u64* h_open = nullptr;                     // pinned landing buffer of the opened values [(ncols + nzs + 4)][4]
   u64* h_open2 = nullptr;                    // second landing buffer: the values at g*zeta of the trace and Z columns (the host is still reading the first)
+  size_t dev_bytes = 0;                      // device memory this context allocated (what the one-shot cache of capi.hip counts)
+  // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
+  hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk
+  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned
+  hipEvent_t slot_copied[UPLOAD_SLOTS];      // copy stream: the copy out of ring slot s has completed
+  bool slot_used[UPLOAD_SLOTS] = {};
+  unsigned slot_next = 0;
+  u64* h_ring = nullptr;                     // [UPLOAD_SLOTS][UPLOAD_SLOT_WORDS], pinned
+  unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
+  unsigned long long* h_first_bad = nullptr; // its pinned landing word
 };
 
-static int dmalloc(u64** p, size_t words) {
+static int dmalloc(u64** p, size_t words, size_t* bytes = nullptr) {   // bytes: the context's running total (sbn_prover::dev_bytes)
   HIPC(hipMalloc((void**)p, words * sizeof(u64)));
+  if (bytes) *bytes += words * sizeof(u64);
   return 0;
 }
 
@@ -291,11 +307,11 @@ static int intt_lde_cols(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, siz
   return ntt_columns(P, cf, P->n, lde_out, P->m, P->d_tmp, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1);
 }
 
-static int tree_alloc(DevTree& t, size_t nleaf, u32 cap_height) {
+static int tree_alloc(DevTree& t, size_t nleaf, u32 cap_height, size_t* bytes = nullptr) {
   t.nleaf = nleaf;
   u32 lg = 0; while (((size_t)1 << lg) < nleaf) lg++;
   t.nlevels = lg - cap_height;
-  return dmalloc(&t.d, 2 * nleaf * 4);
+  return dmalloc(&t.d, 2 * nleaf * 4, bytes);
 }
 static int tree_build_inner(sbn_prover* P, DevTree& t, hipStream_t st) {
   // One permutation costs 39 us on a lane and 16 us on 16 lanes, and a single wave saturates its SIMD.  So: levels with
@@ -336,13 +352,62 @@ static int tree_from_matrix(sbn_prover* P, DevTree& t, const u64* lde, size_t nc
   hipLaunchKernelGGL(leaf_hash_kernel, dim3((unsigned)((P->m + 255) / 256)), dim3(256), 0, P->stream, lde, P->m, P->lde_log, (u32)ncols, t.d);
   return tree_build_inner(P, t, P->stream);
 }
+// ---- prove_host_trace: the upload side ------------------------------------------------------------------------------
+// The trace of sbn_prover_prove_host_trace crosses PCIe in the commit pipeline's own column chunks: host threads copy a piece of
+// the caller's (pageable, possibly read-only) matrix into a pinned ring slot, a hipMemcpyAsync on the copy stream moves it to its
+// place in d_trace, and after the last piece of chunk k the copy stream scans the chunk for words >= p and records
+// upload_done[k].  A slot is refilled only once the event of its previous copy has completed, so the host runs at most
+// UPLOAD_SLOTS pieces ahead of the copy engine.
+struct HostUpload { const u64* src; hipEvent_t* done; };   // the caller's trace; done[k]: chunk k is resident and scanned
+static int upload_setup(sbn_prover* P) {   // idempotent: a call that failed half way is completed by the next one
+  if (!P->ustream) HIPC(hipStreamCreate(&P->ustream));
+  for (auto& e : P->upload_done) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : P->slot_copied) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!P->h_ring) HIPC(hipHostMalloc((void**)&P->h_ring, UPLOAD_SLOTS * UPLOAD_SLOT_WORDS * sizeof(u64), hipHostMallocDefault));
+  if (!P->h_first_bad) HIPC(hipHostMalloc((void**)&P->h_first_bad, sizeof(unsigned long long), hipHostMallocDefault));
+  if (!P->d_first_bad) { HIPC(hipMalloc((void**)&P->d_first_bad, sizeof(unsigned long long))); P->dev_bytes += sizeof(unsigned long long); }
+  return 0;
+}
+static void launch_first_non_canonical(const u64* d_words, size_t count, u64 base, unsigned long long* d_first_bad, hipStream_t st) {
+  const size_t blocks = std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048);   // grid-stride beyond 8 waves per CU
+  hipLaunchKernelGGL(first_non_canonical_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_words, count, base, d_first_bad);
+}
+static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0, size_t nc) {
+  const size_t w0 = c0 * P->n, w1 = w0 + nc * P->n;
+  const size_t threads = std::min<size_t>(tracegen_host_threads(), 16);
+  for (size_t a = w0; a < w1; a += UPLOAD_SLOT_WORDS) {
+    const size_t len = std::min(UPLOAD_SLOT_WORDS, w1 - a);
+    const unsigned s = P->slot_next; P->slot_next = (s + 1) % UPLOAD_SLOTS;
+    if (P->slot_used[s]) HIPC(hipEventSynchronize(P->slot_copied[s]));
+    u64* slot = P->h_ring + (size_t)s * UPLOAD_SLOT_WORDS;
+    const u64* from = up.src + a;
+    const size_t parts = std::max<size_t>(1, std::min(threads, len >> 15)), per = (len + parts - 1) / parts;   // >= 256 KiB per thread
+    host_parallel_for(parts, [&](size_t t) { const size_t b0 = t * per, b1 = std::min(len, b0 + per); if (b0 < b1) memcpy(slot + b0, from + b0, (b1 - b0) * sizeof(u64)); });
+    HIPC(hipMemcpyAsync(P->d_trace + a, slot, len * sizeof(u64), hipMemcpyHostToDevice, P->ustream));
+    HIPC(hipEventRecord(P->slot_copied[s], P->ustream));
+    P->slot_used[s] = true;
+  }
+  launch_first_non_canonical(P->d_trace + w0, w1 - w0, (u64)w0, P->d_first_bad, P->ustream);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(up.done[k], P->ustream));
+  return 0;
+}
+
 // PolynomialBatch::from_values for a wide matrix: per column chunk iNTT + coset LDE on the main stream,
 // sponge absorption of that chunk on the hash stream, then the Merkle levels; main waits at the end.
-static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t ncols, DevTree& t, int ex_ms, int ex_launches) {
+// up (prove_host_trace only; null: nothing below is enqueued that was not before): `vals` is still on the host.  Chunk k is sent
+// on its way right before its transforms are enqueued, and the main stream -- which runs the first transform pass of a chunk in
+// all three branches below (fused two-stream, plain two-stream, one stream) -- waits for upload_done[k] first.
+static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t ncols, DevTree& t, int ex_ms, int ex_launches, const HostUpload* up = nullptr) {
   size_t ch = P->ntt_chunk;
   size_t nchunks = (ncols + ch - 1) / ch;
   if (nchunks > (size_t)MAX_CHUNKS) return fail(SBN_ERR_UNSUPPORTED, "too many column chunks");
   if (ncols <= 4) {   // hash_or_noop: a leaf of at most 4 elements is its own digest (MyStark's 4 columns and its 2 Z columns)
+    if (up) {   // the whole matrix as one upload
+      int rc = upload_chunk(P, *up, 0, 0, ncols);
+      if (rc) return rc;
+      HIPC(hipStreamWaitEvent(P->stream, up->done[0], 0));
+    }
     int rc = intt_then_lde(P, vals, coef, lde, ncols);
     if (rc) return rc;
     P->stage_ms[ST_COUNT + ex_launches] = 0;
@@ -356,6 +421,10 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
   for (size_t k = 0; k < nchunks; k++) {
     size_t c0 = k * ch, nc = std::min(ch, ncols - c0);
     int rc;
+    if (up) {
+      if ((rc = upload_chunk(P, *up, k, c0, nc))) return rc;
+      HIPC(hipStreamWaitEvent(P->stream, up->done[k], 0));
+    }
     if (P->ntt_two_streams && (P->ntt_fused || P->ntt_fused512) && P->d_tmp3) {
       // the fused kernel of chunk k writes buffer k & 1, which the LDE pass B of chunk k - 2 (second stream) must have left
       if (k >= 2) HIPC(hipStreamWaitEvent(P->stream, P->chunk_ready[k - 2], 0));
@@ -559,10 +628,12 @@ static int absorb_times(sbn_prover* P, size_t ncols, int ex_ms) {
   P->stage_ms[ST_COUNT + ex_ms] = tot;
   return 0;
 }
-static int tree_cap_to_host(sbn_prover* P, const DevTree& t, std::vector<u64>& cap) {
+// first_bad (prove_host_trace): the word the upload's scans folded rides back behind the cap, under the same wait
+static int tree_cap_to_host(sbn_prover* P, const DevTree& t, std::vector<u64>& cap, bool first_bad = false) {
   size_t capn = (size_t)1 << P->cfg.cap_height;
   cap.resize(capn * 4);
   HIPC(hipMemcpyAsync(cap.data(), t.level(t.nlevels), capn * 4 * sizeof(u64), hipMemcpyDeviceToHost, P->stream));
+  if (first_bad) HIPC(hipMemcpyAsync(P->h_first_bad, P->d_first_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, P->stream));
   HIPC(stream_wait(P->stream));
   return 0;
 }
@@ -699,43 +770,43 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
     if (S->planes == 2) { S->zlde_n = rbuf; rbuf += Z * S->ml; }
     S->scratch = rbuf; S->scratch_words = sw;
     P->lde_scratch_words = (size_t)(rb / sizeof(u64));   // witness generation runs before the first exchange
-    acc(dmalloc(&P->d_trace, C * n)); acc(dmalloc(&P->d_coef, std::max<size_t>(S->cr, 1) * n));
-    acc(dmalloc(&P->d_zval, std::max<size_t>(S->zr, 1) * n)); acc(dmalloc(&P->d_zcoef, std::max<size_t>(S->zr, 1) * n));
-    acc(dmalloc(&S->d_ldechunk, P->ntt_chunk * m));
-    hipc(hipMalloc((void**)&S->d_idx_local, cfg->num_query_rounds * sizeof(u32)), "hipMalloc");
-    acc(tree_alloc(P->tree_t, S->ml, cfg->cap_height - lr)); acc(tree_alloc(P->tree_z, S->ml, cfg->cap_height - lr));
+    acc(dmalloc(&P->d_trace, C * n, &P->dev_bytes)); acc(dmalloc(&P->d_coef, std::max<size_t>(S->cr, 1) * n, &P->dev_bytes));
+    acc(dmalloc(&P->d_zval, std::max<size_t>(S->zr, 1) * n, &P->dev_bytes)); acc(dmalloc(&P->d_zcoef, std::max<size_t>(S->zr, 1) * n, &P->dev_bytes));
+    acc(dmalloc(&S->d_ldechunk, P->ntt_chunk * m, &P->dev_bytes));
+    hipc(hipMalloc((void**)&S->d_idx_local, cfg->num_query_rounds * sizeof(u32)), "hipMalloc"); P->dev_bytes += cfg->num_query_rounds * sizeof(u32);
+    acc(tree_alloc(P->tree_t, S->ml, cfg->cap_height - lr, &P->dev_bytes)); acc(tree_alloc(P->tree_z, S->ml, cfg->cap_height - lr, &P->dev_bytes));
   } else {
     P->lde_scratch_words = C * m;
-    acc(dmalloc(&P->d_trace, C * n)); acc(dmalloc(&P->d_coef, C * n)); acc(dmalloc(&P->d_lde, C * m));
-    acc(dmalloc(&P->d_zval, std::max<size_t>(Z, 1) * n)); acc(dmalloc(&P->d_zcoef, std::max<size_t>(Z, 1) * n)); acc(dmalloc(&P->d_zlde, std::max<size_t>(Z, 1) * m));
-    acc(tree_alloc(P->tree_t, m, cfg->cap_height)); acc(tree_alloc(P->tree_z, m, cfg->cap_height));
+    acc(dmalloc(&P->d_trace, C * n, &P->dev_bytes)); acc(dmalloc(&P->d_coef, C * n, &P->dev_bytes)); acc(dmalloc(&P->d_lde, C * m, &P->dev_bytes));
+    acc(dmalloc(&P->d_zval, std::max<size_t>(Z, 1) * n, &P->dev_bytes)); acc(dmalloc(&P->d_zcoef, std::max<size_t>(Z, 1) * n, &P->dev_bytes)); acc(dmalloc(&P->d_zlde, std::max<size_t>(Z, 1) * m, &P->dev_bytes));
+    acc(tree_alloc(P->tree_t, m, cfg->cap_height, &P->dev_bytes)); acc(tree_alloc(P->tree_z, m, cfg->cap_height, &P->dev_bytes));
   }
-  acc(dmalloc(&P->d_tmp, std::max(P->ntt_chunk, (size_t)4) * m));
-  if (P->ntt_fused || P->ntt_fused512 || P->ntt_two_streams) acc(dmalloc(&P->d_tmp2, std::max(P->ntt_chunk, (size_t)4) * m));
-  if ((P->ntt_fused || P->ntt_fused512) && P->ntt_two_streams) acc(dmalloc(&P->d_tmp3, std::max(P->ntt_chunk, (size_t)4) * m));
-  acc(dmalloc(&P->d_q, 2 * m)); acc(dmalloc(&P->d_qlde, 4 * m));
-  acc(tree_alloc(P->tree_q, m, cfg->cap_height));
-  acc(dmalloc(&P->d_tw_f, m)); acc(dmalloc(&P->d_tw_i, m)); acc(dmalloc(&P->d_shift, m)); acc(dmalloc(&P->d_shift_inv, m));
-  if (P->ntt_fused512) acc(dmalloc(&P->d_shift_odd, n));   // (ntt_plan)
-  acc(dmalloc(&P->d_xs, m)); acc(dmalloc(&P->d_lag_first, m)); acc(dmalloc(&P->d_lag_last, m));
+  acc(dmalloc(&P->d_tmp, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
+  if (P->ntt_fused || P->ntt_fused512 || P->ntt_two_streams) acc(dmalloc(&P->d_tmp2, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
+  if ((P->ntt_fused || P->ntt_fused512) && P->ntt_two_streams) acc(dmalloc(&P->d_tmp3, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
+  acc(dmalloc(&P->d_q, 2 * m, &P->dev_bytes)); acc(dmalloc(&P->d_qlde, 4 * m, &P->dev_bytes));
+  acc(tree_alloc(P->tree_q, m, cfg->cap_height, &P->dev_bytes));
+  acc(dmalloc(&P->d_tw_f, m, &P->dev_bytes)); acc(dmalloc(&P->d_tw_i, m, &P->dev_bytes)); acc(dmalloc(&P->d_shift, m, &P->dev_bytes)); acc(dmalloc(&P->d_shift_inv, m, &P->dev_bytes));
+  if (P->ntt_fused512) acc(dmalloc(&P->d_shift_odd, n, &P->dev_bytes));   // (ntt_plan)
+  acc(dmalloc(&P->d_xs, m, &P->dev_bytes)); acc(dmalloc(&P->d_lag_first, m, &P->dev_bytes)); acc(dmalloc(&P->d_lag_last, m, &P->dev_bytes));
   P->apow_n = apow_len(as.nconstraints, as.nzs);
-  acc(dmalloc(&P->d_apow, (size_t)SBN_NCH * P->apow_n));
-  acc(dmalloc(&P->d_zpow, 4 * n)); acc(dmalloc(&P->d_open, (C + Z + 4) * 4));
+  acc(dmalloc(&P->d_apow, (size_t)SBN_NCH * P->apow_n, &P->dev_bytes));
+  acc(dmalloc(&P->d_zpow, 4 * n, &P->dev_bytes)); acc(dmalloc(&P->d_open, (C + Z + 4) * 4, &P->dev_bytes));
   hipc(hipHostMalloc((void**)&P->h_open, (C + Z + 4) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
   hipc(hipHostMalloc((void**)&P->h_open2, (C + Z) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
-  acc(dmalloc(&P->d_part, 2 * 32 * n)); acc(dmalloc(&P->d_w, 4096)); acc(dmalloc(&P->d_sponge, 12 * m));
-  acc(dmalloc(&P->d_fa, 4 * n)); acc(dmalloc(&P->d_fcoef, 2 * m)); acc(dmalloc(&P->d_fcoef2, 2 * m));
-  acc(dmalloc(&P->d_pow, 1));
+  acc(dmalloc(&P->d_part, 2 * 32 * n, &P->dev_bytes)); acc(dmalloc(&P->d_w, 4096, &P->dev_bytes)); acc(dmalloc(&P->d_sponge, 12 * m, &P->dev_bytes));
+  acc(dmalloc(&P->d_fa, 4 * n, &P->dev_bytes)); acc(dmalloc(&P->d_fcoef, 2 * m, &P->dev_bytes)); acc(dmalloc(&P->d_fcoef2, 2 * m, &P->dev_bytes));
+  acc(dmalloc(&P->d_pow, 1, &P->dev_bytes));
   if (rc) { sbn_prover_destroy(P); return rc; }
   P->d_fb = P->d_fa + 2 * n;
-  hipc(hipMalloc((void**)&P->d_pic, sizeof(ExpPiConsts<F>)), "hipMalloc");
-  hipc(hipMalloc((void**)&P->d_idx, cfg->num_query_rounds * sizeof(u32)), "hipMalloc");
+  hipc(hipMalloc((void**)&P->d_pic, sizeof(ExpPiConsts<F>)), "hipMalloc"); P->dev_bytes += sizeof(ExpPiConsts<F>);
+  hipc(hipMalloc((void**)&P->d_idx, cfg->num_query_rounds * sizeof(u32)), "hipMalloc"); P->dev_bytes += cfg->num_query_rounds * sizeof(u32);
   // FRI layer buffers
   {
     u32 bits = P->lde_log;
     for (u32 ab : P->fri.arity_bits) {
-      u64* v = nullptr; acc(dmalloc(&v, 2 * ((size_t)1 << bits))); P->fri_vals.push_back(v);
-      DevTree t; acc(tree_alloc(t, (size_t)1 << (bits - ab), cfg->cap_height)); P->fri_trees.push_back(t);
+      u64* v = nullptr; acc(dmalloc(&v, 2 * ((size_t)1 << bits), &P->dev_bytes)); P->fri_vals.push_back(v);
+      DevTree t; acc(tree_alloc(t, (size_t)1 << (bits - ab), cfg->cap_height, &P->dev_bytes)); P->fri_trees.push_back(t);
       bits -= ab;
     }
     if (rc) { sbn_prover_destroy(P); return rc; }
@@ -747,7 +818,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
     u32 bits = P->lde_log;
     for (u32 ab : P->fri.arity_bits) { bits -= ab; s += 2 * ((size_t)1 << ab) + (size_t)(bits - cfg->cap_height) * 4; }
     P->qstride = s;
-    acc(dmalloc(&P->d_qbuf, s * cfg->num_query_rounds));
+    acc(dmalloc(&P->d_qbuf, s * cfg->num_query_rounds, &P->dev_bytes));
     if (rc) { sbn_prover_destroy(P); return rc; }
   }
   // tables
@@ -772,13 +843,13 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
       else exp_shape(as).pair((int)z, l, r);
       pairs[z].lhs = l; pairs[z].rhs = r;
     }
-    hipc(hipMalloc((void**)&P->d_pairs, std::max<size_t>(Z, 1) * sizeof(PairCols)), "hipMalloc");
+    hipc(hipMalloc((void**)&P->d_pairs, std::max<size_t>(Z, 1) * sizeof(PairCols)), "hipMalloc"); P->dev_bytes += std::max<size_t>(Z, 1) * sizeof(PairCols);
     if (!rc && Z) hipc(hipMemcpy(P->d_pairs, pairs.data(), Z * sizeof(PairCols), hipMemcpyHostToDevice), "hipMemcpy");
     if (P->sp && P->sp->zr) {   // the split: the pairs of this rank's Z columns in local order
       SplitCtx* S = P->sp;
       std::vector<PairCols> own(S->zr);
       for (size_t l = 0; l < S->zr; l++) own[l] = pairs[S->zs.global_col(S->zs.rank, l)];
-      hipc(hipMalloc((void**)&S->d_pairs_own, S->zr * sizeof(PairCols)), "hipMalloc");
+      hipc(hipMalloc((void**)&S->d_pairs_own, S->zr * sizeof(PairCols)), "hipMalloc"); P->dev_bytes += S->zr * sizeof(PairCols);
       if (!rc) hipc(hipMemcpy(S->d_pairs_own, own.data(), S->zr * sizeof(PairCols), hipMemcpyHostToDevice), "hipMemcpy");
     }
   }
@@ -789,6 +860,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   return SBN_OK;
 }
 
+namespace sbn { size_t prover_device_bytes(const sbn_prover* P) { return P ? P->dev_bytes : 0; } }   // capi.hip: the one-shot cache
 extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (!P) return;
   (void)hipSetDevice(P->device);
@@ -819,6 +891,13 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (P->h_io) (void)hipHostFree(P->h_io);
   if (P->h_open) (void)hipHostFree(P->h_open);
   if (P->h_open2) (void)hipHostFree(P->h_open2);
+  if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // (a refused call drained it already)
+  for (auto& e : P->upload_done) if (e) (void)hipEventDestroy(e);
+  for (auto& e : P->slot_copied) if (e) (void)hipEventDestroy(e);
+  if (P->h_ring) (void)hipHostFree(P->h_ring);
+  if (P->h_first_bad) (void)hipHostFree(P->h_first_bad);
+  if (P->d_first_bad) (void)hipFree(P->d_first_bad);
+  if (P->ustream) (void)hipStreamDestroy(P->ustream);
   if (P->hstream) (void)hipStreamDestroy(P->hstream);
   if (P->nstream) { (void)hipStreamDestroy(P->nstream); for (auto& e : P->intt_done) if (e) (void)hipEventDestroy(e); }
   if (P->stream) (void)hipStreamDestroy(P->stream);
@@ -837,7 +916,7 @@ extern "C" int sbn_prover_load_trace(sbn_prover* P, const uint64_t* trace, const
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
   size_t words = P->air.ncols * P->n;
   {  // canonical-form check on several host threads (the copy below is the PCIe-bound part)
-    unsigned nt = std::thread::hardware_concurrency(); if (nt == 0) nt = 4; if (nt > 16) nt = 16;
+    unsigned nt = tracegen_host_threads(); if (nt == 0) nt = 1; if (nt > 16) nt = 16;   // (honours SBN_HOST_THREADS)
     std::atomic<size_t> bad(words);
     std::vector<std::thread> th;
     size_t per = (words + nt - 1) / nt;
@@ -1315,10 +1394,11 @@ static int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t
   return 0;
 }
 
-extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) {
+// up: null for sbn_prover_prove (the trace is resident); else the host trace sbn_prover_prove_host_trace streams in
+static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
-  if (!P->loaded && !(P->sp && P->sp->comm.world > 1)) return fail(SBN_ERR_BAD_ARG, "no trace loaded");   // (split: agreed with the other ranks below)
+  if (!up && !P->loaded && !(P->sp && P->sp->comm.world > 1)) return fail(SBN_ERR_BAD_ARG, "no trace loaded");   // (split: agreed with the other ranks below)
   HIPC(hipSetDevice(P->device));
   hipStream_t st = P->stream;
   const size_t n = P->n, m = P->m, C = P->air.ncols, Z = P->air.nzs;
@@ -1342,13 +1422,15 @@ extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) {
     if ((rc = split_all_gather_host(P, &mine, st_all.data(), sizeof(uint32_t)))) return rc;
     for (u32 r = 0; r < S->comm.world; r++) if (!st_all[r]) return fail(SBN_ERR_BAD_ARG, "split proof abandoned: rank %u has no trace loaded", r);
   }
-  if (!P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
+  if (!up && !P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
+  if (up) HIPC(hipMemsetAsync(P->d_first_bad, 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
   if (S) {
     S->tev_used = 0;
     if ((rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t))) return rc;
-  } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES))) return rc;
+  } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up))) return rc;
   HIPC(hipEventRecord(P->ev[ST_PERM_Z], st));
-  if ((rc = S ? split_cap_to_host(P, P->tree_t, trace_cap) : tree_cap_to_host(P, P->tree_t, trace_cap))) return rc;
+  if ((rc = S ? split_cap_to_host(P, P->tree_t, trace_cap) : tree_cap_to_host(P, P->tree_t, trace_cap, up != nullptr))) return rc;
+  if (up && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
   ch.observe_words(trace_cap.data(), capw);
 
   // P2 permutation argument -------------------------------------------------------------------------
@@ -1793,6 +1875,28 @@ extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) {
   *out = pr;
   return SBN_OK;
 }
+extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_impl(P, out, nullptr); }
+
+// load + prove in one call (include/sbn.h): the upload runs inside the trace commitment, the canonical-form check on the device
+extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi, sbn_proof** out) {
+  if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  *out = nullptr;
+  P->loaded = false;   // before any check: a refused call must not leave the previous trace provable
+  if (!trace) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "sbn_prover_prove_host_trace covers single-GPU provers");
+  int rc = check_pi(P, pi, n_pi); if (rc) return rc;
+  HIPC(hipSetDevice(P->device));
+  if ((rc = upload_setup(P))) return rc;
+  const HostUpload up{trace, P->upload_done};
+  if ((rc = prove_impl(P, out, &up))) {
+    // whatever was enqueued (the rest of an upload, transforms of a refused trace) ends before the caller sees the error:
+    // the next call finds idle streams and a free ring
+    for (hipStream_t s : {P->ustream, P->stream, P->hstream, P->nstream}) if (s) (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  P->loaded = true;
+  return SBN_OK;
+}
 
 // ---- building blocks for parity tests ---------------------------------------------------------------
 extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint64_t* cap_out,
@@ -1915,6 +2019,36 @@ extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, 
   }
   (void)hipFree(d);
   if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_bn254_fq_batch: %s", hipGetErrorString(e));
+  return SBN_OK;
+}
+
+// Index of the first word >= p, or `count`: the scan of sbn_prover_prove_host_trace as a building block (host in, host out).
+extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out) {
+  if (!index_out || (!words && count)) return fail(SBN_ERR_BAD_ARG, "null argument");
+  *index_out = count;
+  if (!on_device) {
+    for (size_t i = 0; i < count; i++) if (words[i] >= GLP) { *index_out = i; break; }
+    return SBN_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
+  HIPC(hipSetDevice(g_device));
+  if (count == 0) return SBN_OK;
+  // the device copy keeps the caller's offset from a 16-byte boundary, so the kernel's unaligned head is reachable from a test
+  const size_t off = ((size_t)words & 8) ? 1 : 0;
+  u64* d = nullptr;
+  HIPC(hipMalloc((void**)&d, (2 + off + count) * sizeof(u64)));   // d[0]: the result word; the data from d + 2 + off
+  unsigned long long first = ~0ull;
+  hipError_t e = hipMemset(d, 0xff, sizeof(u64));
+  if (e == hipSuccess) e = hipMemcpy(d + 2 + off, words, count * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_first_non_canonical(d + 2 + off, count, 0, (unsigned long long*)d, 0);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(&first, d, sizeof first, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_first_non_canonical: %s", hipGetErrorString(e));
+  if (first != ~0ull) *index_out = first;
   return SBN_OK;
 }
 

@@ -238,6 +238,7 @@ int tracegen_host_chains(int E, const uint32_t* ios, size_t K, u64* ja, u64* jb,
 
 namespace sbn {
 unsigned tracegen_host_threads() { return pool_threads(); }
+void host_parallel_for(size_t n, const std::function<void(size_t)>& f) { parallel_for(n, f); }
 bool tracegen_host_chains_vectorized() {
 #if defined(SBN_HAVE_IFMA)
   return ifma::available();
