@@ -165,6 +165,13 @@ int sbn_generate_trace_flags(const uint32_t* limbs, size_t num_io, uint64_t* tra
 int sbn_generate_trace_flags_u64(const uint64_t* exps, size_t num_io, uint64_t* trace_out);
 
 /* Prover ---------------------------------------------------------------------------------------- */
+/* Accepted (anything else: SBN_ERR_UNSUPPORTED, checked before a device is looked for): num_challenges = 2, rate_bits = 1,
+ * cap_height 1..8, fri_arity_bits 1..4, num_query_rounds 1..512, proof_of_work_bits 0..32, any fri_final_poly_bits, fri_variant
+ * 0..2; degree_bits 9..22 (the Exp tables: the height their num_io fixes, G1 / G2 / FQ_EXP from 2^16 rows).  Every value of
+ * that range is proved on the device and compared word for word with the CPU oracle under the same config
+ * (tests/test_config_matrix_gpu.py: each field at both ends of its range except 32 proof-of-work bits, LookupStark at every
+ * height up to 2^22 rows).  fri_arity_bits = 1: a FRI leaf is two extension values = four words, which is its own digest
+ * (plonky2 hash_or_noop), as the rows of a matrix of at most four columns are. */
 int sbn_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, sbn_prover** out);
 void sbn_prover_destroy(sbn_prover* p);
 /* Host -> device copy of the trace (PCIe-inclusive path). */
@@ -320,7 +327,8 @@ int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const uint8_t* pr
 
 /* Building blocks exposed for parity tests and benchmarks (device in/out unless noted) --------- */
 /* PolynomialBatch::from_values on a host column-major matrix: Merkle cap (2^cap_height x 4 words),
- * optionally coefficients [ncols][n] and LDE [ncols][n<<rate_bits] (natural order) back to host. */
+ * optionally coefficients [ncols][n] and LDE [ncols][n<<rate_bits] (natural order) back to host.
+ * rate_bits = 1, n a power of two >= 512, cap_height 1..8 (the range of sbn_config); otherwise SBN_ERR_UNSUPPORTED. */
 int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
                       uint64_t* cap_out, uint64_t* coeffs_out, uint64_t* lde_out);
 /* Poseidon permutation of `count` independent width-12 states on the device (host in/out). */

@@ -293,9 +293,21 @@ int orc_flags_u64_generate_trace(const uint64_t* exps, size_t num_io, uint64_t* 
 static int g_final_poly_times_x = 1;
 void orc_set_final_poly_times_x(int on) { g_final_poly_times_x = on ? 1 : 0; }
 
+// The StarkConfig of the *_cfg entry points: six u32 words = cap_height, proof_of_work_bits, arity_bits, final_poly_bits,
+// num_query_rounds, final_poly_times_x.  null = the default config with the orc_set_final_poly_times_x switch.
+static StarkConfig make_config(const uint32_t* c) {
+  StarkConfig cfg;
+  cfg.fri.final_poly_times_x = g_final_poly_times_x != 0;
+  if (c) {
+    cfg.fri.cap_height = c[0]; cfg.fri.proof_of_work_bits = c[1]; cfg.fri.arity_bits = c[2]; cfg.fri.final_poly_bits = c[3];
+    cfg.fri.num_query_rounds = c[4]; cfg.fri.final_poly_times_x = c[5] != 0;
+  }
+  return cfg;
+}
+
 // prove(): trace col-major [ncols][1<<degree_bits]; returns malloc'd canonical proof words.
-int orc_prove(int kind, size_t num_io, const uint64_t* trace, unsigned degree_bits, const uint64_t* pi, size_t npi,
-              uint64_t** proof_out, size_t* nwords_out, double* seconds_out) {
+int orc_prove_cfg(int kind, size_t num_io, const uint64_t* trace, unsigned degree_bits, const uint64_t* pi, size_t npi, const uint32_t* config,
+                  uint64_t** proof_out, size_t* nwords_out, double* seconds_out) {
   auto air = make_air(kind, num_io);
   if (!air) return -1;
   size_t n = (size_t)1 << degree_bits, ncols = air->num_columns();
@@ -303,8 +315,7 @@ int orc_prove(int kind, size_t num_io, const uint64_t* trace, unsigned degree_bi
   std::vector<std::vector<GF>> cols(ncols, std::vector<GF>(n));
   for (size_t c = 0; c < ncols; c++) for (size_t i = 0; i < n; i++) { if (trace[c * n + i] >= GL_P) return -3; cols[c][i] = GF(trace[c * n + i]); }
   std::vector<GF> pis(npi); for (size_t i = 0; i < npi; i++) pis[i] = GF(pi[i]);
-  StarkConfig cfg;
-  cfg.fri.final_poly_times_x = g_final_poly_times_x != 0;
+  StarkConfig cfg = make_config(config);
   auto t0 = std::chrono::steady_clock::now();
   StarkProofWithPublicInputs p = prove(*air, cfg, cols, pis);
   auto t1 = std::chrono::steady_clock::now();
@@ -314,6 +325,10 @@ int orc_prove(int kind, size_t num_io, const uint64_t* trace, unsigned degree_bi
   memcpy(*proof_out, w.data(), w.size() * 8);
   *nwords_out = w.size();
   return 0;
+}
+int orc_prove(int kind, size_t num_io, const uint64_t* trace, unsigned degree_bits, const uint64_t* pi, size_t npi,
+              uint64_t** proof_out, size_t* nwords_out, double* seconds_out) {
+  return orc_prove_cfg(kind, num_io, trace, degree_bits, pi, npi, nullptr, proof_out, nwords_out, seconds_out);
 }
 void orc_free(void* p) { free(p); }
 // OpenMP threads of the following calls (tools/oracle_scaling.py); 0 = leave as is.  Returns the maximum available.
@@ -326,18 +341,20 @@ int orc_last_stage_seconds(int k, const char** name, double* seconds) {
   return (int)v.size();
 }
 
-// 0 = accepted; negative = rejected (message in *why).
-int orc_verify(int kind, size_t num_io, const uint64_t* proof, size_t nwords, const char** why) {
+// 0 = accepted; negative = rejected (message in *why).  config: make_config.
+int orc_verify_cfg(int kind, size_t num_io, const uint64_t* proof, size_t nwords, const uint32_t* config, const char** why) {
   static const char* w0 = ""; if (why) *why = w0;
   auto air = make_air(kind, num_io);
   if (!air) { if (why) *why = "unknown air"; return -1; }
   StarkProofWithPublicInputs p;
   if (!deserialize_proof(proof, nwords, p)) { if (why) *why = "malformed proof bytes"; return -2; }
-  StarkConfig cfg;
-  cfg.fri.final_poly_times_x = g_final_poly_times_x != 0;
+  StarkConfig cfg = make_config(config);
   const char* reason = "";
   if (!verify(*air, cfg, p, &reason)) { if (why) *why = reason; return -3; }
   return 0;
+}
+int orc_verify(int kind, size_t num_io, const uint64_t* proof, size_t nwords, const char** why) {
+  return orc_verify_cfg(kind, num_io, proof, nwords, nullptr, why);
 }
 
 // Constraint probe: evaluate the AIR's constraints (no permutation checks) on given local/next rows

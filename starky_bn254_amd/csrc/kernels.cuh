@@ -213,13 +213,20 @@ __global__ __launch_bounds__(256) void merkle_level_coop_kernel(u64* __restrict_
   if (parent < parents && lane < 4) out[parent * 4 + lane] = r;
 }
 
-// FRI layer leaves: leaf l = the 16 extension values at bit-reversed positions 16l..16l+15 of the
+// FRI layer leaves: leaf l = the 2^arity_bits extension values at bit-reversed positions l 2^arity_bits .. of the
 // layer's evaluation vector (planes va/vb in natural order), flattened c0,c1 (fri/prover.rs).
+// arity_bits = 1: the leaf is four words, which hash_or_noop makes its own digest (as leaf_hash_kernel does for a matrix of
+// at most four columns); from arity_bits = 2 on the leaf is a whole number of four-value sponge blocks.
 __global__ __launch_bounds__(256) void fri_leaf_hash_kernel(const u64* __restrict__ va, const u64* __restrict__ vb, u32 log_m, u32 arity_bits,
                                                             u64* __restrict__ digests) {
   size_t leaf = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t nleaf = (size_t)1 << (log_m - arity_bits);
   if (leaf >= nleaf) return;
+  if (arity_bits == 1) {
+    const u32 n0 = bitrev32((u32)(leaf * 2), log_m), n1 = bitrev32((u32)(leaf * 2 + 1), log_m);
+    digests[leaf * 4 + 0] = va[n0]; digests[leaf * 4 + 1] = vb[n0]; digests[leaf * 4 + 2] = va[n1]; digests[leaf * 4 + 3] = vb[n1];
+    return;
+  }
   F s[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = F(0);
@@ -244,6 +251,13 @@ __global__ __launch_bounds__(256) void fri_leaf_hash_coop_kernel(const u64* __re
   const size_t nleaf = (size_t)1 << (log_m - arity_bits);
   const u32 lane = threadIdx.x & 15, e = lane < 12 ? lane : lane - 12;  // lanes 12..15 mirror elements 0..3
   const u32 arity = 1u << arity_bits;
+  if (arity_bits == 1) {   // wave-uniform (a kernel argument): no lane reaches the DPP rotations below
+    if (leaf < nleaf && lane < 4) {
+      const u32 nat = bitrev32((u32)(leaf * 2 + (lane >> 1)), log_m);
+      digests[leaf * 4 + lane] = (lane & 1) ? vb[nat] : va[nat];
+    }
+    return;
+  }
   u64 st = 0;
   for (u32 t = 0; t < arity; t += 4) {
     if (leaf < nleaf && e < 8) {

@@ -1904,6 +1904,8 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
   if (!cols || !cap_out || ncols == 0) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (rate_bits != 1 || n < 512 || (n & (n - 1))) return fail(SBN_ERR_UNSUPPORTED, "need rate_bits=1 and n a power of two >= 512");
   u32 lg = 0; while (((size_t)1 << lg) < n) lg++;
+  // the range of config_supported: tree_alloc computes the level count lg + 1 - cap_height unsigned, and lg + 1 >= 10
+  if (cap_height < 1 || cap_height > 8) return fail(SBN_ERR_UNSUPPORTED, "cap_height must be 1..8");
   // a throw-away prover-like context built on the G1_OP shape would waste memory; build a minimal one
   sbn_prover P{};
   sbn_standard_fast_config(&P.cfg); P.cfg.cap_height = cap_height;

@@ -45,6 +45,11 @@ def lib():
                                 C.POINTER(u64p), C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
         L.orc_verify.restype = C.c_int
         L.orc_verify.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p)]
+        L.orc_prove_cfg.restype = C.c_int
+        L.orc_prove_cfg.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.POINTER(u64p), C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
+        L.orc_verify_cfg.restype = C.c_int
+        L.orc_verify_cfg.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_char_p)]
         L.orc_free.argtypes = [C.c_void_p]
         L.orc_commit_values.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_hash_no_pad.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
@@ -223,7 +228,24 @@ def g1op_trace(pts):
     return trace
 
 
-def prove(kind, num_io, trace, pi):
+def _config_words(config):
+    """config: None (the oracle's default StarkConfig and the set_final_poly_times_x switch), a 5-tuple (cap_height,
+    proof_of_work_bits, arity_bits, final_poly_bits, num_query_rounds) or a 6-tuple with the times-X switch as a bool at the end
+    (default True), or any object with the product's field names (cap_height, proof_of_work_bits, fri_arity_bits,
+    fri_final_poly_bits, num_query_rounds, fri_variant: 2 = without the times-X step)."""
+    if config is None:
+        return None
+    if hasattr(config, "cap_height"):
+        config = (config.cap_height, config.proof_of_work_bits, config.fri_arity_bits, config.fri_final_poly_bits,
+                  config.num_query_rounds, config.fri_variant != 2)
+    config = tuple(config)
+    if len(config) == 5:
+        config += (True,)
+    assert len(config) == 6
+    return np.array([int(v) for v in config], dtype=np.uint32)
+
+
+def prove(kind, num_io, trace, pi, config=None):
     trace = np.ascontiguousarray(trace, dtype=np.uint64)
     pi = np.ascontiguousarray(pi, dtype=np.uint64)
     n = trace.shape[1]
@@ -231,7 +253,9 @@ def prove(kind, num_io, trace, pi):
     out = C.POINTER(C.c_uint64)()
     nw = C.c_size_t()
     secs = C.c_double()
-    rc = lib().orc_prove(kind, num_io, ptr(trace), degree_bits, ptr(pi), len(pi), C.byref(out), C.byref(nw), C.byref(secs))
+    cw = _config_words(config)
+    rc = lib().orc_prove_cfg(kind, num_io, ptr(trace), degree_bits, ptr(pi), len(pi), ptr(cw) if cw is not None else None,
+                             C.byref(out), C.byref(nw), C.byref(secs))
     if rc != 0:
         raise RuntimeError(f"orc_prove failed rc={rc}")
     words = np.ctypeslib.as_array(out, shape=(nw.value,)).copy()
@@ -257,10 +281,11 @@ def set_final_poly_times_x(on):
     lib().orc_set_final_poly_times_x(1 if on else 0)
 
 
-def verify(kind, num_io, words):
+def verify(kind, num_io, words, config=None):
     words = np.ascontiguousarray(words, dtype=np.uint64)
     why = C.c_char_p()
-    rc = lib().orc_verify(kind, num_io, ptr(words), len(words), C.byref(why))
+    cw = _config_words(config)
+    rc = lib().orc_verify_cfg(kind, num_io, ptr(words), len(words), ptr(cw) if cw is not None else None, C.byref(why))
     return rc, (why.value or b"").decode()
 
 

@@ -87,19 +87,36 @@ def test_poseidon_reduction_edge_cases(gpu, O):
     assert np.array_equal(dev, gpu.poseidon_permute_host(big, use_definition=True))
 
 
-@pytest.mark.parametrize("ncols,n", [(1, 512), (3, 512), (4, 1024), (5, 512), (8, 2048), (9, 4096), (20, 1024), (17, 65536), (130, 16384), (9, 131072), (3, 262144), (66, 262144)])
+@pytest.mark.parametrize("ncols,n", [(1, 512), (3, 512), (4, 1024), (5, 512), (8, 2048), (9, 4096), (20, 1024), (17, 65536), (130, 16384), (9, 131072), (3, 262144), (66, 262144),
+                                     (9, 8192), (9, 32768), (2, 1 << 19), (5, 1 << 20)])
 def test_commit_matches_oracle(gpu, O, ncols, n):
     """PolynomialBatch::from_values: iNTT, coset LDE (shift 7, blow-up 2), Poseidon leaves, Merkle cap.
     Covers <=4 columns (hash_or_noop copies the row), a ragged last sponge block, and NTT sizes that
-    use one, and both, LDS tile widths."""
+    use one, and both, LDS tile widths; 2^13, 2^15, 2^19 and 2^20 rows (transform sizes no other case has).  Every size at the
+    default cap height; the two ends of its range (a tree that stops 2^8 nodes wide, and one that runs down to two) on the sizes
+    that reach a different mix of Merkle kernels."""
     rng = np.random.default_rng(ncols * 1000 + n)
     cols = rng.integers(0, P, size=(ncols, n), dtype=np.uint64)
     cols[0, :4] = [0, P - 1, 1, 0xFFFFFFFF00000000]
-    cap, co, lde = gpu.commit_values(cols, want_coeffs=True, want_lde=True)
-    rcap, rco, rlde = O.commit_values(cols, want_coeffs=True, want_lde=True)
-    assert np.array_equal(co, rco)
-    assert np.array_equal(lde, rlde)
-    assert np.array_equal(cap, rcap)
+    both_ends = (ncols, n) in [(3, 512), (5, 512), (20, 1024), (9, 4096), (17, 65536), (3, 262144), (2, 1 << 19)]
+    for cap_height in ((4, 1, 8) if both_ends else (4,)):
+        cap, co, lde = gpu.commit_values(cols, cap_height=cap_height, want_coeffs=True, want_lde=True)
+        rcap, rco, rlde = O.commit_values(cols, cap_height=cap_height, want_coeffs=True, want_lde=True)
+        assert cap.shape == (1 << cap_height, 4)
+        assert np.array_equal(co, rco), cap_height
+        assert np.array_equal(lde, rlde), cap_height
+        assert np.array_equal(cap, rcap), cap_height
+
+
+@pytest.mark.parametrize("cap_height", [0, 9, 20, 0xFFFFFFFF])
+def test_commit_refuses_a_cap_height_outside_1_to_8(gpu, cap_height):
+    """The range of config_supported: the level count of the tree is computed unsigned, so a cap above the tree would wrap.  The
+    refusal comes before anything is allocated or launched."""
+    cols = np.zeros((2, 512), dtype=np.uint64)
+    cap = np.zeros((1, 4), dtype=np.uint64)   # (never written: the call is refused)
+    with pytest.raises(gpu.SbnError) as e:
+        gpu.api._check(gpu.lib().sbn_commit_values(gpu.api._ptr(cols), 2, 512, 1, cap_height, gpu.api._ptr(cap), None, None))
+    assert e.value.code == -7
 
 
 @pytest.mark.parametrize("n", [65536, 131072, 262144])
