@@ -125,6 +125,9 @@ bool tracegen_host_chains_vectorized();
 size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)
 int current_device();
+// prover.hip: SBN_ERR_NO_DEVICE ("no HIP device available: <why>") unless the process has a HIP device; else current_device() becomes
+// HIP's current device of the calling thread
+int use_current_device(const char* why);
 
 }  // namespace sbn
 

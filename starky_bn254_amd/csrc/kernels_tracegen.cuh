@@ -23,7 +23,7 @@ using namespace bnw;
 
 
 // a^(p-2) with 4-bit fixed windows (252 squarings + <= 64 + 14 products).  The inversion helpers below are host-device only so that
-// sbn_bn254_fq_batch (prover.hip) can run the host build of them as well; the kernels use the device build.
+// sbn_bn254_fq_batch (tracegen_device.hip) can run the host build of them as well; the kernels use the device build.
 __host__ __device__ __noinline__ Fq finv_fermat(const Fq& a) {
   constexpr u64 PL[4] = BNW_PL;
   const u64 e[4] = {PL[0] - 2, PL[1], PL[2], PL[3]};
@@ -81,7 +81,7 @@ __global__ void chain_kernel(const uint32_t* __restrict__ ios, size_t K, u64* __
 // exp_chains is 512 dependent point operations per instance: 13 ms on one lane, 2.2 ms on the host pool.  But a Jacobian doubling
 // and an addition are ~25 Fq (4 x that: Fq2) products of which up to 8 (32) are independent, and the doubling of a and the addition
 // b += a of one step do not depend on each other.  The host lays one step out as LEVELS of independent micro-operations over Fq
-// slots (ChainProgram in prover.hip: every product, sum, difference of jac_double / jac_add, Fq2 products expanded into their four
+// slots (ChainProgram in tracegen_device.hip: every product, sum, difference of jac_double / jac_add, Fq2 products expanded into their four
 // Fq products; level = longest dependency path), and a wave executes a level with one micro-operation per lane, operands and
 // results in LDS.  Field arithmetic is exact, so the stored Jacobian coordinates are word for word those of exp_chains.
 // Micro-operation word: kind | dst << 8 | a << 16 | b << 24 (slot numbers < 256).
@@ -944,7 +944,7 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
   RC_MARK(8);
 }
 
-// ---- parity hook (sbn_bn254_fq_batch, prover.hip): the field helpers above on standard-form operands, 4 words per element --------------
+// ---- parity hook (sbn_bn254_fq_batch, tracegen_device.hip): the field helpers above on standard-form operands, 4 words per element --------------
 enum { FQB_MUL = 0, FQB_ADD = 1, FQB_SUB = 2, FQB_INV = 3, FQB_BATCH_INV = 4, FQB_FQ2_INV = 5 };
 // Item i of op: element i, or group i of TG_INV_BATCH elements for FQB_BATCH_INV.  FQB_INV is finv_fermat on the device and inv_std on
 // the host; FQB_FQ2_INV reads c0 from a and c1 from b and writes out[i] = {c0, c1} (8 words).

@@ -2,10 +2,8 @@
 // G1 tables (call sites src/curves/g1/exp.rs:818-825, src/curves/g1/muladd.rs:669-676).  The host
 // owns only the Fiat-Shamir transcript and proof assembly; every polynomial / hashing / constraint
 // stage runs in the kernels of kernels.cuh on one HIP stream.
-#include "host_common.hpp"
-#include "settings.hpp"
+#include "prover_ctx.hpp"
 #include "kernels.cuh"
-#include "kernels_tracegen.cuh"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -14,15 +12,7 @@
 #include <chrono>
 #include <functional>
 
-using namespace sbn;
-
 namespace sbn { thread_local std::string g_last_error; }
-
-#define HIPC(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return fail(SBN_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 // sbn_set_device: the device of the provers created afterwards by the calling thread, and the default of threads that never
 // chose one; sbn_set_thread_device: the calling thread only (the ranks of a local split group are threads with one device each:
@@ -32,135 +22,21 @@ static std::atomic<int> g_default_device{0};
 static thread_local int t_device = -1;
 static inline int cur_device() { return t_device >= 0 ? t_device : g_default_device.load(); }
 #define g_device (cur_device())
-namespace sbn { int current_device() { return cur_device(); } }   // transport.hip
+namespace sbn {
+int current_device() { return cur_device(); }   // transport.hip
+int use_current_device(const char* why) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: %s", why);
+  HIPC(hipSetDevice(g_device));
+  return 0;
+}
+}  // namespace sbn
 
-// Stage k spans [ev[k], ev[k+1]) on the prover's main stream.  The commit stages overlap NTT (main
-// stream) with sponge absorption (hash stream); the absorption kernels are additionally timed one by
-// one with events on the hash stream (EXTRA_* entries = sum over the chunk launches of one proof).
-enum Stage {
-  ST_TRACE_COMMIT, ST_PERM_Z, ST_Z_COMMIT, ST_QUOTIENT_EVAL, ST_QUOTIENT_COMMIT,
-  ST_OPENINGS, ST_FRI_COMBINE, ST_FRI_LAYERS, ST_POW, ST_QUERIES, ST_COUNT
-};
-enum Extra { EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, EX_TRACEGEN_MS, EX_COMM_MS, EX_COUNT };
 static const char* STAGE_NAMES[ST_COUNT + EX_COUNT] = {
   "trace_commit", "perm_z", "z_commit", "quotient_eval", "quotient_commit",
   "openings", "fri_combine", "fri_layers", "pow", "queries",
   "trace_absorb_kernels_ms", "trace_absorb_launches", "z_absorb_kernels_ms", "z_absorb_launches", "device_tracegen_ms",
   "split_exchange_ms"};
-static constexpr int MAX_CHUNKS = 512;
-// prove_host_trace: the pinned staging ring of one prover, 4 slots of 16 MiB = 64 MiB of pinned host memory at most, allocated on
-// the first call.  A piece of the trace never spans two column chunks; a chunk larger than a slot crosses in several pieces.
-static constexpr int UPLOAD_SLOTS = 4;
-static constexpr size_t UPLOAD_SLOT_WORDS = (size_t)2 << 20;
-
-struct DevTree {  // Merkle digests, levels concatenated (leaf level first)
-  u64* d = nullptr; size_t nleaf = 0; u32 nlevels = 0;  // nlevels = number of levels BELOW the cap
-  u64* level(u32 l) const { return d + (2 * nleaf - ((2 * nleaf) >> l)) * 4; }
-};
-
-// Oversized-trace split (include/sbn.h, sbn_split_prover_*): this rank's share of one proof.
-// The columns of a matrix are dealt to the ranks in blocks of `ob` columns, round-robin: rank r owns the blocks
-// b = r, r + R, r + 2R, ... and keeps them compactly (own block k = global block k * R + r at local columns k * ob ...);
-// only the globally last block can be short, and it is the last own block of its owner.  In step k of a commitment every
-// rank transforms its own block k, the all-to-all of that step moves the blocks k * R .. k * R + R - 1 to their row
-// owners, and the leaf sponge -- sequential over the columns of a row -- absorbs exactly those blocks next.
-struct ColShare {
-  size_t total = 0, ob = 64; u32 R = 1, rank = 0;
-  size_t nblocks() const { return (total + ob - 1) / ob; }
-  size_t steps() const { return (nblocks() + R - 1) / R; }
-  size_t block_cols(size_t b) const { return b < nblocks() ? std::min(ob, total - b * ob) : 0; }
-  size_t own_cols(u32 r) const { size_t s = 0; for (size_t b = r; b < nblocks(); b += R) s += block_cols(b); return s; }
-  size_t own() const { return own_cols(rank); }
-  size_t max_own() const { size_t s = 0; for (u32 r = 0; r < R; r++) s = std::max(s, own_cols(r)); return s; }
-  size_t global_col(u32 r, size_t local) const { return ((local / ob) * R + r) * ob + local % ob; }   // of rank r's local column
-};
-struct SplitCtx {
-  sbn_comm comm;
-  u32 log_r = 0, rho = 0;                 // world = 2^log_r; this rank owns the LDE rows i = j * world + rho
-  size_t ml = 0;                          // local LDE rows = m >> log_r
-  ColShare cs, zs;                        // trace / Z columns of this rank
-  size_t cr = 0, zr = 0;                  // = cs.own(), zs.own()
-  u32 planes = 1;                         // 2 from four ranks up: the rows i + 2 of the local rows arrive as a second plane
-  u64 *lde_l = nullptr, *lde_n = nullptr, *zlde_l = nullptr, *zlde_n = nullptr, *scratch = nullptr;   // views of comm.recv_buf
-  size_t scratch_words = 0;
-  size_t slot_words = 0;                  // one send slot = [plane][dest][ob][ml]; two slots, used alternately by the steps
-  u64* d_ldechunk = nullptr;              // [ntt_chunk][m]: one column block of this rank's LDE before it is packed
-  u32* d_idx_local = nullptr;             // query leaf indices inside this rank's subtrees
-  PairCols* d_pairs_own = nullptr;        // permutation pairs of the own Z columns, local order
-  hipStream_t cstream = nullptr;          // the exchanges of the commit pipeline
-  hipEvent_t xchg_done[MAX_CHUNKS];       // comm stream: the blocks of step k have arrived (and send slot k & 1 is free again)
-  std::vector<hipEvent_t> tev;            // timing events around the exchanges (pairs), consumed in order
-  size_t tev_used = 0;
-};
-
-struct sbn_prover {
-  AirShape air; sbn_config cfg; FriShape fri;
-  SplitCtx* sp = nullptr;                 // null: the whole proof on this GPU
-  size_t lde_scratch_words = 0;           // capacity of d_lde as witness-generation scratch
-  u32 degree_bits, lde_log; size_t n, m;
-  int device; hipStream_t stream;
-  // matrices
-  u64 *d_trace = nullptr, *d_coef = nullptr, *d_lde = nullptr, *d_tmp = nullptr;
-  u64 *d_zval = nullptr, *d_zcoef = nullptr, *d_zlde = nullptr;
-  u64 *d_q = nullptr, *d_qlde = nullptr;
-  DevTree tree_t, tree_z, tree_q;
-  std::vector<DevTree> fri_trees;
-  // tables
-  u64 *d_tw_f = nullptr, *d_tw_i = nullptr, *d_shift = nullptr, *d_shift_inv = nullptr;
-  u64 *d_shift_odd = nullptr;   // 2^19-point LDE (1,024 x 512): 7^i w_1024^(i >> 9), the input scale of the odd half of its split first pass
-  u64 *d_xs = nullptr, *d_lag_first = nullptr, *d_lag_last = nullptr;
-  u64 *d_apow = nullptr;  // [2][apow_n]
-  size_t apow_n = 0;
-  void* d_pic = nullptr;  // ExpPiConsts<F>
-  PairCols* d_pairs = nullptr;
-  // openings / FRI
-  u64 *d_zpow = nullptr;        // 4 planes [n]: z^i (a,b), (g z)^i (a,b)
-  u64 *d_open = nullptr;        // [(ncols + nzs + 4)][4]
-  u64 *d_part = nullptr;        // 2 planes [groups][n]
-  u64 *d_w = nullptr;           // group weights
-  u64 *d_fa = nullptr, *d_fb = nullptr;    // F0 / F1 scratch planes [n] each (a,b) x2
-  u64 *d_fcoef = nullptr;       // final poly coefficient planes [2][m]
-  u64 *d_fcoef2 = nullptr;      // ping-pong for folding [2][m/2^arity]
-  std::vector<u64*> fri_vals;   // per layer value planes [2][size]
-  u64 *d_pow = nullptr;
-  u32 *d_idx = nullptr;
-  u64 *d_qbuf = nullptr; size_t qstride = 0;
-  std::vector<u64> pi;
-  bool loaded = false;
-  hipEvent_t ev[ST_COUNT + 1];
-  float stage_ms[ST_COUNT + EX_COUNT];
-  size_t ntt_chunk;
-  bool ntt_fused = false;                    // the inverse transform's pass B and the LDE's pass A as ONE kernel (2^16 / 2^17 rows)
-  u64* d_tmp2 = nullptr;                     // its output: the fused kernel cannot work in place
-  u64* d_tmp3 = nullptr;                     // 2^18 rows, two transform streams: the fused kernel's second output buffer (chunks alternate)
-  bool ntt_fused512 = false;                 // 2^18-row tables: kernels_ntt.cuh ntt_fused512_inv_b_lde_a_kernel
-  hipStream_t hstream = nullptr;             // sponge absorption / Merkle stream
-  hipStream_t nstream = nullptr;             // second transform stream (2^19 LDE rows and up): the LDE of chunk k beside the inverse transform of chunk k+1
-  hipEvent_t intt_done[MAX_CHUNKS];          // main -> second transform stream: the coefficients of chunk k are complete
-  bool ntt_two_streams = false;
-  Settings set;                              // the SBN_* switches this prover was created under (settings.hpp)
-  int chain_mode = 0;                        // curve witness: 0 host pool, 1 one lane per instance, 2 one wave per instance
-  hipEvent_t chunk_ready[MAX_CHUNKS];        // main -> hash: LDE chunk k is complete
-  hipEvent_t abs_ev[2 * MAX_CHUNKS];         // hash stream: before/after each absorb launch
-  hipEvent_t hash_done;                      // hash -> main
-  u64* d_sponge = nullptr;                   // [12][m] sponge state carried between column chunks
-  u64* h_chain = nullptr;                    // pinned staging for the host-computed curve chains (device tracegen)
-  size_t h_chain_words = 0;
-  u64* h_io = nullptr;                       // pinned staging of the device witness: the instance list in, the outputs + error word back
-  size_t h_io_words = 0;
-  u64* h_open = nullptr;                     // pinned landing buffer of the opened values [(ncols + nzs + 4)][4]
-  u64* h_open2 = nullptr;                    // second landing buffer: the values at g*zeta of the trace and Z columns (the host is still reading the first)
-  size_t dev_bytes = 0;                      // device memory this context allocated (what the one-shot cache of capi.hip counts)
-  // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
-  hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk
-  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned
-  hipEvent_t slot_copied[UPLOAD_SLOTS];      // copy stream: the copy out of ring slot s has completed
-  bool slot_used[UPLOAD_SLOTS] = {};
-  unsigned slot_next = 0;
-  u64* h_ring = nullptr;                     // [UPLOAD_SLOTS][UPLOAD_SLOT_WORDS], pinned
-  unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
-  unsigned long long* h_first_bad = nullptr; // its pinned landing word
-};
 
 static int dmalloc(u64** p, size_t words, size_t* bytes = nullptr) {   // bytes: the context's running total (sbn_prover::dev_bytes)
   HIPC(hipMalloc((void**)p, words * sizeof(u64)));
@@ -225,8 +101,6 @@ static int ntt_columns(sbn_prover* P, const u64* in, size_t in_cs, u64* out, siz
 
 static u64 host_inv_pow2(u32 k) { return f_inv(F((u64)1 << k)).v; }
 // the R = 512 fast pass needs 69,632 bytes of dynamic LDS (> the 64 KiB default)
-// Function attributes are per DEVICE: one flag per device of the process (sbn_set_device may select another GPU later).
-static constexpr int SBN_MAX_DEVICES = 64;
 static int ntt_fast_setup() {  // idempotent, so a race between prover threads is harmless; the flag only saves the call
   static std::atomic<bool> done[SBN_MAX_DEVICES];
   const int d = g_device >= 0 && g_device < SBN_MAX_DEVICES ? g_device : 0;
@@ -673,9 +547,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
     if (as.kind != SBN_AIR_FQ12_EXP && as.kind != SBN_AIR_FQ12_EXP_U64 && degree_bits < 16)
       return fail(SBN_ERR_UNSUPPORTED, "G1_EXP / G2_EXP / FQ_EXP need >= 2^16 rows (u16 range check, range_check.rs:26)");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: the prover path has no CPU fallback");
-  HIPC(hipSetDevice(g_device));
+  if (int rc = use_current_device("the prover path has no CPU fallback")) return rc;
   sbn_prover* P = new sbn_prover();
   P->air = as; P->cfg = *cfg; P->degree_bits = degree_bits; P->lde_log = degree_bits + cfg->rate_bits;
   P->n = (size_t)1 << degree_bits; P->m = (size_t)1 << P->lde_log;
@@ -941,409 +813,6 @@ extern "C" int sbn_prover_load_trace_device(sbn_prover* P, const uint64_t* d_tra
   P->loaded = true;
   return SBN_OK;
 }
-// ---- on-device witness generation (kernels_tracegen.cuh) ----------------------------------------------------------
-// Scratch lives in the (not yet used) LDE buffer; the only host traffic is the instance list in (20 KB) and the
-// instance outputs + error word back (8 KB).
-// the u16 range-check kernel keeps 156 KB in LDS (> the 64 KiB default); idempotent, see ntt_fast_setup
-static int range_check_setup(int device) {
-  static std::atomic<bool> done[SBN_MAX_DEVICES];
-  const int d = device >= 0 && device < SBN_MAX_DEVICES ? device : 0;
-  if (!done[d].load()) {
-    HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_LDS_BYTES));
-    HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_LDS_BYTES));
-    done[d].store(true);
-  }
-  return 0;
-}
-// One step of the curve chains as levels of independent micro-operations for tg::chain_coop_kernel: the formulas of
-// bnw::jac_double / bnw::jac_add (bn254w.cuh) written once over builder values, Fq2 products expanded into four Fq products,
-// every value in a fresh slot (no hazards), level = 1 + the deepest operand.  Program 0: a <- 2a (exponent bit clear);
-// program 1: b <- b + a, a <- 2a.  Persistent slots: a.X a.Y a.Z b.X b.Y b.Z, E each, in that order from slot 0.
-struct ChainProgram {
-  std::vector<uint32_t> ops[2];
-  int levels[2] = {0, 0};
-  int slots = 0;
-};
-static ChainProgram build_chain_program(int E) {
-  struct Op { int kind, d, a, b, level; };
-  struct Val { int s[2]; };
-  ChainProgram out;
-  for (int bit = 0; bit < 2; bit++) {
-    std::vector<int> lvl;
-    std::vector<Op> ops;
-    auto fresh = [&](int level) { lvl.push_back(level); return (int)lvl.size() - 1; };
-    auto emit = [&](int kind, int a, int b) { const int L = 1 + std::max(lvl[a], lvl[b]); const int d = fresh(L); ops.push_back({kind, d, a, b, L}); return d; };
-    auto add = [&](Val x, Val y) { Val r{}; for (int q = 0; q < E; q++) r.s[q] = emit(tg::CP_ADD, x.s[q], y.s[q]); return r; };
-    auto sub = [&](Val x, Val y) { Val r{}; for (int q = 0; q < E; q++) r.s[q] = emit(tg::CP_SUB, x.s[q], y.s[q]); return r; };
-    auto mul = [&](Val x, Val y) {
-      Val r{};
-      if (E == 1) { r.s[0] = emit(tg::CP_MUL, x.s[0], y.s[0]); return r; }
-      const int t0 = emit(tg::CP_MUL, x.s[0], y.s[0]), t1 = emit(tg::CP_MUL, x.s[1], y.s[1]);
-      const int t2 = emit(tg::CP_MUL, x.s[0], y.s[1]), t3 = emit(tg::CP_MUL, x.s[1], y.s[0]);
-      r.s[0] = emit(tg::CP_SUB, t0, t1); r.s[1] = emit(tg::CP_ADD, t2, t3);   // Fq2 = Fq[i] / (i^2 + 1), cmul of bn254w.cuh
-      return r;
-    };
-    auto chk_zero = [&](Val x) {   // czero: every component zero -> TG_ERR_DEGENERATE
-      const int a = x.s[0], b = E == 2 ? x.s[1] : x.s[0];
-      ops.push_back({E == 2 ? tg::CP_CHK2 : tg::CP_CHK1, 0, a, b, 1 + std::max(lvl[a], lvl[b])});
-    };
-    Val pa[3], pb[3];                                           // persistent a, b: slots 0 .. 6E-1, level 0
-    for (int c = 0; c < 3; c++) for (int q = 0; q < E; q++) pa[c].s[q] = fresh(0);
-    for (int c = 0; c < 3; c++) for (int q = 0; q < E; q++) pb[c].s[q] = fresh(0);
-    Val nb[3] = {pb[0], pb[1], pb[2]};
-    if (bit) {   // b + a: add-2007-bl, p = b, q = a (exp_chains: b = jac_add(b, a))
-      const Val Z1Z1 = mul(pb[2], pb[2]), Z2Z2 = mul(pa[2], pa[2]);
-      const Val U1 = mul(pb[0], Z2Z2), U2 = mul(pa[0], Z1Z1);
-      const Val S1 = mul(mul(pb[1], pa[2]), Z2Z2), S2 = mul(mul(pa[1], pb[2]), Z1Z1);
-      const Val H = sub(U2, U1);
-      chk_zero(H);
-      const Val H2 = add(H, H), I = mul(H2, H2), J = mul(H, I);
-      const Val rr0 = sub(S2, S1), r = add(rr0, rr0);
-      const Val V = mul(U1, I);
-      nb[0] = sub(sub(mul(r, r), J), add(V, V));
-      const Val sj = mul(S1, J);
-      nb[1] = sub(mul(r, sub(V, nb[0])), add(sj, sj));
-      const Val zs = add(pb[2], pa[2]);
-      nb[2] = mul(sub(sub(mul(zs, zs), Z1Z1), Z2Z2), H);
-    }
-    chk_zero(pa[1]);   // exp_chains: czero(a.Y) before every doubling
-    Val na[3];
-    {   // 2a: dbl-2009-l
-      const Val A = mul(pa[0], pa[0]), B = mul(pa[1], pa[1]), C = mul(B, B);
-      const Val t0 = add(pa[0], B), t1 = mul(t0, t0), t2 = sub(sub(t1, A), C);
-      const Val D = add(t2, t2), Ee = add(add(A, A), A), F = mul(Ee, Ee);
-      na[0] = sub(F, add(D, D));
-      const Val C2 = add(C, C), C4 = add(C2, C2), C8 = add(C4, C4);
-      na[1] = sub(mul(Ee, sub(D, na[0])), C8);
-      const Val yz = mul(pa[1], pa[2]);
-      na[2] = add(yz, yz);
-    }
-    int top = 0;
-    for (const Op& o : ops) top = std::max(top, o.level);
-    for (int c = 0; c < 3; c++) for (int q = 0; q < E; q++) {   // the new points replace the old ones after every read
-      ops.push_back({tg::CP_COPY, pa[c].s[q], na[c].s[q], na[c].s[q], top + 1});
-      if (bit) ops.push_back({tg::CP_COPY, pb[c].s[q], nb[c].s[q], nb[c].s[q], top + 1});
-    }
-    const int nl = top + 1;
-    out.levels[bit] = nl;
-    out.slots = std::max(out.slots, (int)lvl.size());
-    out.ops[bit].assign((size_t)nl * tg::CP_LANES, 0u);
-    std::vector<int> fill(nl, 0);
-    for (const Op& o : ops) {
-      const int L = o.level - 1;
-      if (fill[L] >= tg::CP_LANES || (int)lvl.size() > tg::CP_MAX_SLOTS) { out.levels[0] = out.levels[1] = -1; return out; }   // (cannot happen for E <= 2: checked by the caller)
-      out.ops[bit][(size_t)L * tg::CP_LANES + fill[L]++] = (uint32_t)o.kind | ((uint32_t)o.d << 8) | ((uint32_t)o.a << 16) | ((uint32_t)o.b << 24);
-    }
-  }
-  return out;
-}
-
-template <int E>
-static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
-  const size_t n = P->n;
-  const size_t IOW = 8 * (4 * E + 1);  // u32 words per instance: x and offset (2E Fq each) + exp_val
-  for (size_t k = 0; k < K; k++)
-    for (int v = 0; v < 4 * E; v++) {
-      u64 t[4]; for (int i = 0; i < 4; i++) t[i] = (u64)ios[IOW * k + 8 * v + 2 * i] | ((u64)ios[IOW * k + 8 * v + 2 * i + 1] << 32);
-      if (bnw::geq_p(t)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (instance %zu)", k);
-    }
-  HIPC(hipSetDevice(P->device));
-  hipStream_t st = P->stream;
-  const ExpShape sh = exp_shape(P->air);
-  // carve the scratch
-  u64* const wbase = P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde;   // scratch: the LDE buffer, not yet in use
-  u64* w = wbase;
-  auto take = [&](size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; };
-  const size_t cw = 257 * 12 * E * K;  // one Jacobian chain of every instance
-  u64* ja = take(cw); u64* jb = take(cw);
-  u64* sv = take(28 * E * n);       u64* inv = take(n);
-  u64* d_out = take(16 * E * K);
-  unsigned char* row_op = (unsigned char*)take(n / 8 + 1);
-  uint32_t* d_ios = (uint32_t*)take(IOW * K / 2 + 1);
-  uint32_t* d_prog[2] = {(uint32_t*)take(64 * tg::CP_LANES / 2), (uint32_t*)take(64 * tg::CP_LANES / 2)};   // chain programs: <= 64 levels of 64 micro-operations
-  int* d_err = (int*)take(1);
-  unsigned int* d_cnt = n > 65536 ? (unsigned int*)take((size_t)sh.num_rc * 32768) : nullptr;   // u32 histograms of the range-checked columns
-  if ((size_t)(w - wbase) > P->lde_scratch_words) return fail(SBN_ERR_UNSUPPORTED, "scratch does not fit");
-  if (int rc = range_check_setup(P->device)) return rc;
-
-  const bool timing = P->set.trace_timing;
-  hipEvent_t e0 = P->abs_ev[0], e1 = P->abs_ev[1];
-  std::vector<hipEvent_t> kev;
-  auto mark = [&]() { if (timing) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess && hipEventRecord(e, st) == hipSuccess) kev.push_back(e); } };
-  // pinned staging (a copy from / to pageable memory blocks the calling thread inside the runtime, once per copy)
-  const size_t io_words = (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
-  if (P->h_io_words < io_words + out_words) {
-    if (P->h_io) (void)hipHostFree(P->h_io);
-    P->h_io = nullptr; P->h_io_words = 0;
-    HIPC(hipHostMalloc((void**)&P->h_io, (io_words + out_words) * sizeof(u64), hipHostMallocDefault));
-    P->h_io_words = io_words + out_words;
-  }
-  memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
-  u64* const h_out = P->h_io + io_words;
-  HIPC(hipEventRecord(e0, st));
-  HIPC(hipMemcpyAsync(d_ios, P->h_io, IOW * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
-  auto blocks = [](size_t k, unsigned b) { return dim3((unsigned)((k + b - 1) / b)); };
-  mark();
-  hipLaunchKernelGGL(tg::flags_kernel, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
-  hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
-  hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, (u64)65535, P->d_trace);
-  hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
-  mark();
-  // the two 256-step curve chains per instance: host threads while the device writes the input-independent columns
-  // chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx picks by the host pool's size): 2 = one wave per instance walking levels of
-  // independent Fq operations (tg::chain_coop_kernel), 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host threads +
-  // pinned upload
-  if (P->chain_mode == 2) {
-    static const ChainProgram prog = build_chain_program(E);
-    if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
-    tg::ChainProgDev cp{};
-    for (int b = 0; b < 2; b++) {
-      HIPC(hipMemcpyAsync(d_prog[b], prog.ops[b].data(), prog.ops[b].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      cp.ops[b] = d_prog[b]; cp.levels[b] = prog.levels[b];
-    }
-    for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) cp.in_slot[v * E + q] = (unsigned char)((v < 2 ? v : v + 1) * E + q);   // a.X a.Y | b.X b.Y
-    cp.one_slot[0] = (unsigned char)(2 * E); cp.one_slot[1] = (unsigned char)(5 * E);
-    cp.zero_slot[0] = (unsigned char)(2 * E + 1); cp.zero_slot[1] = (unsigned char)(5 * E + 1);
-    for (int i = 0; i < 6 * E; i++) cp.coord[i] = (unsigned char)i;
-    hipLaunchKernelGGL(tg::chain_coop_kernel<E>, dim3((unsigned)K), dim3(tg::CP_LANES), 0, st, d_ios, K, ja, jb, d_err, cp);
-  } else if (P->chain_mode == 1) hipLaunchKernelGGL(tg::chain_kernel<E>, blocks(K, 64), dim3(64), 0, st, d_ios, K, ja, jb, d_err);
-  else {
-    if (P->h_chain_words < 2 * cw) {
-      if (P->h_chain) (void)hipHostFree(P->h_chain);
-      P->h_chain = nullptr; P->h_chain_words = 0;
-      HIPC(hipHostMalloc((void**)&P->h_chain, 2 * cw * sizeof(u64), hipHostMallocDefault));
-      P->h_chain_words = 2 * cw;
-    }
-    if (tracegen_host_chains(E, ios, K, P->h_chain, P->h_chain + cw)) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
-    HIPC(hipMemcpyAsync(ja, P->h_chain, cw * sizeof(u64), hipMemcpyHostToDevice, st));
-    HIPC(hipMemcpyAsync(jb, P->h_chain + cw, cw * sizeof(u64), hipMemcpyHostToDevice, st));
-  }
-  mark();
-  hipLaunchKernelGGL(tg::affine_lambda_kernel<E>, blocks((n + tg::TG_ROWS - 1) / tg::TG_ROWS, 64), dim3(64), 0, st, d_ios, K, ja, jb, n, sv, row_op, d_out, d_err);
-  mark();
-  hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, sh.gadget_col, P->d_trace, d_err);
-  mark();
-  if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
-    HIPC(hipMemsetAsync(d_cnt, 0, (size_t)sh.num_rc * 65536 * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(tg::range_count_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, d_cnt, d_err);
-    hipLaunchKernelGGL(tg::range_check_kernel<true>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
-  } else {
-    hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, (const unsigned int*)nullptr, P->set.range_check);
-  }
-  mark();
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(h_out, d_out, 16 * E * K * sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(h_out + 16 * E * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPC(hipEventRecord(e1, st));
-  HIPC(hipStreamSynchronize(st));
-  const u64* out = h_out;
-  const int err = (int)(h_out[16 * E * K] & 0xffffffffu);
-  float ms = 0; HIPC(hipEventElapsedTime(&ms, e0, e1));
-  P->stage_ms[ST_COUNT + EX_TRACEGEN_MS] = ms;
-  if (timing) {
-    static const char* names[] = {"flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
-    for (size_t i = 0; i + 1 < kev.size(); i++) { float t = 0; (void)hipEventElapsedTime(&t, kev[i], kev[i + 1]); fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", names[i], t); }
-    for (auto e : kev) (void)hipEventDestroy(e);
-    fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", "total", ms);
-  }
-  if (err & tg::TG_ERR_DEGENERATE) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
-  if (err & tg::TG_ERR_WITNESS) return fail(SBN_ERR_WITNESS, "modular witness generation failed");
-  if (err & tg::TG_ERR_RANGE) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
-  // public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156)
-  P->pi.resize(P->air.npi);
-  for (size_t k = 0; k < K; k++) {
-    u64* p = P->pi.data() + (size_t)sh.pi_per_io * k;
-    for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
-    for (int i = 0; i < 16 * E; i++) p[IOW + i] = out[16 * E * k + i];
-  }
-  if (pi_out) memcpy(pi_out, P->pi.data(), P->pi.size() * sizeof(u64));
-  P->loaded = true;
-  return SBN_OK;
-}
-
-// Fq12ExpStark: the square-and-multiply chains (no inversion anywhere) on host threads in standard form, then one lane
-// per row for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
-static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
-  const bool u64e = P->air.kind == SBN_AIR_FQ12_EXP_U64;        // 128-row instances, one-element exponent
-  const size_t n = P->n, IOW = u64e ? 194 : 200;
-  const int steps = u64e ? 64 : 256, log_rpb = u64e ? 7 : 9;
-  for (size_t k = 0; k < K; k++)
-    for (int v = 0; v < 24; v++) {
-      u64 t[4]; for (int i = 0; i < 4; i++) t[i] = (u64)ios[IOW * k + 8 * v + 2 * i] | ((u64)ios[IOW * k + 8 * v + 2 * i + 1] << 32);
-      if (bnw::geq_p(t)) return fail(SBN_ERR_BAD_ARG, "coefficient >= p (instance %zu)", k);
-    }
-  HIPC(hipSetDevice(P->device));
-  hipStream_t st = P->stream;
-  const ExpShape sh = exp_shape(P->air);
-  u64* const wbase = P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde;   // scratch: the LDE buffer, not yet in use
-  u64* w = wbase;
-  auto take = [&](size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; };
-  if (u64e)
-    for (size_t k = 0; k < K; k++)
-      if (((u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32)) >= GLP) return fail(SBN_ERR_NON_CANONICAL, "exponent of instance %zu is not a canonical field element", k);
-  const size_t cw = (size_t)(steps + 1) * 48 * K;  // one chain of every instance, standard form
-  u64* ca = take(cw); u64* cb = take(cw);
-  u64* inv = take(n);
-  u64* d_outs = take(K * 48);
-  uint32_t* d_ios = (uint32_t*)take(IOW * K / 2 + 1);
-  int* d_err = (int*)take(1);
-  if ((size_t)(w - wbase) > P->lde_scratch_words) return fail(SBN_ERR_UNSUPPORTED, "scratch does not fit");
-
-  const bool timing = P->set.trace_timing;
-  hipEvent_t e0 = P->abs_ev[0], e1 = P->abs_ev[1];
-  std::vector<hipEvent_t> kev;
-  auto mark = [&]() { if (timing) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess && hipEventRecord(e, st) == hipSuccess) kev.push_back(e); } };
-  HIPC(hipEventRecord(e0, st));
-  HIPC(hipMemcpyAsync(d_ios, ios, IOW * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
-  auto blocks = [](size_t k, unsigned b) { return dim3((unsigned)((k + b - 1) / b)); };
-  mark();
-  if (u64e) hipLaunchKernelGGL(tg::flags_u64_kernel, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
-  else hipLaunchKernelGGL(tg::flags_kernel, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
-  hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
-  hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, (u64)255, P->d_trace);
-  hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
-  mark();
-  // the square-and-multiply chains: one workgroup per instance on the device (kernels_tracegen.cuh fq12_chain_kernel);
-  // SBN_FQ12_HOST_CHAIN=1: the library's host threads + a pinned upload, as in round 2 (A/B)
-  const bool host_chain = P->set.fq12_host_chain;
-  if (host_chain) {
-    if (P->h_chain_words < 2 * cw) {
-      if (P->h_chain) (void)hipHostFree(P->h_chain);
-      P->h_chain = nullptr; P->h_chain_words = 0;
-      HIPC(hipHostMalloc((void**)&P->h_chain, 2 * cw * sizeof(u64), hipHostMallocDefault));
-      P->h_chain_words = 2 * cw;
-    }
-    tracegen_host_chains_fq12(ios, IOW, steps, K, P->h_chain, P->h_chain + cw);
-    HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
-  } else hipLaunchKernelGGL(tg::fq12_chain_kernel, dim3((unsigned)K), dim3(320), 0, st, d_ios, IOW, steps, ca, cb, d_outs);
-  mark();
-  // one lane per (row, output coefficient) by default; SBN_FQ12_ROW_KERNEL=1: round 2's one lane per row (A/B)
-  const bool row_kernel = P->set.fq12_row_kernel;
-  if (row_kernel) hipLaunchKernelGGL(tg::fq12_row_kernel, blocks(n, 64), dim3(64), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
-  else hipLaunchKernelGGL(tg::fq12_gadget_kernel, blocks(12 * n, 256), dim3(256), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
-  mark();
-  hipLaunchKernelGGL(tg::split_range_check_kernel, dim3((unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err);
-  mark();
-  HIPC(hipGetLastError());
-  int err = 0;
-  HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  std::vector<u64> chain_out;                 // B[steps] of every instance (the outputs among the public inputs) when the chains ran on the device
-  if (!host_chain) {
-    chain_out.resize(K * 48);
-    HIPC(hipMemcpyAsync(chain_out.data(), d_outs, K * 48 * sizeof(u64), hipMemcpyDeviceToHost, st));
-  }
-  HIPC(hipEventRecord(e1, st));
-  HIPC(hipStreamSynchronize(st));
-  float ms = 0; HIPC(hipEventElapsedTime(&ms, e0, e1));
-  P->stage_ms[ST_COUNT + EX_TRACEGEN_MS] = ms;
-  if (timing) {
-    static const char* names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
-    for (size_t i = 0; i + 1 < kev.size(); i++) { float t = 0; (void)hipEventElapsedTime(&t, kev[i], kev[i + 1]); fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", names[i], t); }
-    for (auto e : kev) (void)hipEventDestroy(e);
-    fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", "total", ms);
-  }
-  if (err & tg::TG_ERR_WITNESS) return fail(SBN_ERR_WITNESS, "modular witness generation failed");
-  if (err & tg::TG_ERR_RANGE) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
-  // public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117)
-  P->pi.resize(P->air.npi);
-  for (size_t k = 0; k < K; k++) {
-    u64* p = P->pi.data() + (size_t)sh.pi_per_io * k;
-    for (int c = 0; c < 24; c++)
-      for (int i = 0; i < 16; i++) p[16 * c + i] = (ios[IOW * k + 8 * c + (i >> 1)] >> (16 * (i & 1))) & 0xffff;
-    if (u64e) p[384] = (u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32);
-    else for (int i = 0; i < 8; i++) p[384 + i] = ios[IOW * k + 192 + i];
-    const u64* out = host_chain ? P->h_chain + cw + ((k * (steps + 1) + steps) * 12) * 4 : chain_out.data() + k * 48;  // B[steps]
-    const int ob = 384 + sh.n_exp_slots;
-    for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
-  }
-  if (pi_out) memcpy(pi_out, P->pi.data(), P->pi.size() * sizeof(u64));
-  P->loaded = true;
-  return SBN_OK;
-}
-
-// FqExpStark: chains on host threads (512 Montgomery products per instance), rows and the u16 range check on the device.
-static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
-  const size_t n = P->n, IOW = 24;
-  for (size_t k = 0; k < K; k++)
-    for (int v = 0; v < 2; v++) {
-      u64 t[4]; for (int i = 0; i < 4; i++) t[i] = (u64)ios[IOW * k + 8 * v + 2 * i] | ((u64)ios[IOW * k + 8 * v + 2 * i + 1] << 32);
-      if (bnw::geq_p(t)) return fail(SBN_ERR_BAD_ARG, "value >= p (instance %zu)", k);
-    }
-  HIPC(hipSetDevice(P->device));
-  hipStream_t st = P->stream;
-  const ExpShape sh = exp_shape(P->air);
-  u64* const wbase = P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde;   // scratch: the LDE buffer, not yet in use
-  u64* w = wbase;
-  auto take = [&](size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; };
-  const size_t cw = 257 * 4 * K;
-  u64* ca = take(cw); u64* cb = take(cw);
-  u64* inv = take(n);
-  uint32_t* d_ios = (uint32_t*)take(IOW * K / 2 + 1);
-  int* d_err = (int*)take(1);
-  unsigned int* d_cnt = n > 65536 ? (unsigned int*)take((size_t)sh.num_rc * 32768) : nullptr;   // u32 histograms of the range-checked columns
-  if ((size_t)(w - wbase) > P->lde_scratch_words) return fail(SBN_ERR_UNSUPPORTED, "scratch does not fit");
-  if (int rc = range_check_setup(P->device)) return rc;
-  hipEvent_t e0 = P->abs_ev[0], e1 = P->abs_ev[1];
-  HIPC(hipEventRecord(e0, st));
-  HIPC(hipMemcpyAsync(d_ios, ios, IOW * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
-  auto blocks = [](size_t k, unsigned b) { return dim3((unsigned)((k + b - 1) / b)); };
-  hipLaunchKernelGGL(tg::flags_kernel, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
-  hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
-  hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, (u64)65535, P->d_trace);
-  hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
-  if (P->h_chain_words < 2 * cw) {
-    if (P->h_chain) (void)hipHostFree(P->h_chain);
-    P->h_chain = nullptr; P->h_chain_words = 0;
-    HIPC(hipHostMalloc((void**)&P->h_chain, 2 * cw * sizeof(u64), hipHostMallocDefault));
-    P->h_chain_words = 2 * cw;
-  }
-  tracegen_host_chains_fq(ios, K, P->h_chain, P->h_chain + cw);
-  HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
-  hipLaunchKernelGGL(tg::fq_row_kernel, blocks(n, 128), dim3(128), 0, st, d_ios, ca, cb, n, P->d_trace, d_err);
-  if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
-    HIPC(hipMemsetAsync(d_cnt, 0, (size_t)sh.num_rc * 65536 * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(tg::range_count_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, d_cnt, d_err);
-    hipLaunchKernelGGL(tg::range_check_kernel<true>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
-  } else {
-    hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, (const unsigned int*)nullptr, P->set.range_check);
-  }
-  HIPC(hipGetLastError());
-  int err = 0;
-  HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPC(hipEventRecord(e1, st));
-  HIPC(hipStreamSynchronize(st));
-  float ms = 0; HIPC(hipEventElapsedTime(&ms, e0, e1));
-  P->stage_ms[ST_COUNT + EX_TRACEGEN_MS] = ms;
-  if (err & tg::TG_ERR_WITNESS) return fail(SBN_ERR_WITNESS, "modular witness generation failed");
-  if (err & tg::TG_ERR_RANGE) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
-  // public inputs: x, offset, exp_val, output = b at the last row, as u32 limbs (fq/exp.rs:98-108)
-  P->pi.resize(P->air.npi);
-  for (size_t k = 0; k < K; k++) {
-    u64* p = P->pi.data() + (size_t)sh.pi_per_io * k;
-    for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
-    const u64* out = P->h_chain + cw + (k * 257 + 256) * 4;  // B[256]
-    for (int i = 0; i < 8; i++) p[24 + i] = (out[i >> 1] >> (32 * (i & 1))) & 0xffffffffULL;
-  }
-  if (pi_out) memcpy(pi_out, P->pi.data(), P->pi.size() * sizeof(u64));
-  P->loaded = true;
-  return SBN_OK;
-}
-
-extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
-  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->loaded = false;   // before any check: a refused instance list must not leave the previous trace provable
-  if (!ios) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (!is_exp_air(P->air.kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
-  if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
-  if (P->n != exp_rows_per_instance(P->air.kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  if (P->air.kind == SBN_AIR_FQ12_EXP || P->air.kind == SBN_AIR_FQ12_EXP_U64) return generate_trace_device_fq12(P, ios, num_io, pi_out);
-  if (P->n < 65536 || P->n > 262144) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
-  if (P->air.kind == SBN_AIR_FQ_EXP) return generate_trace_device_fq(P, ios, num_io, pi_out);
-  return P->air.kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, ios, num_io, pi_out) : generate_trace_device<2>(P, ios, num_io, pi_out);
-}
 
 extern "C" int sbn_prover_read_trace(sbn_prover* P, uint64_t* out) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
@@ -1372,9 +841,8 @@ template <int KIND>
 static void launch_quotient_kind(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
   const dim3 g1((unsigned)qblocks, 1), g2((unsigned)qblocks, 2);
   if (qp.seg_mask & 12u) hipLaunchKernelGGL((quotient_kernel<KIND, 2>), g2, dim3(256), 0, P->hstream, qp, qp.apow[0], qp.apow[1], qp.pic);
-  const auto tail = quotient_kernel<KIND, 1>;   // (named before PART 0: the order of first use is the kernels' order in the code object)
   if (qp.seg_mask & 1u) hipLaunchKernelGGL((quotient_kernel<KIND, 0>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
-  if (qp.seg_mask & 2u) hipLaunchKernelGGL(tail, g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
+  if (qp.seg_mask & 2u) hipLaunchKernelGGL((quotient_kernel<KIND, 1>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
 }
 static int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
   switch (P->air.kind) {
@@ -1910,9 +1378,7 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
   sbn_prover P{};
   sbn_standard_fast_config(&P.cfg); P.cfg.cap_height = cap_height;
   P.degree_bits = lg; P.lde_log = lg + 1; P.n = n; P.m = 2 * n; P.ntt_chunk = 64; P.device = g_device;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
-  HIPC(hipSetDevice(g_device));
+  if (int rc = use_current_device("no CPU fallback")) return rc;
   { int rc0 = ntt_fast_setup(); if (rc0) return rc0; }
   { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
   ntt_plan(&P);   // the transform kernels the prover picks at this size
@@ -1956,9 +1422,7 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
 
 extern "C" int sbn_poseidon_permute_batch(uint64_t* states, size_t count) {
   if (!states) return fail(SBN_ERR_BAD_ARG, "null argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
-  HIPC(hipSetDevice(g_device));
+  if (int rc = use_current_device("no CPU fallback")) return rc;
   for (size_t i = 0; i < count * 12; i++) if (states[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "state word %zu is not canonical", i);
   u64* d = nullptr;
   HIPC(hipMalloc((void**)&d, count * 12 * sizeof(u64)));
@@ -1971,9 +1435,7 @@ extern "C" int sbn_poseidon_permute_batch(uint64_t* states, size_t count) {
 
 extern "C" int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int mode) {
   if (!a || !b || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
-  HIPC(hipSetDevice(g_device));
+  if (int rc = use_current_device("no CPU fallback")) return rc;
   if (count == 0) return SBN_OK;
   u64* d = nullptr;
   HIPC(hipMalloc((void**)&d, 3 * count * sizeof(u64)));
@@ -1988,41 +1450,6 @@ extern "C" int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_
   return SBN_OK;
 }
 
-extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
-  using namespace tg;
-  if (op < FQB_MUL || op > FQB_FQ2_INV) return fail(SBN_ERR_BAD_ARG, "unknown op %d", op);
-  const bool binary = op == FQB_MUL || op == FQB_ADD || op == FQB_SUB || op == FQB_FQ2_INV;
-  if (!a || !out || (binary && !b)) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (op == FQB_BATCH_INV && count % TG_INV_BATCH) return fail(SBN_ERR_BAD_ARG, "batch inverse needs a multiple of %d values", TG_INV_BATCH);
-  for (size_t i = 0; i < count; i++) {
-    if (bnw::geq_p(a + 4 * i) || (binary && bnw::geq_p(b + 4 * i))) return fail(SBN_ERR_NON_CANONICAL, "element %zu is not below p", i);
-    const bool za = !(a[4 * i] | a[4 * i + 1] | a[4 * i + 2] | a[4 * i + 3]);
-    const bool zb = !binary || !(b[4 * i] | b[4 * i + 1] | b[4 * i + 2] | b[4 * i + 3]);
-    if ((op == FQB_INV || op == FQB_BATCH_INV) && za) return fail(SBN_ERR_BAD_ARG, "element %zu is zero: no inverse", i);
-    if (op == FQB_FQ2_INV && za && zb) return fail(SBN_ERR_BAD_ARG, "element %zu is zero: no inverse", i);
-  }
-  const size_t items = op == FQB_BATCH_INV ? count / TG_INV_BATCH : count, out_words = 4 * count * (op == FQB_FQ2_INV ? 2 : 1);
-  if (!on_device) {
-    for (size_t i = 0; i < items; i++) fq_batch_item(op, a, b, out, i);
-    return SBN_OK;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
-  HIPC(hipSetDevice(g_device));
-  if (count == 0) return SBN_OK;
-  u64* d = nullptr;
-  HIPC(hipMalloc((void**)&d, (8 * count + out_words) * sizeof(u64)));
-  hipError_t e = hipMemcpy(d, a, 4 * count * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess && binary) e = hipMemcpy(d + 4 * count, b, 4 * count * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(fq_batch_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, 0, op, d, d + 4 * count, d + 8 * count, items);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out, d + 8 * count, out_words * sizeof(u64), hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_bn254_fq_batch: %s", hipGetErrorString(e));
-  return SBN_OK;
-}
 
 // Index of the first word >= p, or `count`: the scan of sbn_prover_prove_host_trace as a building block (host in, host out).
 extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out) {
@@ -2032,9 +1459,7 @@ extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int 
     for (size_t i = 0; i < count; i++) if (words[i] >= GLP) { *index_out = i; break; }
     return SBN_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SBN_ERR_NO_DEVICE, "no HIP device available: no CPU fallback");
-  HIPC(hipSetDevice(g_device));
+  if (int rc = use_current_device("no CPU fallback")) return rc;
   if (count == 0) return SBN_OK;
   // the device copy keeps the caller's offset from a 16-byte boundary, so the kernel's unaligned head is reachable from a test
   const size_t off = ((size_t)words & 8) ? 1 : 0;

@@ -1,0 +1,140 @@
+// The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip and by
+// tracegen_device.hip (which fills the trace); every other unit reaches the prover through the C ABI of include/sbn.h.
+#pragma once
+#include "host_common.hpp"
+#include "settings.hpp"
+#include <algorithm>
+
+using namespace sbn;
+struct PairCols;   // kernels.cuh
+
+#define HIPC(expr)                                                                                   \
+  do {                                                                                               \
+    hipError_t e_ = (expr);                                                                          \
+    if (e_ != hipSuccess) return fail(SBN_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+// Stage k spans [ev[k], ev[k+1]) on the prover's main stream.  The commit stages overlap NTT (main
+// stream) with sponge absorption (hash stream); the absorption kernels are additionally timed one by
+// one with events on the hash stream (EXTRA_* entries = sum over the chunk launches of one proof).
+enum Stage {
+  ST_TRACE_COMMIT, ST_PERM_Z, ST_Z_COMMIT, ST_QUOTIENT_EVAL, ST_QUOTIENT_COMMIT,
+  ST_OPENINGS, ST_FRI_COMBINE, ST_FRI_LAYERS, ST_POW, ST_QUERIES, ST_COUNT
+};
+enum Extra { EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, EX_TRACEGEN_MS, EX_COMM_MS, EX_COUNT };
+static constexpr int MAX_CHUNKS = 512;
+// prove_host_trace: the pinned staging ring of one prover, 4 slots of 16 MiB = 64 MiB of pinned host memory at most, allocated on
+// the first call.  A piece of the trace never spans two column chunks; a chunk larger than a slot crosses in several pieces.
+static constexpr int UPLOAD_SLOTS = 4;
+static constexpr size_t UPLOAD_SLOT_WORDS = (size_t)2 << 20;
+// Function attributes are per DEVICE: one flag per device of the process (sbn_set_device may select another GPU later).
+static constexpr int SBN_MAX_DEVICES = 64;
+
+struct DevTree {  // Merkle digests, levels concatenated (leaf level first)
+  u64* d = nullptr; size_t nleaf = 0; u32 nlevels = 0;  // nlevels = number of levels BELOW the cap
+  u64* level(u32 l) const { return d + (2 * nleaf - ((2 * nleaf) >> l)) * 4; }
+};
+
+// Oversized-trace split (include/sbn.h, sbn_split_prover_*): this rank's share of one proof.
+// The columns of a matrix are dealt to the ranks in blocks of `ob` columns, round-robin: rank r owns the blocks
+// b = r, r + R, r + 2R, ... and keeps them compactly (own block k = global block k * R + r at local columns k * ob ...);
+// only the globally last block can be short, and it is the last own block of its owner.  In step k of a commitment every
+// rank transforms its own block k, the all-to-all of that step moves the blocks k * R .. k * R + R - 1 to their row
+// owners, and the leaf sponge -- sequential over the columns of a row -- absorbs exactly those blocks next.
+struct ColShare {
+  size_t total = 0, ob = 64; u32 R = 1, rank = 0;
+  size_t nblocks() const { return (total + ob - 1) / ob; }
+  size_t steps() const { return (nblocks() + R - 1) / R; }
+  size_t block_cols(size_t b) const { return b < nblocks() ? std::min(ob, total - b * ob) : 0; }
+  size_t own_cols(u32 r) const { size_t s = 0; for (size_t b = r; b < nblocks(); b += R) s += block_cols(b); return s; }
+  size_t own() const { return own_cols(rank); }
+  size_t max_own() const { size_t s = 0; for (u32 r = 0; r < R; r++) s = std::max(s, own_cols(r)); return s; }
+  size_t global_col(u32 r, size_t local) const { return ((local / ob) * R + r) * ob + local % ob; }   // of rank r's local column
+};
+struct SplitCtx {
+  sbn_comm comm;
+  u32 log_r = 0, rho = 0;                 // world = 2^log_r; this rank owns the LDE rows i = j * world + rho
+  size_t ml = 0;                          // local LDE rows = m >> log_r
+  ColShare cs, zs;                        // trace / Z columns of this rank
+  size_t cr = 0, zr = 0;                  // = cs.own(), zs.own()
+  u32 planes = 1;                         // 2 from four ranks up: the rows i + 2 of the local rows arrive as a second plane
+  u64 *lde_l = nullptr, *lde_n = nullptr, *zlde_l = nullptr, *zlde_n = nullptr, *scratch = nullptr;   // views of comm.recv_buf
+  size_t scratch_words = 0;
+  size_t slot_words = 0;                  // one send slot = [plane][dest][ob][ml]; two slots, used alternately by the steps
+  u64* d_ldechunk = nullptr;              // [ntt_chunk][m]: one column block of this rank's LDE before it is packed
+  u32* d_idx_local = nullptr;             // query leaf indices inside this rank's subtrees
+  PairCols* d_pairs_own = nullptr;        // permutation pairs of the own Z columns, local order
+  hipStream_t cstream = nullptr;          // the exchanges of the commit pipeline
+  hipEvent_t xchg_done[MAX_CHUNKS];       // comm stream: the blocks of step k have arrived (and send slot k & 1 is free again)
+  std::vector<hipEvent_t> tev;            // timing events around the exchanges (pairs), consumed in order
+  size_t tev_used = 0;
+};
+
+struct sbn_prover {
+  AirShape air; sbn_config cfg; FriShape fri;
+  SplitCtx* sp = nullptr;                 // null: the whole proof on this GPU
+  size_t lde_scratch_words = 0;           // capacity of d_lde as witness-generation scratch
+  u32 degree_bits, lde_log; size_t n, m;
+  int device; hipStream_t stream;
+  // matrices
+  u64 *d_trace = nullptr, *d_coef = nullptr, *d_lde = nullptr, *d_tmp = nullptr;
+  u64 *d_zval = nullptr, *d_zcoef = nullptr, *d_zlde = nullptr;
+  u64 *d_q = nullptr, *d_qlde = nullptr;
+  DevTree tree_t, tree_z, tree_q;
+  std::vector<DevTree> fri_trees;
+  // tables
+  u64 *d_tw_f = nullptr, *d_tw_i = nullptr, *d_shift = nullptr, *d_shift_inv = nullptr;
+  u64 *d_shift_odd = nullptr;   // 2^19-point LDE (1,024 x 512): 7^i w_1024^(i >> 9), the input scale of the odd half of its split first pass
+  u64 *d_xs = nullptr, *d_lag_first = nullptr, *d_lag_last = nullptr;
+  u64 *d_apow = nullptr;  // [2][apow_n]
+  size_t apow_n = 0;
+  void* d_pic = nullptr;  // ExpPiConsts<F>
+  PairCols* d_pairs = nullptr;
+  // openings / FRI
+  u64 *d_zpow = nullptr;        // 4 planes [n]: z^i (a,b), (g z)^i (a,b)
+  u64 *d_open = nullptr;        // [(ncols + nzs + 4)][4]
+  u64 *d_part = nullptr;        // 2 planes [groups][n]
+  u64 *d_w = nullptr;           // group weights
+  u64 *d_fa = nullptr, *d_fb = nullptr;    // F0 / F1 scratch planes [n] each (a,b) x2
+  u64 *d_fcoef = nullptr;       // final poly coefficient planes [2][m]
+  u64 *d_fcoef2 = nullptr;      // ping-pong for folding [2][m/2^arity]
+  std::vector<u64*> fri_vals;   // per layer value planes [2][size]
+  u64 *d_pow = nullptr;
+  u32 *d_idx = nullptr;
+  u64 *d_qbuf = nullptr; size_t qstride = 0;
+  std::vector<u64> pi;
+  bool loaded = false;
+  hipEvent_t ev[ST_COUNT + 1];
+  float stage_ms[ST_COUNT + EX_COUNT];
+  size_t ntt_chunk;
+  bool ntt_fused = false;                    // the inverse transform's pass B and the LDE's pass A as ONE kernel (2^16 / 2^17 rows)
+  u64* d_tmp2 = nullptr;                     // its output: the fused kernel cannot work in place
+  u64* d_tmp3 = nullptr;                     // 2^18 rows, two transform streams: the fused kernel's second output buffer (chunks alternate)
+  bool ntt_fused512 = false;                 // 2^18-row tables: kernels_ntt.cuh ntt_fused512_inv_b_lde_a_kernel
+  hipStream_t hstream = nullptr;             // sponge absorption / Merkle stream
+  hipStream_t nstream = nullptr;             // second transform stream (2^19 LDE rows and up): the LDE of chunk k beside the inverse transform of chunk k+1
+  hipEvent_t intt_done[MAX_CHUNKS];          // main -> second transform stream: the coefficients of chunk k are complete
+  bool ntt_two_streams = false;
+  Settings set;                              // the SBN_* switches this prover was created under (settings.hpp)
+  int chain_mode = 0;                        // curve witness: 0 host pool, 1 one lane per instance, 2 one wave per instance
+  hipEvent_t chunk_ready[MAX_CHUNKS];        // main -> hash: LDE chunk k is complete
+  hipEvent_t abs_ev[2 * MAX_CHUNKS];         // hash stream: before/after each absorb launch
+  hipEvent_t hash_done;                      // hash -> main
+  u64* d_sponge = nullptr;                   // [12][m] sponge state carried between column chunks
+  u64* h_chain = nullptr;                    // pinned staging for the host-computed curve chains (device tracegen)
+  size_t h_chain_words = 0;
+  u64* h_io = nullptr;                       // pinned staging of the device witness: the instance list in, the outputs + error word back
+  size_t h_io_words = 0;
+  u64* h_open = nullptr;                     // pinned landing buffer of the opened values [(ncols + nzs + 4)][4]
+  u64* h_open2 = nullptr;                    // second landing buffer: the values at g*zeta of the trace and Z columns (the host is still reading the first)
+  size_t dev_bytes = 0;                      // device memory this context allocated (what the one-shot cache of capi.hip counts)
+  // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
+  hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk
+  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned
+  hipEvent_t slot_copied[UPLOAD_SLOTS];      // copy stream: the copy out of ring slot s has completed
+  bool slot_used[UPLOAD_SLOTS] = {};
+  unsigned slot_next = 0;
+  u64* h_ring = nullptr;                     // [UPLOAD_SLOTS][UPLOAD_SLOT_WORDS], pinned
+  unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
+  unsigned long long* h_first_bad = nullptr; // its pinned landing word
+};

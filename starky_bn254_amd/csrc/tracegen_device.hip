@@ -1,0 +1,417 @@
+// On-device witness generation of the Exp tables (sbn_prover_generate_trace) and the parity hook of the BN254 field helpers
+// (sbn_bn254_fq_batch): the one unit that includes kernels_tracegen.cuh, whose kernels are ordinary external definitions.
+#include "prover_ctx.hpp"
+#include "kernels_tracegen.cuh"
+#include <atomic>
+#include <cstring>
+
+// Scratch lives in the (not yet used) LDE buffer; the only host traffic is the instance list in (20 KB) and the
+// instance outputs + error word back (8 KB).
+// the u16 range-check kernel keeps 156 KB in LDS (> the 64 KiB default); idempotent, see ntt_fast_setup (prover.hip)
+static int range_check_setup(int device) {
+  static std::atomic<bool> done[SBN_MAX_DEVICES];
+  const int d = device >= 0 && device < SBN_MAX_DEVICES ? device : 0;
+  if (!done[d].load()) {
+    HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_LDS_BYTES));
+    HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_LDS_BYTES));
+    done[d].store(true);
+  }
+  return 0;
+}
+// One step of the curve chains as levels of independent micro-operations for tg::chain_coop_kernel: the formulas of
+// bnw::jac_double / bnw::jac_add (bn254w.cuh) written once over builder values, Fq2 products expanded into four Fq products,
+// every value in a fresh slot (no hazards), level = 1 + the deepest operand.  Program 0: a <- 2a (exponent bit clear);
+// program 1: b <- b + a, a <- 2a.  Persistent slots: a.X a.Y a.Z b.X b.Y b.Z, E each, in that order from slot 0.
+struct ChainProgram {
+  std::vector<uint32_t> ops[2];
+  int levels[2] = {0, 0};
+  int slots = 0;
+};
+static ChainProgram build_chain_program(int E) {
+  struct Op { int kind, d, a, b, level; };
+  struct Val { int s[2]; };
+  ChainProgram out;
+  for (int bit = 0; bit < 2; bit++) {
+    std::vector<int> lvl;
+    std::vector<Op> ops;
+    auto fresh = [&](int level) { lvl.push_back(level); return (int)lvl.size() - 1; };
+    auto emit = [&](int kind, int a, int b) { const int L = 1 + std::max(lvl[a], lvl[b]); const int d = fresh(L); ops.push_back({kind, d, a, b, L}); return d; };
+    auto add = [&](Val x, Val y) { Val r{}; for (int q = 0; q < E; q++) r.s[q] = emit(tg::CP_ADD, x.s[q], y.s[q]); return r; };
+    auto sub = [&](Val x, Val y) { Val r{}; for (int q = 0; q < E; q++) r.s[q] = emit(tg::CP_SUB, x.s[q], y.s[q]); return r; };
+    auto mul = [&](Val x, Val y) {
+      Val r{};
+      if (E == 1) { r.s[0] = emit(tg::CP_MUL, x.s[0], y.s[0]); return r; }
+      const int t0 = emit(tg::CP_MUL, x.s[0], y.s[0]), t1 = emit(tg::CP_MUL, x.s[1], y.s[1]);
+      const int t2 = emit(tg::CP_MUL, x.s[0], y.s[1]), t3 = emit(tg::CP_MUL, x.s[1], y.s[0]);
+      r.s[0] = emit(tg::CP_SUB, t0, t1); r.s[1] = emit(tg::CP_ADD, t2, t3);   // Fq2 = Fq[i] / (i^2 + 1), cmul of bn254w.cuh
+      return r;
+    };
+    auto chk_zero = [&](Val x) {   // czero: every component zero -> TG_ERR_DEGENERATE
+      const int a = x.s[0], b = E == 2 ? x.s[1] : x.s[0];
+      ops.push_back({E == 2 ? tg::CP_CHK2 : tg::CP_CHK1, 0, a, b, 1 + std::max(lvl[a], lvl[b])});
+    };
+    Val pa[3], pb[3];                                           // persistent a, b: slots 0 .. 6E-1, level 0
+    for (int c = 0; c < 3; c++) for (int q = 0; q < E; q++) pa[c].s[q] = fresh(0);
+    for (int c = 0; c < 3; c++) for (int q = 0; q < E; q++) pb[c].s[q] = fresh(0);
+    Val nb[3] = {pb[0], pb[1], pb[2]};
+    if (bit) {   // b + a: add-2007-bl, p = b, q = a (exp_chains: b = jac_add(b, a))
+      const Val Z1Z1 = mul(pb[2], pb[2]), Z2Z2 = mul(pa[2], pa[2]);
+      const Val U1 = mul(pb[0], Z2Z2), U2 = mul(pa[0], Z1Z1);
+      const Val S1 = mul(mul(pb[1], pa[2]), Z2Z2), S2 = mul(mul(pa[1], pb[2]), Z1Z1);
+      const Val H = sub(U2, U1);
+      chk_zero(H);
+      const Val H2 = add(H, H), I = mul(H2, H2), J = mul(H, I);
+      const Val rr0 = sub(S2, S1), r = add(rr0, rr0);
+      const Val V = mul(U1, I);
+      nb[0] = sub(sub(mul(r, r), J), add(V, V));
+      const Val sj = mul(S1, J);
+      nb[1] = sub(mul(r, sub(V, nb[0])), add(sj, sj));
+      const Val zs = add(pb[2], pa[2]);
+      nb[2] = mul(sub(sub(mul(zs, zs), Z1Z1), Z2Z2), H);
+    }
+    chk_zero(pa[1]);   // exp_chains: czero(a.Y) before every doubling
+    Val na[3];
+    {   // 2a: dbl-2009-l
+      const Val A = mul(pa[0], pa[0]), B = mul(pa[1], pa[1]), C = mul(B, B);
+      const Val t0 = add(pa[0], B), t1 = mul(t0, t0), t2 = sub(sub(t1, A), C);
+      const Val D = add(t2, t2), Ee = add(add(A, A), A), F = mul(Ee, Ee);
+      na[0] = sub(F, add(D, D));
+      const Val C2 = add(C, C), C4 = add(C2, C2), C8 = add(C4, C4);
+      na[1] = sub(mul(Ee, sub(D, na[0])), C8);
+      const Val yz = mul(pa[1], pa[2]);
+      na[2] = add(yz, yz);
+    }
+    int top = 0;
+    for (const Op& o : ops) top = std::max(top, o.level);
+    for (int c = 0; c < 3; c++) for (int q = 0; q < E; q++) {   // the new points replace the old ones after every read
+      ops.push_back({tg::CP_COPY, pa[c].s[q], na[c].s[q], na[c].s[q], top + 1});
+      if (bit) ops.push_back({tg::CP_COPY, pb[c].s[q], nb[c].s[q], nb[c].s[q], top + 1});
+    }
+    const int nl = top + 1;
+    out.levels[bit] = nl;
+    out.slots = std::max(out.slots, (int)lvl.size());
+    out.ops[bit].assign((size_t)nl * tg::CP_LANES, 0u);
+    std::vector<int> fill(nl, 0);
+    for (const Op& o : ops) {
+      const int L = o.level - 1;
+      if (fill[L] >= tg::CP_LANES || (int)lvl.size() > tg::CP_MAX_SLOTS) { out.levels[0] = out.levels[1] = -1; return out; }   // (cannot happen for E <= 2: checked by the caller)
+      out.ops[bit][(size_t)L * tg::CP_LANES + fill[L]++] = (uint32_t)o.kind | ((uint32_t)o.d << 8) | ((uint32_t)o.a << 16) | ((uint32_t)o.b << 24);
+    }
+  }
+  return out;
+}
+
+// ---- what the three generators share --------------------------------------------------------------------------------
+static dim3 blocks(size_t k, unsigned b) { return dim3((unsigned)((k + b - 1) / b)); }
+
+// the first `values` Fq elements of every instance (eight u32 words each) are below p
+static int check_below_p(const uint32_t* ios, size_t IOW, int values, size_t K, const char* what) {
+  for (size_t k = 0; k < K; k++)
+    for (int v = 0; v < values; v++) {
+      u64 t[4]; for (int i = 0; i < 4; i++) t[i] = (u64)ios[IOW * k + 8 * v + 2 * i] | ((u64)ios[IOW * k + 8 * v + 2 * i + 1] << 32);
+      if (bnw::geq_p(t)) return fail(SBN_ERR_BAD_ARG, "%s >= p (instance %zu)", what, k);
+    }
+  return 0;
+}
+
+// grow-on-demand pinned staging (a copy from / to pageable memory blocks the calling thread inside the runtime, once per copy)
+static int pinned_reserve(u64** buf, size_t* words, size_t need) {
+  if (*words >= need) return 0;
+  if (*buf) (void)hipHostFree(*buf);
+  *buf = nullptr; *words = 0;
+  HIPC(hipHostMalloc((void**)buf, need * sizeof(u64), hipHostMallocDefault));
+  *words = need;
+  return 0;
+}
+
+// One sbn_prover_generate_trace call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
+struct TraceJob {
+  sbn_prover* const P;
+  const size_t K, IOW, n;   // K instances of IOW u32 words each
+  const hipStream_t st;
+  const ExpShape sh;
+  u64* const wbase;   // scratch: the LDE buffer, not yet in use
+  u64* w;
+  std::vector<hipEvent_t> kev;
+  TraceJob(sbn_prover* P, size_t K, size_t IOW)
+      : P(P), K(K), IOW(IOW), n(P->n), st(P->stream), sh(exp_shape(P->air)), wbase(P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde), w(wbase) {}
+
+  u64* take(size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; }
+  unsigned int* take_histograms() { return n > 65536 ? (unsigned int*)take((size_t)sh.num_rc * 32768) : nullptr; }   // u32 histograms of the range-checked columns
+  int fits() const { return (size_t)(w - wbase) > P->lde_scratch_words ? fail(SBN_ERR_UNSUPPORTED, "scratch does not fit") : 0; }
+
+  void mark() {
+    hipEvent_t e;
+    if (P->set.trace_timing && hipEventCreate(&e) == hipSuccess && hipEventRecord(e, st) == hipSuccess) kev.push_back(e);
+  }
+  // the timed span opens (EX_TRACEGEN_MS); the instance list goes in from `h_ios`, the caller's memory or a pinned copy of it
+  int begin(const void* h_ios, uint32_t* d_ios, int* d_err) {
+    HIPC(hipEventRecord(P->abs_ev[0], st));
+    HIPC(hipMemcpyAsync(d_ios, h_ios, IOW * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
+    mark();
+    return 0;
+  }
+  // the input-independent columns; table_max: the last entry of the lookup table (u16 tables 65535, the split check's 255)
+  template <typename FlagsKernel>
+  void launch_common_columns(FlagsKernel flags, const uint32_t* d_ios, u64* inv, u64 table_max) {
+    hipLaunchKernelGGL(flags, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
+    hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
+    hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, table_max, P->d_trace);
+    hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
+    mark();
+  }
+  int launch_u16_range_check(unsigned int* d_cnt, int* d_err) {
+    if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
+      HIPC(hipMemsetAsync(d_cnt, 0, (size_t)sh.num_rc * 65536 * sizeof(unsigned int), st));
+      hipLaunchKernelGGL(tg::range_count_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, d_cnt, d_err);
+      hipLaunchKernelGGL(tg::range_check_kernel<true>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
+    } else {
+      hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, (const unsigned int*)nullptr, P->set.range_check);
+    }
+    return 0;
+  }
+  // the timed span closes and the stream drains: the generator's copies back to the host, queued before this, have landed
+  int end(const char* const* names) {
+    HIPC(hipEventRecord(P->abs_ev[1], st));
+    HIPC(hipStreamSynchronize(st));
+    float ms = 0; HIPC(hipEventElapsedTime(&ms, P->abs_ev[0], P->abs_ev[1]));
+    P->stage_ms[ST_COUNT + EX_TRACEGEN_MS] = ms;
+    if (P->set.trace_timing) {
+      for (size_t i = 0; i + 1 < kev.size(); i++) { float t = 0; (void)hipEventElapsedTime(&t, kev[i], kev[i + 1]); fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", names[i], t); }
+      for (auto e : kev) (void)hipEventDestroy(e);
+      fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", "total", ms);
+    }
+    return 0;
+  }
+  // the kernels' error word, a degenerate instance first; then the public inputs `pi(k, p)` writes for instance k
+  template <typename PublicInputs>
+  int finish(int err, uint64_t* pi_out, PublicInputs pi) {
+    if (err & tg::TG_ERR_DEGENERATE) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
+    if (err & tg::TG_ERR_WITNESS) return fail(SBN_ERR_WITNESS, "modular witness generation failed");
+    if (err & tg::TG_ERR_RANGE) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
+    P->pi.resize(P->air.npi);
+    for (size_t k = 0; k < K; k++) pi(k, P->pi.data() + (size_t)sh.pi_per_io * k);
+    if (pi_out) memcpy(pi_out, P->pi.data(), P->pi.size() * sizeof(u64));
+    P->loaded = true;
+    return SBN_OK;
+  }
+};
+
+// G1ExpStark / G2ExpStark (E = 1 / 2)
+template <int E>
+static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+  const size_t IOW = 8 * (4 * E + 1);  // u32 words per instance: x and offset (2E Fq each) + exp_val
+  if (int rc = check_below_p(ios, IOW, 4 * E, K, "coordinate")) return rc;
+  HIPC(hipSetDevice(P->device));
+  TraceJob J(P, K, IOW);
+  const size_t n = J.n;
+  const hipStream_t st = J.st;
+  const size_t cw = 257 * 12 * E * K;  // one Jacobian chain of every instance
+  u64* ja = J.take(cw); u64* jb = J.take(cw);
+  u64* sv = J.take(28 * E * n);       u64* inv = J.take(n);
+  u64* d_out = J.take(16 * E * K);
+  unsigned char* row_op = (unsigned char*)J.take(n / 8 + 1);
+  uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
+  uint32_t* d_prog[2] = {(uint32_t*)J.take(64 * tg::CP_LANES / 2), (uint32_t*)J.take(64 * tg::CP_LANES / 2)};   // chain programs: <= 64 levels of 64 micro-operations
+  int* d_err = (int*)J.take(1);
+  unsigned int* d_cnt = J.take_histograms();
+  if (int rc = J.fits()) return rc;
+  if (int rc = range_check_setup(P->device)) return rc;
+  // the instance list in and the outputs + error word back cross through pinned staging
+  const size_t io_words = (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
+  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words)) return rc;
+  memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
+  u64* const h_out = P->h_io + io_words;
+  if (int rc = J.begin(P->h_io, d_ios, d_err)) return rc;
+  J.launch_common_columns(tg::flags_kernel, d_ios, inv, 65535);
+  // the two 256-step curve chains per instance: host threads while the device writes the input-independent columns
+  // chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx picks by the host pool's size): 2 = one wave per instance walking levels of
+  // independent Fq operations (tg::chain_coop_kernel), 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host threads +
+  // pinned upload
+  if (P->chain_mode == 2) {
+    static const ChainProgram prog = build_chain_program(E);
+    if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
+    tg::ChainProgDev cp{};
+    for (int b = 0; b < 2; b++) {
+      HIPC(hipMemcpyAsync(d_prog[b], prog.ops[b].data(), prog.ops[b].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      cp.ops[b] = d_prog[b]; cp.levels[b] = prog.levels[b];
+    }
+    for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) cp.in_slot[v * E + q] = (unsigned char)((v < 2 ? v : v + 1) * E + q);   // a.X a.Y | b.X b.Y
+    cp.one_slot[0] = (unsigned char)(2 * E); cp.one_slot[1] = (unsigned char)(5 * E);
+    cp.zero_slot[0] = (unsigned char)(2 * E + 1); cp.zero_slot[1] = (unsigned char)(5 * E + 1);
+    for (int i = 0; i < 6 * E; i++) cp.coord[i] = (unsigned char)i;
+    hipLaunchKernelGGL(tg::chain_coop_kernel<E>, dim3((unsigned)K), dim3(tg::CP_LANES), 0, st, d_ios, K, ja, jb, d_err, cp);
+  } else if (P->chain_mode == 1) hipLaunchKernelGGL(tg::chain_kernel<E>, blocks(K, 64), dim3(64), 0, st, d_ios, K, ja, jb, d_err);
+  else {
+    if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
+    if (tracegen_host_chains(E, ios, K, P->h_chain, P->h_chain + cw)) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
+    HIPC(hipMemcpyAsync(ja, P->h_chain, cw * sizeof(u64), hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(jb, P->h_chain + cw, cw * sizeof(u64), hipMemcpyHostToDevice, st));
+  }
+  J.mark();
+  hipLaunchKernelGGL(tg::affine_lambda_kernel<E>, blocks((n + tg::TG_ROWS - 1) / tg::TG_ROWS, 64), dim3(64), 0, st, d_ios, K, ja, jb, n, sv, row_op, d_out, d_err);
+  J.mark();
+  hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, J.sh.gadget_col, P->d_trace, d_err);
+  J.mark();
+  if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
+  J.mark();
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h_out, d_out, 16 * E * K * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(h_out + 16 * E * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  static const char* const names[] = {"flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
+  if (int rc = J.end(names)) return rc;
+  // public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156)
+  return J.finish((int)(h_out[16 * E * K] & 0xffffffffu), pi_out, [&](size_t k, u64* p) {
+    for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
+    for (int i = 0; i < 16 * E; i++) p[IOW + i] = h_out[16 * E * k + i];
+  });
+}
+
+// Fq12ExpStark: the square-and-multiply chains (no inversion anywhere) on host threads in standard form, then one lane
+// per row for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
+static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+  const bool u64e = P->air.kind == SBN_AIR_FQ12_EXP_U64;        // 128-row instances, one-element exponent
+  const size_t IOW = u64e ? 194 : 200;
+  const int steps = u64e ? 64 : 256, log_rpb = u64e ? 7 : 9;
+  if (int rc = check_below_p(ios, IOW, 24, K, "coefficient")) return rc;
+  HIPC(hipSetDevice(P->device));
+  if (u64e)
+    for (size_t k = 0; k < K; k++)
+      if (((u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32)) >= GLP) return fail(SBN_ERR_NON_CANONICAL, "exponent of instance %zu is not a canonical field element", k);
+  TraceJob J(P, K, IOW);
+  const size_t n = J.n;
+  const hipStream_t st = J.st;
+  const size_t cw = (size_t)(steps + 1) * 48 * K;  // one chain of every instance, standard form
+  u64* ca = J.take(cw); u64* cb = J.take(cw);
+  u64* inv = J.take(n);
+  u64* d_outs = J.take(K * 48);
+  uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
+  int* d_err = (int*)J.take(1);
+  if (int rc = J.fits()) return rc;
+  if (int rc = J.begin(ios, d_ios, d_err)) return rc;
+  if (u64e) J.launch_common_columns(tg::flags_u64_kernel, d_ios, inv, 255);
+  else J.launch_common_columns(tg::flags_kernel, d_ios, inv, 255);
+  // the square-and-multiply chains: one workgroup per instance on the device (kernels_tracegen.cuh fq12_chain_kernel);
+  // SBN_FQ12_HOST_CHAIN=1: the library's host threads + a pinned upload, as in round 2 (A/B)
+  const bool host_chain = P->set.fq12_host_chain;
+  if (host_chain) {
+    if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
+    tracegen_host_chains_fq12(ios, IOW, steps, K, P->h_chain, P->h_chain + cw);
+    HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
+  } else hipLaunchKernelGGL(tg::fq12_chain_kernel, dim3((unsigned)K), dim3(320), 0, st, d_ios, IOW, steps, ca, cb, d_outs);
+  J.mark();
+  // one lane per (row, output coefficient) by default; SBN_FQ12_ROW_KERNEL=1: round 2's one lane per row (A/B)
+  const bool row_kernel = P->set.fq12_row_kernel;
+  if (row_kernel) hipLaunchKernelGGL(tg::fq12_row_kernel, blocks(n, 64), dim3(64), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
+  else hipLaunchKernelGGL(tg::fq12_gadget_kernel, blocks(12 * n, 256), dim3(256), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
+  J.mark();
+  hipLaunchKernelGGL(tg::split_range_check_kernel, dim3((unsigned)J.sh.num_rc), dim3(256), 0, st, P->d_trace, n, J.sh.rc_start, J.sh.start_lookups, d_err);
+  J.mark();
+  HIPC(hipGetLastError());
+  int err = 0;
+  HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  std::vector<u64> chain_out;                 // B[steps] of every instance (the outputs among the public inputs) when the chains ran on the device
+  if (!host_chain) {
+    chain_out.resize(K * 48);
+    HIPC(hipMemcpyAsync(chain_out.data(), d_outs, K * 48 * sizeof(u64), hipMemcpyDeviceToHost, st));
+  }
+  static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
+  if (int rc = J.end(names)) return rc;
+  // public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117)
+  return J.finish(err, pi_out, [&](size_t k, u64* p) {
+    for (int c = 0; c < 24; c++)
+      for (int i = 0; i < 16; i++) p[16 * c + i] = (ios[IOW * k + 8 * c + (i >> 1)] >> (16 * (i & 1))) & 0xffff;
+    if (u64e) p[384] = (u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32);
+    else for (int i = 0; i < 8; i++) p[384 + i] = ios[IOW * k + 192 + i];
+    const u64* out = host_chain ? P->h_chain + cw + ((k * (steps + 1) + steps) * 12) * 4 : chain_out.data() + k * 48;  // B[steps]
+    const int ob = 384 + J.sh.n_exp_slots;
+    for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
+  });
+}
+
+// FqExpStark: chains on host threads (512 Montgomery products per instance), rows and the u16 range check on the device.
+static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+  const size_t IOW = 24;
+  if (int rc = check_below_p(ios, IOW, 2, K, "value")) return rc;
+  HIPC(hipSetDevice(P->device));
+  TraceJob J(P, K, IOW);
+  const size_t n = J.n;
+  const hipStream_t st = J.st;
+  const size_t cw = 257 * 4 * K;
+  u64* ca = J.take(cw); u64* cb = J.take(cw);
+  u64* inv = J.take(n);
+  uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
+  int* d_err = (int*)J.take(1);
+  unsigned int* d_cnt = J.take_histograms();
+  if (int rc = J.fits()) return rc;
+  if (int rc = range_check_setup(P->device)) return rc;
+  if (int rc = J.begin(ios, d_ios, d_err)) return rc;
+  J.launch_common_columns(tg::flags_kernel, d_ios, inv, 65535);
+  if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
+  tracegen_host_chains_fq(ios, K, P->h_chain, P->h_chain + cw);
+  HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
+  J.mark();
+  hipLaunchKernelGGL(tg::fq_row_kernel, blocks(n, 128), dim3(128), 0, st, d_ios, ca, cb, n, P->d_trace, d_err);
+  J.mark();
+  if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
+  J.mark();
+  HIPC(hipGetLastError());
+  int err = 0;
+  HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
+  if (int rc = J.end(names)) return rc;
+  // public inputs: x, offset, exp_val, output = b at the last row, as u32 limbs (fq/exp.rs:98-108)
+  return J.finish(err, pi_out, [&](size_t k, u64* p) {
+    for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
+    const u64* out = P->h_chain + cw + (k * 257 + 256) * 4;  // B[256]
+    for (int i = 0; i < 8; i++) p[24 + i] = (out[i >> 1] >> (32 * (i & 1))) & 0xffffffffULL;
+  });
+}
+
+extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
+  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;   // before any check: a refused instance list must not leave the previous trace provable
+  if (!ios) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (!is_exp_air(P->air.kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
+  if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
+  if (P->n != exp_rows_per_instance(P->air.kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
+  if (P->air.kind == SBN_AIR_FQ12_EXP || P->air.kind == SBN_AIR_FQ12_EXP_U64) return generate_trace_device_fq12(P, ios, num_io, pi_out);
+  if (P->n < 65536 || P->n > 262144) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  if (P->air.kind == SBN_AIR_FQ_EXP) return generate_trace_device_fq(P, ios, num_io, pi_out);
+  return P->air.kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, ios, num_io, pi_out) : generate_trace_device<2>(P, ios, num_io, pi_out);
+}
+
+extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
+  using namespace tg;
+  if (op < FQB_MUL || op > FQB_FQ2_INV) return fail(SBN_ERR_BAD_ARG, "unknown op %d", op);
+  const bool binary = op == FQB_MUL || op == FQB_ADD || op == FQB_SUB || op == FQB_FQ2_INV;
+  if (!a || !out || (binary && !b)) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (op == FQB_BATCH_INV && count % TG_INV_BATCH) return fail(SBN_ERR_BAD_ARG, "batch inverse needs a multiple of %d values", TG_INV_BATCH);
+  for (size_t i = 0; i < count; i++) {
+    if (bnw::geq_p(a + 4 * i) || (binary && bnw::geq_p(b + 4 * i))) return fail(SBN_ERR_NON_CANONICAL, "element %zu is not below p", i);
+    const bool za = !(a[4 * i] | a[4 * i + 1] | a[4 * i + 2] | a[4 * i + 3]);
+    const bool zb = !binary || !(b[4 * i] | b[4 * i + 1] | b[4 * i + 2] | b[4 * i + 3]);
+    if ((op == FQB_INV || op == FQB_BATCH_INV) && za) return fail(SBN_ERR_BAD_ARG, "element %zu is zero: no inverse", i);
+    if (op == FQB_FQ2_INV && za && zb) return fail(SBN_ERR_BAD_ARG, "element %zu is zero: no inverse", i);
+  }
+  const size_t items = op == FQB_BATCH_INV ? count / TG_INV_BATCH : count, out_words = 4 * count * (op == FQB_FQ2_INV ? 2 : 1);
+  if (!on_device) {
+    for (size_t i = 0; i < items; i++) fq_batch_item(op, a, b, out, i);
+    return SBN_OK;
+  }
+  if (int rc = use_current_device("no CPU fallback")) return rc;
+  if (count == 0) return SBN_OK;
+  u64* d = nullptr;
+  HIPC(hipMalloc((void**)&d, (8 * count + out_words) * sizeof(u64)));
+  hipError_t e = hipMemcpy(d, a, 4 * count * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess && binary) e = hipMemcpy(d + 4 * count, b, 4 * count * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fq_batch_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, 0, op, d, d + 4 * count, d + 8 * count, items);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, d + 8 * count, out_words * sizeof(u64), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_bn254_fq_batch: %s", hipGetErrorString(e));
+  return SBN_OK;
+}

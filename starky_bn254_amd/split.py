@@ -47,7 +47,7 @@ def exchange_bytes(stark, config, degree_bits, world):
 
 
 def own_columns(total, world, rank, block=64):
-    """Columns of a `total`-column matrix that rank `rank` owns (prover.hip ColShare: blocks of 64 dealt round-robin)."""
+    """Columns of a `total`-column matrix that rank `rank` owns (prover_ctx.hpp ColShare: blocks of 64 dealt round-robin)."""
     nblocks = -(-total // block)
     return sum(min(block, total - b * block) for b in range(rank, nblocks, world))
 

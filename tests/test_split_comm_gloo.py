@@ -103,7 +103,7 @@ def test_split_row_ownership_model():
 
 
 def test_split_column_ownership_model():
-    """The column side of the split (prover.hip ColShare): columns are dealt in blocks of 64, round-robin; a rank keeps its
+    """The column side of the split (prover_ctx.hpp ColShare): columns are dealt in blocks of 64, round-robin; a rank keeps its
     blocks compactly; in step k the ranks transform the blocks k*R .. k*R+R-1, which are exactly the columns the sequential
     leaf sponge absorbs next; FRI combines an own block as one group whose weight is alpha^(first global column)."""
     ob = 64
@@ -133,7 +133,7 @@ def test_split_column_ownership_model():
 
 
 def test_python_side_share_and_cpu_helpers():
-    """split.own_columns / exchange_bytes_sent (what bench.py reports as bytes on the wire) restate prover.hip ColShare;
+    """split.own_columns / exchange_bytes_sent (what bench.py reports as bytes on the wire) restate prover_ctx.hpp ColShare;
     sharding.effective_cpus() never exceeds the visible CPUs and honours the affinity mask."""
     sys.path.insert(0, ROOT)
     from starky_bn254_amd import sharding, split
