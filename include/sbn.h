@@ -325,6 +325,25 @@ void sbn_proof_free(sbn_proof* proof);
 /* Verifier: verify_stark_proof(stark, proof, &config) (src/curves/g1/exp.rs:826). */
 int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const uint8_t* proof_bytes, size_t len);
 
+/* Batch verifier: the same verification with the Merkle hashing and the reduction of the opened rows on the device, for up to
+ * max_batch proofs of one (table, config, degree_bits) per call (csrc/verifier_device.hip).  It frees host cores; whether it is
+ * also faster than sbn_verify on as many host threads as the caller has is recorded in DESIGN.md section 7.
+ * config_supported() and the table / degree_bits checks run before a device is looked for (as sbn_prover_create);
+ * 1 <= max_batch <= 65536; no device: SBN_ERR_NO_DEVICE (no fallback: sbn_verify is the host verifier).  The verifier owns
+ * max_batch proof-sized slots of device memory, a stream and 16 MiB of pinned staging; the caller's memory is only read. */
+typedef struct sbn_verifier sbn_verifier;
+int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t max_batch, sbn_verifier** out);
+/* 1 <= count <= max_batch.  Returns SBN_OK when the call ran; status_out[i] is what sbn_verify(air, cfg, proofs[i], lens[i])
+ * returns, and sbn_verifier_reason(v, i) is the message sbn_last_error() would hold after it ("" when accepted), until the
+ * next call.  A call-level failure (null argument, count out of range: SBN_ERR_BAD_ARG; a HIP failure: SBN_ERR_HIP) leaves
+ * status_out untouched.  A proof that names another degree_bits than the verifier's gets its verdict from the host path.
+ * One thread at a time per verifier. */
+int sbn_verifier_verify(sbn_verifier* v, const uint8_t* const* proofs, const size_t* lens, size_t count, int32_t* status_out);
+const char* sbn_verifier_reason(const sbn_verifier* v, size_t i);
+/* Device times of the last call (ms, HIP events on the verifier's stream): upload, kernels, download; returns the number written. */
+int sbn_verifier_stage_times(const sbn_verifier* v, float* ms_out, int cap);
+void sbn_verifier_destroy(sbn_verifier* v);
+
 /* Building blocks exposed for parity tests and benchmarks (device in/out unless noted) --------- */
 /* PolynomialBatch::from_values on a host column-major matrix: Merkle cap (2^cap_height x 4 words),
  * optionally coefficients [ncols][n] and LDE [ncols][n<<rate_bits] (natural order) back to host.

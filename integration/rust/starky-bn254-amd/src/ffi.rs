@@ -36,6 +36,10 @@ pub struct sbn_proof {
 pub struct sbn_batch_prover {
     _opaque: [u8; 0],
 }
+#[repr(C)]
+pub struct sbn_verifier {
+    _opaque: [u8; 0],
+}
 
 pub const SBN_AIR_G1_OP: i32 = 1;
 pub const SBN_AIR_G1_EXP: i32 = 2;
@@ -82,4 +86,10 @@ extern "C" {
     pub fn sbn_proof_words(p: *const sbn_proof) -> *const u64;
     pub fn sbn_proof_free(p: *mut sbn_proof);
     pub fn sbn_verify(air: *const sbn_air_desc, cfg: *const sbn_config, bytes: *const u8, len: usize) -> i32;
+
+    pub fn sbn_verifier_create(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, max_batch: u32, out: *mut *mut sbn_verifier) -> i32;
+    pub fn sbn_verifier_verify(v: *mut sbn_verifier, proofs: *const *const u8, lens: *const usize, count: usize, status_out: *mut i32) -> i32;
+    pub fn sbn_verifier_reason(v: *const sbn_verifier, i: usize) -> *const c_char;
+    pub fn sbn_verifier_stage_times(v: *const sbn_verifier, ms_out: *mut f32, cap: i32) -> i32;
+    pub fn sbn_verifier_destroy(v: *mut sbn_verifier);
 }

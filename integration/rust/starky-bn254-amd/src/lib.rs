@@ -296,6 +296,39 @@ pub fn verify_stark_proof_words<S: SbnTable>(stark: &S, words: &[u64], config: &
     check(unsafe { ffi::sbn_verify(&a, &cfg, bytes.as_ptr(), bytes.len()) }, "sbn_verify")
 }
 
+/// Batch verifier on the device (sbn_verifier_*): up to `max_batch` proofs of one (table, config, degree_bits) per call, the
+/// Merkle hashing and the reduction of the opened rows on the GPU.  Needs a device; `verify_stark_proof_words` is the host verifier.
+pub struct Verifier {
+    raw: *mut ffi::sbn_verifier,
+}
+
+impl Verifier {
+    pub fn new<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: usize, max_batch: usize) -> Result<Self> {
+        let a = air(stark);
+        let cfg = to_sbn_config(config)?;
+        let mut raw = ptr::null_mut();
+        check(unsafe { ffi::sbn_verifier_create(&a, &cfg, degree_bits as u32, max_batch as u32, &mut raw) }, "sbn_verifier_create")?;
+        Ok(Verifier { raw })
+    }
+
+    /// One `(code, reason)` per proof, in order: what `sbn_verify` returns for it (`(0, "")` = accepted).
+    pub fn verify_words(&mut self, proofs: &[&[u64]]) -> Result<Vec<(i32, String)>> {
+        let ptrs: Vec<*const u8> = proofs.iter().map(|w| w.as_ptr() as *const u8).collect();
+        let lens: Vec<usize> = proofs.iter().map(|w| w.len() * 8).collect();
+        let mut status = vec![0i32; proofs.len()];
+        check(unsafe { ffi::sbn_verifier_verify(self.raw, ptrs.as_ptr(), lens.as_ptr(), proofs.len(), status.as_mut_ptr()) }, "sbn_verifier_verify")?;
+        Ok((0..proofs.len())
+            .map(|i| (status[i], unsafe { CStr::from_ptr(ffi::sbn_verifier_reason(self.raw, i)) }.to_string_lossy().into_owned()))
+            .collect())
+    }
+}
+
+impl Drop for Verifier {
+    fn drop(&mut self) {
+        unsafe { ffi::sbn_verifier_destroy(self.raw) }
+    }
+}
+
 pub fn set_device(device: usize) -> Result<()> {
     check(unsafe { ffi::sbn_set_device(device as i32) }, "sbn_set_device")
 }

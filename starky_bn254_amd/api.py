@@ -41,6 +41,7 @@ EXPORTS = [
     "sbn_split_prover_load_trace", "sbn_split_prover_prove", "sbn_split_prover_stage_times",
     "sbn_abi_version", "sbn_rccl_unique_id", "sbn_rccl_comm_create", "sbn_rccl_comm_destroy",
     "sbn_local_comm_create", "sbn_local_comm_abort", "sbn_local_comm_destroy", "sbn_comm_selftest",
+    "sbn_verifier_create", "sbn_verifier_verify", "sbn_verifier_reason", "sbn_verifier_stage_times", "sbn_verifier_destroy",
 ]
 
 
@@ -126,6 +127,12 @@ def lib():
         L.sbn_proof_degree_bits.argtypes = [vp]
         L.sbn_proof_free.argtypes = [vp]
         L.sbn_verify.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, sz]
+        L.sbn_verifier_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(vp)]
+        L.sbn_verifier_verify.argtypes = [vp, vp, vp, sz, vp]
+        L.sbn_verifier_reason.restype = C.c_char_p
+        L.sbn_verifier_reason.argtypes = [vp, sz]
+        L.sbn_verifier_stage_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+        L.sbn_verifier_destroy.argtypes = [vp]
         L.sbn_commit_values.argtypes = [vp, sz, sz, u32, u32, vp, vp, vp]
         L.sbn_poseidon_permute_batch.argtypes = [vp, sz]
         L.sbn_poseidon_permute_host.argtypes = [vp, sz, C.c_int]
@@ -619,6 +626,45 @@ def verify_stark_proof(stark, proof, config):
     b = proof.to_bytes() if isinstance(proof, Proof) else bytes(proof)
     buf = (C.c_uint8 * len(b)).from_buffer_copy(b)
     _check(lib().sbn_verify(C.byref(stark._d), C.byref(config._c), buf, len(b)))
+
+
+class Verifier:
+    """Batch verifier on the device for proofs of one (table, config, degree_bits): the Merkle hashing and the reduction of the
+    opened rows run on the GPU, up to max_batch proofs per call.  Needs a device (SbnError(-3) otherwise): verify_stark_proof
+    is the host verifier."""
+
+    def __init__(self, stark, config, degree_bits, max_batch=64):
+        self.stark, self.config, self.degree_bits, self.max_batch = stark, config, degree_bits, max_batch
+        self._h = C.c_void_p()
+        _check(lib().sbn_verifier_create(C.byref(stark._d), C.byref(config._c), degree_bits, max_batch, C.byref(self._h)))
+
+    def verify(self, proofs):
+        """proofs: Proof objects or byte strings -> [(code, reason)] in order: what sbn_verify returns for each (0, "" = accepted).
+        Raises SbnError when the call itself is refused (an empty list, more than max_batch proofs, a HIP failure)."""
+        bufs = [p.to_bytes() if isinstance(p, Proof) else bytes(p) for p in proofs]
+        n = len(bufs)
+        ptrs = (C.c_char_p * max(n, 1))(*bufs)
+        lens = (C.c_size_t * max(n, 1))(*[len(b) for b in bufs])
+        status = (C.c_int32 * max(n, 1))()
+        _check(lib().sbn_verifier_verify(self._h, ptrs, lens, n, status))
+        return [(int(status[i]), lib().sbn_verifier_reason(self._h, i).decode()) for i in range(n)]
+
+    def stage_times(self):
+        """Device times of the last verify() in ms (HIP events): upload, kernels, download."""
+        buf = (C.c_float * 3)()
+        k = lib().sbn_verifier_stage_times(self._h, buf, 3)
+        return dict(zip(("upload", "kernels", "download"), (float(buf[i]) for i in range(k))))
+
+    def close(self):
+        if self._h:
+            lib().sbn_verifier_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def commit_values(cols, rate_bits=1, cap_height=4, want_coeffs=False, want_lde=False):

@@ -4,7 +4,7 @@
 // over the quadratic extension -- as the reference's verifier reuses eval_packed_generic with
 // P = F::Extension.  Verification is a few thousand field operations and 84 Merkle paths; it runs on
 // the calling thread like the reference's.
-#include "host_common.hpp"
+#include "verifier_core.hpp"
 #include <cstring>
 
 using namespace sbn;
@@ -69,14 +69,44 @@ E2 compute_evaluation(F x, size_t within, u32 arity_bits, const std::vector<E2>&
   return res;
 }
 
+// both sources from the parsed proof, on the calling thread, when the core asks
+struct HostSources : VerifySources {
+  const VerifyProof& p;
+  explicit HostSources(const VerifyProof& p_) : p(p_) {}
+  bool merkle_ok(size_t q, size_t tree) override {
+    const VerifyRound& r = p.rounds[q];
+    const size_t ninit = p.num_initial();
+    if (tree < ninit) {
+      const std::vector<Digest4>& cap = tree == 0 ? p.trace_cap : (tree + 1 == ninit ? p.q_cap : p.z_cap);
+      return merkle_verify(r.init[tree].evals.data(), r.init[tree].evals.size(), p.indices[q], cap, r.init[tree].sib);
+    }
+    const size_t i = tree - ninit;
+    size_t coset_index = p.indices[q];
+    for (size_t k = 0; k <= i; k++) coset_index >>= p.fs.arity_bits[k];
+    const VerifyStep& s = r.steps[i];
+    std::vector<F> flat(2 * s.evals.size());
+    for (size_t j = 0; j < s.evals.size(); j++) { flat[2 * j] = s.evals[j].a; flat[2 * j + 1] = s.evals[j].b; }
+    return merkle_verify(flat.data(), flat.size(), coset_index, p.fri_caps[i], s.sib);
+  }
+  E2 row_reduction(size_t q, size_t t) override {
+    const std::vector<F>& v = p.rounds[q].init[t].evals;
+    E2 acc{F(0), F(0)};
+    for (size_t j = v.size(); j-- > 0;) acc = acc * p.fri_alpha + v[j];
+    return acc;
+  }
+};
+
 }  // namespace
 
-extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const uint8_t* bytes, size_t len) {
+namespace sbn {
+
+int verify_parse(const sbn_air_desc* air, const sbn_config* cfg, const uint8_t* bytes, size_t len, VerifyProof& p, u32 device_degree_bits) {
   if (!air || !cfg || !bytes) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (!config_supported(cfg)) return fail(SBN_ERR_UNSUPPORTED, "unsupported StarkConfig");
-  AirShape as;
+  AirShape& as = p.as;
   if (!air_shape(air, cfg, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
   if (len % 8 || len < 12 * 8) return fail(SBN_ERR_MALFORMED_PROOF, "proof length is not a whole number of words");
+  p.cfg = *cfg;
   std::vector<u64> words(len / 8);
   memcpy(words.data(), bytes, len);  // LE host
   Reader rd{words.data(), words.size()};
@@ -85,74 +115,85 @@ extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const 
       rate_bits = rd.word(), nlayers = rd.word(), arity_bits = rd.word(), fpl = rd.word(), nqueries = rd.word();
   if (magic != PROOF_MAGIC) return fail(SBN_ERR_MALFORMED_PROOF, "bad magic");
   if (degree_bits < 1 || degree_bits > 30) return fail(SBN_ERR_MALFORMED_PROOF, "bad degree_bits");
-  FriShape fs = fri_shape(*cfg, (u32)degree_bits);
+  FriShape& fs = p.fs;
+  fs = fri_shape(*cfg, (u32)degree_bits);
   if (ncol != as.ncols || nz != as.nzs || nq != 2 * cfg->num_challenges || npi != as.npi || cap_h != cfg->cap_height || rate_bits != cfg->rate_bits ||
       nlayers != fs.arity_bits.size() || arity_bits != cfg->fri_arity_bits || fpl != fs.final_poly_len() || nqueries != cfg->num_query_rounds)
     return fail(SBN_ERR_MALFORMED_PROOF, "proof shape does not match the table / config");
   if ((is_exp_air(as.kind) || as.kind == SBN_AIR_FLAGS || as.kind == SBN_AIR_FLAGS_U64) && ((u64)exp_rows_per_instance(as.kind) * as.num_io) != ((u64)1 << degree_bits)) return fail(SBN_ERR_MALFORMED_PROOF, "degree_bits does not match num_io");
   const u32 lde_bits = (u32)degree_bits + cfg->rate_bits;
   if (lde_bits < cfg->cap_height + fs.total_arity()) return fail(SBN_ERR_MALFORMED_PROOF, "degree too small for the FRI parameters");
+  p.degree_bits = (u32)degree_bits; p.lde_bits = lde_bits; p.ncol = ncol; p.nz = nz; p.nq = nq; p.npi = npi; p.nqueries = nqueries;
   const size_t capn = (size_t)1 << cfg->cap_height;
   auto read_cap = [&](std::vector<Digest4>& c) { c.resize(capn); for (auto& d : c) d = rd.d(); };
-  std::vector<Digest4> trace_cap, z_cap, q_cap;
-  read_cap(trace_cap); if (nz) read_cap(z_cap); read_cap(q_cap);
+  read_cap(p.trace_cap); if (nz) read_cap(p.z_cap); read_cap(p.q_cap);
   auto read_ext = [&](std::vector<E2>& v, size_t k) { v.resize(k); for (auto& e : v) e = rd.e(); };
-  std::vector<E2> local, next, zs, zs_next, quot;
-  read_ext(local, ncol); read_ext(next, ncol); read_ext(zs, nz); read_ext(zs_next, nz); read_ext(quot, nq);
-  std::vector<std::vector<Digest4>> fri_caps(nlayers);
-  for (auto& c : fri_caps) read_cap(c);
+  read_ext(p.local, ncol); read_ext(p.next, ncol); read_ext(p.zs, nz); read_ext(p.zs_next, nz); read_ext(p.quot, nq);
+  p.fri_caps.resize(nlayers);
+  for (auto& c : p.fri_caps) read_cap(c);
   if (!rd.ok) return fail(SBN_ERR_MALFORMED_PROOF, "truncated proof or non-canonical element");
-  struct Initial { std::vector<F> evals; std::vector<Digest4> sib; };
-  struct Step { std::vector<E2> evals; std::vector<Digest4> sib; };
-  struct Round { std::vector<Initial> init; std::vector<Step> steps; };
   std::vector<size_t> widths; widths.push_back(ncol); if (nz) widths.push_back(nz); widths.push_back(nq);
-  std::vector<Round> rounds(nqueries);
-  for (auto& r : rounds) {
+  const bool lean = device_degree_bits && degree_bits == device_degree_bits;
+  p.has_query_rows = !lean;
+  p.rounds.resize(nqueries);
+  for (auto& r : p.rounds) {
     for (size_t wd : widths) {
-      Initial in; in.evals.resize(wd); for (auto& v : in.evals) v = rd.f();
+      if (lean) { for (size_t k = wd + 4 * (size_t)(lde_bits - cfg->cap_height); k-- > 0;) (void)rd.f(); continue; }
+      VerifyInitial in; in.evals.resize(wd); for (auto& v : in.evals) v = rd.f();
       in.sib.resize(lde_bits - cfg->cap_height); for (auto& d : in.sib) d = rd.d();
       r.init.push_back(std::move(in));
     }
     u32 bits = lde_bits;
     for (u32 ab : fs.arity_bits) {
       bits -= ab;
-      Step s; s.evals.resize((size_t)1 << ab); for (auto& e : s.evals) e = rd.e();
-      s.sib.resize(bits - cfg->cap_height); for (auto& d : s.sib) d = rd.d();
+      VerifyStep s; s.evals.resize((size_t)1 << ab); for (auto& e : s.evals) e = rd.e();
+      if (lean) for (size_t k = 4 * (size_t)(bits - cfg->cap_height); k-- > 0;) (void)rd.f();
+      else { s.sib.resize(bits - cfg->cap_height); for (auto& d : s.sib) d = rd.d(); }
       r.steps.push_back(std::move(s));
     }
     if (!rd.ok) return fail(SBN_ERR_MALFORMED_PROOF, "truncated proof or non-canonical element");
   }
-  std::vector<E2> final_poly; read_ext(final_poly, fpl);
-  F pow_witness = rd.f();
-  std::vector<F> pi(npi); for (auto& v : pi) v = rd.f();
+  read_ext(p.final_poly, fpl);
+  p.pow_witness = rd.f();
+  p.pi.resize(npi); for (auto& v : p.pi) v = rd.f();
   if (!rd.ok || rd.pos != words.size()) return fail(SBN_ERR_MALFORMED_PROOF, "truncated proof, trailing words or non-canonical element");
+  return SBN_OK;
+}
 
-  // get_challenges (starky get_challenges.rs)
+// get_challenges (starky get_challenges.rs)
+void verify_challenges(VerifyProof& p) {
+  const sbn_config* cfg = &p.cfg;
   Challenger ch;
-  for (auto& d : trace_cap) for (int i = 0; i < 4; i++) ch.observe(d.e[i]);
-  F gam[2][2] = {};
-  if (nz) {
-    for (int s = 0; s < 2; s++) for (u32 c = 0; c < cfg->num_challenges; c++) { (void)ch.challenge(); gam[s][c] = ch.challenge(); }
-    for (auto& d : z_cap) for (int i = 0; i < 4; i++) ch.observe(d.e[i]);
+  for (auto& d : p.trace_cap) for (int i = 0; i < 4; i++) ch.observe(d.e[i]);
+  if (p.nz) {
+    for (int s = 0; s < 2; s++) for (u32 c = 0; c < cfg->num_challenges; c++) { (void)ch.challenge(); p.gam[s][c] = ch.challenge(); }
+    for (auto& d : p.z_cap) for (int i = 0; i < 4; i++) ch.observe(d.e[i]);
   }
-  F alphas[SBN_NCH];
-  for (int j = 0; j < SBN_NCH; j++) alphas[j] = ch.challenge();
-  for (auto& d : q_cap) for (int i = 0; i < 4; i++) ch.observe(d.e[i]);
-  E2 zeta = ch.ext_challenge();
-  for (auto& e : local) ch.observe(e);
-  for (auto& e : zs) ch.observe(e);
-  for (auto& e : quot) ch.observe(e);
-  for (auto& e : next) ch.observe(e);
-  for (auto& e : zs_next) ch.observe(e);
-  E2 fri_alpha = ch.ext_challenge();
-  std::vector<E2> betas;
-  for (auto& c : fri_caps) { for (auto& d : c) for (int i = 0; i < 4; i++) ch.observe(d.e[i]); betas.push_back(ch.ext_challenge()); }
-  for (auto& e : final_poly) ch.observe(e);
-  ch.observe(pow_witness);
-  F pow_response = ch.challenge();
-  std::vector<size_t> indices(nqueries);
-  for (auto& x : indices) x = (size_t)(ch.challenge().v % ((u64)1 << lde_bits));
+  for (int j = 0; j < SBN_NCH; j++) p.alphas[j] = ch.challenge();
+  for (auto& d : p.q_cap) for (int i = 0; i < 4; i++) ch.observe(d.e[i]);
+  p.zeta = ch.ext_challenge();
+  for (auto& e : p.local) ch.observe(e);
+  for (auto& e : p.zs) ch.observe(e);
+  for (auto& e : p.quot) ch.observe(e);
+  for (auto& e : p.next) ch.observe(e);
+  for (auto& e : p.zs_next) ch.observe(e);
+  p.fri_alpha = ch.ext_challenge();
+  p.betas.clear();
+  for (auto& c : p.fri_caps) { for (auto& d : c) for (int i = 0; i < 4; i++) ch.observe(d.e[i]); p.betas.push_back(ch.ext_challenge()); }
+  for (auto& e : p.final_poly) ch.observe(e);
+  ch.observe(p.pow_witness);
+  p.pow_response = ch.challenge();
+  p.indices.resize(p.nqueries);
+  for (auto& x : p.indices) x = (size_t)(ch.challenge().v % ((u64)1 << p.lde_bits));
+}
 
+int verify_finish(const VerifyProof& p, VerifySources& src) {
+  const sbn_config* cfg = &p.cfg;
+  const AirShape& as = p.as;
+  const FriShape& fs = p.fs;
+  const u32 degree_bits = p.degree_bits, lde_bits = p.lde_bits;
+  const size_t ncol = p.ncol, nz = p.nz, npi = p.npi, nqueries = p.nqueries;
+  const E2 zeta = p.zeta, fri_alpha = p.fri_alpha;
   // vanishing polynomial at zeta (verifier.rs verify_stark_proof_with_challenges)
   F g = f_root_of_unity((u32)degree_bits);
   E2 zeta_pow_deg = e2_exp_pow2(zeta, (u32)degree_bits);
@@ -162,7 +203,7 @@ extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const 
   std::vector<E2> apow[SBN_NCH];
   for (int j = 0; j < SBN_NCH; j++) {
     apow[j].resize(apow_len(as.nconstraints, as.nzs));
-    E2 a{F(1), F(0)}, al(alphas[j]);
+    E2 a{F(1), F(0)}, al(p.alphas[j]);
     for (size_t k = 0; k < apow[j].size(); k++) { apow[j][k] = a; a = a * al; }
     cs.alpha[j] = al; cs.apow[j] = apow[j].data();
   }
@@ -170,9 +211,9 @@ extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const 
   cs.z_last = zeta - f_inv(g);
   cs.l_first = z_h_zeta * e2_inv((zeta - F(1)) * nn);        // eval_l_0_and_l_last
   cs.l_last = z_h_zeta * e2_inv((zeta * g - F(1)) * nn);
-  HostRow row{local.data(), next.data()};
-  HostZRow zrow{zs.data(), zs_next.data()};
-  E2 g0(gam[0][0]), g1(gam[1][1]);
+  HostRow row{p.local.data(), p.next.data()};
+  HostZRow zrow{p.zs.data(), p.zs_next.data()};
+  E2 g0(p.gam[0][0]), g1(p.gam[1][1]);
   if (as.kind == SBN_AIR_G1_OP) {
     g1op_eval(cs, row);
     permutation_checks(cs, row, zrow, G1OpShape(), (int)nz, g0, g1);
@@ -189,7 +230,7 @@ extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const 
     flag_u64_eval(cs, row, FlagU64Shape((int)as.num_io));
   } else {
     ExpShape sh = exp_shape(as);
-    std::vector<E2> epi(npi); for (size_t i = 0; i < npi; i++) epi[i] = E2(pi[i]);
+    std::vector<E2> epi(npi); for (size_t i = 0; i < npi; i++) epi[i] = E2(p.pi[i]);
     static thread_local ExpPiConsts<E2> pic;
     const E2* app[SBN_NCH] = {apow[0].data(), apow[1].data()};
     exp_pi_consts<E2>(sh, app, epi.data(), pic);
@@ -198,37 +239,43 @@ extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const 
   }
   for (u32 i = 0; i < cfg->num_challenges; i++) {
     // quotient_degree_factor = 2 chunks per challenge: t(zeta) = t0 + zeta^N t1
-    E2 t = quot[2 * i] + zeta_pow_deg * quot[2 * i + 1];
+    E2 t = p.quot[2 * i] + zeta_pow_deg * p.quot[2 * i + 1];
     if (cs.rem != 0) return fail(SBN_ERR_VERIFY_FAILED, "internal: constraint count mismatch (%d left)", cs.rem);
     if (cs.result((int)i) != z_h_zeta * t) return fail(SBN_ERR_VERIFY_FAILED, "mismatch between evaluation and opening of quotient polynomial");
   }
 
   // verify_fri_proof
   {
-    u32 lz = pow_response.v ? (u32)__builtin_clzll(pow_response.v) : 64;
+    u32 lz = p.pow_response.v ? (u32)__builtin_clzll(p.pow_response.v) : 64;
     if (lz < cfg->proof_of_work_bits) return fail(SBN_ERR_VERIFY_FAILED, "invalid proof of work");
   }
   // batch zeta: trace ++ zs ++ quotient ; batch g*zeta: trace ++ zs
   E2 zeta_next = zeta * g;
   auto reduce = [&](const std::vector<const std::vector<E2>*>& parts) {
     E2 acc{F(0), F(0)};
-    for (size_t p = parts.size(); p-- > 0;) for (size_t j = parts[p]->size(); j-- > 0;) acc = acc * fri_alpha + (*parts[p])[j];
+    for (size_t q = parts.size(); q-- > 0;) for (size_t j = parts[q]->size(); j-- > 0;) acc = acc * fri_alpha + (*parts[q])[j];
     return acc;
   };
-  E2 red0 = reduce({&local, &zs, &quot}), red1 = reduce({&next, &zs_next});
+  E2 red0 = reduce({&p.local, &p.zs, &p.quot}), red1 = reduce({&p.next, &p.zs_next});
   E2 shift1 = e2_pow(fri_alpha, ncol + nz);
-  std::vector<std::vector<Digest4>> init_caps; init_caps.push_back(trace_cap); if (nz) init_caps.push_back(z_cap); init_caps.push_back(q_cap);
+  // the opened rows enter fri_combine_initial as one Horner sum over trace ++ zs ++ quotient: oracle t's own sum P_t times alpha^(columns before it)
+  const size_t ninit = p.num_initial();
+  E2 init_shift[3] = {E2(F(1), F(0)), e2_pow(fri_alpha, ncol), shift1};
+  if (!nz) init_shift[1] = shift1;
   for (size_t q = 0; q < nqueries; q++) {
-    size_t x_index = indices[q];
-    const Round& r = rounds[q];
-    for (size_t t = 0; t < init_caps.size(); t++)
-      if (!merkle_verify(r.init[t].evals.data(), r.init[t].evals.size(), x_index, init_caps[t], r.init[t].sib))
+    size_t x_index = p.indices[q];
+    const VerifyRound& r = p.rounds[q];
+    for (size_t t = 0; t < ninit; t++)
+      if (!src.merkle_ok(q, t))
         return fail(SBN_ERR_VERIFY_FAILED, "invalid Merkle proof (initial oracle %zu, query %zu)", t, q);
     F subgroup_x = F(GL_GEN) * f_pow(f_root_of_unity(lde_bits), bitrev32((u32)x_index, lde_bits));
     // fri_combine_initial
     E2 e0{F(0), F(0)}, e1(F(0), F(0));
-    for (size_t t = init_caps.size(); t-- > 0;) for (size_t j = r.init[t].evals.size(); j-- > 0;) e0 = e0 * fri_alpha + r.init[t].evals[j];
-    for (size_t t = init_caps.size() - 1; t-- > 0;) for (size_t j = r.init[t].evals.size(); j-- > 0;) e1 = e1 * fri_alpha + r.init[t].evals[j];
+    for (size_t t = 0; t < ninit; t++) {
+      const E2 pt = src.row_reduction(q, t) * init_shift[t];
+      e0 = e0 + pt;
+      if (t + 1 < ninit) e1 = e1 + pt;
+    }
     E2 sum = (e0 - red0) * e2_inv(E2(subgroup_x) - zeta);
     sum = sum * shift1 + (e1 - red1) * e2_inv(E2(subgroup_x) - zeta_next);
     // plonky2 0.1.x fri_combine_initial: "Multiply the final polynomial by `X`" (PR #436): `sum * subgroup_x`
@@ -236,21 +283,69 @@ extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const 
     for (size_t i = 0; i < fs.arity_bits.size(); i++) {
       u32 ab = fs.arity_bits[i];
       size_t arity = (size_t)1 << ab, coset_index = x_index >> ab, within = x_index & (arity - 1);
-      const Step& s = r.steps[i];
+      const VerifyStep& s = r.steps[i];
       if (s.evals[within] != old_eval) return fail(SBN_ERR_VERIFY_FAILED, "FRI fold consistency check failed (query %zu, layer %zu)", q, i);
-      old_eval = compute_evaluation(subgroup_x, within, ab, s.evals, betas[i]);
-      std::vector<F> flat(2 * arity);
-      for (size_t j = 0; j < arity; j++) { flat[2 * j] = s.evals[j].a; flat[2 * j + 1] = s.evals[j].b; }
-      if (!merkle_verify(flat.data(), flat.size(), coset_index, fri_caps[i], s.sib))
+      old_eval = compute_evaluation(subgroup_x, within, ab, s.evals, p.betas[i]);
+      if (!src.merkle_ok(q, ninit + i))
         return fail(SBN_ERR_VERIFY_FAILED, "invalid Merkle proof (FRI layer %zu, query %zu)", i, q);
       subgroup_x = f_exp_pow2(subgroup_x, ab);
       x_index = coset_index;
     }
     E2 fe{F(0), F(0)};
-    for (size_t j = final_poly.size(); j-- > 0;) fe = fe * E2(subgroup_x) + final_poly[j];
+    for (size_t j = p.final_poly.size(); j-- > 0;) fe = fe * E2(subgroup_x) + p.final_poly[j];
     if (fe != old_eval) return fail(SBN_ERR_VERIFY_FAILED, "final polynomial evaluation is invalid (query %zu)", q);
   }
   return SBN_OK;
+}
+
+int verify_finish_host(const VerifyProof& p) {
+  if (!p.has_query_rows) return fail(SBN_ERR_BAD_ARG, "internal: the parsed proof carries no query rows");
+  HostSources src(p);
+  return verify_finish(p, src);
+}
+
+bool verify_layout(const AirShape& as, const sbn_config& cfg, u32 degree_bits, VerifyLayout& L) {
+  const FriShape fs = fri_shape(cfg, degree_bits);
+  const u32 lde_bits = degree_bits + cfg.rate_bits;
+  if (lde_bits < cfg.cap_height + fs.total_arity()) return false;
+  const size_t capn = (size_t)1 << cfg.cap_height, ncol = as.ncols, nz = as.nzs, nq = 2 * (size_t)cfg.num_challenges;
+  L.trees.clear();
+  L.nqueries = cfg.num_query_rounds; L.lde_bits = lde_bits; L.ninit = nz ? 3 : 2;
+  size_t pos = 12;
+  std::vector<size_t> cap_off;
+  for (u32 t = 0; t < L.ninit; t++) { cap_off.push_back(pos); pos += capn * 4; }
+  pos += 2 * (2 * ncol + 2 * nz + nq);
+  for (size_t i = 0; i < fs.arity_bits.size(); i++) { cap_off.push_back(pos); pos += capn * 4; }
+  L.query_off = pos;
+  size_t off = 0;
+  const size_t widths[3] = {ncol, nz ? nz : nq, nq};
+  for (u32 t = 0; t < L.ninit; t++) {
+    VerifyTree v{(u32)off, (u32)widths[t], lde_bits - cfg.cap_height, (u32)cap_off[t], 0, 1};
+    L.trees.push_back(v);
+    off += v.leaf_len + 4 * (size_t)v.nsib;
+  }
+  u32 bits = lde_bits, shift = 0;
+  for (size_t i = 0; i < fs.arity_bits.size(); i++) {
+    const u32 ab = fs.arity_bits[i];
+    bits -= ab; shift += ab;
+    VerifyTree v{(u32)off, 2u << ab, bits - cfg.cap_height, (u32)cap_off[L.ninit + i], shift, 0};
+    L.trees.push_back(v);
+    off += v.leaf_len + 4 * (size_t)v.nsib;
+  }
+  L.query_stride = off;
+  pos += off * L.nqueries;
+  pos += 2 * fs.final_poly_len() + 1 + as.npi;
+  L.proof_words = pos;
+  return pos < ((size_t)1 << 32);   // the kernels index a proof with 32-bit word offsets
+}
+
+}  // namespace sbn
+
+extern "C" int sbn_verify(const sbn_air_desc* air, const sbn_config* cfg, const uint8_t* bytes, size_t len) {
+  VerifyProof p;
+  if (int rc = verify_parse(air, cfg, bytes, len, p)) return rc;
+  verify_challenges(p);
+  return verify_finish_host(p);
 }
 
 // Parity hook (include/sbn.h): the table's AIR constraints -- the regrouped templates of air.cuh, here over the base
