@@ -219,6 +219,50 @@ int sbn_prover_generate_trace(sbn_prover* p, const uint32_t* ios, size_t num_io,
 /* Device -> host copy of the loaded trace, column-major [num_columns][N] (tests, debugging). */
 int sbn_prover_read_trace(sbn_prover* p, uint64_t* trace_out);
 
+/* Trace check: which rows of a trace break a constraint -------------------------------------------- */
+/* What starky 0.1.1 prover.rs `check_constraints` does inside prove() in a debug build ([DEP-RECALL]):
+ * every constraint of the table is evaluated on the TRACE domain H (row i against row i + 1 mod N, L_first = [i == 0],
+ * L_last = [i == N - 1], the permutation product Z computed as prove() computes it) and the rows on which one is non-zero are
+ * reported.  prove() itself accepts any canonical matrix and returns a proof that sbn_verify then rejects with a reason about a
+ * quotient opening; this names the row.
+ * A DEBUGGING AID FOR HONEST MISTAKES, NOT A SOUNDNESS STATEMENT: the constraints of a row are folded with powers of two
+ * challenges as in the quotient stage, so a broken row escapes one accumulator with probability of about
+ * (number of constraints) / 2^64.  The challenges come from the host transcript after it has observed a fixed tag, `seed`, the
+ * table kind, num_io, degree_bits and the public inputs: the permutation sets first (tables with Z columns only), then the two
+ * alphas, the order of prove().  The same seed gives the same report from the device form and from the host form.
+ * GRANULARITY: segment and row.  The regrouped evaluator (csrc/air.cuh) merges local Horner sums and cannot name a constraint.
+ * The segments are the four of the quotient stage: 0 = AIR head (public inputs, transitions, flags, gadgets; everything of the
+ * non-Exp tables), 1 = AIR tail of the Exp tables (io pulses, range check), 2 / 3 = the permutation checks of the Z columns
+ * [0, z_split) / [z_split, num_zs).  A wrong cell of a permuted column shows in segment 2 or 3 on row N - 1 only: Z is the
+ * running product, so only its closing row can break. */
+typedef struct sbn_trace_report {
+  uint32_t struct_size;          /* caller sets sizeof(sbn_trace_report) */
+  uint32_t num_segments;         /* 4 */
+  uint64_t rows;                 /* N */
+  uint64_t failing_rows;         /* rows on which any segment is non-zero */
+  uint64_t first_failing_row;    /* UINT64_MAX when failing_rows == 0 */
+  uint64_t seg_failing_rows[4];
+  uint64_t seg_first_row[4];     /* UINT64_MAX when that segment is clean */
+  uint32_t num_zs, z_split;      /* segment 2 = Z columns [0, z_split), segment 3 = [z_split, num_zs) */
+} sbn_trace_report;
+/* The loaded trace of a single-GPU prover, checked on the device (csrc/trace_check.hip: the constraint kernels of the quotient
+ * stage pointed at the trace values, then one reduction).  row_flags_out (optional): [N] bytes, bit s of byte i set when either
+ * accumulator of segment s is non-zero on row i.  SBN_OK = the check ran, the verdict is in the report.  SBN_ERR_BAD_ARG: a null
+ * argument, a wrong struct_size, no trace loaded (also after a failed sbn_prover_generate_trace); SBN_ERR_UNSUPPORTED: the
+ * context of a split prover with world > 1.  The trace stays loaded and untouched (only per-proof scratch is overwritten):
+ * sbn_prover_prove gives the same words before and after. */
+int sbn_prover_check_trace(sbn_prover* p, uint64_t seed, sbn_trace_report* report, uint8_t* row_flags_out);
+/* Device times of the last sbn_prover_check_trace (ms, HIP events): permutation Z, constraint kernels (with the tables of H and
+ * the upload of the alpha powers), reduction, download of the report block; returns the number written. */
+int sbn_prover_check_times(const sbn_prover* p, float* ms_out, int cap);
+/* The same check on host threads (SBN_HOST_THREADS), no device looked for: the same report and the same flags for the same
+ * seed.  Tables and heights as sbn_prover_create accepts them (SBN_ERR_BAD_ARG for an unknown table, SBN_ERR_UNSUPPORTED for a
+ * height it does not prove); a word >= p: SBN_ERR_NON_CANONICAL naming the smallest such index, as sbn_prover_load_trace. */
+int sbn_check_trace_host(const sbn_air_desc* air, const uint64_t* trace_col_major, uint32_t degree_bits,
+                         const uint64_t* public_inputs, size_t n_pi, uint64_t seed,
+                         sbn_trace_report* report, uint8_t* row_flags_out);
+const char* sbn_trace_segment_name(int s);   /* "air_head", "air_tail", "perm_lo", "perm_hi"; "" otherwise */
+
 /* One-shot convenience with the reference's argument list:
  * prove(stark, &config, trace_poly_values, public_inputs) (src/curves/g1/exp.rs:818-825): a device context, then
  * sbn_prover_prove_host_trace.  The context is created and destroyed per call unless sbn_prove_cache_configure keeps it. */
@@ -290,6 +334,10 @@ int sbn_split_prover_load_trace(sbn_split_prover* p, const uint64_t* trace_col_m
 /* The proof of the whole trace, on every rank, word for word the proof sbn_prover_prove gives on one GPU. */
 int sbn_split_prover_prove(sbn_split_prover* p, sbn_proof** out);
 int sbn_split_prover_stage_times(const sbn_split_prover* p, float* ms_out, int cap);
+/* sbn_prover_check_trace on this rank's loaded trace, world = 1 only: with more ranks the Z columns and the rows are shared out
+ * and this returns SBN_ERR_UNSUPPORTED (every rank holds the whole trace: check it with sbn_check_trace_host or on a single-GPU
+ * prover). */
+int sbn_split_prover_check_trace(sbn_split_prover* p, uint64_t seed, sbn_trace_report* report, uint8_t* row_flags_out);
 
 /* Transports that fill an sbn_comm: starky_bn254_amd/csrc/transport.hip ---------------------- */
 /* RCCL over xGMI, one process per GPU, no Python: librccl is loaded at run time (SBN_RCCL_LIB overrides the name), so the

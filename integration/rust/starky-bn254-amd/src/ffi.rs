@@ -41,6 +41,22 @@ pub struct sbn_verifier {
     _opaque: [u8; 0],
 }
 
+/// include/sbn.h `sbn_trace_report`: what sbn_prover_check_trace found, by segment (0 = AIR head, 1 = AIR tail of the Exp tables,
+/// 2 / 3 = the permutation checks of the Z columns below / from `z_split`); `u64::MAX` = no such row.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct sbn_trace_report {
+    pub struct_size: u32,
+    pub num_segments: u32,
+    pub rows: u64,
+    pub failing_rows: u64,
+    pub first_failing_row: u64,
+    pub seg_failing_rows: [u64; 4],
+    pub seg_first_row: [u64; 4],
+    pub num_zs: u32,
+    pub z_split: u32,
+}
+
 pub const SBN_AIR_G1_OP: i32 = 1;
 pub const SBN_AIR_G1_EXP: i32 = 2;
 pub const SBN_AIR_G2_EXP: i32 = 3;
@@ -73,6 +89,8 @@ extern "C" {
     pub fn sbn_prove_cache_configure(budget_bytes: u64) -> i32;
     pub fn sbn_prove_cache_stats(out: *mut u64) -> i32;
     pub fn sbn_first_non_canonical(words: *const u64, count: usize, on_device: i32, index_out: *mut u64) -> i32;
+    pub fn sbn_prover_check_trace(p: *mut sbn_prover, seed: u64, report: *mut sbn_trace_report, row_flags_out: *mut u8) -> i32;
+    pub fn sbn_trace_segment_name(s: i32) -> *const c_char;
     pub fn sbn_prover_stage_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
     pub fn sbn_prover_stage_name(i: i32) -> *const c_char;
     pub fn sbn_prover_describe(p: *const sbn_prover, out: *mut c_char, cap: usize) -> i32;

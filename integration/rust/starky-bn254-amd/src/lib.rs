@@ -197,6 +197,27 @@ impl Prover {
         proof
     }
 
+    /// Which rows of the loaded trace break a constraint (sbn_prover_check_trace): what a debug build of starky's `prove` learns
+    /// from `check_constraints`, for the trace the last `prove` / `prove_host_trace` / `prove_ios` of this prover left on the device.
+    /// `Ok` means the check ran; the verdict is `TraceReport::ok()`.  A debugging aid, not a soundness statement (include/sbn.h).
+    pub fn check_trace(&mut self, seed: u64) -> Result<TraceReport> {
+        let mut raw = ffi::sbn_trace_report { struct_size: std::mem::size_of::<ffi::sbn_trace_report>() as u32, ..Default::default() };
+        check(unsafe { ffi::sbn_prover_check_trace(self.raw, seed, &mut raw, ptr::null_mut()) }, "sbn_prover_check_trace")?;
+        let row = |r: u64| if r == u64::MAX { None } else { Some(r as usize) };
+        Ok(TraceReport {
+            rows: raw.rows as usize,
+            failing_rows: raw.failing_rows as usize,
+            first_failing_row: row(raw.first_failing_row),
+            segments: (0..raw.num_segments as usize)
+                .map(|s| TraceSegment {
+                    name: unsafe { CStr::from_ptr(ffi::sbn_trace_segment_name(s as i32)) }.to_string_lossy().into_owned(),
+                    failing_rows: raw.seg_failing_rows[s] as usize,
+                    first_row: row(raw.seg_first_row[s]),
+                })
+                .collect(),
+        })
+    }
+
     /// Per-stage device times of the last prove() in milliseconds (sbn_prover_stage_times / sbn_prover_stage_name).
     pub fn stage_times(&self) -> Vec<(String, f32)> {
         let mut ms = [0f32; 32];
@@ -204,6 +225,30 @@ impl Prover {
         (0..k)
             .map(|i| (unsafe { CStr::from_ptr(ffi::sbn_prover_stage_name(i as i32)) }.to_string_lossy().into_owned(), ms[i]))
             .collect()
+    }
+}
+
+/// One segment of the constraint stream in a `TraceReport`: "air_head", "air_tail", "perm_lo", "perm_hi".
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct TraceSegment {
+    pub name: String,
+    pub failing_rows: usize,
+    pub first_row: Option<usize>,
+}
+
+/// `Prover::check_trace`: the rows of the trace on which a segment of the constraints is non-zero.  Segment and row are the
+/// granularity; no constraint index.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct TraceReport {
+    pub rows: usize,
+    pub failing_rows: usize,
+    pub first_failing_row: Option<usize>,
+    pub segments: Vec<TraceSegment>,
+}
+
+impl TraceReport {
+    pub fn ok(&self) -> bool {
+        self.failing_rows == 0
     }
 }
 

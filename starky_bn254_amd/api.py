@@ -34,11 +34,12 @@ EXPORTS = [
     "sbn_prover_create", "sbn_prover_destroy", "sbn_prover_load_trace", "sbn_prover_load_trace_device",
     "sbn_prover_prove", "sbn_prover_prove_host_trace", "sbn_prover_stage_times", "sbn_prover_stage_name", "sbn_prover_describe", "sbn_settings_check", "sbn_prover_trace_device_ptr",
     "sbn_prover_generate_trace", "sbn_prover_read_trace",
+    "sbn_prover_check_trace", "sbn_prover_check_times", "sbn_check_trace_host", "sbn_trace_segment_name",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
-    "sbn_split_prover_load_trace", "sbn_split_prover_prove", "sbn_split_prover_stage_times",
+    "sbn_split_prover_load_trace", "sbn_split_prover_prove", "sbn_split_prover_stage_times", "sbn_split_prover_check_trace",
     "sbn_abi_version", "sbn_rccl_unique_id", "sbn_rccl_comm_create", "sbn_rccl_comm_destroy",
     "sbn_local_comm_create", "sbn_local_comm_abort", "sbn_local_comm_destroy", "sbn_comm_selftest",
     "sbn_verifier_create", "sbn_verifier_verify", "sbn_verifier_reason", "sbn_verifier_stage_times", "sbn_verifier_destroy",
@@ -62,6 +63,13 @@ class _Config(C.Structure):
 
 
 FRI_DEFAULT, FRI_TIMES_X, FRI_PLAIN = 0, 1, 2   # sbn_fri_variant (include/sbn.h)
+
+
+class _TraceReport(C.Structure):
+    """sbn_trace_report (include/sbn.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("num_segments", C.c_uint32), ("rows", C.c_uint64), ("failing_rows", C.c_uint64),
+                ("first_failing_row", C.c_uint64), ("seg_failing_rows", C.c_uint64 * 4), ("seg_first_row", C.c_uint64 * 4),
+                ("num_zs", C.c_uint32), ("z_split", C.c_uint32)]
 
 
 def lib_path():
@@ -113,6 +121,12 @@ def lib():
         L.sbn_prover_trace_device_ptr.argtypes = [vp]
         L.sbn_prover_generate_trace.argtypes = [vp, vp, sz, vp]
         L.sbn_prover_read_trace.argtypes = [vp, vp]
+        L.sbn_prover_check_trace.argtypes = [vp, C.c_uint64, C.POINTER(_TraceReport), vp]
+        L.sbn_prover_check_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+        L.sbn_check_trace_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, C.c_uint64, C.POINTER(_TraceReport), vp]
+        L.sbn_trace_segment_name.restype = C.c_char_p
+        L.sbn_trace_segment_name.argtypes = [C.c_int]
+        L.sbn_split_prover_check_trace.argtypes = [vp, C.c_uint64, C.POINTER(_TraceReport), vp]
         L.sbn_batch_prover_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(vp)]
         L.sbn_batch_prover_prove_ios.argtypes = [vp, vp, sz, sz, sz, C.POINTER(vp)]
         L.sbn_batch_prover_destroy.argtypes = [vp]
@@ -482,6 +496,81 @@ def settings_check():
     return dict(kv.partition("=")[::2] for kv in buf.value.decode().split(" "))
 
 
+_NO_ROW = (1 << 64) - 1   # UINT64_MAX: "no such row" in sbn_trace_report
+
+
+class TraceReport:
+    """What Prover.check_trace / check_trace_host found (sbn_trace_report): which rows of the trace break a constraint, by
+    segment (air_head, air_tail, perm_lo, perm_hi).  A debugging aid, not a soundness statement (include/sbn.h).
+    first_failing_row and the segments' first rows are None when nothing fails; row_flags is the uint8 array of per-row
+    segment bits, or None when it was not asked for."""
+
+    def __init__(self, raw, row_flags, rows_per_instance=None):
+        self.rows, self.failing_rows = int(raw.rows), int(raw.failing_rows)
+        self.first_failing_row = None if raw.first_failing_row == _NO_ROW else int(raw.first_failing_row)
+        self.num_zs, self.z_split = int(raw.num_zs), int(raw.z_split)
+        self.segments = [{"name": lib().sbn_trace_segment_name(s).decode(), "failing_rows": int(raw.seg_failing_rows[s]),
+                          "first_row": None if raw.seg_first_row[s] == _NO_ROW else int(raw.seg_first_row[s])}
+                         for s in range(int(raw.num_segments))]
+        self.row_flags = row_flags
+        self.rows_per_instance = rows_per_instance   # Exp and Flag tables: rows of one instance; else None
+
+    @property
+    def ok(self):
+        return self.failing_rows == 0
+
+    def failing_instances(self):
+        """Exp tables: the instances (row // rows_per_instance) with a failing row, ascending.  Every one of them with
+        flags=True; without the flags only what the report itself names (the first failing row of each segment)."""
+        if self.rows_per_instance is None:
+            raise ValueError("this table has no instances")
+        if self.row_flags is not None:
+            return [int(k) for k in np.unique(np.nonzero(self.row_flags)[0] // self.rows_per_instance)]
+        firsts = [s["first_row"] for s in self.segments if s["first_row"] is not None]
+        return sorted({r // self.rows_per_instance for r in firsts})
+
+    def _where(self, row):
+        if self.rows_per_instance is None:
+            return f"row {row}"
+        return f"row {row} (instance {row // self.rows_per_instance}, row {row % self.rows_per_instance} of {self.rows_per_instance})"
+
+    def __str__(self):
+        if self.ok:
+            return f"ok: all {self.rows} rows satisfy the constraints"
+        names = ", ".join(s["name"] for s in self.segments if s["first_row"] == self.first_failing_row)
+        return f"{self._where(self.first_failing_row)}: {names}; {self.failing_rows} row{'s' if self.failing_rows != 1 else ''} fail"
+
+    def __repr__(self):
+        return f"<TraceReport {self}>"
+
+    def __eq__(self, other):
+        if not isinstance(other, TraceReport):
+            return NotImplemented
+        same_flags = (self.row_flags is None) == (other.row_flags is None) and (self.row_flags is None or np.array_equal(self.row_flags, other.row_flags))
+        return same_flags and (self.rows, self.failing_rows, self.first_failing_row, self.num_zs, self.z_split, self.segments) == \
+            (other.rows, other.failing_rows, other.first_failing_row, other.num_zs, other.z_split, other.segments)
+
+
+def _rows_per_instance(stark):
+    if stark.kind in (AIR_G1_EXP, AIR_G2_EXP, AIR_FQ12_EXP, AIR_FQ_EXP, AIR_FLAGS):
+        return 512
+    return 128 if stark.kind in (AIR_FQ12_EXP_U64, AIR_FLAGS_U64) else None
+
+
+def check_trace_host(stark, trace, public_inputs, seed=0, flags=False):
+    """Which rows of `trace` break a constraint of `stark`, on host threads (no device): sbn_check_trace_host.  The same
+    TraceReport, for the same seed, as Prover.check_trace gives for the loaded trace."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    n = trace.shape[1] if trace.ndim == 2 else 0
+    if trace.ndim != 2 or trace.shape[0] != stark.num_columns or n == 0 or n & (n - 1):
+        raise SbnError(-1, "trace shape does not match the table")
+    raw = _TraceReport(struct_size=C.sizeof(_TraceReport))
+    row_flags = np.zeros(n, dtype=np.uint8) if flags else None
+    _check(lib().sbn_check_trace_host(C.byref(stark._d), _ptr(trace), n.bit_length() - 1, _ptr(pi), len(pi), seed, C.byref(raw), _ptr(row_flags)))
+    return TraceReport(raw, row_flags, _rows_per_instance(stark))
+
+
 class Prover:
     """Device context for one (table, degree_bits): buffers stay allocated across proofs."""
 
@@ -513,6 +602,20 @@ class Prover:
         trace = np.zeros((self.stark.num_columns, 1 << self.degree_bits), dtype=np.uint64)
         _check(lib().sbn_prover_read_trace(self._h, _ptr(trace)))
         return trace
+
+    def check_trace(self, seed=0, flags=False):
+        """Which rows of the loaded trace break a constraint (sbn_prover_check_trace: the quotient stage's constraint kernels
+        on the trace domain).  The trace stays loaded; flags=True also returns the per-row segment bits."""
+        raw = _TraceReport(struct_size=C.sizeof(_TraceReport))
+        row_flags = np.zeros(1 << self.degree_bits, dtype=np.uint8) if flags else None
+        _check(lib().sbn_prover_check_trace(self._h, seed, C.byref(raw), _ptr(row_flags)))
+        return TraceReport(raw, row_flags, _rows_per_instance(self.stark))
+
+    def check_times(self):
+        """Device times of the last check_trace() in ms (HIP events)."""
+        buf = (C.c_float * 4)()
+        k = lib().sbn_prover_check_times(self._h, buf, 4)
+        return dict(zip(("perm_z", "constraints", "reduction", "download"), (float(buf[i]) for i in range(k))))
 
     def prove(self):
         h = C.c_void_p()

@@ -844,7 +844,7 @@ static void launch_quotient_kind(sbn_prover* P, const QuotientParams& qp, size_t
   if (qp.seg_mask & 1u) hipLaunchKernelGGL((quotient_kernel<KIND, 0>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
   if (qp.seg_mask & 2u) hipLaunchKernelGGL((quotient_kernel<KIND, 1>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
 }
-static int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
+int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
   switch (P->air.kind) {
     case SBN_AIR_G1_OP: launch_quotient_kind<1>(P, qp, qblocks); break;
     case SBN_AIR_G1_EXP: launch_quotient_kind<2>(P, qp, qblocks); break;
@@ -860,6 +860,66 @@ static int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t
   }
   HIPC(hipGetLastError());
   return 0;
+}
+
+// The Z columns of `pairs` (starky permutation.rs compute_permutation_z_poly) from the trace values; also the trace check's (trace_check.hip).
+void launch_perm_z(sbn_prover* P, const PairCols* pp, size_t cnt, u64 gamma0, u64 gamma1, u64* out, hipStream_t s) {
+  if (cnt == 0) return;
+  const size_t n = P->n;
+  // from 2^13 rows up: chunk products, one wave per column for their prefix / suffix, then Z written once -- 5 words per row
+  // instead of 7 (kernels.cuh permz_chunk_*; the chunk products wait in the idle quotient scratch).  Other shapes: the
+  // one-workgroup-per-column kernel of rounds 1-3.
+  const size_t chunks = n / 2048;
+  if (n >= 8192 && n % 2048 == 0 && cnt <= 65535 && cnt * chunks * 4 <= 2 * 32 * n) {
+    u64* tot = P->d_part; u64* pq = P->d_part + cnt * chunks * 2;
+    hipLaunchKernelGGL(permz_chunk_products_kernel<8>, dim3((unsigned)chunks, (unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0, gamma1, tot);
+    hipLaunchKernelGGL(permz_chunk_scan_kernel, dim3((unsigned)cnt), dim3(64), 0, s, tot, (u32)chunks, pq);
+    hipLaunchKernelGGL(permz_chunk_write_kernel<8>, dim3((unsigned)chunks, (unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0, gamma1, pq, out);
+    return;
+  }
+  if (n % 2048 == 0) hipLaunchKernelGGL(permutation_z_kernel<8>, dim3((unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0, gamma1, out);
+  else if (n % 1024 == 0) hipLaunchKernelGGL(permutation_z_kernel<4>, dim3((unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0, gamma1, out);
+  else hipLaunchKernelGGL(permutation_z_kernel<2>, dim3((unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0, gamma1, out);   // n = 512
+}
+
+// The alpha-power table and the public-input constants of the constraint kernels, for the quotient stage and the trace check alike.
+int upload_alpha_tables(sbn_prover* P, const F alphas[SBN_NCH]) {
+  hipStream_t st = P->stream;
+  const size_t APN = P->apow_n;
+  std::vector<u64> apow((size_t)SBN_NCH * APN);
+  std::vector<F> ap[SBN_NCH];
+  for (int j = 0; j < SBN_NCH; j++) {
+    ap[j].resize(APN);
+    F a(1);
+    for (size_t k = 0; k < APN; k++) { ap[j][k] = a; apow[(size_t)j * APN + k] = a.v; a = a * alphas[j]; }
+  }
+  HIPC(hipMemcpyAsync(P->d_apow, apow.data(), apow.size() * sizeof(u64), hipMemcpyHostToDevice, st));
+  if (is_exp_air(P->air.kind)) {
+    static thread_local ExpPiConsts<F> pic;  // 3 x 2 x 512 field elements
+    const F* app[SBN_NCH] = {ap[0].data(), ap[1].data()};
+    std::vector<F> pif(P->pi.size());
+    for (size_t i = 0; i < pif.size(); i++) pif[i] = F(P->pi[i]);
+    exp_pi_consts<F>(exp_shape(P->air), app, pif.data(), pic);
+    HIPC(hipMemcpyAsync(P->d_pic, &pic, sizeof(pic), hipMemcpyHostToDevice, st));
+  }
+  HIPC(stream_wait(st));
+  return 0;
+}
+void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientParams& qp) {
+  const size_t Z = P->air.nzs;
+  for (int j = 0; j < SBN_NCH; j++) { qp.alpha[j] = alphas[j].v; qp.apow[j] = P->d_apow + (size_t)j * P->apow_n; }
+  qp.num_zs = (int)Z; qp.num_io = (int)P->air.num_io; qp.pic = P->d_pic;
+  // constraints that follow each segment: [AIR head][AIR tail], then the permutation block, whose two segments take the Z
+  // columns below / from zsplit with exponents counted from the end of the stream (nothing follows either of them).
+  // (Measured and dropped: the AIR tail on a third stream beside the other two -- 1.22 -> 1.32 ms for the stage, G2 2.0 -> 2.3.)
+  qp.zsplit = (int)(Z / 2);
+  qp.lookups_in_perm = P->set.quotient_lookups == 1;   // measured slower (quotient stage 1.18 -> 1.25 ms for G1): an experiment switch only
+  const u64 n_tail = is_exp_air(P->air.kind) ? (u64)ExpShape(exp_e(P->air.kind), (int)P->air.num_io).num_tail_constraints() : 0;
+  const u64 after[4] = {n_tail + 2 * (u64)Z, 2 * (u64)Z, 0, 0};
+  qp.seg_count[0] = (int)(P->air.nconstraints - n_tail); qp.seg_count[1] = (int)n_tail;
+  qp.seg_count[2] = qp.seg_count[3] = 2 * (int)Z;
+  for (int sgm = 0; sgm < 4; sgm++) for (int j = 0; j < SBN_NCH; j++) qp.seg_shift[sgm][j] = f_pow(alphas[j], after[sgm]).v;
+  qp.seg_mask = 0xfu;
 }
 
 // up: null for sbn_prover_prove (the trace is resident); else the host trace sbn_prover_prove_host_trace streams in
@@ -911,28 +971,10 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   {
     const size_t zn = S ? S->zr : Z;                       // Z columns computed here (the split: this rank's range)
     const PairCols* pairs = S ? S->d_pairs_own : P->d_pairs;
-    auto launch_z = [&](size_t z0, size_t cnt, hipStream_t s) {
-      if (cnt == 0) return;
-      const PairCols* pp = pairs + z0; u64* out = P->d_zval + z0 * n;
-      // from 2^13 rows up: chunk products, one wave per column for their prefix / suffix, then Z written once -- 5 words per row
-      // instead of 7 (kernels.cuh permz_chunk_*; the chunk products wait in the idle quotient scratch).  Other shapes: the
-      // one-workgroup-per-column kernel of rounds 1-3.
-      const size_t chunks = n / 2048;
-      if (n >= 8192 && n % 2048 == 0 && cnt <= 65535 && cnt * chunks * 4 <= 2 * 32 * n) {
-        u64* tot = P->d_part; u64* pq = P->d_part + cnt * chunks * 2;
-        hipLaunchKernelGGL(permz_chunk_products_kernel<8>, dim3((unsigned)chunks, (unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0.v, gamma1.v, tot);
-        hipLaunchKernelGGL(permz_chunk_scan_kernel, dim3((unsigned)cnt), dim3(64), 0, s, tot, (u32)chunks, pq);
-        hipLaunchKernelGGL(permz_chunk_write_kernel<8>, dim3((unsigned)chunks, (unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0.v, gamma1.v, pq, out);
-        return;
-      }
-      if (n % 2048 == 0) hipLaunchKernelGGL(permutation_z_kernel<8>, dim3((unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0.v, gamma1.v, out);
-      else if (n % 1024 == 0) hipLaunchKernelGGL(permutation_z_kernel<4>, dim3((unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0.v, gamma1.v, out);
-      else hipLaunchKernelGGL(permutation_z_kernel<2>, dim3((unsigned)cnt), dim3(256), 0, s, P->d_trace, n, pp, gamma0.v, gamma1.v, out);   // n = 512
-    };
     // MEASURED and dropped (profiles/r3_ab_z_overlap.txt): only the first column chunk in front of the commit pipeline and the
     // other Z columns on a third stream beside that chunk's transforms and sponge -- the stage in front shrinks by 0.2 ms (a
     // single workgroup's scan chain is 0.36 ms long), the Z commitment grows by 0.44 ms (26.25 -> 26.5 ms per proof, five pairs).
-    launch_z(0, zn, st);
+    launch_perm_z(P, pairs, zn, gamma0.v, gamma1.v, P->d_zval, st);
   }
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(P->ev[ST_Z_COMMIT], st));
@@ -951,26 +993,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   // P3 quotient -------------------------------------------------------------------------------------
   F alphas[SBN_NCH];
   for (int j = 0; j < SBN_NCH; j++) alphas[j] = ch.challenge();
-  {
-    const size_t APN = P->apow_n;
-    std::vector<u64> apow((size_t)SBN_NCH * APN);
-    std::vector<F> ap[SBN_NCH];
-    for (int j = 0; j < SBN_NCH; j++) {
-      ap[j].resize(APN);
-      F a(1);
-      for (size_t k = 0; k < APN; k++) { ap[j][k] = a; apow[(size_t)j * APN + k] = a.v; a = a * alphas[j]; }
-    }
-    HIPC(hipMemcpyAsync(P->d_apow, apow.data(), apow.size() * sizeof(u64), hipMemcpyHostToDevice, st));
-    if (is_exp_air(P->air.kind)) {
-      static thread_local ExpPiConsts<F> pic;  // 3 x 2 x 512 field elements
-      const F* app[SBN_NCH] = {ap[0].data(), ap[1].data()};
-      std::vector<F> pif(P->pi.size());
-      for (size_t i = 0; i < pif.size(); i++) pif[i] = F(P->pi[i]);
-      exp_pi_consts<F>(exp_shape(P->air), app, pif.data(), pic);
-      HIPC(hipMemcpyAsync(P->d_pic, &pic, sizeof(pic), hipMemcpyHostToDevice, st));
-    }
-    HIPC(stream_wait(st));
-  }
+  if ((rc = upload_alpha_tables(P, alphas))) return rc;
   {
     QuotientParams qp{};
     qp.lde = P->d_lde; qp.zlde = P->d_zlde; qp.m = m; qp.next_step = 2;  // 2^quotient_degree_bits
@@ -986,24 +1009,11 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     F gn = f_exp_pow2(F(GL_GEN), P->degree_bits);
     qp.zh_inv[0] = f_inv(gn - F(1)).v; qp.zh_inv[1] = f_inv(-gn - F(1)).v;  // Z_H(7 w^i) = 7^N (-1)^i - 1
     qp.last = f_inv(f_root_of_unity(P->degree_bits)).v;
-    for (int j = 0; j < SBN_NCH; j++) { qp.alpha[j] = alphas[j].v; qp.apow[j] = P->d_apow + (size_t)j * P->apow_n; }
-    qp.gamma0 = gamma0.v; qp.gamma1 = gamma1.v; qp.num_zs = (int)Z; qp.num_io = (int)P->air.num_io; qp.pic = P->d_pic; qp.qout = P->d_q;
+    quotient_segments(P, alphas, qp);
+    qp.gamma0 = gamma0.v; qp.gamma1 = gamma1.v; qp.qout = P->d_q;
     if (S) qp.qout = (u64*)S->comm.send_buf;   // [2][ml]: all-gathered below
     qp.part = P->d_part;   // QSEG x SBN_NCH planes of m words (the FRI combine's scratch, idle here)
-    {
-      // constraints that follow each segment: [AIR head][AIR tail], then the permutation block, whose two segments take the Z
-      // columns below / from zsplit with exponents counted from the end of the stream (nothing follows either of them).
-      // (Measured and dropped: the AIR tail on a third stream beside the other two -- 1.22 -> 1.32 ms for the stage, G2 2.0 -> 2.3.)
-      qp.zsplit = (int)(Z / 2);
-      qp.lookups_in_perm = P->set.quotient_lookups == 1;   // measured slower (quotient stage 1.18 -> 1.25 ms for G1): an experiment switch only
-      const u64 n_tail = is_exp_air(P->air.kind) ? (u64)ExpShape(exp_e(P->air.kind), (int)P->air.num_io).num_tail_constraints() : 0;
-      const u64 after[4] = {n_tail + 2 * (u64)Z, 2 * (u64)Z, 0, 0};
-      qp.seg_count[0] = (int)(P->air.nconstraints - n_tail); qp.seg_count[1] = (int)n_tail;
-      qp.seg_count[2] = qp.seg_count[3] = 2 * (int)Z;
-      for (int sgm = 0; sgm < 4; sgm++) for (int j = 0; j < SBN_NCH; j++) qp.seg_shift[sgm][j] = f_pow(alphas[j], after[sgm]).v;
-    }
     const size_t qblocks = (qp.m + 255) / 256;
-    qp.seg_mask = 0xfu;
 #ifdef SBN_DIAG   // diagnostic builds only (make CXXFLAGS+=-DSBN_DIAG): time single segments; the proof is invalid unless the mask is 15
     { const char* e = std::getenv("SBN_DIAG_QUOTIENT_SEGMASK"); if (e) qp.seg_mask = (u32)atoi(e) & 0xfu; }
     if (qp.seg_mask != 0xfu) HIPC(hipMemsetAsync(qp.part, 0, (size_t)QSEG * SBN_NCH * qp.m * sizeof(u64), st));
@@ -1560,6 +1570,10 @@ extern "C" int sbn_split_prover_load_trace(sbn_split_prover* sp, const uint64_t*
 extern "C" int sbn_split_prover_prove(sbn_split_prover* sp, sbn_proof** out) {
   if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
   return sbn_prover_prove(sp->P, out);
+}
+extern "C" int sbn_split_prover_check_trace(sbn_split_prover* sp, uint64_t seed, sbn_trace_report* rep, uint8_t* row_flags_out) {
+  if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
+  return sbn_prover_check_trace(sp->P, seed, rep, row_flags_out);   // (trace_check.hip refuses world > 1)
 }
 extern "C" int sbn_split_prover_stage_times(const sbn_split_prover* sp, float* ms_out, int cap) {
   if (!sp) return 0;

@@ -1,5 +1,6 @@
-// The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip and by
-// tracegen_device.hip (which fills the trace); every other unit reaches the prover through the C ABI of include/sbn.h.
+// The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
+// tracegen_device.hip (which fills the trace) and by trace_check.hip (which checks it); every other unit reaches the prover
+// through the C ABI of include/sbn.h.
 #pragma once
 #include "host_common.hpp"
 #include "settings.hpp"
@@ -137,4 +138,17 @@ struct sbn_prover {
   u64* h_ring = nullptr;                     // [UPLOAD_SLOTS][UPLOAD_SLOT_WORDS], pinned
   unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
+  float check_ms[4] = {};                    // sbn_prover_check_trace: permutation Z, constraint kernels, reduction, download
 };
+
+// prover.hip, shared with trace_check.hip: the pieces of the permutation and quotient stages that the trace check runs on the
+// trace domain.  All of them enqueue on the prover's streams and leave the waiting to the caller.
+struct QuotientParams;   // kernels_quotient.cuh
+// Z columns [0, cnt) of `pairs` from P->d_trace into out[cnt][n] on stream s (the chunked form from 2^13 rows up uses P->d_part)
+void launch_perm_z(sbn_prover* P, const PairCols* pairs, size_t cnt, u64 gamma0, u64 gamma1, u64* out, hipStream_t s);
+// alpha^k tables into P->d_apow and, for the Exp tables, ExpPiConsts into P->d_pic; waits for the uploads (their sources are locals)
+int upload_alpha_tables(sbn_prover* P, const F alphas[SBN_NCH]);
+// alpha, apow, num_zs, num_io, pic, seg_count, zsplit, seg_shift, lookups_in_perm and seg_mask = 15 of qp
+void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientParams& qp);
+// quotient_kernel<kind, 0 / 1> on P->stream, <kind, 2> on P->hstream
+int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks);

@@ -324,6 +324,13 @@ class SplitProver:
         self._checked(api.lib().sbn_split_prover_prove(self._h, C.byref(h)))
         return api._take_proof(h)
 
+    def check_trace(self, seed=0, flags=False):
+        """Prover.check_trace on this rank's loaded trace; a world of one rank only (SbnError(-7) otherwise)."""
+        raw = api._TraceReport(struct_size=C.sizeof(api._TraceReport))
+        row_flags = np.zeros(1 << self.degree_bits, dtype=np.uint8) if flags else None
+        self._checked(api.lib().sbn_split_prover_check_trace(self._h, seed, C.byref(raw), api._ptr(row_flags)))
+        return api.TraceReport(raw, row_flags, api._rows_per_instance(self.stark))
+
     def stage_times(self):
         buf = (C.c_float * 32)()
         k = api.lib().sbn_split_prover_stage_times(self._h, buf, 32)
