@@ -216,6 +216,29 @@ uint64_t* sbn_prover_trace_device_ptr(sbn_prover* p);
  * (a coordinate >= p, a degenerate instance, a non-canonical exponent), leaves NO trace loaded: sbn_prover_prove then fails
  * with SBN_ERR_BAD_ARG until a trace is generated or loaded again. */
 int sbn_prover_generate_trace(sbn_prover* p, const uint32_t* ios, size_t num_io, uint64_t* pi_out);
+/* Chained instance lists: the call shape of the reference's *_msm tests (test_g1_msm, src/curves/g1/circuit.rs:459-509, and
+ * test_g2_msm, test_fq12_msm, test_fq12_u64_msm), where offset[0] is a fixed start value and offset[k+1] is the output of
+ * instance k, so that the last output is start + sum e_k x_k on the curves and start * prod x_k^e_k in the fields.
+ * kind: one of the five Exp tables (sbn_air_kind).  terms: [count][T] u32, an instance row of the table's `ios` without its
+ * offset words (x, then exp_val): T = 24 (G1_EXP), 40 (G2_EXP), 16 (FQ_EXP), 104 (FQ12_EXP), 98 (FQ12_EXP_U64).  start: the offset
+ * words of instance 0 (16, 32, 8, 96, 96 u32).  ios_out: [count][40 | 72 | 24 | 200 | 194] u32, the explicit list in the layout
+ * the generators above and sbn_prover_generate_trace take: offset[0] = start, offset[k+1] = offset[k] + e_k x_k (curves) or
+ * offset[k] * x_k^e_k (fields, 0^0 = 1), every value canonical and affine.  final_out (optional): the last output, in the word
+ * shape of start.  Any count >= 1; the terms run on the host pool (SBN_HOST_THREADS).
+ * Refused: a coordinate, coefficient or exponent that the generators refuse (>= p: SBN_ERR_BAD_ARG; a FQ12_EXP_U64 exponent that is
+ * not a canonical field element: SBN_ERR_NON_CANONICAL); on the curves a start or an x_k that is not on the table's curve
+ * (y^2 = x^3 + 3, the twist y^2 = x^3 + 3/(9+i); points off the prime-order subgroup of the twist are fine): SBN_ERR_BAD_ARG
+ * naming the instance, because the running sum is independent of its bracketing only inside a group.  The arithmetic that derives
+ * the offsets is complete (identity terms, equal and opposite operands), so SBN_ERR_WITNESS means one of two things only: some
+ * offset (or the last output) is the point at infinity and has no affine form, or the table's own walk of the explicit list is
+ * degenerate (an addition of the chain B[t+1] = B[t] + bit_t 2^t x meets B[t] = +-2^t x), which the generators refuse as well. */
+int sbn_chain_instances(int32_t kind, const uint32_t* terms, size_t count, const uint32_t* start, uint32_t* ios_out, uint32_t* final_out);
+/* sbn_prover_generate_trace on the list sbn_chain_instances derives from (terms, start): same tables, sizes and failure rule (a
+ * failing call leaves NO trace loaded), and on success the same loaded trace and public inputs, word for word.  ios_out
+ * (optional): that list, [num_io][words per instance].  Where the chains of the table run on the device (G1_EXP / G2_EXP under
+ * SBN_TRACEGEN_DEVICE_CHAIN=1 or 2, FQ12_EXP / FQ12_EXP_U64 unless SBN_FQ12_HOST_CHAIN=1) the offsets are built there too and
+ * the instance list never visits the host between the terms and the witness kernels; elsewhere it is derived on the host pool. */
+int sbn_prover_generate_trace_chained(sbn_prover* p, const uint32_t* terms, size_t num_io, const uint32_t* start, uint64_t* pi_out, uint32_t* ios_out);
 /* Device -> host copy of the loaded trace, column-major [num_columns][N] (tests, debugging). */
 int sbn_prover_read_trace(sbn_prover* p, uint64_t* trace_out);
 

@@ -84,6 +84,8 @@ extern "C" {
     pub fn sbn_prover_destroy(p: *mut sbn_prover);
     pub fn sbn_prover_load_trace(p: *mut sbn_prover, trace_col_major: *const u64, public_inputs: *const u64, n_pi: usize) -> i32;
     pub fn sbn_prover_generate_trace(p: *mut sbn_prover, ios: *const u32, num_io: usize, pi_out: *mut u64) -> i32;
+    pub fn sbn_chain_instances(kind: i32, terms: *const u32, count: usize, start: *const u32, ios_out: *mut u32, final_out: *mut u32) -> i32;
+    pub fn sbn_prover_generate_trace_chained(p: *mut sbn_prover, terms: *const u32, num_io: usize, start: *const u32, pi_out: *mut u64, ios_out: *mut u32) -> i32;
     pub fn sbn_prover_prove(p: *mut sbn_prover, out: *mut *mut sbn_proof) -> i32;
     pub fn sbn_prover_prove_host_trace(p: *mut sbn_prover, trace_col_major: *const u64, public_inputs: *const u64, n_pi: usize, out: *mut *mut sbn_proof) -> i32;
     pub fn sbn_prove_cache_configure(budget_bytes: u64) -> i32;

@@ -175,6 +175,34 @@ impl Prover {
         self.finish::<F, C, D>()
     }
 
+    /// The reference's `*_msm` call shape (`test_g1_msm`, src/curves/g1/circuit.rs:459-509): `terms` holds the instance rows
+    /// without their offset words (x, then exp_val), `start` the offset of instance 0, and offset[k+1] is the output of instance
+    /// k; the offsets are derived on the device where the table's chains run there.  Loads the witness and returns
+    /// (public inputs, the explicit instance list as `prove_ios` takes it); `prove_loaded` then proves it.
+    pub fn generate_trace_chained(&mut self, terms: &[u32], start: &[u32]) -> Result<(Vec<u64>, Vec<u32>)> {
+        ensure!(self.io_words > 0, "device witness generation covers the Exp tables");
+        let exp_words = if self.io_words == 194 { 2 } else { 8 };
+        let x_words = (self.io_words - exp_words) / 2;
+        ensure!(terms.len() == (x_words + exp_words) * self.num_io, "terms must hold {} u32 words per instance x {} instances", x_words + exp_words, self.num_io);
+        ensure!(start.len() == x_words, "start must hold {} u32 words", x_words);
+        let mut pi = vec![0u64; self.n_pi];
+        let mut ios = vec![0u32; self.io_words * self.num_io];
+        check(
+            unsafe { ffi::sbn_prover_generate_trace_chained(self.raw, terms.as_ptr(), self.num_io, start.as_ptr(), pi.as_mut_ptr(), ios.as_mut_ptr()) },
+            "sbn_prover_generate_trace_chained",
+        )?;
+        Ok((pi, ios))
+    }
+
+    /// The proof of the witness the last `generate_trace_chained` (or `prove_ios`, `prove`) left on the device.
+    pub fn prove_loaded<F, C, const D: usize>(&mut self) -> Result<StarkProofWithPublicInputs<F, C, D>>
+    where
+        F: RichField + Extendable<D>,
+        C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+    {
+        self.finish::<F, C, D>()
+    }
+
     fn finish<F, C, const D: usize>(&mut self) -> Result<StarkProofWithPublicInputs<F, C, D>>
     where
         F: RichField + Extendable<D>,

@@ -33,7 +33,7 @@ EXPORTS = [
     "sbn_generate_trace_g1_op", "sbn_generate_trace_modular", "sbn_generate_trace_fq12_mul", "sbn_generate_trace_lookup", "sbn_generate_trace_flags", "sbn_generate_trace_flags_u64",
     "sbn_prover_create", "sbn_prover_destroy", "sbn_prover_load_trace", "sbn_prover_load_trace_device",
     "sbn_prover_prove", "sbn_prover_prove_host_trace", "sbn_prover_stage_times", "sbn_prover_stage_name", "sbn_prover_describe", "sbn_settings_check", "sbn_prover_trace_device_ptr",
-    "sbn_prover_generate_trace", "sbn_prover_read_trace",
+    "sbn_prover_generate_trace", "sbn_prover_read_trace", "sbn_chain_instances", "sbn_prover_generate_trace_chained",
     "sbn_prover_check_trace", "sbn_prover_check_times", "sbn_check_trace_host", "sbn_trace_segment_name",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
@@ -121,6 +121,8 @@ def lib():
         L.sbn_prover_trace_device_ptr.argtypes = [vp]
         L.sbn_prover_generate_trace.argtypes = [vp, vp, sz, vp]
         L.sbn_prover_read_trace.argtypes = [vp, vp]
+        L.sbn_chain_instances.argtypes = [C.c_int32, vp, sz, vp, vp, vp]
+        L.sbn_prover_generate_trace_chained.argtypes = [vp, vp, sz, vp, vp, vp]
         L.sbn_prover_check_trace.argtypes = [vp, C.c_uint64, C.POINTER(_TraceReport), vp]
         L.sbn_prover_check_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
         L.sbn_check_trace_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, C.c_uint64, C.POINTER(_TraceReport), vp]
@@ -421,6 +423,35 @@ class Fq12ExpU64Stark(_Stark):
         return self.generate_trace_and_public_inputs(ios)[1]
 
 
+def _chain_words(stark):
+    """(u32 words of x, of the exponent) in an instance row of the Exp table `stark`."""
+    try:
+        return {G1ExpStark.kind: (16, 8), G2ExpStark.kind: (32, 8), FqExpStark.kind: (8, 8), Fq12ExpStark.kind: (96, 8),
+                Fq12ExpU64Stark.kind: (96, 2)}[stark.kind]
+    except KeyError:
+        raise SbnError(-1, "chained instance lists cover the Exp tables") from None
+
+
+def _chain_args(stark, terms, start):
+    xw, ew = _chain_words(stark)
+    terms = np.ascontiguousarray(terms, dtype=np.uint32)
+    start = np.ascontiguousarray(start, dtype=np.uint32).reshape(-1)
+    if terms.ndim != 2 or terms.shape[0] < 1 or terms.shape[1] != xw + ew or start.shape[0] != xw:
+        raise SbnError(-1, f"terms must be [count][{xw + ew}] u32 and start {xw} u32")
+    return terms, start, xw, ew
+
+
+def chain_instances(stark, terms, start):
+    """The explicit instance list of a chained one (sbn_chain_instances): terms = the rows of `ios` without their offset words
+    (x, then exp_val), start = the offset of instance 0; offset[k+1] = output[k].  Returns (ios, final): the list as the
+    generators take it and the last output in the word shape of start.  Any count >= 1; no device needed."""
+    terms, start, xw, ew = _chain_args(stark, terms, start)
+    ios = np.zeros((terms.shape[0], 2 * xw + ew), dtype=np.uint32)
+    final = np.zeros(xw, dtype=np.uint32)
+    _check(lib().sbn_chain_instances(stark.kind, _ptr(terms), terms.shape[0], _ptr(start), _ptr(ios), _ptr(final)))
+    return ios, final
+
+
 class Proof:
     """StarkProofWithPublicInputs as canonical proof words (layout: include/sbn.h)."""
 
@@ -597,6 +628,15 @@ class Prover:
         pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
         _check(lib().sbn_prover_generate_trace(self._h, _ptr(ios), ios.shape[0], _ptr(pi)))
         return pi
+
+    def generate_trace_chained(self, terms, start):
+        """generate_trace on the list chain_instances(stark, terms, start) gives, the offsets built on the device where the
+        table's chains run there; returns (public inputs, ios)."""
+        terms, start, xw, ew = _chain_args(self.stark, terms, start)
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        ios = np.zeros((terms.shape[0], 2 * xw + ew), dtype=np.uint32)
+        _check(lib().sbn_prover_generate_trace_chained(self._h, _ptr(terms), terms.shape[0], _ptr(start), _ptr(pi), _ptr(ios)))
+        return pi, ios
 
     def read_trace(self):
         trace = np.zeros((self.stark.num_columns, 1 << self.degree_bits), dtype=np.uint64)

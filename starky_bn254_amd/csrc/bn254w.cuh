@@ -362,7 +362,7 @@ template <int E> GL_HD Co<E> cone() { Co<E> r; r.c[0] = fq_one(); for (int q = 1
 GL_HD Fq ldq(const u64* base, size_t idx, size_t stride) { Fq r; for (int i = 0; i < 4; i++) r.l[i] = base[i * stride + idx]; return r; }
 GL_HD void stq(u64* base, size_t idx, size_t stride, const Fq& v) { for (int i = 0; i < 4; i++) base[i * stride + idx] = v.l[i]; }
 GL_HD void u32x8_to_u64x4(const uint32_t* w, u64* out) { for (int i = 0; i < 4; i++) out[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32); }
-enum { TG_ERR_DEGENERATE = 1, TG_ERR_WITNESS = 2, TG_ERR_RANGE = 4 };
+enum { TG_ERR_DEGENERATE = 1, TG_ERR_WITNESS = 2, TG_ERR_RANGE = 4, TG_ERR_INFINITY = 8 };   // INFINITY: an offset of a chained list
 
 template <int E> struct Jac { Co<E> X, Y, Z; };
 // dbl-2009-l for y^2 = x^3 + b (no curve constant involved): 2M + 5S.
@@ -388,6 +388,31 @@ template <int E> GL_HD Jac<E> jac_add(const Jac<E>& p, const Jac<E>& q, bool* de
   Co<E> I = cadd(H, H); I = cmul(I, I);
   Co<E> J = cmul(H, I);
   Co<E> r = csub(S2, S1); r = cadd(r, r);
+  Co<E> V = cmul(U1, I);
+  Jac<E> o;
+  o.X = csub(csub(cmul(r, r), J), cadd(V, V));
+  Co<E> sj = cmul(S1, J);
+  o.Y = csub(cmul(r, csub(V, o.X)), cadd(sj, sj));
+  Co<E> zz = cadd(p.Z, q.Z); zz = cmul(zz, zz); zz = csub(csub(zz, Z1Z1), Z2Z2);
+  o.Z = cmul(zz, H);
+  return o;
+}
+
+// COMPLETE addition for the chained instance lists (sbn_chain_instances, tg::chain_prefix_kernel / chain_scan_kernel / chain_rebase_kernel): the point at
+// infinity is Z = 0, equal operands are doubled, opposite operands give infinity.  Otherwise the words of jac_add.  Both curves
+// have odd order, so Y = 0 does not occur on them; jac_double would turn it into Z = 0 all the same.
+template <int E> GL_HD Jac<E> jac_infinity() { Jac<E> r; r.X = cone<E>(); r.Y = cone<E>(); r.Z = csub(r.X, r.X); return r; }
+template <int E> GL_HD Jac<E> jac_add_complete(const Jac<E>& p, const Jac<E>& q) {
+  if (czero<E>(p.Z)) return q;
+  if (czero<E>(q.Z)) return p;
+  Co<E> Z1Z1 = cmul(p.Z, p.Z), Z2Z2 = cmul(q.Z, q.Z);
+  Co<E> U1 = cmul(p.X, Z2Z2), U2 = cmul(q.X, Z1Z1);
+  Co<E> S1 = cmul(cmul(p.Y, q.Z), Z2Z2), S2 = cmul(cmul(q.Y, p.Z), Z1Z1);
+  Co<E> H = csub(U2, U1), r = csub(S2, S1);
+  if (czero<E>(H)) return czero<E>(r) ? jac_double<E>(p) : jac_infinity<E>();
+  Co<E> I = cadd(H, H); I = cmul(I, I);
+  Co<E> J = cmul(H, I);
+  r = cadd(r, r);
   Co<E> V = cmul(U1, I);
   Jac<E> o;
   o.X = csub(csub(cmul(r, r), J), cadd(V, V));

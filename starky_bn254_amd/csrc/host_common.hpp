@@ -121,6 +121,10 @@ unsigned tracegen_host_threads();
 void host_parallel_for(size_t n, const std::function<void(size_t)>& f);
 // tracegen.hip: the curve chains run eight instances per AVX-512 IFMA register on this CPU (0.15 ms per group of eight)
 bool tracegen_host_chains_vectorized();
+// chain_instances.hip: sbn_chain_instances behind its argument checks (kind: sbn_air_kind of an Exp table), and its refusals alone
+// for the curve tables (a coordinate >= p, a point off the curve): what the device derivation of tracegen_device.hip checks first
+int chain_instances_host(int kind, const uint32_t* terms, size_t K, const uint32_t* start, uint32_t* ios, uint32_t* final_out);
+int chain_terms_check_curve(int E, const uint32_t* terms, size_t K, const uint32_t* start);
 // prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)
 size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)

@@ -944,6 +944,146 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
   RC_MARK(8);
 }
 
+// ---- chained instance lists (sbn_prover_generate_trace_chained): offset[0] = start, offset[k+1] = output[k] ------------------------
+// The offsets of the reference's *_msm call shape (src/curves/g1/circuit.rs:459-509) built on the device.  The A chain of an
+// instance (2^t x, or x^(2^t)) does not depend on its offset, so the existing chain kernel runs once on a list whose offsets are all
+// `start` (curves) or one (Fq12) and leaves, per instance, the 256 Jacobian points 2^t x in ja (its B chain and its degenerate
+// flags mean nothing there and are dropped), or x^e in the kernel's compact outputs.  Then
+//   chain_prefix_kernel  I[t] = the sum of the A[s], s <= t, whose bit is set: one workgroup per instance, a Hillis-Steele scan of its
+//                        256 steps in LDS (48 KB for G2); I[255] = e_k x_k;
+//   chain_scan_kernel    ONE workgroup: Hillis-Steele prefix sums of (start, e_0 x_0, e_1 x_1, ...) over K <= 512 lanes, ping-pong
+//                        in global scratch (a Jacobian G2 point is 192 bytes: two copies of 512 do not fit the default LDS), then one
+//                        batch of TG_INV_BATCH Z's per lane for the affine form, written as u32 limbs into the offset words of ios;
+//   fq12_offset_scan_kernel  the same running product in Fq12: K - 1 DEPENDENT products, each spread over 144 lanes as in
+//                        fq12_chain_kernel (a product per lane would be 144 sequential Fq products per level); fq12_rebase_kernel
+//                        then turns the chain of the preliminary list into the chain of the true one, so Fq12 walks its chain once.
+//   chain_rebase_kernel  the B chain of the true list without a second walk: B[t] = offset_k + I[t-1], K x 257 independent additions.
+// Every addition is bnw::jac_add_complete: a term may be the identity, two partial sums may be equal or opposite, and none of that
+// is a property of the explicit list.  The rebased B chain holds other Jacobian representatives than exp_chains would, but
+// affine_lambda_kernel turns every point into its affine form, which is unique, and judges the table's own walk there: a set bit
+// with B[t] = +-A[t] is a zero slope denominator, B[t] at infinity a zero Z, both TG_ERR_DEGENERATE as on the explicit list.
+// Sums in a group do not depend on the bracketing, so the offsets equal sbn_chain_instances' word for word.
+template <int E> __device__ __forceinline__ Jac<E> ld_jac(const u64* p) { Jac<E> r; r.X = ldc<E>(p); r.Y = ldc<E>(p + 4 * E); r.Z = ldc<E>(p + 8 * E); return r; }
+template <int E> __device__ __forceinline__ void st_jac(u64* p, const Jac<E>& v) { stc<E>(p, v.X); stc<E>(p + 4 * E, v.Y); stc<E>(p + 8 * E, v.Z); }
+static constexpr int CT_LANES = 256;   // one lane per step of an instance
+template <int E>
+__global__ void __launch_bounds__(CT_LANES) chain_prefix_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ ja, u64* __restrict__ pre, u64* __restrict__ terms) {
+  __shared__ Jac<E> buf[CT_LANES];
+  const size_t k = blockIdx.x;
+  const int t = threadIdx.x;
+  const uint32_t* e = ios + 8 * (4 * E + 1) * k + 32 * E;
+  Jac<E> cur = ((e[t >> 5] >> (t & 31)) & 1) ? ld_jac<E>(ja + jac_at<E>(k, t, 0)) : jac_infinity<E>();   // (X Y Z of a step are adjacent)
+  for (int d = 1; d < CT_LANES; d <<= 1) {   // Hillis-Steele in one LDS buffer: publish, read the partner, and only then the next level's publish
+    buf[t] = cur;
+    __syncthreads();
+    if (t >= d) cur = jac_add_complete<E>(buf[t - d], cur);
+    __syncthreads();
+  }
+  st_jac<E>(pre + 12 * E * (k * CT_LANES + t), cur);
+  if (t == CT_LANES - 1) st_jac<E>(terms + 12 * E * k, cur);
+}
+// B[0] = offset_k, B[t] = offset_k + I[t-1]: one lane per (instance, step), into the B chain the witness kernels read
+template <int E>
+__global__ void chain_rebase_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ pre, u64* __restrict__ jb) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= K * 257) return;
+  const size_t k = i / 257; const int t = (int)(i % 257);
+  const uint32_t* io = ios + 8 * (4 * E + 1) * k;
+  Jac<E> b; u64 t4[4];
+  for (int q = 0; q < E; q++) { u32x8_to_u64x4(io + 8 * (2 * E + q), t4); b.X.c[q] = to_m(t4); u32x8_to_u64x4(io + 8 * (3 * E + q), t4); b.Y.c[q] = to_m(t4); }
+  b.Z = cone<E>();
+  if (t) b = jac_add_complete<E>(b, ld_jac<E>(pre + 12 * E * (k * CT_LANES + (size_t)(t - 1))));
+  st_jac<E>(jb + jac_at<E>(k, t, 0), b);
+}
+
+static constexpr int CS_LANES = 512;   // >= K: the u16-range-check tables stop at 2^18 rows = 512 instances
+template <int E>
+__global__ void __launch_bounds__(CS_LANES) chain_scan_kernel(uint32_t* ios, size_t K, const u64* __restrict__ terms, u64* s0, u64* s1, int* __restrict__ err) {
+  const size_t IOW = 8 * (4 * E + 1);
+  const size_t k = threadIdx.x;
+  Jac<E> cur = jac_infinity<E>();
+  if (k < K) {
+    if (k == 0) {   // start: the offset every instance of the preliminary list carries
+      u64 t4[4];
+      for (int q = 0; q < E; q++) { u32x8_to_u64x4(ios + 8 * (2 * E + q), t4); cur.X.c[q] = to_m(t4); u32x8_to_u64x4(ios + 8 * (3 * E + q), t4); cur.Y.c[q] = to_m(t4); }
+      cur.Z = cone<E>();
+    } else cur = ld_jac<E>(terms + 12 * E * (k - 1));
+  }
+  u64* buf[2] = {s0, s1};
+  int par = 0;
+  for (size_t d = 1; d < K; d <<= 1, par ^= 1) {
+    if (k < K) st_jac<E>(buf[par] + 12 * E * k, cur);
+    __syncthreads();                                    // one workgroup: the barrier orders its global stores and loads
+    if (k < K && k >= d) cur = jac_add_complete<E>(ld_jac<E>(buf[par] + 12 * E * (k - d)), cur);
+  }
+  if (k < K) st_jac<E>(buf[par] + 12 * E * k, cur);   // (the other buffer than the last level read)
+  __syncthreads();
+  const u64* sum = buf[par];
+  const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
+  if (k >= NL) return;
+  Fq nrm[TG_INV_BATCH];
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = k + (size_t)j * NL;
+    nrm[j] = fq_one();
+    if (i >= K) continue;
+    const Co<E> Z = ldc<E>(sum + 12 * E * i + 8 * E);
+    if (czero<E>(Z)) { atomicOr(err, TG_ERR_INFINITY); continue; }
+    nrm[j] = cnorm(Z);
+  }
+  batch_inverse(nrm);
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = k + (size_t)j * NL;
+    if (i >= K) continue;
+    const Jac<E> p = ld_jac<E>(sum + 12 * E * i);
+    Co<E> v[2];
+    if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
+    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        u64 s[4]; from_m(v[c].c[q], s);
+        for (int w = 0; w < 8; w++) ios[IOW * i + 8 * ((2 + c) * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+      }
+  }
+}
+
+// outs: [K][12][4] = x_k^e_k in standard form (fq12_chain_kernel on offsets of one); start: 12 coefficients of 8 u32 limbs
+__global__ void __launch_bounds__(192) fq12_offset_scan_kernel(uint32_t* ios, size_t iow, size_t K, const uint32_t* __restrict__ start, const u64* __restrict__ outs) {
+  __shared__ Fq B[12], X[12], PB[144];
+  const int tid = threadIdx.x;
+  if (tid < 12) { u64 t4[4]; u32x8_to_u64x4(start + 8 * tid, t4); B[tid] = to_m(t4); }
+  for (size_t k = 0;; k++) {
+    if (tid < 12) {   // lane c owns coefficient c of the running product
+      u64 s[4]; from_m(B[tid], s);
+      for (int w = 0; w < 8; w++) ios[iow * k + 96 + 8 * tid + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+      X[tid] = to_m(outs + (k * 12 + tid) * 4);
+    }
+    if (k + 1 == K) break;
+    __syncthreads();
+    if (tid < 144) PB[tid] = mmul(B[tid / 12], X[tid % 12]);
+    __syncthreads();
+    if (tid < 12) B[tid] = fq12_fold_coeff(PB, tid);   // read again by the products only behind the next barrier
+  }
+}
+
+// The Fq12 chain needs no second walk: products commute, so B[t] = offset_k * B'[t] with B' the chain of the preliminary list
+// (offset one) -- steps + 1 INDEPENDENT products per instance, one workgroup each, in place over cb (standard form); the instance
+// output B[steps] goes to outs again.
+__global__ void __launch_bounds__(192) fq12_rebase_kernel(const uint32_t* __restrict__ ios, size_t iow, int steps, u64* __restrict__ cb, u64* __restrict__ outs) {
+  __shared__ Fq O[12], X[12], PB[144];
+  const size_t entry = blockIdx.x, k = entry / (size_t)(steps + 1);
+  const int tid = threadIdx.x;
+  u64* slot = cb + (entry * 12 + (size_t)(tid < 12 ? tid : 0)) * 4;
+  if (tid < 12) { u64 t4[4]; u32x8_to_u64x4(ios + iow * k + 96 + 8 * tid, t4); O[tid] = to_m(t4); X[tid] = to_m(slot); }
+  __syncthreads();
+  if (tid < 144) PB[tid] = mmul(O[tid / 12], X[tid % 12]);
+  __syncthreads();
+  if (tid < 12) {
+    const Fq v = fq12_fold_coeff(PB, tid);
+    from_m(v, slot);
+    if (entry % (size_t)(steps + 1) == (size_t)steps) from_m(v, outs + (k * 12 + tid) * 4);
+  }
+}
+
 // ---- parity hook (sbn_bn254_fq_batch, tracegen_device.hip): the field helpers above on standard-form operands, 4 words per element --------------
 enum { FQB_MUL = 0, FQB_ADD = 1, FQB_SUB = 2, FQB_INV = 3, FQB_BATCH_INV = 4, FQB_FQ2_INV = 5 };
 // Item i of op: element i, or group i of TG_INV_BATCH elements for FQB_BATCH_INV.  FQB_INV is finv_fermat on the device and inv_std on

@@ -124,6 +124,21 @@ static int pinned_reserve(u64** buf, size_t* words, size_t need) {
   return 0;
 }
 
+// sbn_prover_generate_trace_chained: the offsets are derived on the device from `terms` (instance rows without their offset words)
+// and `start`; the explicit-list call passes none of this and launches what it always launched.
+struct ChainedIn { const uint32_t* terms; const uint32_t* start; uint32_t* ios_out; };
+// the preliminary list: every instance with the same `offset` words (xw words of x, ew of the exponent)
+static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, size_t xw, size_t ew, const uint32_t* offset) {
+  std::vector<uint32_t> ios((2 * xw + ew) * K);
+  for (size_t k = 0; k < K; k++) {
+    uint32_t* io = ios.data() + (2 * xw + ew) * k;
+    memcpy(io, ch.terms + (xw + ew) * k, xw * sizeof(uint32_t));
+    memcpy(io + xw, offset, xw * sizeof(uint32_t));
+    memcpy(io + 2 * xw, ch.terms + (xw + ew) * k + xw, ew * sizeof(uint32_t));
+  }
+  return ios;
+}
+
 // One sbn_prover_generate_trace call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
 struct TraceJob {
   sbn_prover* const P;
@@ -187,6 +202,7 @@ struct TraceJob {
   // the kernels' error word, a degenerate instance first; then the public inputs `pi(k, p)` writes for instance k
   template <typename PublicInputs>
   int finish(int err, uint64_t* pi_out, PublicInputs pi) {
+    if (err & tg::TG_ERR_INFINITY) return fail(SBN_ERR_WITNESS, "an offset of the chained list is the point at infinity");
     if (err & tg::TG_ERR_DEGENERATE) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
     if (err & tg::TG_ERR_WITNESS) return fail(SBN_ERR_WITNESS, "modular witness generation failed");
     if (err & tg::TG_ERR_RANGE) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
@@ -200,9 +216,15 @@ struct TraceJob {
 
 // G1ExpStark / G2ExpStark (E = 1 / 2)
 template <int E>
-static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr) {
   const size_t IOW = 8 * (4 * E + 1);  // u32 words per instance: x and offset (2E Fq each) + exp_val
-  if (int rc = check_below_p(ios, IOW, 4 * E, K, "coordinate")) return rc;
+  std::vector<uint32_t> prelim;        // chained: x, start, exp_val of every instance; the device rewrites the offsets
+  if (ch) {
+    if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a chained list has at most %d instances", tg::CS_LANES);
+    if (int rc = chain_terms_check_curve(E, ch->terms, K, ch->start)) return rc;
+    prelim = preliminary_list(*ch, K, 16 * E, 8, ch->start);
+    ios = prelim.data();
+  } else if (int rc = check_below_p(ios, IOW, 4 * E, K, "coordinate")) return rc;
   HIPC(hipSetDevice(P->device));
   TraceJob J(P, K, IOW);
   const size_t n = J.n;
@@ -216,33 +238,50 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   uint32_t* d_prog[2] = {(uint32_t*)J.take(64 * tg::CP_LANES / 2), (uint32_t*)J.take(64 * tg::CP_LANES / 2)};   // chain programs: <= 64 levels of 64 micro-operations
   int* d_err = (int*)J.take(1);
   unsigned int* d_cnt = J.take_histograms();
+  u64* d_pre = ch ? J.take(12 * E * tg::CT_LANES * K) : nullptr;              // chained: the partial sums of every instance,
+  u64* d_terms = ch ? J.take(12 * E * K) : nullptr;                           // e_k x_k, then the two scan buffers
+  u64* d_scan[2] = {ch ? J.take(12 * E * K) : nullptr, ch ? J.take(12 * E * K) : nullptr};
+  int* d_err_pre = ch ? (int*)J.take(1) : nullptr;                            // flags of the preliminary chains (offsets = start): never read
   if (int rc = J.fits()) return rc;
   if (int rc = range_check_setup(P->device)) return rc;
-  // the instance list in and the outputs + error word back cross through pinned staging
+  // both chains of every instance on the device, flags into `errw` (chain_mode 2 / 1, see below)
+  auto launch_chains = [&](int* errw) -> int {
+    if (P->chain_mode == 2) {
+      static const ChainProgram prog = build_chain_program(E);
+      if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
+      tg::ChainProgDev cp{};
+      for (int b = 0; b < 2; b++) {
+        HIPC(hipMemcpyAsync(d_prog[b], prog.ops[b].data(), prog.ops[b].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        cp.ops[b] = d_prog[b]; cp.levels[b] = prog.levels[b];
+      }
+      for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) cp.in_slot[v * E + q] = (unsigned char)((v < 2 ? v : v + 1) * E + q);   // a.X a.Y | b.X b.Y
+      cp.one_slot[0] = (unsigned char)(2 * E); cp.one_slot[1] = (unsigned char)(5 * E);
+      cp.zero_slot[0] = (unsigned char)(2 * E + 1); cp.zero_slot[1] = (unsigned char)(5 * E + 1);
+      for (int i = 0; i < 6 * E; i++) cp.coord[i] = (unsigned char)i;
+      hipLaunchKernelGGL(tg::chain_coop_kernel<E>, dim3((unsigned)K), dim3(tg::CP_LANES), 0, st, d_ios, K, ja, jb, errw, cp);
+    } else hipLaunchKernelGGL(tg::chain_kernel<E>, blocks(K, 64), dim3(64), 0, st, d_ios, K, ja, jb, errw);
+    return 0;
+  };
+  // the instance list in and the outputs + error word back cross through pinned staging (chained: the derived list comes back too)
   const size_t io_words = (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
-  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words)) return rc;
+  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words + (ch ? io_words : 0))) return rc;
   memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
   u64* const h_out = P->h_io + io_words;
   if (int rc = J.begin(P->h_io, d_ios, d_err)) return rc;
+  if (ch) {   // offsets on the device (kernels_tracegen.cuh, "chained instance lists"); only chain_mode 1 and 2 come here
+    if (int rc = launch_chains(d_err_pre)) return rc;
+    hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, d_pre, d_terms);
+    hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, d_terms, d_scan[0], d_scan[1], d_err);
+    J.mark();
+    ios = (const uint32_t*)(h_out + out_words);   // where the derived list lands, below
+  }
   J.launch_common_columns(tg::flags_kernel, d_ios, inv, 65535);
   // the two 256-step curve chains per instance: host threads while the device writes the input-independent columns
   // chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx picks by the host pool's size): 2 = one wave per instance walking levels of
   // independent Fq operations (tg::chain_coop_kernel), 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host threads +
   // pinned upload
-  if (P->chain_mode == 2) {
-    static const ChainProgram prog = build_chain_program(E);
-    if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
-    tg::ChainProgDev cp{};
-    for (int b = 0; b < 2; b++) {
-      HIPC(hipMemcpyAsync(d_prog[b], prog.ops[b].data(), prog.ops[b].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      cp.ops[b] = d_prog[b]; cp.levels[b] = prog.levels[b];
-    }
-    for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) cp.in_slot[v * E + q] = (unsigned char)((v < 2 ? v : v + 1) * E + q);   // a.X a.Y | b.X b.Y
-    cp.one_slot[0] = (unsigned char)(2 * E); cp.one_slot[1] = (unsigned char)(5 * E);
-    cp.zero_slot[0] = (unsigned char)(2 * E + 1); cp.zero_slot[1] = (unsigned char)(5 * E + 1);
-    for (int i = 0; i < 6 * E; i++) cp.coord[i] = (unsigned char)i;
-    hipLaunchKernelGGL(tg::chain_coop_kernel<E>, dim3((unsigned)K), dim3(tg::CP_LANES), 0, st, d_ios, K, ja, jb, d_err, cp);
-  } else if (P->chain_mode == 1) hipLaunchKernelGGL(tg::chain_kernel<E>, blocks(K, 64), dim3(64), 0, st, d_ios, K, ja, jb, d_err);
+  if (ch) hipLaunchKernelGGL(tg::chain_rebase_kernel<E>, blocks(K * 257, 64), dim3(64), 0, st, d_ios, K, d_pre, jb);   // A is in ja already
+  else if (P->chain_mode) { if (int rc = launch_chains(d_err)) return rc; }
   else {
     if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
     if (tracegen_host_chains(E, ios, K, P->h_chain, P->h_chain + cw)) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
@@ -259,21 +298,33 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h_out, d_out, 16 * E * K * sizeof(u64), hipMemcpyDeviceToHost, st));
   HIPC(hipMemcpyAsync(h_out + 16 * E * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (ch) HIPC(hipMemcpyAsync(h_out + out_words, d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   static const char* const names[] = {"flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
-  if (int rc = J.end(names)) return rc;
+  static const char* const names_chained[] = {"chain_offsets", "flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
+  if (int rc = J.end(ch ? names_chained : names)) return rc;
   // public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156)
-  return J.finish((int)(h_out[16 * E * K] & 0xffffffffu), pi_out, [&](size_t k, u64* p) {
+  const int rc = J.finish((int)(h_out[16 * E * K] & 0xffffffffu), pi_out, [&](size_t k, u64* p) {
     for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
     for (int i = 0; i < 16 * E; i++) p[IOW + i] = h_out[16 * E * k + i];
   });
+  if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
+  return rc;
 }
 
 // Fq12ExpStark: the square-and-multiply chains (no inversion anywhere) on host threads in standard form, then one lane
 // per row for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
-static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr) {
   const bool u64e = P->air.kind == SBN_AIR_FQ12_EXP_U64;        // 128-row instances, one-element exponent
   const size_t IOW = u64e ? 194 : 200;
   const int steps = u64e ? 64 : 256, log_rpb = u64e ? 7 : 9;
+  std::vector<uint32_t> prelim, derived;   // chained: x, one, exp_val of every instance; the device rewrites the offsets
+  if (ch) {
+    if (int rc = check_below_p(ch->start, 96, 12, 1, "coefficient of start")) return rc;
+    uint32_t one[96] = {1};
+    prelim = preliminary_list(*ch, K, 96, IOW - 192, one);
+    derived.resize(IOW * K);
+    ios = prelim.data();
+  }
   if (int rc = check_below_p(ios, IOW, 24, K, "coefficient")) return rc;
   HIPC(hipSetDevice(P->device));
   if (u64e)
@@ -288,8 +339,13 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   u64* d_outs = J.take(K * 48);
   uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
   int* d_err = (int*)J.take(1);
+  uint32_t* d_start = ch ? (uint32_t*)J.take(48) : nullptr;
   if (int rc = J.fits()) return rc;
   if (int rc = J.begin(ios, d_ios, d_err)) return rc;
+  if (ch) {
+    HIPC(hipMemcpyAsync(d_start, ch->start, 96 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ios = derived.data();   // where the derived list lands, below
+  }
   if (u64e) J.launch_common_columns(tg::flags_u64_kernel, d_ios, inv, 255);
   else J.launch_common_columns(tg::flags_kernel, d_ios, inv, 255);
   // the square-and-multiply chains: one workgroup per instance on the device (kernels_tracegen.cuh fq12_chain_kernel);
@@ -301,6 +357,12 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
   } else hipLaunchKernelGGL(tg::fq12_chain_kernel, dim3((unsigned)K), dim3(320), 0, st, d_ios, IOW, steps, ca, cb, d_outs);
   J.mark();
+  if (ch) {   // the chains above ran on offsets of one (device chains only): x^e of every instance is in d_outs; the running product
+    // writes the offsets into d_ios and the chain is rebased onto them (kernels_tracegen.cuh, "chained instance lists")
+    hipLaunchKernelGGL(tg::fq12_offset_scan_kernel, dim3(1), dim3(192), 0, st, d_ios, IOW, K, d_start, d_outs);
+    hipLaunchKernelGGL(tg::fq12_rebase_kernel, dim3((unsigned)(K * (size_t)(steps + 1))), dim3(192), 0, st, d_ios, IOW, steps, cb, d_outs);
+    J.mark();
+  }
   // one lane per (row, output coefficient) by default; SBN_FQ12_ROW_KERNEL=1: round 2's one lane per row (A/B)
   const bool row_kernel = P->set.fq12_row_kernel;
   if (row_kernel) hipLaunchKernelGGL(tg::fq12_row_kernel, blocks(n, 64), dim3(64), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
@@ -316,10 +378,12 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     chain_out.resize(K * 48);
     HIPC(hipMemcpyAsync(chain_out.data(), d_outs, K * 48 * sizeof(u64), hipMemcpyDeviceToHost, st));
   }
+  if (ch) HIPC(hipMemcpyAsync(derived.data(), d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
-  if (int rc = J.end(names)) return rc;
+  static const char* const names_chained[] = {"flags+pulses", "chains", "chain_offsets", "row_witness", "range_check"};
+  if (int rc = J.end(ch ? names_chained : names)) return rc;
   // public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117)
-  return J.finish(err, pi_out, [&](size_t k, u64* p) {
+  const int rc = J.finish(err, pi_out, [&](size_t k, u64* p) {
     for (int c = 0; c < 24; c++)
       for (int i = 0; i < 16; i++) p[16 * c + i] = (ios[IOW * k + 8 * c + (i >> 1)] >> (16 * (i & 1))) & 0xffff;
     if (u64e) p[384] = (u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32);
@@ -328,6 +392,8 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     const int ob = 384 + J.sh.n_exp_slots;
     for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
   });
+  if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
+  return rc;
 }
 
 // FqExpStark: chains on host threads (512 Montgomery products per instance), rows and the u16 range check on the device.
@@ -367,6 +433,31 @@ static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K
     const u64* out = P->h_chain + cw + (k * 257 + 256) * 4;  // B[256]
     for (int i = 0; i < 8; i++) p[24 + i] = (out[i >> 1] >> (32 * (i & 1))) & 0xffffffffULL;
   });
+}
+
+// sbn_prover_generate_trace on the list sbn_chain_instances derives from (terms, start), the offsets built on the device where the
+// chains already run there: G1 / G2 under chain_mode 1 and 2, Fq12 / Fq12U64 unless SBN_FQ12_HOST_CHAIN.  Elsewhere (host-pool
+// curve chains, FqExpStark) the chains are host work anyway and so is the list.
+extern "C" int sbn_prover_generate_trace_chained(sbn_prover* P, const uint32_t* terms, size_t num_io, const uint32_t* start, uint64_t* pi_out, uint32_t* ios_out) {
+  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  if (!terms || !start) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const int kind = P->air.kind;
+  if (!is_exp_air(kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
+  if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
+  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
+  const bool fq12 = kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64;
+  if (!fq12 && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  if (kind == SBN_AIR_FQ_EXP || (fq12 ? P->set.fq12_host_chain : P->chain_mode == 0)) {
+    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
+    if (int rc = chain_instances_host(kind, terms, num_io, start, ios.data(), nullptr)) return rc;
+    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
+    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
+    return rc;
+  }
+  const ChainedIn ch{terms, start, ios_out};
+  if (fq12) return generate_trace_device_fq12(P, nullptr, num_io, pi_out, &ch);
+  return kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, nullptr, num_io, pi_out, &ch) : generate_trace_device<2>(P, nullptr, num_io, pi_out, &ch);
 }
 
 extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
