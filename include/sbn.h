@@ -253,7 +253,8 @@ int sbn_prover_read_trace(sbn_prover* p, uint64_t* trace_out);
  * (number of constraints) / 2^64.  The challenges come from the host transcript after it has observed a fixed tag, `seed`, the
  * table kind, num_io, degree_bits and the public inputs: the permutation sets first (tables with Z columns only), then the two
  * alphas, the order of prove().  The same seed gives the same report from the device form and from the host form.
- * GRANULARITY: segment and row.  The regrouped evaluator (csrc/air.cuh) merges local Horner sums and cannot name a constraint.
+ * GRANULARITY of this report: segment and row.  sbn_explain_rows_host / sbn_prover_explain_rows below name the constraint BLOCKS a
+ * row breaks (the emissions of the regrouped evaluator, csrc/air.cuh).
  * The segments are the four of the quotient stage: 0 = AIR head (public inputs, transitions, flags, gadgets; everything of the
  * non-Exp tables), 1 = AIR tail of the Exp tables (io pulses, range check), 2 / 3 = the permutation checks of the Z columns
  * [0, z_split) / [z_split, num_zs).  A wrong cell of a permuted column shows in segment 2 or 3 on row N - 1 only: Z is the
@@ -285,6 +286,68 @@ int sbn_check_trace_host(const sbn_air_desc* air, const uint64_t* trace_col_majo
                          const uint64_t* public_inputs, size_t n_pi, uint64_t seed,
                          sbn_trace_report* report, uint8_t* row_flags_out);
 const char* sbn_trace_segment_name(int s);   /* "air_head", "air_tail", "perm_lo", "perm_hi"; "" otherwise */
+
+/* Explain: which constraint BLOCKS a failing row breaks ------------------------------------------------ */
+/* The regrouped evaluator (csrc/air.cuh) does not fold constraints one by one: it EMITS either one constraint or a gadget's
+ * local sum over `count` consecutive constraints with the filter factored out.  The sequence of emissions depends on the table
+ * (kind, num_io) only and is in the emission order of the reference's eval_packed_generic; every emission is one block.  A
+ * recording form of the consumer (csrc/air_record.cuh; the forms the prover and the verifier run are untouched) reduces the
+ * contribution of each emission alone under both challenges and flags the block when either is non-zero.
+ * A BLOCK IS THE GRANULARITY: inside a merged block (a gadget: up to 792 constraints; the public-input binding: num_pi
+ * constraints; a transition case; the flags) the factored sums cannot separate constraints.  The same disclaimer as for the
+ * trace check: a debugging aid, a broken block escapes with probability of about count / 2^64.
+ * Sections (sbn_constraint_block.section, names from sbn_constraint_section_name):
+ *    0 output_pulse_sum            is_final - sum of the output pulses (Exp and Flag tables)
+ *    1 public_inputs               the public-input binding of the Exp tables, num_pi constraints in one block
+ *    2 transition_double, 3 transition_add, 4 transition_hold
+ *                                  the three cases of the state transition of the Exp tables (square / multiply / hold in
+ *                                  the square-and-multiply tables FQ_EXP, FQ12_EXP, FQ12_EXP_U64)
+ *    5 flags, 10 flags_repeat      eval_flags and its second emission after the gadgets (one block each)
+ *    6 gadget_add, 7 gadget_double the curve gadgets (G1_OP, G1_EXP, G2_EXP), one block each
+ *    8 gadget_sq, 9 gadget_mul     the field gadgets (FQ_EXP, FQ12_EXP, FQ12_EXP_U64; MODULAR and FQ12_MUL have gadget_mul only)
+ *   11 rotation_pulse              the five constraints of the periodic pulse, instance = 0..4
+ *   12 io_pulse                    the counter's two constraints (no instance), then two per pulse position, instance = position
+ *   13 range_check_recomposition   split range check: target = lo + 256 hi, instance = range-checked column k
+ *   14 range_check_lookup          the two constraints of every lookup pair, one block each, instance = range-checked column k
+ *                                  (a split range check has a lo and a hi pair per column)
+ *   15 range_table                 the three constraints of the range table column
+ *   16 lookup                      the two lookup constraints of the LOOKUP table */
+typedef struct sbn_constraint_block {
+  uint32_t first, count;     /* constraints [first, first + count) of the table's AIR stream, in the emission order of
+                                eval_packed_generic: 0 = the first constraint emitted (its weight is alpha^(n-1)) */
+  uint32_t segment;          /* 0 = air_head, 1 = air_tail: the segments of sbn_trace_report */
+  uint32_t section;          /* what the block is, see above */
+  uint32_t instance;         /* index inside the section where it has one (io pulse i, range-checked column k), else UINT32_MAX */
+  uint32_t col_first, col_count; /* the most specific span of trace columns the block is about (0, 0 where there is none) */
+} sbn_constraint_block;
+/* The block table of a table, no device: recorded by running the recording consumer once over a zero row, so it cannot drift
+ * from the evaluator.  Writes min(B, cap) entries (out may be null) and returns B; 0 for an unknown table.  The blocks are in
+ * order, partition [0, sbn_air_num_constraints), and the head / tail boundary of the Exp tables is a block boundary. */
+size_t sbn_air_constraint_blocks(const sbn_air_desc* air, sbn_constraint_block* out, size_t cap);
+const char* sbn_constraint_section_name(int section);   /* "" for a value that is no section */
+/* The trace columns whose permutation Z column z checks (lhs against rhs), z < sbn_air_num_permutation_zs. */
+int sbn_air_permutation_pair(const sbn_air_desc* air, size_t z, uint32_t* lhs_col, uint32_t* rhs_col);
+/* rows[n_rows]: any rows of the trace.  block_flags_out: [n_rows][(B + 7) / 8] bytes, bit b of row r's entry = block b is non-zero
+ * on rows[r] (row i against row i + 1 mod N, the selectors of the trace domain, the challenges of sbn_check_trace_host for the
+ * same seed).  z_flags_out (optional; tables with Z columns): [n_rows][(num_zs + 7) / 8], bit z = the first-row constraint or the
+ * transition of Z column z is non-zero on that row, Z computed as prove() computes it.  Host threads, no device looked for;
+ * argument checks, canonical-form refusal, tables and heights as sbn_check_trace_host; a row >= N: SBN_ERR_BAD_ARG. */
+int sbn_explain_rows_host(const sbn_air_desc* air, const uint64_t* trace_col_major, uint32_t degree_bits, const uint64_t* public_inputs,
+                          size_t n_pi, uint64_t seed, const uint64_t* rows, size_t n_rows, uint8_t* block_flags_out, uint8_t* z_flags_out);
+typedef struct sbn_block_stat { uint64_t failing_rows, first_row; } sbn_block_stat;   /* first_row = UINT64_MAX when clean */
+/* The same over EVERY row, summed: block_stats_out[B], z_stats_out[num_zs] (optional).  The summary a systematically wrong column
+ * needs: "gadget_add [181, 346) fails on 65,024 rows, first on row 1". */
+int sbn_explain_trace_host(const sbn_air_desc* air, const uint64_t* trace_col_major, uint32_t degree_bits, const uint64_t* public_inputs,
+                           size_t n_pi, uint64_t seed, sbn_block_stat* block_stats_out, sbn_block_stat* z_stats_out);
+/* The same two on the loaded trace of a single-GPU prover (csrc/trace_explain.hip: one thread per row runs the evaluator through
+ * the recording consumer; a wave ballots every block and one lane adds the count), bit for bit what the host forms give for the
+ * same seed.  SBN_ERR_BAD_ARG: a null argument, a row >= N, no trace loaded; SBN_ERR_UNSUPPORTED: the context of a split prover
+ * with world > 1.  Only per-proof scratch is overwritten: sbn_prover_prove gives the same words before and after. */
+int sbn_prover_explain_rows(sbn_prover* p, uint64_t seed, const uint64_t* rows, size_t n_rows, uint8_t* block_flags_out, uint8_t* z_flags_out);
+int sbn_prover_explain_trace(sbn_prover* p, uint64_t seed, sbn_block_stat* block_stats_out, sbn_block_stat* z_stats_out);
+/* Device times of the last explain call (ms, HIP events): permutation Z, explain kernels (with the tables of H and the upload of
+ * the alpha powers), reduction / download; returns the number written. */
+int sbn_prover_explain_times(const sbn_prover* p, float* ms_out, int cap);
 
 /* One-shot convenience with the reference's argument list:
  * prove(stark, &config, trace_poly_values, public_inputs) (src/curves/g1/exp.rs:818-825): a device context, then
@@ -361,6 +424,9 @@ int sbn_split_prover_stage_times(const sbn_split_prover* p, float* ms_out, int c
  * and this returns SBN_ERR_UNSUPPORTED (every rank holds the whole trace: check it with sbn_check_trace_host or on a single-GPU
  * prover). */
 int sbn_split_prover_check_trace(sbn_split_prover* p, uint64_t seed, sbn_trace_report* report, uint8_t* row_flags_out);
+/* sbn_prover_explain_rows / sbn_prover_explain_trace on this rank's loaded trace, world = 1 only, as the check. */
+int sbn_split_prover_explain_rows(sbn_split_prover* p, uint64_t seed, const uint64_t* rows, size_t n_rows, uint8_t* block_flags_out, uint8_t* z_flags_out);
+int sbn_split_prover_explain_trace(sbn_split_prover* p, uint64_t seed, sbn_block_stat* block_stats_out, sbn_block_stat* z_stats_out);
 
 /* Transports that fill an sbn_comm: starky_bn254_amd/csrc/transport.hip ---------------------- */
 /* RCCL over xGMI, one process per GPU, no Python: librccl is loaded at run time (SBN_RCCL_LIB overrides the name), so the

@@ -57,6 +57,27 @@ pub struct sbn_trace_report {
     pub z_split: u32,
 }
 
+/// include/sbn.h `sbn_constraint_block`: one emission of the regrouped evaluator, constraints `[first, first + count)` of the AIR stream.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct sbn_constraint_block {
+    pub first: u32,
+    pub count: u32,
+    pub segment: u32,
+    pub section: u32,
+    pub instance: u32,
+    pub col_first: u32,
+    pub col_count: u32,
+}
+
+/// include/sbn.h `sbn_block_stat`: rows on which a block (or a Z column) is non-zero, and the first of them (`u64::MAX`: none).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct sbn_block_stat {
+    pub failing_rows: u64,
+    pub first_row: u64,
+}
+
 pub const SBN_AIR_G1_OP: i32 = 1;
 pub const SBN_AIR_G1_EXP: i32 = 2;
 pub const SBN_AIR_G2_EXP: i32 = 3;
@@ -93,6 +114,15 @@ extern "C" {
     pub fn sbn_first_non_canonical(words: *const u64, count: usize, on_device: i32, index_out: *mut u64) -> i32;
     pub fn sbn_prover_check_trace(p: *mut sbn_prover, seed: u64, report: *mut sbn_trace_report, row_flags_out: *mut u8) -> i32;
     pub fn sbn_trace_segment_name(s: i32) -> *const c_char;
+    pub fn sbn_air_num_permutation_zs(air: *const sbn_air_desc, cfg: *const sbn_config) -> usize;
+    pub fn sbn_air_constraint_blocks(air: *const sbn_air_desc, out: *mut sbn_constraint_block, cap: usize) -> usize;
+    pub fn sbn_constraint_section_name(section: i32) -> *const c_char;
+    pub fn sbn_air_permutation_pair(air: *const sbn_air_desc, z: usize, lhs_col: *mut u32, rhs_col: *mut u32) -> i32;
+    pub fn sbn_explain_rows_host(air: *const sbn_air_desc, trace_col_major: *const u64, degree_bits: u32, public_inputs: *const u64, n_pi: usize, seed: u64, rows: *const u64, n_rows: usize, block_flags_out: *mut u8, z_flags_out: *mut u8) -> i32;
+    pub fn sbn_explain_trace_host(air: *const sbn_air_desc, trace_col_major: *const u64, degree_bits: u32, public_inputs: *const u64, n_pi: usize, seed: u64, block_stats_out: *mut sbn_block_stat, z_stats_out: *mut sbn_block_stat) -> i32;
+    pub fn sbn_prover_explain_rows(p: *mut sbn_prover, seed: u64, rows: *const u64, n_rows: usize, block_flags_out: *mut u8, z_flags_out: *mut u8) -> i32;
+    pub fn sbn_prover_explain_trace(p: *mut sbn_prover, seed: u64, block_stats_out: *mut sbn_block_stat, z_stats_out: *mut sbn_block_stat) -> i32;
+    pub fn sbn_prover_explain_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
     pub fn sbn_prover_stage_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
     pub fn sbn_prover_stage_name(i: i32) -> *const c_char;
     pub fn sbn_prover_describe(p: *const sbn_prover, out: *mut c_char, cap: usize) -> i32;

@@ -89,6 +89,8 @@ pub struct Prover {
     n_cols: usize,
     degree_bits: usize,
     io_words: usize,
+    blocks: Vec<ConstraintBlock>,
+    num_zs: usize,
 }
 // one prover belongs to one thread at a time (include/sbn.h, "Threading")
 unsafe impl Send for Prover {}
@@ -115,7 +117,40 @@ impl Prover {
             n_cols: unsafe { ffi::sbn_air_num_columns(&a) },
             degree_bits,
             io_words,
+            blocks: constraint_blocks_of(&a),
+            num_zs: unsafe { ffi::sbn_air_num_permutation_zs(&a, &cfg) },
         })
+    }
+
+    /// The blocks of the table's constraint stream (sbn_air_constraint_blocks): what `explain_rows` / `explain_trace` name.
+    pub fn constraint_blocks(&self) -> &[ConstraintBlock] {
+        &self.blocks
+    }
+
+    /// Which constraint blocks and permutation Z columns the listed rows of the loaded trace break (sbn_prover_explain_rows).
+    /// A block is the granularity: inside a merged block the factored sums cannot separate constraints (include/sbn.h).
+    pub fn explain_rows(&mut self, rows: &[u64], seed: u64) -> Result<Vec<RowExplanation>> {
+        let (bb, zb) = ((self.blocks.len() + 7) / 8, (self.num_zs + 7) / 8);
+        let (mut bf, mut zf) = (vec![0u8; rows.len() * bb], vec![0u8; rows.len() * zb]);
+        check(
+            unsafe { ffi::sbn_prover_explain_rows(self.raw, seed, rows.as_ptr(), rows.len(), bf.as_mut_ptr(), zf.as_mut_ptr()) },
+            "sbn_prover_explain_rows",
+        )?;
+        let set = |bits: &[u8], n: usize| (0..n).filter(|i| (bits[i >> 3] >> (i & 7)) & 1 == 1).collect::<Vec<usize>>();
+        Ok(rows
+            .iter()
+            .enumerate()
+            .map(|(k, &r)| RowExplanation { row: r as usize, blocks: set(&bf[k * bb..(k + 1) * bb], self.blocks.len()), zs: set(&zf[k * zb..(k + 1) * zb], self.num_zs) })
+            .collect())
+    }
+
+    /// Per block and per Z column, on how many rows of the loaded trace it fails and where first (sbn_prover_explain_trace).
+    pub fn explain_trace(&mut self, seed: u64) -> Result<TraceExplanation> {
+        let mut bs = vec![ffi::sbn_block_stat::default(); self.blocks.len()];
+        let mut zs = vec![ffi::sbn_block_stat::default(); self.num_zs];
+        check(unsafe { ffi::sbn_prover_explain_trace(self.raw, seed, bs.as_mut_ptr(), zs.as_mut_ptr()) }, "sbn_prover_explain_trace")?;
+        let stat = |s: &ffi::sbn_block_stat| BlockStat { failing_rows: s.failing_rows as usize, first_row: if s.first_row == u64::MAX { None } else { Some(s.first_row as usize) } };
+        Ok(TraceExplanation { blocks: bs.iter().map(stat).collect(), zs: zs.iter().map(stat).collect() })
     }
 
     /// `prove(stark, &config, trace, pi, &mut timing)` with a host-built trace: column-major already, one copy to
@@ -265,7 +300,7 @@ pub struct TraceSegment {
 }
 
 /// `Prover::check_trace`: the rows of the trace on which a segment of the constraints is non-zero.  Segment and row are the
-/// granularity; no constraint index.
+/// granularity of this report; `Prover::explain_rows` names the constraint blocks a row breaks.
 #[derive(Clone, Debug, PartialEq, Eq)]
 pub struct TraceReport {
     pub rows: usize,
@@ -277,6 +312,64 @@ pub struct TraceReport {
 impl TraceReport {
     pub fn ok(&self) -> bool {
         self.failing_rows == 0
+    }
+}
+
+/// One block of a table's constraint stream (include/sbn.h `sbn_constraint_block`).
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct ConstraintBlock {
+    pub first: usize,
+    pub count: usize,
+    /// 0 = air_head, 1 = air_tail
+    pub segment: usize,
+    /// the section name of sbn_constraint_section_name: "gadget_add", "range_check_lookup", ..
+    pub section: String,
+    pub instance: Option<usize>,
+    pub col_first: usize,
+    pub col_count: usize,
+}
+
+fn constraint_blocks_of(a: &ffi::sbn_air_desc) -> Vec<ConstraintBlock> {
+    let n = unsafe { ffi::sbn_air_constraint_blocks(a, ptr::null_mut(), 0) };
+    let mut raw = vec![ffi::sbn_constraint_block::default(); n];
+    unsafe { ffi::sbn_air_constraint_blocks(a, raw.as_mut_ptr(), n) };
+    raw.iter()
+        .map(|b| ConstraintBlock {
+            first: b.first as usize,
+            count: b.count as usize,
+            segment: b.segment as usize,
+            section: unsafe { CStr::from_ptr(ffi::sbn_constraint_section_name(b.section as i32)) }.to_string_lossy().into_owned(),
+            instance: if b.instance == u32::MAX { None } else { Some(b.instance as usize) },
+            col_first: b.col_first as usize,
+            col_count: b.col_count as usize,
+        })
+        .collect()
+}
+
+/// `Prover::explain_rows`: the indices (into `Prover::constraint_blocks`) of the blocks and the Z columns one row breaks.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct RowExplanation {
+    pub row: usize,
+    pub blocks: Vec<usize>,
+    pub zs: Vec<usize>,
+}
+
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct BlockStat {
+    pub failing_rows: usize,
+    pub first_row: Option<usize>,
+}
+
+/// `Prover::explain_trace`: one `BlockStat` per block of `Prover::constraint_blocks` and per permutation Z column.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct TraceExplanation {
+    pub blocks: Vec<BlockStat>,
+    pub zs: Vec<BlockStat>,
+}
+
+impl TraceExplanation {
+    pub fn ok(&self) -> bool {
+        self.blocks.iter().chain(self.zs.iter()).all(|s| s.failing_rows == 0)
     }
 }
 

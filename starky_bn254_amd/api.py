@@ -35,6 +35,8 @@ EXPORTS = [
     "sbn_prover_prove", "sbn_prover_prove_host_trace", "sbn_prover_stage_times", "sbn_prover_stage_name", "sbn_prover_describe", "sbn_settings_check", "sbn_prover_trace_device_ptr",
     "sbn_prover_generate_trace", "sbn_prover_read_trace", "sbn_chain_instances", "sbn_prover_generate_trace_chained",
     "sbn_prover_check_trace", "sbn_prover_check_times", "sbn_check_trace_host", "sbn_trace_segment_name",
+    "sbn_air_constraint_blocks", "sbn_constraint_section_name", "sbn_air_permutation_pair", "sbn_explain_rows_host", "sbn_explain_trace_host",
+    "sbn_prover_explain_rows", "sbn_prover_explain_trace", "sbn_prover_explain_times", "sbn_split_prover_explain_rows", "sbn_split_prover_explain_trace",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
@@ -70,6 +72,16 @@ class _TraceReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_segments", C.c_uint32), ("rows", C.c_uint64), ("failing_rows", C.c_uint64),
                 ("first_failing_row", C.c_uint64), ("seg_failing_rows", C.c_uint64 * 4), ("seg_first_row", C.c_uint64 * 4),
                 ("num_zs", C.c_uint32), ("z_split", C.c_uint32)]
+
+
+class _ConstraintBlock(C.Structure):
+    """sbn_constraint_block (include/sbn.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("first", "count", "segment", "section", "instance", "col_first", "col_count")]
+
+
+class _BlockStat(C.Structure):
+    """sbn_block_stat (include/sbn.h)."""
+    _fields_ = [("failing_rows", C.c_uint64), ("first_row", C.c_uint64)]
 
 
 def lib_path():
@@ -129,6 +141,18 @@ def lib():
         L.sbn_trace_segment_name.restype = C.c_char_p
         L.sbn_trace_segment_name.argtypes = [C.c_int]
         L.sbn_split_prover_check_trace.argtypes = [vp, C.c_uint64, C.POINTER(_TraceReport), vp]
+        L.sbn_air_constraint_blocks.restype = sz
+        L.sbn_air_constraint_blocks.argtypes = [C.POINTER(_AirDesc), vp, sz]
+        L.sbn_constraint_section_name.restype = C.c_char_p
+        L.sbn_constraint_section_name.argtypes = [C.c_int]
+        L.sbn_air_permutation_pair.argtypes = [C.POINTER(_AirDesc), sz, C.POINTER(u32), C.POINTER(u32)]
+        L.sbn_explain_rows_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, C.c_uint64, vp, sz, vp, vp]
+        L.sbn_explain_trace_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, C.c_uint64, vp, vp]
+        L.sbn_prover_explain_rows.argtypes = [vp, C.c_uint64, vp, sz, vp, vp]
+        L.sbn_prover_explain_trace.argtypes = [vp, C.c_uint64, vp, vp]
+        L.sbn_prover_explain_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+        L.sbn_split_prover_explain_rows.argtypes = [vp, C.c_uint64, vp, sz, vp, vp]
+        L.sbn_split_prover_explain_trace.argtypes = [vp, C.c_uint64, vp, vp]
         L.sbn_batch_prover_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(vp)]
         L.sbn_batch_prover_prove_ios.argtypes = [vp, vp, sz, sz, sz, C.POINTER(vp)]
         L.sbn_batch_prover_destroy.argtypes = [vp]
@@ -221,6 +245,25 @@ class _Stark:
 
     def constraint_degree(self):
         return 3
+
+    def constraint_blocks(self):
+        """The blocks of the table's constraint stream (sbn_air_constraint_blocks): the emissions of the regrouped evaluator, in
+        order, as ConstraintBlock objects.  What explain_rows / explain_trace name."""
+        blocks = getattr(self, "_blocks", None)
+        if blocks is None:
+            B = lib().sbn_air_constraint_blocks(C.byref(self._d), None, 0)
+            if B == 0:
+                raise SbnError(-1, lib().sbn_last_error().decode())
+            raw = (_ConstraintBlock * B)()
+            lib().sbn_air_constraint_blocks(C.byref(self._d), raw, B)
+            blocks = self._blocks = [ConstraintBlock(b, r) for b, r in enumerate(raw)]
+        return blocks
+
+    def permutation_pair(self, z):
+        """(lhs column, rhs column) of permutation Z column z (sbn_air_permutation_pair)."""
+        lhs, rhs = C.c_uint32(), C.c_uint32()
+        _check(lib().sbn_air_permutation_pair(C.byref(self._d), z, C.byref(lhs), C.byref(rhs)))
+        return int(lhs.value), int(rhs.value)
 
 
 class G1Stark(_Stark):
@@ -602,6 +645,160 @@ def check_trace_host(stark, trace, public_inputs, seed=0, flags=False):
     return TraceReport(raw, row_flags, _rows_per_instance(stark))
 
 
+class ConstraintBlock:
+    """One block of a table's constraint stream (sbn_constraint_block): constraints [first, first + count) in emission order,
+    the segment of the trace check it belongs to, what it is (section, instance) and the trace columns it is about."""
+
+    def __init__(self, index, raw):
+        self.index, self.first, self.count, self.segment = index, int(raw.first), int(raw.count), int(raw.segment)
+        self.section = int(raw.section)
+        self.name = lib().sbn_constraint_section_name(self.section).decode()
+        self.instance = None if raw.instance == 0xFFFFFFFF else int(raw.instance)
+        self.col_first, self.col_count = int(raw.col_first), int(raw.col_count)
+
+    def __str__(self):
+        s = self.name + (f"[{self.instance}]" if self.instance is not None else "")
+        if self.count > 1:
+            s += f" [{self.first}, {self.first + self.count})"
+        if self.col_count:
+            s += f" cols {self.col_first}..{self.col_first + self.col_count}"
+        return s
+
+    def __repr__(self):
+        return f"<ConstraintBlock {self.index}: {self}>"
+
+
+def _set_bits(bits, count):
+    return [int(i) for i in np.nonzero(np.unpackbits(bits, bitorder="little")[:count])[0]]
+
+
+class RowExplanation:
+    """The blocks and the permutation Z columns one row breaks.  str() reads like a diagnosis."""
+
+    def __init__(self, stark, row, blocks, zs):
+        self.stark, self.row, self.blocks, self.zs = stark, row, blocks, zs
+
+    @property
+    def ok(self):
+        return not self.blocks and not self.zs
+
+    def __str__(self):
+        rpi = _rows_per_instance(self.stark)
+        where = f"row {self.row}" if rpi is None else f"row {self.row} (instance {self.row // rpi}, row {self.row % rpi} of {rpi})"
+        if self.ok:
+            return where + ": clean"
+        parts = list(dict.fromkeys(str(b) for b in self.blocks))   # (the two constraints of a lookup pair read the same)
+        parts += ["Z %d (cols %d, %d)" % ((z,) + self.stark.permutation_pair(z)) for z in self.zs]
+        return where + ": " + "; ".join(parts)
+
+    def __repr__(self):
+        return f"<RowExplanation {self}>"
+
+
+class RowsExplanation:
+    """What explain_rows found: one RowExplanation per listed row (len, index, iterate), and the raw bitmaps block_flags
+    [n_rows][(B + 7) // 8] and z_flags [n_rows][(num_zs + 7) // 8] (bit b of a row's entry, least significant bit first)."""
+
+    def __init__(self, stark, rows, block_flags, z_flags):
+        self.stark, self.rows, self.block_flags, self.z_flags = stark, [int(r) for r in rows], block_flags, z_flags
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, k):
+        blocks = self.stark.constraint_blocks()
+        zs = _set_bits(self.z_flags[k], self.stark.num_permutation_zs())
+        return RowExplanation(self.stark, self.rows[k], [blocks[b] for b in _set_bits(self.block_flags[k], len(blocks))], zs)
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def __str__(self):
+        return "\n".join(str(r) for r in self)
+
+    def __eq__(self, other):
+        if not isinstance(other, RowsExplanation):
+            return NotImplemented
+        return self.rows == other.rows and np.array_equal(self.block_flags, other.block_flags) and np.array_equal(self.z_flags, other.z_flags)
+
+
+class TraceExplanation:
+    """What explain_trace found over every row: per block and per Z column the number of failing rows and the first of them.
+    block_failing_rows / block_first_row [B] and z_failing_rows / z_first_row [num_zs] are uint64 arrays (first row =
+    2^64 - 1 where clean); failing_blocks() / failing_zs() list what fails."""
+
+    def __init__(self, stark, block_stats, z_stats):
+        self.stark = stark
+        self.block_failing_rows, self.block_first_row = block_stats[:, 0].copy(), block_stats[:, 1].copy()
+        self.z_failing_rows, self.z_first_row = z_stats[:, 0].copy(), z_stats[:, 1].copy()
+
+    @property
+    def ok(self):
+        return not self.block_failing_rows.any() and not self.z_failing_rows.any()
+
+    def failing_blocks(self):
+        """[(ConstraintBlock, failing rows, first row)] in stream order."""
+        blocks = self.stark.constraint_blocks()
+        return [(blocks[b], int(self.block_failing_rows[b]), int(self.block_first_row[b])) for b in np.nonzero(self.block_failing_rows)[0]]
+
+    def failing_zs(self):
+        """[(z, failing rows, first row)]."""
+        return [(int(z), int(self.z_failing_rows[z]), int(self.z_first_row[z])) for z in np.nonzero(self.z_failing_rows)[0]]
+
+    def __str__(self):
+        if self.ok:
+            return "ok: no block and no Z column fails on any row"
+        plural = lambda k: f"{k:,} row{'s' if k != 1 else ''}"   # noqa: E731
+        lines = [f"{b} fails on {plural(k)}, first on row {r}" for b, k, r in self.failing_blocks()]
+        lines += ["Z %d (cols %d, %d) fails on %s, first on row %d" % ((z,) + self.stark.permutation_pair(z) + (plural(k), r)) for z, k, r in self.failing_zs()]
+        return "\n".join(lines)
+
+    def __repr__(self):
+        return f"<TraceExplanation {len(self.failing_blocks())} blocks, {len(self.failing_zs())} Z columns fail>"
+
+    def __eq__(self, other):
+        if not isinstance(other, TraceExplanation):
+            return NotImplemented
+        return all(np.array_equal(getattr(self, f), getattr(other, f)) for f in ("block_failing_rows", "block_first_row", "z_failing_rows", "z_first_row"))
+
+
+def _explain_rows_buffers(stark, rows):
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+    B, Z = len(stark.constraint_blocks()), stark.num_permutation_zs()
+    return rows, np.zeros((len(rows), (B + 7) // 8), dtype=np.uint8), np.zeros((len(rows), (Z + 7) // 8), dtype=np.uint8)
+
+
+def _explain_trace_buffers(stark):
+    B, Z = len(stark.constraint_blocks()), stark.num_permutation_zs()
+    return np.zeros((B, 2), dtype=np.uint64), np.zeros((Z, 2), dtype=np.uint64)
+
+
+def _host_trace_args(stark, trace, public_inputs):
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    n = trace.shape[1] if trace.ndim == 2 else 0
+    if trace.ndim != 2 or trace.shape[0] != stark.num_columns or n == 0 or n & (n - 1):
+        raise SbnError(-1, "trace shape does not match the table")
+    return trace, pi, n.bit_length() - 1
+
+
+def explain_rows_host(stark, trace, public_inputs, rows, seed=0):
+    """Which constraint blocks and Z columns the listed rows of `trace` break, on host threads (sbn_explain_rows_host).  The
+    same RowsExplanation, for the same seed, as Prover.explain_rows gives for the loaded trace."""
+    trace, pi, bits = _host_trace_args(stark, trace, public_inputs)
+    rows, bf, zf = _explain_rows_buffers(stark, rows)
+    _check(lib().sbn_explain_rows_host(C.byref(stark._d), _ptr(trace), bits, _ptr(pi), len(pi), seed, _ptr(rows), len(rows), _ptr(bf), _ptr(zf)))
+    return RowsExplanation(stark, rows, bf, zf)
+
+
+def explain_trace_host(stark, trace, public_inputs, seed=0):
+    """Per block and Z column, on how many rows of `trace` it fails and where first, on host threads (sbn_explain_trace_host)."""
+    trace, pi, bits = _host_trace_args(stark, trace, public_inputs)
+    bs, zs = _explain_trace_buffers(stark)
+    _check(lib().sbn_explain_trace_host(C.byref(stark._d), _ptr(trace), bits, _ptr(pi), len(pi), seed, _ptr(bs), _ptr(zs)))
+    return TraceExplanation(stark, bs, zs)
+
+
 class Prover:
     """Device context for one (table, degree_bits): buffers stay allocated across proofs."""
 
@@ -656,6 +853,24 @@ class Prover:
         buf = (C.c_float * 4)()
         k = lib().sbn_prover_check_times(self._h, buf, 4)
         return dict(zip(("perm_z", "constraints", "reduction", "download"), (float(buf[i]) for i in range(k))))
+
+    def explain_rows(self, rows, seed=0):
+        """Which constraint blocks and Z columns the listed rows of the loaded trace break (sbn_prover_explain_rows)."""
+        rows, bf, zf = _explain_rows_buffers(self.stark, rows)
+        _check(lib().sbn_prover_explain_rows(self._h, seed, _ptr(rows), len(rows), _ptr(bf), _ptr(zf)))
+        return RowsExplanation(self.stark, rows, bf, zf)
+
+    def explain_trace(self, seed=0):
+        """Per block and Z column, on how many rows of the loaded trace it fails and where first (sbn_prover_explain_trace)."""
+        bs, zs = _explain_trace_buffers(self.stark)
+        _check(lib().sbn_prover_explain_trace(self._h, seed, _ptr(bs), _ptr(zs)))
+        return TraceExplanation(self.stark, bs, zs)
+
+    def explain_times(self):
+        """Device times of the last explain_rows() / explain_trace() in ms (HIP events)."""
+        buf = (C.c_float * 3)()
+        k = lib().sbn_prover_explain_times(self._h, buf, 3)
+        return dict(zip(("perm_z", "explain", "download"), (float(buf[i]) for i in range(k))))
 
     def prove(self):
         h = C.c_void_p()

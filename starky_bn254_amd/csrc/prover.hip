@@ -1575,6 +1575,14 @@ extern "C" int sbn_split_prover_check_trace(sbn_split_prover* sp, uint64_t seed,
   if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
   return sbn_prover_check_trace(sp->P, seed, rep, row_flags_out);   // (trace_check.hip refuses world > 1)
 }
+extern "C" int sbn_split_prover_explain_rows(sbn_split_prover* sp, uint64_t seed, const uint64_t* rows, size_t n_rows, uint8_t* block_flags_out, uint8_t* z_flags_out) {
+  if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
+  return sbn_prover_explain_rows(sp->P, seed, rows, n_rows, block_flags_out, z_flags_out);   // (trace_explain.hip refuses world > 1)
+}
+extern "C" int sbn_split_prover_explain_trace(sbn_split_prover* sp, uint64_t seed, sbn_block_stat* block_stats_out, sbn_block_stat* z_stats_out) {
+  if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
+  return sbn_prover_explain_trace(sp->P, seed, block_stats_out, z_stats_out);
+}
 extern "C" int sbn_split_prover_stage_times(const sbn_split_prover* sp, float* ms_out, int cap) {
   if (!sp) return 0;
   return sbn_prover_stage_times(sp->P, ms_out, cap);

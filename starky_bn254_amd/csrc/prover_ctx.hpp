@@ -139,6 +139,7 @@ struct sbn_prover {
   unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
   float check_ms[4] = {};                    // sbn_prover_check_trace: permutation Z, constraint kernels, reduction, download
+  float explain_ms[3] = {};                  // sbn_prover_explain_*: permutation Z, explain kernels, reduction / download
 };
 
 // prover.hip, shared with trace_check.hip: the pieces of the permutation and quotient stages that the trace check runs on the
@@ -152,3 +153,7 @@ int upload_alpha_tables(sbn_prover* P, const F alphas[SBN_NCH]);
 void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientParams& qp);
 // quotient_kernel<kind, 0 / 1> on P->stream, <kind, 2> on P->hstream
 int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks);
+// trace_check.hip, shared with trace_explain.hip: the seed-to-challenge transcript of a check and the kernel that fills the tables
+// of the trace domain.
+void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]);
+void launch_trace_domain_tables(u64* xs, u64* lag_first, u64* lag_last, size_t n, u32 degree_bits, hipStream_t s);

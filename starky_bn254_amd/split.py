@@ -331,6 +331,18 @@ class SplitProver:
         self._checked(api.lib().sbn_split_prover_check_trace(self._h, seed, C.byref(raw), api._ptr(row_flags)))
         return api.TraceReport(raw, row_flags, api._rows_per_instance(self.stark))
 
+    def explain_rows(self, rows, seed=0):
+        """Prover.explain_rows on this rank's loaded trace; a world of one rank only (SbnError(-7) otherwise)."""
+        rows, bf, zf = api._explain_rows_buffers(self.stark, rows)
+        self._checked(api.lib().sbn_split_prover_explain_rows(self._h, seed, api._ptr(rows), len(rows), api._ptr(bf), api._ptr(zf)))
+        return api.RowsExplanation(self.stark, rows, bf, zf)
+
+    def explain_trace(self, seed=0):
+        """Prover.explain_trace on this rank's loaded trace; a world of one rank only."""
+        bs, zs = api._explain_trace_buffers(self.stark)
+        self._checked(api.lib().sbn_split_prover_explain_trace(self._h, seed, api._ptr(bs), api._ptr(zs)))
+        return api.TraceExplanation(self.stark, bs, zs)
+
     def stage_times(self):
         buf = (C.c_float * 32)()
         k = api.lib().sbn_split_prover_stage_times(self._h, buf, 32)
