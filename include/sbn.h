@@ -376,6 +376,38 @@ int sbn_batch_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint
 int sbn_batch_prover_prove_ios(sbn_batch_prover* b, const uint32_t* ios, size_t ios_words_per_unit, size_t num_io, size_t count, sbn_proof** proofs_out);
 void sbn_batch_prover_destroy(sbn_batch_prover* b);
 
+/* Long chained lists ------------------------------------------------------------------------------- */
+/* An MSM / multi-exponentiation of ANY length as proofs of one table: the chained list of sbn_chain_instances cut into units of
+ * num_io instances, the last unit padded as the reference's g1_exp_circuit pads a short list (src/curves/g1/circuit.rs:273-277,
+ * 303: resized with copies of the LAST input, only outputs[..n] used).  "These units prove this MSM" means: every unit proof
+ * verifies (sbn_verify / sbn_verifier_verify) AND sbn_msm_check_links accepts their public inputs; the reference states the
+ * second half with `connect` calls inside its circuit (circuit.rs:480-483). */
+size_t sbn_msm_num_units(size_t count, size_t num_io);   /* ceil(count / num_io); 0 when either is 0 */
+/* The padded, unit-cut list, host pool, no device.  kind, terms, start, final_out and the refusals as sbn_chain_instances (the
+ * refusals name the GLOBAL instance index); ios_out: [units * num_io][words per instance]: rows [0, count) are what
+ * sbn_chain_instances writes, rows [count, units * num_io) are copies of row count - 1 (x, offset and exponent), final_out
+ * (optional) is the output of instance count - 1.  count == 0 or num_io == 0: SBN_ERR_BAD_ARG.  num_io is not checked against any
+ * table (this only shapes a list); a single padded unit (count < num_io) is a legal call. */
+int sbn_msm_instances(int32_t kind, const uint32_t* terms, size_t count, size_t num_io, const uint32_t* start, uint32_t* ios_out, uint32_t* final_out);
+/* Proves the units of that list on the contexts of a batch prover (its table's num_io): proofs_out[units] in unit order, final_out
+ * (optional) and ios_out (optional) as sbn_msm_instances.  Proofs, public inputs and ios_out are word for word what
+ * sbn_batch_prover_prove_ios gives on the list of sbn_msm_instances.  Failure rule as prove_ios: the status and message of the first
+ * failing unit (or of the checks of the whole list, naming the global instance), every proof freed, proofs_out all null; the batch
+ * prover stays usable.  The list is derived once on the host pool (sbn_msm_instances) in every placement of the table's chains, so
+ * every unit's start is known before the first unit is taken and no context waits for another; the units then go through the
+ * explicit-list path of sbn_batch_prover_prove_ios. */
+int sbn_batch_prover_prove_msm(sbn_batch_prover* b, const uint32_t* terms, size_t count, const uint32_t* start, sbn_proof** proofs_out,
+                               uint32_t* final_out, uint32_t* ios_out);
+/* The link check on the public inputs of the unit proofs (host, no device): public_inputs[u] = the [num_pi] public inputs of unit
+ * u of the table (kind, num_io).  Checked, in instance order: units == sbn_msm_num_units(count, num_io); the offset of global
+ * instance 0 equals start; offset[g + 1] == output[g] for every g < count - 1, across unit boundaries; every pad instance equals
+ * instance count - 1 in x, offset, exponent and output; with terms (optional, [count][T] as sbn_chain_instances), x and exponent of
+ * every real instance equal the caller's.  SBN_OK and final_out (optional) = the output of instance count - 1 in the word shape of
+ * start, or SBN_ERR_VERIFY_FAILED with sbn_last_error naming the first global instance and field that breaks.
+ * It does NOT verify any proof: that is sbn_verify or sbn_verifier_verify on each unit. */
+int sbn_msm_check_links(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count,
+                        const uint32_t* terms, const uint32_t* start, uint32_t* final_out);
+
 /* One oversized trace split over the GPUs of a node (BASELINE config "Single Fq12 exponentiation proof, trace height
  * 2^18, 8xMI355X with RCCL FRI fold"; reference workload src/fields/fq12/exp.rs:638-696).  One rank per GPU (one process
  * each, or the threads of one process with sbn_local_comm_create); every rank calls the same functions with the same

@@ -131,6 +131,10 @@ extern "C" {
     pub fn sbn_batch_prover_create(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, inflight: u32, out: *mut *mut sbn_batch_prover) -> i32;
     pub fn sbn_batch_prover_prove_ios(b: *mut sbn_batch_prover, ios: *const u32, ios_words_per_unit: usize, num_io: usize, count: usize, proofs_out: *mut *mut sbn_proof) -> i32;
     pub fn sbn_batch_prover_destroy(b: *mut sbn_batch_prover);
+    pub fn sbn_msm_num_units(count: usize, num_io: usize) -> usize;
+    pub fn sbn_msm_instances(kind: i32, terms: *const u32, count: usize, num_io: usize, start: *const u32, ios_out: *mut u32, final_out: *mut u32) -> i32;
+    pub fn sbn_batch_prover_prove_msm(b: *mut sbn_batch_prover, terms: *const u32, count: usize, start: *const u32, proofs_out: *mut *mut sbn_proof, final_out: *mut u32, ios_out: *mut u32) -> i32;
+    pub fn sbn_msm_check_links(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, terms: *const u32, start: *const u32, final_out: *mut u32) -> i32;
 
     pub fn sbn_proof_num_words(p: *const sbn_proof) -> usize;
     pub fn sbn_proof_words(p: *const sbn_proof) -> *const u64;

@@ -454,6 +454,50 @@ where
         .collect()
 }
 
+/// A chained list of any length (`terms`: `count` rows of x and exp_val, `start`: the offset of instance 0; include/sbn.h, "Long
+/// chained lists") proved as units of the table, the last one padded with copies of the last instance as the reference's
+/// `g1_exp_circuit` pads (src/curves/g1/circuit.rs:273-277).  Returns the unit proofs as canonical words, in unit order, and the
+/// last output in the word shape of `start`.
+pub fn prove_msm<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: usize, inflight: usize, terms: &[u32], count: usize, start: &[u32]) -> Result<(Vec<Vec<u64>>, Vec<u32>)> {
+    let a = air(stark);
+    let cfg = to_sbn_config(config)?;
+    let units = unsafe { ffi::sbn_msm_num_units(count, a.num_io as usize) };
+    ensure!(units > 0 && terms.len() % count == 0, "terms length is not a multiple of the instance count");
+    let mut b = ptr::null_mut();
+    check(unsafe { ffi::sbn_batch_prover_create(&a, &cfg, degree_bits as u32, inflight as u32, &mut b) }, "sbn_batch_prover_create")?;
+    let mut raw = vec![ptr::null_mut(); units];
+    let mut last = vec![0u32; start.len()];
+    let rc = unsafe { ffi::sbn_batch_prover_prove_msm(b, terms.as_ptr(), count, start.as_ptr(), raw.as_mut_ptr(), last.as_mut_ptr(), ptr::null_mut()) };
+    unsafe { ffi::sbn_batch_prover_destroy(b) };
+    check(rc, "sbn_batch_prover_prove_msm")?;
+    let proofs = raw
+        .into_iter()
+        .map(|p| {
+            let words = unsafe { std::slice::from_raw_parts(ffi::sbn_proof_words(p), ffi::sbn_proof_num_words(p)) }.to_vec();
+            unsafe { ffi::sbn_proof_free(p) };
+            words
+        })
+        .collect();
+    Ok((proofs, last))
+}
+
+/// Verifies every unit proof of `prove_msm` with the host verifier, then checks on their public inputs (the last header[5] words of
+/// a proof) that the units are one chained list from `start` (`sbn_msm_check_links`; with `terms`, that x and the exponents are the
+/// caller's).  Returns the last output in the word shape of `start`.
+pub fn verify_msm<S: SbnTable>(stark: &S, config: &StarkConfig, proofs: &[Vec<u64>], count: usize, start: &[u32], terms: Option<&[u32]>) -> Result<Vec<u32>> {
+    let a = air(stark);
+    let mut pis = Vec::with_capacity(proofs.len());
+    for w in proofs {
+        verify_stark_proof_words(stark, w, config)?;
+        ensure!(w.len() >= 12 && w[5] as usize <= w.len() - 12, "proof words truncated");
+        pis.push(w[w.len() - w[5] as usize..].as_ptr());
+    }
+    let mut last = vec![0u32; start.len()];
+    let t = terms.map_or(ptr::null(), |t| t.as_ptr());
+    check(unsafe { ffi::sbn_msm_check_links(a.kind, a.num_io as usize, pis.as_ptr(), pis.len(), count, t, start.as_ptr(), last.as_mut_ptr()) }, "sbn_msm_check_links")?;
+    Ok(last)
+}
+
 /// The library's host verifier on canonical proof words (what `verify_stark_proof` above ends in).
 pub fn verify_stark_proof_words<S: SbnTable>(stark: &S, words: &[u64], config: &StarkConfig) -> Result<()> {
     let a = air(stark);

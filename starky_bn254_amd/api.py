@@ -38,6 +38,7 @@ EXPORTS = [
     "sbn_air_constraint_blocks", "sbn_constraint_section_name", "sbn_air_permutation_pair", "sbn_explain_rows_host", "sbn_explain_trace_host",
     "sbn_prover_explain_rows", "sbn_prover_explain_trace", "sbn_prover_explain_times", "sbn_split_prover_explain_rows", "sbn_split_prover_explain_trace",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
+    "sbn_msm_num_units", "sbn_msm_instances", "sbn_batch_prover_prove_msm", "sbn_msm_check_links",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
@@ -156,6 +157,11 @@ def lib():
         L.sbn_batch_prover_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(vp)]
         L.sbn_batch_prover_prove_ios.argtypes = [vp, vp, sz, sz, sz, C.POINTER(vp)]
         L.sbn_batch_prover_destroy.argtypes = [vp]
+        L.sbn_msm_num_units.restype = sz
+        L.sbn_msm_num_units.argtypes = [sz, sz]
+        L.sbn_msm_instances.argtypes = [C.c_int32, vp, sz, sz, vp, vp, vp]
+        L.sbn_batch_prover_prove_msm.argtypes = [vp, vp, sz, vp, C.POINTER(vp), vp, vp]
+        L.sbn_msm_check_links.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, vp, vp, vp]
         L.sbn_prove.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, u32, vp, sz, C.POINTER(vp)]
         L.sbn_proof_num_words.restype = sz
         L.sbn_proof_num_words.argtypes = [vp]
@@ -495,6 +501,47 @@ def chain_instances(stark, terms, start):
     return ios, final
 
 
+def msm_num_units(count, num_io):
+    """ceil(count / num_io); 0 when either is 0 (sbn_msm_num_units)."""
+    return int(lib().sbn_msm_num_units(count, num_io))
+
+
+def msm_instances(stark, terms, start):
+    """A chained list of any length cut into units of stark.num_io instances (sbn_msm_instances): the list of chain_instances, the
+    last unit padded with copies of the last instance.  Returns (ios_units, final): (units, num_io, words per instance) uint32
+    as BatchProver.prove_ios takes it, and the output of the last real instance in the word shape of start.  No device needed."""
+    terms, start, xw, ew = _chain_args(stark, terms, start)
+    if stark.num_io < 1:
+        raise SbnError(-1, "the table has no instances")
+    units = msm_num_units(terms.shape[0], stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * xw + ew), dtype=np.uint32)
+    final = np.zeros(xw, dtype=np.uint32)
+    _check(lib().sbn_msm_instances(stark.kind, _ptr(terms), terms.shape[0], stark.num_io, _ptr(start), _ptr(ios), _ptr(final)))
+    return ios, final
+
+
+def msm_check_links(stark, public_inputs_per_unit, count, start, terms=None):
+    """The link check of a long chained list (sbn_msm_check_links) on the public inputs of its unit proofs: the units are one
+    chained list from `start`, padded as msm_instances pads, and (with `terms`) its x and exponents are the caller's.  Returns the
+    last output in the word shape of start; raises SbnError(-6) naming the first instance and field that breaks.  Verifies NO
+    proof: verify_msm does both."""
+    xw, ew = _chain_words(stark)
+    start = np.ascontiguousarray(start, dtype=np.uint32).reshape(-1)
+    if start.shape[0] != xw:
+        raise SbnError(-1, f"start must be {xw} u32")
+    if terms is not None:
+        terms = np.ascontiguousarray(terms, dtype=np.uint32)
+        if terms.shape != (count, xw + ew):
+            raise SbnError(-1, f"terms must be [count][{xw + ew}] u32")
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
+    if any(p.shape[0] != stark.num_public_inputs for p in pis):
+        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
+    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    final = np.zeros(xw, dtype=np.uint32)
+    _check(lib().sbn_msm_check_links(stark.kind, stark.num_io, ptrs, len(pis), count, _ptr(terms), _ptr(start), _ptr(final)))
+    return final
+
+
 class Proof:
     """StarkProofWithPublicInputs as canonical proof words (layout: include/sbn.h)."""
 
@@ -507,6 +554,11 @@ class Proof:
 
     def recover_degree_bits(self, config=None):
         return self.degree_bits
+
+    def public_inputs(self):
+        """The public inputs the proof carries: the last n_public_inputs words (header word 5)."""
+        n = int(self.words[5])
+        return self.words[len(self.words) - n:]
 
     def fields(self):
         """The proof as the reference's struct tree (starky proof.rs `StarkProof` / `StarkOpeningSet`, plonky2
@@ -932,6 +984,18 @@ class BatchProver:
         _check(lib().sbn_batch_prover_prove_ios(self._h, _ptr(ios), num_io * w, num_io, count, out))
         return [_take_proof(C.c_void_p(h)) for h in out]
 
+    def prove_msm(self, terms, start):
+        """A chained list of any length (terms, start as chain_instances) proved as units of the table, the last one padded
+        (sbn_batch_prover_prove_msm).  Returns (proofs, final, ios): the unit proofs in order, the last output in the word shape
+        of start, and the list as msm_instances gives it."""
+        terms, start, xw, ew = _chain_args(self.stark, terms, start)
+        units = msm_num_units(terms.shape[0], self.stark.num_io)
+        ios = np.zeros((units, self.stark.num_io, 2 * xw + ew), dtype=np.uint32)
+        final = np.zeros(xw, dtype=np.uint32)
+        out = (C.c_void_p * max(units, 1))()
+        _check(lib().sbn_batch_prover_prove_msm(self._h, _ptr(terms), terms.shape[0], _ptr(start), out, _ptr(final), _ptr(ios)))
+        return [_take_proof(C.c_void_p(h)) for h in out[:units]], final, ios
+
     def close(self):
         if self._h:
             lib().sbn_batch_prover_destroy(self._h)
@@ -984,6 +1048,25 @@ def verify_stark_proof(stark, proof, config):
     b = proof.to_bytes() if isinstance(proof, Proof) else bytes(proof)
     buf = (C.c_uint8 * len(b)).from_buffer_copy(b)
     _check(lib().sbn_verify(C.byref(stark._d), C.byref(config._c), buf, len(b)))
+
+
+def verify_msm(stark, config, proofs, count, start, terms=None, verifier=None):
+    """Verifies the unit proofs of a long chained list (BatchProver.prove_msm) and then checks that they link up
+    (msm_check_links): with the host verifier, or on the device with `verifier` (a Verifier of the table).  Returns the last
+    output in the word shape of start; raises SbnError when a unit is rejected (naming the unit) or a link breaks."""
+    proofs = list(proofs)
+    if verifier is None:
+        for u, p in enumerate(proofs):
+            try:
+                verify_stark_proof(stark, p, config)
+            except SbnError as e:
+                raise SbnError(e.code, f"unit {u}: {e}") from None
+    else:
+        for at in range(0, len(proofs), verifier.max_batch):
+            for i, (code, reason) in enumerate(verifier.verify(proofs[at:at + verifier.max_batch])):
+                if code != 0:
+                    raise SbnError(code, f"unit {at + i}: {reason}")
+    return msm_check_links(stark, [p.public_inputs() for p in proofs], count, start, terms)
 
 
 class Verifier:

@@ -146,14 +146,14 @@ int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* tr
 // `inflight` prover contexts on the current GPU, one host thread each; every unit = one instance list of the table,
 // witness generated on the device, then proved.  While one proof sits in a latency-bound tail or waits for the host
 // transcript, the kernels of the others fill the GPU (30.7 instead of 26.5 proofs/s for G1ExpStark(128)).
-struct sbn_batch_prover { std::vector<sbn_prover*> provers; int kind = 0; };
+struct sbn_batch_prover { std::vector<sbn_prover*> provers; int kind = 0; uint32_t num_io = 0; };
 
 int sbn_batch_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t inflight, sbn_batch_prover** out) {
   if (!out || inflight == 0 || inflight > 16) return fail(SBN_ERR_BAD_ARG, "bad arguments (1 <= inflight <= 16)");
   *out = nullptr;
   if (!air) return fail(SBN_ERR_BAD_ARG, "null argument");
   sbn_batch_prover* B = new sbn_batch_prover();
-  B->kind = air->kind;
+  B->kind = air->kind; B->num_io = air->num_io;
   for (uint32_t i = 0; i < inflight; i++) {
     sbn_prover* P = nullptr;
     int rc = sbn_prover_create(air, cfg, degree_bits, &P);
@@ -192,6 +192,24 @@ int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t 
     return fail(first_rc.load(), "%s", msg.c_str());
   }
   return SBN_OK;
+}
+
+// A chained list of any length as units of the batch prover's table (include/sbn.h, "Long chained lists"): the padded, unit-cut
+// list is derived once on the host pool (csrc/msm.hip), then the units go through the explicit-list path above, so the proofs,
+// their public inputs and ios_out are those of sbn_batch_prover_prove_ios on the list of sbn_msm_instances by construction, in
+// every placement of the table's chains.
+int sbn_batch_prover_prove_msm(sbn_batch_prover* B, const uint32_t* terms, size_t count, const uint32_t* start, sbn_proof** proofs_out,
+                               uint32_t* final_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const size_t IOW = exp_io_words(B->kind), units = sbn_msm_num_units(count, B->num_io);
+  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
+  if (IOW == 0) return fail(SBN_ERR_UNSUPPORTED, "chained lists cover the Exp tables");
+  if (!terms || !start || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no instance");
+  std::vector<uint32_t> own;
+  uint32_t* ios = ios_out;
+  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
+  if (int rc = sbn_msm_instances(B->kind, terms, count, B->num_io, start, ios, final_out)) return rc;
+  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
 }
 
 }  // extern "C"
