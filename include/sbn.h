@@ -408,6 +408,61 @@ int sbn_batch_prover_prove_msm(sbn_batch_prover* b, const uint32_t* terms, size_
 int sbn_msm_check_links(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count,
                         const uint32_t* terms, const uint32_t* start, uint32_t* final_out);
 
+/* Scalar multiplications ----------------------------------------------------------------------------- */
+/* The INDEPENDENT batch: every instance of a G1_EXP / G2_EXP list carries the same offset and the caller wants e_k x_k itself, not
+ * offset + e_k x_k.  The reference uses it in g2_mul_by_cofactor_circuit (src/curves/g2/circuit.rs:335-367: x = point, offset = the
+ * G2 generator, exp_val = 2p - r, result = output + (-generator): cofactor clearing) and wherever G1ExpOutputGenerator /
+ * G2ExpOutputGenerator (src/curves/g1/circuit.rs:111-123) run on independent inputs; the offset exists only because the table
+ * cannot hold the point at infinity.  One definition for every entry point below, E = 1 (G1_EXP) or 2 (G2_EXP):
+ *   points   [count][16E] u32: the x words of an `ios` row (x.c0 [x.c1] y.c0 [y.c1], eight little-endian u32 limbs each);
+ *   scalars  [scalar_count][8] u32, scalar_count = count, or 1 for ONE scalar shared by every instance.  256-bit integers, NEVER
+ *            reduced mod r (the twist's group has order r (2p - r): cofactor clearing depends on it);
+ *   offset   [16E] u32, or NULL = the curve's generator (sbn_curve_generator), as the reference uses.
+ * With units = sbn_msm_num_units(count, num_io) the explicit list has units * num_io rows: row g < count is (points[g], offset,
+ * scalar[g]), row g >= count a copy of row count - 1 (the reference's resize rule, as sbn_msm_instances).  Per real instance
+ * product[g] = output[g] + (-offset) by the COMPLETE addition: output = offset (e = 0, or e a multiple of the point's order) is the
+ * point at infinity, which is not an error (infinity_out[g] = 1, the product words zero); output = -offset cannot happen, because
+ * it needs e x = -2 offset, which the doubling branch handles; e x = -offset makes the OUTPUT infinite, which the table cannot
+ * hold: SBN_ERR_WITNESS.  products_out: [count][16E] u32, infinity_out: [count] bytes, ios_out: [units * num_io][40 | 72] u32; every
+ * output pointer is optional.
+ * Refused, in this order: SBN_ERR_UNSUPPORTED for a kind other than the two curve tables (a field table needs none of this: its
+ * offset is multiplicative and one is always legal); SBN_ERR_BAD_ARG for a null argument, count = 0, scalar_count outside
+ * {1, count}, a coordinate >= p, an offset or a point that is not on the table's curve (naming the instance; the rule of
+ * sbn_chain_instances: output - offset = e x only inside a group; points off the prime-order subgroup of the twist are fine and
+ * are the normal input of cofactor clearing); SBN_ERR_WITNESS when the table's own walk of an instance is degenerate (B[t] = +-2^t x
+ * at a set bit, e.g. x = +-offset with an odd scalar), naming the FIRST such instance: the remedy is another offset. */
+int sbn_curve_generator(int32_t kind, uint32_t* out);   /* (1, 2) on G1, ark_bn254's G2Affine::generator() on the twist: [16E] u32 */
+int sbn_g2_cofactor(uint32_t out[8]);                   /* 2p - r = 21888242871839275222246405745257275088844257914179612981679871602714643921549 */
+/* The explicit list and the products on the host pool, no device (e_k x_k as sbn_chain_instances derives its terms, then the
+ * table's-walk check of the list).  num_io is not checked against any table. */
+int sbn_scalar_mul_instances(int32_t kind, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count, size_t num_io,
+                             const uint32_t* offset, uint32_t* ios_out, uint32_t* products_out, uint8_t* infinity_out);
+/* One unit (count = num_io) on a prover of the table: on success the loaded trace and the public inputs are, word for word, those
+ * of sbn_prover_generate_trace on the list of sbn_scalar_mul_instances; sizes and the failure rule as there (a failing call leaves
+ * NO trace loaded).  Where the table's chains run on the device (SBN_TRACEGEN_DEVICE_CHAIN = 1 or 2) the list is expanded there
+ * from the points, the scalars and the offset (24 / 40 words per instance go up instead of 40 / 72) and the products are
+ * computed there from the instance outputs; a degenerate instance is then named by the host walk on the error path.  Elsewhere
+ * the list is derived on the host pool and takes the explicit path. */
+int sbn_prover_generate_trace_scalar_muls(sbn_prover* p, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t num_io,
+                                          const uint32_t* offset, uint64_t* pi_out, uint32_t* products_out, uint8_t* infinity_out, uint32_t* ios_out);
+/* Any count, as units of the batch prover's table (units as sbn_batch_prover_prove_msm): proofs_out[units] in unit order, word for
+ * word what sbn_batch_prover_prove_ios gives on the list of sbn_scalar_mul_instances.  A refused list leaves the batch prover
+ * usable and every proofs_out entry null. */
+int sbn_batch_prover_prove_scalar_muls(sbn_batch_prover* b, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count,
+                                       const uint32_t* offset, sbn_proof** proofs_out, uint32_t* products_out, uint8_t* infinity_out, uint32_t* ios_out);
+/* The twin of sbn_msm_check_links, on the public inputs of the unit proofs (host, no device; it verifies NO proof).
+ * SBN_ERR_VERIFY_FAILED naming the instance and the field for: a wrong unit count; an x or exponent that differs from the caller's;
+ * an offset that differs from the call's; a pad row that differs from instance count - 1 in x, offset, exponent or output; an output
+ * limb out of range; an output that is not a point of the curve.  On success the products and flags are recomputed on the host. */
+int sbn_scalar_mul_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, const uint32_t* points,
+                         const uint32_t* scalars, size_t scalar_count, const uint32_t* offset, uint32_t* products_out, uint8_t* infinity_out);
+/* Cofactor clearing on the twist: the two calls above for G2_EXP with the generator as offset and the shared scalar 2p - r
+ * (g2/circuit.rs:335-367).  A batch prover of any other table: SBN_ERR_BAD_ARG. */
+int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* b, const uint32_t* points, size_t count, sbn_proof** proofs_out, uint32_t* cleared_out,
+                                           uint8_t* infinity_out, uint32_t* ios_out);
+int sbn_mul_by_cofactor_check(size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, const uint32_t* points,
+                              uint32_t* cleared_out, uint8_t* infinity_out);
+
 /* One oversized trace split over the GPUs of a node (BASELINE config "Single Fq12 exponentiation proof, trace height
  * 2^18, 8xMI355X with RCCL FRI fold"; reference workload src/fields/fq12/exp.rs:638-696).  One rank per GPU (one process
  * each, or the threads of one process with sbn_local_comm_create); every rank calls the same functions with the same

@@ -135,6 +135,14 @@ extern "C" {
     pub fn sbn_msm_instances(kind: i32, terms: *const u32, count: usize, num_io: usize, start: *const u32, ios_out: *mut u32, final_out: *mut u32) -> i32;
     pub fn sbn_batch_prover_prove_msm(b: *mut sbn_batch_prover, terms: *const u32, count: usize, start: *const u32, proofs_out: *mut *mut sbn_proof, final_out: *mut u32, ios_out: *mut u32) -> i32;
     pub fn sbn_msm_check_links(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, terms: *const u32, start: *const u32, final_out: *mut u32) -> i32;
+    pub fn sbn_curve_generator(kind: i32, out: *mut u32) -> i32;
+    pub fn sbn_g2_cofactor(out: *mut u32) -> i32;
+    pub fn sbn_scalar_mul_instances(kind: i32, points: *const u32, scalars: *const u32, scalar_count: usize, count: usize, num_io: usize, offset: *const u32, ios_out: *mut u32, products_out: *mut u32, infinity_out: *mut u8) -> i32;
+    pub fn sbn_prover_generate_trace_scalar_muls(p: *mut sbn_prover, points: *const u32, scalars: *const u32, scalar_count: usize, num_io: usize, offset: *const u32, pi_out: *mut u64, products_out: *mut u32, infinity_out: *mut u8, ios_out: *mut u32) -> i32;
+    pub fn sbn_batch_prover_prove_scalar_muls(b: *mut sbn_batch_prover, points: *const u32, scalars: *const u32, scalar_count: usize, count: usize, offset: *const u32, proofs_out: *mut *mut sbn_proof, products_out: *mut u32, infinity_out: *mut u8, ios_out: *mut u32) -> i32;
+    pub fn sbn_scalar_mul_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, points: *const u32, scalars: *const u32, scalar_count: usize, offset: *const u32, products_out: *mut u32, infinity_out: *mut u8) -> i32;
+    pub fn sbn_batch_prover_prove_mul_by_cofactor(b: *mut sbn_batch_prover, points: *const u32, count: usize, proofs_out: *mut *mut sbn_proof, cleared_out: *mut u32, infinity_out: *mut u8, ios_out: *mut u32) -> i32;
+    pub fn sbn_mul_by_cofactor_check(num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, points: *const u32, cleared_out: *mut u32, infinity_out: *mut u8) -> i32;
 
     pub fn sbn_proof_num_words(p: *const sbn_proof) -> usize;
     pub fn sbn_proof_words(p: *const sbn_proof) -> *const u64;

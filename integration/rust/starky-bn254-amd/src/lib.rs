@@ -498,6 +498,72 @@ pub fn verify_msm<S: SbnTable>(stark: &S, config: &StarkConfig, proofs: &[Vec<u6
     Ok(last)
 }
 
+/// Independent scalar multiplications e_k x_k (include/sbn.h, "Scalar multiplications"; the call shape of the reference's
+/// `g2_mul_by_cofactor_circuit`, src/curves/g2/circuit.rs:335-367) proved as units of a curve table: `points` holds `count` rows
+/// of x words, `scalars` `count` rows of eight u32 limbs or ONE row shared by every instance (256-bit, never reduced), `offset` the
+/// offset every instance carries (`None`: the curve's generator).  Returns the unit proofs as canonical words, in unit order, the
+/// products in the word shape of a point and one flag per product that is the point at infinity (its words are zero).
+pub fn prove_scalar_muls<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: usize, inflight: usize, points: &[u32], count: usize, scalars: &[u32], offset: Option<&[u32]>) -> Result<(Vec<Vec<u64>>, Vec<u32>, Vec<u8>)> {
+    let a = air(stark);
+    let cfg = to_sbn_config(config)?;
+    let units = unsafe { ffi::sbn_msm_num_units(count, a.num_io as usize) };
+    ensure!(units > 0 && points.len() % count == 0, "points length is not a multiple of the instance count");
+    ensure!(scalars.len() == 8 || scalars.len() == 8 * count, "scalars must be one row of 8 u32 or one per instance");
+    let mut b = ptr::null_mut();
+    check(unsafe { ffi::sbn_batch_prover_create(&a, &cfg, degree_bits as u32, inflight as u32, &mut b) }, "sbn_batch_prover_create")?;
+    let mut raw = vec![ptr::null_mut(); units];
+    let mut products = vec![0u32; points.len()];
+    let mut infinity = vec![0u8; count];
+    let off = offset.map_or(ptr::null(), |o| o.as_ptr());
+    let rc = unsafe {
+        ffi::sbn_batch_prover_prove_scalar_muls(b, points.as_ptr(), scalars.as_ptr(), scalars.len() / 8, count, off, raw.as_mut_ptr(), products.as_mut_ptr(), infinity.as_mut_ptr(), ptr::null_mut())
+    };
+    unsafe { ffi::sbn_batch_prover_destroy(b) };
+    check(rc, "sbn_batch_prover_prove_scalar_muls")?;
+    let proofs = raw
+        .into_iter()
+        .map(|p| {
+            let words = unsafe { std::slice::from_raw_parts(ffi::sbn_proof_words(p), ffi::sbn_proof_num_words(p)) }.to_vec();
+            unsafe { ffi::sbn_proof_free(p) };
+            words
+        })
+        .collect();
+    Ok((proofs, products, infinity))
+}
+
+/// Verifies every unit proof of `prove_scalar_muls` with the host verifier, then checks on their public inputs that x, exponents
+/// and offset are the caller's, that the pads repeat the last instance and that every output is a point of the curve
+/// (`sbn_scalar_mul_check`).  Returns the products and infinity flags recomputed from the outputs.
+pub fn verify_scalar_muls<S: SbnTable>(stark: &S, config: &StarkConfig, proofs: &[Vec<u64>], points: &[u32], count: usize, scalars: &[u32], offset: Option<&[u32]>) -> Result<(Vec<u32>, Vec<u8>)> {
+    let a = air(stark);
+    let mut pis = Vec::with_capacity(proofs.len());
+    for w in proofs {
+        verify_stark_proof_words(stark, w, config)?;
+        ensure!(w.len() >= 12 && w[5] as usize <= w.len() - 12, "proof words truncated");
+        pis.push(w[w.len() - w[5] as usize..].as_ptr());
+    }
+    ensure!(scalars.len() == 8 || scalars.len() == 8 * count, "scalars must be one row of 8 u32 or one per instance");
+    let mut products = vec![0u32; points.len()];
+    let mut infinity = vec![0u8; count];
+    let off = offset.map_or(ptr::null(), |o| o.as_ptr());
+    check(
+        unsafe {
+            ffi::sbn_scalar_mul_check(a.kind, a.num_io as usize, pis.as_ptr(), pis.len(), count, points.as_ptr(), scalars.as_ptr(), scalars.len() / 8, off, products.as_mut_ptr(), infinity.as_mut_ptr())
+        },
+        "sbn_scalar_mul_check",
+    )?;
+    Ok((products, infinity))
+}
+
+/// Cofactor clearing on the twist (g2/circuit.rs:335-367): `prove_scalar_muls` on a `G2ExpStark` with the generator as offset and
+/// the shared scalar 2p - r (`sbn_g2_cofactor`).  Returns the unit proofs, the cleared points and their infinity flags.
+pub fn prove_mul_by_cofactor<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: usize, inflight: usize, points: &[u32], count: usize) -> Result<(Vec<Vec<u64>>, Vec<u32>, Vec<u8>)> {
+    let mut cofactor = [0u32; 8];
+    check(unsafe { ffi::sbn_g2_cofactor(cofactor.as_mut_ptr()) }, "sbn_g2_cofactor")?;
+    ensure!(air(stark).kind == ffi::SBN_AIR_G2_EXP, "cofactor clearing is a call of G2ExpStark (the twist)");
+    prove_scalar_muls(stark, config, degree_bits, inflight, points, count, &cofactor, None)
+}
+
 /// The library's host verifier on canonical proof words (what `verify_stark_proof` above ends in).
 pub fn verify_stark_proof_words<S: SbnTable>(stark: &S, words: &[u64], config: &StarkConfig) -> Result<()> {
     let a = air(stark);

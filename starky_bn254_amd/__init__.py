@@ -9,4 +9,5 @@ from .api import (  # noqa: F401
     FqExpStark, Fq12ExpU64Stark, Prover, BatchProver, Verifier, Proof, TraceReport, check_trace_host,
     ConstraintBlock, RowExplanation, RowsExplanation, TraceExplanation, explain_rows_host, explain_trace_host,
     prove, prove_cache_configure, prove_cache_stats, first_non_canonical, verify_stark_proof, commit_values, eval_constraints_host, poseidon_permute_batch, poseidon_permute_host, field_mul_batch, bn254_fq_batch, chain_instances, msm_num_units, msm_instances, msm_check_links, verify_msm, lib, lib_path, EXPORTS,
+    G2_COFACTOR, generator, scalar_mul_instances, scalar_mul_check, mul_by_cofactor_check, verify_scalar_muls, verify_mul_by_cofactor,
 )

@@ -39,6 +39,8 @@ EXPORTS = [
     "sbn_prover_explain_rows", "sbn_prover_explain_trace", "sbn_prover_explain_times", "sbn_split_prover_explain_rows", "sbn_split_prover_explain_trace",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_msm_num_units", "sbn_msm_instances", "sbn_batch_prover_prove_msm", "sbn_msm_check_links",
+    "sbn_curve_generator", "sbn_g2_cofactor", "sbn_scalar_mul_instances", "sbn_prover_generate_trace_scalar_muls",
+    "sbn_batch_prover_prove_scalar_muls", "sbn_scalar_mul_check", "sbn_batch_prover_prove_mul_by_cofactor", "sbn_mul_by_cofactor_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
@@ -162,6 +164,14 @@ def lib():
         L.sbn_msm_instances.argtypes = [C.c_int32, vp, sz, sz, vp, vp, vp]
         L.sbn_batch_prover_prove_msm.argtypes = [vp, vp, sz, vp, C.POINTER(vp), vp, vp]
         L.sbn_msm_check_links.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, vp, vp, vp]
+        L.sbn_curve_generator.argtypes = [C.c_int32, vp]
+        L.sbn_g2_cofactor.argtypes = [vp]
+        L.sbn_scalar_mul_instances.argtypes = [C.c_int32, vp, vp, sz, sz, sz, vp, vp, vp, vp]
+        L.sbn_prover_generate_trace_scalar_muls.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.sbn_batch_prover_prove_scalar_muls.argtypes = [vp, vp, vp, sz, sz, vp, C.POINTER(vp), vp, vp, vp]
+        L.sbn_scalar_mul_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, vp, vp, sz, vp, vp, vp]
+        L.sbn_batch_prover_prove_mul_by_cofactor.argtypes = [vp, vp, sz, C.POINTER(vp), vp, vp, vp]
+        L.sbn_mul_by_cofactor_check.argtypes = [sz, C.POINTER(vp), sz, sz, vp, vp, vp]
         L.sbn_prove.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, u32, vp, sz, C.POINTER(vp)]
         L.sbn_proof_num_words.restype = sz
         L.sbn_proof_num_words.argtypes = [vp]
@@ -542,6 +552,99 @@ def msm_check_links(stark, public_inputs_per_unit, count, start, terms=None):
     return final
 
 
+# 2p - r: the twist's group has order r (2p - r); the scalar of cofactor clearing (sbn_g2_cofactor; g2/circuit.rs:335-367)
+G2_COFACTOR = 21888242871839275222246405745257275088844257914179612981679871602714643921549
+
+
+def _curve_words(stark):
+    """u32 words of a point of the curve table `stark` (16 on G1, 32 on the twist)."""
+    try:
+        return {AIR_G1_EXP: 16, AIR_G2_EXP: 32}[stark.kind]
+    except KeyError:
+        raise SbnError(-7, "scalar multiplications cover the curve tables G1ExpStark and G2ExpStark") from None
+
+
+def generator(stark):
+    """The generator the reference uses as the offset of independent instances (sbn_curve_generator): (1, 2) on G1, ark_bn254's
+    G2Affine::generator() on the twist, as the x words of an `ios` row."""
+    out = np.zeros(_curve_words(stark), dtype=np.uint32)
+    _check(lib().sbn_curve_generator(stark.kind, _ptr(out)))
+    return out
+
+
+def _scalar_mul_args(stark, points, scalars, offset):
+    """points (count, 16E), scalars (count, 8) or (8,) / (1, 8) = one scalar shared by every instance (Python ints are taken as
+    256-bit little-endian limbs), offset (16E,) or None = the generator."""
+    w = _curve_words(stark)
+    points = np.ascontiguousarray(points, dtype=np.uint32)
+    if isinstance(scalars, int):
+        scalars = [(scalars >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint32)
+    if scalars.ndim == 1:
+        scalars = scalars.reshape(1, -1)
+    if points.ndim != 2 or points.shape[1] != w or scalars.ndim != 2 or scalars.shape[1] != 8:
+        raise SbnError(-1, f"points must be [count][{w}] u32 and scalars [count][8] or [8] u32")
+    if offset is not None:
+        offset = np.ascontiguousarray(offset, dtype=np.uint32).reshape(-1)
+        if offset.shape[0] != w:
+            raise SbnError(-1, f"offset must be {w} u32")
+    return points, scalars, offset, w
+
+
+def scalar_mul_instances(stark, points, scalars, offset=None):
+    """Independent scalar multiplications e_k x_k as instances of the curve table `stark` (sbn_scalar_mul_instances): every
+    instance carries `offset` (None: the generator) and the last unit is padded with copies of the last instance.  Returns
+    (ios_units, products, infinity): (units, num_io, words per instance) uint32 as BatchProver.prove_ios takes it, the products
+    (count, 16E) uint32 and a (count,) uint8 flag per product that is the point at infinity (its words are zero).  Scalars are
+    256-bit and never reduced.  No device needed."""
+    points, scalars, offset, w = _scalar_mul_args(stark, points, scalars, offset)
+    count = points.shape[0]
+    units = msm_num_units(count, stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * w + 8), dtype=np.uint32)
+    products = np.zeros((count, w), dtype=np.uint32)
+    infinity = np.zeros(count, dtype=np.uint8)
+    _check(lib().sbn_scalar_mul_instances(stark.kind, _ptr(points), _ptr(scalars), scalars.shape[0], count, stark.num_io, _ptr(offset),
+                                          _ptr(ios), _ptr(products), _ptr(infinity)))
+    return ios, products, infinity
+
+
+def scalar_mul_check(stark, public_inputs_per_unit, points, scalars, offset=None):
+    """The check of a batch of scalar multiplications (sbn_scalar_mul_check) on the public inputs of its unit proofs: x, exponents
+    and offset are the caller's, the pads repeat the last instance, every output is a point of the curve.  Returns (products,
+    infinity) recomputed from the outputs; raises SbnError(-6) naming the first instance and field that breaks.  Verifies NO proof:
+    verify_scalar_muls does both."""
+    points, scalars, offset, w = _scalar_mul_args(stark, points, scalars, offset)
+    count = points.shape[0]
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
+    if any(p.shape[0] != stark.num_public_inputs for p in pis):
+        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
+    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    products = np.zeros((count, w), dtype=np.uint32)
+    infinity = np.zeros(count, dtype=np.uint8)
+    _check(lib().sbn_scalar_mul_check(stark.kind, stark.num_io, ptrs, len(pis), count, _ptr(points), _ptr(scalars), scalars.shape[0],
+                                      _ptr(offset), _ptr(products), _ptr(infinity)))
+    return products, infinity
+
+
+def mul_by_cofactor_check(stark, public_inputs_per_unit, points):
+    """scalar_mul_check for cofactor clearing on the twist (sbn_mul_by_cofactor_check): the generator as offset, the shared scalar
+    G2_COFACTOR.  Returns (cleared, infinity).  Any table but G2ExpStark is refused."""
+    if stark.kind != AIR_G2_EXP:
+        raise SbnError(-1, "cofactor clearing is a call of G2ExpStark (the twist)")
+    points = np.ascontiguousarray(points, dtype=np.uint32)
+    if points.ndim != 2 or points.shape[1] != 32:
+        raise SbnError(-1, "points must be [count][32] u32")
+    count = points.shape[0]
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
+    if any(p.shape[0] != stark.num_public_inputs for p in pis):
+        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
+    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    cleared = np.zeros((count, 32), dtype=np.uint32)
+    infinity = np.zeros(count, dtype=np.uint8)
+    _check(lib().sbn_mul_by_cofactor_check(stark.num_io, ptrs, len(pis), count, _ptr(points), _ptr(cleared), _ptr(infinity)))
+    return cleared, infinity
+
+
 class Proof:
     """StarkProofWithPublicInputs as canonical proof words (layout: include/sbn.h)."""
 
@@ -887,6 +990,19 @@ class Prover:
         _check(lib().sbn_prover_generate_trace_chained(self._h, _ptr(terms), terms.shape[0], _ptr(start), _ptr(pi), _ptr(ios)))
         return pi, ios
 
+    def generate_trace_scalar_muls(self, points, scalars, offset=None):
+        """generate_trace on the one-unit list scalar_mul_instances(stark, points, scalars, offset) gives, expanded and un-offset
+        on the device where the table's chains run there; returns (public inputs, products, infinity, ios)."""
+        points, scalars, offset, w = _scalar_mul_args(self.stark, points, scalars, offset)
+        count = points.shape[0]
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        products = np.zeros((count, w), dtype=np.uint32)
+        infinity = np.zeros(count, dtype=np.uint8)
+        ios = np.zeros((count, 2 * w + 8), dtype=np.uint32)
+        _check(lib().sbn_prover_generate_trace_scalar_muls(self._h, _ptr(points), _ptr(scalars), scalars.shape[0], count, _ptr(offset),
+                                                           _ptr(pi), _ptr(products), _ptr(infinity), _ptr(ios)))
+        return pi, products, infinity, ios
+
     def read_trace(self):
         trace = np.zeros((self.stark.num_columns, 1 << self.degree_bits), dtype=np.uint64)
         _check(lib().sbn_prover_read_trace(self._h, _ptr(trace)))
@@ -996,6 +1112,35 @@ class BatchProver:
         _check(lib().sbn_batch_prover_prove_msm(self._h, _ptr(terms), terms.shape[0], _ptr(start), out, _ptr(final), _ptr(ios)))
         return [_take_proof(C.c_void_p(h)) for h in out[:units]], final, ios
 
+    def prove_scalar_muls(self, points, scalars, offset=None):
+        """Independent scalar multiplications of any count (arguments as scalar_mul_instances) proved as units of the table, the
+        last one padded (sbn_batch_prover_prove_scalar_muls).  Returns (proofs, products, infinity, ios)."""
+        points, scalars, offset, w = _scalar_mul_args(self.stark, points, scalars, offset)
+        count = points.shape[0]
+        units = msm_num_units(count, self.stark.num_io)
+        ios = np.zeros((units, self.stark.num_io, 2 * w + 8), dtype=np.uint32)
+        products = np.zeros((count, w), dtype=np.uint32)
+        infinity = np.zeros(count, dtype=np.uint8)
+        out = (C.c_void_p * max(units, 1))()
+        _check(lib().sbn_batch_prover_prove_scalar_muls(self._h, _ptr(points), _ptr(scalars), scalars.shape[0], count, _ptr(offset), out,
+                                                        _ptr(products), _ptr(infinity), _ptr(ios)))
+        return [_take_proof(C.c_void_p(h)) for h in out[:units]], products, infinity, ios
+
+    def prove_mul_by_cofactor(self, points):
+        """Cofactor clearing of twist points (g2/circuit.rs:335-367; sbn_batch_prover_prove_mul_by_cofactor): (2p - r) x for every
+        point, the generator as offset.  Returns (proofs, cleared, infinity, ios).  A G2ExpStark batch prover only."""
+        points = np.ascontiguousarray(points, dtype=np.uint32)
+        if points.ndim != 2 or points.shape[1] != 32:
+            raise SbnError(-1, "points must be [count][32] u32")
+        count = points.shape[0]
+        units = msm_num_units(count, self.stark.num_io)
+        ios = np.zeros((units, self.stark.num_io, 72), dtype=np.uint32)
+        cleared = np.zeros((count, 32), dtype=np.uint32)
+        infinity = np.zeros(count, dtype=np.uint8)
+        out = (C.c_void_p * max(units, 1))()
+        _check(lib().sbn_batch_prover_prove_mul_by_cofactor(self._h, _ptr(points), count, out, _ptr(cleared), _ptr(infinity), _ptr(ios)))
+        return [_take_proof(C.c_void_p(h)) for h in out[:units]], cleared, infinity, ios
+
     def close(self):
         if self._h:
             lib().sbn_batch_prover_destroy(self._h)
@@ -1067,6 +1212,37 @@ def verify_msm(stark, config, proofs, count, start, terms=None, verifier=None):
                 if code != 0:
                     raise SbnError(code, f"unit {at + i}: {reason}")
     return msm_check_links(stark, [p.public_inputs() for p in proofs], count, start, terms)
+
+
+def _verify_units(stark, config, proofs, verifier):
+    """Every unit proof verifies: the host verifier, or `verifier` in batches; raises SbnError naming the unit."""
+    if verifier is None:
+        for u, p in enumerate(proofs):
+            try:
+                verify_stark_proof(stark, p, config)
+            except SbnError as e:
+                raise SbnError(e.code, f"unit {u}: {e}") from None
+    else:
+        for at in range(0, len(proofs), verifier.max_batch):
+            for i, (code, reason) in enumerate(verifier.verify(proofs[at:at + verifier.max_batch])):
+                if code != 0:
+                    raise SbnError(code, f"unit {at + i}: {reason}")
+
+
+def verify_scalar_muls(stark, config, proofs, points, scalars, offset=None, verifier=None):
+    """Verifies the unit proofs of BatchProver.prove_scalar_muls (host verifier, or a Verifier of the table in batches) and then
+    runs scalar_mul_check on their public inputs.  Returns (products, infinity); raises SbnError when a unit is rejected (naming
+    the unit) or the check fails (naming the instance and field)."""
+    proofs = list(proofs)
+    _verify_units(stark, config, proofs, verifier)
+    return scalar_mul_check(stark, [p.public_inputs() for p in proofs], points, scalars, offset)
+
+
+def verify_mul_by_cofactor(stark, config, proofs, points, verifier=None):
+    """verify_scalar_muls for BatchProver.prove_mul_by_cofactor: returns (cleared, infinity)."""
+    proofs = list(proofs)
+    _verify_units(stark, config, proofs, verifier)
+    return mul_by_cofactor_check(stark, [p.public_inputs() for p in proofs], points)
 
 
 class Verifier:

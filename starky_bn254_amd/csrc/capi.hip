@@ -212,4 +212,26 @@ int sbn_batch_prover_prove_msm(sbn_batch_prover* B, const uint32_t* terms, size_
   return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
 }
 
+// Independent scalar multiplications of any count (include/sbn.h, "Scalar multiplications"; csrc/scalar_mul.hip): as above, the
+// padded, unit-cut list and the products are derived once on the host pool and the units go through the explicit-list path.
+int sbn_batch_prover_prove_scalar_muls(sbn_batch_prover* B, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count,
+                                       const uint32_t* offset, sbn_proof** proofs_out, uint32_t* products_out, uint8_t* infinity_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const size_t IOW = exp_io_words(B->kind), units = sbn_msm_num_units(count, B->num_io);
+  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
+  std::vector<uint32_t> own;
+  uint32_t* ios = ios_out;
+  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
+  if (int rc = sbn_scalar_mul_instances(B->kind, points, scalars, scalar_count, count, B->num_io, offset, ios, products_out, infinity_out)) return rc;
+  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+}
+
+int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* B, const uint32_t* points, size_t count, sbn_proof** proofs_out, uint32_t* cleared_out,
+                                           uint8_t* infinity_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  for (size_t u = 0; u < sbn_msm_num_units(count, B->num_io); u++) proofs_out[u] = nullptr;
+  if (B->kind != SBN_AIR_G2_EXP) return fail(SBN_ERR_BAD_ARG, "cofactor clearing is a call of the G2_EXP table (the twist), this batch prover's table is kind %d", B->kind);
+  return sbn_batch_prover_prove_scalar_muls(B, points, g2_cofactor_words(), 1, count, nullptr, proofs_out, cleared_out, infinity_out, ios_out);
+}
+
 }  // extern "C"

@@ -9,64 +9,17 @@
 //  * the table's own walk of the resulting explicit list is then checked with the chains the witness generators use
 //    (tracegen_host_chains): only that, or an offset at infinity, refuses a list.
 // tracegen_device.hip runs the same derivation on the device and falls back to this one where the chains are host work anyway.
-#include "host_common.hpp"
-#include "bn254w.cuh"
-#include <atomic>
+#include "curve_host.hpp"
 #include <cstring>
 
 using namespace sbn;
 
 namespace {
 using namespace bnw;
-
-inline void ld_u32(const uint32_t* w, u64* out) { for (int i = 0; i < 4; i++) out[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32); }
-inline void st_u32(const Fq& m, uint32_t* w) { u64 s[4]; from_m(m, s); for (int i = 0; i < 8; i++) w[i] = (uint32_t)(s[i >> 1] >> (32 * (i & 1))); }
-inline Fq fq_small(u64 v) { u64 t[4] = {v, 0, 0, 0}; return to_m(t); }
-inline Fq fq_inv_m(const Fq& a) { u64 s[4], si[4]; from_m(a, s); inv_std(s, si); return to_m(si); }
-
-// the curve constant b of y^2 = x^3 + b: 3 on G1, 3 / (9 + i) = (27 - 3i) / 82 on the twist
-template <int E> Co<E> curve_b() {
-  Co<E> r;
-  if (E == 1) { r.c[0] = fq_small(3); return r; }
-  const Fq i82 = fq_inv_m(fq_small(82)), z = {{0, 0, 0, 0}};
-  r.c[0] = mmul(fq_small(27), i82); r.c[E - 1] = fsub(z, mmul(fq_small(3), i82));
-  return r;
-}
-template <int E> bool on_curve(const Co<E>& x, const Co<E>& y, const Co<E>& b) {
-  return czero<E>(csub(cmul(y, y), cadd(cmul(cmul(x, x), x), b)));
-}
-inline Fq norm_of(const Co<1>& a) { return a.c[0]; }
-inline Fq norm_of(const Co<2>& a) { return fadd(mmul(a.c[0], a.c[0]), mmul(a.c[1], a.c[1])); }
-inline Co<1> inv_from_norm(const Co<1>&, const Fq& ni) { Co<1> r; r.c[0] = ni; return r; }
-inline Co<2> inv_from_norm(const Co<2>& a, const Fq& ni) { Co<2> r; r.c[0] = mmul(a.c[0], ni); r.c[1] = fsub(Fq{{0, 0, 0, 0}}, mmul(a.c[1], ni)); return r; }
-
-// `values` Fq elements of 8 u32 words each are below p
-bool below_p(const uint32_t* w, int values) {
-  for (int v = 0; v < values; v++) { u64 t[4]; ld_u32(w + 8 * v, t); if (geq_p(t)) return false; }
-  return true;
-}
-
-template <int E> Jac<E> ld_point(const uint32_t* w) {
-  Jac<E> p; u64 t[4];
-  for (int q = 0; q < E; q++) { ld_u32(w + 8 * q, t); p.X.c[q] = to_m(t); ld_u32(w + 8 * (E + q), t); p.Y.c[q] = to_m(t); }
-  p.Z = cone<E>();
-  return p;
-}
+using namespace sbn::curve_host;
 
 template <int E> int check_curve_terms(const uint32_t* terms, size_t K, const uint32_t* start) {
-  const size_t T = 16 * E + 8;
-  if (!below_p(start, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (start)");
-  for (size_t k = 0; k < K; k++) if (!below_p(terms + T * k, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (instance %zu)", k);
-  const Co<E> b = curve_b<E>();
-  const Jac<E> s = ld_point<E>(start);
-  if (!on_curve<E>(s.X, s.Y, b)) return fail(SBN_ERR_BAD_ARG, "start is not a point of the curve");
-  std::atomic<size_t> bad(K);
-  host_parallel_for(K, [&](size_t k) {
-    const Jac<E> p = ld_point<E>(terms + T * k);
-    if (!on_curve<E>(p.X, p.Y, b)) { size_t cur = bad.load(); while (k < cur && !bad.compare_exchange_weak(cur, k)) {} }
-  });
-  if (bad.load() < K) return fail(SBN_ERR_BAD_ARG, "x of instance %zu is not a point of the curve", bad.load());
-  return SBN_OK;
+  return check_curve_points<E>(terms, 16 * E + 8, K, start, "start");
 }
 
 template <int E> int chain_curve(const uint32_t* terms, size_t K, const uint32_t* start, uint32_t* ios, uint32_t* final_out) {
@@ -75,14 +28,7 @@ template <int E> int chain_curve(const uint32_t* terms, size_t K, const uint32_t
   std::vector<Jac<E>> sum(K + 1);          // sum[k] = offset[k], sum[K] = the last output
   std::vector<Jac<E>> term(K);
   host_parallel_for(K, [&](size_t k) {     // e_k x_k, most significant bit first
-    const Jac<E> x = ld_point<E>(terms + T * k);
-    const uint32_t* e = terms + T * k + 16 * E;
-    Jac<E> acc = jac_infinity<E>();
-    for (int t = 255; t >= 0; t--) {
-      acc = jac_double<E>(acc);
-      if ((e[t >> 5] >> (t & 31)) & 1) acc = jac_add_complete<E>(acc, x);
-    }
-    term[k] = acc;
+    term[k] = scalar_mul_jac<E>(ld_point<E>(terms + T * k), terms + T * k + 16 * E);
   });
   sum[0] = ld_point<E>(start);
   for (size_t k = 0; k < K; k++) sum[k + 1] = jac_add_complete<E>(sum[k], term[k]);

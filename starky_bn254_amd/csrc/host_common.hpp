@@ -125,6 +125,17 @@ bool tracegen_host_chains_vectorized();
 // for the curve tables (a coordinate >= p, a point off the curve): what the device derivation of tracegen_device.hip checks first
 int chain_instances_host(int kind, const uint32_t* terms, size_t K, const uint32_t* start, uint32_t* ios, uint32_t* final_out);
 int chain_terms_check_curve(int E, const uint32_t* terms, size_t K, const uint32_t* start);
+// scalar_mul.hip (independent scalar multiplications on the curve tables, E = 1 / 2): the generator words ([16E] u32) and 2p - r;
+// the refusals of the points and the offset (>= p, off the curve); the explicit list of `total` >= count rows (x, offset, scalar;
+// rows past count repeat row count - 1); SBN_ERR_WITNESS naming the first of K instances the table cannot walk (SBN_OK: none);
+// product = output + (-offset) by the complete addition for K affine outputs ([K][16E] u32; flag 1 and zero words = infinity)
+const uint32_t* curve_generator_words(int E);
+const uint32_t* g2_cofactor_words();
+int scalar_mul_check_points(int E, const uint32_t* points, size_t count, const uint32_t* offset);
+void scalar_mul_explicit_list(int E, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count, size_t total,
+                              const uint32_t* offset, uint32_t* ios);
+int scalar_mul_name_degenerate(int E, const uint32_t* ios, size_t K);
+void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* offset, size_t K, uint32_t* products, uint8_t* infinity);
 // prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)
 size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)

@@ -1046,6 +1046,76 @@ __global__ void __launch_bounds__(CS_LANES) chain_scan_kernel(uint32_t* ios, siz
   }
 }
 
+// ---- independent scalar multiplications (sbn_prover_generate_trace_scalar_muls): every instance carries the same offset --------------
+// The call shape of the reference's g2_mul_by_cofactor_circuit (src/curves/g2/circuit.rs:335-367): the caller wants e_k x_k, the table
+// proves offset + e_k x_k.  Two kernels of K-lane work around the unchanged witness kernels:
+//   scalar_mul_list_kernel      the `ios` rows the chain and witness kernels read, from the compact upload `cin` = points [K][16E],
+//                               scalars [SC][8] (SC = K, or 1: one scalar shared by every instance), offset [16E]: one lane per u32
+//                               word of the list, broadcasting the offset and the shared scalar;
+//   scalar_mul_unoffset_kernel  after affine_lambda_kernel has left the instance outputs in `outs` (one u32 limb per u64 word):
+//                               product = output + (-offset) by bnw::jac_add_complete -- output = offset (e = 0, or e a multiple of
+//                               the point's order) meets opposite operands and is the point at infinity; e x = -2 offset makes
+//                               output = -offset, equal operands, the doubling branch; the table refuses neither --
+//                               then one batched inversion of TG_INV_BATCH norms per lane for the affine form, a zero Z skipped and
+//                               flagged as in the tail of chain_scan_kernel.  The Jacobian sums wait in `jp` ([K][12E] u64) between
+//                               the two passes of a lane, so a lane holds one point at a time.
+// An instance the table cannot walk leaves garbage in `outs`; the arithmetic here is total (no index depends on a value), the call
+// is refused through the error word of the witness kernels and the host drops what this kernel wrote.
+template <int E>
+__global__ void scalar_mul_list_kernel(const uint32_t* __restrict__ cin, size_t K, size_t SC, uint32_t* __restrict__ ios) {
+  const size_t W = 16 * E, IOW = 2 * W + 8;
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= IOW * K) return;
+  const size_t k = i / IOW, w = i % IOW;
+  const uint32_t* scal = cin + W * K;
+  const uint32_t* off = scal + 8 * SC;
+  ios[i] = w < W ? cin[W * k + w] : (w < 2 * W ? off[w - W] : scal[(SC == 1 ? 0 : 8 * k) + (w - 2 * W)]);
+}
+template <int E>
+__global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ outs, u64* __restrict__ jp,
+                                           uint32_t* __restrict__ products, unsigned char* __restrict__ infinity) {
+  const size_t W = 16 * E, IOW = 2 * W + 8;
+  const size_t L = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
+  if (L >= NL) return;
+  Fq nrm[TG_INV_BATCH];
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = L + (size_t)j * NL;
+    nrm[j] = fq_one();
+    if (i >= K) continue;
+    Jac<E> o, m; u64 t4[4];
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        const u64* src = outs + W * i + 8 * (c * E + q);
+        for (int h = 0; h < 4; h++) t4[h] = (src[2 * h] & 0xffffffffULL) | (src[2 * h + 1] << 32);
+        (c ? o.Y : o.X).c[q] = to_m(t4);
+        u32x8_to_u64x4(ios + IOW * i + W + 8 * (c * E + q), t4);
+        (c ? m.Y : m.X).c[q] = to_m(t4);
+      }
+    o.Z = cone<E>(); m.Z = o.Z;
+    m.Y = csub(csub(m.Y, m.Y), m.Y);   // -offset
+    const Jac<E> r = jac_add_complete<E>(o, m);
+    st_jac<E>(jp + 12 * E * i, r);
+    if (!czero<E>(r.Z)) nrm[j] = cnorm(r.Z);
+  }
+  batch_inverse(nrm);
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = L + (size_t)j * NL;
+    if (i >= K) continue;
+    const Jac<E> p = ld_jac<E>(jp + 12 * E * i);
+    const bool inf = czero<E>(p.Z);
+    Co<E> v[2];
+    if (inf) { v[0] = p.Z; v[1] = p.Z; }   // the point at infinity: zero words and its flag
+    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        u64 s[4]; from_m(v[c].c[q], s);
+        for (int w = 0; w < 8; w++) products[W * i + 8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+      }
+    infinity[i] = inf ? 1 : 0;
+  }
+}
+
 // outs: [K][12][4] = x_k^e_k in standard form (fq12_chain_kernel on offsets of one); start: 12 coefficients of 8 u32 limbs
 __global__ void __launch_bounds__(192) fq12_offset_scan_kernel(uint32_t* ios, size_t iow, size_t K, const uint32_t* __restrict__ start, const u64* __restrict__ outs) {
   __shared__ Fq B[12], X[12], PB[144];

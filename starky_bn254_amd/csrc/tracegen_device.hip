@@ -139,6 +139,11 @@ static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, siz
   return ios;
 }
 
+// sbn_prover_generate_trace_scalar_muls: every instance carries `offset`; the list is expanded on the device from the points, the
+// one-or-K scalars and the offset, and the products output + (-offset) are computed there (kernels_tracegen.cuh, "independent
+// scalar multiplications").  G1 / G2 only.
+struct ScalarMulIn { const uint32_t* points; const uint32_t* scalars; size_t scalar_count; const uint32_t* offset; uint32_t* products_out; uint8_t* infinity_out; uint32_t* ios_out; };
+
 // One sbn_prover_generate_trace call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
 struct TraceJob {
   sbn_prover* const P;
@@ -160,9 +165,10 @@ struct TraceJob {
     if (P->set.trace_timing && hipEventCreate(&e) == hipSuccess && hipEventRecord(e, st) == hipSuccess) kev.push_back(e);
   }
   // the timed span opens (EX_TRACEGEN_MS); the instance list goes in from `h_ios`, the caller's memory or a pinned copy of it
-  int begin(const void* h_ios, uint32_t* d_ios, int* d_err) {
+  // (`words`: u32 words that go up when it is not the whole list: the compact form of the scalar multiplications)
+  int begin(const void* h_ios, uint32_t* d_ios, int* d_err, size_t words = 0) {
     HIPC(hipEventRecord(P->abs_ev[0], st));
-    HIPC(hipMemcpyAsync(d_ios, h_ios, IOW * K * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_ios, h_ios, (words ? words : IOW * K) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
     mark();
     return 0;
@@ -216,10 +222,16 @@ struct TraceJob {
 
 // G1ExpStark / G2ExpStark (E = 1 / 2)
 template <int E>
-static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr) {
+static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const ScalarMulIn* sm = nullptr) {
   const size_t IOW = 8 * (4 * E + 1);  // u32 words per instance: x and offset (2E Fq each) + exp_val
   std::vector<uint32_t> prelim;        // chained: x, start, exp_val of every instance; the device rewrites the offsets
-  if (ch) {
+  const size_t cin_words = sm ? 16 * E * K + 8 * sm->scalar_count + 16 * E : 0;   // scalar multiplications: u32 words of the compact upload
+  if (sm) {   // the host keeps its own explicit list for the public inputs; only the compact form goes up
+    if (int rc = scalar_mul_check_points(E, sm->points, K, sm->offset)) return rc;
+    prelim.resize(IOW * K);
+    scalar_mul_explicit_list(E, sm->points, sm->scalars, sm->scalar_count, K, K, sm->offset, prelim.data());
+    ios = prelim.data();
+  } else if (ch) {
     if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a chained list has at most %d instances", tg::CS_LANES);
     if (int rc = chain_terms_check_curve(E, ch->terms, K, ch->start)) return rc;
     prelim = preliminary_list(*ch, K, 16 * E, 8, ch->start);
@@ -242,6 +254,10 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   u64* d_terms = ch ? J.take(12 * E * K) : nullptr;                           // e_k x_k, then the two scan buffers
   u64* d_scan[2] = {ch ? J.take(12 * E * K) : nullptr, ch ? J.take(12 * E * K) : nullptr};
   int* d_err_pre = ch ? (int*)J.take(1) : nullptr;                            // flags of the preliminary chains (offsets = start): never read
+  uint32_t* d_cin = sm ? (uint32_t*)J.take(cin_words / 2 + 1) : nullptr;      // scalar multiplications: the compact upload, the Jacobian
+  u64* d_jp = sm ? J.take(12 * E * K) : nullptr;                              // products between the two passes of a lane, the affine
+  uint32_t* d_prod = sm ? (uint32_t*)J.take(8 * E * K) : nullptr;             // products ([K][16E] u32) and their infinity flags
+  unsigned char* d_inf = sm ? (unsigned char*)J.take(K / 8 + 1) : nullptr;
   if (int rc = J.fits()) return rc;
   if (int rc = range_check_setup(P->device)) return rc;
   // both chains of every instance on the device, flags into `errw` (chain_mode 2 / 1, see below)
@@ -263,11 +279,24 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
     return 0;
   };
   // the instance list in and the outputs + error word back cross through pinned staging (chained: the derived list comes back too)
-  const size_t io_words = (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
-  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words + (ch ? io_words : 0))) return rc;
-  memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
+  // (scalar multiplications: the compact form in, the products and their flags back behind the outputs)
+  const size_t io_words = sm ? (cin_words + 1) / 2 : (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
+  const size_t prod_words = sm ? 8 * E * K : 0, inf_words = sm ? (K + 7) / 8 : 0;
+  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words + (ch ? io_words : 0) + prod_words + inf_words)) return rc;
   u64* const h_out = P->h_io + io_words;
-  if (int rc = J.begin(P->h_io, d_ios, d_err)) return rc;
+  u64* const h_prod = h_out + out_words;
+  if (sm) {
+    uint32_t* h = (uint32_t*)P->h_io;
+    memcpy(h, sm->points, 16 * E * K * sizeof(uint32_t));
+    memcpy(h + 16 * E * K, sm->scalars, 8 * sm->scalar_count * sizeof(uint32_t));
+    memcpy(h + 16 * E * K + 8 * sm->scalar_count, sm->offset, 16 * E * sizeof(uint32_t));
+    if (int rc = J.begin(P->h_io, d_cin, d_err, cin_words)) return rc;
+    hipLaunchKernelGGL(tg::scalar_mul_list_kernel<E>, blocks(IOW * K, 256), dim3(256), 0, st, d_cin, K, sm->scalar_count, d_ios);
+    J.mark();
+  } else {
+    memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
+    if (int rc = J.begin(P->h_io, d_ios, d_err)) return rc;
+  }
   if (ch) {   // offsets on the device (kernels_tracegen.cuh, "chained instance lists"); only chain_mode 1 and 2 come here
     if (int rc = launch_chains(d_err_pre)) return rc;
     hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, d_pre, d_terms);
@@ -291,6 +320,10 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   J.mark();
   hipLaunchKernelGGL(tg::affine_lambda_kernel<E>, blocks((n + tg::TG_ROWS - 1) / tg::TG_ROWS, 64), dim3(64), 0, st, d_ios, K, ja, jb, n, sv, row_op, d_out, d_err);
   J.mark();
+  if (sm) {   // the products from the instance outputs affine_lambda_kernel left in d_out
+    hipLaunchKernelGGL(tg::scalar_mul_unoffset_kernel<E>, blocks((K + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, K, d_out, d_jp, d_prod, d_inf);
+    J.mark();
+  }
   hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, J.sh.gadget_col, P->d_trace, d_err);
   J.mark();
   if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
@@ -300,14 +333,29 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   HIPC(hipMemcpyAsync(h_out + 16 * E * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
   if (ch) HIPC(hipMemcpyAsync(h_out + out_words, d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   static const char* const names[] = {"flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
+  if (sm) {
+    HIPC(hipMemcpyAsync(h_prod, d_prod, 16 * E * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(h_prod + prod_words, d_inf, K, hipMemcpyDeviceToHost, st));
+  }
   static const char* const names_chained[] = {"chain_offsets", "flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
-  if (int rc = J.end(ch ? names_chained : names)) return rc;
+  static const char* const names_scalar[] = {"scalar_list", "flags+pulses", "chains", "affine+lambda", "un_offset", "row_witness", "range_check"};
+  if (int rc = J.end(sm ? names_scalar : ch ? names_chained : names)) return rc;
   // public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156)
   const int rc = J.finish((int)(h_out[16 * E * K] & 0xffffffffu), pi_out, [&](size_t k, u64* p) {
     for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
     for (int i = 0; i < 16 * E; i++) p[IOW + i] = h_out[16 * E * k + i];
   });
   if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
+  if (sm && rc == SBN_ERR_WITNESS && ((int)(h_out[16 * E * K] & 0xffffffffu) & tg::TG_ERR_DEGENERATE)) {
+    // the kernels report an error word only: the host walk names the first instance the table cannot walk (error path)
+    if (int named = scalar_mul_name_degenerate(E, ios, K)) return named;
+    return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
+  }
+  if (sm && rc == SBN_OK) {
+    if (sm->products_out) memcpy(sm->products_out, h_prod, 16 * E * K * sizeof(uint32_t));
+    if (sm->infinity_out) memcpy(sm->infinity_out, h_prod + prod_words, K);
+    if (sm->ios_out) memcpy(sm->ios_out, ios, IOW * K * sizeof(uint32_t));
+  }
   return rc;
 }
 
@@ -458,6 +506,33 @@ extern "C" int sbn_prover_generate_trace_chained(sbn_prover* P, const uint32_t* 
   const ChainedIn ch{terms, start, ios_out};
   if (fq12) return generate_trace_device_fq12(P, nullptr, num_io, pi_out, &ch);
   return kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, nullptr, num_io, pi_out, &ch) : generate_trace_device<2>(P, nullptr, num_io, pi_out, &ch);
+}
+
+// sbn_prover_generate_trace on the list sbn_scalar_mul_instances derives from (points, scalars, offset), one unit: where the curve
+// chains run on the device (chain_mode 1 and 2) the list is expanded and un-offset there; with host-pool chains the list is host
+// work anyway and takes the explicit path.
+extern "C" int sbn_prover_generate_trace_scalar_muls(sbn_prover* P, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t num_io,
+                                                     const uint32_t* offset, uint64_t* pi_out, uint32_t* products_out, uint8_t* infinity_out, uint32_t* ios_out) {
+  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  const int kind = P->air.kind;
+  if (kind != SBN_AIR_G1_EXP && kind != SBN_AIR_G2_EXP) return fail(SBN_ERR_UNSUPPORTED, "scalar multiplications cover the curve tables G1_EXP and G2_EXP");
+  if (!points || !scalars || num_io == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no instance");
+  if (scalar_count != 1 && scalar_count != num_io) return fail(SBN_ERR_BAD_ARG, "scalar_count must be 1 (one shared scalar) or count = %zu, got %zu", num_io, scalar_count);
+  if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
+  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
+  if (P->n < 65536 || P->n > 262144) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  const int E = kind == SBN_AIR_G1_EXP ? 1 : 2;
+  if (!offset) offset = curve_generator_words(E);
+  if (P->chain_mode == 0) {
+    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
+    if (int rc = sbn_scalar_mul_instances(kind, points, scalars, scalar_count, num_io, num_io, offset, ios.data(), products_out, infinity_out)) return rc;
+    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
+    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
+    return rc;
+  }
+  const ScalarMulIn sm{points, scalars, scalar_count, offset, products_out, infinity_out, ios_out};
+  return E == 1 ? generate_trace_device<1>(P, nullptr, num_io, pi_out, nullptr, &sm) : generate_trace_device<2>(P, nullptr, num_io, pi_out, nullptr, &sm);
 }
 
 extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
