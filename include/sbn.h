@@ -463,6 +463,60 @@ int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* b, const uint32_t* 
 int sbn_mul_by_cofactor_check(size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, const uint32_t* points,
                               uint32_t* cleared_out, uint8_t* infinity_out);
 
+/* Field powers --------------------------------------------------------------------------------------- */
+/* Powers and POWER TOWERS on the three field Exp tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64: the caller wants x^e itself.  A field
+ * table needs no offset trick (its offset is multiplicative: every instance here carries offset = 1, word 0 = 1 and the rest 0), but
+ * one call shape cannot be said as a list of independent or offset-chained instances: a TOWER, `depth` >= 1 consecutive instances
+ * where level 0 has x = base and level l has x = the OUTPUT of level l - 1.  Every level carries the tower's exponent e, so level l
+ * outputs base^(e^(l+1)).  FQ12_EXP_U64 exists for this: the BN parameter x = 4965661367192848881 fits a u64 (sbn_bn_x) and the hard
+ * part of the final exponentiation starts from f^x, f^(x^2), f^(x^3): one tower of depth 3.  depth = 1 is a batch of independent
+ * powers (inverses with e = p - 2, Legendre symbols with (p - 1) / 2, square roots with (p + 1) / 4 in FQ_EXP).
+ * One definition for every entry point below, W = 8 (FQ_EXP) or 96 (the Fq12 tables: twelve flat-basis coefficients) u32 words per
+ * field element, as in `ios`:
+ *   bases  [count][W] u32: the level-0 x of every tower;
+ *   exps   [exp_count][8] u32 ([exp_count][2], low word first, for FQ12_EXP_U64), exp_count = count (one exponent per tower), or 1
+ *          for ONE exponent shared by every tower; 256-bit integers as they are, never reduced;
+ *   depth  common to the towers of a call; the count * depth instances are laid out tower-major (instance g = tower * depth + level).
+ * With M = count * depth and units = sbn_msm_num_units(M, num_io) the explicit list has units * num_io rows: row g < M is (x of its
+ * level, one, the tower's exponent), row g >= M a copy of row M - 1 (the reference's resize rule, as sbn_msm_instances).  Towers may
+ * straddle unit boundaries.  powers_out: [count][depth][W] u32 (the output of every real instance), ios_out: [units * num_io][24 |
+ * 200 | 194] u32; both optional.  A zero base and a zero exponent are legal and the table defines the result (x^0 = 1, also for
+ * x = 0; 0^e = 0 for e > 0).
+ * Refused, in this order: SBN_ERR_UNSUPPORTED for a curve table or a kind that is no Exp table (a curve table takes the scalar
+ * multiplications above); SBN_ERR_BAD_ARG for a null argument, count = 0, depth = 0, num_io = 0 or exp_count outside {1, count};
+ * then, tower by tower and as the table's own generator refuses an instance, SBN_ERR_BAD_ARG for a base with a coefficient >= p
+ * and SBN_ERR_NON_CANONICAL for a u64 exponent that is no canonical field element (>= 2^64 - 2^32 + 1), naming the tower. */
+int sbn_bn_x(uint32_t out[2]);   /* the BN parameter x = 4965661367192848881 = 0x44E992B44A6909F1, low word first */
+/* The explicit list and the powers on the host pool, no device: towers side by side, the levels of a tower one after the other.
+ * num_io is not checked against any table (this only shapes a list). */
+int sbn_power_instances(int32_t kind, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth, size_t num_io,
+                        uint32_t* ios_out, uint32_t* powers_out);
+/* One unit on a prover of the table: count * depth <= the table's num_io (SBN_ERR_BAD_ARG otherwise), the rest of the unit is padded.
+ * On success the loaded trace, the public inputs and ios_out ([num_io][words per instance]) are, word for word, those of
+ * sbn_prover_generate_trace on the list of sbn_power_instances; sizes and the failure rule as there (a failing call leaves NO trace
+ * loaded).  On the Fq12 tables, whose chains run on the device, one workgroup per tower walks its levels there: it writes the output
+ * of a level into the x words of the next instance and runs that level's chain, with no host round trip between levels; the pads are
+ * filled on the device from the last real instance, and the derived list and the powers come back in the download of the instance
+ * outputs.  FQ_EXP (chains on the host pool) and an Fq12 prover created under SBN_FQ12_HOST_CHAIN walk the towers on the host pool and
+ * take the explicit path.  The words are the same in every placement. */
+int sbn_prover_generate_trace_powers(sbn_prover* p, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth,
+                                     uint64_t* pi_out, uint32_t* powers_out, uint32_t* ios_out);
+/* Any count, as units of the batch prover's table (units as above): proofs_out[units] in unit order, word for word what
+ * sbn_batch_prover_prove_ios gives on the list of sbn_power_instances, which is derived once (every unit's first x is known before
+ * the first unit is taken, so no context waits for another).  Failure rule as sbn_batch_prover_prove_msm: a refused list leaves the
+ * batch prover usable and every proofs_out entry null. */
+int sbn_batch_prover_prove_powers(sbn_batch_prover* b, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth,
+                                  sbn_proof** proofs_out, uint32_t* powers_out, uint32_t* ios_out);
+/* The twin of sbn_msm_check_links, on the public inputs of the unit proofs (host, no device; it verifies NO proof): what a circuit
+ * states with `connect` calls.  Checked, in instance order: units == sbn_msm_num_units(count * depth, num_io); every offset is one;
+ * every exponent is the caller's; x of level 0 equals the tower's base; x of level l equals the output of level l - 1, across unit
+ * boundaries; every output limb is in range (16 bits in the Fq12 tables, 32 in FQ_EXP) and every output coefficient is < p; every
+ * pad instance equals instance count * depth - 1 in x, offset, exponent and output.  SBN_OK and powers_out (optional,
+ * [count][depth][W]) = the outputs, or SBN_ERR_VERIFY_FAILED with sbn_last_error naming the first global instance and the field
+ * (x, offset, exponent, output) that breaks. */
+int sbn_power_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, size_t depth,
+                    const uint32_t* bases, const uint32_t* exps, size_t exp_count, uint32_t* powers_out);
+
 /* One oversized trace split over the GPUs of a node (BASELINE config "Single Fq12 exponentiation proof, trace height
  * 2^18, 8xMI355X with RCCL FRI fold"; reference workload src/fields/fq12/exp.rs:638-696).  One rank per GPU (one process
  * each, or the threads of one process with sbn_local_comm_create); every rank calls the same functions with the same

@@ -143,6 +143,11 @@ extern "C" {
     pub fn sbn_scalar_mul_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, points: *const u32, scalars: *const u32, scalar_count: usize, offset: *const u32, products_out: *mut u32, infinity_out: *mut u8) -> i32;
     pub fn sbn_batch_prover_prove_mul_by_cofactor(b: *mut sbn_batch_prover, points: *const u32, count: usize, proofs_out: *mut *mut sbn_proof, cleared_out: *mut u32, infinity_out: *mut u8, ios_out: *mut u32) -> i32;
     pub fn sbn_mul_by_cofactor_check(num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, points: *const u32, cleared_out: *mut u32, infinity_out: *mut u8) -> i32;
+    pub fn sbn_bn_x(out: *mut u32) -> i32;
+    pub fn sbn_power_instances(kind: i32, bases: *const u32, exps: *const u32, exp_count: usize, count: usize, depth: usize, num_io: usize, ios_out: *mut u32, powers_out: *mut u32) -> i32;
+    pub fn sbn_prover_generate_trace_powers(p: *mut sbn_prover, bases: *const u32, exps: *const u32, exp_count: usize, count: usize, depth: usize, pi_out: *mut u64, powers_out: *mut u32, ios_out: *mut u32) -> i32;
+    pub fn sbn_batch_prover_prove_powers(b: *mut sbn_batch_prover, bases: *const u32, exps: *const u32, exp_count: usize, count: usize, depth: usize, proofs_out: *mut *mut sbn_proof, powers_out: *mut u32, ios_out: *mut u32) -> i32;
+    pub fn sbn_power_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, depth: usize, bases: *const u32, exps: *const u32, exp_count: usize, powers_out: *mut u32) -> i32;
 
     pub fn sbn_proof_num_words(p: *const sbn_proof) -> usize;
     pub fn sbn_proof_words(p: *const sbn_proof) -> *const u64;

@@ -41,6 +41,7 @@ EXPORTS = [
     "sbn_msm_num_units", "sbn_msm_instances", "sbn_batch_prover_prove_msm", "sbn_msm_check_links",
     "sbn_curve_generator", "sbn_g2_cofactor", "sbn_scalar_mul_instances", "sbn_prover_generate_trace_scalar_muls",
     "sbn_batch_prover_prove_scalar_muls", "sbn_scalar_mul_check", "sbn_batch_prover_prove_mul_by_cofactor", "sbn_mul_by_cofactor_check",
+    "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
@@ -172,6 +173,11 @@ def lib():
         L.sbn_scalar_mul_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, vp, vp, sz, vp, vp, vp]
         L.sbn_batch_prover_prove_mul_by_cofactor.argtypes = [vp, vp, sz, C.POINTER(vp), vp, vp, vp]
         L.sbn_mul_by_cofactor_check.argtypes = [sz, C.POINTER(vp), sz, sz, vp, vp, vp]
+        L.sbn_bn_x.argtypes = [vp]
+        L.sbn_power_instances.argtypes = [C.c_int32, vp, vp, sz, sz, sz, sz, vp, vp]
+        L.sbn_prover_generate_trace_powers.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
+        L.sbn_batch_prover_prove_powers.argtypes = [vp, vp, vp, sz, sz, sz, C.POINTER(vp), vp, vp]
+        L.sbn_power_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, sz, vp, vp, sz, vp]
         L.sbn_prove.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, u32, vp, sz, C.POINTER(vp)]
         L.sbn_proof_num_words.restype = sz
         L.sbn_proof_num_words.argtypes = [vp]
@@ -645,6 +651,103 @@ def mul_by_cofactor_check(stark, public_inputs_per_unit, points):
     return cleared, infinity
 
 
+# ---- field powers and power towers (include/sbn.h, "Field powers") -------------------------------------------------------------
+BN_P = 21888242871839275222246405745257275088696311157297823662689037894645226208583   # the base field of BN254
+BN_X = 4965661367192848881                # the BN parameter x = 0x44E992B44A6909F1 (sbn_bn_x): p, r and the final exponentiation are polynomials in it
+FQ_INVERSE_EXP = BN_P - 2                 # x^(p-2) = 1/x for x != 0 (and 0 for x = 0)
+FQ_LEGENDRE_EXP = (BN_P - 1) // 2         # 1 for a non-zero square, p - 1 for a non-residue, 0 for 0
+FQ_SQRT_EXP = (BN_P + 1) // 4             # a square root of x when x is a square: valid because p = 3 mod 4 (check with fq_sqrt_flags)
+
+
+def _power_words(stark):
+    """(u32 words of a field element, of the exponent) in an instance row of the field Exp table `stark`."""
+    try:
+        return {AIR_FQ_EXP: (8, 8), AIR_FQ12_EXP: (96, 8), AIR_FQ12_EXP_U64: (96, 2)}[stark.kind]
+    except (KeyError, AttributeError):
+        raise SbnError(-7, "field powers cover the field tables FqExpStark, Fq12ExpStark and Fq12ExpU64Stark") from None
+
+
+def _int_limbs(v, n):
+    if v < 0 or v >> (32 * n):
+        raise SbnError(-1, f"{v} does not fit {32 * n} bits")
+    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
+
+
+def _power_args(stark, bases, exps, depth):
+    """bases (count, W) uint32, or Python ints for FqExpStark; exps (count, ew) uint32, or (ew,) / (1, ew) / one Python int = one
+    exponent shared by every tower, or a list of Python ints = one per tower (little-endian u32 limbs); depth >= 1."""
+    w, ew = _power_words(stark)
+    if w == 8 and not isinstance(bases, np.ndarray) and len(bases) and all(isinstance(b, int) for b in bases):
+        bases = [_int_limbs(b, 8) for b in bases]
+    bases = np.ascontiguousarray(bases, dtype=np.uint32)
+    if isinstance(exps, int):
+        exps = _int_limbs(exps, ew)
+    elif not isinstance(exps, np.ndarray) and len(exps) and all(isinstance(e, int) for e in exps) and len(exps) != ew:
+        exps = [_int_limbs(e, ew) for e in exps]
+    exps = np.ascontiguousarray(exps, dtype=np.uint32)
+    if exps.ndim == 1:
+        exps = exps.reshape(1, -1)
+    if bases.ndim != 2 or bases.shape[0] < 1 or bases.shape[1] != w or exps.ndim != 2 or exps.shape[1] != ew:
+        raise SbnError(-1, f"bases must be [count][{w}] u32 and exps [count][{ew}] or [{ew}] u32")
+    if int(depth) < 1:
+        raise SbnError(-1, "depth must be >= 1")
+    return bases, exps, int(depth), w, ew
+
+
+def bn_x():
+    """The BN parameter as the library states it (sbn_bn_x); equals BN_X."""
+    out = np.zeros(2, dtype=np.uint32)
+    _check(lib().sbn_bn_x(_ptr(out)))
+    return int(out[0]) | (int(out[1]) << 32)
+
+
+def power_instances(stark, bases, exps, depth=1):
+    """Powers and power towers as instances of the field Exp table `stark` (sbn_power_instances): `count` towers of `depth`
+    consecutive instances, offset one, level 0 x = base, level l x = the output of level l - 1, every level with the tower's
+    exponent; the last unit is padded with copies of the last instance.  Returns (ios_units, powers): (units, num_io, words per
+    instance) uint32 as BatchProver.prove_ios takes it and the outputs (count, depth, W) uint32, powers[k][l] = base_k^(e^(l+1)).
+    Exponents are never reduced.  No device needed."""
+    bases, exps, depth, w, ew = _power_args(stark, bases, exps, depth)
+    count = bases.shape[0]
+    if stark.num_io < 1:
+        raise SbnError(-1, "the table has no instances")
+    units = msm_num_units(count * depth, stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * w + ew), dtype=np.uint32)
+    powers = np.zeros((count, depth, w), dtype=np.uint32)
+    _check(lib().sbn_power_instances(stark.kind, _ptr(bases), _ptr(exps), exps.shape[0], count, depth, stark.num_io, _ptr(ios), _ptr(powers)))
+    return ios, powers
+
+
+def power_check(stark, public_inputs_per_unit, bases, exps, depth=1):
+    """The check of a batch of powers / power towers (sbn_power_check) on the public inputs of its unit proofs: offsets are one,
+    exponents the caller's, level 0 starts from the caller's base and level l from the output of level l - 1 (across units), the
+    pads repeat the last instance, every output is a field element.  Returns the powers (count, depth, W); raises SbnError(-6)
+    naming the first instance and field that breaks.  Verifies NO proof: verify_powers does both."""
+    bases, exps, depth, w, ew = _power_args(stark, bases, exps, depth)
+    count = bases.shape[0]
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
+    if any(p.shape[0] != stark.num_public_inputs for p in pis):
+        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
+    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    powers = np.zeros((count, depth, w), dtype=np.uint32)
+    _check(lib().sbn_power_check(stark.kind, stark.num_io, ptrs, len(pis), count, depth, _ptr(bases), _ptr(exps), exps.shape[0], _ptr(powers)))
+    return powers
+
+
+def fq_sqrt_flags(xs, roots):
+    """Per element, whether root^2 == x in Fq: what a caller of FqExpStark with FQ_SQRT_EXP checks, because x^((p+1)/4) is a square
+    root only when x is a square (a non-residue gives a root of -x: not an error, the flag is False).  xs, roots: Python ints or
+    (count, 8) uint32 limbs.  Returns a (count,) bool array."""
+    def ints(v):
+        if isinstance(v, np.ndarray):
+            return [sum(int(w) << (32 * i) for i, w in enumerate(row)) for row in v.reshape(-1, 8)]
+        return [int(x) for x in v]
+    xs, roots = ints(xs), ints(roots)
+    if len(xs) != len(roots):
+        raise SbnError(-1, "xs and roots differ in length")
+    return np.array([x < BN_P and r < BN_P and r * r % BN_P == x for x, r in zip(xs, roots)], dtype=bool)
+
+
 class Proof:
     """StarkProofWithPublicInputs as canonical proof words (layout: include/sbn.h)."""
 
@@ -1003,6 +1106,18 @@ class Prover:
                                                            _ptr(pi), _ptr(products), _ptr(infinity), _ptr(ios)))
         return pi, products, infinity, ios
 
+    def generate_trace_powers(self, bases, exps, depth=1):
+        """generate_trace on the one-unit list power_instances(stark, bases, exps, depth) gives (count * depth <= num_io, the
+        rest padded), the towers linked and walked on the device where the table's chains run there; returns (public inputs,
+        powers, ios)."""
+        bases, exps, depth, w, ew = _power_args(self.stark, bases, exps, depth)
+        count = bases.shape[0]
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        powers = np.zeros((count, depth, w), dtype=np.uint32)
+        ios = np.zeros((self.stark.num_io, 2 * w + ew), dtype=np.uint32)
+        _check(lib().sbn_prover_generate_trace_powers(self._h, _ptr(bases), _ptr(exps), exps.shape[0], count, depth, _ptr(pi), _ptr(powers), _ptr(ios)))
+        return pi, powers, ios
+
     def read_trace(self):
         trace = np.zeros((self.stark.num_columns, 1 << self.degree_bits), dtype=np.uint64)
         _check(lib().sbn_prover_read_trace(self._h, _ptr(trace)))
@@ -1141,6 +1256,26 @@ class BatchProver:
         _check(lib().sbn_batch_prover_prove_mul_by_cofactor(self._h, _ptr(points), count, out, _ptr(cleared), _ptr(infinity), _ptr(ios)))
         return [_take_proof(C.c_void_p(h)) for h in out[:units]], cleared, infinity, ios
 
+    def prove_powers(self, bases, exps, depth=1):
+        """Powers / power towers of any count (arguments as power_instances) proved as units of the table, the last one padded
+        (sbn_batch_prover_prove_powers).  Returns (proofs, powers, ios)."""
+        bases, exps, depth, w, ew = _power_args(self.stark, bases, exps, depth)
+        count = bases.shape[0]
+        units = msm_num_units(count * depth, self.stark.num_io)
+        ios = np.zeros((units, self.stark.num_io, 2 * w + ew), dtype=np.uint32)
+        powers = np.zeros((count, depth, w), dtype=np.uint32)
+        out = (C.c_void_p * max(units, 1))()
+        _check(lib().sbn_batch_prover_prove_powers(self._h, _ptr(bases), _ptr(exps), exps.shape[0], count, depth, out, _ptr(powers), _ptr(ios)))
+        return [_take_proof(C.c_void_p(h)) for h in out[:units]], powers, ios
+
+    def prove_bn_x_powers(self, fs):
+        """f^x, f^(x^2), f^(x^3) for the BN parameter x = BN_X and every f of fs ((count, 96) uint32): towers of depth 3 with the
+        shared exponent BN_X, what the hard part of the final exponentiation starts from.  Returns (proofs, powers, ios), powers
+        (count, 3, 96).  A Fq12ExpU64Stark batch prover only."""
+        if self.stark.kind != AIR_FQ12_EXP_U64:
+            raise SbnError(-1, "the BN-parameter powers are a call of Fq12ExpU64Stark")
+        return self.prove_powers(fs, BN_X, depth=3)
+
     def close(self):
         if self._h:
             lib().sbn_batch_prover_destroy(self._h)
@@ -1243,6 +1378,22 @@ def verify_mul_by_cofactor(stark, config, proofs, points, verifier=None):
     proofs = list(proofs)
     _verify_units(stark, config, proofs, verifier)
     return mul_by_cofactor_check(stark, [p.public_inputs() for p in proofs], points)
+
+
+def verify_powers(stark, config, proofs, bases, exps, depth=1, verifier=None):
+    """Verifies the unit proofs of BatchProver.prove_powers (host verifier, or a Verifier of the table in batches) and then runs
+    power_check on their public inputs.  Returns the powers (count, depth, W); raises SbnError when a unit is rejected (naming the
+    unit) or the check fails (naming the instance and field)."""
+    proofs = list(proofs)
+    _verify_units(stark, config, proofs, verifier)
+    return power_check(stark, [p.public_inputs() for p in proofs], bases, exps, depth)
+
+
+def verify_bn_x_powers(stark, config, proofs, fs, verifier=None):
+    """verify_powers for BatchProver.prove_bn_x_powers: returns (count, 3, 96) = f^x, f^(x^2), f^(x^3) per input."""
+    if stark.kind != AIR_FQ12_EXP_U64:
+        raise SbnError(-1, "the BN-parameter powers are a call of Fq12ExpU64Stark")
+    return verify_powers(stark, config, proofs, fs, BN_X, depth=3, verifier=verifier)
 
 
 class Verifier:

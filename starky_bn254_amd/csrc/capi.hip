@@ -226,6 +226,22 @@ int sbn_batch_prover_prove_scalar_muls(sbn_batch_prover* B, const uint32_t* poin
   return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
 }
 
+// Field powers and power towers of any count (include/sbn.h, "Field powers"; csrc/powers.hip): as above, the padded, unit-cut list
+// and the powers are derived once on the host pool, so a tower that straddles two units needs no context to wait for another, and
+// the units go through the explicit-list path.
+int sbn_batch_prover_prove_powers(sbn_batch_prover* B, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth,
+                                  sbn_proof** proofs_out, uint32_t* powers_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const size_t IOW = exp_io_words(B->kind), fits = count && depth <= (size_t)-1 / 2 / count;
+  const size_t units = fits ? sbn_msm_num_units(count * depth, B->num_io) : 0;
+  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
+  std::vector<uint32_t> own;
+  uint32_t* ios = ios_out;
+  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
+  if (int rc = sbn_power_instances(B->kind, bases, exps, exp_count, count, depth, B->num_io, ios, powers_out)) return rc;
+  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+}
+
 int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* B, const uint32_t* points, size_t count, sbn_proof** proofs_out, uint32_t* cleared_out,
                                            uint8_t* infinity_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");

@@ -136,6 +136,11 @@ void scalar_mul_explicit_list(int E, const uint32_t* points, const uint32_t* sca
                               const uint32_t* offset, uint32_t* ios);
 int scalar_mul_name_degenerate(int E, const uint32_t* ios, size_t K);
 void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* offset, size_t K, uint32_t* products, uint8_t* infinity);
+// powers.hip (field powers and power towers on the field Exp tables): u32 words of one field element in `ios` (8 / 96; 0: not a
+// field Exp table); the refusals of the bases and exponents (a coefficient >= p, a u64 exponent that is no canonical field element),
+// naming the tower
+size_t power_elem_words(int kind);
+int power_check_inputs(int kind, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count);
 // prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)
 size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)

@@ -1154,6 +1154,63 @@ __global__ void __launch_bounds__(192) fq12_rebase_kernel(const uint32_t* __rest
   }
 }
 
+// ---- power towers (sbn_prover_generate_trace_powers): x of level l = the output of level l - 1, offset = one everywhere ------------
+// `count` towers of `depth` consecutive instances (tower-major: instance g = tower * depth + level).  The levels of a tower are
+// sequential by definition, the towers independent, so ONE workgroup walks the levels of its tower with the lane roles, the LDS
+// layout and the step of fq12_chain_kernel: at the end of a level the output sits in B in LDS; the twelve coefficient lanes turn
+// it into standard form, store it into the x words of the next instance in `ios` (for the kernels that follow: the row kernel, the
+// flags and the download read them behind the kernel boundary, which is where those stores become visible to other workgroups) and
+// load A from those very registers, as fq12_chain_kernel would from the words.  Nothing this kernel stores to global memory is read
+// again inside it, so no fence and no scope question arises; the barrier orders LDS only.  `ios` arrives with the level-0 x, the
+// offsets (one) and the exponents of every instance; the x words of the levels above 0 are written here.
+//   fq12_tower_pad_kernel  the reference's resize rule on the device: instances [M, K) become instance M - 1 again -- its `ios`
+//                          row (whose x may have been derived above), both chains and the compact output -- one workgroup per pad.
+__global__ void __launch_bounds__(320) fq12_tower_kernel(uint32_t* ios, size_t iow, int steps, size_t depth, u64* __restrict__ ca, u64* __restrict__ cb,
+                                                         u64* __restrict__ outs) {
+  __shared__ Fq A[12], B[12], PA[144], PB[144];
+  const int tid = threadIdx.x, c = tid % 12;
+  const bool is_a = tid < 12, is_b = tid >= 12 && tid < 24;
+  for (size_t l = 0; l < depth; l++) {
+    const size_t k = blockIdx.x * depth + l;
+    uint32_t* io = ios + iow * k;
+    Fq nv;
+    if (is_a) {
+      u64 t4[4];
+      if (l == 0) u32x8_to_u64x4(io + 8 * c, t4);
+      else {   // the link: output of level l - 1 -> x of level l
+        from_m(B[c], t4);
+        for (int w = 0; w < 8; w++) io[8 * c + w] = (uint32_t)(t4[w >> 1] >> (32 * (w & 1)));
+      }
+      nv = to_m(t4);
+    } else if (is_b) { u64 t4[4]; u32x8_to_u64x4(io + 96 + 8 * c, t4); nv = to_m(t4); }
+    __syncthreads();                                                     // the previous level's B has been read
+    if (is_a) A[c] = nv; else if (is_b) B[c] = nv;
+    __syncthreads();
+    for (int t = 0;; t++) {
+      if (is_a || is_b) from_m((is_a ? A : B)[c], (is_a ? ca : cb) + ((k * (size_t)(steps + 1) + t) * 12 + c) * 4);
+      if (t == steps) { if (is_b) from_m(B[c], outs + (k * 12 + c) * 4); break; }
+      const bool bit = (io[192 + (t >> 5)] >> (t & 31)) & 1;            // uniform over the workgroup
+      if (tid < 144) PA[tid] = mmul(A[tid / 12], A[tid % 12]);
+      else if (tid < 288 && bit) PB[tid - 144] = mmul(A[(tid - 144) / 12], B[(tid - 144) % 12]);
+      __syncthreads();
+      Fq fv;
+      if (is_a) fv = fq12_fold_coeff(PA, c);
+      else if (is_b && bit) fv = fq12_fold_coeff(PB, c);
+      __syncthreads();                                                   // every product has been read, A / B may change
+      if (is_a) A[c] = fv; else if (is_b && bit) B[c] = fv;
+      __syncthreads();
+    }
+  }
+}
+// instances [M, K) <- instance M - 1: blockIdx.x = pad index; cw1 = u64 words of one chain of one instance ((steps + 1) * 48)
+__global__ void __launch_bounds__(256) fq12_tower_pad_kernel(uint32_t* ios, size_t iow, size_t M, size_t K, size_t cw1, u64* ca, u64* cb, u64* outs) {
+  const size_t g = M + blockIdx.x, src = M - 1;
+  if (g >= K) return;
+  for (size_t i = threadIdx.x; i < iow; i += blockDim.x) ios[iow * g + i] = ios[iow * src + i];
+  for (size_t i = threadIdx.x; i < cw1; i += blockDim.x) { ca[cw1 * g + i] = ca[cw1 * src + i]; cb[cw1 * g + i] = cb[cw1 * src + i]; }
+  for (size_t i = threadIdx.x; i < 48; i += blockDim.x) outs[48 * g + i] = outs[48 * src + i];
+}
+
 // ---- parity hook (sbn_bn254_fq_batch, tracegen_device.hip): the field helpers above on standard-form operands, 4 words per element --------------
 enum { FQB_MUL = 0, FQB_ADD = 1, FQB_SUB = 2, FQB_INV = 3, FQB_BATCH_INV = 4, FQB_FQ2_INV = 5 };
 // Item i of op: element i, or group i of TG_INV_BATCH elements for FQB_BATCH_INV.  FQB_INV is finv_fermat on the device and inv_std on

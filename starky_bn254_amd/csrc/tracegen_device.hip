@@ -144,6 +144,10 @@ static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, siz
 // scalar multiplications").  G1 / G2 only.
 struct ScalarMulIn { const uint32_t* points; const uint32_t* scalars; size_t scalar_count; const uint32_t* offset; uint32_t* products_out; uint8_t* infinity_out; uint32_t* ios_out; };
 
+// sbn_prover_generate_trace_powers: `count` towers of `depth` levels on an Fq12 table whose chains run on the device; level 0 takes
+// its x from `bases`, level l from the output of level l - 1, derived on the device (kernels_tracegen.cuh, "power towers").
+struct PowerIn { const uint32_t* bases; const uint32_t* exps; size_t exp_count, count, depth; uint32_t* powers_out; uint32_t* ios_out; };
+
 // One sbn_prover_generate_trace call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
 struct TraceJob {
   sbn_prover* const P;
@@ -361,7 +365,7 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
 
 // Fq12ExpStark: the square-and-multiply chains (no inversion anywhere) on host threads in standard form, then one lane
 // per row for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
-static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr) {
+static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const PowerIn* pw = nullptr) {
   const bool u64e = P->air.kind == SBN_AIR_FQ12_EXP_U64;        // 128-row instances, one-element exponent
   const size_t IOW = u64e ? 194 : 200;
   const int steps = u64e ? 64 : 256, log_rpb = u64e ? 7 : 9;
@@ -371,6 +375,20 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     uint32_t one[96] = {1};
     prelim = preliminary_list(*ch, K, 96, IOW - 192, one);
     derived.resize(IOW * K);
+    ios = prelim.data();
+  }
+  const size_t M = pw ? pw->count * pw->depth : K;   // towers: the real instances; rows [M, K) are pads
+  if (pw) {   // x of level 0, zeros above it (the device writes them), one, the tower's exponent; a pad row repeats row M - 1
+    if (int rc = power_check_inputs(P->air.kind, pw->bases, pw->exps, pw->exp_count, pw->count)) return rc;
+    const size_t ew = IOW - 192;
+    prelim.assign(IOW * K, 0u);
+    for (size_t g = 0; g < K; g++) {
+      const size_t r = g < M ? g : M - 1, k = r / pw->depth;
+      uint32_t* io = prelim.data() + IOW * g;
+      if (r % pw->depth == 0) memcpy(io, pw->bases + 96 * k, 96 * sizeof(uint32_t));
+      io[96] = 1;
+      memcpy(io + 192, pw->exps + (pw->exp_count == 1 ? 0 : ew * k), ew * sizeof(uint32_t));
+    }
     ios = prelim.data();
   }
   if (int rc = check_below_p(ios, IOW, 24, K, "coefficient")) return rc;
@@ -389,6 +407,7 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   int* d_err = (int*)J.take(1);
   uint32_t* d_start = ch ? (uint32_t*)J.take(48) : nullptr;
   if (int rc = J.fits()) return rc;
+  if (pw && (u64*)d_ios != d_outs + K * 48) return fail(SBN_ERR_UNSUPPORTED, "internal: the instance list does not follow the outputs");   // (one download, below)
   if (int rc = J.begin(ios, d_ios, d_err)) return rc;
   if (ch) {
     HIPC(hipMemcpyAsync(d_start, ch->start, 96 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -398,8 +417,12 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   else J.launch_common_columns(tg::flags_kernel, d_ios, inv, 255);
   // the square-and-multiply chains: one workgroup per instance on the device (kernels_tracegen.cuh fq12_chain_kernel);
   // SBN_FQ12_HOST_CHAIN=1: the library's host threads + a pinned upload, as in round 2 (A/B)
-  const bool host_chain = P->set.fq12_host_chain;
-  if (host_chain) {
+  const bool host_chain = P->set.fq12_host_chain && !pw;   // (towers under the host-chain switch never come here)
+  if (pw) {   // d_ios holds the level-0 x, the offsets and the exponents: one workgroup per tower links and walks its levels
+    hipLaunchKernelGGL(tg::fq12_tower_kernel, dim3((unsigned)pw->count), dim3(320), 0, st, d_ios, IOW, steps, pw->depth, ca, cb, d_outs);
+    J.mark();
+    if (M < K) hipLaunchKernelGGL(tg::fq12_tower_pad_kernel, dim3((unsigned)(K - M)), dim3(256), 0, st, d_ios, IOW, M, K, (size_t)(steps + 1) * 48, ca, cb, d_outs);
+  } else if (host_chain) {
     if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
     tracegen_host_chains_fq12(ios, IOW, steps, K, P->h_chain, P->h_chain + cw);
     HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
@@ -422,14 +445,20 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   int err = 0;
   HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
   std::vector<u64> chain_out;                 // B[steps] of every instance (the outputs among the public inputs) when the chains ran on the device
-  if (!host_chain) {
+  if (pw) {   // d_ios follows d_outs in the scratch (take() above): the outputs = the powers and the derived list in ONE download
+    const size_t ios_u64 = (IOW * K + 1) / 2;
+    chain_out.resize(K * 48 + ios_u64);
+    HIPC(hipMemcpyAsync(chain_out.data(), d_outs, chain_out.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    ios = (const uint32_t*)(chain_out.data() + K * 48);   // where the derived list lands
+  } else if (!host_chain) {
     chain_out.resize(K * 48);
     HIPC(hipMemcpyAsync(chain_out.data(), d_outs, K * 48 * sizeof(u64), hipMemcpyDeviceToHost, st));
   }
   if (ch) HIPC(hipMemcpyAsync(derived.data(), d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
   static const char* const names_chained[] = {"flags+pulses", "chains", "chain_offsets", "row_witness", "range_check"};
-  if (int rc = J.end(ch ? names_chained : names)) return rc;
+  static const char* const names_tower[] = {"flags+pulses", "tower_links", "tower_pads", "row_witness", "range_check"};
+  if (int rc = J.end(pw ? names_tower : ch ? names_chained : names)) return rc;
   // public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117)
   const int rc = J.finish(err, pi_out, [&](size_t k, u64* p) {
     for (int c = 0; c < 24; c++)
@@ -441,6 +470,11 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
   });
   if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
+  if (rc == SBN_OK && pw) {
+    if (pw->ios_out) memcpy(pw->ios_out, ios, IOW * K * sizeof(uint32_t));
+    if (pw->powers_out)   // [count][depth][96] u32 = the outputs of the M real instances, standard form
+      for (size_t i = 0; i < 48 * M; i++) { pw->powers_out[2 * i] = (uint32_t)chain_out[i]; pw->powers_out[2 * i + 1] = (uint32_t)(chain_out[i] >> 32); }
+  }
   return rc;
 }
 
@@ -533,6 +567,33 @@ extern "C" int sbn_prover_generate_trace_scalar_muls(sbn_prover* P, const uint32
   }
   const ScalarMulIn sm{points, scalars, scalar_count, offset, products_out, infinity_out, ios_out};
   return E == 1 ? generate_trace_device<1>(P, nullptr, num_io, pi_out, nullptr, &sm) : generate_trace_device<2>(P, nullptr, num_io, pi_out, nullptr, &sm);
+}
+
+// sbn_prover_generate_trace on the one-unit list sbn_power_instances derives from (bases, exps, depth): on an Fq12 table whose
+// chains run on the device the towers are linked and walked there (one workgroup per tower) and the pads filled there; FqExpStark
+// (host-pool chains) and an Fq12 prover under SBN_FQ12_HOST_CHAIN walk the towers on the host pool and take the explicit path.
+extern "C" int sbn_prover_generate_trace_powers(sbn_prover* P, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth,
+                                                uint64_t* pi_out, uint32_t* powers_out, uint32_t* ios_out) {
+  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  const int kind = P->air.kind;
+  if (!power_elem_words(kind)) return fail(SBN_ERR_UNSUPPORTED, "field powers cover the field tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64");
+  if (!bases || !exps || count == 0 || depth == 0) return fail(SBN_ERR_BAD_ARG, "null argument, no tower or depth = 0");
+  if (exp_count != 1 && exp_count != count) return fail(SBN_ERR_BAD_ARG, "exp_count must be 1 (one shared exponent) or count = %zu, got %zu", count, exp_count);
+  const size_t num_io = P->air.num_io;
+  if (count > num_io || depth > num_io / count) return fail(SBN_ERR_BAD_ARG, "%zu towers of depth %zu do not fit one unit of %zu instances", count, depth, num_io);
+  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
+  const bool fq12 = kind != SBN_AIR_FQ_EXP;
+  if (!fq12 && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  if (!fq12 || P->set.fq12_host_chain) {
+    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
+    if (int rc = sbn_power_instances(kind, bases, exps, exp_count, count, depth, num_io, ios.data(), powers_out)) return rc;
+    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
+    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
+    return rc;
+  }
+  const PowerIn pw{bases, exps, exp_count, count, depth, powers_out, ios_out};
+  return generate_trace_device_fq12(P, nullptr, num_io, pi_out, nullptr, &pw);
 }
 
 extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
