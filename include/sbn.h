@@ -463,6 +463,67 @@ int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* b, const uint32_t* 
 int sbn_mul_by_cofactor_check(size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, const uint32_t* points,
                               uint32_t* cleared_out, uint8_t* infinity_out);
 
+/* Batches of short MSMs -------------------------------------------------------------------------------- */
+/* SEGMENTED chained lists packed into shared units.  The reference's g1_exp_circuit (src/curves/g1/circuit.rs:262-304) takes any list
+ * of inputs and the caller wires the offsets: some inputs continue a chain, others start a new one.  The everyday workload looks
+ * like that -- one public-key aggregation per signature, one product of a few x_k^e_k per pairing check: many short sums, not one
+ * long MSM.  One sbn_batch_prover_prove_msm call per sum pads every sum to a whole unit: a thousand 10-term G1 sums are 1,000 unit
+ * proofs (the sum of ceil(len_s / num_io)) where their 10,000 instances fit 79 units (ceil of the sum of len_s over num_io).  The
+ * two shapes above are the ends of this one: sbn_msm_instances is one segment, sbn_scalar_mul_instances is segments of length 1
+ * with a shared start.  One definition for every entry point below; kind is one of the five Exp tables and T (words per term: 24 /
+ * 40 / 16 / 104 / 98), W (words per offset value: 16 / 32 / 8 / 96 / 96) and the words per `ios` row are as in sbn_chain_instances:
+ *   terms    [M][T] u32: the instances of all segments, one after the other;
+ *   lengths  [segments] u64: every length >= 1, their sum is M; head(s) = the global index of the first instance of segment s;
+ *   starts   [start_count][W] u32, start_count = segments (one start per segment) or 1 for ONE start shared by all; NULL = the
+ *            generator (sbn_curve_generator) on a curve table and one on a field table (start_count is then not read).
+ * With units = sbn_msm_num_units(M, num_io) the explicit list has units * num_io rows.  Row g < M: offset[g] = start_s when g =
+ * head(s), otherwise the output of instance g - 1 (offset + e x on the curves, offset * x^e in the fields, 0^0 = 1); row g >= M is a
+ * copy of row M - 1 in x, offset and exponent (the reference's resize rule, as sbn_msm_instances).  Segments may straddle unit
+ * boundaries.  Per segment: finals_out [segments][W] = the output of its last instance; on the two curve tables also sums_out
+ * [segments][W] and infinity_out [segments] = final_s + (-start_s) by the COMPLETE addition, as sbn_scalar_mul_instances (a sum at
+ * infinity is not an error: flag 1, words zero).  On a field table sums_out / infinity_out must be NULL: with the default start the
+ * final is the product.  Every output pointer is optional.
+ * Refused, in this order, each naming the GLOBAL instance and its segment: SBN_ERR_UNSUPPORTED for a kind that is no Exp table;
+ * SBN_ERR_BAD_ARG for a null argument, segments = 0, a zero length, start_count outside {1, segments}, num_io = 0, sums_out on a field
+ * table, a coordinate or coefficient >= p, a start or an x off the table's curve; SBN_ERR_NON_CANONICAL for a FQ12_EXP_U64 exponent
+ * that is no canonical field element; SBN_ERR_WITNESS when an offset or a final inside a segment is the point at infinity; then
+ * SBN_ERR_WITNESS when the table's own walk of an instance is degenerate.  The same partial sum in another segment with another
+ * start is fine. */
+/* The explicit list, the finals and the sums on the host pool, no device: the terms in parallel, one pass of complete additions
+ * (products) per segment, one batched inversion for the affine forms, then the table's-walk check of the list.  num_io is not
+ * checked against any table (this only shapes a list). */
+int sbn_msm_batch_instances(int32_t kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count,
+                            size_t num_io, uint32_t* ios_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out);
+/* One unit on a prover of the table: M <= the table's num_io (SBN_ERR_BAD_ARG otherwise), the rest of the unit is padded.  On success
+ * the loaded trace, the public inputs and ios_out ([num_io][words per instance]) are, word for word, those of
+ * sbn_prover_generate_trace on the list of sbn_msm_batch_instances; a failing call leaves NO trace loaded.  Where the table's chains
+ * run on the device (G1_EXP / G2_EXP under SBN_TRACEGEN_DEVICE_CHAIN = 1 or 2; FQ12_EXP / FQ12_EXP_U64 unless SBN_FQ12_HOST_CHAIN)
+ * the offsets are built there: on the curves a segmented prefix scan over the terms (a lane adds its partner only inside its own
+ * segment), in Fq12 one workgroup per segment walking its own running product; the pads take the offset of instance M - 1; the
+ * derived list, the finals and the sums come back with the instance outputs, and an instance the device refuses is named by the host
+ * derivation on the error path.  FQ_EXP and the host-chain placements derive on the host pool and take the explicit path.  The
+ * words are the same in every placement. */
+int sbn_prover_generate_trace_msm_batch(sbn_prover* p, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts,
+                                        size_t start_count, uint64_t* pi_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out,
+                                        uint32_t* ios_out);
+/* Any M, as units of the batch prover's table: proofs_out[units] in unit order, word for word what sbn_batch_prover_prove_ios
+ * gives on the list of sbn_msm_batch_instances, which is derived once on the host pool (every unit's first offset is known before
+ * the first unit is taken, so no context waits for another).  Failure rule as sbn_batch_prover_prove_msm: every proof freed,
+ * proofs_out all null, the batch prover usable. */
+int sbn_batch_prover_prove_msm_batch(sbn_batch_prover* b, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts,
+                                     size_t start_count, sbn_proof** proofs_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out,
+                                     uint32_t* ios_out);
+/* The twin of sbn_msm_check_links, on the public inputs of the unit proofs (host, no device; it verifies NO proof).  Checked, in
+ * instance order: units == sbn_msm_num_units(M, num_io); the offset of every head equals the start of its segment; offset[g + 1] ==
+ * output[g] inside a segment, across unit boundaries; every pad instance equals instance M - 1 in x, offset, exponent and output;
+ * with terms (optional), x and exponent of every real instance are the caller's; every output limb is in range.  On the curves
+ * every output must be a point of the curve (as sbn_scalar_mul_check) and the sums and flags are recomputed on the host.  SBN_OK
+ * and finals_out / sums_out / infinity_out (optional, as above), or SBN_ERR_VERIFY_FAILED with sbn_last_error naming the first global
+ * instance, its segment and the field that breaks. */
+int sbn_msm_batch_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units, const uint64_t* lengths, size_t segments,
+                        const uint32_t* terms /*optional*/, const uint32_t* starts, size_t start_count, uint32_t* finals_out, uint32_t* sums_out,
+                        uint8_t* infinity_out);
+
 /* Field powers --------------------------------------------------------------------------------------- */
 /* Powers and POWER TOWERS on the three field Exp tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64: the caller wants x^e itself.  A field
  * table needs no offset trick (its offset is multiplicative: every instance here carries offset = 1, word 0 = 1 and the rest 0), but

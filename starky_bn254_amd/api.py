@@ -41,6 +41,7 @@ EXPORTS = [
     "sbn_msm_num_units", "sbn_msm_instances", "sbn_batch_prover_prove_msm", "sbn_msm_check_links",
     "sbn_curve_generator", "sbn_g2_cofactor", "sbn_scalar_mul_instances", "sbn_prover_generate_trace_scalar_muls",
     "sbn_batch_prover_prove_scalar_muls", "sbn_scalar_mul_check", "sbn_batch_prover_prove_mul_by_cofactor", "sbn_mul_by_cofactor_check",
+    "sbn_msm_batch_instances", "sbn_prover_generate_trace_msm_batch", "sbn_batch_prover_prove_msm_batch", "sbn_msm_batch_check",
     "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
@@ -173,6 +174,10 @@ def lib():
         L.sbn_scalar_mul_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, vp, vp, sz, vp, vp, vp]
         L.sbn_batch_prover_prove_mul_by_cofactor.argtypes = [vp, vp, sz, C.POINTER(vp), vp, vp, vp]
         L.sbn_mul_by_cofactor_check.argtypes = [sz, C.POINTER(vp), sz, sz, vp, vp, vp]
+        L.sbn_msm_batch_instances.argtypes = [C.c_int32, vp, vp, sz, vp, sz, sz, vp, vp, vp, vp]
+        L.sbn_prover_generate_trace_msm_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.sbn_batch_prover_prove_msm_batch.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(vp), vp, vp, vp, vp]
+        L.sbn_msm_batch_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, vp, sz, vp, vp, sz, vp, vp, vp]
         L.sbn_bn_x.argtypes = [vp]
         L.sbn_power_instances.argtypes = [C.c_int32, vp, vp, sz, sz, sz, sz, vp, vp]
         L.sbn_prover_generate_trace_powers.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
@@ -651,6 +656,73 @@ def mul_by_cofactor_check(stark, public_inputs_per_unit, points):
     return cleared, infinity
 
 
+# ---- batches of short MSMs: segmented chained lists (include/sbn.h, "Batches of short MSMs") -----------------------------------
+def _msm_batch_args(stark, terms, lengths, starts):
+    """terms (M, T) uint32 as chain_instances takes them, lengths (segments,) with every length >= 1 and sum M, starts (segments, W)
+    = one start per segment, (W,) / (1, W) = one start shared by all, or None = the generator on a curve table, one on a field
+    table.  Returns (terms, lengths, starts, xw, ew, curve)."""
+    xw, ew = _chain_words(stark)
+    terms = np.ascontiguousarray(terms, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+    if terms.ndim != 2 or terms.shape[0] < 1 or terms.shape[1] != xw + ew:
+        raise SbnError(-1, f"terms must be [M][{xw + ew}] u32")
+    if lengths.shape[0] and int(lengths.sum()) != terms.shape[0]:
+        raise SbnError(-1, f"the lengths add up to {int(lengths.sum())} instances, terms holds {terms.shape[0]}")
+    if starts is not None:
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        if starts.ndim == 1:
+            starts = starts.reshape(1, -1)
+        if starts.ndim != 2 or starts.shape[1] != xw:
+            raise SbnError(-1, f"starts must be [segments][{xw}] or [{xw}] u32")
+    return terms, lengths, starts, xw, ew, stark.kind in (AIR_G1_EXP, AIR_G2_EXP)
+
+
+def _msm_batch_outputs(segments, xw, curve):
+    finals = np.zeros((segments, xw), dtype=np.uint32)
+    sums = np.zeros((segments, xw), dtype=np.uint32) if curve else None
+    infinity = np.zeros(segments, dtype=np.uint8) if curve else None
+    return finals, sums, infinity
+
+
+def msm_batch_instances(stark, terms, lengths, starts=None):
+    """Many short chained lists packed into shared units (sbn_msm_batch_instances): segment s holds lengths[s] consecutive rows of
+    terms; its first instance starts from its start, every other one from the output before it; the last unit is padded with copies
+    of the last instance.  Returns (ios_units, finals, sums, infinity): (units, num_io, words per instance) uint32 as
+    BatchProver.prove_ios takes it, the last output of every segment, and on the curve tables final - start with a flag per sum that
+    is the point at infinity (None, None on field tables).  No device needed."""
+    terms, lengths, starts, xw, ew, curve = _msm_batch_args(stark, terms, lengths, starts)
+    if stark.num_io < 1:
+        raise SbnError(-1, "the table has no instances")
+    units = msm_num_units(terms.shape[0], stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * xw + ew), dtype=np.uint32)
+    finals, sums, infinity = _msm_batch_outputs(len(lengths), xw, curve)
+    _check(lib().sbn_msm_batch_instances(stark.kind, _ptr(terms), _ptr(lengths), len(lengths), _ptr(starts), starts.shape[0] if starts is not None else 1,
+                                         stark.num_io, _ptr(ios), _ptr(finals), _ptr(sums), _ptr(infinity)))
+    return ios, finals, sums, infinity
+
+
+def msm_batch_check(stark, public_inputs_per_unit, lengths, starts=None, terms=None):
+    """The check of a batch of short MSMs (sbn_msm_batch_check) on the public inputs of its unit proofs: every head starts from the
+    start of its segment, every other offset is the output before it (across unit boundaries), the pads repeat the last instance
+    and (with `terms`) x and exponents are the caller's.  Returns (finals, sums, infinity) read and recomputed from the outputs;
+    raises SbnError(-6) naming the first instance, its segment and the field that breaks.  Verifies NO proof: verify_msms does
+    both."""
+    xw, ew = _chain_words(stark)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+    if terms is None:   # only the starts need shaping
+        _, _, starts, _, _, curve = _msm_batch_args(stark, np.zeros((1, xw + ew), dtype=np.uint32), lengths[:0], starts)
+    else:
+        terms, _, starts, _, _, curve = _msm_batch_args(stark, terms, lengths, starts)
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
+    if any(p.shape[0] != stark.num_public_inputs for p in pis):
+        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
+    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    finals, sums, infinity = _msm_batch_outputs(len(lengths), xw, curve)
+    _check(lib().sbn_msm_batch_check(stark.kind, stark.num_io, ptrs, len(pis), _ptr(lengths), len(lengths), _ptr(terms), _ptr(starts),
+                                     starts.shape[0] if starts is not None else 1, _ptr(finals), _ptr(sums), _ptr(infinity)))
+    return finals, sums, infinity
+
+
 # ---- field powers and power towers (include/sbn.h, "Field powers") -------------------------------------------------------------
 BN_P = 21888242871839275222246405745257275088696311157297823662689037894645226208583   # the base field of BN254
 BN_X = 4965661367192848881                # the BN parameter x = 0x44E992B44A6909F1 (sbn_bn_x): p, r and the final exponentiation are polynomials in it
@@ -1106,6 +1178,19 @@ class Prover:
                                                            _ptr(pi), _ptr(products), _ptr(infinity), _ptr(ios)))
         return pi, products, infinity, ios
 
+    def generate_trace_msms(self, terms, lengths, starts=None):
+        """generate_trace on the one-unit list msm_batch_instances(stark, terms, lengths, starts) gives (M <= num_io, the rest
+        padded), the offsets, finals and sums derived on the device where the table's chains run there; returns (public inputs,
+        finals, sums, infinity, ios)."""
+        terms, lengths, starts, xw, ew, curve = _msm_batch_args(self.stark, terms, lengths, starts)
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        ios = np.zeros((self.stark.num_io, 2 * xw + ew), dtype=np.uint32)
+        finals, sums, infinity = _msm_batch_outputs(len(lengths), xw, curve)
+        _check(lib().sbn_prover_generate_trace_msm_batch(self._h, _ptr(terms), _ptr(lengths), len(lengths), _ptr(starts),
+                                                         starts.shape[0] if starts is not None else 1, _ptr(pi), _ptr(finals), _ptr(sums), _ptr(infinity),
+                                                         _ptr(ios)))
+        return pi, finals, sums, infinity, ios
+
     def generate_trace_powers(self, bases, exps, depth=1):
         """generate_trace on the one-unit list power_instances(stark, bases, exps, depth) gives (count * depth <= num_io, the
         rest padded), the towers linked and walked on the device where the table's chains run there; returns (public inputs,
@@ -1256,6 +1341,18 @@ class BatchProver:
         _check(lib().sbn_batch_prover_prove_mul_by_cofactor(self._h, _ptr(points), count, out, _ptr(cleared), _ptr(infinity), _ptr(ios)))
         return [_take_proof(C.c_void_p(h)) for h in out[:units]], cleared, infinity, ios
 
+    def prove_msms(self, terms, lengths, starts=None):
+        """A batch of short MSMs of any total length (arguments as msm_batch_instances) proved as units of the table, segments
+        sharing units and the last unit padded (sbn_batch_prover_prove_msm_batch).  Returns (proofs, finals, sums, infinity, ios)."""
+        terms, lengths, starts, xw, ew, curve = _msm_batch_args(self.stark, terms, lengths, starts)
+        units = msm_num_units(terms.shape[0], self.stark.num_io)
+        ios = np.zeros((units, self.stark.num_io, 2 * xw + ew), dtype=np.uint32)
+        finals, sums, infinity = _msm_batch_outputs(len(lengths), xw, curve)
+        out = (C.c_void_p * max(units, 1))()
+        _check(lib().sbn_batch_prover_prove_msm_batch(self._h, _ptr(terms), _ptr(lengths), len(lengths), _ptr(starts),
+                                                      starts.shape[0] if starts is not None else 1, out, _ptr(finals), _ptr(sums), _ptr(infinity), _ptr(ios)))
+        return [_take_proof(C.c_void_p(h)) for h in out[:units]], finals, sums, infinity, ios
+
     def prove_powers(self, bases, exps, depth=1):
         """Powers / power towers of any count (arguments as power_instances) proved as units of the table, the last one padded
         (sbn_batch_prover_prove_powers).  Returns (proofs, powers, ios)."""
@@ -1378,6 +1475,15 @@ def verify_mul_by_cofactor(stark, config, proofs, points, verifier=None):
     proofs = list(proofs)
     _verify_units(stark, config, proofs, verifier)
     return mul_by_cofactor_check(stark, [p.public_inputs() for p in proofs], points)
+
+
+def verify_msms(stark, config, proofs, lengths, starts=None, terms=None, verifier=None):
+    """Verifies the unit proofs of BatchProver.prove_msms (host verifier, or a Verifier of the table in batches) and then runs
+    msm_batch_check on their public inputs.  Returns (finals, sums, infinity); raises SbnError when a unit is rejected (naming the
+    unit) or the check fails (naming the instance, its segment and the field)."""
+    proofs = list(proofs)
+    _verify_units(stark, config, proofs, verifier)
+    return msm_batch_check(stark, [p.public_inputs() for p in proofs], lengths, starts, terms)
 
 
 def verify_powers(stark, config, proofs, bases, exps, depth=1, verifier=None):

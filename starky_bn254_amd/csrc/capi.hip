@@ -242,6 +242,24 @@ int sbn_batch_prover_prove_powers(sbn_batch_prover* B, const uint32_t* bases, co
   return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
 }
 
+// Batches of short MSMs of any total length (include/sbn.h, "Batches of short MSMs"; csrc/msm_batch.hip): as above, the segmented
+// list, padded and unit-cut, is derived once on the host pool -- a segment that straddles two units needs no context to wait for
+// another -- and the units go through the explicit-list path.
+int sbn_batch_prover_prove_msm_batch(sbn_batch_prover* B, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count,
+                                     sbn_proof** proofs_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  size_t M = 0;   // (a list whose lengths are refused has no unit count: M stays 0 and nothing of proofs_out is touched)
+  const int bad = msm_batch_check_args(B->kind, terms, lengths, segments, &starts, &start_count, B->num_io, sums_out, infinity_out, &M);
+  const size_t IOW = exp_io_words(B->kind), units = sbn_msm_num_units(M, B->num_io);
+  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
+  if (bad) return bad;
+  std::vector<uint32_t> own;
+  uint32_t* ios = ios_out;
+  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
+  if (int rc = msm_batch_derive(B->kind, terms, lengths, segments, starts, start_count, M, units * B->num_io, ios, finals_out, sums_out, infinity_out)) return rc;
+  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+}
+
 int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* B, const uint32_t* points, size_t count, sbn_proof** proofs_out, uint32_t* cleared_out,
                                            uint8_t* infinity_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");

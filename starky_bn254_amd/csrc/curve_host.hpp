@@ -1,9 +1,11 @@
 // Host helpers over bn254w.cuh shared by the units that derive instance lists on the host pool (chain_instances.hip,
-// scalar_mul.hip): u32-limb loads and stores, the curve constants, the on-curve test and the norm-based inversion of a Z.
+// scalar_mul.hip, powers.hip, msm_batch.hip): u32-limb loads and stores, the curve constants, the on-curve test, the norm-based
+// inversion of a Z, and the batched affine form of a list of Jacobian points that may hold the point at infinity.
 #pragma once
 #include "host_common.hpp"
 #include "bn254w.cuh"
 #include <atomic>
+#include <cstring>
 
 namespace sbn {
 namespace curve_host {
@@ -69,6 +71,32 @@ template <int E> Jac<E> scalar_mul_jac(const Jac<E>& x, const uint32_t* e) {
     if ((e[t >> 5] >> (t & 31)) & 1) acc = jac_add_complete<E>(acc, x);
   }
   return acc;
+}
+
+template <int E> Jac<E> neg_point(const Jac<E>& p) { Jac<E> r = p; r.Y = csub(csub(p.Y, p.Y), p.Y); return r; }
+
+// K Jacobian points -> affine u32 words ([K][16E]) and flags ([K], 1 = the point at infinity, its words zero): one inversion for
+// every non-zero Z (through the norms on the twist); either output may be null
+template <int E> void affine_or_infinity(const std::vector<Jac<E>>& pts, uint32_t* words, uint8_t* inf) {
+  const size_t K = pts.size();
+  std::vector<Fq> nrm(K), pre(K);
+  Fq acc = fq_one();
+  for (size_t k = 0; k < K; k++) {
+    const bool z = czero<E>(pts[k].Z);
+    if (inf) inf[k] = z ? 1 : 0;
+    nrm[k] = z ? fq_one() : norm_of(pts[k].Z);
+    pre[k] = acc; acc = mmul(acc, nrm[k]);
+  }
+  if (!words) return;
+  Fq inv = fq_inv_m(acc);
+  for (size_t k = K; k-- > 0;) { const Fq ni = mmul(inv, pre[k]); inv = mmul(inv, nrm[k]); nrm[k] = ni; }
+  for (size_t k = 0; k < K; k++) {
+    uint32_t* out = words + 16 * E * k;
+    if (czero<E>(pts[k].Z)) { memset(out, 0, 16 * E * sizeof(uint32_t)); continue; }
+    const Co<E> zi = inv_from_norm(pts[k].Z, nrm[k]), zi2 = cmul(zi, zi);
+    const Co<E> x = cmul(pts[k].X, zi2), y = cmul(pts[k].Y, cmul(zi2, zi));
+    for (int q = 0; q < E; q++) { st_u32(x.c[q], out + 8 * q); st_u32(y.c[q], out + 8 * (E + q)); }
+  }
 }
 }  // namespace curve_host
 }  // namespace sbn

@@ -141,6 +141,15 @@ void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* of
 // naming the tower
 size_t power_elem_words(int kind);
 int power_check_inputs(int kind, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count);
+// msm_batch.hip (segmented chained lists on the five Exp tables): the argument refusals every entry point shares, in the header's
+// order (a null `*starts` becomes the generator / one with *start_count = 1; *M_out = the sum of the lengths); the refusals of the
+// values (>= p, off the curve, a non-canonical u64 exponent), naming the global instance and its segment; and the derivation behind
+// both: `total` >= M rows of ios (rows past M repeat row M - 1), the finals, and on the curves the sums and their infinity flags
+int msm_batch_check_args(int kind, const void* terms, const uint64_t* lengths, size_t segments, const uint32_t** starts, size_t* start_count, size_t num_io,
+                         const void* sums_out, const void* infinity_out, size_t* M_out);
+int msm_batch_check_inputs(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M);
+int msm_batch_derive(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M,
+                     size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out);
 // prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)
 size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)

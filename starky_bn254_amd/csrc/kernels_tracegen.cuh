@@ -1059,6 +1059,9 @@ __global__ void __launch_bounds__(CS_LANES) chain_scan_kernel(uint32_t* ios, siz
 //                               then one batched inversion of TG_INV_BATCH norms per lane for the affine form, a zero Z skipped and
 //                               flagged as in the tail of chain_scan_kernel.  The Jacobian sums wait in `jp` ([K][12E] u64) between
 //                               the two passes of a lane, so a lane holds one point at a time.
+// out_at / off_at (null in the call above: item i reads instance i): item i reads the output of instance out_at[i] and the offset
+// words of instance off_at[i] -- the un-offset of a SEGMENTED list, K = its segments, final_s + (-start_s) from the segment's tail
+// and head ("segmented chained lists" below).
 // An instance the table cannot walk leaves garbage in `outs`; the arithmetic here is total (no index depends on a value), the call
 // is refused through the error word of the witness kernels and the host drops what this kernel wrote.
 template <int E>
@@ -1073,7 +1076,8 @@ __global__ void scalar_mul_list_kernel(const uint32_t* __restrict__ cin, size_t 
 }
 template <int E>
 __global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ outs, u64* __restrict__ jp,
-                                           uint32_t* __restrict__ products, unsigned char* __restrict__ infinity) {
+                                           uint32_t* __restrict__ products, unsigned char* __restrict__ infinity,
+                                           const uint32_t* __restrict__ out_at = nullptr, const uint32_t* __restrict__ off_at = nullptr) {
   const size_t W = 16 * E, IOW = 2 * W + 8;
   const size_t L = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
@@ -1084,12 +1088,13 @@ __global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, siz
     nrm[j] = fq_one();
     if (i >= K) continue;
     Jac<E> o, m; u64 t4[4];
+    const size_t io = out_at ? out_at[i] : i, im = off_at ? off_at[i] : i;   // (segmented lists: the tail and the head of segment i)
     for (int c = 0; c < 2; c++)
       for (int q = 0; q < E; q++) {
-        const u64* src = outs + W * i + 8 * (c * E + q);
+        const u64* src = outs + W * io + 8 * (c * E + q);
         for (int h = 0; h < 4; h++) t4[h] = (src[2 * h] & 0xffffffffULL) | (src[2 * h + 1] << 32);
         (c ? o.Y : o.X).c[q] = to_m(t4);
-        u32x8_to_u64x4(ios + IOW * i + W + 8 * (c * E + q), t4);
+        u32x8_to_u64x4(ios + IOW * im + W + 8 * (c * E + q), t4);
         (c ? m.Y : m.X).c[q] = to_m(t4);
       }
     o.Z = cone<E>(); m.Z = o.Z;
@@ -1151,6 +1156,103 @@ __global__ void __launch_bounds__(192) fq12_rebase_kernel(const uint32_t* __rest
     const Fq v = fq12_fold_coeff(PB, tid);
     from_m(v, slot);
     if (entry % (size_t)(steps + 1) == (size_t)steps) from_m(v, outs + (k * 12 + tid) * 4);
+  }
+}
+
+// ---- segmented chained lists (sbn_prover_generate_trace_msm_batch): many short chains packed into one unit --------------------------
+// The list of a unit is cut into segments; instance g is a HEAD (its offset is the start of its segment, which the preliminary list
+// carries in its offset words) or continues the chain (offset[g] = output[g - 1]).  Rows [M, K) are pads: copies of row M - 1 in x,
+// offset and exponent -- they do not continue the chain.  chain_prefix_kernel, chain_rebase_kernel and fq12_rebase_kernel run
+// unchanged on all K rows (the preliminary rows of the pads are row M - 1 already, so their chains and outputs are its too).
+//   chain_seg_scan_kernel  the segmented form of chain_scan_kernel, ONE workgroup, lane k = instance k: it starts from the start of
+//                          its segment when k is a head (head[k] == k), else from the term e_{k-1} x_{k-1}; the Hillis-Steele level of
+//                          stride d adds the partner k - d only while k - d >= head[k], so after that level lane k holds the sum over
+//                          [max(head, k - 2d + 1), k] and a segment never reads across its head.  Same ping-pong in global scratch
+//                          (the workgroup barrier orders its stores and loads), same batched-inversion tail and TG_ERR_INFINITY;
+//                          the tail writes the offset of row i from the sum of lane min(i, M - 1): the pads.
+//   fq12_seg_scan_kernel   fq12_offset_scan_kernel with ONE WORKGROUP PER SEGMENT, the same lane roles and LDS layout: each walks
+//                          the len - 1 dependent products of its own instances from its own start; the workgroup of the last segment
+//                          also writes its last offset into the pad rows.
+// Nothing either kernel stores to global memory is read by ANOTHER workgroup inside it: the scan is one workgroup, and an Fq12
+// segment writes the offset words of its own rows (and of the pads), which the kernels behind the kernel boundary read.
+template <int E>
+__global__ void __launch_bounds__(CS_LANES) chain_seg_scan_kernel(uint32_t* ios, size_t K, size_t M, const uint32_t* __restrict__ head, const u64* __restrict__ terms,
+                                                                  u64* s0, u64* s1, int* __restrict__ err) {
+  const size_t IOW = 8 * (4 * E + 1);
+  const size_t k = threadIdx.x;
+  Jac<E> cur = jac_infinity<E>();
+  size_t hd = 0;
+  if (k < M) {
+    hd = head[k];
+    if (hd == k) {   // a head: the start of its segment, in the offset words of its preliminary row
+      u64 t4[4];
+      for (int q = 0; q < E; q++) { u32x8_to_u64x4(ios + IOW * k + 8 * (2 * E + q), t4); cur.X.c[q] = to_m(t4); u32x8_to_u64x4(ios + IOW * k + 8 * (3 * E + q), t4); cur.Y.c[q] = to_m(t4); }
+      cur.Z = cone<E>();
+    } else cur = ld_jac<E>(terms + 12 * E * (k - 1));   // (hd < k here, so k >= 1)
+  }
+  u64* buf[2] = {s0, s1};
+  int par = 0;
+  for (size_t d = 1; d < M; d <<= 1, par ^= 1) {
+    if (k < M) st_jac<E>(buf[par] + 12 * E * k, cur);
+    __syncthreads();                                    // one workgroup: the barrier orders its global stores and loads
+    if (k < M && k >= hd + d) cur = jac_add_complete<E>(ld_jac<E>(buf[par] + 12 * E * (k - d)), cur);   // the partner is in lane k's segment
+  }
+  if (k < M) st_jac<E>(buf[par] + 12 * E * k, cur);   // (the other buffer than the last level read)
+  __syncthreads();
+  const u64* sum = buf[par];
+  const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
+  if (k >= NL) return;
+  Fq nrm[TG_INV_BATCH];
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = k + (size_t)j * NL;
+    nrm[j] = fq_one();
+    if (i >= K) continue;
+    const Co<E> Z = ldc<E>(sum + 12 * E * (i < M ? i : M - 1) + 8 * E);
+    if (czero<E>(Z)) { atomicOr(err, TG_ERR_INFINITY); continue; }
+    nrm[j] = cnorm(Z);
+  }
+  batch_inverse(nrm);
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = k + (size_t)j * NL;
+    if (i >= K) continue;
+    const Jac<E> p = ld_jac<E>(sum + 12 * E * (i < M ? i : M - 1));   // a pad row carries the offset of row M - 1
+    Co<E> v[2];
+    if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
+    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        u64 s[4]; from_m(v[c].c[q], s);
+        for (int w = 0; w < 8; w++) ios[IOW * i + 8 * ((2 + c) * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+      }
+  }
+}
+// seg_head / seg_len: [segments] (blockIdx.x = segment; the host has checked head + len <= M <= K); starts: [SC][96] u32, SC = 1
+// (one start shared by every segment) or the number of segments; outs as fq12_offset_scan_kernel
+__global__ void __launch_bounds__(192) fq12_seg_scan_kernel(uint32_t* ios, size_t iow, size_t K, size_t M, const uint32_t* __restrict__ seg_head,
+                                                            const uint32_t* __restrict__ seg_len, const uint32_t* __restrict__ starts, size_t SC,
+                                                            const u64* __restrict__ outs) {
+  __shared__ Fq B[12], X[12], PB[144];
+  const int tid = threadIdx.x;
+  const size_t s = blockIdx.x, h = seg_head[s], len = seg_len[s];
+  const uint32_t* start = starts + (SC == 1 ? 0 : 96 * s);
+  if (tid < 12) { u64 t4[4]; u32x8_to_u64x4(start + 8 * tid, t4); B[tid] = to_m(t4); }
+  for (size_t j = 0;; j++) {
+    const size_t k = h + j;
+    if (tid < 12) {   // lane c owns coefficient c of the running product
+      u64 sw[4]; from_m(B[tid], sw);
+      for (int w = 0; w < 8; w++) ios[iow * k + 96 + 8 * tid + w] = (uint32_t)(sw[w >> 1] >> (32 * (w & 1)));
+      X[tid] = to_m(outs + (k * 12 + tid) * 4);
+    }
+    if (j + 1 == len) break;
+    __syncthreads();
+    if (tid < 144) PB[tid] = mmul(B[tid / 12], X[tid % 12]);
+    __syncthreads();
+    if (tid < 12) B[tid] = fq12_fold_coeff(PB, tid);   // read again by the products only behind the next barrier
+  }
+  if (s + 1 == gridDim.x && tid < 12) {   // the pads: the offset of instance M - 1 again (lane c wrote B[c] itself)
+    u64 sw[4]; from_m(B[tid], sw);
+    for (size_t g = M; g < K; g++)
+      for (int w = 0; w < 8; w++) ios[iow * g + 96 + 8 * tid + w] = (uint32_t)(sw[w >> 1] >> (32 * (w & 1)));
   }
 }
 

@@ -31,32 +31,6 @@ const uint32_t G2_COFACTOR[8] = {0xc0f9fa8du, 0x345f2299u, 0x572a2489u, 0x06ceec
 
 inline int curve_e(int kind) { return kind == SBN_AIR_G1_EXP ? 1 : (kind == SBN_AIR_G2_EXP ? 2 : 0); }
 
-template <int E> Jac<E> neg_point(const Jac<E>& p) { Jac<E> r = p; r.Y = csub(csub(p.Y, p.Y), p.Y); return r; }
-
-// K Jacobian points -> affine u32 words ([K][16E]) and flags ([K], 1 = the point at infinity, its words zero): one inversion for
-// every non-zero Z (through the norms on the twist); either output may be null
-template <int E> void affine_or_infinity(const std::vector<Jac<E>>& pts, uint32_t* words, uint8_t* inf) {
-  const size_t K = pts.size();
-  std::vector<Fq> nrm(K), pre(K);
-  Fq acc = fq_one();
-  for (size_t k = 0; k < K; k++) {
-    const bool z = czero<E>(pts[k].Z);
-    if (inf) inf[k] = z ? 1 : 0;
-    nrm[k] = z ? fq_one() : norm_of(pts[k].Z);
-    pre[k] = acc; acc = mmul(acc, nrm[k]);
-  }
-  if (!words) return;
-  Fq inv = fq_inv_m(acc);
-  for (size_t k = K; k-- > 0;) { const Fq ni = mmul(inv, pre[k]); inv = mmul(inv, nrm[k]); nrm[k] = ni; }
-  for (size_t k = 0; k < K; k++) {
-    uint32_t* out = words + 16 * E * k;
-    if (czero<E>(pts[k].Z)) { memset(out, 0, 16 * E * sizeof(uint32_t)); continue; }
-    const Co<E> zi = inv_from_norm(pts[k].Z, nrm[k]), zi2 = cmul(zi, zi);
-    const Co<E> x = cmul(pts[k].X, zi2), y = cmul(pts[k].Y, cmul(zi2, zi));
-    for (int q = 0; q < E; q++) { st_u32(x.c[q], out + 8 * q); st_u32(y.c[q], out + 8 * (E + q)); }
-  }
-}
-
 // the table's own walk (g1/exp.rs:165-230) of the K instances of an explicit list, one at a time: the first one it cannot walk
 template <int E> int name_degenerate(const uint32_t* ios, size_t K, size_t base = 0) {
   const size_t IOW = 32 * E + 8;

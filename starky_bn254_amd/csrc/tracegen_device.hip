@@ -148,6 +148,38 @@ struct ScalarMulIn { const uint32_t* points; const uint32_t* scalars; size_t sca
 // its x from `bases`, level l from the output of level l - 1, derived on the device (kernels_tracegen.cuh, "power towers").
 struct PowerIn { const uint32_t* bases; const uint32_t* exps; size_t exp_count, count, depth; uint32_t* powers_out; uint32_t* ios_out; };
 
+// sbn_prover_generate_trace_msm_batch: one unit of `segments` chained lists, M real instances and num_io - M pads; the offsets are
+// derived on the device from the terms, the heads and the starts (kernels_tracegen.cuh, "segmented chained lists"), the finals
+// are the instance outputs at the segment tails and, on the curves, the sums final + (-start) are computed there too.
+struct BatchIn {
+  const uint32_t* terms; const uint64_t* lengths; size_t segments; const uint32_t* starts; size_t start_count, M;
+  uint32_t* finals_out; uint32_t* sums_out; uint8_t* infinity_out; uint32_t* ios_out;
+};
+// the preliminary list of a segmented one: row g carries x and exponent of instance min(g, M - 1) and `offset_of(segment)` as its
+// offset; head_of[g] = the head of the segment of that instance (optional); seg_head / seg_len: per segment
+static std::vector<uint32_t> batch_preliminary_list(const BatchIn& mb, size_t K, size_t xw, size_t ew, const std::function<const uint32_t*(size_t)>& offset_of,
+                                                    std::vector<uint32_t>& seg_head, std::vector<uint32_t>& seg_len, std::vector<uint32_t>* head_of) {
+  std::vector<uint32_t> ios((2 * xw + ew) * K);
+  seg_head.resize(mb.segments); seg_len.resize(mb.segments);
+  if (head_of) head_of->resize(K);
+  size_t g = 0;
+  for (size_t s = 0; s < mb.segments; s++) {
+    seg_head[s] = (uint32_t)g; seg_len[s] = (uint32_t)mb.lengths[s];
+    for (size_t j = 0; j < mb.lengths[s]; j++, g++) {
+      uint32_t* io = ios.data() + (2 * xw + ew) * g;
+      memcpy(io, mb.terms + (xw + ew) * g, xw * sizeof(uint32_t));
+      memcpy(io + xw, offset_of(s), xw * sizeof(uint32_t));
+      memcpy(io + 2 * xw, mb.terms + (xw + ew) * g + xw, ew * sizeof(uint32_t));
+      if (head_of) (*head_of)[g] = seg_head[s];
+    }
+  }
+  for (; g < K; g++) {   // the reference's resize rule: a pad row is the last row again
+    memcpy(ios.data() + (2 * xw + ew) * g, ios.data() + (2 * xw + ew) * (mb.M - 1), (2 * xw + ew) * sizeof(uint32_t));
+    if (head_of) (*head_of)[g] = (uint32_t)g;   // (never read: the scan's lanes stop at M)
+  }
+  return ios;
+}
+
 // One sbn_prover_generate_trace call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
 struct TraceJob {
   sbn_prover* const P;
@@ -226,10 +258,13 @@ struct TraceJob {
 
 // G1ExpStark / G2ExpStark (E = 1 / 2)
 template <int E>
-static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const ScalarMulIn* sm = nullptr) {
+static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const ScalarMulIn* sm = nullptr,
+                                 const BatchIn* mb = nullptr) {
   const size_t IOW = 8 * (4 * E + 1);  // u32 words per instance: x and offset (2E Fq each) + exp_val
   std::vector<uint32_t> prelim;        // chained: x, start, exp_val of every instance; the device rewrites the offsets
   const size_t cin_words = sm ? 16 * E * K + 8 * sm->scalar_count + 16 * E : 0;   // scalar multiplications: u32 words of the compact upload
+  std::vector<uint32_t> aux;           // segmented: head[K], then tail[segments] and head-of-segment[segments]
+  const size_t NP = sm ? K : (mb ? mb->segments : 0);   // products (scalar multiplications) / sums (segmented) that come back
   if (sm) {   // the host keeps its own explicit list for the public inputs; only the compact form goes up
     if (int rc = scalar_mul_check_points(E, sm->points, K, sm->offset)) return rc;
     prelim.resize(IOW * K);
@@ -239,6 +274,14 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
     if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a chained list has at most %d instances", tg::CS_LANES);
     if (int rc = chain_terms_check_curve(E, ch->terms, K, ch->start)) return rc;
     prelim = preliminary_list(*ch, K, 16 * E, 8, ch->start);
+    ios = prelim.data();
+  } else if (mb) {   // segmented: x, the start of its segment, exp_val of every instance; heads of the lanes, then tail and head per segment
+    if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a segmented list has at most %d instances", tg::CS_LANES);
+    if (int rc = msm_batch_check_inputs(P->air.kind, mb->terms, mb->lengths, mb->segments, mb->starts, mb->start_count, mb->M)) return rc;
+    std::vector<uint32_t> seg_head, seg_len;
+    prelim = batch_preliminary_list(*mb, K, 16 * E, 8, [&](size_t s) { return mb->starts + (mb->start_count == 1 ? 0 : 16 * E * s); }, seg_head, seg_len, &aux);
+    for (size_t s = 0; s < mb->segments; s++) aux.push_back(seg_head[s] + seg_len[s] - 1);
+    aux.insert(aux.end(), seg_head.begin(), seg_head.end());
     ios = prelim.data();
   } else if (int rc = check_below_p(ios, IOW, 4 * E, K, "coordinate")) return rc;
   HIPC(hipSetDevice(P->device));
@@ -254,14 +297,16 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   uint32_t* d_prog[2] = {(uint32_t*)J.take(64 * tg::CP_LANES / 2), (uint32_t*)J.take(64 * tg::CP_LANES / 2)};   // chain programs: <= 64 levels of 64 micro-operations
   int* d_err = (int*)J.take(1);
   unsigned int* d_cnt = J.take_histograms();
-  u64* d_pre = ch ? J.take(12 * E * tg::CT_LANES * K) : nullptr;              // chained: the partial sums of every instance,
-  u64* d_terms = ch ? J.take(12 * E * K) : nullptr;                           // e_k x_k, then the two scan buffers
-  u64* d_scan[2] = {ch ? J.take(12 * E * K) : nullptr, ch ? J.take(12 * E * K) : nullptr};
-  int* d_err_pre = ch ? (int*)J.take(1) : nullptr;                            // flags of the preliminary chains (offsets = start): never read
+  const bool scan = ch || mb;                                                 // chained and segmented lists derive their offsets here
+  u64* d_pre = scan ? J.take(12 * E * tg::CT_LANES * K) : nullptr;            // chained: the partial sums of every instance,
+  u64* d_terms = scan ? J.take(12 * E * K) : nullptr;                         // e_k x_k, then the two scan buffers
+  u64* d_scan[2] = {scan ? J.take(12 * E * K) : nullptr, scan ? J.take(12 * E * K) : nullptr};
+  int* d_err_pre = scan ? (int*)J.take(1) : nullptr;                          // flags of the preliminary chains (offsets = start): never read
   uint32_t* d_cin = sm ? (uint32_t*)J.take(cin_words / 2 + 1) : nullptr;      // scalar multiplications: the compact upload, the Jacobian
-  u64* d_jp = sm ? J.take(12 * E * K) : nullptr;                              // products between the two passes of a lane, the affine
-  uint32_t* d_prod = sm ? (uint32_t*)J.take(8 * E * K) : nullptr;             // products ([K][16E] u32) and their infinity flags
-  unsigned char* d_inf = sm ? (unsigned char*)J.take(K / 8 + 1) : nullptr;
+  u64* d_jp = NP ? J.take(12 * E * NP) : nullptr;                             // products between the two passes of a lane, the affine
+  uint32_t* d_prod = NP ? (uint32_t*)J.take(8 * E * NP) : nullptr;            // products ([NP][16E] u32) and their infinity flags
+  unsigned char* d_inf = NP ? (unsigned char*)J.take(NP / 8 + 1) : nullptr;
+  uint32_t* d_aux = mb ? (uint32_t*)J.take(aux.size() / 2 + 1) : nullptr;     // segmented: the index arrays
   if (int rc = J.fits()) return rc;
   if (int rc = range_check_setup(P->device)) return rc;
   // both chains of every instance on the device, flags into `errw` (chain_mode 2 / 1, see below)
@@ -285,10 +330,10 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   // the instance list in and the outputs + error word back cross through pinned staging (chained: the derived list comes back too)
   // (scalar multiplications: the compact form in, the products and their flags back behind the outputs)
   const size_t io_words = sm ? (cin_words + 1) / 2 : (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
-  const size_t prod_words = sm ? 8 * E * K : 0, inf_words = sm ? (K + 7) / 8 : 0;
-  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words + (ch ? io_words : 0) + prod_words + inf_words)) return rc;
+  const size_t prod_words = 8 * E * NP, inf_words = (NP + 7) / 8;
+  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words + (scan ? io_words : 0) + prod_words + inf_words)) return rc;
   u64* const h_out = P->h_io + io_words;
-  u64* const h_prod = h_out + out_words;
+  u64* const h_prod = h_out + out_words + (scan ? io_words : 0);   // (behind the derived list where one comes back)
   if (sm) {
     uint32_t* h = (uint32_t*)P->h_io;
     memcpy(h, sm->points, 16 * E * K * sizeof(uint32_t));
@@ -301,10 +346,12 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
     memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
     if (int rc = J.begin(P->h_io, d_ios, d_err)) return rc;
   }
-  if (ch) {   // offsets on the device (kernels_tracegen.cuh, "chained instance lists"); only chain_mode 1 and 2 come here
+  if (scan) {   // offsets on the device (kernels_tracegen.cuh, "chained instance lists"); only chain_mode 1 and 2 come here
+    if (mb) HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (int rc = launch_chains(d_err_pre)) return rc;
     hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, d_pre, d_terms);
-    hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, d_terms, d_scan[0], d_scan[1], d_err);
+    if (mb) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, mb->M, d_aux, d_terms, d_scan[0], d_scan[1], d_err);
+    else hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, d_terms, d_scan[0], d_scan[1], d_err);
     J.mark();
     ios = (const uint32_t*)(h_out + out_words);   // where the derived list lands, below
   }
@@ -313,7 +360,7 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   // chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx picks by the host pool's size): 2 = one wave per instance walking levels of
   // independent Fq operations (tg::chain_coop_kernel), 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host threads +
   // pinned upload
-  if (ch) hipLaunchKernelGGL(tg::chain_rebase_kernel<E>, blocks(K * 257, 64), dim3(64), 0, st, d_ios, K, d_pre, jb);   // A is in ja already
+  if (scan) hipLaunchKernelGGL(tg::chain_rebase_kernel<E>, blocks(K * 257, 64), dim3(64), 0, st, d_ios, K, d_pre, jb);   // A is in ja already
   else if (P->chain_mode) { if (int rc = launch_chains(d_err)) return rc; }
   else {
     if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
@@ -328,6 +375,11 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
     hipLaunchKernelGGL(tg::scalar_mul_unoffset_kernel<E>, blocks((K + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, K, d_out, d_jp, d_prod, d_inf);
     J.mark();
   }
+  if (mb) {   // final_s + (-start_s): the same kernel, indexed by the tail and the head of every segment
+    hipLaunchKernelGGL(tg::scalar_mul_unoffset_kernel<E>, blocks((NP + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, NP, d_out, d_jp, d_prod, d_inf,
+                       d_aux + K, d_aux + K + NP);
+    J.mark();
+  }
   hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, J.sh.gadget_col, P->d_trace, d_err);
   J.mark();
   if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
@@ -335,15 +387,16 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h_out, d_out, 16 * E * K * sizeof(u64), hipMemcpyDeviceToHost, st));
   HIPC(hipMemcpyAsync(h_out + 16 * E * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (ch) HIPC(hipMemcpyAsync(h_out + out_words, d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (scan) HIPC(hipMemcpyAsync(h_out + out_words, d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   static const char* const names[] = {"flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
-  if (sm) {
-    HIPC(hipMemcpyAsync(h_prod, d_prod, 16 * E * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(h_prod + prod_words, d_inf, K, hipMemcpyDeviceToHost, st));
+  if (NP) {
+    HIPC(hipMemcpyAsync(h_prod, d_prod, 16 * E * NP * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(h_prod + prod_words, d_inf, NP, hipMemcpyDeviceToHost, st));
   }
   static const char* const names_chained[] = {"chain_offsets", "flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
   static const char* const names_scalar[] = {"scalar_list", "flags+pulses", "chains", "affine+lambda", "un_offset", "row_witness", "range_check"};
-  if (int rc = J.end(sm ? names_scalar : ch ? names_chained : names)) return rc;
+  static const char* const names_batch[] = {"chain_offsets", "flags+pulses", "chains", "affine+lambda", "un_offset", "row_witness", "range_check"};
+  if (int rc = J.end(sm ? names_scalar : mb ? names_batch : ch ? names_chained : names)) return rc;
   // public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156)
   const int rc = J.finish((int)(h_out[16 * E * K] & 0xffffffffu), pi_out, [&](size_t k, u64* p) {
     for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
@@ -355,6 +408,19 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
     if (int named = scalar_mul_name_degenerate(E, ios, K)) return named;
     return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
   }
+  if (mb && rc == SBN_ERR_WITNESS && ((int)(h_out[16 * E * K] & 0xffffffffu) & (tg::TG_ERR_INFINITY | tg::TG_ERR_DEGENERATE))) {
+    // the kernels report an error word only: the host derivation names the instance and its segment (error path)
+    std::vector<uint32_t> named(IOW * K);
+    if (int why = msm_batch_derive(P->air.kind, mb->terms, mb->lengths, mb->segments, mb->starts, mb->start_count, mb->M, K, named.data(), nullptr, nullptr, nullptr)) return why;
+    return rc;
+  }
+  if (mb && rc == SBN_OK) {
+    if (mb->ios_out) memcpy(mb->ios_out, ios, IOW * K * sizeof(uint32_t));
+    if (mb->finals_out)   // the instance outputs at the segment tails: one u32 limb per u64 word
+      for (size_t s = 0; s < NP; s++) for (int i = 0; i < 16 * E; i++) mb->finals_out[16 * E * s + i] = (uint32_t)h_out[16 * E * aux[K + s] + i];
+    if (mb->sums_out) memcpy(mb->sums_out, h_prod, 16 * E * NP * sizeof(uint32_t));
+    if (mb->infinity_out) memcpy(mb->infinity_out, h_prod + prod_words, NP);
+  }
   if (sm && rc == SBN_OK) {
     if (sm->products_out) memcpy(sm->products_out, h_prod, 16 * E * K * sizeof(uint32_t));
     if (sm->infinity_out) memcpy(sm->infinity_out, h_prod + prod_words, K);
@@ -365,7 +431,8 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
 
 // Fq12ExpStark: the square-and-multiply chains (no inversion anywhere) on host threads in standard form, then one lane
 // per row for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
-static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const PowerIn* pw = nullptr) {
+static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const PowerIn* pw = nullptr,
+                                      const BatchIn* mb = nullptr) {
   const bool u64e = P->air.kind == SBN_AIR_FQ12_EXP_U64;        // 128-row instances, one-element exponent
   const size_t IOW = u64e ? 194 : 200;
   const int steps = u64e ? 64 : 256, log_rpb = u64e ? 7 : 9;
@@ -374,6 +441,18 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     if (int rc = check_below_p(ch->start, 96, 12, 1, "coefficient of start")) return rc;
     uint32_t one[96] = {1};
     prelim = preliminary_list(*ch, K, 96, IOW - 192, one);
+    derived.resize(IOW * K);
+    ios = prelim.data();
+  }
+  std::vector<uint32_t> aux;   // segmented: head[segments], len[segments], then the starts ([start_count][96])
+  if (mb) {   // x, one, exp_val of every instance (a pad row repeats row M - 1); the device rewrites the offsets
+    if (int rc = msm_batch_check_inputs(P->air.kind, mb->terms, mb->lengths, mb->segments, mb->starts, mb->start_count, mb->M)) return rc;
+    uint32_t one[96] = {1};
+    std::vector<uint32_t> seg_head, seg_len;
+    prelim = batch_preliminary_list(*mb, K, 96, IOW - 192, [&](size_t) { return (const uint32_t*)one; }, seg_head, seg_len, nullptr);
+    aux = seg_head;
+    aux.insert(aux.end(), seg_len.begin(), seg_len.end());
+    aux.insert(aux.end(), mb->starts, mb->starts + 96 * mb->start_count);
     derived.resize(IOW * K);
     ios = prelim.data();
   }
@@ -406,12 +485,17 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
   int* d_err = (int*)J.take(1);
   uint32_t* d_start = ch ? (uint32_t*)J.take(48) : nullptr;
+  uint32_t* d_aux = mb ? (uint32_t*)J.take(aux.size() / 2 + 1) : nullptr;
   if (int rc = J.fits()) return rc;
   if (pw && (u64*)d_ios != d_outs + K * 48) return fail(SBN_ERR_UNSUPPORTED, "internal: the instance list does not follow the outputs");   // (one download, below)
   if (int rc = J.begin(ios, d_ios, d_err)) return rc;
   if (ch) {
     HIPC(hipMemcpyAsync(d_start, ch->start, 96 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     ios = derived.data();   // where the derived list lands, below
+  }
+  if (mb) {
+    HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ios = derived.data();
   }
   if (u64e) J.launch_common_columns(tg::flags_u64_kernel, d_ios, inv, 255);
   else J.launch_common_columns(tg::flags_kernel, d_ios, inv, 255);
@@ -431,6 +515,12 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
   if (ch) {   // the chains above ran on offsets of one (device chains only): x^e of every instance is in d_outs; the running product
     // writes the offsets into d_ios and the chain is rebased onto them (kernels_tracegen.cuh, "chained instance lists")
     hipLaunchKernelGGL(tg::fq12_offset_scan_kernel, dim3(1), dim3(192), 0, st, d_ios, IOW, K, d_start, d_outs);
+    hipLaunchKernelGGL(tg::fq12_rebase_kernel, dim3((unsigned)(K * (size_t)(steps + 1))), dim3(192), 0, st, d_ios, IOW, steps, cb, d_outs);
+    J.mark();
+  }
+  if (mb) {   // the same on a segmented list: one workgroup per segment walks its own running product ("segmented chained lists")
+    const size_t S = mb->segments;
+    hipLaunchKernelGGL(tg::fq12_seg_scan_kernel, dim3((unsigned)S), dim3(192), 0, st, d_ios, IOW, K, mb->M, d_aux, d_aux + S, d_aux + 2 * S, mb->start_count, d_outs);
     hipLaunchKernelGGL(tg::fq12_rebase_kernel, dim3((unsigned)(K * (size_t)(steps + 1))), dim3(192), 0, st, d_ios, IOW, steps, cb, d_outs);
     J.mark();
   }
@@ -454,11 +544,11 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     chain_out.resize(K * 48);
     HIPC(hipMemcpyAsync(chain_out.data(), d_outs, K * 48 * sizeof(u64), hipMemcpyDeviceToHost, st));
   }
-  if (ch) HIPC(hipMemcpyAsync(derived.data(), d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (ch || mb) HIPC(hipMemcpyAsync(derived.data(), d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
   static const char* const names_chained[] = {"flags+pulses", "chains", "chain_offsets", "row_witness", "range_check"};
   static const char* const names_tower[] = {"flags+pulses", "tower_links", "tower_pads", "row_witness", "range_check"};
-  if (int rc = J.end(pw ? names_tower : ch ? names_chained : names)) return rc;
+  if (int rc = J.end(pw ? names_tower : (ch || mb) ? names_chained : names)) return rc;
   // public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117)
   const int rc = J.finish(err, pi_out, [&](size_t k, u64* p) {
     for (int c = 0; c < 24; c++)
@@ -470,6 +560,14 @@ static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t
     for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
   });
   if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
+  if (rc == SBN_OK && mb) {
+    if (mb->ios_out) memcpy(mb->ios_out, ios, IOW * K * sizeof(uint32_t));
+    if (mb->finals_out)   // [segments][96] u32 = the outputs of the segment tails, standard form
+      for (size_t s = 0; s < mb->segments; s++) {
+        const u64* out = chain_out.data() + 48 * (size_t)(aux[s] + aux[mb->segments + s] - 1);
+        for (size_t i = 0; i < 48; i++) { mb->finals_out[96 * s + 2 * i] = (uint32_t)out[i]; mb->finals_out[96 * s + 2 * i + 1] = (uint32_t)(out[i] >> 32); }
+      }
+  }
   if (rc == SBN_OK && pw) {
     if (pw->ios_out) memcpy(pw->ios_out, ios, IOW * K * sizeof(uint32_t));
     if (pw->powers_out)   // [count][depth][96] u32 = the outputs of the M real instances, standard form
@@ -567,6 +665,35 @@ extern "C" int sbn_prover_generate_trace_scalar_muls(sbn_prover* P, const uint32
   }
   const ScalarMulIn sm{points, scalars, scalar_count, offset, products_out, infinity_out, ios_out};
   return E == 1 ? generate_trace_device<1>(P, nullptr, num_io, pi_out, nullptr, &sm) : generate_trace_device<2>(P, nullptr, num_io, pi_out, nullptr, &sm);
+}
+
+// sbn_prover_generate_trace on the one-unit list sbn_msm_batch_instances derives from (terms, lengths, starts): where the table's
+// chains run on the device (G1 / G2 under chain_mode 1 and 2, Fq12 / Fq12U64 unless SBN_FQ12_HOST_CHAIN) the offsets, the finals and
+// the sums are derived there; elsewhere (host-pool curve chains, FqExpStark) the list is host work anyway and takes the explicit path.
+extern "C" int sbn_prover_generate_trace_msm_batch(sbn_prover* P, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts,
+                                                   size_t start_count, uint64_t* pi_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out,
+                                                   uint32_t* ios_out) {
+  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  const int kind = P->air.kind;
+  const size_t num_io = P->air.num_io;
+  size_t M = 0;
+  if (int rc = msm_batch_check_args(kind, terms, lengths, segments, &starts, &start_count, num_io, sums_out, infinity_out, &M)) return rc;
+  if (M > num_io) return fail(SBN_ERR_BAD_ARG, "%zu segments of %zu instances do not fit one unit of %zu instances", segments, M, num_io);
+  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
+  const bool fq12 = kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64;
+  if (!fq12 && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  if (kind == SBN_AIR_FQ_EXP || (fq12 ? P->set.fq12_host_chain : P->chain_mode == 0)) {
+    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
+    if (int rc = msm_batch_derive(kind, terms, lengths, segments, starts, start_count, M, num_io, ios.data(), finals_out, sums_out, infinity_out)) return rc;
+    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
+    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
+    return rc;
+  }
+  const BatchIn mb{terms, lengths, segments, starts, start_count, M, finals_out, sums_out, infinity_out, ios_out};
+  if (fq12) return generate_trace_device_fq12(P, nullptr, num_io, pi_out, nullptr, nullptr, &mb);
+  return kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, nullptr, num_io, pi_out, nullptr, nullptr, &mb)
+                                : generate_trace_device<2>(P, nullptr, num_io, pi_out, nullptr, nullptr, &mb);
 }
 
 // sbn_prover_generate_trace on the one-unit list sbn_power_instances derives from (bases, exps, depth): on an Fq12 table whose
