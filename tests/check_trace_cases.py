@@ -1,4 +1,4 @@
-"""Shared by tests/test_check_trace_host.py and tests/test_check_trace_gpu.py: the tables of the trace check at their smallest
+"""Shared by tests/test_check_trace_host.py, tests/test_check_trace_gpu.py and the column sweep (tests/column_sweep.py): the tables of the trace check at their smallest
 height, the cells the tests change, and the independent reference -- the oracle's constraint-by-constraint evaluator
 (orc_eval_constraints) applied on the trace domain H: L_first = [i == 0], L_last = [i == n - 1], z_last = g^i - g^(n - 1).
 Traces and the oracle's verdict on the valid trace are built once per process."""
@@ -20,6 +20,12 @@ def _exp_start_lookups(stark, flag_cols, periodic):
     """First column of the range-check block of an Fq12 Exp table (csrc/air.cuh ExpShape): main columns, flags, the rotation
     pulse (counter, witness) where the table has one, the io-pulse counter and (witness, pulse) per block boundary."""
     return 108 * 16 + flag_cols + (2 if periodic else 0) + 1 + 4 * stark.num_io
+
+
+def exp_ios(name):
+    """The instances of the three 2^16-row Exp cases (128 each: the u16 range check needs that many rows), as the host and the
+    device generators take them."""
+    return {"g1exp": lambda: O.g1exp_inputs(128, 1), "g2exp": lambda: O.g2exp_inputs(128, 2), "fqexp": lambda: O.fqexp_inputs(128, 4)}[name]()[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,6 +69,18 @@ def case(name):
         ios = O.g1exp_inputs(128, 1)[0]
         trace, pi = stark.generate_trace_and_public_inputs(ios)
         cols = (64 + 16, 384 + 14 + 2 + 1 + 4 * 128 + 2)             # new_x limb 0; the sorted copy of range-check target 0
+    elif name == "fq12mul":
+        stark = S.Fq12Stark()
+        trace, pi = stark.generate_trace(O.fq12mul_inputs(512, 7)[0]), NOPI
+        cols = (24 * 16, 108 * 16 + 1 + 1 + 2)     # output coefficient 0 limb 0; the sorted copy of target 0
+    elif name == "g2exp":
+        stark = S.G2ExpStark(128)
+        trace, pi = stark.generate_trace_and_public_inputs(exp_ios(name))
+        cols = (128 + 32, 768 + 14 + 2 + 1 + 4 * 128 + 2)            # new_x.c0 limb 0; the sorted copy of range-check target 0
+    elif name == "fqexp":
+        stark = S.FqExpStark(128)
+        trace, pi = stark.generate_trace_and_public_inputs(exp_ios(name))
+        cols = (32, 144 + 14 + 2 + 1 + 4 * 128 + 2)                  # output limb 0; the sorted copy of range-check target 0
     else:
         raise KeyError(name)
     n = trace.shape[1]
@@ -70,7 +88,7 @@ def case(name):
     assert all(0 <= c < trace.shape[0] for c in cols) and len(set(cols)) == 3
     rows = [0, 1, 255, 256, n - 1]                 # 255 | 256: the workgroup boundary of the kernels
     rpi = S.api._rows_per_instance(stark)
-    if stark.kind in (S.AIR_G1_EXP, S.AIR_FQ12_EXP, S.AIR_FQ12_EXP_U64):
+    if stark.kind in (S.AIR_G1_EXP, S.AIR_G2_EXP, S.AIR_FQ12_EXP, S.AIR_FQ_EXP, S.AIR_FQ12_EXP_U64):
         rows += [r for r in (rpi - 1, rpi, 511, 512) if r < n]       # the instance boundary, where the table has one
     rows = sorted(set(rows))
     trace.setflags(write=False)
