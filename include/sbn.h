@@ -121,6 +121,12 @@ int sbn_set_device(int device);
 /* The same for the calling thread ONLY (the process default stays): for rank threads of one process (sbn_local_comm_create). */
 int sbn_set_thread_device(int device);
 void sbn_standard_fast_config(sbn_config* out);      /* StarkConfig::standard_fast_config */
+/* sbn_standard_fast_config with another blowup at the same conjectured security (rate_bits * num_query_rounds + proof_of_work_bits
+ * >= security_bits): rate_bits set and num_query_rounds = ceil((security_bits - proof_of_work_bits) / rate_bits), i.e. 84 / 42 / 28
+ * queries at rate_bits 1 / 2 / 3.  rate_bits 3 with 28 queries are the FRI parameters of plonky2's standard_recursion_config: a proof a
+ * third the size for a recursive verifier, for four times the LDE rows to hash.  rate_bits = 0 is taken as 1.  The helper only fills
+ * the struct: which values the provers and verifiers accept is stated at sbn_prover_create. */
+void sbn_config_for_rate(uint32_t rate_bits, sbn_config* out);
 
 /* Table shape (ExpStarkConstants, src/curves/g1/exp.rs:6-34) ----------------------------------- */
 size_t sbn_air_num_columns(const sbn_air_desc* air);
@@ -165,12 +171,15 @@ int sbn_generate_trace_flags(const uint32_t* limbs, size_t num_io, uint64_t* tra
 int sbn_generate_trace_flags_u64(const uint64_t* exps, size_t num_io, uint64_t* trace_out);
 
 /* Prover ---------------------------------------------------------------------------------------- */
-/* Accepted (anything else: SBN_ERR_UNSUPPORTED, checked before a device is looked for): num_challenges = 2, rate_bits = 1,
- * cap_height 1..8, fri_arity_bits 1..4, num_query_rounds 1..512, proof_of_work_bits 0..32, any fri_final_poly_bits, fri_variant
- * 0..2; degree_bits 9..22 (the Exp tables: the height their num_io fixes, G1 / G2 / FQ_EXP from 2^16 rows).  Every value of
+/* Accepted (anything else: SBN_ERR_UNSUPPORTED, checked before a device is looked for): num_challenges = 2, rate_bits 1 or 3
+ * (2 is refused: the transforms and the Merkle kernels run at it through sbn_commit_values only), cap_height 1..8, fri_arity_bits
+ * 1..4, num_query_rounds 1..512, proof_of_work_bits 0..32, any fri_final_poly_bits, fri_variant 0..2; degree_bits >= 9 with
+ * degree_bits + rate_bits <= 23, the largest LDE being 2^23 points: 9..22 at rate_bits 1, 9..20 at rate_bits 3 (the Exp tables: the
+ * height their num_io fixes, G1 / G2 / FQ_EXP from 2^16 rows).  sbn_verifier_create accepts the same range.  Every value of
  * that range is proved on the device and compared word for word with the CPU oracle under the same config
- * (tests/test_config_matrix_gpu.py: each field at both ends of its range except 32 proof-of-work bits, LookupStark at every
- * height up to 2^22 rows).  fri_arity_bits = 1: a FRI leaf is two extension values = four words, which is its own digest
+ * (tests/test_config_matrix_gpu.py at rate_bits 1: each field at both ends of its range except 32 proof-of-work bits, LookupStark
+ * at every height up to 2^22 rows; tests/test_rate_gpu.py at rate_bits 3).  At rate_bits r the quotient is evaluated on the coset of
+ * 2n points, every 2^(r-1)-th row of the LDE, as starky does (the section on rate_bits).  fri_arity_bits = 1: a FRI leaf is two extension values = four words, which is its own digest
  * (plonky2 hash_or_noop), as the rows of a matrix of at most four columns are. */
 int sbn_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, sbn_prover** out);
 void sbn_prover_destroy(sbn_prover* p);
@@ -591,7 +600,9 @@ int sbn_power_check(int32_t kind, size_t num_io, const uint64_t* const* public_i
  * openings, FRI partial sums, query rows).  The collectives come with the sbn_comm: the transports of this library
  * (sbn_rccl_comm_create: RCCL send / recv over xGMI; sbn_local_comm_create: the ranks are threads of one process), or the
  * caller's own (torch.distributed in starky_bn254_amd/split.py; a host-staged backend for tests).
- * world must be 1, 2, 4, 8 or 16 (<= 2^cap_height). */
+ * world must be 1, 2, 4, 8 or 16 (<= 2^cap_height).
+ * rate_bits = 1 only: with rate_bits > 1 sbn_split_exchange_bytes and sbn_split_prover_create return SBN_ERR_UNSUPPORTED for every
+ * world, 1 included (the exchange plans deal the rows of a 2n-point LDE, which is then also the quotient's domain). */
 typedef struct sbn_comm {
   uint32_t struct_size;      /* sizeof(sbn_comm) of the caller's header (ABI check) */
   uint32_t reserved;
@@ -686,7 +697,8 @@ void sbn_verifier_destroy(sbn_verifier* v);
 /* Building blocks exposed for parity tests and benchmarks (device in/out unless noted) --------- */
 /* PolynomialBatch::from_values on a host column-major matrix: Merkle cap (2^cap_height x 4 words),
  * optionally coefficients [ncols][n] and LDE [ncols][n<<rate_bits] (natural order) back to host.
- * rate_bits = 1, n a power of two >= 512, cap_height 1..8 (the range of sbn_config); otherwise SBN_ERR_UNSUPPORTED. */
+ * rate_bits 1..3 with n << rate_bits <= 2^23, n a power of two >= 512, cap_height 1..8 (the range of sbn_config); otherwise
+ * SBN_ERR_UNSUPPORTED.  Runs the transform plan and the kernels a prover of n rows and this rate_bits runs. */
 int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
                       uint64_t* cap_out, uint64_t* coeffs_out, uint64_t* lde_out);
 /* Poseidon permutation of `count` independent width-12 states on the device (host in/out). */

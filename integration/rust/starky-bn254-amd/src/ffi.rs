@@ -98,6 +98,9 @@ extern "C" {
     pub fn sbn_set_device(device: i32) -> i32;
     pub fn sbn_set_thread_device(device: i32) -> i32;
     pub fn sbn_device_count() -> i32;
+    pub fn sbn_standard_fast_config(out: *mut sbn_config);
+    /// standard_fast_config at another blowup and the same conjectured security: 84 / 42 / 28 queries at rate_bits 1 / 2 / 3
+    pub fn sbn_config_for_rate(rate_bits: u32, out: *mut sbn_config);
     pub fn sbn_air_num_columns(air: *const sbn_air_desc) -> usize;
     pub fn sbn_air_num_public_inputs(air: *const sbn_air_desc) -> usize;
 

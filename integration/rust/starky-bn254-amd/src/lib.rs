@@ -81,6 +81,16 @@ pub fn to_sbn_config(c: &StarkConfig) -> Result<ffi::sbn_config> {
     })
 }
 
+/// include/sbn.h `sbn_config_for_rate`: `standard_fast_config` at another blowup and the same conjectured security (84 / 42 / 28
+/// queries at `rate_bits` 1 / 2 / 3; 3 = the FRI parameters of plonky2's `standard_recursion_config`).  The provers and verifiers
+/// accept `rate_bits` 1 and 3.  `to_sbn_config` passes a `StarkConfig`'s own `fri_config.rate_bits` through unchanged.
+pub fn sbn_config_for_rate(rate_bits: u32) -> ffi::sbn_config {
+    let mut c = ffi::sbn_config::default();
+    unsafe { ffi::sbn_config_for_rate(rate_bits, &mut c) };
+    c.fri_variant = FRI_VARIANT;
+    c
+}
+
 /// Device context for one (table, degree_bits): HBM buffers, streams, twiddles.  Create once, prove many times.
 pub struct Prover {
     raw: *mut ffi::sbn_prover,

@@ -27,7 +27,7 @@ _LIB = None
 
 # every symbol include/sbn.h declares
 EXPORTS = [
-    "sbn_version", "sbn_last_error", "sbn_device_count", "sbn_set_device", "sbn_set_thread_device", "sbn_standard_fast_config",
+    "sbn_version", "sbn_last_error", "sbn_device_count", "sbn_set_device", "sbn_set_thread_device", "sbn_standard_fast_config", "sbn_config_for_rate",
     "sbn_air_num_columns", "sbn_air_num_public_inputs", "sbn_air_num_permutation_zs", "sbn_air_num_constraints",
     "sbn_generate_trace_g1_exp", "sbn_generate_trace_g2_exp", "sbn_generate_trace_fq12_exp", "sbn_generate_trace_fq_exp", "sbn_generate_trace_fq12_exp_u64",
     "sbn_generate_trace_g1_op", "sbn_generate_trace_modular", "sbn_generate_trace_fq12_mul", "sbn_generate_trace_lookup", "sbn_generate_trace_flags", "sbn_generate_trace_flags_u64",
@@ -113,6 +113,8 @@ def lib():
         L.sbn_air_num_permutation_zs.restype = sz
         L.sbn_air_num_permutation_zs.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config)]
         L.sbn_standard_fast_config.argtypes = [C.POINTER(_Config)]
+        L.sbn_config_for_rate.argtypes = [u32, C.POINTER(_Config)]
+        L.sbn_config_for_rate.restype = None
         L.sbn_generate_trace_g1_exp.argtypes = [vp, sz, vp, vp]
         L.sbn_generate_trace_g2_exp.argtypes = [vp, sz, vp, vp]
         L.sbn_generate_trace_fq12_exp.argtypes = [vp, sz, vp, vp]
@@ -233,6 +235,14 @@ class StarkConfig:
     @staticmethod
     def standard_fast_config(num_columns=None, num_public_inputs=None):
         return StarkConfig()
+
+    @staticmethod
+    def for_rate(rate_bits):
+        """standard_fast_config at another blowup and the same conjectured security (sbn_config_for_rate): 84 / 42 / 28 queries
+        at rate_bits 1 / 2 / 3.  The provers and verifiers accept rate_bits 1 and 3."""
+        cfg = StarkConfig()
+        lib().sbn_config_for_rate(rate_bits, C.byref(cfg._c))
+        return cfg
 
     def __getattr__(self, name):
         return getattr(object.__getattribute__(self, "_c"), name)

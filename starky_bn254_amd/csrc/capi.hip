@@ -103,6 +103,14 @@ void sbn_standard_fast_config(sbn_config* c) {
   c->fri_arity_bits = 4; c->fri_final_poly_bits = 5; c->num_query_rounds = 84;
   c->fri_variant = SBN_FRI_TIMES_X;
 }
+// the same security from another blowup: rate_bits * num_query_rounds + proof_of_work_bits >= security_bits
+void sbn_config_for_rate(uint32_t rate_bits, sbn_config* c) {
+  if (!c) return;
+  sbn_standard_fast_config(c);
+  if (rate_bits == 0) rate_bits = 1;
+  c->rate_bits = rate_bits;
+  c->num_query_rounds = (c->security_bits - c->proof_of_work_bits + rate_bits - 1) / rate_bits;
+}
 
 size_t sbn_air_num_columns(const sbn_air_desc* air) { AirShape s; return air_shape(air, nullptr, s) ? s.ncols : 0; }
 size_t sbn_air_num_public_inputs(const sbn_air_desc* air) { AirShape s; return air_shape(air, nullptr, s) ? s.npi : 0; }

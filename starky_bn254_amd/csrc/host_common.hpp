@@ -101,11 +101,17 @@ static inline size_t exp_io_words(int kind) {
   }
 }
 static inline ExpShape exp_shape(const AirShape& a) { return ExpShape(exp_e(a.kind), (int)a.num_io); }
+// rate_bits: 1 (standard_fast_config) and 3 (plonky2's standard_recursion_config, the blowup of 8).  The code is general in
+// rate_bits >= 1; 2 is exercised through sbn_commit_values only and stays refused here (include/sbn.h).
 static inline bool config_supported(const sbn_config* c) {
-  return c && c->num_challenges == SBN_NCH && c->rate_bits == 1 && c->cap_height >= 1 && c->cap_height <= 8 &&
+  return c && c->num_challenges == SBN_NCH && (c->rate_bits == 1 || c->rate_bits == 3) && c->cap_height >= 1 && c->cap_height <= 8 &&
          c->fri_arity_bits >= 1 && c->fri_arity_bits <= 4 && c->num_query_rounds >= 1 && c->num_query_rounds <= 512 &&
          c->proof_of_work_bits <= 32 && c->fri_variant <= SBN_FRI_PLAIN;
 }
+// The largest LDE a prover or a device verifier is created for: 2^23 points (2^22 rows at rate_bits 1, 2^20 at rate_bits 3).
+static constexpr u32 SBN_MAX_LDE_BITS = 23;
+static inline bool height_supported(const sbn_config* c, u32 degree_bits) { return degree_bits >= 9 && degree_bits + c->rate_bits <= SBN_MAX_LDE_BITS; }
+static constexpr const char* HEIGHT_REFUSAL = "degree_bits out of range (9 <= degree_bits and degree_bits + rate_bits <= 23: the largest LDE is 2^23 points)";
 // sbn_config.fri_variant: 0 selects the default (the 0.1.x line: final polynomial times X)
 static inline u32 fri_times_x(const sbn_config& c) { return c.fri_variant == SBN_FRI_PLAIN ? 0u : 1u; }
 

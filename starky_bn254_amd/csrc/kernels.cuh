@@ -19,6 +19,13 @@ __global__ void shift_odd_table_kernel(u64* out, size_t n, const u64* __restrict
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (F(shift[i]) * F(tw[(i >> log_s) << log_s])).v;
 }
+// out[v][i] = shift[i] * w_m^((v * (i >> log_s)) << log_s), i < n, v = blockIdx.y: the input scales of the 2^r sub-passes of a
+// zero-aware first LDE pass (kernels_ntt.cuh ntt_lde_first_pass_kernel; tw = the full forward table w_m^e, e < m).
+__global__ void shift_za_table_kernel(u64* out, size_t n, const u64* __restrict__ shift, const u64* __restrict__ tw, u32 log_s) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t v = blockIdx.y;
+  if (i < n) out[v * n + i] = (F(shift[i]) * F(tw[(v * (i >> log_s)) << log_s])).v;
+}
 // v[i] *= base^i, for the small FRI layers.
 __global__ void scale_pow_kernel(u64* v, size_t n, u64 base) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -537,3 +537,58 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
 __global__ void ntt_fused512_inv_b_lde_a_kernel(NttFusedParams p);
 #endif
 
+// -------------------------------------------------------------------------------------------------------------
+// K1-za: the first pass of a coset LDE with a blowup of 2^r, r >= 2, at 2^16 / 2^17 rows, zero-aware.  The n coefficients are
+// rows 0 .. 255 of a (256 * 2^r) x S matrix (S = n / 256 tile columns) whose other rows are zero, and
+//   DFT_{256 K}(x)[K j + v] = DFT_256(x_r w_{256 K}^(v r))[j],   K = 2^r, v < K:
+// the pass is K independent 256-point passes on grid.z, each over the SAME 256 non-zero rows with its own input scale
+// pre2[v][i] = 7^i w_{256 K}^(v * row of i) (the coset shift and the pre-twist in one table, built at context creation), writing
+// the output rows K j + v.  No zero row is loaded or enters a butterfly: n loads and two DFT-16 rounds per n / 16 values and
+// sub-pass, where the generic radix-2 pass stages all 256 K rows through LDS in tiles of 4 columns (48 KiB hold no more).
+// NttPassParams as the fast pass reads them: split = r, pre2 = the table, n_in = n = its stride, in_sr = out_sr = S, in_st =
+// out_st = 1, twiddle w_m^(k * tile column) always, (columns, tiles, v) grid.  Lanes run over the tile column first: loads and
+// stores are 128-byte runs.  LDS: 16 x 272 words = 34,816 bytes, the layout of ntt_fast_pass_kernel<0> (conflict-free both ways).
+// -------------------------------------------------------------------------------------------------------------
+#ifdef SBN_NTT_KERNELS_HERE
+__global__ __launch_bounds__(256) void ntt_lde_first_pass_kernel(NttPassParams p, u32 kperm) {
+  extern __shared__ u64 lds[];
+  const size_t col = blockIdx.x;
+  const size_t t0 = (size_t)blockIdx.y << 4;
+  const u32 v = blockIdx.z;                               // which residue mod 2^r of the output rows
+  const u64* __restrict__ pre = p.pre2 + (size_t)v * p.n_in;
+  const u64* __restrict__ in = p.in + col * p.in_col_stride;
+  u64* out = p.out + col * p.out_col_stride;
+  const u32 t = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const size_t tg = t0 + t;
+  u64 x[16];
+  // ---- load the 256 non-zero rows r = g + 16 q, scaled for this sub-pass
+#pragma unroll
+  for (u32 q = 0; q < 16; q++) {
+    const size_t gi = (size_t)(g + 16 * q) * p.in_sr + tg;   // < 256 S = n
+    x[q] = nw::mul(in[gi], pre[gi]);
+  }
+  // ---- round 1: DFT-16 over q, twiddle by w_256^(g k1), exchange through LDS
+  nw::dft16_rho(x);
+#pragma unroll
+  for (u32 pidx = 0; pidx < 16; pidx++) {
+    const u32 m = __brev(pidx) >> 28, k1 = (kperm * m) & 15;
+    u64 w = x[pidx];
+    if (g && k1) w = nw::mul(w, tw_full(p.tw, p.tw_log, (u32)(g * k1), 8));
+    lds[k1 * 272 + g * 16 + t] = w;
+  }
+  __syncthreads();
+  // ---- round 2: this lane owns k1 = g
+#pragma unroll
+  for (u32 gp = 0; gp < 16; gp++) x[gp] = lds[g * 272 + gp * 16 + t];
+  nw::dft16_rho(x);
+#pragma unroll
+  for (u32 pidx = 0; pidx < 16; pidx++) {
+    const u32 m = __brev(pidx) >> 28, k2 = (kperm * m) & 15;
+    const u32 k = ((g + 16 * k2) << p.split) + v;           // output row of the whole pass, < 256 * 2^r
+    const u64 w = nw::mul(x[pidx], tw_full(p.tw, p.tw_log, (u32)(k * tg), p.log_n));   // k * tg < m <= 2^23
+    out[(size_t)k * p.out_sr + tg] = nw::canon(w);
+  }
+}
+#else
+__global__ void ntt_lde_first_pass_kernel(NttPassParams p, u32 kperm);
+#endif

@@ -6,6 +6,9 @@
 
 struct QuotientParams {
   const u64* lde; const u64* zlde; size_t m; u32 next_step;
+  // m = points evaluated.  Point j reads row j << row_log of matrices whose columns are lde_stride words apart: the quotient's
+  // domain is every 2^(rate_bits - 1)-th row of the LDE (row_log = 0 and lde_stride = m at rate_bits 1 and on the trace domain).
+  size_t lde_stride; u32 row_log;
   // Row sharding (all zero / equal to lde, zlde on one GPU): m = LOCAL point count, local point j is LDE point
   // (j << row_shift) | row_rho (tables xs / lag_* / zh_inv are indexed by the LDE point), its next row is local row
   // (j + next_step) mod m of lde_next / zlde_next.

@@ -56,6 +56,11 @@ static int ntt_columns(sbn_prover* P, const u64* in, size_t in_cs, u64* out, siz
   if (ncols == 0) return 0;                 // which: bit 0 = pass A (in -> tmp), bit 1 = pass B (tmp -> out)
   if (!st) st = P->stream;
   u32 log_n1 = (log_n + 1) / 2, log_n2 = log_n - log_n1;
+  // The coset LDE of an r-bit blowup at 2^16 / 2^17 rows (ntt_plan): rows n.. of the input are zero, so the transform is cut as
+  // (256 * 2^r) x (n / 256): the first pass then has exactly 256 non-zero rows, and a 2^r * 256-point DFT of 256 inputs is 2^r
+  // pre-twisted 256-point DFTs (kernels_ntt.cuh ntt_lde_first_pass_kernel on grid.z), none of which loads or butterflies a zero.
+  const bool za = !inverse && P->lde_za_log && log_n == P->lde_log && n_in == P->n && pre == P->d_shift && P->d_shift_za;
+  if (za) { log_n1 = 8 + P->lde_za_log; log_n2 = log_n - log_n1; }
   size_t n1 = (size_t)1 << log_n1, n2 = (size_t)1 << log_n2;
   NttPassParams a{};
   a.in = in; a.out = tmp; a.in_col_stride = in_cs; a.out_col_stride = tmp_cs;
@@ -92,7 +97,10 @@ static int ntt_columns(sbn_prover* P, const u64* in, size_t in_cs, u64* out, siz
     if (split_a) { pa.log_r = 9; pa.log_t = 4; pa.split = 1; pa.pre2 = P->d_shift_odd; }
     ga = dim3((unsigned)(n2 >> pa.log_t), (unsigned)nc, split_a ? 2u : 1u); gb = dim3((unsigned)(n1 >> pb.log_t), (unsigned)nc);
     la = ((size_t)1 << pa.log_r) * ((1u << pa.log_t) + 1) * 8; lb = ((size_t)1 << pb.log_r) * ((1u << pb.log_t) + 1) * 8;
-    if (which & 1) launch(pa, ga, la);
+    if (za) {   // pa as 2^r passes of 256 points: sub-pass v reads the rows scaled by d_shift_za[v] and writes the rows k * 2^r + v
+      pa.log_r = 8; pa.log_t = 4; pa.split = P->lde_za_log; pa.pre = nullptr; pa.pre2 = P->d_shift_za; pa.xcd_order = 1;
+      if (which & 1) hipLaunchKernelGGL(ntt_lde_first_pass_kernel, dim3((unsigned)nc, (unsigned)(n2 >> 4), 1u << P->lde_za_log), dim3(256), 16 * 272 * 8, st, pa, kperm);
+    } else if (which & 1) launch(pa, ga, la);
     if (which & 2) launch(pb, gb, lb);
   }
   HIPC(hipGetLastError());
@@ -112,13 +120,24 @@ static int ntt_fast_setup() {  // idempotent, so a race between prover threads i
   }
   return 0;
 }
-// The transform kernels of a table, a function of its size alone.  create_ctx and sbn_commit_values both pick them here, so the
-// parity tests of sbn_commit_values run the kernels the prover runs.  2^16 / 2^17 rows: the fused middle pass; 2^18 rows (the
-// 2^19-point LDE): its 512-point form, and the LDE's 1,024-point first pass as two 512-point halves -- both read d_shift_odd,
-// which the callers allocate exactly when ntt_fused512 is set.
+// The transform kernels of a table, a function of its height and rate_bits alone.  create_ctx and sbn_commit_values both pick them
+// here, so the parity tests of sbn_commit_values run the kernels the prover runs.  rate_bits 1 -- 2^16 / 2^17 rows: the fused middle
+// pass (its geometry is that of a 2n-point LDE); 2^18 rows (the 2^19-point LDE): its 512-point form, and the LDE's 1,024-point
+// first pass as two 512-point halves -- both read d_shift_odd, which the callers allocate exactly when ntt_fused512 is set.
+// rate_bits r >= 2 -- 2^16 / 2^17 rows: the LDE's first pass skips the zero rows (ntt_columns, lde_za_log), and reads the
+// pre-twisted coset tables d_shift_za, which the callers allocate and fill (lde_za_tables) exactly when lde_za_log is set.
 static void ntt_plan(sbn_prover* P) {
-  P->ntt_fused = P->degree_bits == 16 || P->degree_bits == 17;
+  const u32 rate = P->lde_log - P->degree_bits;
+  P->ntt_fused = rate == 1 && (P->degree_bits == 16 || P->degree_bits == 17);
   P->ntt_fused512 = P->degree_bits == 18 && P->lde_log == 19;
+  P->lde_za_log = (rate >= 2 && (P->degree_bits == 16 || P->degree_bits == 17)) ? rate : 0;
+}
+// d_shift_za[v][i] = 7^i w^(v * (i >> log_s)), v < 2^lde_za_log, i < n, with w the root of order 2^(8 + lde_za_log) and
+// log_s = lde_log - 8 - lde_za_log (the row of coefficient i in the zero-aware first pass is i >> log_s, below 256)
+static void lde_za_tables(sbn_prover* P) {
+  const u32 log_s = P->lde_log - 8 - P->lde_za_log;
+  hipLaunchKernelGGL(shift_za_table_kernel, dim3((unsigned)((P->n + 255) / 256), 1u << P->lde_za_log), dim3(256), 0, P->stream, P->d_shift_za, P->n, P->d_shift,
+                     P->d_tw_f, log_s);
 }
 
 // values [ncols][n] -> coefficients [ncols][n]
@@ -536,10 +555,11 @@ extern "C" int sbn_prover_create(const sbn_air_desc* air, const sbn_config* cfg,
 static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, sbn_prover** out) {
   if (!air || !cfg || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
-  if (!config_supported(cfg)) return fail(SBN_ERR_UNSUPPORTED, "unsupported StarkConfig (need num_challenges=2, rate_bits=1)");
+  if (!config_supported(cfg)) return fail(SBN_ERR_UNSUPPORTED, "unsupported StarkConfig (need num_challenges=2, rate_bits 1 or 3, cap_height 1..8, fri_arity_bits 1..4)");
+  if (comm && cfg->rate_bits != 1) return fail(SBN_ERR_UNSUPPORTED, "the split prover covers rate_bits = 1 only");
   AirShape as;
   if (!air_shape(air, cfg, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
-  if (degree_bits < 9 || degree_bits > 22) return fail(SBN_ERR_UNSUPPORTED, "degree_bits out of range");
+  if (!height_supported(cfg, degree_bits)) return fail(SBN_ERR_UNSUPPORTED, "%s", HEIGHT_REFUSAL);
   if (as.kind == SBN_AIR_FLAGS && (512 * (size_t)as.num_io) != ((size_t)1 << degree_bits)) return fail(SBN_ERR_BAD_ARG, "FlagStark needs 512*num_io rows");
   if (as.kind == SBN_AIR_FLAGS_U64 && (128 * (size_t)as.num_io) != ((size_t)1 << degree_bits)) return fail(SBN_ERR_BAD_ARG, "the u64 FlagStark needs 128*num_io rows");
   if (is_exp_air(as.kind)) {
@@ -599,7 +619,8 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   hipc(hipEventCreateWithFlags(&P->hash_done, hipEventDisableTiming), "hipEventCreate");
   for (auto& v : P->stage_ms) v = 0;
   if (rc) { sbn_prover_destroy(P); return rc; }
-  const size_t n = P->n, m = P->m, C = as.ncols, Z = as.nzs;
+  // qn: the quotient's domain, the coset of 2n points (quotient_degree_bits = 1) whatever the rate: LDE rows k * m / qn
+  const size_t n = P->n, m = P->m, qn = 2 * n, C = as.ncols, Z = as.nzs;
   if (comm && (C <= 4 || Z == 0)) { sbn_prover_destroy(P); return fail(SBN_ERR_UNSUPPORTED, "the split prover covers the wide tables (this one has %zu columns and %zu permutation Zs)", C, Z); }
   if (comm) {
     // one trace over comm->world GPUs: this rank keeps the coefficients of its own columns and the LDE ROWS of its Merkle
@@ -656,11 +677,12 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   acc(dmalloc(&P->d_tmp, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
   if (P->ntt_fused || P->ntt_fused512 || P->ntt_two_streams) acc(dmalloc(&P->d_tmp2, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
   if ((P->ntt_fused || P->ntt_fused512) && P->ntt_two_streams) acc(dmalloc(&P->d_tmp3, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
-  acc(dmalloc(&P->d_q, 2 * m, &P->dev_bytes)); acc(dmalloc(&P->d_qlde, 4 * m, &P->dev_bytes));
+  acc(dmalloc(&P->d_q, 2 * qn, &P->dev_bytes)); acc(dmalloc(&P->d_qlde, 4 * m, &P->dev_bytes));
   acc(tree_alloc(P->tree_q, m, cfg->cap_height, &P->dev_bytes));
   acc(dmalloc(&P->d_tw_f, m, &P->dev_bytes)); acc(dmalloc(&P->d_tw_i, m, &P->dev_bytes)); acc(dmalloc(&P->d_shift, m, &P->dev_bytes)); acc(dmalloc(&P->d_shift_inv, m, &P->dev_bytes));
   if (P->ntt_fused512) acc(dmalloc(&P->d_shift_odd, n, &P->dev_bytes));   // (ntt_plan)
-  acc(dmalloc(&P->d_xs, m, &P->dev_bytes)); acc(dmalloc(&P->d_lag_first, m, &P->dev_bytes)); acc(dmalloc(&P->d_lag_last, m, &P->dev_bytes));
+  if (P->lde_za_log) acc(dmalloc(&P->d_shift_za, n << P->lde_za_log, &P->dev_bytes));   // (ntt_plan)
+  acc(dmalloc(&P->d_xs, qn, &P->dev_bytes)); acc(dmalloc(&P->d_lag_first, qn, &P->dev_bytes)); acc(dmalloc(&P->d_lag_last, qn, &P->dev_bytes));   // per quotient point
   P->apow_n = apow_len(as.nconstraints, as.nzs);
   acc(dmalloc(&P->d_apow, (size_t)SBN_NCH * P->apow_n, &P->dev_bytes));
   acc(dmalloc(&P->d_zpow, 4 * n, &P->dev_bytes)); acc(dmalloc(&P->d_open, (C + Z + 4) * 4, &P->dev_bytes));
@@ -702,8 +724,9 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_tw_i, m, f_inv(w).v);
   hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_shift, m, (u64)GL_GEN);
   hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_shift_inv, m, f_inv(F(GL_GEN)).v);
-  hipLaunchKernelGGL(domain_tables_kernel, blocks(m), dim3(256), 0, P->stream, P->d_xs, P->d_lag_first, P->d_lag_last, m, P->lde_log, degree_bits);
+  hipLaunchKernelGGL(domain_tables_kernel, blocks(qn), dim3(256), 0, P->stream, P->d_xs, P->d_lag_first, P->d_lag_last, qn, degree_bits + 1, degree_bits);
   if (P->d_shift_odd) hipLaunchKernelGGL(shift_odd_table_kernel, blocks(n), dim3(256), 0, P->stream, P->d_shift_odd, n, P->d_shift, P->d_tw_f, 9u);
+  if (P->d_shift_za) lde_za_tables(P);
   // permutation pairs
   {
     std::vector<PairCols> pairs(Z);
@@ -738,7 +761,7 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   (void)hipSetDevice(P->device);
   u64* bufs[] = {P->d_trace, P->d_coef, P->d_lde, P->d_tmp, P->d_tmp2, P->d_tmp3, P->d_zval, P->d_zcoef, P->d_zlde, P->d_q, P->d_qlde, P->tree_t.d, P->tree_z.d,
                  P->tree_q.d, P->d_tw_f, P->d_tw_i, P->d_shift, P->d_shift_inv, P->d_xs, P->d_lag_first, P->d_lag_last, P->d_apow, P->d_zpow,
-                 P->d_open, P->d_part, P->d_w, P->d_fa, P->d_fcoef, P->d_fcoef2, P->d_pow, P->d_qbuf, P->d_shift_odd};
+                 P->d_open, P->d_part, P->d_w, P->d_fa, P->d_fcoef, P->d_fcoef2, P->d_pow, P->d_qbuf, P->d_shift_odd, P->d_shift_za};
   for (u64* b : bufs) if (b) (void)hipFree(b);
   for (u64* b : P->fri_vals) if (b) (void)hipFree(b);
   for (auto& t : P->fri_trees) if (t.d) (void)hipFree(t.d);
@@ -929,7 +952,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   if (!up && !P->loaded && !(P->sp && P->sp->comm.world > 1)) return fail(SBN_ERR_BAD_ARG, "no trace loaded");   // (split: agreed with the other ranks below)
   HIPC(hipSetDevice(P->device));
   hipStream_t st = P->stream;
-  const size_t n = P->n, m = P->m, C = P->air.ncols, Z = P->air.nzs;
+  const size_t n = P->n, m = P->m, qn = 2 * n, C = P->air.ncols, Z = P->air.nzs;   // qn: points of the quotient's domain
   const sbn_config& cfg = P->cfg;
   const size_t capw = ((size_t)1 << cfg.cap_height) * 4;
   auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
@@ -996,12 +1019,16 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   if ((rc = upload_alpha_tables(P, alphas))) return rc;
   {
     QuotientParams qp{};
-    qp.lde = P->d_lde; qp.zlde = P->d_zlde; qp.m = m; qp.next_step = 2;  // 2^quotient_degree_bits
+    // starky evaluates the quotient on the coset of qn = 2n points (quotient_degree_bits = 1): quotient point k is LDE row
+    // k << (rate_bits - 1), its next row quotient point k + 2.  The LDE stays in natural row order, so this is a strided view
+    // (the section on rate_bits, has the byte counts against a dense copy); at rate_bits 1 the stride is one row.
+    qp.lde = P->d_lde; qp.zlde = P->d_zlde; qp.m = qn; qp.next_step = 2;  // 2^quotient_degree_bits
+    qp.lde_stride = m; qp.row_log = cfg.rate_bits - 1;
     qp.lde_next = qp.lde; qp.zlde_next = qp.zlde; qp.row_shift = 0; qp.row_rho = 0;
     if (S) {
       // this rank's LDE points j * R + rho; the row two LDE points on is local row j + 1 (two ranks) or sits at local row j
       // of the second plane (four ranks and more)
-      qp.lde = S->lde_l; qp.zlde = S->zlde_l; qp.m = S->ml; qp.row_shift = S->log_r; qp.row_rho = S->rho;
+      qp.lde = S->lde_l; qp.zlde = S->zlde_l; qp.m = S->ml; qp.lde_stride = S->ml; qp.row_shift = S->log_r; qp.row_rho = S->rho;   // (rate_bits 1: create_ctx)
       qp.lde_next = S->planes == 2 ? S->lde_n : S->lde_l; qp.zlde_next = S->planes == 2 ? S->zlde_n : S->zlde_l;
       qp.next_step = S->comm.world == 1 ? 2 : (S->comm.world == 2 ? 1 : 0);
     }
@@ -1012,7 +1039,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     quotient_segments(P, alphas, qp);
     qp.gamma0 = gamma0.v; qp.gamma1 = gamma1.v; qp.qout = P->d_q;
     if (S) qp.qout = (u64*)S->comm.send_buf;   // [2][ml]: all-gathered below
-    qp.part = P->d_part;   // QSEG x SBN_NCH planes of m words (the FRI combine's scratch, idle here)
+    qp.part = P->d_part;   // QSEG x SBN_NCH planes of qn words = 16 n of its 64 n (the FRI combine's scratch, idle here)
     const size_t qblocks = (qp.m + 255) / 256;
 #ifdef SBN_DIAG   // diagnostic builds only (make CXXFLAGS+=-DSBN_DIAG): time single segments; the proof is invalid unless the mask is 15
     { const char* e = std::getenv("SBN_DIAG_QUOTIENT_SEGMASK"); if (e) qp.seg_mask = (u32)atoi(e) & 0xfu; }
@@ -1035,9 +1062,9 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     } else if (Z > 4) { if ((rc = absorb_times(P, Z, EX_Z_ABSORB_MS))) return rc; }   // behind the quotient kernel
   }
   HIPC(hipEventRecord(P->ev[ST_QUOTIENT_COMMIT], st));
-  // coset_ifft(7) of the 2 quotient value vectors (size m), in place via tmp; the result viewed as
+  // coset_ifft(7) of the 2 quotient value vectors (size qn = 2n), in place via tmp; the result viewed as
   // [4][n] is exactly quotient_poly.chunks(degree) in the order q0_lo, q0_hi, q1_lo, q1_hi.
-  if ((rc = ntt_columns(P, P->d_q, m, P->d_q, m, P->d_tmp, m, 2, P->lde_log, true, m, nullptr, P->d_shift_inv, host_inv_pow2(P->lde_log)))) return rc;
+  if ((rc = ntt_columns(P, P->d_q, qn, P->d_q, qn, P->d_tmp, m, 2, P->degree_bits + 1, true, qn, nullptr, P->d_shift_inv, host_inv_pow2(P->degree_bits + 1)))) return rc;
   if ((rc = lde_coeffs(P, P->d_q, P->d_qlde, 4))) return rc;
   if ((rc = tree_from_matrix(P, P->tree_q, P->d_qlde, 4))) return rc;
   HIPC(hipEventRecord(P->ev[ST_OPENINGS], st));
@@ -1380,14 +1407,16 @@ extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace,
 extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint64_t* cap_out,
                                  uint64_t* coeffs_out, uint64_t* lde_out) {
   if (!cols || !cap_out || ncols == 0) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (rate_bits != 1 || n < 512 || (n & (n - 1))) return fail(SBN_ERR_UNSUPPORTED, "need rate_bits=1 and n a power of two >= 512");
+  if (rate_bits < 1 || rate_bits > 3 || n < 512 || (n & (n - 1))) return fail(SBN_ERR_UNSUPPORTED, "need rate_bits 1..3 and n a power of two >= 512");
   u32 lg = 0; while (((size_t)1 << lg) < n) lg++;
-  // the range of config_supported: tree_alloc computes the level count lg + 1 - cap_height unsigned, and lg + 1 >= 10
+  if (lg + rate_bits > SBN_MAX_LDE_BITS) return fail(SBN_ERR_UNSUPPORTED, "n << rate_bits exceeds 2^%u points", SBN_MAX_LDE_BITS);
+  // the range of config_supported: tree_alloc computes the level count lg + rate_bits - cap_height unsigned, and lg + rate_bits >= 10
   if (cap_height < 1 || cap_height > 8) return fail(SBN_ERR_UNSUPPORTED, "cap_height must be 1..8");
   // a throw-away prover-like context built on the G1_OP shape would waste memory; build a minimal one
   sbn_prover P{};
   sbn_standard_fast_config(&P.cfg); P.cfg.cap_height = cap_height;
-  P.degree_bits = lg; P.lde_log = lg + 1; P.n = n; P.m = 2 * n; P.ntt_chunk = 64; P.device = g_device;
+  P.cfg.rate_bits = rate_bits;
+  P.degree_bits = lg; P.lde_log = lg + rate_bits; P.n = n; P.m = n << rate_bits; P.ntt_chunk = 64; P.device = g_device;
   if (int rc = use_current_device("no CPU fallback")) return rc;
   { int rc0 = ntt_fast_setup(); if (rc0) return rc0; }
   { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
@@ -1398,6 +1427,7 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
   rc |= dmalloc(&d_vals, ncols * n); rc |= dmalloc(&d_coef, ncols * n); rc |= dmalloc(&d_lde, ncols * P.m); rc |= dmalloc(&P.d_tmp, 64 * P.m);
   if (P.ntt_fused || P.ntt_fused512) rc |= dmalloc(&P.d_tmp2, 64 * P.m);
   if (P.ntt_fused512) rc |= dmalloc(&P.d_shift_odd, n);
+  if (P.lde_za_log) rc |= dmalloc(&P.d_shift_za, n << P.lde_za_log);
   rc |= dmalloc(&P.d_tw_f, P.m); rc |= dmalloc(&P.d_tw_i, P.m); rc |= dmalloc(&P.d_shift, P.m);
   rc |= tree_alloc(P.tree_t, P.m, cap_height);
   if (!rc) {
@@ -1407,6 +1437,7 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
     hipLaunchKernelGGL(pow_table_kernel, blocks(P.m), dim3(256), 0, P.stream, P.d_tw_i, P.m, f_inv(w).v);
     hipLaunchKernelGGL(pow_table_kernel, blocks(P.m), dim3(256), 0, P.stream, P.d_shift, P.m, (u64)GL_GEN);
     if (P.d_shift_odd) hipLaunchKernelGGL(shift_odd_table_kernel, blocks(n), dim3(256), 0, P.stream, P.d_shift_odd, n, P.d_shift, P.d_tw_f, 9u);
+    if (P.d_shift_za) lde_za_tables(&P);
     if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess) rc = fail(SBN_ERR_HIP, "H2D failed");
   }
   for (size_t c0 = 0; !rc && c0 < ncols; c0 += P.ntt_chunk) rc = intt_lde_cols(&P, d_vals + c0 * n, d_coef + c0 * n, d_lde + c0 * P.m, std::min(P.ntt_chunk, ncols - c0));
@@ -1425,7 +1456,7 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
   if (!rc) memcpy(cap_out, cap.data(), cap.size() * sizeof(u64));
   if (!rc && coeffs_out && hipMemcpy(coeffs_out, d_coef, ncols * n * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBN_ERR_HIP, "D2H failed");
   if (!rc && lde_out && hipMemcpy(lde_out, d_lde, ncols * P.m * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBN_ERR_HIP, "D2H failed");
-  for (u64* b : {d_vals, d_coef, d_lde, P.d_tmp, P.d_tmp2, P.d_shift_odd, P.d_tw_f, P.d_tw_i, P.d_shift, P.tree_t.d, P.d_sponge}) if (b) (void)hipFree(b);
+  for (u64* b : {d_vals, d_coef, d_lde, P.d_tmp, P.d_tmp2, P.d_shift_odd, P.d_shift_za, P.d_tw_f, P.d_tw_i, P.d_shift, P.tree_t.d, P.d_sponge}) if (b) (void)hipFree(b);
   (void)hipStreamDestroy(P.stream);
   return rc;
 }
@@ -1525,9 +1556,9 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
   const char* chain = P->chain_mode == 0 && tracegen_host_chains_vectorized() ? "host_pool_ifma_x8" : CH[P->chain_mode < 0 || P->chain_mode > 2 ? 0 : P->chain_mode];
   char buf[1024];
   snprintf(buf, sizeof buf,
-           "abi=%d device=%d ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d "
+           "abi=%d device=%d dev_bytes=%zu ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d ntt_lde_zero_aware=%d "
            "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d ignored=[%s]",
-           SBN_ABI_VERSION, P->device, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0,
+           SBN_ABI_VERSION, P->device, P->dev_bytes, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0, P->d_shift_za ? 1 : 0,
            chain, tracegen_host_threads(), (int)s.fq12_host_chain,
            (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, s.ignored.c_str());
   snprintf(out, cap, "%s", buf);
@@ -1542,6 +1573,7 @@ extern "C" int sbn_split_exchange_bytes(const sbn_air_desc* air, const sbn_confi
   if (!air || !cfg || !send_bytes || !recv_bytes || world == 0) return fail(SBN_ERR_BAD_ARG, "null argument");
   AirShape as;
   if (!air_shape(air, cfg, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
+  if (cfg->rate_bits != 1) return fail(SBN_ERR_UNSUPPORTED, "the split prover covers rate_bits = 1 only");
   size_t sw;
   return split_sizes(as, degree_bits, cfg->rate_bits, world, SPLIT_BLOCK, send_bytes, recv_bytes, &sw, nullptr);
 }

@@ -86,7 +86,9 @@ struct sbn_prover {
   // tables
   u64 *d_tw_f = nullptr, *d_tw_i = nullptr, *d_shift = nullptr, *d_shift_inv = nullptr;
   u64 *d_shift_odd = nullptr;   // 2^19-point LDE (1,024 x 512): 7^i w_1024^(i >> 9), the input scale of the odd half of its split first pass
-  u64 *d_xs = nullptr, *d_lag_first = nullptr, *d_lag_last = nullptr;
+  u32 lde_za_log = 0;           // rate_bits >= 2 at 2^16 / 2^17 rows: the LDE's first pass as 2^lde_za_log zero-aware 256-point passes (= rate_bits; 0: off)
+  u64 *d_shift_za = nullptr;    // its input scales [2^lde_za_log][n]: 7^i w^(v * row of i), w of order 256 * 2^lde_za_log (prover.hip lde_za_tables)
+  u64 *d_xs = nullptr, *d_lag_first = nullptr, *d_lag_last = nullptr;   // per QUOTIENT point: the coset of 2n points
   u64 *d_apow = nullptr;  // [2][apow_n]
   size_t apow_n = 0;
   void* d_pic = nullptr;  // ExpPiConsts<F>
@@ -94,7 +96,7 @@ struct sbn_prover {
   // openings / FRI
   u64 *d_zpow = nullptr;        // 4 planes [n]: z^i (a,b), (g z)^i (a,b)
   u64 *d_open = nullptr;        // [(ncols + nzs + 4)][4]
-  u64 *d_part = nullptr;        // 2 planes [groups][n]
+  u64 *d_part = nullptr;        // 2 planes [groups][n] = 64 n words; also the quotient's 8 planes of 2n and the trace check's of n
   u64 *d_w = nullptr;           // group weights
   u64 *d_fa = nullptr, *d_fb = nullptr;    // F0 / F1 scratch planes [n] each (a,b) x2
   u64 *d_fcoef = nullptr;       // final poly coefficient planes [2][m]

@@ -4,9 +4,9 @@
 
 // =================================================================================================
 // K5  constraint / quotient evaluation (starky prover.rs `compute_quotient_polys`; P3)
-// One thread per LDE point i; local row = i, next row = (i + 2^quotient_degree_bits) mod M.
-// Lanes are consecutive points, so every column access is a coalesced 512-byte wave segment and the
-// "next" access re-hits the same lines.  Output: quotient values acc_j / Z_H(x_i) for j < 2.
+// One thread per point i of the quotient's domain (2n points); local row = i, next row = (i + 2^quotient_degree_bits) mod 2n,
+// each at LDE row (i << row_log).  At rate_bits 1 lanes are consecutive rows, so every column access is a coalesced 512-byte
+// wave segment and the "next" access re-hits the same lines; at rate_bits r a wave's segment is 2^(r-1) times as long.  Output: quotient values acc_j / Z_H(x_i) for j < 2.
 // Algorithmic bytes: 8*M*(C + Zc) read once, 16*M written.
 // =================================================================================================
 // `base` holds the local rows, `nbase` the next rows (the same matrix on one GPU; in the oversized-trace split a rank
@@ -41,8 +41,8 @@ __global__ __launch_bounds__(256, 2) void quotient_kernel(QuotientParams p, cons
   cs.z_last = F(p.xs[ig]) - F(p.last);
   cs.l_first = F(p.lag_first[ig]);
   cs.l_last = F(p.lag_last[ig]);
-  DevRow row{p.lde, p.lde_next, p.m, i, inext};
-  DevZRow zrow{p.zlde, p.zlde_next, p.m, i, inext};
+  DevRow row{p.lde, p.lde_next, p.lde_stride, i << p.row_log, inext << p.row_log};
+  DevZRow zrow{p.zlde, p.zlde_next, p.lde_stride, i << p.row_log, inext << p.row_log};
   if (KIND == 1) {
     if (PART == 0) g1op_eval(cs, row);
     else if (PART == 2) {

@@ -122,7 +122,7 @@ extern "C" int sbn_prover_check_trace(sbn_prover* P, uint64_t seed, sbn_trace_re
   HIPC(hipGetLastError());
   if ((rc = upload_alpha_tables(P, alphas))) return rc;
   QuotientParams qp{};
-  qp.lde = qp.lde_next = P->d_trace; qp.zlde = qp.zlde_next = P->d_zval; qp.m = n; qp.next_step = 1;
+  qp.lde = qp.lde_next = P->d_trace; qp.zlde = qp.zlde_next = P->d_zval; qp.m = n; qp.lde_stride = n; qp.row_log = 0; qp.next_step = 1;
   qp.row_shift = 0; qp.row_rho = 0;
   qp.xs = xs; qp.lag_first = lag_first; qp.lag_last = lag_last;
   qp.last = f_inv(f_root_of_unity(P->degree_bits)).v;

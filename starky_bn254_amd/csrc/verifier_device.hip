@@ -105,7 +105,7 @@ int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t
   AirShape as;
   if (!air_shape(air, cfg, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
   if (max_batch == 0 || max_batch > VERIFY_MAX_BATCH) return fail(SBN_ERR_BAD_ARG, "bad arguments (1 <= max_batch <= %u)", VERIFY_MAX_BATCH);
-  if (degree_bits < 9 || degree_bits > 22) return fail(SBN_ERR_UNSUPPORTED, "degree_bits out of range");
+  if (!height_supported(cfg, degree_bits)) return fail(SBN_ERR_UNSUPPORTED, "%s", HEIGHT_REFUSAL);
   if ((is_exp_air(as.kind) || as.kind == SBN_AIR_FLAGS || as.kind == SBN_AIR_FLAGS_U64) && (exp_rows_per_instance(as.kind) * as.num_io) != ((size_t)1 << degree_bits))
     return fail(SBN_ERR_BAD_ARG, "degree_bits does not match num_io");
   VerifyLayout L;
