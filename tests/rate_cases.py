@@ -30,6 +30,8 @@ def table(S, O, name):
         return S.G1Stark(), O.AIR_G1_OP, 0, O.g1op_trace(O.g1op_inputs(rows, 0)[0])
     if name == "modular":
         return S.ModularStark(), O.AIR_MODULAR, 0, O.modular_trace(O.modular_inputs(512, 7)[0])
+    if name == "fq12mul":   # the widest single-operation table (9722 columns, 5328 Zs), the inputs of the rate-1 parity test
+        return S.Fq12Stark(), O.AIR_FQ12_MUL, 0, O.fq12mul_trace(O.fq12mul_inputs(512, 7)[0])
     if name.startswith("lookup"):
         rows = 1 << int(name[6:] or 9)
         return S.LookupStark(), O.AIR_LOOKUP, 0, O.lookup_trace(*O.lookup_inputs(rows, 9))

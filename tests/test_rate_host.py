@@ -64,6 +64,58 @@ def test_a_proof_under_the_other_rate_is_a_shape_refusal(S, O, R, proofs, g1op_c
     assert R.verify(kind, num_io, r3, 1, case[0])[0] != 0 and R.verify(kind, num_io, r1, 3, case[0])[0] != 0
 
 
+# ---- tests/golden/rate3_digests.json and its generator -------------------------------------------------------------------------
+EXP_DIGESTS = {"g1exp": 128, "fqexp": 128, "fq12expu64": 16, "g2exp": 128, "fq12exp": 16}   # name -> num_io
+LOOKUP_DIGESTS = {"lookup18": 18, "lookup19": 19, "lookup20": 20}                            # name -> degree_bits
+
+
+def is_sha256(v):
+    return isinstance(v, str) and len(v) == 64 and set(v) <= set("0123456789abcdef")
+
+
+def test_every_rate_3_digest_entry_has_its_fields(golden):
+    g = golden["rate3_digests"]
+    assert (g["rate_bits"], tuple(g["config"])) == (3, RC.ROWS[0])
+    assert set(g["cases"]) == set(EXP_DIGESTS) | set(LOOKUP_DIGESTS)
+    for name, num_io in EXP_DIGESTS.items():
+        e = g["cases"][name]
+        assert set(e) == {"num_io", "seed", "proof_words", "proof_sha256", "public_inputs_sha256"}, name
+        assert e["num_io"] == num_io and is_sha256(e["proof_sha256"]) and is_sha256(e["public_inputs_sha256"]), name
+    for name, bits in LOOKUP_DIGESTS.items():
+        e = g["cases"][name]
+        assert set(e) == {"degree_bits", "seed", "proof_words", "proof_sha256"}, name
+        assert (e["degree_bits"], e["seed"]) == (bits, 200 + bits) and is_sha256(e["proof_sha256"]), name
+    for name, e in g["cases"].items():
+        assert isinstance(e["proof_words"], int) and e["proof_words"] > 12, name
+    # four columns, two Zs, two quotient columns, no public inputs: a height only adds words to the Merkle paths and the FRI layers
+    words = [g["cases"][n]["proof_words"] for n in LOOKUP_DIGESTS]
+    assert words == sorted(words) and len(set(words)) == 3
+    # the entries of the change that brought rate_bits 3 are the ones committed then
+    assert g["cases"]["g1exp"]["proof_sha256"] == "0cc626c1219e6ee5ab63fd0af7c34215f11d98a8459428ed92427c76013c4427"
+    assert g["cases"]["fqexp"]["proof_sha256"] == "5931d0e6949b503f32ae62caf2cd8b6e89b86d070a2b9d3caf3725b382a59d72"
+    assert g["cases"]["fq12expu64"]["proof_sha256"] == "dfb555ea3607aa551f6cf18848b539f4d6d69150f7f2774144d9962b56083317"
+
+
+def test_the_generator_reproduces_one_entry_alone(golden, tmp_path):
+    """make_rate3_digests.py --only fq12expu64 (the smallest table of the file: 2^11 rows): that entry comes out as committed, every
+    other entry is copied, and the committed file is not written."""
+    import importlib.util
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_rate3_digests.py")
+    spec = importlib.util.spec_from_file_location("make_rate3_digests", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert set(gen.NAMES) == set(EXP_DIGESTS) | set(LOOKUP_DIGESTS)
+    before = os.stat(gen.JSON).st_mtime_ns
+    out = tmp_path / "rate3_digests.json"
+    gen.main(["--only", "fq12expu64", "--out", str(out)])
+    assert json.load(open(out)) == golden["rate3_digests"]
+    assert open(out).read() == open(gen.JSON).read() and os.stat(gen.JSON).st_mtime_ns == before
+    with pytest.raises(SystemExit):
+        gen.main(["--only", "no_such_case", "--out", str(out)])
+
+
 def test_config_helpers(S):
     std, c1 = S.StarkConfig(), S.StarkConfig.for_rate(1)
     for name, _ in S.api._Config._fields_:
