@@ -551,6 +551,15 @@ def msm_instances(stark, terms, start):
     return ios, final
 
 
+def _unit_public_inputs(stark, public_inputs_per_unit):
+    """(pis, ptrs, n): the public inputs of every unit as flat uint64 arrays, their addresses as the C array the *_check calls take,
+    and the unit count.  ptrs points into pis: keep pis referenced across the C call."""
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
+    if any(p.shape[0] != stark.num_public_inputs for p in pis):
+        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
+    return pis, (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis]), len(pis)
+
+
 def msm_check_links(stark, public_inputs_per_unit, count, start, terms=None):
     """The link check of a long chained list (sbn_msm_check_links) on the public inputs of its unit proofs: the units are one
     chained list from `start`, padded as msm_instances pads, and (with `terms`) its x and exponents are the caller's.  Returns the
@@ -564,12 +573,9 @@ def msm_check_links(stark, public_inputs_per_unit, count, start, terms=None):
         terms = np.ascontiguousarray(terms, dtype=np.uint32)
         if terms.shape != (count, xw + ew):
             raise SbnError(-1, f"terms must be [count][{xw + ew}] u32")
-    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
-    if any(p.shape[0] != stark.num_public_inputs for p in pis):
-        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
-    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
     final = np.zeros(xw, dtype=np.uint32)
-    _check(lib().sbn_msm_check_links(stark.kind, stark.num_io, ptrs, len(pis), count, _ptr(terms), _ptr(start), _ptr(final)))
+    _check(lib().sbn_msm_check_links(stark.kind, stark.num_io, ptrs, n, count, _ptr(terms), _ptr(start), _ptr(final)))
     return final
 
 
@@ -636,13 +642,10 @@ def scalar_mul_check(stark, public_inputs_per_unit, points, scalars, offset=None
     verify_scalar_muls does both."""
     points, scalars, offset, w = _scalar_mul_args(stark, points, scalars, offset)
     count = points.shape[0]
-    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
-    if any(p.shape[0] != stark.num_public_inputs for p in pis):
-        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
-    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
     products = np.zeros((count, w), dtype=np.uint32)
     infinity = np.zeros(count, dtype=np.uint8)
-    _check(lib().sbn_scalar_mul_check(stark.kind, stark.num_io, ptrs, len(pis), count, _ptr(points), _ptr(scalars), scalars.shape[0],
+    _check(lib().sbn_scalar_mul_check(stark.kind, stark.num_io, ptrs, n, count, _ptr(points), _ptr(scalars), scalars.shape[0],
                                       _ptr(offset), _ptr(products), _ptr(infinity)))
     return products, infinity
 
@@ -656,13 +659,10 @@ def mul_by_cofactor_check(stark, public_inputs_per_unit, points):
     if points.ndim != 2 or points.shape[1] != 32:
         raise SbnError(-1, "points must be [count][32] u32")
     count = points.shape[0]
-    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
-    if any(p.shape[0] != stark.num_public_inputs for p in pis):
-        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
-    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
     cleared = np.zeros((count, 32), dtype=np.uint32)
     infinity = np.zeros(count, dtype=np.uint8)
-    _check(lib().sbn_mul_by_cofactor_check(stark.num_io, ptrs, len(pis), count, _ptr(points), _ptr(cleared), _ptr(infinity)))
+    _check(lib().sbn_mul_by_cofactor_check(stark.num_io, ptrs, n, count, _ptr(points), _ptr(cleared), _ptr(infinity)))
     return cleared, infinity
 
 
@@ -723,12 +723,9 @@ def msm_batch_check(stark, public_inputs_per_unit, lengths, starts=None, terms=N
         _, _, starts, _, _, curve = _msm_batch_args(stark, np.zeros((1, xw + ew), dtype=np.uint32), lengths[:0], starts)
     else:
         terms, _, starts, _, _, curve = _msm_batch_args(stark, terms, lengths, starts)
-    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
-    if any(p.shape[0] != stark.num_public_inputs for p in pis):
-        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
-    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
     finals, sums, infinity = _msm_batch_outputs(len(lengths), xw, curve)
-    _check(lib().sbn_msm_batch_check(stark.kind, stark.num_io, ptrs, len(pis), _ptr(lengths), len(lengths), _ptr(terms), _ptr(starts),
+    _check(lib().sbn_msm_batch_check(stark.kind, stark.num_io, ptrs, n, _ptr(lengths), len(lengths), _ptr(terms), _ptr(starts),
                                      starts.shape[0] if starts is not None else 1, _ptr(finals), _ptr(sums), _ptr(infinity)))
     return finals, sums, infinity
 
@@ -807,12 +804,9 @@ def power_check(stark, public_inputs_per_unit, bases, exps, depth=1):
     naming the first instance and field that breaks.  Verifies NO proof: verify_powers does both."""
     bases, exps, depth, w, ew = _power_args(stark, bases, exps, depth)
     count = bases.shape[0]
-    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in public_inputs_per_unit]
-    if any(p.shape[0] != stark.num_public_inputs for p in pis):
-        raise SbnError(-1, f"every unit has {stark.num_public_inputs} public inputs")
-    ptrs = (C.c_void_p * max(len(pis), 1))(*[p.ctypes.data for p in pis])
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
     powers = np.zeros((count, depth, w), dtype=np.uint32)
-    _check(lib().sbn_power_check(stark.kind, stark.num_io, ptrs, len(pis), count, depth, _ptr(bases), _ptr(exps), exps.shape[0], _ptr(powers)))
+    _check(lib().sbn_power_check(stark.kind, stark.num_io, ptrs, n, count, depth, _ptr(bases), _ptr(exps), exps.shape[0], _ptr(powers)))
     return powers
 
 
@@ -1302,39 +1296,45 @@ class BatchProver:
         self._h = C.c_void_p()
         _check(lib().sbn_batch_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, inflight, C.byref(self._h)))
 
+    def _unit_buffers(self, count, words):
+        """(ios, out) for `count` instances of `words` u32 each cut into units: the (units, num_io, words) list buffer and the
+        array of proof handles (never empty)."""
+        units = msm_num_units(count, self.stark.num_io)
+        return np.zeros((units, self.stark.num_io, words), dtype=np.uint32), (C.c_void_p * max(units, 1))()
+
+    @staticmethod
+    def _proofs(out, units):
+        return [_take_proof(C.c_void_p(h)) for h in out[:units]]
+
     def prove_ios(self, ios_units):
         """ios_units: (count, num_io, words_per_instance) uint32 -> list of Proof, in unit order."""
         ios = np.ascontiguousarray(ios_units, dtype=np.uint32)
         count, num_io, w = ios.shape
         out = (C.c_void_p * count)()
         _check(lib().sbn_batch_prover_prove_ios(self._h, _ptr(ios), num_io * w, num_io, count, out))
-        return [_take_proof(C.c_void_p(h)) for h in out]
+        return self._proofs(out, count)
 
     def prove_msm(self, terms, start):
         """A chained list of any length (terms, start as chain_instances) proved as units of the table, the last one padded
         (sbn_batch_prover_prove_msm).  Returns (proofs, final, ios): the unit proofs in order, the last output in the word shape
         of start, and the list as msm_instances gives it."""
         terms, start, xw, ew = _chain_args(self.stark, terms, start)
-        units = msm_num_units(terms.shape[0], self.stark.num_io)
-        ios = np.zeros((units, self.stark.num_io, 2 * xw + ew), dtype=np.uint32)
+        ios, out = self._unit_buffers(terms.shape[0], 2 * xw + ew)
         final = np.zeros(xw, dtype=np.uint32)
-        out = (C.c_void_p * max(units, 1))()
         _check(lib().sbn_batch_prover_prove_msm(self._h, _ptr(terms), terms.shape[0], _ptr(start), out, _ptr(final), _ptr(ios)))
-        return [_take_proof(C.c_void_p(h)) for h in out[:units]], final, ios
+        return self._proofs(out, len(ios)), final, ios
 
     def prove_scalar_muls(self, points, scalars, offset=None):
         """Independent scalar multiplications of any count (arguments as scalar_mul_instances) proved as units of the table, the
         last one padded (sbn_batch_prover_prove_scalar_muls).  Returns (proofs, products, infinity, ios)."""
         points, scalars, offset, w = _scalar_mul_args(self.stark, points, scalars, offset)
         count = points.shape[0]
-        units = msm_num_units(count, self.stark.num_io)
-        ios = np.zeros((units, self.stark.num_io, 2 * w + 8), dtype=np.uint32)
+        ios, out = self._unit_buffers(count, 2 * w + 8)
         products = np.zeros((count, w), dtype=np.uint32)
         infinity = np.zeros(count, dtype=np.uint8)
-        out = (C.c_void_p * max(units, 1))()
         _check(lib().sbn_batch_prover_prove_scalar_muls(self._h, _ptr(points), _ptr(scalars), scalars.shape[0], count, _ptr(offset), out,
                                                         _ptr(products), _ptr(infinity), _ptr(ios)))
-        return [_take_proof(C.c_void_p(h)) for h in out[:units]], products, infinity, ios
+        return self._proofs(out, len(ios)), products, infinity, ios
 
     def prove_mul_by_cofactor(self, points):
         """Cofactor clearing of twist points (g2/circuit.rs:335-367; sbn_batch_prover_prove_mul_by_cofactor): (2p - r) x for every
@@ -1343,37 +1343,31 @@ class BatchProver:
         if points.ndim != 2 or points.shape[1] != 32:
             raise SbnError(-1, "points must be [count][32] u32")
         count = points.shape[0]
-        units = msm_num_units(count, self.stark.num_io)
-        ios = np.zeros((units, self.stark.num_io, 72), dtype=np.uint32)
+        ios, out = self._unit_buffers(count, 72)
         cleared = np.zeros((count, 32), dtype=np.uint32)
         infinity = np.zeros(count, dtype=np.uint8)
-        out = (C.c_void_p * max(units, 1))()
         _check(lib().sbn_batch_prover_prove_mul_by_cofactor(self._h, _ptr(points), count, out, _ptr(cleared), _ptr(infinity), _ptr(ios)))
-        return [_take_proof(C.c_void_p(h)) for h in out[:units]], cleared, infinity, ios
+        return self._proofs(out, len(ios)), cleared, infinity, ios
 
     def prove_msms(self, terms, lengths, starts=None):
         """A batch of short MSMs of any total length (arguments as msm_batch_instances) proved as units of the table, segments
         sharing units and the last unit padded (sbn_batch_prover_prove_msm_batch).  Returns (proofs, finals, sums, infinity, ios)."""
         terms, lengths, starts, xw, ew, curve = _msm_batch_args(self.stark, terms, lengths, starts)
-        units = msm_num_units(terms.shape[0], self.stark.num_io)
-        ios = np.zeros((units, self.stark.num_io, 2 * xw + ew), dtype=np.uint32)
+        ios, out = self._unit_buffers(terms.shape[0], 2 * xw + ew)
         finals, sums, infinity = _msm_batch_outputs(len(lengths), xw, curve)
-        out = (C.c_void_p * max(units, 1))()
         _check(lib().sbn_batch_prover_prove_msm_batch(self._h, _ptr(terms), _ptr(lengths), len(lengths), _ptr(starts),
                                                       starts.shape[0] if starts is not None else 1, out, _ptr(finals), _ptr(sums), _ptr(infinity), _ptr(ios)))
-        return [_take_proof(C.c_void_p(h)) for h in out[:units]], finals, sums, infinity, ios
+        return self._proofs(out, len(ios)), finals, sums, infinity, ios
 
     def prove_powers(self, bases, exps, depth=1):
         """Powers / power towers of any count (arguments as power_instances) proved as units of the table, the last one padded
         (sbn_batch_prover_prove_powers).  Returns (proofs, powers, ios)."""
         bases, exps, depth, w, ew = _power_args(self.stark, bases, exps, depth)
         count = bases.shape[0]
-        units = msm_num_units(count * depth, self.stark.num_io)
-        ios = np.zeros((units, self.stark.num_io, 2 * w + ew), dtype=np.uint32)
+        ios, out = self._unit_buffers(count * depth, 2 * w + ew)
         powers = np.zeros((count, depth, w), dtype=np.uint32)
-        out = (C.c_void_p * max(units, 1))()
         _check(lib().sbn_batch_prover_prove_powers(self._h, _ptr(bases), _ptr(exps), exps.shape[0], count, depth, out, _ptr(powers), _ptr(ios)))
-        return [_take_proof(C.c_void_p(h)) for h in out[:units]], powers, ios
+        return self._proofs(out, len(ios)), powers, ios
 
     def prove_bn_x_powers(self, fs):
         """f^x, f^(x^2), f^(x^3) for the BN parameter x = BN_X and every f of fs ((count, 96) uint32): towers of depth 3 with the
@@ -1442,17 +1436,7 @@ def verify_msm(stark, config, proofs, count, start, terms=None, verifier=None):
     (msm_check_links): with the host verifier, or on the device with `verifier` (a Verifier of the table).  Returns the last
     output in the word shape of start; raises SbnError when a unit is rejected (naming the unit) or a link breaks."""
     proofs = list(proofs)
-    if verifier is None:
-        for u, p in enumerate(proofs):
-            try:
-                verify_stark_proof(stark, p, config)
-            except SbnError as e:
-                raise SbnError(e.code, f"unit {u}: {e}") from None
-    else:
-        for at in range(0, len(proofs), verifier.max_batch):
-            for i, (code, reason) in enumerate(verifier.verify(proofs[at:at + verifier.max_batch])):
-                if code != 0:
-                    raise SbnError(code, f"unit {at + i}: {reason}")
+    _verify_units(stark, config, proofs, verifier)
     return msm_check_links(stark, [p.public_inputs() for p in proofs], count, start, terms)
 
 

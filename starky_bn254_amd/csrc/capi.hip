@@ -2,6 +2,7 @@
 #include "host_common.hpp"
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -202,70 +203,63 @@ int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t 
   return SBN_OK;
 }
 
-// A chained list of any length as units of the batch prover's table (include/sbn.h, "Long chained lists"): the padded, unit-cut
-// list is derived once on the host pool (csrc/msm.hip), then the units go through the explicit-list path above, so the proofs,
-// their public inputs and ios_out are those of sbn_batch_prover_prove_ios on the list of sbn_msm_instances by construction, in
-// every placement of the table's chains.
+// What the four calls below share: every proof slot of the `units` units is nulled; `derive(ios)` checks what is left to check and
+// derives the padded, unit-cut list once on the host pool (into ios_out, or into a buffer of this call); then the units go through
+// the explicit-list path above, so the proofs, their public inputs and ios_out are those of sbn_batch_prover_prove_ios on that list
+// by construction, in every placement of the table's chains.
+static int prove_derived_units(sbn_batch_prover* B, size_t units, uint32_t* ios_out, sbn_proof** proofs_out, const std::function<int(uint32_t*)>& derive) {
+  const size_t unit_words = exp_io_words(B->kind) * B->num_io;
+  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
+  std::vector<uint32_t> own;
+  uint32_t* ios = ios_out;
+  if (!ios) { own.resize(unit_words * units); ios = own.data(); }
+  if (int rc = derive(ios)) return rc;
+  return sbn_batch_prover_prove_ios(B, ios, unit_words, B->num_io, units, proofs_out);
+}
+
+// A chained list of any length as units of the batch prover's table (include/sbn.h, "Long chained lists"; csrc/msm.hip).
 int sbn_batch_prover_prove_msm(sbn_batch_prover* B, const uint32_t* terms, size_t count, const uint32_t* start, sbn_proof** proofs_out,
                                uint32_t* final_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  const size_t IOW = exp_io_words(B->kind), units = sbn_msm_num_units(count, B->num_io);
-  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
-  if (IOW == 0) return fail(SBN_ERR_UNSUPPORTED, "chained lists cover the Exp tables");
-  if (!terms || !start || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no instance");
-  std::vector<uint32_t> own;
-  uint32_t* ios = ios_out;
-  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
-  if (int rc = sbn_msm_instances(B->kind, terms, count, B->num_io, start, ios, final_out)) return rc;
-  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+  return prove_derived_units(B, sbn_msm_num_units(count, B->num_io), ios_out, proofs_out, [&](uint32_t* ios) {
+    if (exp_io_words(B->kind) == 0) return fail(SBN_ERR_UNSUPPORTED, "chained lists cover the Exp tables");
+    if (!terms || !start || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no instance");
+    return sbn_msm_instances(B->kind, terms, count, B->num_io, start, ios, final_out);
+  });
 }
 
-// Independent scalar multiplications of any count (include/sbn.h, "Scalar multiplications"; csrc/scalar_mul.hip): as above, the
-// padded, unit-cut list and the products are derived once on the host pool and the units go through the explicit-list path.
+// Independent scalar multiplications of any count (include/sbn.h, "Scalar multiplications"; csrc/scalar_mul.hip): the products
+// are derived with the list.
 int sbn_batch_prover_prove_scalar_muls(sbn_batch_prover* B, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count,
                                        const uint32_t* offset, sbn_proof** proofs_out, uint32_t* products_out, uint8_t* infinity_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  const size_t IOW = exp_io_words(B->kind), units = sbn_msm_num_units(count, B->num_io);
-  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
-  std::vector<uint32_t> own;
-  uint32_t* ios = ios_out;
-  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
-  if (int rc = sbn_scalar_mul_instances(B->kind, points, scalars, scalar_count, count, B->num_io, offset, ios, products_out, infinity_out)) return rc;
-  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+  return prove_derived_units(B, sbn_msm_num_units(count, B->num_io), ios_out, proofs_out, [&](uint32_t* ios) {
+    return sbn_scalar_mul_instances(B->kind, points, scalars, scalar_count, count, B->num_io, offset, ios, products_out, infinity_out);
+  });
 }
 
-// Field powers and power towers of any count (include/sbn.h, "Field powers"; csrc/powers.hip): as above, the padded, unit-cut list
-// and the powers are derived once on the host pool, so a tower that straddles two units needs no context to wait for another, and
-// the units go through the explicit-list path.
+// Field powers and power towers of any count (include/sbn.h, "Field powers"; csrc/powers.hip): the powers are derived with the
+// list, so a tower that straddles two units needs no context to wait for another.
 int sbn_batch_prover_prove_powers(sbn_batch_prover* B, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth,
                                   sbn_proof** proofs_out, uint32_t* powers_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  const size_t IOW = exp_io_words(B->kind), fits = count && depth <= (size_t)-1 / 2 / count;
-  const size_t units = fits ? sbn_msm_num_units(count * depth, B->num_io) : 0;
-  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
-  std::vector<uint32_t> own;
-  uint32_t* ios = ios_out;
-  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
-  if (int rc = sbn_power_instances(B->kind, bases, exps, exp_count, count, depth, B->num_io, ios, powers_out)) return rc;
-  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+  const bool fits = count && depth <= (size_t)-1 / 2 / count;   // (what does not fit has no unit count: sbn_power_instances refuses it)
+  return prove_derived_units(B, fits ? sbn_msm_num_units(count * depth, B->num_io) : 0, ios_out, proofs_out, [&](uint32_t* ios) {
+    return sbn_power_instances(B->kind, bases, exps, exp_count, count, depth, B->num_io, ios, powers_out);
+  });
 }
 
-// Batches of short MSMs of any total length (include/sbn.h, "Batches of short MSMs"; csrc/msm_batch.hip): as above, the segmented
-// list, padded and unit-cut, is derived once on the host pool -- a segment that straddles two units needs no context to wait for
-// another -- and the units go through the explicit-list path.
+// Batches of short MSMs of any total length (include/sbn.h, "Batches of short MSMs"; csrc/msm_batch.hip): a segment that straddles
+// two units needs no context to wait for another.
 int sbn_batch_prover_prove_msm_batch(sbn_batch_prover* B, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count,
                                      sbn_proof** proofs_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
   size_t M = 0;   // (a list whose lengths are refused has no unit count: M stays 0 and nothing of proofs_out is touched)
   const int bad = msm_batch_check_args(B->kind, terms, lengths, segments, &starts, &start_count, B->num_io, sums_out, infinity_out, &M);
-  const size_t IOW = exp_io_words(B->kind), units = sbn_msm_num_units(M, B->num_io);
-  for (size_t u = 0; u < units; u++) proofs_out[u] = nullptr;
-  if (bad) return bad;
-  std::vector<uint32_t> own;
-  uint32_t* ios = ios_out;
-  if (!ios) { own.resize(IOW * B->num_io * units); ios = own.data(); }
-  if (int rc = msm_batch_derive(B->kind, terms, lengths, segments, starts, start_count, M, units * B->num_io, ios, finals_out, sums_out, infinity_out)) return rc;
-  return sbn_batch_prover_prove_ios(B, ios, IOW * B->num_io, B->num_io, units, proofs_out);
+  const size_t units = sbn_msm_num_units(M, B->num_io);
+  return prove_derived_units(B, units, ios_out, proofs_out, [&](uint32_t* ios) {
+    return bad ? bad : msm_batch_derive(B->kind, terms, lengths, segments, starts, start_count, M, units * B->num_io, ios, finals_out, sums_out, infinity_out);
+  });
 }
 
 int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* B, const uint32_t* points, size_t count, sbn_proof** proofs_out, uint32_t* cleared_out,

@@ -124,20 +124,10 @@ static int pinned_reserve(u64** buf, size_t* words, size_t need) {
   return 0;
 }
 
+// ---- the list sources: what each sbn_prover_generate_trace_* call hands its driver -----------------------------------------------
 // sbn_prover_generate_trace_chained: the offsets are derived on the device from `terms` (instance rows without their offset words)
-// and `start`; the explicit-list call passes none of this and launches what it always launched.
+// and `start`.
 struct ChainedIn { const uint32_t* terms; const uint32_t* start; uint32_t* ios_out; };
-// the preliminary list: every instance with the same `offset` words (xw words of x, ew of the exponent)
-static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, size_t xw, size_t ew, const uint32_t* offset) {
-  std::vector<uint32_t> ios((2 * xw + ew) * K);
-  for (size_t k = 0; k < K; k++) {
-    uint32_t* io = ios.data() + (2 * xw + ew) * k;
-    memcpy(io, ch.terms + (xw + ew) * k, xw * sizeof(uint32_t));
-    memcpy(io + xw, offset, xw * sizeof(uint32_t));
-    memcpy(io + 2 * xw, ch.terms + (xw + ew) * k + xw, ew * sizeof(uint32_t));
-  }
-  return ios;
-}
 
 // sbn_prover_generate_trace_scalar_muls: every instance carries `offset`; the list is expanded on the device from the points, the
 // one-or-K scalars and the offset, and the products output + (-offset) are computed there (kernels_tracegen.cuh, "independent
@@ -155,32 +145,43 @@ struct BatchIn {
   const uint32_t* terms; const uint64_t* lengths; size_t segments; const uint32_t* starts; size_t start_count, M;
   uint32_t* finals_out; uint32_t* sums_out; uint8_t* infinity_out; uint32_t* ios_out;
 };
-// the preliminary list of a segmented one: row g carries x and exponent of instance min(g, M - 1) and `offset_of(segment)` as its
-// offset; head_of[g] = the head of the segment of that instance (optional); seg_head / seg_len: per segment
-static std::vector<uint32_t> batch_preliminary_list(const BatchIn& mb, size_t K, size_t xw, size_t ew, const std::function<const uint32_t*(size_t)>& offset_of,
-                                                    std::vector<uint32_t>& seg_head, std::vector<uint32_t>& seg_len, std::vector<uint32_t>* head_of) {
+// the preliminary list of a segmented one (a chained list is one segment): row g carries x and exponent of instance min(g, M - 1)
+// and `offset_of(segment)` as its offset (xw words each, ew of the exponent); head_of[g] = the head of the segment of that
+// instance (optional); seg_head / seg_len: per segment
+static std::vector<uint32_t> preliminary_list(const uint32_t* terms, const uint64_t* lengths, size_t segments, size_t M, size_t K, size_t xw, size_t ew,
+                                              const std::function<const uint32_t*(size_t)>& offset_of, std::vector<uint32_t>& seg_head, std::vector<uint32_t>& seg_len,
+                                              std::vector<uint32_t>* head_of = nullptr) {
   std::vector<uint32_t> ios((2 * xw + ew) * K);
-  seg_head.resize(mb.segments); seg_len.resize(mb.segments);
+  seg_head.resize(segments); seg_len.resize(segments);
   if (head_of) head_of->resize(K);
   size_t g = 0;
-  for (size_t s = 0; s < mb.segments; s++) {
-    seg_head[s] = (uint32_t)g; seg_len[s] = (uint32_t)mb.lengths[s];
-    for (size_t j = 0; j < mb.lengths[s]; j++, g++) {
+  for (size_t s = 0; s < segments; s++) {
+    seg_head[s] = (uint32_t)g; seg_len[s] = (uint32_t)lengths[s];
+    for (size_t j = 0; j < lengths[s]; j++, g++) {
       uint32_t* io = ios.data() + (2 * xw + ew) * g;
-      memcpy(io, mb.terms + (xw + ew) * g, xw * sizeof(uint32_t));
+      memcpy(io, terms + (xw + ew) * g, xw * sizeof(uint32_t));
       memcpy(io + xw, offset_of(s), xw * sizeof(uint32_t));
-      memcpy(io + 2 * xw, mb.terms + (xw + ew) * g + xw, ew * sizeof(uint32_t));
+      memcpy(io + 2 * xw, terms + (xw + ew) * g + xw, ew * sizeof(uint32_t));
       if (head_of) (*head_of)[g] = seg_head[s];
     }
   }
   for (; g < K; g++) {   // the reference's resize rule: a pad row is the last row again
-    memcpy(ios.data() + (2 * xw + ew) * g, ios.data() + (2 * xw + ew) * (mb.M - 1), (2 * xw + ew) * sizeof(uint32_t));
+    memcpy(ios.data() + (2 * xw + ew) * g, ios.data() + (2 * xw + ew) * (M - 1), (2 * xw + ew) * sizeof(uint32_t));
     if (head_of) (*head_of)[g] = (uint32_t)g;   // (never read: the scan's lanes stop at M)
   }
   return ios;
 }
+static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, size_t xw, size_t ew, const uint32_t* offset) {
+  const uint64_t length = K;
+  std::vector<uint32_t> head, len;
+  return preliminary_list(ch.terms, &length, 1, K, K, xw, ew, [&](size_t) { return offset; }, head, len);
+}
 
-// One sbn_prover_generate_trace call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
+// ---- the stages -----------------------------------------------------------------------------------------------------------------
+// One sbn_prover_generate_trace* call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
+// The two jobs below add the buffers and the stages of their tables.  A stage launches what it always launched and never asks
+// which list source called it; one driver per source calls the stages top to bottom, carves what only its source needs behind
+// the shared buffers (which so stay where they were) and owns its staging layout, its output copies and its error naming.
 struct TraceJob {
   sbn_prover* const P;
   const size_t K, IOW, n;   // K instances of IOW u32 words each
@@ -188,7 +189,8 @@ struct TraceJob {
   const ExpShape sh;
   u64* const wbase;   // scratch: the LDE buffer, not yet in use
   u64* w;
-  std::vector<hipEvent_t> kev;
+  struct Mark { hipEvent_t ev; const char* closes; };
+  std::vector<Mark> marks;
   TraceJob(sbn_prover* P, size_t K, size_t IOW)
       : P(P), K(K), IOW(IOW), n(P->n), st(P->stream), sh(exp_shape(P->air)), wbase(P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde), w(wbase) {}
 
@@ -196,9 +198,10 @@ struct TraceJob {
   unsigned int* take_histograms() { return n > 65536 ? (unsigned int*)take((size_t)sh.num_rc * 32768) : nullptr; }   // u32 histograms of the range-checked columns
   int fits() const { return (size_t)(w - wbase) > P->lde_scratch_words ? fail(SBN_ERR_UNSUPPORTED, "scratch does not fit") : 0; }
 
-  void mark() {
+  // SBN_TRACE_TIMING: a point on the stream; `closes` names the span that ends here (begin() opens the first one)
+  void mark(const char* closes) {
     hipEvent_t e;
-    if (P->set.trace_timing && hipEventCreate(&e) == hipSuccess && hipEventRecord(e, st) == hipSuccess) kev.push_back(e);
+    if (P->set.trace_timing && hipEventCreate(&e) == hipSuccess && hipEventRecord(e, st) == hipSuccess) marks.push_back({e, closes});
   }
   // the timed span opens (EX_TRACEGEN_MS); the instance list goes in from `h_ios`, the caller's memory or a pinned copy of it
   // (`words`: u32 words that go up when it is not the whole list: the compact form of the scalar multiplications)
@@ -206,7 +209,7 @@ struct TraceJob {
     HIPC(hipEventRecord(P->abs_ev[0], st));
     HIPC(hipMemcpyAsync(d_ios, h_ios, (words ? words : IOW * K) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPC(hipMemsetAsync(d_err, 0, sizeof(int), st));
-    mark();
+    mark(nullptr);
     return 0;
   }
   // the input-independent columns; table_max: the last entry of the lookup table (u16 tables 65535, the split check's 255)
@@ -216,8 +219,9 @@ struct TraceJob {
     hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
     hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, table_max, P->d_trace);
     hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
-    mark();
+    mark("flags+pulses");
   }
+  // the last launches of the u16 tables, then whatever a launch since begin() left as an error
   int launch_u16_range_check(unsigned int* d_cnt, int* d_err) {
     if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
       HIPC(hipMemsetAsync(d_cnt, 0, (size_t)sh.num_rc * 65536 * sizeof(unsigned int), st));
@@ -226,17 +230,19 @@ struct TraceJob {
     } else {
       hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, (const unsigned int*)nullptr, P->set.range_check);
     }
+    mark("range_check");
+    HIPC(hipGetLastError());
     return 0;
   }
-  // the timed span closes and the stream drains: the generator's copies back to the host, queued before this, have landed
-  int end(const char* const* names) {
+  // the timed span closes and the stream drains: the copies back to the host, queued before this, have landed; the spans print
+  int end() {
     HIPC(hipEventRecord(P->abs_ev[1], st));
     HIPC(hipStreamSynchronize(st));
     float ms = 0; HIPC(hipEventElapsedTime(&ms, P->abs_ev[0], P->abs_ev[1]));
     P->stage_ms[ST_COUNT + EX_TRACEGEN_MS] = ms;
     if (P->set.trace_timing) {
-      for (size_t i = 0; i + 1 < kev.size(); i++) { float t = 0; (void)hipEventElapsedTime(&t, kev[i], kev[i + 1]); fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", names[i], t); }
-      for (auto e : kev) (void)hipEventDestroy(e);
+      for (size_t i = 0; i + 1 < marks.size(); i++) { float t = 0; (void)hipEventElapsedTime(&t, marks[i].ev, marks[i + 1].ev); fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", marks[i + 1].closes, t); }
+      for (const Mark& m : marks) (void)hipEventDestroy(m.ev);
       fprintf(stderr, "[device tracegen] %-14s %8.3f ms\n", "total", ms);
     }
     return 0;
@@ -258,59 +264,51 @@ struct TraceJob {
 
 // G1ExpStark / G2ExpStark (E = 1 / 2)
 template <int E>
-static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const ScalarMulIn* sm = nullptr,
-                                 const BatchIn* mb = nullptr) {
-  const size_t IOW = 8 * (4 * E + 1);  // u32 words per instance: x and offset (2E Fq each) + exp_val
-  std::vector<uint32_t> prelim;        // chained: x, start, exp_val of every instance; the device rewrites the offsets
-  const size_t cin_words = sm ? 16 * E * K + 8 * sm->scalar_count + 16 * E : 0;   // scalar multiplications: u32 words of the compact upload
-  std::vector<uint32_t> aux;           // segmented: head[K], then tail[segments] and head-of-segment[segments]
-  const size_t NP = sm ? K : (mb ? mb->segments : 0);   // products (scalar multiplications) / sums (segmented) that come back
-  if (sm) {   // the host keeps its own explicit list for the public inputs; only the compact form goes up
-    if (int rc = scalar_mul_check_points(E, sm->points, K, sm->offset)) return rc;
-    prelim.resize(IOW * K);
-    scalar_mul_explicit_list(E, sm->points, sm->scalars, sm->scalar_count, K, K, sm->offset, prelim.data());
-    ios = prelim.data();
-  } else if (ch) {
-    if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a chained list has at most %d instances", tg::CS_LANES);
-    if (int rc = chain_terms_check_curve(E, ch->terms, K, ch->start)) return rc;
-    prelim = preliminary_list(*ch, K, 16 * E, 8, ch->start);
-    ios = prelim.data();
-  } else if (mb) {   // segmented: x, the start of its segment, exp_val of every instance; heads of the lanes, then tail and head per segment
-    if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a segmented list has at most %d instances", tg::CS_LANES);
-    if (int rc = msm_batch_check_inputs(P->air.kind, mb->terms, mb->lengths, mb->segments, mb->starts, mb->start_count, mb->M)) return rc;
-    std::vector<uint32_t> seg_head, seg_len;
-    prelim = batch_preliminary_list(*mb, K, 16 * E, 8, [&](size_t s) { return mb->starts + (mb->start_count == 1 ? 0 : 16 * E * s); }, seg_head, seg_len, &aux);
-    for (size_t s = 0; s < mb->segments; s++) aux.push_back(seg_head[s] + seg_len[s] - 1);
-    aux.insert(aux.end(), seg_head.begin(), seg_head.end());
-    ios = prelim.data();
-  } else if (int rc = check_below_p(ios, IOW, 4 * E, K, "coordinate")) return rc;
-  HIPC(hipSetDevice(P->device));
-  TraceJob J(P, K, IOW);
-  const size_t n = J.n;
-  const hipStream_t st = J.st;
-  const size_t cw = 257 * 12 * E * K;  // one Jacobian chain of every instance
-  u64* ja = J.take(cw); u64* jb = J.take(cw);
-  u64* sv = J.take(28 * E * n);       u64* inv = J.take(n);
-  u64* d_out = J.take(16 * E * K);
-  unsigned char* row_op = (unsigned char*)J.take(n / 8 + 1);
-  uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
-  uint32_t* d_prog[2] = {(uint32_t*)J.take(64 * tg::CP_LANES / 2), (uint32_t*)J.take(64 * tg::CP_LANES / 2)};   // chain programs: <= 64 levels of 64 micro-operations
-  int* d_err = (int*)J.take(1);
-  unsigned int* d_cnt = J.take_histograms();
-  const bool scan = ch || mb;                                                 // chained and segmented lists derive their offsets here
-  u64* d_pre = scan ? J.take(12 * E * tg::CT_LANES * K) : nullptr;            // chained: the partial sums of every instance,
-  u64* d_terms = scan ? J.take(12 * E * K) : nullptr;                         // e_k x_k, then the two scan buffers
-  u64* d_scan[2] = {scan ? J.take(12 * E * K) : nullptr, scan ? J.take(12 * E * K) : nullptr};
-  int* d_err_pre = scan ? (int*)J.take(1) : nullptr;                          // flags of the preliminary chains (offsets = start): never read
-  uint32_t* d_cin = sm ? (uint32_t*)J.take(cin_words / 2 + 1) : nullptr;      // scalar multiplications: the compact upload, the Jacobian
-  u64* d_jp = NP ? J.take(12 * E * NP) : nullptr;                             // products between the two passes of a lane, the affine
-  uint32_t* d_prod = NP ? (uint32_t*)J.take(8 * E * NP) : nullptr;            // products ([NP][16E] u32) and their infinity flags
-  unsigned char* d_inf = NP ? (unsigned char*)J.take(NP / 8 + 1) : nullptr;
-  uint32_t* d_aux = mb ? (uint32_t*)J.take(aux.size() / 2 + 1) : nullptr;     // segmented: the index arrays
-  if (int rc = J.fits()) return rc;
-  if (int rc = range_check_setup(P->device)) return rc;
-  // both chains of every instance on the device, flags into `errw` (chain_mode 2 / 1, see below)
-  auto launch_chains = [&](int* errw) -> int {
+struct CurveJob : TraceJob {
+  static constexpr size_t PW = 16 * E;   // u32 words of a point = u64 words of one instance's output in d_out
+  const size_t cw = 257 * 12 * E * K;    // one Jacobian chain of every instance
+  const size_t list_words = (IOW * K + 1) / 2, out_words = PW * K + 1;   // pinned staging, u64 words: the list; the outputs + error word
+  u64 *ja, *jb, *sv, *inv, *d_out;
+  unsigned char* row_op;
+  uint32_t *d_ios, *d_prog[2];   // (chain programs: <= 64 levels of 64 micro-operations)
+  int* d_err;
+  unsigned int* d_cnt;
+  u64 *pre, *terms, *scan[2];  int* err_pre;                        // carve_scan()
+  size_t np = 0;  u64* jp;  uint32_t* prod;  unsigned char* inf;    // carve_products()
+  u64* h_out = nullptr;                                             // ready()
+  CurveJob(sbn_prover* P, size_t K) : TraceJob(P, K, 8 * (4 * E + 1)) {   // u32 words per instance: x and offset (2E Fq each) + exp_val
+    ja = take(cw); jb = take(cw);
+    sv = take(28 * E * n); inv = take(n);
+    d_out = take(PW * K);
+    row_op = (unsigned char*)take(n / 8 + 1);
+    d_ios = (uint32_t*)take(IOW * K / 2 + 1);
+    d_prog[0] = (uint32_t*)take(64 * tg::CP_LANES / 2); d_prog[1] = (uint32_t*)take(64 * tg::CP_LANES / 2);
+    d_err = (int*)take(1);
+    d_cnt = take_histograms();
+  }
+  // chain offsets: the partial sums of every instance, e_k x_k, the two scan buffers, the flags of the preliminary chains (never read)
+  void carve_scan() { pre = take(12 * E * tg::CT_LANES * K); terms = take(12 * E * K); scan[0] = take(12 * E * K); scan[1] = take(12 * E * K); err_pre = (int*)take(1); }
+  // un-offset of `count` outputs: the Jacobian products between the two passes of a lane, the affine products ([count][16E] u32), their infinity flags
+  void carve_products(size_t count) { np = count; jp = take(12 * E * np); prod = (uint32_t*)take(8 * E * np); inf = (unsigned char*)take(np / 8 + 1); }
+  // after the last take().  Pinned staging as the driver lays it out: `in_words` u64 words go up, the outputs + error word land
+  // behind them at h_out, `back_words` more behind those at h_back()
+  int ready(size_t in_words, size_t back_words = 0) {
+    if (int rc = fits()) return rc;
+    if (int rc = range_check_setup(P->device)) return rc;
+    if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, in_words + out_words + back_words)) return rc;
+    h_out = P->h_io + in_words;
+    return 0;
+  }
+  u64* h_back() const { return h_out + out_words; }
+  int upload_list(const uint32_t* ios) {   // the whole list, explicit or preliminary
+    memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
+    return begin(P->h_io, d_ios, d_err);
+  }
+  void common_columns() { launch_common_columns(tg::flags_kernel, d_ios, inv, 65535); }
+  // both 256-step chains of every instance on the device, flags into `errw`.  chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx
+  // picks by the host pool's size): 2 = one wave per instance walking levels of independent Fq operations (tg::chain_coop_kernel),
+  // 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host_chains()
+  int launch_chains(int* errw) {
     if (P->chain_mode == 2) {
       static const ChainProgram prog = build_chain_program(E);
       if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
@@ -326,258 +324,372 @@ static int generate_trace_device(sbn_prover* P, const uint32_t* ios, size_t K, u
       hipLaunchKernelGGL(tg::chain_coop_kernel<E>, dim3((unsigned)K), dim3(tg::CP_LANES), 0, st, d_ios, K, ja, jb, errw, cp);
     } else hipLaunchKernelGGL(tg::chain_kernel<E>, blocks(K, 64), dim3(64), 0, st, d_ios, K, ja, jb, errw);
     return 0;
-  };
-  // the instance list in and the outputs + error word back cross through pinned staging (chained: the derived list comes back too)
-  // (scalar multiplications: the compact form in, the products and their flags back behind the outputs)
-  const size_t io_words = sm ? (cin_words + 1) / 2 : (IOW * K + 1) / 2, out_words = 16 * E * K + 1;
-  const size_t prod_words = 8 * E * NP, inf_words = (NP + 7) / 8;
-  if (int rc = pinned_reserve(&P->h_io, &P->h_io_words, io_words + out_words + (scan ? io_words : 0) + prod_words + inf_words)) return rc;
-  u64* const h_out = P->h_io + io_words;
-  u64* const h_prod = h_out + out_words + (scan ? io_words : 0);   // (behind the derived list where one comes back)
-  if (sm) {
-    uint32_t* h = (uint32_t*)P->h_io;
-    memcpy(h, sm->points, 16 * E * K * sizeof(uint32_t));
-    memcpy(h + 16 * E * K, sm->scalars, 8 * sm->scalar_count * sizeof(uint32_t));
-    memcpy(h + 16 * E * K + 8 * sm->scalar_count, sm->offset, 16 * E * sizeof(uint32_t));
-    if (int rc = J.begin(P->h_io, d_cin, d_err, cin_words)) return rc;
-    hipLaunchKernelGGL(tg::scalar_mul_list_kernel<E>, blocks(IOW * K, 256), dim3(256), 0, st, d_cin, K, sm->scalar_count, d_ios);
-    J.mark();
-  } else {
-    memcpy(P->h_io, ios, IOW * K * sizeof(uint32_t));
-    if (int rc = J.begin(P->h_io, d_ios, d_err)) return rc;
   }
-  if (scan) {   // offsets on the device (kernels_tracegen.cuh, "chained instance lists"); only chain_mode 1 and 2 come here
-    if (mb) HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (int rc = launch_chains(d_err_pre)) return rc;
-    hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, d_pre, d_terms);
-    if (mb) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, mb->M, d_aux, d_terms, d_scan[0], d_scan[1], d_err);
-    else hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, d_terms, d_scan[0], d_scan[1], d_err);
-    J.mark();
-    ios = (const uint32_t*)(h_out + out_words);   // where the derived list lands, below
-  }
-  J.launch_common_columns(tg::flags_kernel, d_ios, inv, 65535);
-  // the two 256-step curve chains per instance: host threads while the device writes the input-independent columns
-  // chain_mode (SBN_TRACEGEN_DEVICE_CHAIN; create_ctx picks by the host pool's size): 2 = one wave per instance walking levels of
-  // independent Fq operations (tg::chain_coop_kernel), 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host threads +
-  // pinned upload
-  if (scan) hipLaunchKernelGGL(tg::chain_rebase_kernel<E>, blocks(K * 257, 64), dim3(64), 0, st, d_ios, K, d_pre, jb);   // A is in ja already
-  else if (P->chain_mode) { if (int rc = launch_chains(d_err)) return rc; }
-  else {
+  // host threads while the device writes the input-independent columns, then a pinned upload
+  int host_chains(const uint32_t* ios) {
     if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
     if (tracegen_host_chains(E, ios, K, P->h_chain, P->h_chain + cw)) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
     HIPC(hipMemcpyAsync(ja, P->h_chain, cw * sizeof(u64), hipMemcpyHostToDevice, st));
     HIPC(hipMemcpyAsync(jb, P->h_chain + cw, cw * sizeof(u64), hipMemcpyHostToDevice, st));
+    return 0;
   }
-  J.mark();
-  hipLaunchKernelGGL(tg::affine_lambda_kernel<E>, blocks((n + tg::TG_ROWS - 1) / tg::TG_ROWS, 64), dim3(64), 0, st, d_ios, K, ja, jb, n, sv, row_op, d_out, d_err);
-  J.mark();
-  if (sm) {   // the products from the instance outputs affine_lambda_kernel left in d_out
-    hipLaunchKernelGGL(tg::scalar_mul_unoffset_kernel<E>, blocks((K + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, K, d_out, d_jp, d_prod, d_inf);
-    J.mark();
+  // chain offsets on the device (kernels_tracegen.cuh, "chained instance lists", "segmented chained lists"): the chains of the
+  // preliminary list and the partial sums of every instance, then a scan over the list, or over M instances in segments with
+  // head d_head_of[k], writes the offsets into d_ios
+  int chain_scan(size_t M = 0, const uint32_t* d_head_of = nullptr) {
+    if (int rc = launch_chains(err_pre)) return rc;
+    hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, pre, terms);
+    if (d_head_of) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, M, d_head_of, terms, scan[0], scan[1], d_err);
+    else hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, terms, scan[0], scan[1], d_err);
+    mark("chain_offsets");
+    return 0;
   }
-  if (mb) {   // final_s + (-start_s): the same kernel, indexed by the tail and the head of every segment
-    hipLaunchKernelGGL(tg::scalar_mul_unoffset_kernel<E>, blocks((NP + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, NP, d_out, d_jp, d_prod, d_inf,
-                       d_aux + K, d_aux + K + NP);
-    J.mark();
+  void rebase() {   // the chain of b onto the derived offsets; A is in ja already
+    hipLaunchKernelGGL(tg::chain_rebase_kernel<E>, blocks(K * 257, 64), dim3(64), 0, st, d_ios, K, pre, jb);
+    mark("chains");
   }
-  hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, J.sh.gadget_col, P->d_trace, d_err);
-  J.mark();
-  if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
-  J.mark();
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(h_out, d_out, 16 * E * K * sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIPC(hipMemcpyAsync(h_out + 16 * E * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (scan) HIPC(hipMemcpyAsync(h_out + out_words, d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  static const char* const names[] = {"flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
-  if (NP) {
-    HIPC(hipMemcpyAsync(h_prod, d_prod, 16 * E * NP * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(h_prod + prod_words, d_inf, NP, hipMemcpyDeviceToHost, st));
+  void affine_lambda() {
+    hipLaunchKernelGGL(tg::affine_lambda_kernel<E>, blocks((n + tg::TG_ROWS - 1) / tg::TG_ROWS, 64), dim3(64), 0, st, d_ios, K, ja, jb, n, sv, row_op, d_out, d_err);
+    mark("affine+lambda");
   }
-  static const char* const names_chained[] = {"chain_offsets", "flags+pulses", "chains", "affine+lambda", "row_witness", "range_check"};
-  static const char* const names_scalar[] = {"scalar_list", "flags+pulses", "chains", "affine+lambda", "un_offset", "row_witness", "range_check"};
-  static const char* const names_batch[] = {"chain_offsets", "flags+pulses", "chains", "affine+lambda", "un_offset", "row_witness", "range_check"};
-  if (int rc = J.end(sm ? names_scalar : mb ? names_batch : ch ? names_chained : names)) return rc;
-  // public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156)
-  const int rc = J.finish((int)(h_out[16 * E * K] & 0xffffffffu), pi_out, [&](size_t k, u64* p) {
-    for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
-    for (int i = 0; i < 16 * E; i++) p[IOW + i] = h_out[16 * E * k + i];
-  });
-  if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
-  if (sm && rc == SBN_ERR_WITNESS && ((int)(h_out[16 * E * K] & 0xffffffffu) & tg::TG_ERR_DEGENERATE)) {
-    // the kernels report an error word only: the host walk names the first instance the table cannot walk (error path)
-    if (int named = scalar_mul_name_degenerate(E, ios, K)) return named;
-    return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
+  // output + (-offset) of np instances from what affine_lambda() left in d_out: of instance i, or output d_out_at[i] and the offset
+  // of instance d_off_at[i]
+  void un_offset(const uint32_t* d_out_at = nullptr, const uint32_t* d_off_at = nullptr) {
+    hipLaunchKernelGGL(tg::scalar_mul_unoffset_kernel<E>, blocks((np + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, np, d_out, jp, prod, inf, d_out_at, d_off_at);
+    mark("un_offset");
   }
-  if (mb && rc == SBN_ERR_WITNESS && ((int)(h_out[16 * E * K] & 0xffffffffu) & (tg::TG_ERR_INFINITY | tg::TG_ERR_DEGENERATE))) {
-    // the kernels report an error word only: the host derivation names the instance and its segment (error path)
-    std::vector<uint32_t> named(IOW * K);
-    if (int why = msm_batch_derive(P->air.kind, mb->terms, mb->lengths, mb->segments, mb->starts, mb->start_count, mb->M, K, named.data(), nullptr, nullptr, nullptr)) return why;
+  // the last launches; the outputs and the error word come back
+  int witness_and_range_check() {
+    hipLaunchKernelGGL(tg::gadget_witness_kernel<E>, blocks(3 * E * n, 256), dim3(256), 0, st, sv, row_op, n, sh.gadget_col, P->d_trace, d_err);
+    mark("row_witness");
+    if (int rc = launch_u16_range_check(d_cnt, d_err)) return rc;
+    HIPC(hipMemcpyAsync(h_out, d_out, PW * K * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(h_out + PW * K, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    return 0;
+  }
+  int download_list(u64* h_list) {   // the list as the device derived it
+    HIPC(hipMemcpyAsync(h_list, d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return 0;
+  }
+  int download_products(u64* h_prod) {   // the flags land 8E * np u64 words behind the products
+    HIPC(hipMemcpyAsync(h_prod, prod, PW * np * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(h_prod + 8 * E * np, inf, np, hipMemcpyDeviceToHost, st));
+    return 0;
+  }
+  int error_word() const { return (int)(h_out[PW * K] & 0xffffffffu); }   // after publish()
+  // the span closes; public inputs: x, offset, exp_val, output as u32 limbs (g1/exp.rs:124-135, g2/exp.rs:139-156); `ios` to ios_out
+  int publish(const uint32_t* ios, uint64_t* pi_out, uint32_t* ios_out = nullptr) {
+    if (int rc = end()) return rc;
+    const int rc = finish(error_word(), pi_out, [&](size_t k, u64* p) {
+      for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
+      for (size_t i = 0; i < PW; i++) p[IOW + i] = h_out[PW * k + i];
+    });
+    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios, IOW * K * sizeof(uint32_t));
     return rc;
   }
-  if (mb && rc == SBN_OK) {
-    if (mb->ios_out) memcpy(mb->ios_out, ios, IOW * K * sizeof(uint32_t));
-    if (mb->finals_out)   // the instance outputs at the segment tails: one u32 limb per u64 word
-      for (size_t s = 0; s < NP; s++) for (int i = 0; i < 16 * E; i++) mb->finals_out[16 * E * s + i] = (uint32_t)h_out[16 * E * aux[K + s] + i];
-    if (mb->sums_out) memcpy(mb->sums_out, h_prod, 16 * E * NP * sizeof(uint32_t));
-    if (mb->infinity_out) memcpy(mb->infinity_out, h_prod + prod_words, NP);
+};
+
+template <int E>
+static int curve_trace_explicit(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+  CurveJob<E> J(P, K);
+  if (int rc = check_below_p(ios, J.IOW, 4 * E, K, "coordinate")) return rc;
+  HIPC(hipSetDevice(P->device));
+  if (int rc = J.ready(J.list_words)) return rc;
+  if (int rc = J.upload_list(ios)) return rc;
+  J.common_columns();
+  if (int rc = P->chain_mode ? J.launch_chains(J.d_err) : J.host_chains(ios)) return rc;
+  J.mark("chains");
+  J.affine_lambda();
+  if (int rc = J.witness_and_range_check()) return rc;
+  return J.publish(ios, pi_out);
+}
+
+// chained: x, start, exp_val of every instance go up; the device rewrites the offsets and the derived list comes back behind the
+// outputs.  Only chain_mode 1 and 2 come here, as to the two drivers below.
+template <int E>
+static int curve_trace_chained(sbn_prover* P, const ChainedIn& ch, size_t K, uint64_t* pi_out) {
+  if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a chained list has at most %d instances", tg::CS_LANES);
+  if (int rc = chain_terms_check_curve(E, ch.terms, K, ch.start)) return rc;
+  const std::vector<uint32_t> prelim = preliminary_list(ch, K, 16 * E, 8, ch.start);
+  HIPC(hipSetDevice(P->device));
+  CurveJob<E> J(P, K);
+  J.carve_scan();
+  if (int rc = J.ready(J.list_words, J.list_words)) return rc;
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  if (int rc = J.chain_scan()) return rc;
+  J.common_columns();
+  J.rebase();
+  J.affine_lambda();
+  if (int rc = J.witness_and_range_check()) return rc;
+  if (int rc = J.download_list(J.h_back())) return rc;
+  return J.publish((const uint32_t*)J.h_back(), pi_out, ch.ios_out);
+}
+
+// scalar multiplications: the host keeps its own explicit list for the public inputs; only the compact form (points, scalars,
+// offset) goes up, and the products and their flags come back behind the outputs
+template <int E>
+static int curve_trace_scalar_muls(sbn_prover* P, const ScalarMulIn& sm, size_t K, uint64_t* pi_out) {
+  if (int rc = scalar_mul_check_points(E, sm.points, K, sm.offset)) return rc;
+  CurveJob<E> J(P, K);
+  std::vector<uint32_t> ios(J.IOW * K);
+  scalar_mul_explicit_list(E, sm.points, sm.scalars, sm.scalar_count, K, K, sm.offset, ios.data());
+  HIPC(hipSetDevice(P->device));
+  const size_t pts = 16 * E * K, cin_words = pts + 8 * sm.scalar_count + 16 * E;   // u32 words: the points, the compact upload
+  uint32_t* d_cin = (uint32_t*)J.take(cin_words / 2 + 1);
+  J.carve_products(K);
+  if (int rc = J.ready((cin_words + 1) / 2, 8 * E * K + (K + 7) / 8)) return rc;
+  uint32_t* h = (uint32_t*)P->h_io;
+  memcpy(h, sm.points, pts * sizeof(uint32_t));
+  memcpy(h + pts, sm.scalars, 8 * sm.scalar_count * sizeof(uint32_t));
+  memcpy(h + pts + 8 * sm.scalar_count, sm.offset, 16 * E * sizeof(uint32_t));
+  if (int rc = J.begin(h, d_cin, J.d_err, cin_words)) return rc;
+  hipLaunchKernelGGL(tg::scalar_mul_list_kernel<E>, blocks(J.IOW * K, 256), dim3(256), 0, J.st, d_cin, K, sm.scalar_count, J.d_ios);
+  J.mark("scalar_list");
+  J.common_columns();
+  if (int rc = J.launch_chains(J.d_err)) return rc;
+  J.mark("chains");
+  J.affine_lambda();
+  J.un_offset();
+  if (int rc = J.witness_and_range_check()) return rc;
+  if (int rc = J.download_products(J.h_back())) return rc;
+  const int rc = J.publish(ios.data(), pi_out, sm.ios_out);
+  if (rc == SBN_ERR_WITNESS && (J.error_word() & tg::TG_ERR_DEGENERATE)) {
+    // the kernels report an error word only: the host walk names the first instance the table cannot walk (error path)
+    if (int named = scalar_mul_name_degenerate(E, ios.data(), K)) return named;
+    return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
   }
-  if (sm && rc == SBN_OK) {
-    if (sm->products_out) memcpy(sm->products_out, h_prod, 16 * E * K * sizeof(uint32_t));
-    if (sm->infinity_out) memcpy(sm->infinity_out, h_prod + prod_words, K);
-    if (sm->ios_out) memcpy(sm->ios_out, ios, IOW * K * sizeof(uint32_t));
-  }
+  if (rc == SBN_OK && sm.products_out) memcpy(sm.products_out, J.h_back(), pts * sizeof(uint32_t));
+  if (rc == SBN_OK && sm.infinity_out) memcpy(sm.infinity_out, J.h_back() + 8 * E * K, K);
   return rc;
 }
 
-// Fq12ExpStark: the square-and-multiply chains (no inversion anywhere) on host threads in standard form, then one lane
-// per row for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
-static int generate_trace_device_fq12(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out, const ChainedIn* ch = nullptr, const PowerIn* pw = nullptr,
-                                      const BatchIn* mb = nullptr) {
-  const bool u64e = P->air.kind == SBN_AIR_FQ12_EXP_U64;        // 128-row instances, one-element exponent
-  const size_t IOW = u64e ? 194 : 200;
-  const int steps = u64e ? 64 : 256, log_rpb = u64e ? 7 : 9;
-  std::vector<uint32_t> prelim, derived;   // chained: x, one, exp_val of every instance; the device rewrites the offsets
-  if (ch) {
-    if (int rc = check_below_p(ch->start, 96, 12, 1, "coefficient of start")) return rc;
-    uint32_t one[96] = {1};
-    prelim = preliminary_list(*ch, K, 96, IOW - 192, one);
-    derived.resize(IOW * K);
-    ios = prelim.data();
-  }
-  std::vector<uint32_t> aux;   // segmented: head[segments], len[segments], then the starts ([start_count][96])
-  if (mb) {   // x, one, exp_val of every instance (a pad row repeats row M - 1); the device rewrites the offsets
-    if (int rc = msm_batch_check_inputs(P->air.kind, mb->terms, mb->lengths, mb->segments, mb->starts, mb->start_count, mb->M)) return rc;
-    uint32_t one[96] = {1};
-    std::vector<uint32_t> seg_head, seg_len;
-    prelim = batch_preliminary_list(*mb, K, 96, IOW - 192, [&](size_t) { return (const uint32_t*)one; }, seg_head, seg_len, nullptr);
-    aux = seg_head;
-    aux.insert(aux.end(), seg_len.begin(), seg_len.end());
-    aux.insert(aux.end(), mb->starts, mb->starts + 96 * mb->start_count);
-    derived.resize(IOW * K);
-    ios = prelim.data();
-  }
-  const size_t M = pw ? pw->count * pw->depth : K;   // towers: the real instances; rows [M, K) are pads
-  if (pw) {   // x of level 0, zeros above it (the device writes them), one, the tower's exponent; a pad row repeats row M - 1
-    if (int rc = power_check_inputs(P->air.kind, pw->bases, pw->exps, pw->exp_count, pw->count)) return rc;
-    const size_t ew = IOW - 192;
-    prelim.assign(IOW * K, 0u);
-    for (size_t g = 0; g < K; g++) {
-      const size_t r = g < M ? g : M - 1, k = r / pw->depth;
-      uint32_t* io = prelim.data() + IOW * g;
-      if (r % pw->depth == 0) memcpy(io, pw->bases + 96 * k, 96 * sizeof(uint32_t));
-      io[96] = 1;
-      memcpy(io + 192, pw->exps + (pw->exp_count == 1 ? 0 : ew * k), ew * sizeof(uint32_t));
-    }
-    ios = prelim.data();
-  }
-  if (int rc = check_below_p(ios, IOW, 24, K, "coefficient")) return rc;
+// segmented: x, the start of its segment, exp_val of every instance go up with three index arrays (aux: the head of every lane's
+// segment [K], then tail and head per segment); the derived list comes back behind the outputs, the sums final + (-start) and
+// their flags behind the list
+template <int E>
+static int curve_trace_segmented(sbn_prover* P, const BatchIn& mb, size_t K, uint64_t* pi_out) {
+  if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a segmented list has at most %d instances", tg::CS_LANES);
+  if (int rc = msm_batch_check_inputs(P->air.kind, mb.terms, mb.lengths, mb.segments, mb.starts, mb.start_count, mb.M)) return rc;
+  const size_t S = mb.segments;
+  std::vector<uint32_t> aux, seg_head, seg_len;
+  const std::vector<uint32_t> prelim = preliminary_list(mb.terms, mb.lengths, S, mb.M, K, 16 * E, 8, [&](size_t s) { return mb.starts + (mb.start_count == 1 ? 0 : 16 * E * s); },
+                                                        seg_head, seg_len, &aux);
+  for (size_t s = 0; s < S; s++) aux.push_back(seg_head[s] + seg_len[s] - 1);
+  aux.insert(aux.end(), seg_head.begin(), seg_head.end());
   HIPC(hipSetDevice(P->device));
-  if (u64e)
-    for (size_t k = 0; k < K; k++)
-      if (((u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32)) >= GLP) return fail(SBN_ERR_NON_CANONICAL, "exponent of instance %zu is not a canonical field element", k);
-  TraceJob J(P, K, IOW);
-  const size_t n = J.n;
-  const hipStream_t st = J.st;
-  const size_t cw = (size_t)(steps + 1) * 48 * K;  // one chain of every instance, standard form
-  u64* ca = J.take(cw); u64* cb = J.take(cw);
-  u64* inv = J.take(n);
-  u64* d_outs = J.take(K * 48);
-  uint32_t* d_ios = (uint32_t*)J.take(IOW * K / 2 + 1);
-  int* d_err = (int*)J.take(1);
-  uint32_t* d_start = ch ? (uint32_t*)J.take(48) : nullptr;
-  uint32_t* d_aux = mb ? (uint32_t*)J.take(aux.size() / 2 + 1) : nullptr;
-  if (int rc = J.fits()) return rc;
-  if (pw && (u64*)d_ios != d_outs + K * 48) return fail(SBN_ERR_UNSUPPORTED, "internal: the instance list does not follow the outputs");   // (one download, below)
-  if (int rc = J.begin(ios, d_ios, d_err)) return rc;
-  if (ch) {
-    HIPC(hipMemcpyAsync(d_start, ch->start, 96 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    ios = derived.data();   // where the derived list lands, below
+  CurveJob<E> J(P, K);
+  J.carve_scan();
+  J.carve_products(S);
+  uint32_t* d_aux = (uint32_t*)J.take(aux.size() / 2 + 1);
+  if (int rc = J.ready(J.list_words, J.list_words + 8 * E * S + (S + 7) / 8)) return rc;
+  const uint32_t* ios = (const uint32_t*)J.h_back();
+  u64* const h_sums = J.h_back() + J.list_words;
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+  if (int rc = J.chain_scan(mb.M, d_aux)) return rc;
+  J.common_columns();
+  J.rebase();
+  J.affine_lambda();
+  J.un_offset(d_aux + K, d_aux + K + S);   // final_s + (-start_s): indexed by the tail and the head of every segment
+  if (int rc = J.witness_and_range_check()) return rc;
+  if (int rc = J.download_list(J.h_back())) return rc;
+  if (int rc = J.download_products(h_sums)) return rc;
+  const int rc = J.publish(ios, pi_out, mb.ios_out);
+  if (rc == SBN_ERR_WITNESS && (J.error_word() & (tg::TG_ERR_INFINITY | tg::TG_ERR_DEGENERATE))) {
+    // the kernels report an error word only: the host derivation names the instance and its segment (error path)
+    std::vector<uint32_t> named(J.IOW * K);
+    if (int why = msm_batch_derive(P->air.kind, mb.terms, mb.lengths, S, mb.starts, mb.start_count, mb.M, K, named.data(), nullptr, nullptr, nullptr)) return why;
   }
-  if (mb) {
-    HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    ios = derived.data();
+  if (rc == SBN_OK && mb.finals_out)   // the instance outputs at the segment tails: one u32 limb per u64 word
+    for (size_t s = 0; s < S; s++) for (int i = 0; i < 16 * E; i++) mb.finals_out[16 * E * s + i] = (uint32_t)J.h_out[16 * E * aux[K + s] + i];
+  if (rc == SBN_OK && mb.sums_out) memcpy(mb.sums_out, h_sums, 16 * E * S * sizeof(uint32_t));
+  if (rc == SBN_OK && mb.infinity_out) memcpy(mb.infinity_out, h_sums + 8 * E * S, S);
+  return rc;
+}
+
+// Fq12ExpStark / Fq12ExpU64Stark: the square-and-multiply chains (no inversion anywhere) in standard form, then one lane per
+// (row, output coefficient) for the limb columns and the twelve modular-gadget witnesses, and the split range check per target column.
+struct Fq12Job : TraceJob {
+  const bool u64e;            // 128-row instances, one-element exponent
+  const int steps, log_rpb;
+  const size_t cw;            // one chain of every instance, standard form
+  u64 *ca, *cb, *inv, *d_outs;
+  uint32_t* d_ios;
+  int* d_err;
+  int err = 0;                // the kernels' error word and what came back from d_outs on, after publish()
+  std::vector<u64> h_outs;
+  Fq12Job(sbn_prover* P, size_t K)
+      : TraceJob(P, K, P->air.kind == SBN_AIR_FQ12_EXP_U64 ? 194 : 200), u64e(IOW == 194), steps(u64e ? 64 : 256), log_rpb(u64e ? 7 : 9), cw((size_t)(steps + 1) * 48 * K) {
+    ca = take(cw); cb = take(cw);
+    inv = take(n);
+    d_outs = take(K * 48 + IOW * K / 2 + 1);   // the outputs and, right behind them, the list: ONE block, so that a source whose
+    d_ios = (uint32_t*)(d_outs + K * 48);      // list is derived in place (the towers) takes both back in one download
+    d_err = (int*)take(1);
   }
-  if (u64e) J.launch_common_columns(tg::flags_u64_kernel, d_ios, inv, 255);
-  else J.launch_common_columns(tg::flags_kernel, d_ios, inv, 255);
-  // the square-and-multiply chains: one workgroup per instance on the device (kernels_tracegen.cuh fq12_chain_kernel);
-  // SBN_FQ12_HOST_CHAIN=1: the library's host threads + a pinned upload, as in round 2 (A/B)
-  const bool host_chain = P->set.fq12_host_chain && !pw;   // (towers under the host-chain switch never come here)
-  if (pw) {   // d_ios holds the level-0 x, the offsets and the exponents: one workgroup per tower links and walks its levels
-    hipLaunchKernelGGL(tg::fq12_tower_kernel, dim3((unsigned)pw->count), dim3(320), 0, st, d_ios, IOW, steps, pw->depth, ca, cb, d_outs);
-    J.mark();
-    if (M < K) hipLaunchKernelGGL(tg::fq12_tower_pad_kernel, dim3((unsigned)(K - M)), dim3(256), 0, st, d_ios, IOW, M, K, (size_t)(steps + 1) * 48, ca, cb, d_outs);
-  } else if (host_chain) {
+  // after the last take(): the list that goes up is canonical (coefficients below p, a u64 exponent below the Goldilocks prime), the
+  // scratch fits; the timed span opens
+  int upload_list(const uint32_t* ios) {
+    if (int rc = check_below_p(ios, IOW, 24, K, "coefficient")) return rc;
+    HIPC(hipSetDevice(P->device));
+    if (u64e)
+      for (size_t k = 0; k < K; k++)
+        if (((u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32)) >= GLP) return fail(SBN_ERR_NON_CANONICAL, "exponent of instance %zu is not a canonical field element", k);
+    if (int rc = fits()) return rc;
+    return begin(ios, d_ios, d_err);
+  }
+  void common_columns() {
+    if (u64e) launch_common_columns(tg::flags_u64_kernel, d_ios, inv, 255);
+    else launch_common_columns(tg::flags_kernel, d_ios, inv, 255);
+  }
+  // one workgroup per instance (kernels_tracegen.cuh fq12_chain_kernel): the chains, and B[steps] of every instance in d_outs
+  void device_chains() {
+    hipLaunchKernelGGL(tg::fq12_chain_kernel, dim3((unsigned)K), dim3(320), 0, st, d_ios, IOW, steps, ca, cb, d_outs);
+    mark("chains");
+  }
+  // SBN_FQ12_HOST_CHAIN=1: the library's host threads + a pinned upload, as in round 2 (A/B); the outputs stay in P->h_chain
+  int host_chains(const uint32_t* ios) {
     if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
     tracegen_host_chains_fq12(ios, IOW, steps, K, P->h_chain, P->h_chain + cw);
     HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
-  } else hipLaunchKernelGGL(tg::fq12_chain_kernel, dim3((unsigned)K), dim3(320), 0, st, d_ios, IOW, steps, ca, cb, d_outs);
-  J.mark();
-  if (ch) {   // the chains above ran on offsets of one (device chains only): x^e of every instance is in d_outs; the running product
-    // writes the offsets into d_ios and the chain is rebased onto them (kernels_tracegen.cuh, "chained instance lists")
-    hipLaunchKernelGGL(tg::fq12_offset_scan_kernel, dim3(1), dim3(192), 0, st, d_ios, IOW, K, d_start, d_outs);
+    mark("chains");
+    return 0;
+  }
+  // chain offsets (kernels_tracegen.cuh, "chained instance lists"): the chains ran on offsets of one, so x^e of every instance is in
+  // d_outs; the driver's running product has written the offsets into d_ios and the chain of b is rebased onto them
+  void rebase() {
     hipLaunchKernelGGL(tg::fq12_rebase_kernel, dim3((unsigned)(K * (size_t)(steps + 1))), dim3(192), 0, st, d_ios, IOW, steps, cb, d_outs);
-    J.mark();
+    mark("chain_offsets");
   }
-  if (mb) {   // the same on a segmented list: one workgroup per segment walks its own running product ("segmented chained lists")
-    const size_t S = mb->segments;
-    hipLaunchKernelGGL(tg::fq12_seg_scan_kernel, dim3((unsigned)S), dim3(192), 0, st, d_ios, IOW, K, mb->M, d_aux, d_aux + S, d_aux + 2 * S, mb->start_count, d_outs);
-    hipLaunchKernelGGL(tg::fq12_rebase_kernel, dim3((unsigned)(K * (size_t)(steps + 1))), dim3(192), 0, st, d_ios, IOW, steps, cb, d_outs);
-    J.mark();
+  // the last launches (one lane per (row, output coefficient) by default; SBN_FQ12_ROW_KERNEL=1: round 2's one lane per row, A/B);
+  // the error word comes back and `words` u64 words from d_outs on: B[steps] of every instance, K * 48, or the list as well
+  int witness_and_range_check(size_t words) {
+    if (P->set.fq12_row_kernel) hipLaunchKernelGGL(tg::fq12_row_kernel, blocks(n, 64), dim3(64), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
+    else hipLaunchKernelGGL(tg::fq12_gadget_kernel, blocks(12 * n, 256), dim3(256), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
+    mark("row_witness");
+    hipLaunchKernelGGL(tg::split_range_check_kernel, dim3((unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err);
+    mark("range_check");
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    h_outs.resize(words);
+    if (words) HIPC(hipMemcpyAsync(h_outs.data(), d_outs, words * sizeof(u64), hipMemcpyDeviceToHost, st));
+    return 0;
   }
-  // one lane per (row, output coefficient) by default; SBN_FQ12_ROW_KERNEL=1: round 2's one lane per row (A/B)
-  const bool row_kernel = P->set.fq12_row_kernel;
-  if (row_kernel) hipLaunchKernelGGL(tg::fq12_row_kernel, blocks(n, 64), dim3(64), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
-  else hipLaunchKernelGGL(tg::fq12_gadget_kernel, blocks(12 * n, 256), dim3(256), 0, st, d_ios, IOW, log_rpb, ca, cb, n, P->d_trace, d_err);
-  J.mark();
-  hipLaunchKernelGGL(tg::split_range_check_kernel, dim3((unsigned)J.sh.num_rc), dim3(256), 0, st, P->d_trace, n, J.sh.rc_start, J.sh.start_lookups, d_err);
-  J.mark();
-  HIPC(hipGetLastError());
-  int err = 0;
-  HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  std::vector<u64> chain_out;                 // B[steps] of every instance (the outputs among the public inputs) when the chains ran on the device
-  if (pw) {   // d_ios follows d_outs in the scratch (take() above): the outputs = the powers and the derived list in ONE download
-    const size_t ios_u64 = (IOW * K + 1) / 2;
-    chain_out.resize(K * 48 + ios_u64);
-    HIPC(hipMemcpyAsync(chain_out.data(), d_outs, chain_out.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    ios = (const uint32_t*)(chain_out.data() + K * 48);   // where the derived list lands
-  } else if (!host_chain) {
-    chain_out.resize(K * 48);
-    HIPC(hipMemcpyAsync(chain_out.data(), d_outs, K * 48 * sizeof(u64), hipMemcpyDeviceToHost, st));
+  int download_list(std::vector<uint32_t>& h_list) {   // the list as the device derived it
+    h_list.resize(IOW * K);
+    HIPC(hipMemcpyAsync(h_list.data(), d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return 0;
   }
-  if (ch || mb) HIPC(hipMemcpyAsync(derived.data(), d_ios, IOW * K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
-  static const char* const names_chained[] = {"flags+pulses", "chains", "chain_offsets", "row_witness", "range_check"};
-  static const char* const names_tower[] = {"flags+pulses", "tower_links", "tower_pads", "row_witness", "range_check"};
-  if (int rc = J.end(pw ? names_tower : (ch || mb) ? names_chained : names)) return rc;
-  // public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117)
-  const int rc = J.finish(err, pi_out, [&](size_t k, u64* p) {
-    for (int c = 0; c < 24; c++)
-      for (int i = 0; i < 16; i++) p[16 * c + i] = (ios[IOW * k + 8 * c + (i >> 1)] >> (16 * (i & 1))) & 0xffff;
-    if (u64e) p[384] = (u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32);
-    else for (int i = 0; i < 8; i++) p[384 + i] = ios[IOW * k + 192 + i];
-    const u64* out = host_chain ? P->h_chain + cw + ((k * (steps + 1) + steps) * 12) * 4 : chain_out.data() + k * 48;  // B[steps]
-    const int ob = 384 + J.sh.n_exp_slots;
-    for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
-  });
-  if (rc == SBN_OK && ch && ch->ios_out) memcpy(ch->ios_out, ios, IOW * K * sizeof(uint32_t));
-  if (rc == SBN_OK && mb) {
-    if (mb->ios_out) memcpy(mb->ios_out, ios, IOW * K * sizeof(uint32_t));
-    if (mb->finals_out)   // [segments][96] u32 = the outputs of the segment tails, standard form
-      for (size_t s = 0; s < mb->segments; s++) {
-        const u64* out = chain_out.data() + 48 * (size_t)(aux[s] + aux[mb->segments + s] - 1);
-        for (size_t i = 0; i < 48; i++) { mb->finals_out[96 * s + 2 * i] = (uint32_t)out[i]; mb->finals_out[96 * s + 2 * i + 1] = (uint32_t)(out[i] >> 32); }
-      }
+  // the span closes; public inputs: x, offset as 16-bit limbs, exp_val, output = b at the last row (fq12/exp.rs:95-117), the 48
+  // words at outs + stride * k for instance k; `ios` to ios_out
+  int publish(const uint32_t* ios, const u64* outs, size_t stride, uint64_t* pi_out, uint32_t* ios_out = nullptr) {
+    if (int rc = end()) return rc;
+    const int rc = finish(err, pi_out, [&](size_t k, u64* p) {
+      for (int c = 0; c < 24; c++)
+        for (int i = 0; i < 16; i++) p[16 * c + i] = (ios[IOW * k + 8 * c + (i >> 1)] >> (16 * (i & 1))) & 0xffff;
+      if (u64e) p[384] = (u64)ios[IOW * k + 192] | ((u64)ios[IOW * k + 193] << 32);
+      else for (int i = 0; i < 8; i++) p[384 + i] = ios[IOW * k + 192 + i];
+      const u64* out = outs + stride * k;
+      const int ob = 384 + sh.n_exp_slots;
+      for (int c = 0; c < 12; c++) for (int i = 0; i < 16; i++) p[ob + 16 * c + i] = (out[4 * c + (i >> 2)] >> (16 * (i & 3))) & 0xffff;
+    });
+    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios, IOW * K * sizeof(uint32_t));
+    return rc;
   }
-  if (rc == SBN_OK && pw) {
-    if (pw->ios_out) memcpy(pw->ios_out, ios, IOW * K * sizeof(uint32_t));
-    if (pw->powers_out)   // [count][depth][96] u32 = the outputs of the M real instances, standard form
-      for (size_t i = 0; i < 48 * M; i++) { pw->powers_out[2 * i] = (uint32_t)chain_out[i]; pw->powers_out[2 * i + 1] = (uint32_t)(chain_out[i] >> 32); }
+};
+
+static int fq12_trace_explicit(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+  Fq12Job J(P, K);
+  if (int rc = J.upload_list(ios)) return rc;
+  J.common_columns();
+  if (!P->set.fq12_host_chain) {
+    J.device_chains();
+    if (int rc = J.witness_and_range_check(K * 48)) return rc;
+    return J.publish(ios, J.h_outs.data(), 48, pi_out);
   }
+  if (int rc = J.host_chains(ios)) return rc;
+  if (int rc = J.witness_and_range_check(0)) return rc;
+  return J.publish(ios, P->h_chain + J.cw + (size_t)J.steps * 48, (size_t)(J.steps + 1) * 48, pi_out);   // B[steps] of the uploaded chains
+}
+
+// chained: x, one, exp_val of every instance go up; a running product from `start` writes the offsets and the derived list comes
+// back.  Only device chains come here, as to the two drivers below.
+static int fq12_trace_chained(sbn_prover* P, const ChainedIn& ch, size_t K, uint64_t* pi_out) {
+  if (int rc = check_below_p(ch.start, 96, 12, 1, "coefficient of start")) return rc;
+  Fq12Job J(P, K);
+  const uint32_t one[96] = {1};
+  const std::vector<uint32_t> prelim = preliminary_list(ch, K, 96, J.IOW - 192, one);
+  std::vector<uint32_t> ios;
+  uint32_t* d_start = (uint32_t*)J.take(48);
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  HIPC(hipMemcpyAsync(d_start, ch.start, 96 * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+  J.common_columns();
+  J.device_chains();
+  hipLaunchKernelGGL(tg::fq12_offset_scan_kernel, dim3(1), dim3(192), 0, J.st, J.d_ios, J.IOW, K, d_start, J.d_outs);
+  J.rebase();
+  if (int rc = J.witness_and_range_check(K * 48)) return rc;
+  if (int rc = J.download_list(ios)) return rc;
+  return J.publish(ios.data(), J.h_outs.data(), 48, pi_out, ch.ios_out);
+}
+
+// segmented: x, one, exp_val of every instance (a pad row repeats row M - 1) go up with aux = head[S], len[S] and the starts
+// ([start_count][96]); one workgroup per segment walks its own running product and the derived list comes back
+static int fq12_trace_segmented(sbn_prover* P, const BatchIn& mb, size_t K, uint64_t* pi_out) {
+  if (int rc = msm_batch_check_inputs(P->air.kind, mb.terms, mb.lengths, mb.segments, mb.starts, mb.start_count, mb.M)) return rc;
+  Fq12Job J(P, K);
+  const size_t S = mb.segments;
+  const uint32_t one[96] = {1};
+  std::vector<uint32_t> aux, seg_len, ios;
+  const std::vector<uint32_t> prelim = preliminary_list(mb.terms, mb.lengths, S, mb.M, K, 96, J.IOW - 192, [&](size_t) { return one; }, aux, seg_len);
+  aux.insert(aux.end(), seg_len.begin(), seg_len.end());
+  aux.insert(aux.end(), mb.starts, mb.starts + 96 * mb.start_count);
+  uint32_t* d_aux = (uint32_t*)J.take(aux.size() / 2 + 1);
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+  J.common_columns();
+  J.device_chains();
+  hipLaunchKernelGGL(tg::fq12_seg_scan_kernel, dim3((unsigned)S), dim3(192), 0, J.st, J.d_ios, J.IOW, K, mb.M, d_aux, d_aux + S, d_aux + 2 * S, mb.start_count, J.d_outs);
+  J.rebase();
+  if (int rc = J.witness_and_range_check(K * 48)) return rc;
+  if (int rc = J.download_list(ios)) return rc;
+  const int rc = J.publish(ios.data(), J.h_outs.data(), 48, pi_out, mb.ios_out);
+  if (rc == SBN_OK && mb.finals_out)   // [segments][96] u32 = the outputs of the segment tails, standard form
+    for (size_t s = 0; s < S; s++) {
+      const u64* out = J.h_outs.data() + 48 * (size_t)(aux[s] + aux[S + s] - 1);
+      for (size_t i = 0; i < 48; i++) { mb.finals_out[96 * s + 2 * i] = (uint32_t)out[i]; mb.finals_out[96 * s + 2 * i + 1] = (uint32_t)(out[i] >> 32); }
+    }
+  return rc;
+}
+
+// towers: x of level 0, zeros above it (the device writes them), one and the tower's exponent go up, a pad row repeating row
+// M - 1; one workgroup per tower links and walks its levels, the pads are filled behind them, and the outputs (= the powers) come
+// back together with the derived list in one download: the job carved them as one block
+static int fq12_trace_towers(sbn_prover* P, const PowerIn& pw, size_t K, uint64_t* pi_out) {
+  if (int rc = power_check_inputs(P->air.kind, pw.bases, pw.exps, pw.exp_count, pw.count)) return rc;
+  Fq12Job J(P, K);
+  const size_t IOW = J.IOW, ew = IOW - 192, M = pw.count * pw.depth;   // M real instances; rows [M, K) are pads
+  std::vector<uint32_t> prelim(IOW * K, 0u);
+  for (size_t g = 0; g < K; g++) {
+    const size_t r = g < M ? g : M - 1, k = r / pw.depth;
+    uint32_t* io = prelim.data() + IOW * g;
+    if (r % pw.depth == 0) memcpy(io, pw.bases + 96 * k, 96 * sizeof(uint32_t));
+    io[96] = 1;
+    memcpy(io + 192, pw.exps + (pw.exp_count == 1 ? 0 : ew * k), ew * sizeof(uint32_t));
+  }
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  J.common_columns();
+  hipLaunchKernelGGL(tg::fq12_tower_kernel, dim3((unsigned)pw.count), dim3(320), 0, J.st, J.d_ios, IOW, J.steps, pw.depth, J.ca, J.cb, J.d_outs);
+  J.mark("tower_links");
+  if (M < K) hipLaunchKernelGGL(tg::fq12_tower_pad_kernel, dim3((unsigned)(K - M)), dim3(256), 0, J.st, J.d_ios, IOW, M, K, (size_t)(J.steps + 1) * 48, J.ca, J.cb, J.d_outs);
+  J.mark("tower_pads");
+  if (int rc = J.witness_and_range_check(K * 48 + (IOW * K + 1) / 2)) return rc;
+  const int rc = J.publish((const uint32_t*)(J.h_outs.data() + K * 48), J.h_outs.data(), 48, pi_out, pw.ios_out);
+  if (rc == SBN_OK && pw.powers_out)   // [count][depth][96] u32 = the outputs of the M real instances, standard form
+    for (size_t i = 0; i < 48 * M; i++) { pw.powers_out[2 * i] = (uint32_t)J.h_outs[i]; pw.powers_out[2 * i + 1] = (uint32_t)(J.h_outs[i] >> 32); }
   return rc;
 }
 
 // FqExpStark: chains on host threads (512 Montgomery products per instance), rows and the u16 range check on the device.
-static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
+static int fq_trace_explicit(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
   const size_t IOW = 24;
   if (int rc = check_below_p(ios, IOW, 2, K, "value")) return rc;
   HIPC(hipSetDevice(P->device));
@@ -597,16 +709,13 @@ static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K
   if (int rc = pinned_reserve(&P->h_chain, &P->h_chain_words, 2 * cw)) return rc;
   tracegen_host_chains_fq(ios, K, P->h_chain, P->h_chain + cw);
   HIPC(hipMemcpyAsync(ca, P->h_chain, 2 * cw * sizeof(u64), hipMemcpyHostToDevice, st));  // ca and cb are adjacent
-  J.mark();
+  J.mark("chains");
   hipLaunchKernelGGL(tg::fq_row_kernel, blocks(n, 128), dim3(128), 0, st, d_ios, ca, cb, n, P->d_trace, d_err);
-  J.mark();
+  J.mark("row_witness");
   if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
-  J.mark();
-  HIPC(hipGetLastError());
   int err = 0;
   HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-  static const char* const names[] = {"flags+pulses", "chains", "row_witness", "range_check"};
-  if (int rc = J.end(names)) return rc;
+  if (int rc = J.end()) return rc;
   // public inputs: x, offset, exp_val, output = b at the last row, as u32 limbs (fq/exp.rs:98-108)
   return J.finish(err, pi_out, [&](size_t k, u64* p) {
     for (size_t i = 0; i < IOW; i++) p[i] = ios[IOW * k + i];
@@ -615,125 +724,117 @@ static int generate_trace_device_fq(sbn_prover* P, const uint32_t* ios, size_t K
   });
 }
 
-// sbn_prover_generate_trace on the list sbn_chain_instances derives from (terms, start), the offsets built on the device where the
-// chains already run there: G1 / G2 under chain_mode 1 and 2, Fq12 / Fq12U64 unless SBN_FQ12_HOST_CHAIN.  Elsewhere (host-pool
-// curve chains, FqExpStark) the chains are host work anyway and so is the list.
-extern "C" int sbn_prover_generate_trace_chained(sbn_prover* P, const uint32_t* terms, size_t num_io, const uint32_t* start, uint64_t* pi_out, uint32_t* ios_out) {
+// ---- the entry points: argument checks of their own, the gate, then the explicit-list fallback or the source's driver -------------
+// every entry point starts here, before any check: a refused call must not leave the previous trace provable
+static int unload(sbn_prover* P) {
   if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->loaded = false;   // before any check, as sbn_prover_generate_trace
-  if (!terms || !start) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->loaded = false;
+  return 0;
+}
+static bool is_fq12(int kind) { return kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64; }
+// what every entry point asks of the prover.  *device_chains: the table's chains run on the device (G1 / G2 under chain_mode 1 and
+// 2, Fq12 / Fq12U64 unless SBN_FQ12_HOST_CHAIN), so a derived list is derived there; elsewhere (host-pool curve chains,
+// FqExpStark) the chains are host work anyway and so is the list
+static int trace_gate(sbn_prover* P, size_t num_io, bool* device_chains) {
   const int kind = P->air.kind;
   if (!is_exp_air(kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
   if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
   if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  const bool fq12 = kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64;
-  if (!fq12 && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
-  if (kind == SBN_AIR_FQ_EXP || (fq12 ? P->set.fq12_host_chain : P->chain_mode == 0)) {
-    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
-    if (int rc = chain_instances_host(kind, terms, num_io, start, ios.data(), nullptr)) return rc;
-    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
-    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
-    return rc;
-  }
-  const ChainedIn ch{terms, start, ios_out};
-  if (fq12) return generate_trace_device_fq12(P, nullptr, num_io, pi_out, &ch);
-  return kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, nullptr, num_io, pi_out, &ch) : generate_trace_device<2>(P, nullptr, num_io, pi_out, &ch);
+  if (!is_fq12(kind) && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  *device_chains = kind != SBN_AIR_FQ_EXP && (is_fq12(kind) ? !P->set.fq12_host_chain : P->chain_mode != 0);
+  return 0;
+}
+// the fallback: `derive(ios)` writes the explicit list on the host and the explicit call takes it
+template <typename Derive>
+static int trace_from_host_list(sbn_prover* P, size_t num_io, uint64_t* pi_out, uint32_t* ios_out, Derive derive) {
+  std::vector<uint32_t> ios(exp_io_words(P->air.kind) * num_io);
+  if (int rc = derive(ios.data())) return rc;
+  const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
+  if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
+  return rc;
 }
 
-// sbn_prover_generate_trace on the list sbn_scalar_mul_instances derives from (points, scalars, offset), one unit: where the curve
-// chains run on the device (chain_mode 1 and 2) the list is expanded and un-offset there; with host-pool chains the list is host
-// work anyway and takes the explicit path.
+extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
+  if (int rc = unload(P)) return rc;
+  if (!ios) return fail(SBN_ERR_BAD_ARG, "null argument");
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  const int kind = P->air.kind;
+  if (is_fq12(kind)) return fq12_trace_explicit(P, ios, num_io, pi_out);
+  if (kind == SBN_AIR_FQ_EXP) return fq_trace_explicit(P, ios, num_io, pi_out);
+  return kind == SBN_AIR_G1_EXP ? curve_trace_explicit<1>(P, ios, num_io, pi_out) : curve_trace_explicit<2>(P, ios, num_io, pi_out);
+}
+
+// sbn_prover_generate_trace on the list sbn_chain_instances derives from (terms, start)
+extern "C" int sbn_prover_generate_trace_chained(sbn_prover* P, const uint32_t* terms, size_t num_io, const uint32_t* start, uint64_t* pi_out, uint32_t* ios_out) {
+  if (int rc = unload(P)) return rc;
+  if (!terms || !start) return fail(SBN_ERR_BAD_ARG, "null argument");
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  const int kind = P->air.kind;
+  if (!device_chains) return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) { return chain_instances_host(kind, terms, num_io, start, ios, nullptr); });
+  const ChainedIn ch{terms, start, ios_out};
+  if (is_fq12(kind)) return fq12_trace_chained(P, ch, num_io, pi_out);
+  return kind == SBN_AIR_G1_EXP ? curve_trace_chained<1>(P, ch, num_io, pi_out) : curve_trace_chained<2>(P, ch, num_io, pi_out);
+}
+
+// sbn_prover_generate_trace on the list sbn_scalar_mul_instances derives from (points, scalars, offset), one unit
 extern "C" int sbn_prover_generate_trace_scalar_muls(sbn_prover* P, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t num_io,
                                                      const uint32_t* offset, uint64_t* pi_out, uint32_t* products_out, uint8_t* infinity_out, uint32_t* ios_out) {
-  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  if (int rc = unload(P)) return rc;
   const int kind = P->air.kind;
   if (kind != SBN_AIR_G1_EXP && kind != SBN_AIR_G2_EXP) return fail(SBN_ERR_UNSUPPORTED, "scalar multiplications cover the curve tables G1_EXP and G2_EXP");
   if (!points || !scalars || num_io == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no instance");
   if (scalar_count != 1 && scalar_count != num_io) return fail(SBN_ERR_BAD_ARG, "scalar_count must be 1 (one shared scalar) or count = %zu, got %zu", num_io, scalar_count);
-  if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
-  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  if (P->n < 65536 || P->n > 262144) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
   const int E = kind == SBN_AIR_G1_EXP ? 1 : 2;
   if (!offset) offset = curve_generator_words(E);
-  if (P->chain_mode == 0) {
-    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
-    if (int rc = sbn_scalar_mul_instances(kind, points, scalars, scalar_count, num_io, num_io, offset, ios.data(), products_out, infinity_out)) return rc;
-    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
-    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
-    return rc;
-  }
+  if (!device_chains)
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) {
+      return sbn_scalar_mul_instances(kind, points, scalars, scalar_count, num_io, num_io, offset, ios, products_out, infinity_out);
+    });
   const ScalarMulIn sm{points, scalars, scalar_count, offset, products_out, infinity_out, ios_out};
-  return E == 1 ? generate_trace_device<1>(P, nullptr, num_io, pi_out, nullptr, &sm) : generate_trace_device<2>(P, nullptr, num_io, pi_out, nullptr, &sm);
+  return E == 1 ? curve_trace_scalar_muls<1>(P, sm, num_io, pi_out) : curve_trace_scalar_muls<2>(P, sm, num_io, pi_out);
 }
 
-// sbn_prover_generate_trace on the one-unit list sbn_msm_batch_instances derives from (terms, lengths, starts): where the table's
-// chains run on the device (G1 / G2 under chain_mode 1 and 2, Fq12 / Fq12U64 unless SBN_FQ12_HOST_CHAIN) the offsets, the finals and
-// the sums are derived there; elsewhere (host-pool curve chains, FqExpStark) the list is host work anyway and takes the explicit path.
+// sbn_prover_generate_trace on the one-unit list sbn_msm_batch_instances derives from (terms, lengths, starts)
 extern "C" int sbn_prover_generate_trace_msm_batch(sbn_prover* P, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts,
                                                    size_t start_count, uint64_t* pi_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out,
                                                    uint32_t* ios_out) {
-  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  if (int rc = unload(P)) return rc;
   const int kind = P->air.kind;
   const size_t num_io = P->air.num_io;
   size_t M = 0;
   if (int rc = msm_batch_check_args(kind, terms, lengths, segments, &starts, &start_count, num_io, sums_out, infinity_out, &M)) return rc;
   if (M > num_io) return fail(SBN_ERR_BAD_ARG, "%zu segments of %zu instances do not fit one unit of %zu instances", segments, M, num_io);
-  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  const bool fq12 = kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64;
-  if (!fq12 && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
-  if (kind == SBN_AIR_FQ_EXP || (fq12 ? P->set.fq12_host_chain : P->chain_mode == 0)) {
-    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
-    if (int rc = msm_batch_derive(kind, terms, lengths, segments, starts, start_count, M, num_io, ios.data(), finals_out, sums_out, infinity_out)) return rc;
-    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
-    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
-    return rc;
-  }
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  if (!device_chains)
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) {
+      return msm_batch_derive(kind, terms, lengths, segments, starts, start_count, M, num_io, ios, finals_out, sums_out, infinity_out);
+    });
   const BatchIn mb{terms, lengths, segments, starts, start_count, M, finals_out, sums_out, infinity_out, ios_out};
-  if (fq12) return generate_trace_device_fq12(P, nullptr, num_io, pi_out, nullptr, nullptr, &mb);
-  return kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, nullptr, num_io, pi_out, nullptr, nullptr, &mb)
-                                : generate_trace_device<2>(P, nullptr, num_io, pi_out, nullptr, nullptr, &mb);
+  if (is_fq12(kind)) return fq12_trace_segmented(P, mb, num_io, pi_out);
+  return kind == SBN_AIR_G1_EXP ? curve_trace_segmented<1>(P, mb, num_io, pi_out) : curve_trace_segmented<2>(P, mb, num_io, pi_out);
 }
 
-// sbn_prover_generate_trace on the one-unit list sbn_power_instances derives from (bases, exps, depth): on an Fq12 table whose
-// chains run on the device the towers are linked and walked there (one workgroup per tower) and the pads filled there; FqExpStark
-// (host-pool chains) and an Fq12 prover under SBN_FQ12_HOST_CHAIN walk the towers on the host pool and take the explicit path.
+// sbn_prover_generate_trace on the one-unit list sbn_power_instances derives from (bases, exps, depth)
 extern "C" int sbn_prover_generate_trace_powers(sbn_prover* P, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count, size_t depth,
                                                 uint64_t* pi_out, uint32_t* powers_out, uint32_t* ios_out) {
-  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->loaded = false;   // before any check, as sbn_prover_generate_trace
+  if (int rc = unload(P)) return rc;
   const int kind = P->air.kind;
   if (!power_elem_words(kind)) return fail(SBN_ERR_UNSUPPORTED, "field powers cover the field tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64");
   if (!bases || !exps || count == 0 || depth == 0) return fail(SBN_ERR_BAD_ARG, "null argument, no tower or depth = 0");
   if (exp_count != 1 && exp_count != count) return fail(SBN_ERR_BAD_ARG, "exp_count must be 1 (one shared exponent) or count = %zu, got %zu", count, exp_count);
   const size_t num_io = P->air.num_io;
   if (count > num_io || depth > num_io / count) return fail(SBN_ERR_BAD_ARG, "%zu towers of depth %zu do not fit one unit of %zu instances", count, depth, num_io);
-  if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  const bool fq12 = kind != SBN_AIR_FQ_EXP;
-  if (!fq12 && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
-  if (!fq12 || P->set.fq12_host_chain) {
-    std::vector<uint32_t> ios(exp_io_words(kind) * num_io);
-    if (int rc = sbn_power_instances(kind, bases, exps, exp_count, count, depth, num_io, ios.data(), powers_out)) return rc;
-    const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
-    if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
-    return rc;
-  }
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  if (!device_chains)
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) { return sbn_power_instances(kind, bases, exps, exp_count, count, depth, num_io, ios, powers_out); });
   const PowerIn pw{bases, exps, exp_count, count, depth, powers_out, ios_out};
-  return generate_trace_device_fq12(P, nullptr, num_io, pi_out, nullptr, &pw);
-}
-
-extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
-  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->loaded = false;   // before any check: a refused instance list must not leave the previous trace provable
-  if (!ios) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (!is_exp_air(P->air.kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
-  if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
-  if (P->n != exp_rows_per_instance(P->air.kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  if (P->air.kind == SBN_AIR_FQ12_EXP || P->air.kind == SBN_AIR_FQ12_EXP_U64) return generate_trace_device_fq12(P, ios, num_io, pi_out);
-  if (P->n < 65536 || P->n > 262144) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
-  if (P->air.kind == SBN_AIR_FQ_EXP) return generate_trace_device_fq(P, ios, num_io, pi_out);
-  return P->air.kind == SBN_AIR_G1_EXP ? generate_trace_device<1>(P, ios, num_io, pi_out) : generate_trace_device<2>(P, ios, num_io, pi_out);
+  return fq12_trace_towers(P, pw, num_io, pi_out);
 }
 
 extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
