@@ -182,6 +182,28 @@ int sbn_generate_trace_flags_u64(const uint64_t* exps, size_t num_io, uint64_t* 
  * 2n points, every 2^(r-1)-th row of the LDE, as starky does (the section on rate_bits).  fri_arity_bits = 1: a FRI leaf is two extension values = four words, which is its own digest
  * (plonky2 hash_or_noop), as the rows of a matrix of at most four columns are. */
 int sbn_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, sbn_prover** out);
+/* How a context stores the coset LDEs of its trace and Z matrices between the commitment and the queries.
+ * SBN_LDE_FULL: whole, [cols][n << rate_bits] each (what sbn_prover_create does).
+ * SBN_LDE_COMPACT (rate_bits > 1): a matrix of more than 4 columns keeps only the rows the quotient reads, [cols][2n]; the LDE of a
+ * column chunk lives in a small ring between its transform and the leaf sponge, and the rows a query opens are evaluated again
+ * from the coefficients.  Same proof words; device memory per wide column falls from (2 + 2^rate_bits) n to 4 n words.  Matrices of
+ * at most 4 columns (their rows are their own digests) stay whole in both modes. */
+enum { SBN_LDE_FULL = 0, SBN_LDE_COMPACT = 1 };
+typedef struct sbn_prover_options { uint32_t struct_size; uint32_t lde_storage; } sbn_prover_options;
+/* sbn_prover_create with options; opt == NULL or lde_storage = SBN_LDE_FULL is exactly sbn_prover_create.  Checked before a device
+ * is looked for, in this order: struct_size != sizeof the struct or an unknown lde_storage: SBN_ERR_BAD_ARG; then the refusals of
+ * sbn_prover_create, and SBN_LDE_COMPACT with rate_bits 1: SBN_ERR_UNSUPPORTED (the quotient's domain is the whole LDE there,
+ * qn = m, so nothing would be dropped), and SBN_LDE_COMPACT for a table with more than 4 trace columns and 1..4 Z columns (no
+ * table has that shape; its quotient would need two row strides): SBN_ERR_UNSUPPORTED.  sbn_prover_describe reports
+ * lde=full|compact, the ring depth and its bytes.
+ * Known defect, in both storage modes and older than this option: a batch prover with three contexts in
+ * flight has returned wrong proofs for units after a context's first; one and two contexts in flight have not. */
+int sbn_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_prover_options* opt, sbn_prover** out);
+/* Device bytes sbn_prover_create_with allocates at creation (dev_bytes of sbn_prover_describe right after it), computed without a
+ * device from the list of buffers the creation itself allocates from; the same argument checks.  Outside the plan, allocated by
+ * the first call that needs them: 8 bytes of device memory for the canonical-form scan of sbn_prover_prove_host_trace (its upload
+ * ring is pinned host memory, 64 MiB). */
+int sbn_prover_memory_plan(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_prover_options* opt, uint64_t* bytes_out);
 void sbn_prover_destroy(sbn_prover* p);
 /* Host -> device copy of the trace (PCIe-inclusive path). */
 int sbn_prover_load_trace(sbn_prover* p, const uint64_t* trace_col_major, const uint64_t* public_inputs, size_t n_pi);
@@ -382,6 +404,9 @@ int sbn_prove_cache_stats(uint64_t out[6]);
  * of `G1ExpStarkyProofGenerator::run_once` calls over chunks of 128 instances (src/curves/g1/circuit.rs:161-202). */
 typedef struct sbn_batch_prover sbn_batch_prover;
 int sbn_batch_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t inflight, sbn_batch_prover** out);
+/* The same with the options of sbn_prover_create_with for every context of the batch (NULL: as above). */
+int sbn_batch_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t inflight, const sbn_prover_options* opt,
+                                 sbn_batch_prover** out);
 int sbn_batch_prover_prove_ios(sbn_batch_prover* b, const uint32_t* ios, size_t ios_words_per_unit, size_t num_io, size_t count, sbn_proof** proofs_out);
 void sbn_batch_prover_destroy(sbn_batch_prover* b);
 
@@ -701,6 +726,13 @@ void sbn_verifier_destroy(sbn_verifier* v);
  * SBN_ERR_UNSUPPORTED.  Runs the transform plan and the kernels a prover of n rows and this rate_bits runs. */
 int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height,
                       uint64_t* cap_out, uint64_t* coeffs_out, uint64_t* lde_out);
+/* The twin of sbn_commit_values for SBN_LDE_COMPACT: rows of the coset LDE at rate_bits, computed from the values by the compact
+ * mode's own kernels (values -> coefficients through the transform plan of a prover of this height, then the evaluation at the
+ * opened points).  leaf_indices[k] < 2^(degree_bits + rate_bits) is a Merkle leaf index, i.e. LDE row bitrev(leaf index), as the
+ * query indices of a proof are (SBN_ERR_BAD_ARG beyond); 1 <= count <= 65536 (SBN_ERR_BAD_ARG otherwise); rows_out: [count][ncols].  rate_bits 1..3, degree_bits >= 9,
+ * degree_bits + rate_bits <= 23, otherwise SBN_ERR_UNSUPPORTED.  Host in/out. */
+int sbn_lde_rows(const uint64_t* values_col_major, size_t ncols, uint32_t degree_bits, uint32_t rate_bits, const uint32_t* leaf_indices, size_t count,
+                 uint64_t* rows_out);
 /* Poseidon permutation of `count` independent width-12 states on the device (host in/out). */
 int sbn_poseidon_permute_batch(uint64_t* states, size_t count);
 /* out[i] = a[i] * b[i] in the Goldilocks field with the DEVICE multiply of every kernel (csrc/gl.cuh: 13-instruction weak product +

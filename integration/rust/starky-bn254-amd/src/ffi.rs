@@ -24,6 +24,16 @@ pub struct sbn_config {
     pub fri_variant: u32,
 }
 
+/// sbn_prover_options.lde_storage
+pub const SBN_LDE_FULL: u32 = 0;
+pub const SBN_LDE_COMPACT: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct sbn_prover_options {
+    pub struct_size: u32,
+    pub lde_storage: u32,
+}
+
 #[repr(C)]
 pub struct sbn_prover {
     _opaque: [u8; 0],
@@ -105,6 +115,8 @@ extern "C" {
     pub fn sbn_air_num_public_inputs(air: *const sbn_air_desc) -> usize;
 
     pub fn sbn_prover_create(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, out: *mut *mut sbn_prover) -> i32;
+    pub fn sbn_prover_create_with(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, opt: *const sbn_prover_options, out: *mut *mut sbn_prover) -> i32;
+    pub fn sbn_prover_memory_plan(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, opt: *const sbn_prover_options, bytes_out: *mut u64) -> i32;
     pub fn sbn_prover_destroy(p: *mut sbn_prover);
     pub fn sbn_prover_load_trace(p: *mut sbn_prover, trace_col_major: *const u64, public_inputs: *const u64, n_pi: usize) -> i32;
     pub fn sbn_prover_generate_trace(p: *mut sbn_prover, ios: *const u32, num_io: usize, pi_out: *mut u64) -> i32;
@@ -132,6 +144,8 @@ extern "C" {
     pub fn sbn_settings_check(out: *mut c_char, cap: usize) -> i32;
 
     pub fn sbn_batch_prover_create(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, inflight: u32, out: *mut *mut sbn_batch_prover) -> i32;
+    pub fn sbn_batch_prover_create_with(air: *const sbn_air_desc, cfg: *const sbn_config, degree_bits: u32, inflight: u32, opt: *const sbn_prover_options, out: *mut *mut sbn_batch_prover) -> i32;
+    pub fn sbn_lde_rows(values_col_major: *const u64, ncols: usize, degree_bits: u32, rate_bits: u32, leaf_indices: *const u32, count: usize, rows_out: *mut u64) -> i32;
     pub fn sbn_batch_prover_prove_ios(b: *mut sbn_batch_prover, ios: *const u32, ios_words_per_unit: usize, num_io: usize, count: usize, proofs_out: *mut *mut sbn_proof) -> i32;
     pub fn sbn_batch_prover_destroy(b: *mut sbn_batch_prover);
     pub fn sbn_msm_num_units(count: usize, num_io: usize) -> usize;

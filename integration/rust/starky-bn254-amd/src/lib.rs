@@ -105,12 +105,51 @@ pub struct Prover {
 // one prover belongs to one thread at a time (include/sbn.h, "Threading")
 unsafe impl Send for Prover {}
 
+/// How a prover context stores the LDEs of its wide matrices (include/sbn.h, sbn_prover_options.lde_storage).
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)]
+pub enum LdeStorage {
+    /// every LDE whole in device memory
+    #[default]
+    Full,
+    /// rate_bits > 1: only the rows the quotient reads are kept, the opened rows are recomputed from the coefficients; same proofs
+    Compact,
+}
+
+#[derive(Clone, Copy, Debug, Default)]
+pub struct ProverOptions {
+    pub lde_storage: LdeStorage,
+}
+
+impl ProverOptions {
+    fn raw(&self) -> ffi::sbn_prover_options {
+        ffi::sbn_prover_options {
+            struct_size: std::mem::size_of::<ffi::sbn_prover_options>() as u32,
+            lde_storage: if self.lde_storage == LdeStorage::Compact { ffi::SBN_LDE_COMPACT } else { ffi::SBN_LDE_FULL },
+        }
+    }
+}
+
+/// Device bytes `Prover::with_options` allocates at creation (sbn_prover_memory_plan); needs no device.
+pub fn prover_memory_plan(stark: &impl SbnTable, config: &StarkConfig, degree_bits: usize, options: &ProverOptions) -> Result<u64> {
+    let a = air(stark);
+    let cfg = to_sbn_config(config)?;
+    let opt = options.raw();
+    let mut bytes = 0u64;
+    check(unsafe { ffi::sbn_prover_memory_plan(&a, &cfg, degree_bits as u32, &opt, &mut bytes) }, "sbn_prover_memory_plan")?;
+    Ok(bytes)
+}
+
 impl Prover {
     pub fn new(stark: &impl SbnTable, config: &StarkConfig, degree_bits: usize) -> Result<Self> {
+        Self::with_options(stark, config, degree_bits, &ProverOptions::default())
+    }
+
+    pub fn with_options(stark: &impl SbnTable, config: &StarkConfig, degree_bits: usize, options: &ProverOptions) -> Result<Self> {
         let a = air(stark);
         let cfg = to_sbn_config(config)?;
+        let opt = options.raw();
         let mut raw = ptr::null_mut();
-        check(unsafe { ffi::sbn_prover_create(&a, &cfg, degree_bits as u32, &mut raw) }, "sbn_prover_create")?;
+        check(unsafe { ffi::sbn_prover_create_with(&a, &cfg, degree_bits as u32, &opt, &mut raw) }, "sbn_prover_create_with")?;
         // u32 words of one instance in `ios` (include/sbn.h, per table)
         let io_words = match a.kind {
             ffi::SBN_AIR_G1_EXP => 40,

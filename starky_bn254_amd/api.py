@@ -50,6 +50,7 @@ EXPORTS = [
     "sbn_abi_version", "sbn_rccl_unique_id", "sbn_rccl_comm_create", "sbn_rccl_comm_destroy",
     "sbn_local_comm_create", "sbn_local_comm_abort", "sbn_local_comm_destroy", "sbn_comm_selftest",
     "sbn_verifier_create", "sbn_verifier_verify", "sbn_verifier_reason", "sbn_verifier_stage_times", "sbn_verifier_destroy",
+    "sbn_prover_create_with", "sbn_batch_prover_create_with", "sbn_prover_memory_plan", "sbn_lde_rows",
 ]
 
 
@@ -70,6 +71,29 @@ class _Config(C.Structure):
 
 
 FRI_DEFAULT, FRI_TIMES_X, FRI_PLAIN = 0, 1, 2   # sbn_fri_variant (include/sbn.h)
+
+
+class _ProverOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("lde_storage", C.c_uint32)]
+
+
+LDE_STORAGE = {"full": 0, "compact": 1}   # SBN_LDE_FULL, SBN_LDE_COMPACT
+
+
+def _prover_options(lde):
+    """The sbn_prover_options of an `lde=` argument: None stands for no options at all, a name for its mode, an integer for itself
+    (so that a caller can hand the library a mode it does not know)."""
+    if lde is None:
+        return None
+    if isinstance(lde, str):
+        if lde not in LDE_STORAGE:
+            raise ValueError(f"lde must be one of {sorted(LDE_STORAGE)}, not {lde!r}")
+        lde = LDE_STORAGE[lde]
+    return _ProverOptions(C.sizeof(_ProverOptions), int(lde))
+
+
+def _opt_ref(opt):
+    return C.byref(opt) if opt is not None else None
 
 
 class _TraceReport(C.Structure):
@@ -127,6 +151,11 @@ def lib():
         L.sbn_generate_trace_flags.argtypes = [vp, sz, vp]
         L.sbn_generate_trace_flags_u64.argtypes = [vp, sz, vp]
         L.sbn_prover_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, C.POINTER(vp)]
+        if hasattr(L, "sbn_prover_create_with"):   # (an older build named by SBN_LIB for an A/B lacks the four: full contexts still work with it)
+            L.sbn_prover_create_with.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, C.POINTER(_ProverOptions), C.POINTER(vp)]
+            L.sbn_batch_prover_create_with.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(_ProverOptions), C.POINTER(vp)]
+            L.sbn_prover_memory_plan.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, C.POINTER(_ProverOptions), C.POINTER(C.c_uint64)]
+            L.sbn_lde_rows.argtypes = [vp, sz, u32, u32, vp, sz, vp]
         L.sbn_prover_destroy.argtypes = [vp]
         L.sbn_prover_load_trace.argtypes = [vp, vp, vp, sz]
         L.sbn_prover_load_trace_device.argtypes = [vp, vp, vp, sz]
@@ -1134,12 +1163,20 @@ def explain_trace_host(stark, trace, public_inputs, seed=0):
 
 
 class Prover:
-    """Device context for one (table, degree_bits): buffers stay allocated across proofs."""
+    """Device context for one (table, degree_bits): buffers stay allocated across proofs.  lde="compact" (rate_bits > 1): the
+    LDEs of the wide matrices are not kept, the opened rows are recomputed from the coefficients (include/sbn.h SBN_LDE_COMPACT);
+    the proofs are the same words."""
 
-    def __init__(self, stark, config, degree_bits):
+    def __init__(self, stark, config, degree_bits, lde="full"):
         self.stark, self.config, self.degree_bits = stark, config, degree_bits
         self._h = C.c_void_p()
-        _check(lib().sbn_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, C.byref(self._h)))
+        opt = _prover_options(lde)
+        # by the header's contract the same call; so the "full" path of this class never enters sbn_prover_create_with (a GPU test calls
+        # it with SBN_LDE_FULL through ctypes), and a library named by SBN_LIB that lacks the new entry points still serves it
+        if opt is None or opt.lde_storage == LDE_STORAGE["full"]:
+            _check(lib().sbn_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, C.byref(self._h)))
+        else:
+            _check(lib().sbn_prover_create_with(C.byref(stark._d), C.byref(config._c), degree_bits, C.byref(opt), C.byref(self._h)))
 
     def load_trace(self, trace, public_inputs):
         trace = np.ascontiguousarray(trace, dtype=np.uint64)
@@ -1291,10 +1328,14 @@ class Prover:
 class BatchProver:
     """`inflight` prover contexts on one GPU: proves a batch of instance lists (witness generated on the device)."""
 
-    def __init__(self, stark, config, degree_bits, inflight=3):
+    def __init__(self, stark, config, degree_bits, inflight=3, lde="full"):
         self.stark, self.config, self.degree_bits = stark, config, degree_bits
         self._h = C.c_void_p()
-        _check(lib().sbn_batch_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, inflight, C.byref(self._h)))
+        opt = _prover_options(lde)
+        if opt is None or opt.lde_storage == LDE_STORAGE["full"]:
+            _check(lib().sbn_batch_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, inflight, C.byref(self._h)))
+        else:
+            _check(lib().sbn_batch_prover_create_with(C.byref(stark._d), C.byref(config._c), degree_bits, inflight, C.byref(opt), C.byref(self._h)))
 
     def _unit_buffers(self, count, words):
         """(ios, out) for `count` instances of `words` u32 each cut into units: the (units, num_io, words) list buffer and the
@@ -1544,6 +1585,24 @@ def commit_values(cols, rate_bits=1, cap_height=4, want_coeffs=False, want_lde=F
     lde = np.zeros((ncols, n << rate_bits), dtype=np.uint64) if want_lde else None
     _check(lib().sbn_commit_values(_ptr(cols), ncols, n, rate_bits, cap_height, _ptr(cap), _ptr(coeffs), _ptr(lde)))
     return cap, coeffs, lde
+
+
+def prover_memory_plan(stark, config, degree_bits, lde="full"):
+    """Device bytes Prover(stark, config, degree_bits, lde=lde) allocates at creation; needs no device.  lde=None: no options."""
+    out = C.c_uint64(0)
+    _check(lib().sbn_prover_memory_plan(C.byref(stark._d), C.byref(config._c), degree_bits, _opt_ref(_prover_options(lde)), C.byref(out)))
+    return int(out.value)
+
+
+def lde_rows(cols, rate_bits, leaf_indices):
+    """Rows of the coset LDE of `cols` (ncols, n) at Merkle leaf indices `leaf_indices`, evaluated from the coefficients by the
+    kernels of the compact storage -> (len(leaf_indices), ncols)."""
+    cols = np.ascontiguousarray(cols, dtype=np.uint64)
+    idx = np.ascontiguousarray(leaf_indices, dtype=np.uint32)
+    ncols, n = cols.shape
+    out = np.zeros((len(idx), ncols), dtype=np.uint64)
+    _check(lib().sbn_lde_rows(_ptr(cols), ncols, max(n.bit_length() - 1, 0), rate_bits, _ptr(idx), len(idx), _ptr(out)))
+    return out
 
 
 def poseidon_permute_batch(states):

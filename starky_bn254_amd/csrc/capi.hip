@@ -158,6 +158,11 @@ int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* tr
 struct sbn_batch_prover { std::vector<sbn_prover*> provers; int kind = 0; uint32_t num_io = 0; };
 
 int sbn_batch_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t inflight, sbn_batch_prover** out) {
+  return sbn_batch_prover_create_with(air, cfg, degree_bits, inflight, nullptr, out);
+}
+// opt: every context of the batch is created with it (sbn_prover_create_with checks it)
+int sbn_batch_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t inflight, const sbn_prover_options* opt,
+                                 sbn_batch_prover** out) {
   if (!out || inflight == 0 || inflight > 16) return fail(SBN_ERR_BAD_ARG, "bad arguments (1 <= inflight <= 16)");
   *out = nullptr;
   if (!air) return fail(SBN_ERR_BAD_ARG, "null argument");
@@ -165,7 +170,7 @@ int sbn_batch_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint
   B->kind = air->kind; B->num_io = air->num_io;
   for (uint32_t i = 0; i < inflight; i++) {
     sbn_prover* P = nullptr;
-    int rc = sbn_prover_create(air, cfg, degree_bits, &P);
+    int rc = sbn_prover_create_with(air, cfg, degree_bits, opt, &P);
     if (rc) { for (auto q : B->provers) sbn_prover_destroy(q); delete B; return rc; }
     B->provers.push_back(P);
   }

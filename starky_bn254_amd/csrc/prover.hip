@@ -176,7 +176,9 @@ static int intt_then_lde(sbn_prover* P, const u64* vals, u64* coef, u64* lde, si
 // (kernels_ntt.cuh ntt_fused_inv_b_lde_a_kernel at 2^16 / 2^17 rows; ntt_fused512_inv_b_lde_a_kernel at 2^18 rows, where the LDE's
 // pass A is the 1,024-point one in two halves); the LDE's pass B follows on `lde_stream` (the main stream, or the second transform
 // stream behind `handoff`).  Three launches per chunk instead of four / five.
-static int intt_lde_cols_fused(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, size_t nc, u64* tmp2, hipStream_t lde_stream, hipEvent_t handoff) {
+// `before_write` (compact storage, else null): lde_out is a ring slot, and the stream of the pass that writes it waits for the event first.
+static int intt_lde_cols_fused(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, size_t nc, u64* tmp2, hipStream_t lde_stream, hipEvent_t handoff,
+                               hipEvent_t before_write = nullptr) {
   int rc = ntt_columns(P, v, P->n, cf, P->n, P->d_tmp, P->m, nc, P->degree_bits, true, P->n, nullptr, nullptr, host_inv_pow2(P->degree_bits), nullptr, 1);
   if (rc) return rc;
   NttFusedParams f{};
@@ -190,14 +192,23 @@ static int intt_lde_cols_fused(sbn_prover* P, const u64* v, u64* cf, u64* lde_ou
     HIPC(hipEventRecord(handoff, P->stream));
     HIPC(hipStreamWaitEvent(lde_stream, handoff, 0));
   }
+  if (before_write) HIPC(hipStreamWaitEvent(lde_stream, before_write, 0));
   return ntt_columns(P, cf, P->n, lde_out, P->m, tmp2, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1, lde_stream, 2);
 }
 // values -> coefficients -> coset LDE of nc columns (column strides n, n, m): the unit of the commit pipelines
-static int intt_lde_cols(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, size_t nc) {
-  if ((P->ntt_fused || P->ntt_fused512) && P->d_tmp2) return intt_lde_cols_fused(P, v, cf, lde_out, nc, P->d_tmp2, P->stream, nullptr);
+// coefficients -> coset LDE of nc columns on `st` through `tmp`; before_write as above: waited for between the two passes
+static int lde_cols(sbn_prover* P, const u64* cf, u64* lde_out, u64* tmp, size_t nc, hipStream_t st, hipEvent_t before_write) {
+  if (!before_write) return ntt_columns(P, cf, P->n, lde_out, P->m, tmp, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1, st);
+  int rc = ntt_columns(P, cf, P->n, lde_out, P->m, tmp, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1, st, 1);
+  if (rc) return rc;
+  HIPC(hipStreamWaitEvent(st, before_write, 0));
+  return ntt_columns(P, cf, P->n, lde_out, P->m, tmp, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1, st, 2);
+}
+static int intt_lde_cols(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, size_t nc, hipEvent_t before_write = nullptr) {
+  if ((P->ntt_fused || P->ntt_fused512) && P->d_tmp2) return intt_lde_cols_fused(P, v, cf, lde_out, nc, P->d_tmp2, P->stream, nullptr, before_write);
   int rc = ntt_columns(P, v, P->n, cf, P->n, P->d_tmp, P->m, nc, P->degree_bits, true, P->n, nullptr, nullptr, host_inv_pow2(P->degree_bits));
   if (rc) return rc;
-  return ntt_columns(P, cf, P->n, lde_out, P->m, P->d_tmp, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1);
+  return lde_cols(P, cf, lde_out, P->d_tmp, nc, P->stream, before_write);
 }
 
 static int tree_alloc(DevTree& t, size_t nleaf, u32 cap_height, size_t* bytes = nullptr) {
@@ -291,8 +302,18 @@ static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0
 // up (prove_host_trace only; null: nothing below is enqueued that was not before): `vals` is still on the host.  Chunk k is sent
 // on its way right before its transforms are enqueued, and the main stream -- which runs the first transform pass of a chunk in
 // all three branches below (fused two-stream, plain two-stream, one stream) -- waits for upload_done[k] first.
-static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t ncols, DevTree& t, int ex_ms, int ex_launches, const HostUpload* up = nullptr) {
+// dense (compact storage of a wide matrix; null: the LDE stays whole in `lde`): [ncols][qn], the quotient's rows.  The last LDE pass
+// of chunk k then writes ring slot k % ring_depth, the sponge reads the slot, lde_keep_rows_kernel behind it copies the slot's
+// quotient rows to `dense`, and ring_free[k] is recorded behind that; the stream that runs the writing pass of chunk
+// k + ring_depth waits for it in front of that pass -- the one dependency of the transforms on the hash stream.  (The first
+// ring_depth chunks of a commitment need no wait: the main stream has waited for hash_done of the commitment before, and the
+// second transform stream starts every chunk behind an event of the main stream.)
+static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t ncols, DevTree& t, int ex_ms, int ex_launches, const HostUpload* up = nullptr,
+                           u64* dense = nullptr) {
   size_t ch = P->ntt_chunk;
+  const bool ring = dense != nullptr && ncols > 4;
+  const size_t qn = 2 * P->n;
+  if (ring && (!P->d_ring || P->ring_depth == 0)) return fail(SBN_ERR_HIP, "internal: compact commitment without a chunk ring");
   size_t nchunks = (ncols + ch - 1) / ch;
   if (nchunks > (size_t)MAX_CHUNKS) return fail(SBN_ERR_UNSUPPORTED, "too many column chunks");
   if (ncols <= 4) {   // hash_or_noop: a leaf of at most 4 elements is its own digest (MyStark's 4 columns and its 2 Z columns)
@@ -314,6 +335,9 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
   for (size_t k = 0; k < nchunks; k++) {
     size_t c0 = k * ch, nc = std::min(ch, ncols - c0);
     int rc;
+    const u32 slot = ring ? (u32)(k % P->ring_depth) : 0;
+    u64* const lde_k = ring ? P->d_ring + (size_t)slot * ch * P->m : lde + c0 * P->m;
+    const hipEvent_t slot_free = (ring && k >= P->ring_depth) ? P->ring_free[k - P->ring_depth] : nullptr;
     if (up) {
       if ((rc = upload_chunk(P, *up, k, c0, nc))) return rc;
       HIPC(hipStreamWaitEvent(P->stream, up->done[k], 0));
@@ -321,7 +345,7 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
     if (P->ntt_two_streams && (P->ntt_fused || P->ntt_fused512) && P->d_tmp3) {
       // the fused kernel of chunk k writes buffer k & 1, which the LDE pass B of chunk k - 2 (second stream) must have left
       if (k >= 2) HIPC(hipStreamWaitEvent(P->stream, P->chunk_ready[k - 2], 0));
-      rc = intt_lde_cols_fused(P, vals + c0 * P->n, coef + c0 * P->n, lde + c0 * P->m, nc, (k & 1) ? P->d_tmp3 : P->d_tmp2, P->nstream, P->intt_done[k]);
+      rc = intt_lde_cols_fused(P, vals + c0 * P->n, coef + c0 * P->n, lde_k, nc, (k & 1) ? P->d_tmp3 : P->d_tmp2, P->nstream, P->intt_done[k], slot_free);
       if (rc) return rc;
       HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
     } else if (P->ntt_two_streams && !P->ntt_fused && !P->ntt_fused512) {
@@ -329,20 +353,25 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
       if (rc) return rc;
       HIPC(hipEventRecord(P->intt_done[k], P->stream));
       HIPC(hipStreamWaitEvent(P->nstream, P->intt_done[k], 0));
-      rc = ntt_columns(P, coef + c0 * P->n, P->n, lde + c0 * P->m, P->m, P->d_tmp2, P->m, nc, P->lde_log, false, P->n, P->d_shift, nullptr, 1, P->nstream);
+      rc = lde_cols(P, coef + c0 * P->n, lde_k, P->d_tmp2, nc, P->nstream, slot_free);
       if (rc) return rc;
       HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
     } else {
-      rc = intt_lde_cols(P, vals + c0 * P->n, coef + c0 * P->n, lde + c0 * P->m, nc);
+      rc = intt_lde_cols(P, vals + c0 * P->n, coef + c0 * P->n, lde_k, nc, slot_free);
       if (rc) return rc;
       HIPC(hipEventRecord(P->chunk_ready[k], P->stream));
     }
     HIPC(hipStreamWaitEvent(P->hstream, P->chunk_ready[k], 0));
     HIPC(hipEventRecord(P->abs_ev[2 * k], P->hstream));
-    hipLaunchKernelGGL(leaf_absorb_kernel, dim3((unsigned)((P->m + 255) / 256)), dim3(256), 0, P->hstream, lde + c0 * P->m, P->m, P->lde_log, (u32)nc,
+    hipLaunchKernelGGL(leaf_absorb_kernel, dim3((unsigned)((P->m + 255) / 256)), dim3(256), 0, P->hstream, lde_k, P->m, P->lde_log, (u32)nc,
                        P->d_sponge, k == 0 ? 1 : 0, k + 1 == nchunks ? 1 : 0, t.d,
                        (k + 1 < nchunks && std::min(ch, ncols - (c0 + nc)) >= 8) ? 1 : 0);
     HIPC(hipEventRecord(P->abs_ev[2 * k + 1], P->hstream));
+    if (ring) {
+      launch_lde_keep_rows(lde_k, P->m, dense + c0 * qn, qn, P->cfg.rate_bits - 1, nc, P->hstream);
+      HIPC(hipGetLastError());
+      HIPC(hipEventRecord(P->ring_free[k], P->hstream));
+    }
   }
   int rc = tree_build_inner(P, t, P->hstream);
   if (rc) return rc;
@@ -548,16 +577,24 @@ static int split_sizes(const AirShape& as, u32 degree_bits, u32 rate_bits, u32 w
   if (slot_words) *slot_words = slot;
   return 0;
 }
-static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, sbn_prover** out);
-extern "C" int sbn_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, sbn_prover** out) {
-  return create_ctx(air, cfg, degree_bits, nullptr, out);
-}
-static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, sbn_prover** out) {
-  if (!air || !cfg || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  *out = nullptr;
+// ---- what a context is made of --------------------------------------------------------------------------------------------
+// create_ctx runs in three steps so that sbn_prover_memory_plan can follow it without a device: ctx_check_args (the refusals that
+// need no device), ctx_shape (every size-bearing field of the context: transform plan, chunk, FRI shape, query stride, storage
+// mode) and ctx_buffers, the ONE list of (buffer, bytes) of a context.  create_ctx allocates the list, the plan sums it.
+struct BufReq { void** slot; size_t bytes; };
+static int ctx_check_args(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, const sbn_prover_options* opt, AirShape& as,
+                          u32& lde_storage) {
+  if (!air || !cfg) return fail(SBN_ERR_BAD_ARG, "null argument");
+  lde_storage = SBN_LDE_FULL;
+  if (opt) {
+    if (opt->struct_size != sizeof(sbn_prover_options)) return fail(SBN_ERR_BAD_ARG, "sbn_prover_options.struct_size does not match this library (ABI %d)", SBN_ABI_VERSION);
+    if (opt->lde_storage != SBN_LDE_FULL && opt->lde_storage != SBN_LDE_COMPACT) return fail(SBN_ERR_BAD_ARG, "unknown sbn_prover_options.lde_storage %u", opt->lde_storage);
+    lde_storage = opt->lde_storage;
+  }
   if (!config_supported(cfg)) return fail(SBN_ERR_UNSUPPORTED, "unsupported StarkConfig (need num_challenges=2, rate_bits 1 or 3, cap_height 1..8, fri_arity_bits 1..4)");
+  if (lde_storage == SBN_LDE_COMPACT && cfg->rate_bits == 1)
+    return fail(SBN_ERR_UNSUPPORTED, "SBN_LDE_COMPACT needs rate_bits > 1: at rate_bits 1 the quotient's domain is the whole LDE (qn = m), so nothing would be dropped");
   if (comm && cfg->rate_bits != 1) return fail(SBN_ERR_UNSUPPORTED, "the split prover covers rate_bits = 1 only");
-  AirShape as;
   if (!air_shape(air, cfg, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
   if (!height_supported(cfg, degree_bits)) return fail(SBN_ERR_UNSUPPORTED, "%s", HEIGHT_REFUSAL);
   if (as.kind == SBN_AIR_FLAGS && (512 * (size_t)as.num_io) != ((size_t)1 << degree_bits)) return fail(SBN_ERR_BAD_ARG, "FlagStark needs 512*num_io rows");
@@ -567,18 +604,15 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
     if (as.kind != SBN_AIR_FQ12_EXP && as.kind != SBN_AIR_FQ12_EXP_U64 && degree_bits < 16)
       return fail(SBN_ERR_UNSUPPORTED, "G1_EXP / G2_EXP / FQ_EXP need >= 2^16 rows (u16 range check, range_check.rs:26)");
   }
-  if (int rc = use_current_device("the prover path has no CPU fallback")) return rc;
-  sbn_prover* P = new sbn_prover();
+  // a wide trace beside a Z matrix of 1..4 columns would need two row strides in the quotient (no table has that shape)
+  if (lde_storage == SBN_LDE_COMPACT && as.ncols > 4 && as.nzs >= 1 && as.nzs <= 4) return fail(SBN_ERR_UNSUPPORTED, "SBN_LDE_COMPACT: a wide trace with at most 4 Z columns");
+  return 0;
+}
+static int ctx_shape(sbn_prover* P, const AirShape& as, const sbn_config* cfg, uint32_t degree_bits, u32 lde_storage) {
   P->air = as; P->cfg = *cfg; P->degree_bits = degree_bits; P->lde_log = degree_bits + cfg->rate_bits;
   P->n = (size_t)1 << degree_bits; P->m = (size_t)1 << P->lde_log;
   P->fri = fri_shape(*cfg, degree_bits);
-  P->device = g_device;
-  // every failure below releases what was created so far (sbn_prover_destroy accepts a partly built context) and
-  // returns the FIRST error code
-  int rc = 0;
-  auto acc = [&](int r) { if (!rc) rc = r; };
-  auto hipc = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(SBN_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
-  if (P->fri.total_arity() > degree_bits + cfg->rate_bits - cfg->cap_height) { sbn_prover_destroy(P); return fail(SBN_ERR_UNSUPPORTED, "FRI total reduction arity is too large"); }
+  if (P->fri.total_arity() > degree_bits + cfg->rate_bits - cfg->cap_height) return fail(SBN_ERR_UNSUPPORTED, "FRI total reduction arity is too large");
   // Column chunk of the commit pipeline: a multiple of 8 (the sponge permutes after every 8 absorbed columns, so any other
   // chunk boundary would change the leaf digests), between 8 and 256.
   // Default 64; 48 from 2^19 LDE rows up: a chunk's LDE (chunk * M * 8 bytes) is written by the transform stream and read by the
@@ -589,7 +623,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   P->ntt_chunk = P->lde_log >= 18 ? 48 : 64;
   {
     std::string serr;
-    if (!P->set.load(serr)) { sbn_prover_destroy(P); return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
+    if (!P->set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str());
   }
   const Settings& set = P->set;
   if (set.ntt_chunk) P->ntt_chunk = (size_t)set.ntt_chunk;
@@ -601,15 +635,137 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   // instance on the device (5.2 ms whatever the host share: an 8-rank node may leave a rank two CPUs, where the scalar host chains
   // take ~18 ms)
   P->chain_mode = set.device_chain >= 0 ? set.device_chain : ((tracegen_host_chains_vectorized() || tracegen_host_threads() >= 8) ? 0 : 2);
-  acc(ntt_fast_setup());
-  hipc(hipStreamCreate(&P->stream), "hipStreamCreate");
-  hipc(hipStreamCreate(&P->hstream), "hipStreamCreate");
   // From 2^19 LDE rows up the transform stream, not the sum of the instruction streams, bounds the commitments (profiles/
   // r3_v8_fq12_512_kernel_stats.csv: five passes of 410 us per chunk beside a 1.19 ms sponge launch, 1.63 ms of VALU work in a 2.05 ms
   // period): the LDE passes of chunk k then run on a second stream beside the inverse passes of chunk k+1 (two streams at 2^16 rows,
   // where the stage IS at its VALU bound, were measured slower in round 2).
   P->ntt_two_streams = P->lde_log >= 19;
-  if (P->ntt_two_streams) {
+  // compact storage takes effect on the wide tables: a matrix of at most 4 columns (hash_or_noop) stays whole in both modes
+  P->lde_storage = lde_storage;
+  P->compact = lde_storage == SBN_LDE_COMPACT && as.ncols > 4;
+  P->ring_depth = P->compact ? LDE_RING_DEPTH : 0;
+  P->apow_n = apow_len(as.nconstraints, as.nzs);
+  // query section stride (words per query round)
+  {
+    const size_t C = as.ncols, Z = as.nzs;
+    size_t sib = (size_t)(P->lde_log - cfg->cap_height) * 4;
+    size_t s = C + sib + (Z ? Z + sib : 0) + 4 + sib;
+    u32 bits = P->lde_log;
+    for (u32 ab : P->fri.arity_bits) { bits -= ab; s += 2 * ((size_t)1 << ab) + (size_t)(bits - cfg->cap_height) * 4; }
+    P->qstride = s;
+  }
+  return 0;
+}
+static void tree_shape(DevTree& t, size_t nleaf, u32 cap_height) {
+  t.nleaf = nleaf;
+  u32 lg = 0; while (((size_t)1 << lg) < nleaf) lg++;
+  t.nlevels = lg - cap_height;
+}
+// Not a pure function of P: it also completes the shape it lists -- lde_scratch_words, the leaf and level counts of the trees, the
+// lengths of fri_vals / fri_trees (whose elements the list points into) -- so it is called exactly once per context, by create_ctx
+// or by the plan.  (tree_alloc above is what sbn_commit_values still uses for its one tree.)
+// Every device buffer a context holds from creation on, in allocation order.  Not in the list (allocated by the first call that
+// needs them, include/sbn.h sbn_prover_memory_plan): d_first_bad of prove_host_trace (8 bytes; its upload ring is pinned host memory).
+static void ctx_buffers(sbn_prover* P, std::vector<BufReq>& L) {
+  const AirShape& as = P->air; const sbn_config* cfg = &P->cfg;
+  // qn: the quotient's domain, the coset of 2n points (quotient_degree_bits = 1) whatever the rate: LDE rows k * m / qn
+  const size_t n = P->n, m = P->m, qn = 2 * n, C = as.ncols, Z = as.nzs;
+  auto words = [&](u64** p, size_t w) { L.push_back(BufReq{(void**)p, w * sizeof(u64)}); };
+  auto bytes = [&](void** p, size_t b) { L.push_back(BufReq{p, b}); };
+  auto tree = [&](DevTree& t, size_t nleaf, u32 cap_height) { tree_shape(t, nleaf, cap_height); words(&t.d, 2 * nleaf * 4); };
+  if (SplitCtx* S = P->sp) {
+    const u32 lr = S->log_r;
+    words(&P->d_trace, C * n); words(&P->d_coef, std::max<size_t>(S->cr, 1) * n);
+    words(&P->d_zval, std::max<size_t>(S->zr, 1) * n); words(&P->d_zcoef, std::max<size_t>(S->zr, 1) * n);
+    words(&S->d_ldechunk, P->ntt_chunk * m);
+    bytes((void**)&S->d_idx_local, cfg->num_query_rounds * sizeof(u32));
+    tree(P->tree_t, S->ml, cfg->cap_height - lr); tree(P->tree_z, S->ml, cfg->cap_height - lr);
+  } else {
+    // compact: the wide matrices keep the quotient's rows only (P->compact: C > 4, and Z = 0 or Z > 4), and the LDE of a chunk
+    // passes through the ring
+    const size_t rows = P->compact ? qn : m;
+    P->lde_scratch_words = C * rows;
+    words(&P->d_trace, C * n); words(&P->d_coef, C * n); words(&P->d_lde, C * rows);
+    words(&P->d_zval, std::max<size_t>(Z, 1) * n); words(&P->d_zcoef, std::max<size_t>(Z, 1) * n); words(&P->d_zlde, Z > 4 ? Z * rows : std::max<size_t>(Z, 1) * m);
+    if (P->compact) words(&P->d_ring, (size_t)P->ring_depth * P->ntt_chunk * m);
+    tree(P->tree_t, m, cfg->cap_height); tree(P->tree_z, m, cfg->cap_height);
+  }
+  words(&P->d_tmp, std::max(P->ntt_chunk, (size_t)4) * m);
+  if (P->ntt_fused || P->ntt_fused512 || P->ntt_two_streams) words(&P->d_tmp2, std::max(P->ntt_chunk, (size_t)4) * m);
+  if ((P->ntt_fused || P->ntt_fused512) && P->ntt_two_streams) words(&P->d_tmp3, std::max(P->ntt_chunk, (size_t)4) * m);
+  words(&P->d_q, 2 * qn); words(&P->d_qlde, 4 * m);
+  tree(P->tree_q, m, cfg->cap_height);
+  words(&P->d_tw_f, m); words(&P->d_tw_i, m); words(&P->d_shift, m); words(&P->d_shift_inv, m);
+  if (P->ntt_fused512) words(&P->d_shift_odd, n);   // (ntt_plan)
+  if (P->lde_za_log) words(&P->d_shift_za, n << P->lde_za_log);   // (ntt_plan)
+  words(&P->d_xs, qn); words(&P->d_lag_first, qn); words(&P->d_lag_last, qn);   // per quotient point
+  words(&P->d_apow, (size_t)SBN_NCH * P->apow_n);
+  words(&P->d_zpow, 4 * n); words(&P->d_open, (C + Z + 4) * 4);
+  words(&P->d_part, 2 * 32 * n); words(&P->d_w, 4096); words(&P->d_sponge, 12 * m);
+  words(&P->d_fa, 4 * n); words(&P->d_fcoef, 2 * m); words(&P->d_fcoef2, 2 * m);
+  words(&P->d_pow, 1);
+  bytes(&P->d_pic, sizeof(ExpPiConsts<F>));
+  bytes((void**)&P->d_idx, cfg->num_query_rounds * sizeof(u32));
+  // FRI layer buffers
+  {
+    const size_t layers = P->fri.arity_bits.size();
+    P->fri_vals.assign(layers, nullptr); P->fri_trees.assign(layers, DevTree());
+    u32 bits = P->lde_log;
+    for (size_t li = 0; li < layers; li++) {
+      const u32 ab = P->fri.arity_bits[li];
+      words(&P->fri_vals[li], 2 * ((size_t)1 << bits));
+      tree(P->fri_trees[li], (size_t)1 << (bits - ab), cfg->cap_height);
+      bits -= ab;
+    }
+  }
+  words(&P->d_qbuf, P->qstride * cfg->num_query_rounds);
+  bytes((void**)&P->d_pairs, std::max<size_t>(Z, 1) * sizeof(PairCols));
+  if (P->sp && P->sp->zr) bytes((void**)&P->sp->d_pairs_own, P->sp->zr * sizeof(PairCols));
+}
+extern "C" int sbn_prover_memory_plan(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_prover_options* opt, uint64_t* bytes_out) {
+  if (!bytes_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  *bytes_out = 0;
+  AirShape as; u32 storage = 0;
+  if (int rc = ctx_check_args(air, cfg, degree_bits, nullptr, opt, as, storage)) return rc;
+  sbn_prover* P = new sbn_prover();   // shape fields only: nothing of it touches a device
+  std::vector<BufReq> L;
+  int rc = ctx_shape(P, as, cfg, degree_bits, storage);
+  if (!rc) {
+    ctx_buffers(P, L);
+    uint64_t total = 0;
+    for (const BufReq& b : L) total += b.bytes;
+    *bytes_out = total;
+  }
+  delete P;
+  return rc;
+}
+
+static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, const sbn_prover_options* opt, sbn_prover** out);
+extern "C" int sbn_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_prover_options* opt, sbn_prover** out) {
+  return create_ctx(air, cfg, degree_bits, nullptr, opt, out);
+}
+extern "C" int sbn_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, sbn_prover** out) {
+  return sbn_prover_create_with(air, cfg, degree_bits, nullptr, out);
+}
+static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, const sbn_prover_options* opt, sbn_prover** out) {
+  if (!air || !cfg || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  *out = nullptr;
+  AirShape as; u32 storage = 0;
+  if (int rc = ctx_check_args(air, cfg, degree_bits, comm, opt, as, storage)) return rc;
+  if (int rc = use_current_device("the prover path has no CPU fallback")) return rc;
+  sbn_prover* P = new sbn_prover();
+  P->device = g_device;
+  // every failure below releases what was created so far (sbn_prover_destroy accepts a partly built context) and
+  // returns the FIRST error code
+  int rc = 0;
+  auto acc = [&](int r) { if (!rc) rc = r; };
+  auto hipc = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(SBN_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
+  if ((rc = ctx_shape(P, as, cfg, degree_bits, storage))) { sbn_prover_destroy(P); return rc; }
+  const Settings& set = P->set;
+  acc(ntt_fast_setup());
+  hipc(hipStreamCreate(&P->stream), "hipStreamCreate");
+  hipc(hipStreamCreate(&P->hstream), "hipStreamCreate");
+  if (P->ntt_two_streams) {   // (ctx_shape)
     hipc(hipStreamCreate(&P->nstream), "hipStreamCreate");
     for (auto& e : P->intt_done) hipc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
   }
@@ -617,9 +773,9 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   for (auto& e : P->abs_ev) hipc(hipEventCreate(&e), "hipEventCreate");
   for (auto& e : P->chunk_ready) hipc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
   hipc(hipEventCreateWithFlags(&P->hash_done, hipEventDisableTiming), "hipEventCreate");
+  if (P->compact) for (auto& e : P->ring_free) hipc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
   for (auto& v : P->stage_ms) v = 0;
   if (rc) { sbn_prover_destroy(P); return rc; }
-  // qn: the quotient's domain, the coset of 2n points (quotient_degree_bits = 1) whatever the rate: LDE rows k * m / qn
   const size_t n = P->n, m = P->m, qn = 2 * n, C = as.ncols, Z = as.nzs;
   if (comm && (C <= 4 || Z == 0)) { sbn_prover_destroy(P); return fail(SBN_ERR_UNSUPPORTED, "the split prover covers the wide tables (this one has %zu columns and %zu permutation Zs)", C, Z); }
   if (comm) {
@@ -663,58 +819,21 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
     if (S->planes == 2) { S->zlde_n = rbuf; rbuf += Z * S->ml; }
     S->scratch = rbuf; S->scratch_words = sw;
     P->lde_scratch_words = (size_t)(rb / sizeof(u64));   // witness generation runs before the first exchange
-    acc(dmalloc(&P->d_trace, C * n, &P->dev_bytes)); acc(dmalloc(&P->d_coef, std::max<size_t>(S->cr, 1) * n, &P->dev_bytes));
-    acc(dmalloc(&P->d_zval, std::max<size_t>(S->zr, 1) * n, &P->dev_bytes)); acc(dmalloc(&P->d_zcoef, std::max<size_t>(S->zr, 1) * n, &P->dev_bytes));
-    acc(dmalloc(&S->d_ldechunk, P->ntt_chunk * m, &P->dev_bytes));
-    hipc(hipMalloc((void**)&S->d_idx_local, cfg->num_query_rounds * sizeof(u32)), "hipMalloc"); P->dev_bytes += cfg->num_query_rounds * sizeof(u32);
-    acc(tree_alloc(P->tree_t, S->ml, cfg->cap_height - lr, &P->dev_bytes)); acc(tree_alloc(P->tree_z, S->ml, cfg->cap_height - lr, &P->dev_bytes));
-  } else {
-    P->lde_scratch_words = C * m;
-    acc(dmalloc(&P->d_trace, C * n, &P->dev_bytes)); acc(dmalloc(&P->d_coef, C * n, &P->dev_bytes)); acc(dmalloc(&P->d_lde, C * m, &P->dev_bytes));
-    acc(dmalloc(&P->d_zval, std::max<size_t>(Z, 1) * n, &P->dev_bytes)); acc(dmalloc(&P->d_zcoef, std::max<size_t>(Z, 1) * n, &P->dev_bytes)); acc(dmalloc(&P->d_zlde, std::max<size_t>(Z, 1) * m, &P->dev_bytes));
-    acc(tree_alloc(P->tree_t, m, cfg->cap_height, &P->dev_bytes)); acc(tree_alloc(P->tree_z, m, cfg->cap_height, &P->dev_bytes));
   }
-  acc(dmalloc(&P->d_tmp, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
-  if (P->ntt_fused || P->ntt_fused512 || P->ntt_two_streams) acc(dmalloc(&P->d_tmp2, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
-  if ((P->ntt_fused || P->ntt_fused512) && P->ntt_two_streams) acc(dmalloc(&P->d_tmp3, std::max(P->ntt_chunk, (size_t)4) * m, &P->dev_bytes));
-  acc(dmalloc(&P->d_q, 2 * qn, &P->dev_bytes)); acc(dmalloc(&P->d_qlde, 4 * m, &P->dev_bytes));
-  acc(tree_alloc(P->tree_q, m, cfg->cap_height, &P->dev_bytes));
-  acc(dmalloc(&P->d_tw_f, m, &P->dev_bytes)); acc(dmalloc(&P->d_tw_i, m, &P->dev_bytes)); acc(dmalloc(&P->d_shift, m, &P->dev_bytes)); acc(dmalloc(&P->d_shift_inv, m, &P->dev_bytes));
-  if (P->ntt_fused512) acc(dmalloc(&P->d_shift_odd, n, &P->dev_bytes));   // (ntt_plan)
-  if (P->lde_za_log) acc(dmalloc(&P->d_shift_za, n << P->lde_za_log, &P->dev_bytes));   // (ntt_plan)
-  acc(dmalloc(&P->d_xs, qn, &P->dev_bytes)); acc(dmalloc(&P->d_lag_first, qn, &P->dev_bytes)); acc(dmalloc(&P->d_lag_last, qn, &P->dev_bytes));   // per quotient point
-  P->apow_n = apow_len(as.nconstraints, as.nzs);
-  acc(dmalloc(&P->d_apow, (size_t)SBN_NCH * P->apow_n, &P->dev_bytes));
-  acc(dmalloc(&P->d_zpow, 4 * n, &P->dev_bytes)); acc(dmalloc(&P->d_open, (C + Z + 4) * 4, &P->dev_bytes));
-  hipc(hipHostMalloc((void**)&P->h_open, (C + Z + 4) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
-  hipc(hipHostMalloc((void**)&P->h_open2, (C + Z) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
-  acc(dmalloc(&P->d_part, 2 * 32 * n, &P->dev_bytes)); acc(dmalloc(&P->d_w, 4096, &P->dev_bytes)); acc(dmalloc(&P->d_sponge, 12 * m, &P->dev_bytes));
-  acc(dmalloc(&P->d_fa, 4 * n, &P->dev_bytes)); acc(dmalloc(&P->d_fcoef, 2 * m, &P->dev_bytes)); acc(dmalloc(&P->d_fcoef2, 2 * m, &P->dev_bytes));
-  acc(dmalloc(&P->d_pow, 1, &P->dev_bytes));
-  if (rc) { sbn_prover_destroy(P); return rc; }
-  P->d_fb = P->d_fa + 2 * n;
-  hipc(hipMalloc((void**)&P->d_pic, sizeof(ExpPiConsts<F>)), "hipMalloc"); P->dev_bytes += sizeof(ExpPiConsts<F>);
-  hipc(hipMalloc((void**)&P->d_idx, cfg->num_query_rounds * sizeof(u32)), "hipMalloc"); P->dev_bytes += cfg->num_query_rounds * sizeof(u32);
-  // FRI layer buffers
   {
-    u32 bits = P->lde_log;
-    for (u32 ab : P->fri.arity_bits) {
-      u64* v = nullptr; acc(dmalloc(&v, 2 * ((size_t)1 << bits), &P->dev_bytes)); P->fri_vals.push_back(v);
-      DevTree t; acc(tree_alloc(t, (size_t)1 << (bits - ab), cfg->cap_height, &P->dev_bytes)); P->fri_trees.push_back(t);
-      bits -= ab;
+    std::vector<BufReq> L;
+    ctx_buffers(P, L);
+    for (const BufReq& b : L) {
+      if (rc) break;
+      hipc(hipMalloc(b.slot, b.bytes), "hipMalloc");
+      if (!rc) P->dev_bytes += b.bytes;
     }
     if (rc) { sbn_prover_destroy(P); return rc; }
   }
-  // query section stride (words per query round)
-  {
-    size_t sib = (size_t)(P->lde_log - cfg->cap_height) * 4;
-    size_t s = C + sib + (Z ? Z + sib : 0) + 4 + sib;
-    u32 bits = P->lde_log;
-    for (u32 ab : P->fri.arity_bits) { bits -= ab; s += 2 * ((size_t)1 << ab) + (size_t)(bits - cfg->cap_height) * 4; }
-    P->qstride = s;
-    acc(dmalloc(&P->d_qbuf, s * cfg->num_query_rounds, &P->dev_bytes));
-    if (rc) { sbn_prover_destroy(P); return rc; }
-  }
+  P->d_fb = P->d_fa + 2 * n;
+  hipc(hipHostMalloc((void**)&P->h_open, (C + Z + 4) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
+  hipc(hipHostMalloc((void**)&P->h_open2, (C + Z) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
+  if (rc) { sbn_prover_destroy(P); return rc; }
   // tables
   auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
   F w = f_root_of_unity(P->lde_log);
@@ -738,13 +857,11 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
       else exp_shape(as).pair((int)z, l, r);
       pairs[z].lhs = l; pairs[z].rhs = r;
     }
-    hipc(hipMalloc((void**)&P->d_pairs, std::max<size_t>(Z, 1) * sizeof(PairCols)), "hipMalloc"); P->dev_bytes += std::max<size_t>(Z, 1) * sizeof(PairCols);
     if (!rc && Z) hipc(hipMemcpy(P->d_pairs, pairs.data(), Z * sizeof(PairCols), hipMemcpyHostToDevice), "hipMemcpy");
     if (P->sp && P->sp->zr) {   // the split: the pairs of this rank's Z columns in local order
       SplitCtx* S = P->sp;
       std::vector<PairCols> own(S->zr);
       for (size_t l = 0; l < S->zr; l++) own[l] = pairs[S->zs.global_col(S->zs.rank, l)];
-      hipc(hipMalloc((void**)&S->d_pairs_own, S->zr * sizeof(PairCols)), "hipMalloc"); P->dev_bytes += S->zr * sizeof(PairCols);
       if (!rc) hipc(hipMemcpy(S->d_pairs_own, own.data(), S->zr * sizeof(PairCols), hipMemcpyHostToDevice), "hipMemcpy");
     }
   }
@@ -761,7 +878,7 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   (void)hipSetDevice(P->device);
   u64* bufs[] = {P->d_trace, P->d_coef, P->d_lde, P->d_tmp, P->d_tmp2, P->d_tmp3, P->d_zval, P->d_zcoef, P->d_zlde, P->d_q, P->d_qlde, P->tree_t.d, P->tree_z.d,
                  P->tree_q.d, P->d_tw_f, P->d_tw_i, P->d_shift, P->d_shift_inv, P->d_xs, P->d_lag_first, P->d_lag_last, P->d_apow, P->d_zpow,
-                 P->d_open, P->d_part, P->d_w, P->d_fa, P->d_fcoef, P->d_fcoef2, P->d_pow, P->d_qbuf, P->d_shift_odd, P->d_shift_za};
+                 P->d_open, P->d_part, P->d_w, P->d_fa, P->d_fcoef, P->d_fcoef2, P->d_pow, P->d_qbuf, P->d_shift_odd, P->d_shift_za, P->d_ring};
   for (u64* b : bufs) if (b) (void)hipFree(b);
   for (u64* b : P->fri_vals) if (b) (void)hipFree(b);
   for (auto& t : P->fri_trees) if (t.d) (void)hipFree(t.d);
@@ -781,6 +898,7 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   for (auto& e : P->abs_ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : P->chunk_ready) if (e) (void)hipEventDestroy(e);
   if (P->hash_done) (void)hipEventDestroy(P->hash_done);
+  for (auto& e : P->ring_free) if (e) (void)hipEventDestroy(e);
   if (P->d_sponge) (void)hipFree(P->d_sponge);
   if (P->h_chain) (void)hipHostFree(P->h_chain);
   if (P->h_io) (void)hipHostFree(P->h_io);
@@ -978,7 +1096,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   if (S) {
     S->tev_used = 0;
     if ((rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t))) return rc;
-  } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up))) return rc;
+  } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up, P->compact ? P->d_lde : nullptr))) return rc;
   HIPC(hipEventRecord(P->ev[ST_PERM_Z], st));
   if ((rc = S ? split_cap_to_host(P, P->tree_t, trace_cap) : tree_cap_to_host(P, P->tree_t, trace_cap, up != nullptr))) return rc;
   if (up && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
@@ -1005,7 +1123,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     if ((rc = commit_split(P, S->zs, P->d_zval, false, P->d_zcoef, S->zlde_l, S->zlde_n, P->tree_z))) return rc;
   } else {
     if (C > 4) if ((rc = absorb_times(P, C, EX_TRACE_ABSORB_MS))) return rc;   // (27 event queries: behind the Z kernel, not in front of it)
-    if (Z) if ((rc = commit_pipeline(P, P->d_zval, P->d_zcoef, P->d_zlde, Z, P->tree_z, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES))) return rc;
+    if (Z) if ((rc = commit_pipeline(P, P->d_zval, P->d_zcoef, P->d_zlde, Z, P->tree_z, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, nullptr, P->compact ? P->d_zlde : nullptr))) return rc;
   }
   HIPC(hipEventRecord(P->ev[ST_QUOTIENT_EVAL], st));
   if (Z) {
@@ -1024,6 +1142,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     // (the section on rate_bits, has the byte counts against a dense copy); at rate_bits 1 the stride is one row.
     qp.lde = P->d_lde; qp.zlde = P->d_zlde; qp.m = qn; qp.next_step = 2;  // 2^quotient_degree_bits
     qp.lde_stride = m; qp.row_log = cfg.rate_bits - 1;
+    if (P->compact) { qp.lde_stride = qn; qp.row_log = 0; }   // d_lde / d_zlde hold the quotient's rows only, densely
     qp.lde_next = qp.lde; qp.zlde_next = qp.zlde; qp.row_shift = 0; qp.row_rho = 0;
     if (S) {
       // this rank's LDE points j * R + rho; the row two LDE points on is local row j + 1 (two ranks) or sits at local row j
@@ -1305,8 +1424,12 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     const u32 nsib = P->lde_log - cfg.cap_height;
     // a row-sharded matrix (the split): `rows` local rows, leaf index inside this rank's subtrees; the rank that owns a
     // query's leaf holds its whole row and its Merkle path up to the cap (other ranks gather a row that is dropped below)
-    auto initial = [&](const u64* mat, size_t ncols, const DevTree& t, size_t rows, u32 log_rows, const u32* d_index) {
-      hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ncols + 255) / 256), nq), dim3(256), 0, st, mat, rows, log_rows, (u32)ncols, d_index, P->d_qbuf, P->qstride, off);
+    // coef (compact storage of a wide matrix; else null): the rows are not resident and are evaluated from the coefficients
+    // (lde_compact.hip; its point tables sit in d_part, idle since the FRI combine)
+    int rows_rc = 0;
+    auto initial = [&](const u64* mat, size_t ncols, const DevTree& t, size_t rows, u32 log_rows, const u32* d_index, const u64* coef = nullptr) {
+      if (coef) { if (!rows_rc) rows_rc = launch_query_rows(coef, ncols, n, P->lde_log, P->d_shift, P->d_tw_f, d_index, nq, P->d_part, P->d_qbuf, P->qstride, off, st); }
+      else hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ncols + 255) / 256), nq), dim3(256), 0, st, mat, rows, log_rows, (u32)ncols, d_index, P->d_qbuf, P->qstride, off);
       off += ncols;
       hipLaunchKernelGGL(gather_siblings_kernel, dim3(nq), dim3(128), 0, st, t.d, t.nleaf, nsib, d_index, 0u, P->d_qbuf, P->qstride, off);
       off += (size_t)nsib * 4;
@@ -1318,8 +1441,9 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
       if (Z) initial(S->zlde_l, Z, P->tree_z, S->ml, P->lde_log - S->log_r, S->d_idx_local);
       split_section = off;
     } else {
-      initial(P->d_lde, C, P->tree_t, m, P->lde_log, P->d_idx);
-      if (Z) initial(P->d_zlde, Z, P->tree_z, m, P->lde_log, P->d_idx);
+      initial(P->d_lde, C, P->tree_t, m, P->lde_log, P->d_idx, P->compact ? P->d_coef : nullptr);
+      if (Z) initial(P->d_zlde, Z, P->tree_z, m, P->lde_log, P->d_idx, P->compact ? P->d_zcoef : nullptr);
+      if (rows_rc) return rows_rc;
     }
     initial(P->d_qlde, 4, P->tree_q, m, P->lde_log, P->d_idx);
     u32 bits = P->lde_log, shift = 0;
@@ -1461,6 +1585,48 @@ extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, u
   return rc;
 }
 
+// The twin of sbn_commit_values for the compact storage: values -> coefficients through the transform plan of a prover of this
+// height and rate, then the opened rows of the coset LDE from the coefficients by the kernels of lde_compact.hip.
+extern "C" int sbn_lde_rows(const uint64_t* cols, size_t ncols, uint32_t degree_bits, uint32_t rate_bits, const uint32_t* leaf_indices, size_t count, uint64_t* rows_out) {
+  if (!cols || !leaf_indices || !rows_out || ncols == 0 || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (count > 65536) return fail(SBN_ERR_BAD_ARG, "at most 65536 leaf indices per call");
+  if (rate_bits < 1 || rate_bits > 3 || degree_bits < 9 || degree_bits + rate_bits > SBN_MAX_LDE_BITS)
+    return fail(SBN_ERR_UNSUPPORTED, "need rate_bits 1..3 and 9 <= degree_bits with degree_bits + rate_bits <= %u", SBN_MAX_LDE_BITS);
+  const size_t n = (size_t)1 << degree_bits, m = n << rate_bits;
+  for (size_t i = 0; i < count; i++) if (leaf_indices[i] >= m) return fail(SBN_ERR_BAD_ARG, "leaf index %zu is %u, beyond the %zu leaves", i, leaf_indices[i], m);
+  sbn_prover P{};
+  sbn_standard_fast_config(&P.cfg); P.cfg.rate_bits = rate_bits;
+  P.degree_bits = degree_bits; P.lde_log = degree_bits + rate_bits; P.n = n; P.m = m; P.ntt_chunk = 64;
+  if (int rc = use_current_device("no CPU fallback")) return rc;
+  P.device = g_device;
+  { int rc0 = ntt_fast_setup(); if (rc0) return rc0; }
+  { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
+  ntt_plan(&P);   // the transform kernels the prover picks at this size
+  HIPC(hipStreamCreate(&P.stream));   // (nothing is allocated yet)
+  u64 *d_vals = nullptr, *d_coef = nullptr, *d_table = nullptr, *d_out = nullptr; u32* d_index = nullptr;
+  int rc = 0;
+  rc |= dmalloc(&d_vals, ncols * n); rc |= dmalloc(&d_coef, ncols * n); rc |= dmalloc(&P.d_tmp, 64 * m); rc |= dmalloc(&d_table, 64 * n); rc |= dmalloc(&d_out, count * ncols);
+  rc |= dmalloc(&P.d_tw_f, m); rc |= dmalloc(&P.d_tw_i, m); rc |= dmalloc(&P.d_shift, m);
+  if (!rc && hipMalloc((void**)&d_index, count * sizeof(u32)) != hipSuccess) rc = fail(SBN_ERR_HIP, "hipMalloc failed");
+  if (!rc) {
+    auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
+    F w = f_root_of_unity(P.lde_log);
+    hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P.stream, P.d_tw_f, m, w.v);
+    hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P.stream, P.d_tw_i, m, f_inv(w).v);
+    hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P.stream, P.d_shift, m, (u64)GL_GEN);
+    if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_index, leaf_indices, count * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess) rc = fail(SBN_ERR_HIP, "H2D failed");
+  }
+  if (!rc) rc = intt_values(&P, d_vals, d_coef, ncols);
+  if (!rc) rc = launch_query_rows(d_coef, ncols, n, P.lde_log, P.d_shift, P.d_tw_f, d_index, (u32)count, d_table, d_out, ncols, 0, P.stream);
+  if (!rc && hipStreamSynchronize(P.stream) != hipSuccess) rc = fail(SBN_ERR_HIP, "sbn_lde_rows: the kernels failed");
+  if (!rc && hipMemcpy(rows_out, d_out, count * ncols * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBN_ERR_HIP, "D2H failed");
+  for (u64* b : {d_vals, d_coef, d_table, d_out, P.d_tmp, P.d_tw_f, P.d_tw_i, P.d_shift}) if (b) (void)hipFree(b);
+  if (d_index) (void)hipFree(d_index);
+  (void)hipStreamDestroy(P.stream);
+  return rc;
+}
+
 extern "C" int sbn_poseidon_permute_batch(uint64_t* states, size_t count) {
   if (!states) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (int rc = use_current_device("no CPU fallback")) return rc;
@@ -1557,10 +1723,11 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
   char buf[1024];
   snprintf(buf, sizeof buf,
            "abi=%d device=%d dev_bytes=%zu ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d ntt_lde_zero_aware=%d "
-           "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d ignored=[%s]",
+           "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d lde=%s lde_ring=%u lde_ring_bytes=%zu ignored=[%s]",
            SBN_ABI_VERSION, P->device, P->dev_bytes, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0, P->d_shift_za ? 1 : 0,
            chain, tracegen_host_threads(), (int)s.fq12_host_chain,
-           (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, s.ignored.c_str());
+           (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, P->lde_storage == SBN_LDE_COMPACT ? "compact" : "full", P->ring_depth,
+           P->d_ring ? (size_t)P->ring_depth * P->ntt_chunk * P->m * sizeof(u64) : (size_t)0, s.ignored.c_str());
   snprintf(out, cap, "%s", buf);
   return SBN_OK;
 }
@@ -1581,7 +1748,7 @@ extern "C" int sbn_split_prover_create(const sbn_air_desc* air, const sbn_config
   if (!out || !comm) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   sbn_prover* P = nullptr;
-  int rc = create_ctx(air, cfg, degree_bits, comm, &P);
+  int rc = create_ctx(air, cfg, degree_bits, comm, nullptr, &P);
   if (rc) return rc;
   *out = new sbn_split_prover{P};
   return SBN_OK;

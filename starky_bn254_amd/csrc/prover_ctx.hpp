@@ -30,6 +30,9 @@ static constexpr int UPLOAD_SLOTS = 4;
 static constexpr size_t UPLOAD_SLOT_WORDS = (size_t)2 << 20;
 // Function attributes are per DEVICE: one flag per device of the process (sbn_set_device may select another GPU later).
 static constexpr int SBN_MAX_DEVICES = 64;
+// Compact LDE storage (include/sbn.h SBN_LDE_COMPACT): slots of the LDE chunk ring at most; create_ctx picks LDE_RING_DEPTH
+static constexpr int LDE_RING_MAX = 3;
+static constexpr u32 LDE_RING_DEPTH = 2;
 
 struct DevTree {  // Merkle digests, levels concatenated (leaf level first)
   u64* d = nullptr; size_t nleaf = 0; u32 nlevels = 0;  // nlevels = number of levels BELOW the cap
@@ -75,6 +78,14 @@ struct sbn_prover {
   AirShape air; sbn_config cfg; FriShape fri;
   SplitCtx* sp = nullptr;                 // null: the whole proof on this GPU
   size_t lde_scratch_words = 0;           // capacity of d_lde as witness-generation scratch
+  // SBN_LDE_COMPACT: a matrix of more than 4 columns keeps only the quotient's rows of its LDE, d_lde = [C][qn] and d_zlde = [Z][qn]
+  // (dense, point j = LDE row j << (rate_bits - 1)); the LDE of a column chunk passes through a ring slot [ntt_chunk][m] between its
+  // last transform pass and the sponge, and the opened rows are recomputed from the coefficients (lde_compact.hip)
+  u32 lde_storage = 0;                    // SBN_LDE_FULL / SBN_LDE_COMPACT as asked for
+  bool compact = false;                   // ... and in effect: compact storage and a table of more than 4 columns
+  u32 ring_depth = 0;
+  u64* d_ring = nullptr;                  // [ring_depth][ntt_chunk][m]
+  hipEvent_t ring_free[MAX_CHUNKS] = {};  // hash stream: the sponge and lde_keep_rows_kernel have left the slot of chunk k (one event per chunk, as chunk_ready)
   u32 degree_bits, lde_log; size_t n, m;
   int device; hipStream_t stream;
   // matrices
@@ -155,6 +166,13 @@ int upload_alpha_tables(sbn_prover* P, const F alphas[SBN_NCH]);
 void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientParams& qp);
 // quotient_kernel<kind, 0 / 1> on P->stream, <kind, 2> on P->hstream
 int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks);
+// lde_compact.hip: the two stages of the compact LDE storage.  Both enqueue on `s` and leave the waiting to the caller.
+// dense[c][j] = slot[c][j << row_log] for c < nc, j < qn (slot columns m words apart, dense columns qn)
+void launch_lde_keep_rows(const u64* slot, size_t m, u64* dense, size_t qn, u32 row_log, size_t nc, hipStream_t s);
+// the opened rows of `ncols` columns from their coefficients [ncols][n]: out[q * qstride + off + c] = sum_j coef[c][j] x_q^j at
+// x_q = 7 w_m^bitrev(idx[q]), q < nq, what gather_rows_kernel reads out of a resident LDE.  table: 64 n words of scratch.
+int launch_query_rows(const u64* coef, size_t ncols, size_t n, u32 lde_log, const u64* shift, const u64* tw_f, const u32* d_idx, u32 nq, u64* table,
+                      u64* out, size_t qstride, size_t off, hipStream_t s);
 // trace_check.hip, shared with trace_explain.hip: the seed-to-challenge transcript of a check and the kernel that fills the tables
 // of the trace domain.
 void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]);
