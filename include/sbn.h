@@ -735,6 +735,11 @@ int sbn_lde_rows(const uint64_t* values_col_major, size_t ncols, uint32_t degree
                  uint64_t* rows_out);
 /* Poseidon permutation of `count` independent width-12 states on the device (host in/out). */
 int sbn_poseidon_permute_batch(uint64_t* states, size_t count);
+/* The same permutation through the 16-lane cooperative form that the narrow Merkle levels, the FRI leaves and the device verifier
+ * run (csrc/poseidon.cuh poseidon_permute_coop16): one group of 16 lanes per state, `count` passed to the kernel as it is, so counts
+ * that are no multiple of 4 (groups per wave) or 16 (groups per workgroup) run partly filled waves and workgroups.  A null pointer
+ * (SBN_ERR_BAD_ARG) and a word >= p (SBN_ERR_NON_CANONICAL) are refused before a device is looked for.  Host in/out. */
+int sbn_poseidon_permute_coop_batch(uint64_t* states, size_t count);
 /* out[i] = a[i] * b[i] in the Goldilocks field with the DEVICE multiply of every kernel (csrc/gl.cuh: 13-instruction weak product +
  * canonicalisation; mode 0), or the weak product of the transform passes canonicalised afterwards (mode 1).  a, b: any 64-bit
  * values (non-canonical representatives included: the kernels' intermediate values are); out canonical.  Host in/out. */

@@ -44,7 +44,7 @@ EXPORTS = [
     "sbn_msm_batch_instances", "sbn_prover_generate_trace_msm_batch", "sbn_batch_prover_prove_msm_batch", "sbn_msm_batch_check",
     "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
-    "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
+    "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_coop_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
     "sbn_split_prover_load_trace", "sbn_split_prover_prove", "sbn_split_prover_stage_times", "sbn_split_prover_check_trace",
     "sbn_abi_version", "sbn_rccl_unique_id", "sbn_rccl_comm_create", "sbn_rccl_comm_destroy",
@@ -233,6 +233,8 @@ def lib():
         L.sbn_verifier_destroy.argtypes = [vp]
         L.sbn_commit_values.argtypes = [vp, sz, sz, u32, u32, vp, vp, vp]
         L.sbn_poseidon_permute_batch.argtypes = [vp, sz]
+        if hasattr(L, "sbn_poseidon_permute_coop_batch"):   # (absent from an older build named by SBN_LIB for an A/B)
+            L.sbn_poseidon_permute_coop_batch.argtypes = [vp, sz]
         L.sbn_poseidon_permute_host.argtypes = [vp, sz, C.c_int]
         L.sbn_field_mul_batch.argtypes = [vp, vp, vp, sz, C.c_int]
         L.sbn_bn254_fq_batch.argtypes = [C.c_int, vp, vp, vp, sz, C.c_int]
@@ -1608,6 +1610,13 @@ def lde_rows(cols, rate_bits, leaf_indices):
 def poseidon_permute_batch(states):
     s = np.ascontiguousarray(states, dtype=np.uint64).copy()
     _check(lib().sbn_poseidon_permute_batch(_ptr(s), s.shape[0]))
+    return s
+
+
+def poseidon_permute_coop_batch(states):
+    """The permutation of (count, 12) states through the 16-lane cooperative form (one lane group per state)."""
+    s = np.ascontiguousarray(states, dtype=np.uint64).copy()
+    _check(lib().sbn_poseidon_permute_coop_batch(_ptr(s), s.shape[0]))
     return s
 
 

@@ -133,9 +133,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void l
   }
 }
 
-// Measured (tools/microbench/coop_latency.hip): one permutation takes 49 us on one lane and 16 us on 16 lanes, and a
-// single wave already saturates its SIMD's issue slots, so more waves per SIMD only queue up: 256 lanes (one wave per
-// SIMD) is the best workgroup size for the latency-bound levels (A/B against 512 and 1024 lanes on the G1 proof).
+// Measured (tools/microbench/coop_latency.hip, profiles/coop16_exchange_ab.txt): one permutation takes 27 us on one lane and
+// 8.7 us on 16 lanes, and a single wave already saturates its SIMD's issue slots, so more waves per SIMD only queue up: 256
+// lanes (one wave per SIMD) is the best workgroup size for the latency-bound levels (A/B against 512 and 1024 lanes on the G1 proof).
 static constexpr u32 MERKLE_SUBTREE_THREADS = 256;
 // K3' fused Merkle levels: a workgroup owns up to 512 consecutive digests of level `l0` and hashes
 // up to `nlev` levels above them through LDS, writing every level to the tree (levels concatenated,
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void merkle_level_coop_kernel(u64* __restrict_
   const u64* child = tree + (2 * nleaf - ((2 * nleaf) >> l)) * 4;
   u64* out = tree + (2 * nleaf - ((2 * nleaf) >> (l + 1))) * 4;
   const u64 v = (parent < parents && e < 8) ? child[parent * 8 + e] : 0;
-  const u64 r = poseidon_permute_coop16(v, lane);   // every lane of the row takes part (DPP rotations)
+  const u64 r = poseidon_permute_coop16(v, lane);   // every lane of the row takes part (DPP broadcasts)
   if (parent < parents && lane < 4) out[parent * 4 + lane] = r;
 }
 
@@ -251,14 +251,14 @@ __global__ __launch_bounds__(256) void fri_leaf_hash_kernel(const u64* __restric
 }
 
 // The same with 16 lanes per leaf (poseidon_permute_coop16): a FRI layer has few leaves and four dependent permutations
-// per leaf, so the one-lane-per-leaf form is bound by the latency of a permutation (34 us) rather than by work.
+// per leaf, so the one-lane-per-leaf form is bound by the latency of a permutation (27 us) rather than by work.
 __global__ __launch_bounds__(256) void fri_leaf_hash_coop_kernel(const u64* __restrict__ va, const u64* __restrict__ vb, u32 log_m, u32 arity_bits,
                                                                  u64* __restrict__ digests) {
   const size_t leaf = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const size_t nleaf = (size_t)1 << (log_m - arity_bits);
   const u32 lane = threadIdx.x & 15, e = lane < 12 ? lane : lane - 12;  // lanes 12..15 mirror elements 0..3
   const u32 arity = 1u << arity_bits;
-  if (arity_bits == 1) {   // wave-uniform (a kernel argument): no lane reaches the DPP rotations below
+  if (arity_bits == 1) {   // wave-uniform (a kernel argument): no lane reaches the DPP broadcasts below
     if (leaf < nleaf && lane < 4) {
       const u32 nat = bitrev32((u32)(leaf * 2 + (lane >> 1)), log_m);
       digests[leaf * 4 + lane] = (lane & 1) ? vb[nat] : va[nat];
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void fri_leaf_hash_coop_kernel(const u64* __re
       const u32 nat = bitrev32((u32)(leaf * arity + t + (e >> 1)), log_m);
       st = (e & 1) ? vb[nat] : va[nat];
     }
-    st = poseidon_permute_coop16(st, lane);   // every lane of the row takes part (DPP rotations)
+    st = poseidon_permute_coop16(st, lane);   // every lane of the row takes part (DPP broadcasts)
   }
   if (leaf < nleaf && lane < 4) digests[leaf * 4 + lane] = st;
 }
@@ -291,6 +291,17 @@ __global__ void poseidon_batch_kernel(u64* states, size_t count) {
   for (int k = 0; k < 12; k++) s[k] = F(states[i * 12 + k]);
   poseidon_permute(s);
   for (int k = 0; k < 12; k++) states[i * 12 + k] = s[k].v;
+}
+
+// test hook: one 16-lane group per state through poseidon_permute_coop16 (sbn_poseidon_permute_coop_batch).  `count` is taken as it
+// is: a last wave or workgroup with fewer than 4 / 16 states runs its idle groups on zeros -- only the loads and stores are predicated.
+__global__ __launch_bounds__(256) void poseidon_coop_batch_kernel(u64* states, size_t count) {
+  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+  const u32 lane = threadIdx.x & 15;
+  const bool live = i < count && lane < 12;
+  const u64 v = live ? states[i * 12 + lane] : 0;
+  const u64 r = poseidon_permute_coop16(v, lane);   // every lane of the row takes part (DPP broadcasts)
+  if (live) states[i * 12 + lane] = r;
 }
 
 // =================================================================================================

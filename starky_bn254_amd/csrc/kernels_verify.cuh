@@ -5,7 +5,7 @@
 // from the words the sponge absorbs anyway.  An item is a chain of dependent permutations (G1ExpStark(128): 210 leaf blocks and
 // 13 path nodes for the trace oracle), so it runs on the 16-lane form of the permutation (poseidon_permute_coop16, as
 // fri_leaf_hash_coop_kernel and merkle_level_coop_kernel do): lane j < 12 holds state[j], lanes 12..15 mirror lanes 0..3.
-// Every lane of a row executes every permutation (DPP rotations): an item beyond the batch is masked at its loads and stores
+// Every lane of a row executes every permutation (DPP broadcasts): an item beyond the batch is masked at its loads and stores
 // and never returns early.  blockIdx.y = tree, so the 16 items of a workgroup share their trip counts.
 //
 // All proofs of one (table, config, degree_bits) share one layout (verifier_core.hpp VerifyLayout): the kernel reads a proof

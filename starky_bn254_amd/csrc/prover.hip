@@ -218,9 +218,12 @@ static int tree_alloc(DevTree& t, size_t nleaf, u32 cap_height, size_t* bytes = 
   return dmalloc(&t.d, 2 * nleaf * 4, bytes);
 }
 static int tree_build_inner(sbn_prover* P, DevTree& t, hipStream_t st) {
-  // One permutation costs 39 us on a lane and 16 us on 16 lanes, and a single wave saturates its SIMD.  So: levels with
-  // >= 2^14 parents run one lane per parent over the whole GPU; narrower levels run 16 lanes per parent, 16 parents per
+  // One permutation costs 27 us on a lane and 8.7 us on 16 lanes, and a single wave saturates its SIMD.  So: levels with
+  // >= 2^15 parents run one lane per parent over the whole GPU; narrower levels run 16 lanes per parent, 16 parents per
   // workgroup (one wave per SIMD), one launch per level; the last <= 16 parents finish inside one workgroup.
+  // The 2^14-parent level was measured both ways with the broadcast form of the 16-lane permutation: 24.9 us on 16 lanes per
+  // parent (four waves per SIMD) against 31.6 us on one lane per parent (profiles/coop16_exchange_ab.txt); with the rotation
+  // form it lost there, and the crossover sat one level lower.
   // Round 3: the narrow levels (<= 8192 parents) run FIVE levels per launch -- a workgroup owns 32 consecutive nodes and hashes its
   // own 16 -> 8 -> 4 -> 2 -> 1 parents through LDS (merkle_subtree_kernel, 16 lanes per permutation), so a 2^17-leaf tree takes
   // 3 + 2 launches instead of 3 + 10 and the dependent chain loses eight launch gaps.
@@ -233,7 +236,7 @@ static int tree_build_inner(sbn_prover* P, DevTree& t, hipStream_t st) {
       l0 += nlev;
       continue;
     }
-    if (parents >= 16384) {
+    if (parents >= 32768) {
       hipLaunchKernelGGL(merkle_level_thread_kernel, dim3((unsigned)((parents + 255) / 256)), dim3(256), 0, st, t.d, t.nleaf, l0);
       l0++;
     } else if (parents > 16) {
@@ -833,6 +836,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   P->d_fb = P->d_fa + 2 * n;
   hipc(hipHostMalloc((void**)&P->h_open, (C + Z + 4) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
   hipc(hipHostMalloc((void**)&P->h_open2, (C + Z) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
+  hipc(hipHostMalloc((void**)&P->h_w, 4096 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
   if (rc) { sbn_prover_destroy(P); return rc; }
   // tables
   auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
@@ -904,6 +908,7 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (P->h_io) (void)hipHostFree(P->h_io);
   if (P->h_open) (void)hipHostFree(P->h_open);
   if (P->h_open2) (void)hipHostFree(P->h_open2);
+  if (P->h_w) (void)hipHostFree(P->h_w);
   if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // (a refused call drained it already)
   for (auto& e : P->upload_done) if (e) (void)hipEventDestroy(e);
   for (auto& e : P->slot_copied) if (e) (void)hipEventDestroy(e);
@@ -1290,7 +1295,7 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     const u32 RW = S ? S->comm.world : 1;
     const u32 GS = RW > 1 ? (u32)SPLIT_BLOCK : 128;
     // all group weights alpha^(offset + g*stride) are known up front: one upload, no host sync in the loop
-    std::vector<u64> wall;
+    std::vector<u64> wall;   // (staged here, uploaded from the context's pinned h_w)
     auto plan = [&](u32 npoly, E2 weight0, u64 stride) { size_t off = wall.size(); u32 ng = (npoly + GS - 1) / GS; E2 ag = e2_pow(fri_alpha, stride), cur = weight0;
                                                          for (u32 k = 0; k < ng; k++) { wall.push_back(cur.a.v); wall.push_back(cur.b.v); cur = cur * ag; } return off; };
     // the split: this rank's columns only, with the weights of their global positions
@@ -1299,7 +1304,8 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     size_t w_t = tcn ? plan((u32)tcn, e2_pow(fri_alpha, RW > 1 ? tc0 : 0), gstride) : 0, w_z = tzn ? plan((u32)tzn, e2_pow(fri_alpha, C + (RW > 1 ? tc0 : 0)), gstride) : 0,
            w_q = plan(4, e2_pow(fri_alpha, C + Z), GS);
     if (wall.size() > 4096) return fail(SBN_ERR_UNSUPPORTED, "too many FRI combine groups");
-    HIPC(hipMemcpyAsync(P->d_w, wall.data(), wall.size() * sizeof(u64), hipMemcpyHostToDevice, st));
+    memcpy(P->h_w, wall.data(), wall.size() * sizeof(u64));   // pinned: the upload needs no host wait behind it
+    HIPC(hipMemcpyAsync(P->d_w, P->h_w, wall.size() * sizeof(u64), hipMemcpyHostToDevice, st));
     // alpha^k, k < GS, as two planes in the quotient's alpha-power buffer (idle now; it holds at least 1,025 words per plane)
     hipLaunchKernelGGL(ext_pow_table_kernel, dim3(1), dim3(GS), 0, st, P->d_apow, P->d_apow + GS, (size_t)GS, fri_alpha.a.v, fri_alpha.b.v);
     auto combine = [&](const u64* coeffs, u32 npoly, size_t woff, u64* oa, u64* ob, int accumulate) -> int {
@@ -1327,7 +1333,6 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     }
     HIPC(hipMemcpyAsync(f0a, f1a, 2 * n * sizeof(u64), hipMemcpyDeviceToDevice, st));
     if ((rc = combine(P->d_q, 4, w_q, f0a, f0b, 1))) return rc;
-    HIPC(stream_wait(st));  // `wall` (pageable host memory) must outlive its upload
     // final_poly = alpha^(C+Z) * (F0 / (X - zeta)) + F1 / (X - g zeta), n-1 coefficients each; times X (a zero in front, plonky2
     // 0.1.x, sbn_config.fri_variant) or zero-padded at the end; then lde -> m
     HIPC(hipMemsetAsync(P->d_fcoef, 0, 2 * m * sizeof(u64), st));
@@ -1355,11 +1360,16 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     for (size_t li = 0; li < P->fri.arity_bits.size(); li++) {
       u32 ab = P->fri.arity_bits[li];
       u64* va = P->fri_vals[li]; u64* vb = va + clen;
-      // values = coeffs.coset_fft(shift): scale by shift^i then NTT (2 base planes)
-      HIPC(hipMemcpyAsync(va, coef, 2 * clen * sizeof(u64), hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, va, clen, shift.v);
-      hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, vb, clen, shift.v);
-      if ((rc = ntt_columns(P, va, clen, va, clen, P->d_tmp, m, 2, bits, false, clen, nullptr, nullptr, 1))) return rc;
+      // values = coeffs.coset_fft(shift): scale by shift^i then NTT (2 base planes).  Layer 0 is n coefficients zero-padded to m on
+      // the coset of 7: the coset LDE of lde_coeffs, out of place, whose first pass skips the zero half
+      if (li == 0) {
+        if ((rc = ntt_columns(P, coef, clen, va, clen, P->d_tmp, m, 2, bits, false, n, P->d_shift, nullptr, 1))) return rc;
+      } else {
+        HIPC(hipMemcpyAsync(va, coef, 2 * clen * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, va, clen, shift.v);
+        hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, vb, clen, shift.v);
+        if ((rc = ntt_columns(P, va, clen, va, clen, P->d_tmp, m, 2, bits, false, clen, nullptr, nullptr, 1))) return rc;
+      }
       DevTree& t = P->fri_trees[li];
       if (t.nleaf <= 16384) hipLaunchKernelGGL(fri_leaf_hash_coop_kernel, blocks(t.nleaf * 16), dim3(256), 0, st, va, vb, bits, ab, t.d);
       else hipLaunchKernelGGL(fri_leaf_hash_kernel, blocks(t.nleaf), dim3(256), 0, st, va, vb, bits, ab, t.d);
@@ -1637,6 +1647,23 @@ extern "C" int sbn_poseidon_permute_batch(uint64_t* states, size_t count) {
   hipLaunchKernelGGL(poseidon_batch_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d, count);
   HIPC(hipMemcpy(states, d, count * 12 * sizeof(u64), hipMemcpyDeviceToHost));
   (void)hipFree(d);
+  return SBN_OK;
+}
+
+extern "C" int sbn_poseidon_permute_coop_batch(uint64_t* states, size_t count) {
+  if (!states) return fail(SBN_ERR_BAD_ARG, "null argument");
+  for (size_t i = 0; i < count * 12; i++) if (states[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "state word %zu is not canonical", i);
+  if (int rc = use_current_device("no CPU fallback")) return rc;
+  if (count == 0) return SBN_OK;
+  u64* d = nullptr;
+  HIPC(hipMalloc((void**)&d, count * 12 * sizeof(u64)));
+  hipError_t e = hipMemcpy(d, states, count * 12 * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(poseidon_coop_batch_kernel, dim3((unsigned)((count * 16 + 255) / 256)), dim3(256), 0, 0, d, count);
+    e = hipMemcpy(states, d, count * 12 * sizeof(u64), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_poseidon_permute_coop_batch: %s", hipGetErrorString(e));
   return SBN_OK;
 }
 

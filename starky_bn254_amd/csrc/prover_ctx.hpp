@@ -141,6 +141,7 @@ struct sbn_prover {
   size_t h_io_words = 0;
   u64* h_open = nullptr;                     // pinned landing buffer of the opened values [(ncols + nzs + 4)][4]
   u64* h_open2 = nullptr;                    // second landing buffer: the values at g*zeta of the trace and Z columns (the host is still reading the first)
+  u64* h_w = nullptr;                        // pinned source of the FRI combine weights (d_w, at most 4,096 words)
   size_t dev_bytes = 0;                      // device memory this context allocated (what the one-shot cache of capi.hip counts)
   // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
   hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk

@@ -1,6 +1,6 @@
 // Latency of ONE Poseidon permutation per wave in three shapes (dependent chain of `iters` permutations, one wave):
 //   thread : one lane per permutation (poseidon_permute_fast)
-//   dpp16  : 16 lanes per permutation, DPP row rotations (poseidon_permute_coop16)
+//   dpp16  : 16 lanes per permutation, DPP row broadcasts (poseidon_permute_coop16)
 //   bperm16: 16 lanes per permutation, ds_bpermute (__shfl width 16)
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../starky_bn254_amd/csrc coop_latency.hip -o coop_latency
 #include <hip/hip_runtime.h>
