@@ -220,6 +220,22 @@ int sbn_prover_prove(sbn_prover* p, sbn_proof** out);
  * such index, as load_trace does, after the trace commitment instead of in front of it.  Single-GPU provers only; the
  * trace_commit stage time includes the upload. */
 int sbn_prover_prove_host_trace(sbn_prover* p, const uint64_t* trace_col_major, const uint64_t* public_inputs, size_t n_pi, sbn_proof** out);
+/* The same for a trace held as one allocation per column, the reference's `Vec<PolynomialValues<F>>` (prove(stark, &config, trace,
+ * ...), src/curves/g1/circuit.rs:187-201): column c of the trace is columns[c][0 .. n), n = 2^degree_bits.  No flat copy is made:
+ * the upload gathers from the columns into its pinned ring (csrc/host_columns.hpp).  The columns need 8-byte alignment only, two
+ * entries may be the same pointer, and the memory is only read.
+ * flags = 0: exactly the call above on the flattened matrix -- same proof words, same refusal, same message ("trace word %zu is
+ * not canonical" with the index c * n + row, smallest first).
+ * flags = SBN_TRACE_REDUCE: the words may be any 64-bit representatives.  A trace word >= p becomes w - p on the device, behind the
+ * upload, where the scan would have run (csrc/kernels.cuh reduce_words_kernel; one subtraction suffices, 2^64 - 1 - p < p), and
+ * public inputs >= p are reduced on the host.  *reduced_out (optional) receives the number of trace words changed (0 without the
+ * flag).  Afterwards the trace is resident in canonical form: read_trace returns the reduced words.
+ * Refused before any device work, in this order: p or out null, n_columns other than the table's column count, columns[c] null or
+ * not 8-byte aligned (the message names c), an unknown flag bit (all SBN_ERR_BAD_ARG), the public-input checks of the call above,
+ * a split prover (SBN_ERR_UNSUPPORTED).  A failing call leaves no trace loaded, the streams idle and the ring free. */
+#define SBN_TRACE_REDUCE 1u   /* flags bit 0: a word >= p is taken mod p on the device instead of refused */
+int sbn_prover_prove_host_columns(sbn_prover* p, const uint64_t* const* columns, size_t n_columns, uint32_t flags,
+                                  const uint64_t* public_inputs, size_t n_pi, uint64_t* reduced_out, sbn_proof** out);
 /* Per-stage device times (ms, HIP events on the prover's stream) of the last prove():
  * names via sbn_prover_stage_name(i); returns the number of stages written. */
 int sbn_prover_stage_times(const sbn_prover* p, float* ms_out, int cap);
@@ -386,6 +402,10 @@ int sbn_prover_explain_times(const sbn_prover* p, float* ms_out, int cap);
 int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* trace_col_major, uint32_t degree_bits,
               const uint64_t* public_inputs, size_t n_pi, sbn_proof** out);
 
+/* sbn_prove with the argument list of sbn_prover_prove_host_columns: the same context cache, key and statistics. */
+int sbn_prove_columns(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* const* columns, size_t n_columns,
+                      uint32_t degree_bits, uint32_t flags, const uint64_t* public_inputs, size_t n_pi, sbn_proof** out);
+
 /* sbn_prove keeps the device contexts it creates, keyed by (device, kind, num_io, degree_bits, every sbn_config field),
  * up to budget_bytes of device memory, least recently used evicted first.  0 (the default) = create and destroy per
  * call, as before; setting 0 also destroys what is cached.  Thread-safe.  A context is handed to one call at a time: a
@@ -408,6 +428,15 @@ int sbn_batch_prover_create(const sbn_air_desc* air, const sbn_config* cfg, uint
 int sbn_batch_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t inflight, const sbn_prover_options* opt,
                                  sbn_batch_prover** out);
 int sbn_batch_prover_prove_ios(sbn_batch_prover* b, const uint32_t* ios, size_t ios_words_per_unit, size_t num_io, size_t count, sbn_proof** proofs_out);
+/* `count` units whose traces are in host memory, one allocation per column: columns[u * n_columns + c] is column c of unit u,
+ * public_inputs[u] its n_pi public inputs (public_inputs may be null when n_pi is 0), flags as for sbn_prover_prove_host_columns.
+ * Any table kind.  Each context's thread takes the next unit and uploads on the context's own copy stream, so one unit's PCIe time
+ * runs beside the other contexts' kernels.  proofs_out[count] in unit order, each the proof of sbn_prover_prove_host_columns on
+ * that unit.  On a failure: the status of the failing unit with the smallest index, its message behind "unit %zu: ", every
+ * proofs_out entry null, and the batch prover usable. */
+int sbn_batch_prover_prove_host_columns(sbn_batch_prover* b, const uint64_t* const* columns /* [count][n_columns] */, size_t n_columns,
+                                        uint32_t flags, const uint64_t* const* public_inputs /* [count] */, size_t n_pi, size_t count,
+                                        sbn_proof** proofs_out);
 void sbn_batch_prover_destroy(sbn_batch_prover* b);
 
 /* Long chained lists ------------------------------------------------------------------------------- */
@@ -755,6 +784,14 @@ int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* o
  * sbn_prover_prove_host_trace runs behind each chunk it uploads (csrc/kernels.cuh first_non_canonical_kernel), host in/out.
  * on_device = 0 runs a host loop and needs no device. */
 int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out);
+/* out[0 .. len) = the flat words [word0, word0 + len) of the column-major matrix [n_columns][n] whose column c is
+ * columns[c][0 .. n): the copy sbn_prover_prove_host_columns makes into each piece of its upload ring (csrc/host_columns.hpp).
+ * SBN_ERR_BAD_ARG when word0 + len > n_columns * n or a column pointer is null or not 8-byte aligned.  Host only. */
+int sbn_gather_columns(const uint64_t* const* columns, size_t n_columns, size_t n, size_t word0, size_t len, uint64_t* out);
+/* In place: every word >= p becomes w - p; *reduced_out (optional) = the number of words changed.  The kernel
+ * SBN_TRACE_REDUCE runs behind each chunk it uploads (csrc/kernels.cuh reduce_words_kernel), host in/out; on_device = 0 runs a
+ * host loop and needs no device. */
+int sbn_reduce_words(uint64_t* words, size_t count, int on_device, uint64_t* reduced_out);
 /* The host permutation behind the Fiat-Shamir transcript of prove()/verify() (plonky2 Challenger's
  * PoseidonPermutation): sparse partial rounds, or the plain definition when use_definition != 0.  Host only. */
 int sbn_poseidon_permute_host(uint64_t* states, size_t count, int use_definition);

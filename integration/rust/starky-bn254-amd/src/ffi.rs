@@ -124,6 +124,11 @@ extern "C" {
     pub fn sbn_prover_generate_trace_chained(p: *mut sbn_prover, terms: *const u32, num_io: usize, start: *const u32, pi_out: *mut u64, ios_out: *mut u32) -> i32;
     pub fn sbn_prover_prove(p: *mut sbn_prover, out: *mut *mut sbn_proof) -> i32;
     pub fn sbn_prover_prove_host_trace(p: *mut sbn_prover, trace_col_major: *const u64, public_inputs: *const u64, n_pi: usize, out: *mut *mut sbn_proof) -> i32;
+    pub fn sbn_prover_prove_host_columns(p: *mut sbn_prover, columns: *const *const u64, n_columns: usize, flags: u32, public_inputs: *const u64, n_pi: usize, reduced_out: *mut u64, out: *mut *mut sbn_proof) -> i32;
+    pub fn sbn_prove_columns(air: *const sbn_air_desc, cfg: *const sbn_config, columns: *const *const u64, n_columns: usize, degree_bits: u32, flags: u32, public_inputs: *const u64, n_pi: usize, out: *mut *mut sbn_proof) -> i32;
+    pub fn sbn_batch_prover_prove_host_columns(b: *mut sbn_batch_prover, columns: *const *const u64, n_columns: usize, flags: u32, public_inputs: *const *const u64, n_pi: usize, count: usize, proofs_out: *mut *mut sbn_proof) -> i32;
+    pub fn sbn_gather_columns(columns: *const *const u64, n_columns: usize, n: usize, word0: usize, len: usize, out: *mut u64) -> i32;
+    pub fn sbn_reduce_words(words: *mut u64, count: usize, on_device: i32, reduced_out: *mut u64) -> i32;
     pub fn sbn_prove_cache_configure(budget_bytes: u64) -> i32;
     pub fn sbn_prove_cache_stats(out: *mut u64) -> i32;
     pub fn sbn_first_non_canonical(words: *const u64, count: usize, on_device: i32, index_out: *mut u64) -> i32;

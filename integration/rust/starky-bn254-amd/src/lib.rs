@@ -214,6 +214,7 @@ impl Prover {
         self.finish::<F, C, D>()
     }
 
+    /// (`Prover::prove` / sbn_prover_load_trace only; `prove_host_trace` and the free `prove` read the columns where they lie.)
     /// The trace as the C ABI takes it (column-major, flat) and the public inputs, as canonical u64.  The library reads
     /// num_columns * 2^degree_bits words and n_pi public inputs: the sizes are checked here, before the FFI call.
     fn flatten<F: RichField>(&self, trace: Vec<PolynomialValues<F>>, public_inputs: &[F]) -> Result<(Vec<u64>, Vec<u64>)> {
@@ -229,18 +230,36 @@ impl Prover {
         Ok((flat, public_inputs.iter().map(|x| x.to_canonical_u64()).collect()))
     }
 
-    /// The same call with the upload INSIDE the proof (sbn_prover_prove_host_trace): the flattened trace crosses PCIe in the
-    /// commit pipeline's column chunks while earlier chunks are transformed and hashed, and the canonical-form check runs on the
-    /// device.  Same proof as `prove`; afterwards the trace is resident on the device.  (Source only, like the rest of this
-    /// crate: no Rust toolchain where the library is built and tested.)
+    /// The column pointers of a trace as sbn_prover_prove_host_columns takes them, after the size checks of `flatten`; nothing is
+    /// copied.  ASSUMPTION, unverified here (no Rust toolchain, plonky2 not vendored): `GoldilocksField` is
+    /// `#[repr(transparent)]` over one `u64`, so a column's `values.as_ptr()` points at `len` u64 words.  The words may be any
+    /// 64-bit representatives: the callers pass SBN_TRACE_REDUCE and the library takes them mod p on the device.
+    fn column_ptrs<F: RichField>(&self, trace: &[PolynomialValues<F>]) -> Result<Vec<*const u64>> {
+        let n = trace.first().map(|c| c.len()).unwrap_or(0);
+        ensure!(std::mem::size_of::<F>() == 8 && std::mem::align_of::<F>() == 8, "the field element is not one u64 word");
+        ensure!(trace.len() == self.n_cols, "the table has {} columns, the trace {}", self.n_cols, trace.len());
+        ensure!(n == 1usize << self.degree_bits, "the prover was created for 2^{} rows, the trace has {}", self.degree_bits, n);
+        ensure!(trace.iter().all(|c| c.len() == n), "ragged trace");
+        Ok(trace.iter().map(|col| col.values.as_ptr() as *const u64).collect())
+    }
+
+    /// The same call with the upload INSIDE the proof (sbn_prover_prove_host_columns): the trace crosses PCIe in the commit
+    /// pipeline's column chunks while earlier chunks are transformed and hashed, read from the columns where they lie -- no
+    /// flattened copy, no `to_canonical_u64` pass: words >= p are reduced on the device behind the upload (SBN_TRACE_REDUCE).
+    /// Same proof as `prove`; afterwards the trace is resident on the device.  (Source only, like the rest of this crate: no Rust
+    /// toolchain where the library is built and tested.)
     pub fn prove_host_trace<F, C, const D: usize>(&mut self, trace: Vec<PolynomialValues<F>>, public_inputs: &[F]) -> Result<StarkProofWithPublicInputs<F, C, D>>
     where
         F: RichField + Extendable<D>,
         C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
     {
-        let (flat, pis) = self.flatten(trace, public_inputs)?;
+        ensure!(public_inputs.len() == self.n_pi, "expected {} public inputs, got {}", self.n_pi, public_inputs.len());
+        let cols = self.column_ptrs(&trace)?;
+        let pis: Vec<u64> = public_inputs.iter().map(|x| x.to_canonical_u64()).collect();
         let mut p = ptr::null_mut();
-        check(unsafe { ffi::sbn_prover_prove_host_trace(self.raw, flat.as_ptr(), pis.as_ptr(), pis.len(), &mut p) }, "sbn_prover_prove_host_trace")?;
+        let rc = unsafe { ffi::sbn_prover_prove_host_columns(self.raw, cols.as_ptr(), cols.len(), SBN_TRACE_REDUCE, pis.as_ptr(), pis.len(), ptr::null_mut(), &mut p) };
+        drop(trace);   // the columns are read until the call returns
+        check(rc, "sbn_prover_prove_host_columns")?;
         Self::take_proof::<F, C, D>(p)
     }
 
@@ -422,6 +441,9 @@ impl TraceExplanation {
     }
 }
 
+/// flags bit 0 of sbn_prover_prove_host_columns (include/sbn.h): a word >= p is taken mod p on the device instead of refused
+pub const SBN_TRACE_REDUCE: u32 = 1;
+
 impl Drop for Prover {
     fn drop(&mut self) {
         unsafe { ffi::sbn_prover_destroy(self.raw) }
@@ -453,7 +475,7 @@ where
     ensure!(n.is_power_of_two(), "trace height must be a power of two");
     timing.push("sbn prove (MI355X)", log::Level::Debug);
     let mut prover = Prover::new(&stark, config, n.trailing_zeros() as usize)?;
-    let proof = prover.prove_host_trace::<F, C, D>(trace_poly_values, &public_inputs);   // the upload inside the trace commitment
+    let proof = prover.prove_host_trace::<F, C, D>(trace_poly_values, &public_inputs);   // the upload inside the trace commitment, from the columns where they lie
     for (name, ms) in prover.stage_times() {
         log::debug!("sbn stage {name}: {ms:.3} ms");
     }
@@ -475,6 +497,53 @@ where
     let degree_bits = proof_with_pis.proof.recover_degree_bits(config);
     let words = convert::words_from_proof::<F, C, D>(&proof_with_pis, degree_bits, config)?;
     verify_stark_proof_words(&stark, &words, config)
+}
+
+/// Several host traces in flight on one GPU (sbn_batch_prover_prove_host_columns): every unit is a trace as `prove` takes it with
+/// its public inputs; one unit's upload runs beside the other contexts' kernels.  The columns are read where they lie
+/// (`Prover::column_ptrs` names the layout assumption) and reduced on the device.  Proofs in unit order.
+pub fn prove_host_traces<F, C, S, const D: usize>(
+    stark: &S,
+    config: &StarkConfig,
+    degree_bits: usize,
+    inflight: usize,
+    traces: Vec<Vec<PolynomialValues<F>>>,
+    public_inputs: &[Vec<F>],
+) -> Result<Vec<StarkProofWithPublicInputs<F, C, D>>>
+where
+    F: RichField + Extendable<D>,
+    C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+    S: SbnTable,
+{
+    let a = air(stark);
+    let cfg = to_sbn_config(config)?;
+    let n_cols = unsafe { ffi::sbn_air_num_columns(&a) };
+    let n_pi = unsafe { ffi::sbn_air_num_public_inputs(&a) };
+    ensure!(traces.len() == public_inputs.len(), "one list of public inputs per trace");
+    ensure!(std::mem::size_of::<F>() == 8 && std::mem::align_of::<F>() == 8, "the field element is not one u64 word");
+    let mut cols: Vec<*const u64> = Vec::with_capacity(traces.len() * n_cols);
+    for t in &traces {
+        ensure!(t.len() == n_cols && t.iter().all(|c| c.len() == 1usize << degree_bits), "a trace does not have the table's shape");
+        cols.extend(t.iter().map(|col| col.values.as_ptr() as *const u64));
+    }
+    ensure!(public_inputs.iter().all(|p| p.len() == n_pi), "expected {} public inputs per trace", n_pi);
+    let pis: Vec<Vec<u64>> = public_inputs.iter().map(|p| p.iter().map(|x| x.to_canonical_u64()).collect()).collect();
+    let pi_ptrs: Vec<*const u64> = pis.iter().map(|p| p.as_ptr()).collect();
+    let mut b = ptr::null_mut();
+    check(unsafe { ffi::sbn_batch_prover_create(&a, &cfg, degree_bits as u32, inflight as u32, &mut b) }, "sbn_batch_prover_create")?;
+    let mut raw = vec![ptr::null_mut(); traces.len()];
+    let rc = unsafe { ffi::sbn_batch_prover_prove_host_columns(b, cols.as_ptr(), n_cols, SBN_TRACE_REDUCE, pi_ptrs.as_ptr(), n_pi, traces.len(), raw.as_mut_ptr()) };
+    unsafe { ffi::sbn_batch_prover_destroy(b) };
+    drop(traces);   // the columns are read until the call returns
+    check(rc, "sbn_batch_prover_prove_host_columns")?;
+    raw.into_iter()
+        .map(|p| {
+            let words = unsafe { std::slice::from_raw_parts(ffi::sbn_proof_words(p), ffi::sbn_proof_num_words(p)) };
+            let proof = convert::proof_from_words::<F, C, D>(words);
+            unsafe { ffi::sbn_proof_free(p) };
+            proof
+        })
+        .collect()
 }
 
 /// Several proofs in flight on one GPU (BASELINE config 2): `units` instance lists of `num_io` instances each.

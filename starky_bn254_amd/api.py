@@ -51,6 +51,7 @@ EXPORTS = [
     "sbn_local_comm_create", "sbn_local_comm_abort", "sbn_local_comm_destroy", "sbn_comm_selftest",
     "sbn_verifier_create", "sbn_verifier_verify", "sbn_verifier_reason", "sbn_verifier_stage_times", "sbn_verifier_destroy",
     "sbn_prover_create_with", "sbn_batch_prover_create_with", "sbn_prover_memory_plan", "sbn_lde_rows",
+    "sbn_prover_prove_host_columns", "sbn_prove_columns", "sbn_batch_prover_prove_host_columns", "sbn_gather_columns", "sbn_reduce_words",
 ]
 
 
@@ -161,6 +162,12 @@ def lib():
         L.sbn_prover_load_trace_device.argtypes = [vp, vp, vp, sz]
         L.sbn_prover_prove.argtypes = [vp, C.POINTER(vp)]
         L.sbn_prover_prove_host_trace.argtypes = [vp, vp, vp, sz, C.POINTER(vp)]
+        if hasattr(L, "sbn_prover_prove_host_columns"):   # (absent from an older build named by SBN_LIB for an A/B)
+            L.sbn_prover_prove_host_columns.argtypes = [vp, vp, sz, u32, vp, sz, vp, C.POINTER(vp)]
+            L.sbn_prove_columns.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, sz, u32, u32, vp, sz, C.POINTER(vp)]
+            L.sbn_batch_prover_prove_host_columns.argtypes = [vp, vp, sz, u32, vp, sz, sz, C.POINTER(vp)]
+            L.sbn_gather_columns.argtypes = [vp, sz, sz, sz, sz, vp]
+            L.sbn_reduce_words.argtypes = [vp, sz, C.c_int, vp]
         L.sbn_prove_cache_configure.argtypes = [C.c_uint64]
         L.sbn_prove_cache_stats.argtypes = [vp]
         L.sbn_first_non_canonical.argtypes = [vp, sz, C.c_int, vp]
@@ -1147,6 +1154,68 @@ def _host_trace_args(stark, trace, public_inputs):
     return trace, pi, n.bit_length() - 1
 
 
+TRACE_REDUCE = 1   # SBN_TRACE_REDUCE (include/sbn.h)
+
+
+_U64 = np.dtype(np.uint64)
+
+
+class ColumnTable:
+    """The pointer table of a trace held as separate columns, built once for several calls: a sequence of 1-D uint64 arrays, or a
+    2-D uint64 array whose rows are contiguous, with any stride between rows (big[::2], big[::-1]).  Nothing is copied -- an array
+    of another dtype or with strided elements is refused -- and the table keeps the references that keep the memory alive.
+    Prover.prove_host_columns, prove_columns and BatchProver.prove_host_traces take a ColumnTable wherever they take columns
+    (building the table of 1676 arrays costs about as much Python time as a millisecond of proving)."""
+
+    def __init__(self, columns):
+        if isinstance(columns, np.ndarray) and columns.ndim == 2:
+            a = columns
+            if a.dtype != _U64 or (a.shape[1] > 1 and a.strides[1] != 8):
+                raise SbnError(-1, "columns must be uint64 with contiguous rows")
+            self.addr = (a.ctypes.data + np.arange(a.shape[0], dtype=np.int64) * a.strides[0]).astype(np.uint64)
+            self.n, self._keep = a.shape[1], [a]
+        else:
+            keep = list(columns)
+            n = len(keep[0]) if keep and isinstance(keep[0], np.ndarray) and keep[0].ndim == 1 else 0
+            addr = np.empty(len(keep), dtype=np.uint64)
+            for c, a in enumerate(keep):
+                if type(a) is not np.ndarray or (a.dtype is not _U64 and a.dtype != _U64) or a.shape != (n,) or (n > 1 and a.strides[0] != 8):
+                    raise SbnError(-1, f"column {c} must be a contiguous 1-D uint64 array of the first column's length")
+                addr[c] = a.__array_interface__["data"][0]
+            self.addr, self.n, self._keep = addr, n, keep
+
+    def __len__(self):
+        return len(self.addr)
+
+
+def _column_pointers(columns, ncols=None, n=None):
+    """The ColumnTable of `columns` (itself, if it is one), checked against a table's column count and height."""
+    t = columns if isinstance(columns, ColumnTable) else ColumnTable(columns)
+    if (ncols is not None and len(t) != ncols) or (n is not None and t.n != n):
+        raise SbnError(-1, "columns do not match the table")
+    return t
+
+
+def gather_columns(columns, word0, length):
+    """Flat words [word0, word0 + length) of the column-major matrix whose columns are `columns` (sbn_gather_columns: the copy
+    Prover.prove_host_columns makes into each piece of its upload ring; test hook).  No device needed."""
+    t = _column_pointers(columns)
+    out = np.zeros(length, dtype=np.uint64)
+    _check(lib().sbn_gather_columns(_ptr(t.addr), len(t), t.n, word0, length, _ptr(out)))
+    return out
+
+
+def reduce_words(words, on_device=True):
+    """In place, every word >= p of a contiguous 1-D uint64 array becomes w - p; returns how many changed (sbn_reduce_words: the
+    kernel of Prover.prove_host_columns(reduce=True); test hook).  on_device=False runs a host loop and needs no device."""
+    w = words
+    if not isinstance(w, np.ndarray) or w.dtype != np.uint64 or w.ndim != 1 or (len(w) > 1 and w.strides[0] != 8) or not w.flags.writeable:
+        raise SbnError(-1, "words must be a writeable contiguous 1-D uint64 array")
+    out = C.c_uint64(0)
+    _check(lib().sbn_reduce_words(_ptr(w), len(w), 1 if on_device else 0, C.byref(out)))
+    return int(out.value)
+
+
 def explain_rows_host(stark, trace, public_inputs, rows, seed=0):
     """Which constraint blocks and Z columns the listed rows of `trace` break, on host threads (sbn_explain_rows_host).  The
     same RowsExplanation, for the same seed, as Prover.explain_rows gives for the loaded trace."""
@@ -1300,6 +1369,19 @@ class Prover:
         _check(lib().sbn_prover_prove_host_trace(self._h, _ptr(trace), _ptr(pi), len(pi), C.byref(h)))
         return _take_proof(h)
 
+    def prove_host_columns(self, columns, public_inputs, reduce=False):
+        """prove_host_trace for a trace held as separate columns (the reference's Vec<PolynomialValues<F>>): a sequence of 1-D
+        uint64 arrays, or a 2-D array whose rows are contiguous with any stride between them.  The data is never copied on the
+        host: the upload gathers from the columns into its pinned ring.  reduce=False: the proof and the refusals of
+        prove_host_trace on the flattened matrix.  reduce=True: words and public inputs >= p are taken mod p (the words on the
+        device) instead of refused, and (Proof, number of trace words changed) is returned."""
+        t = _column_pointers(columns, self.stark.num_columns, 1 << self.degree_bits)   # (holds the references during the call)
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        h, reduced = C.c_void_p(), C.c_uint64(0)
+        _check(lib().sbn_prover_prove_host_columns(self._h, _ptr(t.addr), len(t), TRACE_REDUCE if reduce else 0, _ptr(pi), len(pi), C.byref(reduced), C.byref(h)))
+        proof = _take_proof(h)
+        return (proof, int(reduced.value)) if reduce else proof
+
     def stage_times(self):
         buf = (C.c_float * 32)()
         k = lib().sbn_prover_stage_times(self._h, buf, 32)
@@ -1355,6 +1437,23 @@ class BatchProver:
         count, num_io, w = ios.shape
         out = (C.c_void_p * count)()
         _check(lib().sbn_batch_prover_prove_ios(self._h, _ptr(ios), num_io * w, num_io, count, out))
+        return self._proofs(out, count)
+
+    def prove_host_traces(self, units, public_inputs, reduce=False):
+        """Units whose traces are in host memory: `units` is a sequence of column sequences as Prover.prove_host_columns takes
+        them, public_inputs one array per unit (sbn_batch_prover_prove_host_columns; any table).  -> list of Proof, in unit order;
+        one unit's upload runs beside the other contexts' kernels."""
+        ncols, n = self.stark.num_columns, 1 << self.degree_bits
+        tables = [_column_pointers(u, ncols, n) for u in units]
+        count = len(tables)
+        pis = [np.ascontiguousarray(p, dtype=np.uint64) for p in public_inputs]
+        n_pi = self.stark.num_public_inputs
+        if len(pis) != count or any(len(p) != n_pi for p in pis):
+            raise SbnError(-1, "one array of the table's public inputs per unit")
+        addr = np.concatenate([t.addr for t in tables]) if count else np.zeros(0, dtype=np.uint64)
+        pi_addr = np.array([p.ctypes.data for p in pis], dtype=np.uint64)
+        out = (C.c_void_p * max(count, 1))()
+        _check(lib().sbn_batch_prover_prove_host_columns(self._h, _ptr(addr), ncols, TRACE_REDUCE if reduce else 0, _ptr(pi_addr), n_pi, count, out))
         return self._proofs(out, count)
 
     def prove_msm(self, terms, start):
@@ -1441,6 +1540,19 @@ def prove(stark, config, trace_poly_values, public_inputs, timing=None):
         raise SbnError(-1, "trace shape does not match the table")
     h = C.c_void_p()
     _check(lib().sbn_prove(C.byref(stark._d), C.byref(config._c), _ptr(trace), n.bit_length() - 1, _ptr(pi), len(pi), C.byref(h)))
+    return _take_proof(h)
+
+
+def prove_columns(stark, config, columns, public_inputs, reduce=False):
+    """prove() for a trace held as separate columns (Prover.prove_host_columns says which forms), through the same context cache."""
+    t = _column_pointers(columns, stark.num_columns)
+    n = t.n
+    if n == 0 or n & (n - 1):
+        raise SbnError(-1, "trace shape does not match the table")
+    pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    h = C.c_void_p()
+    _check(lib().sbn_prove_columns(C.byref(stark._d), C.byref(config._c), _ptr(t.addr), len(t), n.bit_length() - 1, TRACE_REDUCE if reduce else 0,
+                                   _ptr(pi), len(pi), C.byref(h)))
     return _take_proof(h)
 
 

@@ -129,8 +129,8 @@ size_t sbn_proof_serialize(const sbn_proof* p, uint8_t* buf, size_t cap) {
 uint32_t sbn_proof_degree_bits(const sbn_proof* p) { return p ? p->degree_bits : 0; }
 void sbn_proof_free(sbn_proof* p) { delete p; }
 
-int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* trace, uint32_t degree_bits, const uint64_t* pi, size_t n_pi,
-              sbn_proof** out) {
+// the one-shot call on a context of the cache (or a fresh one): `call` is the prover call with the caller's trace
+static int prove_one_shot(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, sbn_proof** out, const std::function<int(sbn_prover*)>& call) {
   if (!out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   CacheKey key{};
@@ -139,8 +139,7 @@ int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* tr
   sbn_prover* P = keyed ? cache_take(key) : nullptr;
   int rc = 0;
   if (!P && (rc = sbn_prover_create(air, cfg, degree_bits, &P))) return rc;
-  if (!trace) rc = fail(SBN_ERR_BAD_ARG, "null argument");
-  else rc = sbn_prover_prove_host_trace(P, trace, pi, n_pi, out);
+  rc = call(P);
   if (rc) {   // a context whose call failed is not kept (destroy leaves the message of the failure in place)
     const std::string msg = g_last_error;
     sbn_prover_destroy(P);
@@ -149,6 +148,18 @@ int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* tr
   }
   cache_give(key, P);
   return rc;
+}
+int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* trace, uint32_t degree_bits, const uint64_t* pi, size_t n_pi,
+              sbn_proof** out) {
+  return prove_one_shot(air, cfg, degree_bits, out, [&](sbn_prover* P) {
+    if (!trace) return fail(SBN_ERR_BAD_ARG, "null argument");
+    return sbn_prover_prove_host_trace(P, trace, pi, n_pi, out);
+  });
+}
+// sbn_prove for a trace held as one allocation per column (sbn_prover_prove_host_columns): the same cache, key and statistics
+int sbn_prove_columns(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* const* columns, size_t n_columns, uint32_t degree_bits, uint32_t flags,
+                      const uint64_t* pi, size_t n_pi, sbn_proof** out) {
+  return prove_one_shot(air, cfg, degree_bits, out, [&](sbn_prover* P) { return sbn_prover_prove_host_columns(P, columns, n_columns, flags, pi, n_pi, nullptr, out); });
 }
 
 // ---- batch mode (BASELINE config[2]: a batch of independent proofs per GPU) -------------------------------------------
@@ -204,6 +215,34 @@ int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t 
   if (first_rc.load()) {
     for (size_t i = 0; i < count; i++) { delete proofs_out[i]; proofs_out[i] = nullptr; }
     return fail(first_rc.load(), "%s", msg.c_str());
+  }
+  return SBN_OK;
+}
+
+// Units whose traces are already in host memory, one allocation per column (sbn_prover_prove_host_columns per unit): the shape of
+// prove_ios above, each context's thread takes the next unit.  Every context uploads on its own copy stream through its own pinned
+// ring, so one unit's PCIe time runs beside the others' kernels; the host copies into the rings share the worker pool, which runs
+// one parallel loop at a time (tracegen.hip WorkerPool::run), as the witness loops of prove_ios do.
+int sbn_batch_prover_prove_host_columns(sbn_batch_prover* B, const uint64_t* const* columns, size_t n_columns, uint32_t flags,
+                                        const uint64_t* const* public_inputs, size_t n_pi, size_t count, sbn_proof** proofs_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  for (size_t i = 0; i < count; i++) proofs_out[i] = nullptr;
+  if (count && (!columns || (n_pi && !public_inputs))) return fail(SBN_ERR_BAD_ARG, "null argument");
+  std::atomic<size_t> next(0), first_unit(count);
+  std::mutex m; int first_rc = 0; std::string msg;
+  auto work = [&](sbn_prover* P) {
+    for (size_t u; (u = next.fetch_add(1)) < count && first_unit.load() == count;) {
+      const int rc = sbn_prover_prove_host_columns(P, columns + u * n_columns, n_columns, flags, n_pi ? public_inputs[u] : nullptr, n_pi, nullptr, &proofs_out[u]);
+      if (rc) { std::lock_guard<std::mutex> g(m); if (u < first_unit.load()) { first_unit = u; first_rc = rc; msg = g_last_error; } }
+    }
+  };
+  std::vector<std::thread> th;
+  for (size_t i = 1; i < B->provers.size() && i < count; i++) th.emplace_back(work, B->provers[i]);
+  work(B->provers[0]);
+  for (auto& t : th) t.join();
+  if (first_rc) {
+    for (size_t i = 0; i < count; i++) { delete proofs_out[i]; proofs_out[i] = nullptr; }
+    return fail(first_rc, "unit %zu: %s", first_unit.load(), msg.c_str());
   }
   return SBN_OK;
 }

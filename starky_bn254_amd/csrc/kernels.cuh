@@ -881,3 +881,33 @@ __global__ __launch_bounds__(256) void first_non_canonical_kernel(const u64* __r
   for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor((unsigned long long)bad, d, 64); bad = o < bad ? o : bad; }
   if ((threadIdx.x & 63) == 0) atomicMin(first_bad, (unsigned long long)(base + bad));
 }
+
+// The scan's twin for SBN_TRACE_REDUCE (prover.hip prove_host_columns; sbn_reduce_words): in place, w[i] >= p becomes w[i] - p
+// (one subtraction: 2^64 - 1 - p < p), and *reduced grows by the number of words changed.  Bandwidth-bound: 16-byte loads,
+// grid-stride, no LDS; a lane stores only a vector it changed, so a canonical trace costs what the scan costs (reads only).  The
+// loop is wave-uniform (a wave leaves it as a whole), so the changed words are counted from ballots, and a wave that changed
+// something issues one atomicAdd from its first lane.  Head and tail as in the scan: `w` may sit 8 bytes off a 16-byte boundary.
+__global__ __launch_bounds__(256) void reduce_words_kernel(u64* __restrict__ w, size_t count, unsigned long long* reduced) {
+  const size_t head = (((size_t)w & 8) && count) ? 1 : 0;
+  u64x2_t* __restrict__ v = reinterpret_cast<u64x2_t*>(w + head);
+  const size_t nvec = (count - head) >> 1;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t lane = threadIdx.x & 63;
+  unsigned long long changed = 0;   // wave-uniform
+  for (size_t i0 = tid - lane; i0 < nvec; i0 += stride) {
+    const size_t i = i0 + lane;
+    bool b0 = false, b1 = false;
+    if (i < nvec) {
+      u64x2_t x = v[i];
+      b0 = x.x >= GLP; b1 = x.y >= GLP;
+      if (b0 | b1) { if (b0) x.x -= GLP; if (b1) x.y -= GLP; v[i] = x; }
+    }
+    if (__any(b0 | b1)) changed += (unsigned long long)(__popcll(__ballot(b0)) + __popcll(__ballot(b1)));
+  }
+  if (tid == 0) {   // (lane 0 of the grid's first wave: what it adds here its atomicAdd below carries)
+    const size_t last = head + 2 * nvec;   // < count iff one word is left behind the vectors
+    if (last < count && w[last] >= GLP) { w[last] -= GLP; changed++; }
+    if (head && w[0] >= GLP) { w[0] -= GLP; changed++; }
+  }
+  if (lane == 0 && changed) atomicAdd(reduced, changed);
+}

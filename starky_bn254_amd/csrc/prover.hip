@@ -4,6 +4,7 @@
 // stage runs in the kernels of kernels.cuh on one HIP stream.
 #include "prover_ctx.hpp"
 #include "kernels.cuh"
+#include "host_columns.hpp"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -261,11 +262,14 @@ static int tree_from_matrix(sbn_prover* P, DevTree& t, const u64* lde, size_t nc
 }
 // ---- prove_host_trace: the upload side ------------------------------------------------------------------------------
 // The trace of sbn_prover_prove_host_trace crosses PCIe in the commit pipeline's own column chunks: host threads copy a piece of
-// the caller's (pageable, possibly read-only) matrix into a pinned ring slot, a hipMemcpyAsync on the copy stream moves it to its
+// the caller's (pageable, possibly read-only) matrix into a pinned ring slot (through gather_columns of host_columns.hpp: the matrix
+// may be one flat allocation or one allocation per column), a hipMemcpyAsync on the copy stream moves it to its
 // place in d_trace, and after the last piece of chunk k the copy stream scans the chunk for words >= p and records
 // upload_done[k].  A slot is refilled only once the event of its previous copy has completed, so the host runs at most
 // UPLOAD_SLOTS pieces ahead of the copy engine.
-struct HostUpload { const u64* src; hipEvent_t* done; };   // the caller's trace; done[k]: chunk k is resident and scanned
+// the caller's trace; done[k]: chunk k is resident and scanned; reduce (SBN_TRACE_REDUCE): reduce_words_kernel takes the scan's
+// place, and d_first_bad counts the words it changed instead of holding the first one refused
+struct HostUpload { HostColumns src; hipEvent_t* done; bool reduce; };
 static int upload_setup(sbn_prover* P) {   // idempotent: a call that failed half way is completed by the next one
   if (!P->ustream) HIPC(hipStreamCreate(&P->ustream));
   for (auto& e : P->upload_done) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -279,6 +283,10 @@ static void launch_first_non_canonical(const u64* d_words, size_t count, u64 bas
   const size_t blocks = std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048);   // grid-stride beyond 8 waves per CU
   hipLaunchKernelGGL(first_non_canonical_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_words, count, base, d_first_bad);
 }
+static void launch_reduce_words(u64* d_words, size_t count, unsigned long long* d_reduced, hipStream_t st) {
+  const size_t blocks = std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048);   // the scan's grid
+  hipLaunchKernelGGL(reduce_words_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_words, count, d_reduced);
+}
 static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0, size_t nc) {
   const size_t w0 = c0 * P->n, w1 = w0 + nc * P->n;
   const size_t threads = std::min<size_t>(tracegen_host_threads(), 16);
@@ -287,14 +295,14 @@ static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0
     const unsigned s = P->slot_next; P->slot_next = (s + 1) % UPLOAD_SLOTS;
     if (P->slot_used[s]) HIPC(hipEventSynchronize(P->slot_copied[s]));
     u64* slot = P->h_ring + (size_t)s * UPLOAD_SLOT_WORDS;
-    const u64* from = up.src + a;
     const size_t parts = std::max<size_t>(1, std::min(threads, len >> 15)), per = (len + parts - 1) / parts;   // >= 256 KiB per thread
-    host_parallel_for(parts, [&](size_t t) { const size_t b0 = t * per, b1 = std::min(len, b0 + per); if (b0 < b1) memcpy(slot + b0, from + b0, (b1 - b0) * sizeof(u64)); });
+    host_parallel_for(parts, [&](size_t t) { const size_t b0 = t * per, b1 = std::min(len, b0 + per); if (b0 < b1) gather_columns(up.src, a + b0, b1 - b0, slot + b0); });
     HIPC(hipMemcpyAsync(P->d_trace + a, slot, len * sizeof(u64), hipMemcpyHostToDevice, P->ustream));
     HIPC(hipEventRecord(P->slot_copied[s], P->ustream));
     P->slot_used[s] = true;
   }
-  launch_first_non_canonical(P->d_trace + w0, w1 - w0, (u64)w0, P->d_first_bad, P->ustream);
+  if (up.reduce) launch_reduce_words(P->d_trace + w0, w1 - w0, P->d_first_bad, P->ustream);
+  else launch_first_non_canonical(P->d_trace + w0, w1 - w0, (u64)w0, P->d_first_bad, P->ustream);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(up.done[k], P->ustream));
   return 0;
@@ -1097,14 +1105,14 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
     for (u32 r = 0; r < S->comm.world; r++) if (!st_all[r]) return fail(SBN_ERR_BAD_ARG, "split proof abandoned: rank %u has no trace loaded", r);
   }
   if (!up && !P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
-  if (up) HIPC(hipMemsetAsync(P->d_first_bad, 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
+  if (up) HIPC(hipMemsetAsync(P->d_first_bad, up->reduce ? 0 : 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
   if (S) {
     S->tev_used = 0;
     if ((rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t))) return rc;
   } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up, P->compact ? P->d_lde : nullptr))) return rc;
   HIPC(hipEventRecord(P->ev[ST_PERM_Z], st));
   if ((rc = S ? split_cap_to_host(P, P->tree_t, trace_cap) : tree_cap_to_host(P, P->tree_t, trace_cap, up != nullptr))) return rc;
-  if (up && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
+  if (up && !up->reduce && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
   ch.observe_words(trace_cap.data(), capw);
 
   // P2 permutation argument -------------------------------------------------------------------------
@@ -1517,6 +1525,21 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
 extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_impl(P, out, nullptr); }
 
 // load + prove in one call (include/sbn.h): the upload runs inside the trace commitment, the canonical-form check on the device
+static int prove_upload(sbn_prover* P, const HostColumns& src, bool reduce, uint64_t* reduced_out, sbn_proof** out) {
+  HIPC(hipSetDevice(P->device));
+  int rc;
+  if ((rc = upload_setup(P))) return rc;
+  const HostUpload up{src, P->upload_done, reduce};
+  if ((rc = prove_impl(P, out, &up))) {
+    // whatever was enqueued (the rest of an upload, transforms of a refused trace) ends before the caller sees the error:
+    // the next call finds idle streams and a free ring
+    for (hipStream_t s : {P->ustream, P->stream, P->hstream, P->nstream}) if (s) (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  if (reduce && reduced_out) *reduced_out = *P->h_first_bad;   // (the counter came back with the trace cap)
+  P->loaded = true;
+  return SBN_OK;
+}
 extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi, sbn_proof** out) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
@@ -1524,17 +1547,31 @@ extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace,
   if (!trace) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "sbn_prover_prove_host_trace covers single-GPU provers");
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
-  HIPC(hipSetDevice(P->device));
-  if ((rc = upload_setup(P))) return rc;
-  const HostUpload up{trace, P->upload_done};
-  if ((rc = prove_impl(P, out, &up))) {
-    // whatever was enqueued (the rest of an upload, transforms of a refused trace) ends before the caller sees the error:
-    // the next call finds idle streams and a free ring
-    for (hipStream_t s : {P->ustream, P->stream, P->hstream, P->nstream}) if (s) (void)hipStreamSynchronize(s);
-    return rc;
-  }
-  P->loaded = true;
-  return SBN_OK;
+  return prove_upload(P, HostColumns{nullptr, trace, P->n}, false, nullptr, out);
+}
+// the same for a trace held as one allocation per column (csrc/host_columns.hpp); SBN_TRACE_REDUCE: words and public inputs >= p
+// are taken mod p (the words on the device, behind the upload) instead of refused
+extern "C" int sbn_prover_prove_host_columns(sbn_prover* P, const uint64_t* const* columns, size_t n_columns, uint32_t flags, const uint64_t* pi, size_t n_pi,
+                                             uint64_t* reduced_out, sbn_proof** out) {
+  if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  *out = nullptr;
+  P->loaded = false;
+  if (reduced_out) *reduced_out = 0;
+  if (n_columns != P->air.ncols) return fail(SBN_ERR_BAD_ARG, "expected %zu columns, got %zu", P->air.ncols, n_columns);
+  if (!columns) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (const size_t bad = gather_columns_refused(columns, n_columns, P->n, 0, n_columns * P->n))
+    return fail(SBN_ERR_BAD_ARG, "column %zu is null or not 8-byte aligned", bad - 2);
+  if (flags & ~SBN_TRACE_REDUCE) return fail(SBN_ERR_BAD_ARG, "unknown flag bits 0x%x", flags & ~SBN_TRACE_REDUCE);
+  const bool reduce = (flags & SBN_TRACE_REDUCE) != 0;
+  int rc;
+  if (reduce && pi && n_pi == P->air.npi) {   // (a wrong count or a null pointer: check_pi below says so)
+    std::vector<u64> red(pi, pi + n_pi);
+    reduce_words_host(red.data(), n_pi);
+    rc = check_pi(P, red.data(), n_pi);
+  } else rc = check_pi(P, pi, n_pi);
+  if (rc) return rc;
+  if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "sbn_prover_prove_host_columns covers single-GPU provers");
+  return prove_upload(P, HostColumns{columns, nullptr, P->n}, reduce, reduced_out, out);
 }
 
 // ---- building blocks for parity tests ---------------------------------------------------------------
@@ -1710,6 +1747,47 @@ extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int 
   (void)hipFree(d);
   if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_first_non_canonical: %s", hipGetErrorString(e));
   if (first != ~0ull) *index_out = first;
+  return SBN_OK;
+}
+
+// gather_columns of csrc/host_columns.hpp as a building block: what the upload of sbn_prover_prove_host_columns copies into a ring piece
+extern "C" int sbn_gather_columns(const uint64_t* const* columns, size_t n_columns, size_t n, size_t word0, size_t len, uint64_t* out) {
+  if (const size_t bad = gather_columns_refused(columns, n_columns, n, word0, len)) {
+    if (bad == 1) return fail(SBN_ERR_BAD_ARG, "words %zu + %zu lie beyond the %zu x %zu matrix", word0, len, n_columns, n);
+    return fail(SBN_ERR_BAD_ARG, "column %zu is null or not 8-byte aligned", bad - 2);
+  }
+  if (len && !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  gather_columns(HostColumns{columns, nullptr, n}, word0, len, out);
+  return SBN_OK;
+}
+// In place: words >= p become w - p; *reduced_out (optional) = how many changed.  reduce_words_kernel of SBN_TRACE_REDUCE as a
+// building block (host in, host out), or the host loop.
+extern "C" int sbn_reduce_words(uint64_t* words, size_t count, int on_device, uint64_t* reduced_out) {
+  if (!words && count) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (reduced_out) *reduced_out = 0;
+  if (!on_device) {
+    const uint64_t changed = reduce_words_host(words, count);
+    if (reduced_out) *reduced_out = changed;
+    return SBN_OK;
+  }
+  if (int rc = use_current_device("no CPU fallback")) return rc;
+  if (count == 0) return SBN_OK;
+  // the device copy keeps the caller's offset from a 16-byte boundary, so the kernel's unaligned head is reachable from a test
+  const size_t off = ((size_t)words & 8) ? 1 : 0;
+  u64* d = nullptr;
+  HIPC(hipMalloc((void**)&d, (2 + off + count) * sizeof(u64)));   // d[0]: the counter; the data from d + 2 + off
+  unsigned long long changed = 0;
+  hipError_t e = hipMemset(d, 0, sizeof(u64));
+  if (e == hipSuccess) e = hipMemcpy(d + 2 + off, words, count * sizeof(u64), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_reduce_words(d + 2 + off, count, (unsigned long long*)d, 0);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(&changed, d, sizeof changed, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(words, d + 2 + off, count * sizeof(u64), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_reduce_words: %s", hipGetErrorString(e));
+  if (reduced_out) *reduced_out = changed;
   return SBN_OK;
 }
 
