@@ -12,6 +12,7 @@
 #include <atomic>
 #include <chrono>
 #include <functional>
+#include <memory>
 
 namespace sbn { thread_local std::string g_last_error; }
 
@@ -39,11 +40,23 @@ static const char* STAGE_NAMES[ST_COUNT + EX_COUNT] = {
   "trace_absorb_kernels_ms", "trace_absorb_launches", "z_absorb_kernels_ms", "z_absorb_launches", "device_tracegen_ms",
   "split_exchange_ms"};
 
-static int dmalloc(u64** p, size_t words, size_t* bytes = nullptr) {   // bytes: the context's running total (sbn_prover::dev_bytes)
-  HIPC(hipMalloc((void**)p, words * sizeof(u64)));
-  if (bytes) *bytes += words * sizeof(u64);
+static inline dim3 blocks(size_t k) { return dim3((unsigned)((k + 255) / 256)); }   // workgroups of 256 threads over k items
+
+// ---- device memory of a context ---------------------------------------------------------------------
+// Every device buffer of a context -- the list of ctx_buffers, the lazy d_first_bad of prove_host_trace, the buffers of a scratch
+// context -- is allocated here and nowhere else: the pointer joins P->owned, which is all that sbn_prover_destroy frees, and the
+// bytes join P->dev_bytes.  Stops at the first failure; what was allocated until then is in `owned` already.
+struct BufReq { void** slot; size_t bytes; };
+static int alloc_buffers(sbn_prover* P, const std::vector<BufReq>& L) {
+  for (const BufReq& b : L) {
+    const hipError_t e = hipMalloc(b.slot, b.bytes);
+    if (e != hipSuccess) { *b.slot = nullptr; return fail(SBN_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
+    P->owned.push_back(*b.slot);
+    P->dev_bytes += b.bytes;
+  }
   return 0;
 }
+static inline BufReq words_req(u64** p, size_t words) { return BufReq{(void**)p, words * sizeof(u64)}; }
 
 // ---- NTT driver -----------------------------------------------------------------------------------
 static u32 pick_log_t(u32 log_r, u32 log_s) {
@@ -121,7 +134,7 @@ static int ntt_fast_setup() {  // idempotent, so a race between prover threads i
   }
   return 0;
 }
-// The transform kernels of a table, a function of its height and rate_bits alone.  create_ctx and sbn_commit_values both pick them
+// The transform kernels of a table, a function of its height and rate_bits alone.  create_ctx and ScratchCtx both pick them
 // here, so the parity tests of sbn_commit_values run the kernels the prover runs.  rate_bits 1 -- 2^16 / 2^17 rows: the fused middle
 // pass (its geometry is that of a 2n-point LDE); 2^18 rows (the 2^19-point LDE): its 512-point form, and the LDE's 1,024-point
 // first pass as two 512-point halves -- both read d_shift_odd, which the callers allocate exactly when ntt_fused512 is set.
@@ -139,6 +152,20 @@ static void lde_za_tables(sbn_prover* P) {
   const u32 log_s = P->lde_log - 8 - P->lde_za_log;
   hipLaunchKernelGGL(shift_za_table_kernel, dim3((unsigned)((P->n + 255) / 256), 1u << P->lde_za_log), dim3(256), 0, P->stream, P->d_shift_za, P->n, P->d_shift,
                      P->d_tw_f, log_s);
+}
+// The tables of the transforms, on P->stream: of a real context (create_ctx) and of a scratch context alike, each table exactly
+// when its buffer is allocated.
+// d_tw_f / d_tw_i: FULL root tables (w^i for every i < m: the second half is the negated first): the register passes index them
+// without the compare / negate of a half table (tw_full, kernels_ntt.cuh); everything else reads the first half only
+static void fill_transform_tables(sbn_prover* P) {
+  const size_t n = P->n, m = P->m;
+  const F w = f_root_of_unity(P->lde_log);
+  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_tw_f, m, w.v);
+  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_tw_i, m, f_inv(w).v);
+  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_shift, m, (u64)GL_GEN);
+  if (P->d_shift_inv) hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_shift_inv, m, f_inv(F(GL_GEN)).v);
+  if (P->d_shift_odd) hipLaunchKernelGGL(shift_odd_table_kernel, blocks(n), dim3(256), 0, P->stream, P->d_shift_odd, n, P->d_shift, P->d_tw_f, 9u);
+  if (P->d_shift_za) lde_za_tables(P);
 }
 
 // values [ncols][n] -> coefficients [ncols][n]
@@ -212,11 +239,10 @@ static int intt_lde_cols(sbn_prover* P, const u64* v, u64* cf, u64* lde_out, siz
   return lde_cols(P, cf, lde_out, P->d_tmp, nc, P->stream, before_write);
 }
 
-static int tree_alloc(DevTree& t, size_t nleaf, u32 cap_height, size_t* bytes = nullptr) {
+static void tree_shape(DevTree& t, size_t nleaf, u32 cap_height) {   // the digests themselves: 2 * nleaf * 4 words at t.d
   t.nleaf = nleaf;
   u32 lg = 0; while (((size_t)1 << lg) < nleaf) lg++;
   t.nlevels = lg - cap_height;
-  return dmalloc(&t.d, 2 * nleaf * 4, bytes);
 }
 static int tree_build_inner(sbn_prover* P, DevTree& t, hipStream_t st) {
   // One permutation costs 27 us on a lane and 8.7 us on 16 lanes, and a single wave saturates its SIMD.  So: levels with
@@ -276,16 +302,16 @@ static int upload_setup(sbn_prover* P) {   // idempotent: a call that failed hal
   for (auto& e : P->slot_copied) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   if (!P->h_ring) HIPC(hipHostMalloc((void**)&P->h_ring, UPLOAD_SLOTS * UPLOAD_SLOT_WORDS * sizeof(u64), hipHostMallocDefault));
   if (!P->h_first_bad) HIPC(hipHostMalloc((void**)&P->h_first_bad, sizeof(unsigned long long), hipHostMallocDefault));
-  if (!P->d_first_bad) { HIPC(hipMalloc((void**)&P->d_first_bad, sizeof(unsigned long long))); P->dev_bytes += sizeof(unsigned long long); }
+  if (!P->d_first_bad) return alloc_buffers(P, {BufReq{(void**)&P->d_first_bad, sizeof(unsigned long long)}});   // lazy, outside the plan (include/sbn.h)
   return 0;
 }
+// the grid of the scan and of its reducing twin: two words per thread, grid-stride beyond 8 waves per CU
+static inline dim3 scan_grid(size_t count) { return dim3((unsigned)std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048)); }
 static void launch_first_non_canonical(const u64* d_words, size_t count, u64 base, unsigned long long* d_first_bad, hipStream_t st) {
-  const size_t blocks = std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048);   // grid-stride beyond 8 waves per CU
-  hipLaunchKernelGGL(first_non_canonical_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_words, count, base, d_first_bad);
+  hipLaunchKernelGGL(first_non_canonical_kernel, scan_grid(count), dim3(256), 0, st, d_words, count, base, d_first_bad);
 }
 static void launch_reduce_words(u64* d_words, size_t count, unsigned long long* d_reduced, hipStream_t st) {
-  const size_t blocks = std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048);   // the scan's grid
-  hipLaunchKernelGGL(reduce_words_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_words, count, d_reduced);
+  hipLaunchKernelGGL(reduce_words_kernel, scan_grid(count), dim3(256), 0, st, d_words, count, d_reduced);
 }
 static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0, size_t nc) {
   const size_t w0 = c0 * P->n, w1 = w0 + nc * P->n;
@@ -591,8 +617,8 @@ static int split_sizes(const AirShape& as, u32 degree_bits, u32 rate_bits, u32 w
 // ---- what a context is made of --------------------------------------------------------------------------------------------
 // create_ctx runs in three steps so that sbn_prover_memory_plan can follow it without a device: ctx_check_args (the refusals that
 // need no device), ctx_shape (every size-bearing field of the context: transform plan, chunk, FRI shape, query stride, storage
-// mode) and ctx_buffers, the ONE list of (buffer, bytes) of a context.  create_ctx allocates the list, the plan sums it.
-struct BufReq { void** slot; size_t bytes; };
+// mode) and ctx_buffers, the ONE list of (buffer, bytes) of a context.  create_ctx allocates the list (alloc_buffers: into P->owned,
+// which sbn_prover_destroy frees), the plan sums it.
 static int ctx_check_args(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, const sbn_prover_options* opt, AirShape& as,
                           u32& lde_storage) {
   if (!air || !cfg) return fail(SBN_ERR_BAD_ARG, "null argument");
@@ -667,21 +693,16 @@ static int ctx_shape(sbn_prover* P, const AirShape& as, const sbn_config* cfg, u
   }
   return 0;
 }
-static void tree_shape(DevTree& t, size_t nleaf, u32 cap_height) {
-  t.nleaf = nleaf;
-  u32 lg = 0; while (((size_t)1 << lg) < nleaf) lg++;
-  t.nlevels = lg - cap_height;
-}
 // Not a pure function of P: it also completes the shape it lists -- lde_scratch_words, the leaf and level counts of the trees, the
 // lengths of fri_vals / fri_trees (whose elements the list points into) -- so it is called exactly once per context, by create_ctx
-// or by the plan.  (tree_alloc above is what sbn_commit_values still uses for its one tree.)
+// or by the plan.
 // Every device buffer a context holds from creation on, in allocation order.  Not in the list (allocated by the first call that
 // needs them, include/sbn.h sbn_prover_memory_plan): d_first_bad of prove_host_trace (8 bytes; its upload ring is pinned host memory).
 static void ctx_buffers(sbn_prover* P, std::vector<BufReq>& L) {
   const AirShape& as = P->air; const sbn_config* cfg = &P->cfg;
   // qn: the quotient's domain, the coset of 2n points (quotient_degree_bits = 1) whatever the rate: LDE rows k * m / qn
   const size_t n = P->n, m = P->m, qn = 2 * n, C = as.ncols, Z = as.nzs;
-  auto words = [&](u64** p, size_t w) { L.push_back(BufReq{(void**)p, w * sizeof(u64)}); };
+  auto words = [&](u64** p, size_t w) { L.push_back(words_req(p, w)); };
   auto bytes = [&](void** p, size_t b) { L.push_back(BufReq{p, b}); };
   auto tree = [&](DevTree& t, size_t nleaf, u32 cap_height) { tree_shape(t, nleaf, cap_height); words(&t.d, 2 * nleaf * 4); };
   if (SplitCtx* S = P->sp) {
@@ -738,17 +759,12 @@ extern "C" int sbn_prover_memory_plan(const sbn_air_desc* air, const sbn_config*
   *bytes_out = 0;
   AirShape as; u32 storage = 0;
   if (int rc = ctx_check_args(air, cfg, degree_bits, nullptr, opt, as, storage)) return rc;
-  sbn_prover* P = new sbn_prover();   // shape fields only: nothing of it touches a device
+  const std::unique_ptr<sbn_prover> P(new sbn_prover());   // shape fields only: nothing of it touches a device
+  if (int rc = ctx_shape(P.get(), as, cfg, degree_bits, storage)) return rc;
   std::vector<BufReq> L;
-  int rc = ctx_shape(P, as, cfg, degree_bits, storage);
-  if (!rc) {
-    ctx_buffers(P, L);
-    uint64_t total = 0;
-    for (const BufReq& b : L) total += b.bytes;
-    *bytes_out = total;
-  }
-  delete P;
-  return rc;
+  ctx_buffers(P.get(), L);
+  for (const BufReq& b : L) *bytes_out += b.bytes;
+  return SBN_OK;
 }
 
 static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_comm* comm, const sbn_prover_options* opt, sbn_prover** out);
@@ -834,12 +850,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   {
     std::vector<BufReq> L;
     ctx_buffers(P, L);
-    for (const BufReq& b : L) {
-      if (rc) break;
-      hipc(hipMalloc(b.slot, b.bytes), "hipMalloc");
-      if (!rc) P->dev_bytes += b.bytes;
-    }
-    if (rc) { sbn_prover_destroy(P); return rc; }
+    if ((rc = alloc_buffers(P, L))) { sbn_prover_destroy(P); return rc; }
   }
   P->d_fb = P->d_fa + 2 * n;
   hipc(hipHostMalloc((void**)&P->h_open, (C + Z + 4) * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
@@ -847,17 +858,8 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   hipc(hipHostMalloc((void**)&P->h_w, 4096 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
   if (rc) { sbn_prover_destroy(P); return rc; }
   // tables
-  auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
-  F w = f_root_of_unity(P->lde_log);
-  // FULL root tables (w^i for every i < m: the second half is the negated first): the register passes index them without the
-  // compare / negate of a half table (tw_full, kernels_ntt.cuh); everything else reads the first half only
-  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_tw_f, m, w.v);
-  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_tw_i, m, f_inv(w).v);
-  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_shift, m, (u64)GL_GEN);
-  hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P->stream, P->d_shift_inv, m, f_inv(F(GL_GEN)).v);
+  fill_transform_tables(P);
   hipLaunchKernelGGL(domain_tables_kernel, blocks(qn), dim3(256), 0, P->stream, P->d_xs, P->d_lag_first, P->d_lag_last, qn, degree_bits + 1, degree_bits);
-  if (P->d_shift_odd) hipLaunchKernelGGL(shift_odd_table_kernel, blocks(n), dim3(256), 0, P->stream, P->d_shift_odd, n, P->d_shift, P->d_tw_f, 9u);
-  if (P->d_shift_za) lde_za_tables(P);
   // permutation pairs
   {
     std::vector<PairCols> pairs(Z);
@@ -888,41 +890,22 @@ namespace sbn { size_t prover_device_bytes(const sbn_prover* P) { return P ? P->
 extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (!P) return;
   (void)hipSetDevice(P->device);
-  u64* bufs[] = {P->d_trace, P->d_coef, P->d_lde, P->d_tmp, P->d_tmp2, P->d_tmp3, P->d_zval, P->d_zcoef, P->d_zlde, P->d_q, P->d_qlde, P->tree_t.d, P->tree_z.d,
-                 P->tree_q.d, P->d_tw_f, P->d_tw_i, P->d_shift, P->d_shift_inv, P->d_xs, P->d_lag_first, P->d_lag_last, P->d_apow, P->d_zpow,
-                 P->d_open, P->d_part, P->d_w, P->d_fa, P->d_fcoef, P->d_fcoef2, P->d_pow, P->d_qbuf, P->d_shift_odd, P->d_shift_za, P->d_ring};
-  for (u64* b : bufs) if (b) (void)hipFree(b);
-  for (u64* b : P->fri_vals) if (b) (void)hipFree(b);
-  for (auto& t : P->fri_trees) if (t.d) (void)hipFree(t.d);
+  if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // in front of the frees: it writes d_trace and d_first_bad (a refused call drained it already)
+  for (void* b : P->owned) (void)hipFree(b);                 // every device buffer of the context (alloc_buffers)
   if (P->sp) {
-    if (P->sp->d_ldechunk) (void)hipFree(P->sp->d_ldechunk);
-    if (P->sp->d_idx_local) (void)hipFree(P->sp->d_idx_local);
-    if (P->sp->d_pairs_own) (void)hipFree(P->sp->d_pairs_own);
     for (auto& e : P->sp->xchg_done) if (e) (void)hipEventDestroy(e);
     for (auto& e : P->sp->tev) if (e) (void)hipEventDestroy(e);
     if (P->sp->cstream) (void)hipStreamDestroy(P->sp->cstream);
     delete P->sp;
   }
-  if (P->d_pic) (void)hipFree(P->d_pic);
-  if (P->d_idx) (void)hipFree(P->d_idx);
-  if (P->d_pairs) (void)hipFree(P->d_pairs);
   for (auto& e : P->ev) if (e) (void)hipEventDestroy(e);   // a partly built context (failed create) holds null handles
   for (auto& e : P->abs_ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : P->chunk_ready) if (e) (void)hipEventDestroy(e);
   if (P->hash_done) (void)hipEventDestroy(P->hash_done);
   for (auto& e : P->ring_free) if (e) (void)hipEventDestroy(e);
-  if (P->d_sponge) (void)hipFree(P->d_sponge);
-  if (P->h_chain) (void)hipHostFree(P->h_chain);
-  if (P->h_io) (void)hipHostFree(P->h_io);
-  if (P->h_open) (void)hipHostFree(P->h_open);
-  if (P->h_open2) (void)hipHostFree(P->h_open2);
-  if (P->h_w) (void)hipHostFree(P->h_w);
-  if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // (a refused call drained it already)
+  for (void* h : {(void*)P->h_chain, (void*)P->h_io, (void*)P->h_open, (void*)P->h_open2, (void*)P->h_w, (void*)P->h_ring, (void*)P->h_first_bad}) if (h) (void)hipHostFree(h);   // pinned
   for (auto& e : P->upload_done) if (e) (void)hipEventDestroy(e);
   for (auto& e : P->slot_copied) if (e) (void)hipEventDestroy(e);
-  if (P->h_ring) (void)hipHostFree(P->h_ring);
-  if (P->h_first_bad) (void)hipHostFree(P->h_first_bad);
-  if (P->d_first_bad) (void)hipFree(P->d_first_bad);
   if (P->ustream) (void)hipStreamDestroy(P->ustream);
   if (P->hstream) (void)hipStreamDestroy(P->hstream);
   if (P->nstream) { (void)hipStreamDestroy(P->nstream); for (auto& e : P->intt_done) if (e) (void)hipEventDestroy(e); }
@@ -1076,451 +1059,524 @@ void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientPar
   qp.seg_mask = 0xfu;
 }
 
+// ---- prove: one ProofRun, one function per Stage -----------------------------------------------------
+// The state of one prove() call that crosses a stage boundary, and nothing else: per member, the stage that writes it; the stages
+// that read it.  The stage functions stand in the order of enum Stage (prover_ctx.hpp), the order of the transcript.  Stage X spans
+// [ev[X], ev[X + 1]) on the main stream and records ev[X + 1] itself (next_stage): behind what it enqueued and IN FRONT of its host
+// wait (cap download, opening slices, stream_wait), so that round trip is not in the time it reports.  (fri_layers and pow wait
+// inside their loops: their event follows the last wait.)
+struct ProofRun {
+  sbn_prover* P = nullptr;                    // prove_impl; read by every stage
+  SplitCtx* S = nullptr;                      // prove_impl: P->sp, non-null: this rank's share of one trace split over S->comm.world GPUs; every stage
+  const HostUpload* up = nullptr;             // prove_impl: null for sbn_prover_prove (the trace is resident), else the host trace streamed in; trace_commit
+  Challenger ch;                              // the transcript: every stage observes into it and draws from it, in stage order
+  std::vector<u64> trace_cap, z_cap, q_cap;   // trace_commit, z_commit (Z > 0 only), quotient_commit; assemble_proof
+  F gamma0, gamma1;                           // perm_z; quotient_eval
+  F alphas[SBN_NCH];                          // quotient_eval draws them, for its own tables and kernels
+  E2 zeta, zeta_next;                         // openings; fri_combine
+  E2 fri_alpha;                               // fri_combine draws it, for its weights and its divisions
+  const u64 *open = nullptr, *open2 = nullptr;   // openings: the values at zeta / at g * zeta (pinned, [(C + Z + 4)][4]); assemble_proof
+  std::vector<std::vector<u64>> fri_caps; std::vector<u64> final_poly;   // fri_layers; assemble_proof
+  u64 pow_witness = ~0ULL;                    // pow; assemble_proof
+  std::vector<u32> idx, idx_local;            // queries: the leaf indices, pageable sources of async uploads that live until its wait
+  std::vector<u64> qwords;                    // queries; assemble_proof
+  size_t split_section = 0;                   // queries (the split): words per query that come from the row-sharded trees
+
+  size_t capw() const { return ((size_t)1 << P->cfg.cap_height) * 4; }   // words of a Merkle cap
+  // the cap of a commitment to the host -- a host wait -- and into the transcript (sharded: a row-sharded tree of the split)
+  int observe_cap(const DevTree& t, std::vector<u64>& cap, bool sharded, bool first_bad = false) {
+    if (int rc = sharded ? split_cap_to_host(P, t, cap) : tree_cap_to_host(P, t, cap, first_bad)) return rc;
+    ch.observe_words(cap.data(), capw());
+    return 0;
+  }
+  // closes the interval of the stage in front of `next` (and opens that of `next`) on the main stream
+  int next_stage(int next) { HIPC(hipEventRecord(P->ev[next], P->stream)); return 0; }
+};
+
+// P1 trace commitment ---------------------------------------------------------------------------
+static int stage_trace_commit(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S; const HostUpload* up = run.up;
+  if (up) HIPC(hipMemsetAsync(P->d_first_bad, up->reduce ? 0 : 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
+  if (S) {
+    S->tev_used = 0;
+    if (int rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t)) return rc;
+  } else if (int rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, P->air.ncols, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up, P->compact ? P->d_lde : nullptr)) return rc;
+  if (int rc = run.next_stage(ST_PERM_Z)) return rc;
+  if (int rc = run.observe_cap(P->tree_t, run.trace_cap, S != nullptr, up != nullptr)) return rc;   // (the scans' word rides back behind the cap)
+  if (up && !up->reduce && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
+  return 0;
+}
+
+// P2 permutation argument -------------------------------------------------------------------------
+// get_n_permutation_challenge_sets(num_challenges, batch_size=2): sets[s].challenges[c] = (beta, gamma)
+// (a table without permutation pairs -- FlagStark -- draws no permutation challenges and commits no Z: starky prover.rs
+//  `stark.uses_permutation_args()`)
+static int stage_perm_z(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S;
+  const size_t Z = P->air.nzs;
+  F gam[2][2] = {};
+  if (Z) for (int s = 0; s < 2; s++) for (int c = 0; c < (int)P->cfg.num_challenges; c++) { (void)run.ch.challenge(); gam[s][c] = run.ch.challenge(); }
+  run.gamma0 = gam[0][0]; run.gamma1 = gam[1][1];  // instance i of a batch uses sets[i].challenges[chal]
+  const size_t zn = S ? S->zr : Z;                       // Z columns computed here (the split: this rank's range)
+  const PairCols* pairs = S ? S->d_pairs_own : P->d_pairs;
+  // MEASURED and dropped (profiles/r3_ab_z_overlap.txt): only the first column chunk in front of the commit pipeline and the
+  // other Z columns on a third stream beside that chunk's transforms and sponge -- the stage in front shrinks by 0.2 ms (a
+  // single workgroup's scan chain is 0.36 ms long), the Z commitment grows by 0.44 ms (26.25 -> 26.5 ms per proof, five pairs).
+  launch_perm_z(P, pairs, zn, run.gamma0.v, run.gamma1.v, P->d_zval, P->stream);
+  HIPC(hipGetLastError());
+  return run.next_stage(ST_Z_COMMIT);
+}
+static int stage_z_commit(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S;
+  const size_t C = P->air.ncols, Z = P->air.nzs;
+  if (S) {
+    if (int rc = commit_split(P, S->zs, P->d_zval, false, P->d_zcoef, S->zlde_l, S->zlde_n, P->tree_z)) return rc;
+  } else {
+    if (C > 4) if (int rc = absorb_times(P, C, EX_TRACE_ABSORB_MS)) return rc;   // (27 event queries: behind the Z kernel, not in front of it)
+    if (Z) if (int rc = commit_pipeline(P, P->d_zval, P->d_zcoef, P->d_zlde, Z, P->tree_z, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, nullptr, P->compact ? P->d_zlde : nullptr)) return rc;
+  }
+  if (int rc = run.next_stage(ST_QUOTIENT_EVAL)) return rc;
+  return Z ? run.observe_cap(P->tree_z, run.z_cap, S != nullptr) : 0;
+}
+
+// P3 quotient -------------------------------------------------------------------------------------
+static int stage_quotient_eval(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S; hipStream_t st = P->stream;
+  const size_t n = P->n, m = P->m, qn = 2 * n, Z = P->air.nzs;   // qn: points of the quotient's domain
+  for (int j = 0; j < SBN_NCH; j++) run.alphas[j] = run.ch.challenge();
+  if (int rc = upload_alpha_tables(P, run.alphas)) return rc;
+  QuotientParams qp{};
+  // starky evaluates the quotient on the coset of qn = 2n points (quotient_degree_bits = 1): quotient point k is LDE row
+  // k << (rate_bits - 1), its next row quotient point k + 2.  The LDE stays in natural row order, so this is a strided view
+  // (the section on rate_bits, has the byte counts against a dense copy); at rate_bits 1 the stride is one row.
+  qp.lde = P->d_lde; qp.zlde = P->d_zlde; qp.m = qn; qp.next_step = 2;  // 2^quotient_degree_bits
+  qp.lde_stride = m; qp.row_log = P->cfg.rate_bits - 1;
+  if (P->compact) { qp.lde_stride = qn; qp.row_log = 0; }   // d_lde / d_zlde hold the quotient's rows only, densely
+  qp.lde_next = qp.lde; qp.zlde_next = qp.zlde; qp.row_shift = 0; qp.row_rho = 0;
+  if (S) {
+    // this rank's LDE points j * R + rho; the row two LDE points on is local row j + 1 (two ranks) or sits at local row j
+    // of the second plane (four ranks and more)
+    qp.lde = S->lde_l; qp.zlde = S->zlde_l; qp.m = S->ml; qp.lde_stride = S->ml; qp.row_shift = S->log_r; qp.row_rho = S->rho;   // (rate_bits 1: create_ctx)
+    qp.lde_next = S->planes == 2 ? S->lde_n : S->lde_l; qp.zlde_next = S->planes == 2 ? S->zlde_n : S->zlde_l;
+    qp.next_step = S->comm.world == 1 ? 2 : (S->comm.world == 2 ? 1 : 0);
+  }
+  qp.xs = P->d_xs; qp.lag_first = P->d_lag_first; qp.lag_last = P->d_lag_last;
+  F gn = f_exp_pow2(F(GL_GEN), P->degree_bits);
+  qp.zh_inv[0] = f_inv(gn - F(1)).v; qp.zh_inv[1] = f_inv(-gn - F(1)).v;  // Z_H(7 w^i) = 7^N (-1)^i - 1
+  qp.last = f_inv(f_root_of_unity(P->degree_bits)).v;
+  quotient_segments(P, run.alphas, qp);
+  qp.gamma0 = run.gamma0.v; qp.gamma1 = run.gamma1.v; qp.qout = P->d_q;
+  if (S) qp.qout = (u64*)S->comm.send_buf;   // [2][ml]: all-gathered below
+  qp.part = P->d_part;   // QSEG x SBN_NCH planes of qn words = 16 n of its 64 n (the FRI combine's scratch, idle here)
+  const size_t qblocks = (qp.m + 255) / 256;
+#ifdef SBN_DIAG   // diagnostic builds only (make CXXFLAGS+=-DSBN_DIAG): time single segments; the proof is invalid unless the mask is 15
+  { const char* e = std::getenv("SBN_DIAG_QUOTIENT_SEGMASK"); if (e) qp.seg_mask = (u32)atoi(e) & 0xfu; }
+  if (qp.seg_mask != 0xfu) HIPC(hipMemsetAsync(qp.part, 0, (size_t)QSEG * SBN_NCH * qp.m * sizeof(u64), st));
+#endif
+  // AIR head and tail on the main stream, the permutation checks beside them on the second stream (idle here)
+  HIPC(hipEventRecord(P->chunk_ready[3], st));
+  HIPC(hipStreamWaitEvent(P->hstream, P->chunk_ready[3], 0));
+  if (int rc = launch_quotient_parts(P, qp, qblocks)) return rc;
+  HIPC(hipEventRecord(P->hash_done, P->hstream));
+  HIPC(hipStreamWaitEvent(st, P->hash_done, 0));
+  hipLaunchKernelGGL(quotient_combine_kernel, blocks(qp.m), dim3(256), 0, st, qp);
+  HIPC(hipGetLastError());
+  if (S) {
+    // quotient values of every rank's points -> all ranks, natural order; the 4 quotient columns are then committed on
+    // every rank alike (no exchange: 4 columns)
+    if (int rc = split_all_gather_device(P, 2 * S->ml)) return rc;
+    hipLaunchKernelGGL(split_unpack_rows_kernel, blocks(m), dim3(256), 0, st, S->scratch, m, 2u, S->log_r, P->d_q);
+    HIPC(hipGetLastError());
+  } else if (Z > 4) { if (int rc = absorb_times(P, Z, EX_Z_ABSORB_MS)) return rc; }   // behind the quotient kernel
+  return run.next_stage(ST_QUOTIENT_COMMIT);
+}
+static int stage_quotient_commit(ProofRun& run) {
+  sbn_prover* P = run.P;
+  const size_t qn = 2 * P->n;
+  // coset_ifft(7) of the 2 quotient value vectors (size qn = 2n), in place via tmp; the result viewed as
+  // [4][n] is exactly quotient_poly.chunks(degree) in the order q0_lo, q0_hi, q1_lo, q1_hi.
+  if (int rc = ntt_columns(P, P->d_q, qn, P->d_q, qn, P->d_tmp, P->m, 2, P->degree_bits + 1, true, qn, nullptr, P->d_shift_inv, host_inv_pow2(P->degree_bits + 1))) return rc;
+  if (int rc = lde_coeffs(P, P->d_q, P->d_qlde, 4)) return rc;
+  if (int rc = tree_from_matrix(P, P->tree_q, P->d_qlde, 4)) return rc;
+  if (int rc = run.next_stage(ST_OPENINGS)) return rc;
+  return run.observe_cap(P->tree_q, run.q_cap, false);
+}
+
+// P4 openings -------------------------------------------------------------------------------------
+// The split (world > 1): this rank evaluates its own trace / Z columns at both points (the quotient columns everywhere; own columns
+// sit compactly in local order at the start of the trace / Z sections of d_open), the values are all-gathered on the host,
+// scattered to their global positions and observed in transcript order
+static int openings_split(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S; Challenger& ch = run.ch; hipStream_t st = P->stream;
+  const size_t n = P->n, C = P->air.ncols, Z = P->air.nzs;
+  const u64 *zp0 = P->d_zpow, *zp1 = P->d_zpow + n, *zp2 = P->d_zpow + 2 * n, *zp3 = P->d_zpow + 3 * n;
+  auto open_k = n % 1024 == 0 ? openings_kernel<4> : openings_kernel<1>;
+  if (S->cr) hipLaunchKernelGGL(open_k, dim3((unsigned)S->cr), dim3(256), 0, st, P->d_coef, n, zp0, zp1, zp2, zp3, P->d_open);
+  if (S->zr) hipLaunchKernelGGL(open_k, dim3((unsigned)S->zr), dim3(256), 0, st, P->d_zcoef, n, zp0, zp1, zp2, zp3, P->d_open + C * 4);
+  hipLaunchKernelGGL(open_k, dim3(4), dim3(256), 0, st, P->d_q, n, zp0, zp1, zp2, zp3, P->d_open + (C + Z) * 4);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(P->h_open, P->d_open, (C + Z + 4) * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+  if (int rc = run.next_stage(ST_FRI_COMBINE)) return rc;
+  HIPC(stream_wait(st));
+  const u32 R = S->comm.world;
+  const size_t cmax = S->cs.max_own(), zmax = S->zs.max_own(), per = (cmax + zmax) * 4;
+  std::vector<u64> mine(per, 0), all((size_t)R * per);
+  memcpy(mine.data(), P->h_open, S->cr * 4 * sizeof(u64));
+  memcpy(mine.data() + cmax * 4, P->h_open + C * 4, S->zr * 4 * sizeof(u64));
+  if (int rc = split_all_gather_host(P, mine.data(), all.data(), per * sizeof(u64))) return rc;
+  for (u32 r = 0; r < R; r++) {
+    const u64* src = all.data() + (size_t)r * per;
+    for (size_t l = 0, cnt = S->cs.own_cols(r); l < cnt; l++) memcpy(P->h_open + S->cs.global_col(r, l) * 4, src + l * 4, 4 * sizeof(u64));
+    for (size_t l = 0, cnt = S->zs.own_cols(r); l < cnt; l++) memcpy(P->h_open + (C + S->zs.global_col(r, l)) * 4, src + (cmax + l) * 4, 4 * sizeof(u64));
+  }
+  const u64* open = run.open2 = run.open;   // one pass: both points of a column sit in one row of h_open
+  for (size_t p = 0; p < C + Z + 4; p++) { ch.observe(F(open[4 * p])); ch.observe(F(open[4 * p + 1])); }
+  for (size_t p = 0; p < C + Z; p++) { ch.observe(F(open[4 * p + 2])); ch.observe(F(open[4 * p + 3])); }
+  return 0;
+}
+static int openings_single(ProofRun& run) {
+  sbn_prover* P = run.P; Challenger& ch = run.ch; hipStream_t st = P->stream;
+  const size_t n = P->n, C = P->air.ncols, Z = P->air.nzs;
+  const u64 *open = run.open, *open2 = run.open2;
+  auto open1_k = n % 1024 == 0 ? openings1_kernel<4> : openings1_kernel<1>;
+  const u64 *zp0 = P->d_zpow, *zp1 = P->d_zpow + n, *zp2 = P->d_zpow + 2 * n, *zp3 = P->d_zpow + 3 * n;
+  // The host hashes ~3 columns per microsecond, the device evaluates ~5: the trace columns at zeta go out in slices that
+  // double in size (C/16, C/8, C/4, rest), so the host starts after a sixteenth of an opening pass and is never starved.
+  size_t sl[5] = {0, C / 16, C / 16 + C / 8, C / 16 + C / 8 + C / 4, C};
+  for (int k = 0; k < 4; k++) {
+    const size_t a = sl[k], cnt = sl[k + 1] - sl[k];
+    if (cnt) {
+      hipLaunchKernelGGL(open1_k, dim3((unsigned)cnt), dim3(256), 0, st, P->d_coef + a * n, n, zp0, zp1, P->d_open + a * 4, 0u);
+      HIPC(hipMemcpyAsync(P->h_open + a * 4, P->d_open + a * 4, cnt * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipEventRecord(P->chunk_ready[8 + k], st));  // (the commit pipeline's chunk events are idle here)
+  }
+  // Z and quotient at zeta, then everything at g*zeta, again in slices: the host (0.86 us per permutation, 4 columns each)
+  // is the slower side, and it must never find the next values missing -- with the trace at g*zeta evaluated last in one
+  // kernel it idled 0.3 ms before it.
+  if (Z) hipLaunchKernelGGL(open1_k, dim3((unsigned)Z), dim3(256), 0, st, P->d_zcoef, n, zp0, zp1, P->d_open + C * 4, 0u);
+  hipLaunchKernelGGL(open1_k, dim3(4), dim3(256), 0, st, P->d_q, n, zp0, zp1, P->d_open + (C + Z) * 4, 0u);
+  HIPC(hipMemcpyAsync(P->h_open + C * 4, P->d_open + C * 4, (Z + 4) * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIPC(hipEventRecord(P->chunk_ready[1], st));
+  size_t sn[5] = {0, C / 4, C / 2, C / 2 + C / 4, C};
+  for (int k = 0; k < 4; k++) {
+    const size_t a = sn[k], cnt = sn[k + 1] - sn[k];
+    if (cnt) {
+      hipLaunchKernelGGL(open1_k, dim3((unsigned)cnt), dim3(256), 0, st, P->d_coef + a * n, n, zp2, zp3, P->d_open + a * 4, 2u);
+      HIPC(hipMemcpyAsync(P->h_open2 + a * 4, P->d_open + a * 4, cnt * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipEventRecord(P->chunk_ready[12 + k], st));
+  }
+  if (Z) hipLaunchKernelGGL(open1_k, dim3((unsigned)Z), dim3(256), 0, st, P->d_zcoef, n, zp2, zp3, P->d_open + C * 4, 2u);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(P->h_open2 + C * 4, P->d_open + C * 4, Z * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
+  if (int rc = run.next_stage(ST_FRI_COMBINE)) return rc;   // in front of the host hashing
+  // observe_openings: batch zeta = local ++ perm_zs ++ quotient ; batch g*zeta = next ++ perm_zs_next
+  for (int k = 0; k < 4; k++) {
+    HIPC(event_wait(P->chunk_ready[8 + k]));
+    for (size_t p = sl[k]; p < sl[k + 1]; p++) { ch.observe(F(open[4 * p])); ch.observe(F(open[4 * p + 1])); }
+  }
+  HIPC(event_wait(P->chunk_ready[1]));
+  for (size_t p = C; p < C + Z + 4; p++) { ch.observe(F(open[4 * p])); ch.observe(F(open[4 * p + 1])); }
+  for (int k = 0; k < 4; k++) {
+    HIPC(event_wait(P->chunk_ready[12 + k]));
+    for (size_t p = sn[k]; p < sn[k + 1]; p++) { ch.observe(F(open2[4 * p + 2])); ch.observe(F(open2[4 * p + 3])); }
+  }
+  HIPC(stream_wait(st));
+  for (size_t p = C; p < C + Z; p++) { ch.observe(F(open2[4 * p + 2])); ch.observe(F(open2[4 * p + 3])); }
+  return 0;
+}
+static int stage_openings(ProofRun& run) {
+  sbn_prover* P = run.P; hipStream_t st = P->stream;
+  const size_t n = P->n;
+  run.zeta = run.ch.ext_challenge();
+  F g = f_root_of_unity(P->degree_bits);
+  if (e2_exp_pow2(run.zeta, P->degree_bits) == E2(F(1), F(0))) return fail(SBN_ERR_HIP, "opening point is in the subgroup");
+  run.zeta_next = run.zeta * g;
+  hipLaunchKernelGGL(ext_pow_table_kernel, blocks(n), dim3(256), 0, st, P->d_zpow, P->d_zpow + n, n, run.zeta.a.v, run.zeta.b.v);
+  hipLaunchKernelGGL(ext_pow_table_kernel, blocks(n), dim3(256), 0, st, P->d_zpow + 2 * n, P->d_zpow + 3 * n, n, run.zeta_next.a.v, run.zeta_next.b.v);
+  // Transcript order: local (trace at zeta), Z at zeta, quotient at zeta, then next (trace at g*zeta), Z at g*zeta.  The
+  // 1,220 sequential permutations that hash them are the longest host stretch of a proof, so the device produces the
+  // values in that order behind three events: trace at zeta alone first (the host starts hashing after half an opening
+  // pass), then Z and quotient at both points, then trace at g*zeta -- the coefficients are read twice, in time the
+  // device would otherwise spend waiting for the host.
+  run.open = P->h_open; run.open2 = P->h_open2;
+  return (run.S && run.S->comm.world > 1) ? openings_split(run) : openings_single(run);
+}
+
+// P5 FRI ------------------------------------------------------------------------------------------
+// The weights alpha^(offset + g * stride) of the ceil(npoly / GS) groups of one matrix, appended to `wall`; returns where they start.
+static size_t fri_plan_weights(std::vector<u64>& wall, E2 fri_alpha, u32 GS, u32 npoly, E2 weight0, u64 stride) {
+  const size_t off = wall.size();
+  E2 ag = e2_pow(fri_alpha, stride), cur = weight0;
+  for (u32 k = 0, ng = (npoly + GS - 1) / GS; k < ng; k++) { wall.push_back(cur.a.v); wall.push_back(cur.b.v); cur = cur * ag; }
+  return off;
+}
+// (oa, ob) = [accumulate: (oa, ob) +] sum over the groups of `coeffs` [npoly][n], GS polynomials each, of weight * sum_k alpha^k f_k:
+// groups run on grid.y, <= 32 per launch; the weights from P->d_w + woff, alpha^k from the two planes at P->d_apow
+static int fri_combine(sbn_prover* P, u32 GS, const u64* coeffs, u32 npoly, size_t woff, u64* oa, u64* ob, int accumulate) {
+  const size_t n = P->n;
+  const u32 ng = (npoly + GS - 1) / GS;
+  for (u32 g0 = 0; g0 < ng; g0 += 32) {
+    u32 gc = std::min<u32>(32, ng - g0);
+    hipLaunchKernelGGL(fri_combine_partial_kernel, dim3((unsigned)((n + 255) / 256), gc), dim3(256), 0, P->stream, coeffs + (size_t)g0 * GS * n, n,
+                       npoly - g0 * GS, GS, P->d_apow, P->d_apow + GS, P->d_part, P->d_part + 32 * n);
+    hipLaunchKernelGGL(fri_combine_reduce_kernel, blocks(n), dim3(256), 0, P->stream, P->d_part, P->d_part + 32 * n, n, gc, P->d_w + woff + 2 * g0, oa, ob,
+                       (accumulate || g0 > 0) ? 1 : 0);
+  }
+  HIPC(hipGetLastError());
+  return 0;
+}
+// (ca, cb) / (X - z), n - 1 coefficients, into d_fcoef: chunk remainders, their scan, then the quotient (mul, accumulate: pass 3)
+static void fri_divide(sbn_prover* P, const u64* ca, const u64* cb, E2 z, E2 mul, int accumulate) {
+  const size_t nch = P->n / DBL_CHUNK;  // a power of two >= 32
+  hipStream_t st = P->stream;
+  u64 *ha = P->d_part, *hb = P->d_part + nch;
+  hipLaunchKernelGGL(divide_by_linear_pass1, blocks(nch), dim3(256), 0, st, ca, cb, nch, z.a.v, z.b.v, ha, hb);
+  hipLaunchKernelGGL(divide_by_linear_pass2, dim3(1), dim3(256), 0, st, ha, hb, nch, z.a.v, z.b.v);
+  hipLaunchKernelGGL(divide_by_linear_pass3, blocks(nch), dim3(256), 0, st, ca, cb, nch, z.a.v, z.b.v, ha, hb, mul.a.v, mul.b.v, P->d_fcoef, P->d_fcoef + P->m, accumulate,
+                     fri_times_x(P->cfg));
+}
+static int stage_fri_combine(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S; hipStream_t st = P->stream;
+  const size_t n = P->n, m = P->m, C = P->air.ncols, Z = P->air.nzs;
+  const E2 fri_alpha = run.fri_alpha = run.ch.ext_challenge();
+  // F1 = sum_{j < C+Z} alpha^j f_j ; F0 = F1 + alpha^(C+Z) * sum_{j<4} alpha^j q_j
+  // polys per group; groups run on grid.y, <= 32 per launch.  The split: a group = one own column block (ColShare), whose
+  // weight is alpha^(global position of the block); consecutive own blocks are `world` blocks apart.
+  const u32 RW = S ? S->comm.world : 1;
+  const u32 GS = RW > 1 ? (u32)SPLIT_BLOCK : 128;
+  // all group weights alpha^(offset + g*stride) are known up front: one upload, no host sync in the loop
+  std::vector<u64> wall;   // (staged here, uploaded from the context's pinned h_w)
+  // the split: this rank's columns only, with the weights of their global positions
+  const size_t tc0 = S ? (size_t)S->comm.rank * GS : 0, tcn = S ? S->cr : C, tzn = S ? S->zr : Z;
+  const u64 gstride = (u64)GS * RW;
+  const size_t w_t = tcn ? fri_plan_weights(wall, fri_alpha, GS, (u32)tcn, e2_pow(fri_alpha, RW > 1 ? tc0 : 0), gstride) : 0;
+  const size_t w_z = tzn ? fri_plan_weights(wall, fri_alpha, GS, (u32)tzn, e2_pow(fri_alpha, C + (RW > 1 ? tc0 : 0)), gstride) : 0;
+  const size_t w_q = fri_plan_weights(wall, fri_alpha, GS, 4, e2_pow(fri_alpha, C + Z), GS);
+  if (wall.size() > 4096) return fail(SBN_ERR_UNSUPPORTED, "too many FRI combine groups");
+  memcpy(P->h_w, wall.data(), wall.size() * sizeof(u64));   // pinned: the upload needs no host wait behind it
+  HIPC(hipMemcpyAsync(P->d_w, P->h_w, wall.size() * sizeof(u64), hipMemcpyHostToDevice, st));
+  // alpha^k, k < GS, as two planes in the quotient's alpha-power buffer (idle now; it holds at least 1,025 words per plane)
+  hipLaunchKernelGGL(ext_pow_table_kernel, dim3(1), dim3(GS), 0, st, P->d_apow, P->d_apow + GS, (size_t)GS, fri_alpha.a.v, fri_alpha.b.v);
+  u64 *f1a = P->d_fb, *f1b = P->d_fb + n, *f0a = P->d_fa, *f0b = P->d_fa + n;
+  if (!tcn) HIPC(hipMemsetAsync(f1a, 0, 2 * n * sizeof(u64), st));
+  if (tcn) if (int rc = fri_combine(P, GS, P->d_coef, (u32)tcn, w_t, f1a, f1b, 0)) return rc;
+  if (tzn) if (int rc = fri_combine(P, GS, P->d_zcoef, (u32)tzn, w_z, f1a, f1b, 1)) return rc;
+  if (S) {
+    // F1 = sum over ranks of the partial sums: all-gather + a mod-p add kernel (RCCL has no mod-p reduction); 16 N bytes per rank
+    HIPC(hipMemcpyAsync(S->comm.send_buf, f1a, 2 * n * sizeof(u64), hipMemcpyDeviceToDevice, st));
+    if (int rc = split_all_gather_device(P, 2 * n)) return rc;   // stream-ordered behind the copy
+    hipLaunchKernelGGL(split_modadd_kernel, blocks(2 * n), dim3(256), 0, st, S->scratch, 2 * n, S->comm.world, f1a);
+    HIPC(hipGetLastError());
+  }
+  HIPC(hipMemcpyAsync(f0a, f1a, 2 * n * sizeof(u64), hipMemcpyDeviceToDevice, st));
+  if (int rc = fri_combine(P, GS, P->d_q, 4, w_q, f0a, f0b, 1)) return rc;
+  // final_poly = alpha^(C+Z) * (F0 / (X - zeta)) + F1 / (X - g zeta), n-1 coefficients each; times X (a zero in front, plonky2
+  // 0.1.x, sbn_config.fri_variant) or zero-padded at the end; then lde -> m
+  HIPC(hipMemsetAsync(P->d_fcoef, 0, 2 * m * sizeof(u64), st));
+  fri_divide(P, f0a, f0b, run.zeta, E2{F(0), F(0)}, 0);
+  fri_divide(P, f1a, f1b, run.zeta_next, e2_pow(fri_alpha, C + Z), 1);
+  HIPC(hipGetLastError());
+  return run.next_stage(ST_FRI_LAYERS);
+}
+// fri_committed_trees
+static int stage_fri_layers(ProofRun& run) {
+  sbn_prover* P = run.P; Challenger& ch = run.ch; hipStream_t st = P->stream;
+  const size_t n = P->n, m = P->m;
+  u32 bits = P->lde_log;
+  u64* coef = P->d_fcoef; u64* coef_alt = P->d_fcoef2;
+  size_t clen = m;  // coefficient vector length (planes at coef, coef + clen)
+  F shift(GL_GEN);
+  for (size_t li = 0; li < P->fri.arity_bits.size(); li++) {
+    u32 ab = P->fri.arity_bits[li];
+    u64* va = P->fri_vals[li]; u64* vb = va + clen;
+    // values = coeffs.coset_fft(shift): scale by shift^i then NTT (2 base planes).  Layer 0 is n coefficients zero-padded to m on
+    // the coset of 7: the coset LDE of lde_coeffs, out of place, whose first pass skips the zero half
+    if (li == 0) {
+      if (int rc = ntt_columns(P, coef, clen, va, clen, P->d_tmp, m, 2, bits, false, n, P->d_shift, nullptr, 1)) return rc;
+    } else {
+      HIPC(hipMemcpyAsync(va, coef, 2 * clen * sizeof(u64), hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, va, clen, shift.v);
+      hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, vb, clen, shift.v);
+      if (int rc = ntt_columns(P, va, clen, va, clen, P->d_tmp, m, 2, bits, false, clen, nullptr, nullptr, 1)) return rc;
+    }
+    DevTree& t = P->fri_trees[li];
+    if (t.nleaf <= 16384) hipLaunchKernelGGL(fri_leaf_hash_coop_kernel, blocks(t.nleaf * 16), dim3(256), 0, st, va, vb, bits, ab, t.d);
+    else hipLaunchKernelGGL(fri_leaf_hash_kernel, blocks(t.nleaf), dim3(256), 0, st, va, vb, bits, ab, t.d);
+    if (int rc = tree_build_inner(P, t, st)) return rc;
+    run.fri_caps.emplace_back();
+    if (int rc = run.observe_cap(t, run.fri_caps.back(), false)) return rc;
+    E2 beta = ch.ext_challenge();
+    size_t nout = clen >> ab;
+    hipLaunchKernelGGL(fri_fold_kernel, blocks(nout), dim3(256), 0, st, coef, coef + clen, nout, 1u << ab, beta.a.v, beta.b.v, coef_alt, coef_alt + nout);
+    HIPC(hipGetLastError());
+    std::swap(coef, coef_alt);
+    clen = nout; bits -= ab;
+    shift = f_pow(shift, (u64)1 << ab);
+  }
+  size_t fl = clen >> P->cfg.rate_bits;  // coefficients beyond are zero
+  run.final_poly.resize(2 * fl);
+  std::vector<u64> fa(fl), fb(fl);
+  HIPC(hipMemcpyAsync(fa.data(), coef, fl * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(fb.data(), coef + clen, fl * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIPC(stream_wait(st));
+  for (size_t i = 0; i < fl; i++) { run.final_poly[2 * i] = fa[i]; run.final_poly[2 * i + 1] = fb[i]; ch.observe(F(fa[i])); ch.observe(F(fb[i])); }
+  return run.next_stage(ST_POW);
+}
+// fri_proof_of_work: smallest witness
+static int stage_pow(ProofRun& run) {
+  sbn_prover* P = run.P; Challenger& ch = run.ch; hipStream_t st = P->stream;
+  PowParams pp{};
+  for (int i = 0; i < 12; i++) pp.state[i] = ch.st[i].v;
+  for (size_t i = 0; i < ch.in.size(); i++) pp.state[i] = ch.in[i].v;
+  pp.wpos = (u32)ch.in.size(); pp.min_lz = P->cfg.proof_of_work_bits; pp.result = P->d_pow;
+  // candidates are scanned in increasing windows (2^17, then 2^20 each): a 16-bit PoW is found in the
+  // first window with probability 1 - e^-2; the smallest witness over the scanned prefix is kept.
+  u64 base = 0;
+  for (int round = 0; run.pow_witness == ~0ULL; round++) {
+    const u64 BATCH = round == 0 ? (1ULL << 17) : (1ULL << 20);
+    if (base >= GLP - BATCH) return fail(SBN_ERR_HIP, "proof of work failed");
+    u64 init = ~0ULL;
+    HIPC(hipMemcpyAsync(P->d_pow, &init, sizeof(u64), hipMemcpyHostToDevice, st));
+    pp.base = base; pp.count = BATCH;
+    hipLaunchKernelGGL(pow_kernel, blocks(BATCH), dim3(256), 0, st, pp);
+    HIPC(hipMemcpyAsync(&run.pow_witness, P->d_pow, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPC(stream_wait(st));
+    base += BATCH;
+  }
+  ch.observe(F(run.pow_witness));
+  F resp = ch.challenge();
+  u32 lz = resp.v ? (u32)__builtin_clzll(resp.v) : 64;
+  if (lz < P->cfg.proof_of_work_bits) return fail(SBN_ERR_HIP, "proof-of-work witness check failed");
+  return run.next_stage(ST_QUERIES);
+}
+// The initial-tree section of every query into d_qbuf at `off` (advanced): the opened row of a matrix and its Merkle path.
+// A row-sharded matrix (the split): `rows` local rows, leaf index inside this rank's subtrees; the rank that owns a
+// query's leaf holds its whole row and its Merkle path up to the cap (other ranks gather a row that is dropped below)
+// coef (compact storage of a wide matrix; else null): the rows are not resident and are evaluated from the coefficients
+// (lde_compact.hip; its point tables sit in d_part, idle since the FRI combine)
+static int query_initial(sbn_prover* P, size_t& off, const u64* mat, size_t ncols, const DevTree& t, size_t rows, u32 log_rows, const u32* d_index, const u64* coef = nullptr) {
+  hipStream_t st = P->stream;
+  const u32 nq = P->cfg.num_query_rounds, nsib = P->lde_log - P->cfg.cap_height;
+  if (coef) { if (int rc = launch_query_rows(coef, ncols, P->n, P->lde_log, P->d_shift, P->d_tw_f, d_index, nq, P->d_part, P->d_qbuf, P->qstride, off, st)) return rc; }
+  else hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ncols + 255) / 256), nq), dim3(256), 0, st, mat, rows, log_rows, (u32)ncols, d_index, P->d_qbuf, P->qstride, off);
+  off += ncols;
+  hipLaunchKernelGGL(gather_siblings_kernel, dim3(nq), dim3(128), 0, st, t.d, t.nleaf, nsib, d_index, 0u, P->d_qbuf, P->qstride, off);
+  off += (size_t)nsib * 4;
+  return 0;
+}
+// fri_prover_query_rounds
+static int stage_queries(ProofRun& run) {
+  sbn_prover* P = run.P; SplitCtx* S = run.S; hipStream_t st = P->stream;
+  const size_t m = P->m, C = P->air.ncols, Z = P->air.nzs;
+  const u32 nq = P->cfg.num_query_rounds;
+  run.qwords.resize(P->qstride * nq);
+  run.idx.resize(nq); run.idx_local.resize(nq);
+  for (u32 q = 0; q < nq; q++) run.idx[q] = (u32)(run.ch.challenge().v % m);
+  HIPC(hipMemcpyAsync(P->d_idx, run.idx.data(), nq * sizeof(u32), hipMemcpyHostToDevice, st));
+  size_t off = 0;
+  if (S) {
+    for (u32 q = 0; q < nq; q++) run.idx_local[q] = run.idx[q] & (u32)(S->ml - 1);
+    HIPC(hipMemcpyAsync(S->d_idx_local, run.idx_local.data(), nq * sizeof(u32), hipMemcpyHostToDevice, st));
+    if (int rc = query_initial(P, off, S->lde_l, C, P->tree_t, S->ml, P->lde_log - S->log_r, S->d_idx_local)) return rc;
+    if (Z) if (int rc = query_initial(P, off, S->zlde_l, Z, P->tree_z, S->ml, P->lde_log - S->log_r, S->d_idx_local)) return rc;
+    run.split_section = off;
+  } else {
+    if (int rc = query_initial(P, off, P->d_lde, C, P->tree_t, m, P->lde_log, P->d_idx, P->compact ? P->d_coef : nullptr)) return rc;
+    if (Z) if (int rc = query_initial(P, off, P->d_zlde, Z, P->tree_z, m, P->lde_log, P->d_idx, P->compact ? P->d_zcoef : nullptr)) return rc;
+  }
+  if (int rc = query_initial(P, off, P->d_qlde, 4, P->tree_q, m, P->lde_log, P->d_idx)) return rc;
+  u32 bits = P->lde_log, shift = 0;
+  for (size_t li = 0; li < P->fri.arity_bits.size(); li++) {
+    u32 ab = P->fri.arity_bits[li];
+    shift += ab;
+    size_t len = (size_t)1 << bits;
+    hipLaunchKernelGGL(gather_fri_leaf_kernel, dim3(nq), dim3(64), 0, st, P->fri_vals[li], P->fri_vals[li] + len, bits, ab, P->d_idx, shift, P->d_qbuf, P->qstride, off);
+    off += 2 * ((size_t)1 << ab);
+    const DevTree& t = P->fri_trees[li];
+    hipLaunchKernelGGL(gather_siblings_kernel, dim3(nq), dim3(128), 0, st, t.d, t.nleaf, t.nlevels, P->d_idx, shift, P->d_qbuf, P->qstride, off);
+    off += (size_t)t.nlevels * 4;
+    bits -= ab;
+  }
+  HIPC(hipGetLastError());
+  if (off != P->qstride) return fail(SBN_ERR_HIP, "internal: query layout mismatch (%zu vs %zu)", off, P->qstride);
+  HIPC(hipMemcpyAsync(run.qwords.data(), P->d_qbuf, run.qwords.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+  if (int rc = run.next_stage(ST_COUNT)) return rc;
+  HIPC(stream_wait(st));
+  if (S) {
+    // the trace / Z sections of every query come from the rank that owns the leaf: all-gather on the host and pick
+    const u32 R = S->comm.world;
+    const size_t sec = run.split_section;
+    std::vector<u64> mine((size_t)nq * sec), all((size_t)R * nq * sec);
+    for (u32 q = 0; q < nq; q++) memcpy(mine.data() + (size_t)q * sec, run.qwords.data() + (size_t)q * P->qstride, sec * sizeof(u64));
+    if (int rc = split_all_gather_host(P, mine.data(), all.data(), mine.size() * sizeof(u64))) return rc;
+    for (u32 q = 0; q < nq; q++) {
+      const u32 owner = run.idx[q] >> (P->lde_log - S->log_r);
+      memcpy(run.qwords.data() + (size_t)q * P->qstride, all.data() + ((size_t)owner * nq + q) * sec, sec * sizeof(u64));
+    }
+    float xms = 0;   // device time inside the exchanges (waiting for the peers' blocks included)
+    for (size_t i = 0; i + 1 < S->tev_used; i += 2) { float t = 0; HIPC(hipEventElapsedTime(&t, S->tev[i], S->tev[i + 1])); xms += t; }
+    P->stage_ms[ST_COUNT + EX_COMM_MS] = xms;
+  }
+  return 0;
+}
+// the canonical proof words (layout: include/sbn.h)
+static int assemble_proof(const ProofRun& run, sbn_proof** out) {
+  const sbn_prover* P = run.P;
+  const sbn_config& cfg = P->cfg;
+  const size_t C = P->air.ncols, Z = P->air.nzs;
+  const u64 *open = run.open, *open2 = run.open2;
+  sbn_proof* pr = new sbn_proof();
+  pr->degree_bits = P->degree_bits;
+  std::vector<u64>& w = pr->words;
+  w.reserve(12 + 3 * run.capw() + (C + Z + 4) * 4 + run.fri_caps.size() * run.capw() + run.qwords.size() + run.final_poly.size() + 1 + P->pi.size());
+  u64 hdr[12] = {PROOF_MAGIC, P->degree_bits, C, Z, 4, P->pi.size(), cfg.cap_height, cfg.rate_bits, run.fri_caps.size(), cfg.fri_arity_bits,
+                 run.final_poly.size() / 2, cfg.num_query_rounds};
+  w.insert(w.end(), hdr, hdr + 12);
+  w.insert(w.end(), run.trace_cap.begin(), run.trace_cap.end());
+  if (Z) w.insert(w.end(), run.z_cap.begin(), run.z_cap.end());
+  w.insert(w.end(), run.q_cap.begin(), run.q_cap.end());
+  for (size_t p = 0; p < C; p++) { w.push_back(open[4 * p]); w.push_back(open[4 * p + 1]); }          // local_values
+  for (size_t p = 0; p < C; p++) { w.push_back(open2[4 * p + 2]); w.push_back(open2[4 * p + 3]); }    // next_values
+  for (size_t p = C; p < C + Z; p++) { w.push_back(open[4 * p]); w.push_back(open[4 * p + 1]); }      // permutation_zs
+  for (size_t p = C; p < C + Z; p++) { w.push_back(open2[4 * p + 2]); w.push_back(open2[4 * p + 3]); }  // permutation_zs_next
+  for (size_t p = C + Z; p < C + Z + 4; p++) { w.push_back(open[4 * p]); w.push_back(open[4 * p + 1]); }  // quotient_polys
+  for (auto& cap : run.fri_caps) w.insert(w.end(), cap.begin(), cap.end());
+  w.insert(w.end(), run.qwords.begin(), run.qwords.end());
+  w.insert(w.end(), run.final_poly.begin(), run.final_poly.end());
+  w.push_back(run.pow_witness);
+  w.insert(w.end(), P->pi.begin(), P->pi.end());
+  *out = pr;
+  return SBN_OK;
+}
 // up: null for sbn_prover_prove (the trace is resident); else the host trace sbn_prover_prove_host_trace streams in
 static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   if (!up && !P->loaded && !(P->sp && P->sp->comm.world > 1)) return fail(SBN_ERR_BAD_ARG, "no trace loaded");   // (split: agreed with the other ranks below)
   HIPC(hipSetDevice(P->device));
-  hipStream_t st = P->stream;
-  const size_t n = P->n, m = P->m, qn = 2 * n, C = P->air.ncols, Z = P->air.nzs;   // qn: points of the quotient's domain
-  const sbn_config& cfg = P->cfg;
-  const size_t capw = ((size_t)1 << cfg.cap_height) * 4;
-  auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
-  int rc;
-  Challenger ch;
-  std::vector<u64> trace_cap, z_cap, q_cap;
-
-  // P1 trace commitment ---------------------------------------------------------------------------
-  HIPC(hipEventRecord(P->ev[ST_TRACE_COMMIT], st));
-  SplitCtx* const S = P->sp;   // non-null: this rank's share of one trace split over S->comm.world GPUs
+  ProofRun run;
+  run.P = P; run.S = P->sp; run.up = up;
+  if (int rc = run.next_stage(ST_TRACE_COMMIT)) return rc;   // (the first interval opens in front of the ranks' agreement)
   struct DeadlineScope { ~DeadlineScope() { t_wait_deadline_s = 0; } } deadline_scope;
-  if (S && S->comm.world > 1) {
+  if (SplitCtx* S = run.S; S && S->comm.world > 1) {
     // every rank must have a witness before anyone walks into the first exchange (a rank whose generate_trace failed would
     // leave the others waiting for its blocks): agree on a status word first
     t_wait_deadline_s = P->set.comm_timeout_s;
     std::vector<uint32_t> st_all(S->comm.world, 0);
     const uint32_t mine = P->loaded ? 1u : 0u;
-    if ((rc = split_all_gather_host(P, &mine, st_all.data(), sizeof(uint32_t)))) return rc;
+    if (int rc = split_all_gather_host(P, &mine, st_all.data(), sizeof(uint32_t))) return rc;
     for (u32 r = 0; r < S->comm.world; r++) if (!st_all[r]) return fail(SBN_ERR_BAD_ARG, "split proof abandoned: rank %u has no trace loaded", r);
   }
   if (!up && !P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
-  if (up) HIPC(hipMemsetAsync(P->d_first_bad, up->reduce ? 0 : 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
-  if (S) {
-    S->tev_used = 0;
-    if ((rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t))) return rc;
-  } else if ((rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, C, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up, P->compact ? P->d_lde : nullptr))) return rc;
-  HIPC(hipEventRecord(P->ev[ST_PERM_Z], st));
-  if ((rc = S ? split_cap_to_host(P, P->tree_t, trace_cap) : tree_cap_to_host(P, P->tree_t, trace_cap, up != nullptr))) return rc;
-  if (up && !up->reduce && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
-  ch.observe_words(trace_cap.data(), capw);
-
-  // P2 permutation argument -------------------------------------------------------------------------
-  // get_n_permutation_challenge_sets(num_challenges, batch_size=2): sets[s].challenges[c] = (beta, gamma)
-  // (a table without permutation pairs -- FlagStark -- draws no permutation challenges and commits no Z: starky prover.rs
-  //  `stark.uses_permutation_args()`)
-  F gam[2][2] = {};
-  if (Z) for (int s = 0; s < 2; s++) for (int c = 0; c < (int)cfg.num_challenges; c++) { (void)ch.challenge(); gam[s][c] = ch.challenge(); }
-  const F gamma0 = gam[0][0], gamma1 = gam[1][1];  // instance i of a batch uses sets[i].challenges[chal]
-  {
-    const size_t zn = S ? S->zr : Z;                       // Z columns computed here (the split: this rank's range)
-    const PairCols* pairs = S ? S->d_pairs_own : P->d_pairs;
-    // MEASURED and dropped (profiles/r3_ab_z_overlap.txt): only the first column chunk in front of the commit pipeline and the
-    // other Z columns on a third stream beside that chunk's transforms and sponge -- the stage in front shrinks by 0.2 ms (a
-    // single workgroup's scan chain is 0.36 ms long), the Z commitment grows by 0.44 ms (26.25 -> 26.5 ms per proof, five pairs).
-    launch_perm_z(P, pairs, zn, gamma0.v, gamma1.v, P->d_zval, st);
-  }
-  HIPC(hipGetLastError());
-  HIPC(hipEventRecord(P->ev[ST_Z_COMMIT], st));
-  if (S) {
-    if ((rc = commit_split(P, S->zs, P->d_zval, false, P->d_zcoef, S->zlde_l, S->zlde_n, P->tree_z))) return rc;
-  } else {
-    if (C > 4) if ((rc = absorb_times(P, C, EX_TRACE_ABSORB_MS))) return rc;   // (27 event queries: behind the Z kernel, not in front of it)
-    if (Z) if ((rc = commit_pipeline(P, P->d_zval, P->d_zcoef, P->d_zlde, Z, P->tree_z, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, nullptr, P->compact ? P->d_zlde : nullptr))) return rc;
-  }
-  HIPC(hipEventRecord(P->ev[ST_QUOTIENT_EVAL], st));
-  if (Z) {
-    if ((rc = S ? split_cap_to_host(P, P->tree_z, z_cap) : tree_cap_to_host(P, P->tree_z, z_cap))) return rc;
-    ch.observe_words(z_cap.data(), capw);
-  }
-
-  // P3 quotient -------------------------------------------------------------------------------------
-  F alphas[SBN_NCH];
-  for (int j = 0; j < SBN_NCH; j++) alphas[j] = ch.challenge();
-  if ((rc = upload_alpha_tables(P, alphas))) return rc;
-  {
-    QuotientParams qp{};
-    // starky evaluates the quotient on the coset of qn = 2n points (quotient_degree_bits = 1): quotient point k is LDE row
-    // k << (rate_bits - 1), its next row quotient point k + 2.  The LDE stays in natural row order, so this is a strided view
-    // (the section on rate_bits, has the byte counts against a dense copy); at rate_bits 1 the stride is one row.
-    qp.lde = P->d_lde; qp.zlde = P->d_zlde; qp.m = qn; qp.next_step = 2;  // 2^quotient_degree_bits
-    qp.lde_stride = m; qp.row_log = cfg.rate_bits - 1;
-    if (P->compact) { qp.lde_stride = qn; qp.row_log = 0; }   // d_lde / d_zlde hold the quotient's rows only, densely
-    qp.lde_next = qp.lde; qp.zlde_next = qp.zlde; qp.row_shift = 0; qp.row_rho = 0;
-    if (S) {
-      // this rank's LDE points j * R + rho; the row two LDE points on is local row j + 1 (two ranks) or sits at local row j
-      // of the second plane (four ranks and more)
-      qp.lde = S->lde_l; qp.zlde = S->zlde_l; qp.m = S->ml; qp.lde_stride = S->ml; qp.row_shift = S->log_r; qp.row_rho = S->rho;   // (rate_bits 1: create_ctx)
-      qp.lde_next = S->planes == 2 ? S->lde_n : S->lde_l; qp.zlde_next = S->planes == 2 ? S->zlde_n : S->zlde_l;
-      qp.next_step = S->comm.world == 1 ? 2 : (S->comm.world == 2 ? 1 : 0);
-    }
-    qp.xs = P->d_xs; qp.lag_first = P->d_lag_first; qp.lag_last = P->d_lag_last;
-    F gn = f_exp_pow2(F(GL_GEN), P->degree_bits);
-    qp.zh_inv[0] = f_inv(gn - F(1)).v; qp.zh_inv[1] = f_inv(-gn - F(1)).v;  // Z_H(7 w^i) = 7^N (-1)^i - 1
-    qp.last = f_inv(f_root_of_unity(P->degree_bits)).v;
-    quotient_segments(P, alphas, qp);
-    qp.gamma0 = gamma0.v; qp.gamma1 = gamma1.v; qp.qout = P->d_q;
-    if (S) qp.qout = (u64*)S->comm.send_buf;   // [2][ml]: all-gathered below
-    qp.part = P->d_part;   // QSEG x SBN_NCH planes of qn words = 16 n of its 64 n (the FRI combine's scratch, idle here)
-    const size_t qblocks = (qp.m + 255) / 256;
-#ifdef SBN_DIAG   // diagnostic builds only (make CXXFLAGS+=-DSBN_DIAG): time single segments; the proof is invalid unless the mask is 15
-    { const char* e = std::getenv("SBN_DIAG_QUOTIENT_SEGMASK"); if (e) qp.seg_mask = (u32)atoi(e) & 0xfu; }
-    if (qp.seg_mask != 0xfu) HIPC(hipMemsetAsync(qp.part, 0, (size_t)QSEG * SBN_NCH * qp.m * sizeof(u64), st));
-#endif
-    // AIR head and tail on the main stream, the permutation checks beside them on the second stream (idle here)
-    HIPC(hipEventRecord(P->chunk_ready[3], st));
-    HIPC(hipStreamWaitEvent(P->hstream, P->chunk_ready[3], 0));
-    if ((rc = launch_quotient_parts(P, qp, qblocks))) return rc;
-    HIPC(hipEventRecord(P->hash_done, P->hstream));
-    HIPC(hipStreamWaitEvent(st, P->hash_done, 0));
-    hipLaunchKernelGGL(quotient_combine_kernel, blocks(qp.m), dim3(256), 0, st, qp);
-    HIPC(hipGetLastError());
-    if (S) {
-      // quotient values of every rank's points -> all ranks, natural order; the 4 quotient columns are then committed on
-      // every rank alike (no exchange: 4 columns)
-      if ((rc = split_all_gather_device(P, 2 * S->ml))) return rc;
-      hipLaunchKernelGGL(split_unpack_rows_kernel, blocks(m), dim3(256), 0, st, S->scratch, m, 2u, S->log_r, P->d_q);
-      HIPC(hipGetLastError());
-    } else if (Z > 4) { if ((rc = absorb_times(P, Z, EX_Z_ABSORB_MS))) return rc; }   // behind the quotient kernel
-  }
-  HIPC(hipEventRecord(P->ev[ST_QUOTIENT_COMMIT], st));
-  // coset_ifft(7) of the 2 quotient value vectors (size qn = 2n), in place via tmp; the result viewed as
-  // [4][n] is exactly quotient_poly.chunks(degree) in the order q0_lo, q0_hi, q1_lo, q1_hi.
-  if ((rc = ntt_columns(P, P->d_q, qn, P->d_q, qn, P->d_tmp, m, 2, P->degree_bits + 1, true, qn, nullptr, P->d_shift_inv, host_inv_pow2(P->degree_bits + 1)))) return rc;
-  if ((rc = lde_coeffs(P, P->d_q, P->d_qlde, 4))) return rc;
-  if ((rc = tree_from_matrix(P, P->tree_q, P->d_qlde, 4))) return rc;
-  HIPC(hipEventRecord(P->ev[ST_OPENINGS], st));
-  if ((rc = tree_cap_to_host(P, P->tree_q, q_cap))) return rc;
-  ch.observe_words(q_cap.data(), capw);
-
-  // P4 openings -------------------------------------------------------------------------------------
-  E2 zeta = ch.ext_challenge();
-  F g = f_root_of_unity(P->degree_bits);
-  if (e2_exp_pow2(zeta, P->degree_bits) == E2(F(1), F(0))) return fail(SBN_ERR_HIP, "opening point is in the subgroup");
-  E2 zeta_next = zeta * g;
-  hipLaunchKernelGGL(ext_pow_table_kernel, blocks(n), dim3(256), 0, st, P->d_zpow, P->d_zpow + n, n, zeta.a.v, zeta.b.v);
-  hipLaunchKernelGGL(ext_pow_table_kernel, blocks(n), dim3(256), 0, st, P->d_zpow + 2 * n, P->d_zpow + 3 * n, n, zeta_next.a.v, zeta_next.b.v);
-  // Transcript order: local (trace at zeta), Z at zeta, quotient at zeta, then next (trace at g*zeta), Z at g*zeta.  The
-  // 1,220 sequential permutations that hash them are the longest host stretch of a proof, so the device produces the
-  // values in that order behind three events: trace at zeta alone first (the host starts hashing after half an opening
-  // pass), then Z and quotient at both points, then trace at g*zeta -- the coefficients are read twice, in time the
-  // device would otherwise spend waiting for the host.
-  const u64* open = P->h_open;
-  const u64* open2 = P->h_open2;
-  if (S && S->comm.world > 1) {
-    // this rank evaluates its own trace / Z columns at both points (the quotient columns everywhere; own columns sit
-    // compactly in local order at the start of the trace / Z sections of d_open), the values are all-gathered on the host,
-    // scattered to their global positions and observed in transcript order
-    const u64 *zp0 = P->d_zpow, *zp1 = P->d_zpow + n, *zp2 = P->d_zpow + 2 * n, *zp3 = P->d_zpow + 3 * n;
-    auto open_k = n % 1024 == 0 ? openings_kernel<4> : openings_kernel<1>;
-    if (S->cr) hipLaunchKernelGGL(open_k, dim3((unsigned)S->cr), dim3(256), 0, st, P->d_coef, n, zp0, zp1, zp2, zp3, P->d_open);
-    if (S->zr) hipLaunchKernelGGL(open_k, dim3((unsigned)S->zr), dim3(256), 0, st, P->d_zcoef, n, zp0, zp1, zp2, zp3, P->d_open + C * 4);
-    hipLaunchKernelGGL(open_k, dim3(4), dim3(256), 0, st, P->d_q, n, zp0, zp1, zp2, zp3, P->d_open + (C + Z) * 4);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(P->h_open, P->d_open, (C + Z + 4) * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(hipEventRecord(P->ev[ST_FRI_COMBINE], st));
-    HIPC(stream_wait(st));
-    const u32 R = S->comm.world;
-    const size_t cmax = S->cs.max_own(), zmax = S->zs.max_own(), per = (cmax + zmax) * 4;
-    std::vector<u64> mine(per, 0), all((size_t)R * per);
-    memcpy(mine.data(), P->h_open, S->cr * 4 * sizeof(u64));
-    memcpy(mine.data() + cmax * 4, P->h_open + C * 4, S->zr * 4 * sizeof(u64));
-    if ((rc = split_all_gather_host(P, mine.data(), all.data(), per * sizeof(u64)))) return rc;
-    for (u32 r = 0; r < R; r++) {
-      const u64* src = all.data() + (size_t)r * per;
-      for (size_t l = 0, cnt = S->cs.own_cols(r); l < cnt; l++) memcpy(P->h_open + S->cs.global_col(r, l) * 4, src + l * 4, 4 * sizeof(u64));
-      for (size_t l = 0, cnt = S->zs.own_cols(r); l < cnt; l++) memcpy(P->h_open + (C + S->zs.global_col(r, l)) * 4, src + (cmax + l) * 4, 4 * sizeof(u64));
-    }
-    open2 = open;
-    for (size_t p = 0; p < C + Z + 4; p++) { ch.observe(F(open[4 * p])); ch.observe(F(open[4 * p + 1])); }
-    for (size_t p = 0; p < C + Z; p++) { ch.observe(F(open[4 * p + 2])); ch.observe(F(open[4 * p + 3])); }
-  } else {
-    const bool u4 = n % 1024 == 0;
-    auto open1_k = u4 ? openings1_kernel<4> : openings1_kernel<1>;
-    const u64 *zp0 = P->d_zpow, *zp1 = P->d_zpow + n, *zp2 = P->d_zpow + 2 * n, *zp3 = P->d_zpow + 3 * n;
-    // The host hashes ~3 columns per microsecond, the device evaluates ~5: the trace columns at zeta go out in slices that
-    // double in size (C/16, C/8, C/4, rest), so the host starts after a sixteenth of an opening pass and is never starved.
-    size_t sl[5] = {0, C / 16, C / 16 + C / 8, C / 16 + C / 8 + C / 4, C};
-    for (int k = 0; k < 4; k++) {
-      const size_t a = sl[k], cnt = sl[k + 1] - sl[k];
-      if (cnt) {
-        hipLaunchKernelGGL(open1_k, dim3((unsigned)cnt), dim3(256), 0, st, P->d_coef + a * n, n, zp0, zp1, P->d_open + a * 4, 0u);
-        HIPC(hipMemcpyAsync(P->h_open + a * 4, P->d_open + a * 4, cnt * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
-      }
-      HIPC(hipEventRecord(P->chunk_ready[8 + k], st));  // (the commit pipeline's chunk events are idle here)
-    }
-    // Z and quotient at zeta, then everything at g*zeta, again in slices: the host (0.86 us per permutation, 4 columns each)
-    // is the slower side, and it must never find the next values missing -- with the trace at g*zeta evaluated last in one
-    // kernel it idled 0.3 ms before it.
-    if (Z) hipLaunchKernelGGL(open1_k, dim3((unsigned)Z), dim3(256), 0, st, P->d_zcoef, n, zp0, zp1, P->d_open + C * 4, 0u);
-    hipLaunchKernelGGL(open1_k, dim3(4), dim3(256), 0, st, P->d_q, n, zp0, zp1, P->d_open + (C + Z) * 4, 0u);
-    HIPC(hipMemcpyAsync(P->h_open + C * 4, P->d_open + C * 4, (Z + 4) * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(hipEventRecord(P->chunk_ready[1], st));
-    size_t sn[5] = {0, C / 4, C / 2, C / 2 + C / 4, C};
-    for (int k = 0; k < 4; k++) {
-      const size_t a = sn[k], cnt = sn[k + 1] - sn[k];
-      if (cnt) {
-        hipLaunchKernelGGL(open1_k, dim3((unsigned)cnt), dim3(256), 0, st, P->d_coef + a * n, n, zp2, zp3, P->d_open + a * 4, 2u);
-        HIPC(hipMemcpyAsync(P->h_open2 + a * 4, P->d_open + a * 4, cnt * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
-      }
-      HIPC(hipEventRecord(P->chunk_ready[12 + k], st));
-    }
-    if (Z) hipLaunchKernelGGL(open1_k, dim3((unsigned)Z), dim3(256), 0, st, P->d_zcoef, n, zp2, zp3, P->d_open + C * 4, 2u);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(P->h_open2 + C * 4, P->d_open + C * 4, Z * 4 * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(hipEventRecord(P->ev[ST_FRI_COMBINE], st));
-    // observe_openings: batch zeta = local ++ perm_zs ++ quotient ; batch g*zeta = next ++ perm_zs_next
-    for (int k = 0; k < 4; k++) {
-      HIPC(event_wait(P->chunk_ready[8 + k]));
-      for (size_t p = sl[k]; p < sl[k + 1]; p++) { ch.observe(F(open[4 * p])); ch.observe(F(open[4 * p + 1])); }
-    }
-    HIPC(event_wait(P->chunk_ready[1]));
-    for (size_t p = C; p < C + Z + 4; p++) { ch.observe(F(open[4 * p])); ch.observe(F(open[4 * p + 1])); }
-    for (int k = 0; k < 4; k++) {
-      HIPC(event_wait(P->chunk_ready[12 + k]));
-      for (size_t p = sn[k]; p < sn[k + 1]; p++) { ch.observe(F(open2[4 * p + 2])); ch.observe(F(open2[4 * p + 3])); }
-    }
-    HIPC(stream_wait(st));
-    for (size_t p = C; p < C + Z; p++) { ch.observe(F(open2[4 * p + 2])); ch.observe(F(open2[4 * p + 3])); }
-  }
-
-  // P5 FRI ------------------------------------------------------------------------------------------
-  E2 fri_alpha = ch.ext_challenge();
-  {
-    // F1 = sum_{j < C+Z} alpha^j f_j ; F0 = F1 + alpha^(C+Z) * sum_{j<4} alpha^j q_j
-    // polys per group; groups run on grid.y, <= 32 per launch.  The split: a group = one own column block (ColShare), whose
-    // weight is alpha^(global position of the block); consecutive own blocks are `world` blocks apart.
-    const u32 RW = S ? S->comm.world : 1;
-    const u32 GS = RW > 1 ? (u32)SPLIT_BLOCK : 128;
-    // all group weights alpha^(offset + g*stride) are known up front: one upload, no host sync in the loop
-    std::vector<u64> wall;   // (staged here, uploaded from the context's pinned h_w)
-    auto plan = [&](u32 npoly, E2 weight0, u64 stride) { size_t off = wall.size(); u32 ng = (npoly + GS - 1) / GS; E2 ag = e2_pow(fri_alpha, stride), cur = weight0;
-                                                         for (u32 k = 0; k < ng; k++) { wall.push_back(cur.a.v); wall.push_back(cur.b.v); cur = cur * ag; } return off; };
-    // the split: this rank's columns only, with the weights of their global positions
-    const size_t tc0 = S ? (size_t)S->comm.rank * GS : 0, tcn = S ? S->cr : C, tzn = S ? S->zr : Z;
-    const u64 gstride = (u64)GS * RW;
-    size_t w_t = tcn ? plan((u32)tcn, e2_pow(fri_alpha, RW > 1 ? tc0 : 0), gstride) : 0, w_z = tzn ? plan((u32)tzn, e2_pow(fri_alpha, C + (RW > 1 ? tc0 : 0)), gstride) : 0,
-           w_q = plan(4, e2_pow(fri_alpha, C + Z), GS);
-    if (wall.size() > 4096) return fail(SBN_ERR_UNSUPPORTED, "too many FRI combine groups");
-    memcpy(P->h_w, wall.data(), wall.size() * sizeof(u64));   // pinned: the upload needs no host wait behind it
-    HIPC(hipMemcpyAsync(P->d_w, P->h_w, wall.size() * sizeof(u64), hipMemcpyHostToDevice, st));
-    // alpha^k, k < GS, as two planes in the quotient's alpha-power buffer (idle now; it holds at least 1,025 words per plane)
-    hipLaunchKernelGGL(ext_pow_table_kernel, dim3(1), dim3(GS), 0, st, P->d_apow, P->d_apow + GS, (size_t)GS, fri_alpha.a.v, fri_alpha.b.v);
-    auto combine = [&](const u64* coeffs, u32 npoly, size_t woff, u64* oa, u64* ob, int accumulate) -> int {
-      u32 ng = (npoly + GS - 1) / GS;
-      for (u32 g0 = 0; g0 < ng; g0 += 32) {
-        u32 gc = std::min<u32>(32, ng - g0);
-        hipLaunchKernelGGL(fri_combine_partial_kernel, dim3((unsigned)((n + 255) / 256), gc), dim3(256), 0, st, coeffs + (size_t)g0 * GS * n, n,
-                           npoly - g0 * GS, GS, P->d_apow, P->d_apow + GS, P->d_part, P->d_part + 32 * n);
-        hipLaunchKernelGGL(fri_combine_reduce_kernel, blocks(n), dim3(256), 0, st, P->d_part, P->d_part + 32 * n, n, gc, P->d_w + woff + 2 * g0, oa, ob,
-                           (accumulate || g0 > 0) ? 1 : 0);
-      }
-      HIPC(hipGetLastError());
-      return 0;
-    };
-    u64 *f1a = P->d_fb, *f1b = P->d_fb + n, *f0a = P->d_fa, *f0b = P->d_fa + n;
-    if (!tcn) HIPC(hipMemsetAsync(f1a, 0, 2 * n * sizeof(u64), st));
-    if (tcn) if ((rc = combine(P->d_coef, (u32)tcn, w_t, f1a, f1b, 0))) return rc;
-    if (tzn) if ((rc = combine(P->d_zcoef, (u32)tzn, w_z, f1a, f1b, 1))) return rc;
-    if (S) {
-      // F1 = sum over ranks of the partial sums: all-gather + a mod-p add kernel (RCCL has no mod-p reduction); 16 N bytes per rank
-      HIPC(hipMemcpyAsync(S->comm.send_buf, f1a, 2 * n * sizeof(u64), hipMemcpyDeviceToDevice, st));
-      if ((rc = split_all_gather_device(P, 2 * n))) return rc;   // stream-ordered behind the copy
-      hipLaunchKernelGGL(split_modadd_kernel, blocks(2 * n), dim3(256), 0, st, S->scratch, 2 * n, S->comm.world, f1a);
-      HIPC(hipGetLastError());
-    }
-    HIPC(hipMemcpyAsync(f0a, f1a, 2 * n * sizeof(u64), hipMemcpyDeviceToDevice, st));
-    if ((rc = combine(P->d_q, 4, w_q, f0a, f0b, 1))) return rc;
-    // final_poly = alpha^(C+Z) * (F0 / (X - zeta)) + F1 / (X - g zeta), n-1 coefficients each; times X (a zero in front, plonky2
-    // 0.1.x, sbn_config.fri_variant) or zero-padded at the end; then lde -> m
-    HIPC(hipMemsetAsync(P->d_fcoef, 0, 2 * m * sizeof(u64), st));
-    E2 shift2 = e2_pow(fri_alpha, C + Z);
-    auto divide = [&](const u64* ca, const u64* cb, E2 z, E2 mul, int accumulate) {
-      const size_t nch = n / DBL_CHUNK;  // a power of two >= 32
-      u64 *ha = P->d_part, *hb = P->d_part + nch;
-      hipLaunchKernelGGL(divide_by_linear_pass1, blocks(nch), dim3(256), 0, st, ca, cb, nch, z.a.v, z.b.v, ha, hb);
-      hipLaunchKernelGGL(divide_by_linear_pass2, dim3(1), dim3(256), 0, st, ha, hb, nch, z.a.v, z.b.v);
-      hipLaunchKernelGGL(divide_by_linear_pass3, blocks(nch), dim3(256), 0, st, ca, cb, nch, z.a.v, z.b.v, ha, hb, mul.a.v, mul.b.v, P->d_fcoef, P->d_fcoef + m, accumulate, fri_times_x(cfg));
-    };
-    divide(f0a, f0b, zeta, E2{F(0), F(0)}, 0);
-    divide(f1a, f1b, zeta_next, shift2, 1);
-    HIPC(hipGetLastError());
-  }
-  HIPC(hipEventRecord(P->ev[ST_FRI_LAYERS], st));
-  std::vector<std::vector<u64>> fri_caps;
-  std::vector<u64> final_poly;
-  {
-    // fri_committed_trees
-    u32 bits = P->lde_log;
-    u64* coef = P->d_fcoef; u64* coef_alt = P->d_fcoef2;
-    size_t clen = m;  // coefficient vector length (planes at coef, coef + clen)
-    F shift(GL_GEN);
-    for (size_t li = 0; li < P->fri.arity_bits.size(); li++) {
-      u32 ab = P->fri.arity_bits[li];
-      u64* va = P->fri_vals[li]; u64* vb = va + clen;
-      // values = coeffs.coset_fft(shift): scale by shift^i then NTT (2 base planes).  Layer 0 is n coefficients zero-padded to m on
-      // the coset of 7: the coset LDE of lde_coeffs, out of place, whose first pass skips the zero half
-      if (li == 0) {
-        if ((rc = ntt_columns(P, coef, clen, va, clen, P->d_tmp, m, 2, bits, false, n, P->d_shift, nullptr, 1))) return rc;
-      } else {
-        HIPC(hipMemcpyAsync(va, coef, 2 * clen * sizeof(u64), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, va, clen, shift.v);
-        hipLaunchKernelGGL(scale_pow_kernel, blocks(clen), dim3(256), 0, st, vb, clen, shift.v);
-        if ((rc = ntt_columns(P, va, clen, va, clen, P->d_tmp, m, 2, bits, false, clen, nullptr, nullptr, 1))) return rc;
-      }
-      DevTree& t = P->fri_trees[li];
-      if (t.nleaf <= 16384) hipLaunchKernelGGL(fri_leaf_hash_coop_kernel, blocks(t.nleaf * 16), dim3(256), 0, st, va, vb, bits, ab, t.d);
-      else hipLaunchKernelGGL(fri_leaf_hash_kernel, blocks(t.nleaf), dim3(256), 0, st, va, vb, bits, ab, t.d);
-      if ((rc = tree_build_inner(P, t, st))) return rc;
-      std::vector<u64> cap;
-      if ((rc = tree_cap_to_host(P, t, cap))) return rc;
-      ch.observe_words(cap.data(), capw);
-      fri_caps.push_back(cap);
-      E2 beta = ch.ext_challenge();
-      size_t nout = clen >> ab;
-      hipLaunchKernelGGL(fri_fold_kernel, blocks(nout), dim3(256), 0, st, coef, coef + clen, nout, 1u << ab, beta.a.v, beta.b.v, coef_alt, coef_alt + nout);
-      HIPC(hipGetLastError());
-      std::swap(coef, coef_alt);
-      clen = nout; bits -= ab;
-      shift = f_pow(shift, (u64)1 << ab);
-    }
-    size_t fl = clen >> cfg.rate_bits;  // coefficients beyond are zero
-    final_poly.resize(2 * fl);
-    std::vector<u64> fa(fl), fb(fl);
-    HIPC(hipMemcpyAsync(fa.data(), coef, fl * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(fb.data(), coef + clen, fl * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(stream_wait(st));
-    for (size_t i = 0; i < fl; i++) { final_poly[2 * i] = fa[i]; final_poly[2 * i + 1] = fb[i]; ch.observe(F(fa[i])); ch.observe(F(fb[i])); }
-  }
-  HIPC(hipEventRecord(P->ev[ST_POW], st));
-  // fri_proof_of_work: smallest witness
-  u64 pow_witness = ~0ULL;
-  {
-    PowParams pp{};
-    for (int i = 0; i < 12; i++) pp.state[i] = ch.st[i].v;
-    for (size_t i = 0; i < ch.in.size(); i++) pp.state[i] = ch.in[i].v;
-    pp.wpos = (u32)ch.in.size(); pp.min_lz = cfg.proof_of_work_bits; pp.result = P->d_pow;
-    // candidates are scanned in increasing windows (2^17, then 2^20 each): a 16-bit PoW is found in the
-    // first window with probability 1 - e^-2; the smallest witness over the scanned prefix is kept.
-    u64 base = 0;
-    for (int round = 0; pow_witness == ~0ULL; round++) {
-      const u64 BATCH = round == 0 ? (1ULL << 17) : (1ULL << 20);
-      if (base >= GLP - BATCH) return fail(SBN_ERR_HIP, "proof of work failed");
-      u64 init = ~0ULL;
-      HIPC(hipMemcpyAsync(P->d_pow, &init, sizeof(u64), hipMemcpyHostToDevice, st));
-      pp.base = base; pp.count = BATCH;
-      hipLaunchKernelGGL(pow_kernel, blocks(BATCH), dim3(256), 0, st, pp);
-      HIPC(hipMemcpyAsync(&pow_witness, P->d_pow, sizeof(u64), hipMemcpyDeviceToHost, st));
-      HIPC(stream_wait(st));
-      base += BATCH;
-    }
-    ch.observe(F(pow_witness));
-    F resp = ch.challenge();
-    u32 lz = resp.v ? (u32)__builtin_clzll(resp.v) : 64;
-    if (lz < cfg.proof_of_work_bits) return fail(SBN_ERR_HIP, "proof-of-work witness check failed");
-  }
-  HIPC(hipEventRecord(P->ev[ST_QUERIES], st));
-  // fri_prover_query_rounds
-  const u32 nq = cfg.num_query_rounds;
-  std::vector<u64> qwords(P->qstride * nq);
-  std::vector<u32> idx(nq), idx_local(nq);  // pageable sources of async uploads: they live until the stream_wait below
-  size_t split_section = 0;                 // the split: words per query that come from the row-sharded trees
-  {
-    for (u32 q = 0; q < nq; q++) idx[q] = (u32)(ch.challenge().v % m);
-    HIPC(hipMemcpyAsync(P->d_idx, idx.data(), nq * sizeof(u32), hipMemcpyHostToDevice, st));
-    size_t off = 0;
-    const u32 nsib = P->lde_log - cfg.cap_height;
-    // a row-sharded matrix (the split): `rows` local rows, leaf index inside this rank's subtrees; the rank that owns a
-    // query's leaf holds its whole row and its Merkle path up to the cap (other ranks gather a row that is dropped below)
-    // coef (compact storage of a wide matrix; else null): the rows are not resident and are evaluated from the coefficients
-    // (lde_compact.hip; its point tables sit in d_part, idle since the FRI combine)
-    int rows_rc = 0;
-    auto initial = [&](const u64* mat, size_t ncols, const DevTree& t, size_t rows, u32 log_rows, const u32* d_index, const u64* coef = nullptr) {
-      if (coef) { if (!rows_rc) rows_rc = launch_query_rows(coef, ncols, n, P->lde_log, P->d_shift, P->d_tw_f, d_index, nq, P->d_part, P->d_qbuf, P->qstride, off, st); }
-      else hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((ncols + 255) / 256), nq), dim3(256), 0, st, mat, rows, log_rows, (u32)ncols, d_index, P->d_qbuf, P->qstride, off);
-      off += ncols;
-      hipLaunchKernelGGL(gather_siblings_kernel, dim3(nq), dim3(128), 0, st, t.d, t.nleaf, nsib, d_index, 0u, P->d_qbuf, P->qstride, off);
-      off += (size_t)nsib * 4;
-    };
-    if (S) {
-      for (u32 q = 0; q < nq; q++) idx_local[q] = idx[q] & (u32)(S->ml - 1);
-      HIPC(hipMemcpyAsync(S->d_idx_local, idx_local.data(), nq * sizeof(u32), hipMemcpyHostToDevice, st));
-      initial(S->lde_l, C, P->tree_t, S->ml, P->lde_log - S->log_r, S->d_idx_local);
-      if (Z) initial(S->zlde_l, Z, P->tree_z, S->ml, P->lde_log - S->log_r, S->d_idx_local);
-      split_section = off;
-    } else {
-      initial(P->d_lde, C, P->tree_t, m, P->lde_log, P->d_idx, P->compact ? P->d_coef : nullptr);
-      if (Z) initial(P->d_zlde, Z, P->tree_z, m, P->lde_log, P->d_idx, P->compact ? P->d_zcoef : nullptr);
-      if (rows_rc) return rows_rc;
-    }
-    initial(P->d_qlde, 4, P->tree_q, m, P->lde_log, P->d_idx);
-    u32 bits = P->lde_log, shift = 0;
-    for (size_t li = 0; li < P->fri.arity_bits.size(); li++) {
-      u32 ab = P->fri.arity_bits[li];
-      shift += ab;
-      size_t len = (size_t)1 << bits;
-      hipLaunchKernelGGL(gather_fri_leaf_kernel, dim3(nq), dim3(64), 0, st, P->fri_vals[li], P->fri_vals[li] + len, bits, ab, P->d_idx, shift, P->d_qbuf, P->qstride, off);
-      off += 2 * ((size_t)1 << ab);
-      const DevTree& t = P->fri_trees[li];
-      hipLaunchKernelGGL(gather_siblings_kernel, dim3(nq), dim3(128), 0, st, t.d, t.nleaf, t.nlevels, P->d_idx, shift, P->d_qbuf, P->qstride, off);
-      off += (size_t)t.nlevels * 4;
-      bits -= ab;
-    }
-    HIPC(hipGetLastError());
-    if (off != P->qstride) return fail(SBN_ERR_HIP, "internal: query layout mismatch (%zu vs %zu)", off, P->qstride);
-    HIPC(hipMemcpyAsync(qwords.data(), P->d_qbuf, qwords.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-  }
-  HIPC(hipEventRecord(P->ev[ST_COUNT], st));
-  HIPC(stream_wait(st));
+  int rc;
+  if ((rc = stage_trace_commit(run)) || (rc = stage_perm_z(run)) || (rc = stage_z_commit(run)) || (rc = stage_quotient_eval(run)) ||
+      (rc = stage_quotient_commit(run)) || (rc = stage_openings(run)) || (rc = stage_fri_combine(run)) || (rc = stage_fri_layers(run)) ||
+      (rc = stage_pow(run)) || (rc = stage_queries(run)))
+    return rc;
   for (int i = 0; i < ST_COUNT; i++) HIPC(hipEventElapsedTime(&P->stage_ms[i], P->ev[i], P->ev[i + 1]));
-  if (S) {
-    // the trace / Z sections of every query come from the rank that owns the leaf: all-gather on the host and pick
-    const u32 R = S->comm.world;
-    std::vector<u64> mine((size_t)nq * split_section), all((size_t)R * nq * split_section);
-    for (u32 q = 0; q < nq; q++) memcpy(mine.data() + (size_t)q * split_section, qwords.data() + (size_t)q * P->qstride, split_section * sizeof(u64));
-    if ((rc = split_all_gather_host(P, mine.data(), all.data(), mine.size() * sizeof(u64)))) return rc;
-    for (u32 q = 0; q < nq; q++) {
-      const u32 owner = idx[q] >> (P->lde_log - S->log_r);
-      memcpy(qwords.data() + (size_t)q * P->qstride, all.data() + ((size_t)owner * nq + q) * split_section, split_section * sizeof(u64));
-    }
-    float xms = 0;   // device time inside the exchanges (waiting for the peers' blocks included)
-    for (size_t i = 0; i + 1 < S->tev_used; i += 2) { float t = 0; HIPC(hipEventElapsedTime(&t, S->tev[i], S->tev[i + 1])); xms += t; }
-    P->stage_ms[ST_COUNT + EX_COMM_MS] = xms;
-  }
-
-  // assemble canonical proof words (layout: include/sbn.h) -----------------------------------------
-  sbn_proof* pr = new sbn_proof();
-  pr->degree_bits = P->degree_bits;
-  std::vector<u64>& w = pr->words;
-  w.reserve(12 + 3 * capw + (C + Z + 4) * 4 + fri_caps.size() * capw + qwords.size() + final_poly.size() + 1 + P->pi.size());
-  u64 hdr[12] = {PROOF_MAGIC, P->degree_bits, C, Z, 4, P->pi.size(), cfg.cap_height, cfg.rate_bits, fri_caps.size(), cfg.fri_arity_bits,
-                 final_poly.size() / 2, nq};
-  w.insert(w.end(), hdr, hdr + 12);
-  w.insert(w.end(), trace_cap.begin(), trace_cap.end());
-  if (Z) w.insert(w.end(), z_cap.begin(), z_cap.end());
-  w.insert(w.end(), q_cap.begin(), q_cap.end());
-  for (size_t p = 0; p < C; p++) { w.push_back(open[4 * p]); w.push_back(open[4 * p + 1]); }          // local_values
-  for (size_t p = 0; p < C; p++) { w.push_back(open2[4 * p + 2]); w.push_back(open2[4 * p + 3]); }    // next_values
-  for (size_t p = C; p < C + Z; p++) { w.push_back(open[4 * p]); w.push_back(open[4 * p + 1]); }      // permutation_zs
-  for (size_t p = C; p < C + Z; p++) { w.push_back(open2[4 * p + 2]); w.push_back(open2[4 * p + 3]); }  // permutation_zs_next
-  for (size_t p = C + Z; p < C + Z + 4; p++) { w.push_back(open[4 * p]); w.push_back(open[4 * p + 1]); }  // quotient_polys
-  for (auto& cap : fri_caps) w.insert(w.end(), cap.begin(), cap.end());
-  w.insert(w.end(), qwords.begin(), qwords.end());
-  w.insert(w.end(), final_poly.begin(), final_poly.end());
-  w.push_back(pow_witness);
-  w.insert(w.end(), P->pi.begin(), P->pi.end());
-  *out = pr;
-  return SBN_OK;
+  return assemble_proof(run, out);
 }
 extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_impl(P, out, nullptr); }
 
@@ -1575,61 +1631,69 @@ extern "C" int sbn_prover_prove_host_columns(sbn_prover* P, const uint64_t* cons
 }
 
 // ---- building blocks for parity tests ---------------------------------------------------------------
+// A stub context for the transforms of one (degree_bits, rate_bits, cap_height): the shape fields, the switches, the transform plan
+// of a real context of this size (ntt_plan), one stream, and the buffers of `L` -- the caller's own, to which open() adds the
+// transforms' scratch and tables (lde: those of the coset LDE too, as ntt_plan picks them) -- allocated through alloc_buffers and
+// released through `owned` on every return path.
+struct ScratchCtx {
+  sbn_prover P{};
+  ~ScratchCtx() { for (void* b : P.owned) (void)hipFree(b); if (P.stream) (void)hipStreamDestroy(P.stream); }
+  int open(u32 degree_bits, u32 rate_bits, u32 cap_height, bool lde, std::vector<BufReq> L) {
+    sbn_standard_fast_config(&P.cfg); P.cfg.cap_height = cap_height; P.cfg.rate_bits = rate_bits;
+    P.degree_bits = degree_bits; P.lde_log = degree_bits + rate_bits; P.n = (size_t)1 << degree_bits; P.m = P.n << rate_bits; P.ntt_chunk = 64;
+    if (int rc = use_current_device("no CPU fallback")) return rc;
+    P.device = g_device;
+    if (int rc = ntt_fast_setup()) return rc;
+    { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
+    ntt_plan(&P);   // the transform kernels the prover picks at this size
+    HIPC(hipStreamCreate(&P.stream));
+    L.insert(L.end(), {words_req(&P.d_tmp, 64 * P.m), words_req(&P.d_tw_f, P.m), words_req(&P.d_tw_i, P.m), words_req(&P.d_shift, P.m)});
+    if (lde && (P.ntt_fused || P.ntt_fused512)) L.push_back(words_req(&P.d_tmp2, 64 * P.m));
+    if (lde && P.ntt_fused512) L.push_back(words_req(&P.d_shift_odd, P.n));
+    if (lde && P.lde_za_log) L.push_back(words_req(&P.d_shift_za, P.n << P.lde_za_log));
+    if (int rc = alloc_buffers(&P, L)) return rc;
+    fill_transform_tables(&P);
+    return 0;
+  }
+};
+
 extern "C" int sbn_commit_values(const uint64_t* cols, size_t ncols, size_t n, uint32_t rate_bits, uint32_t cap_height, uint64_t* cap_out,
                                  uint64_t* coeffs_out, uint64_t* lde_out) {
   if (!cols || !cap_out || ncols == 0) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (rate_bits < 1 || rate_bits > 3 || n < 512 || (n & (n - 1))) return fail(SBN_ERR_UNSUPPORTED, "need rate_bits 1..3 and n a power of two >= 512");
   u32 lg = 0; while (((size_t)1 << lg) < n) lg++;
   if (lg + rate_bits > SBN_MAX_LDE_BITS) return fail(SBN_ERR_UNSUPPORTED, "n << rate_bits exceeds 2^%u points", SBN_MAX_LDE_BITS);
-  // the range of config_supported: tree_alloc computes the level count lg + rate_bits - cap_height unsigned, and lg + rate_bits >= 10
+  // the range of config_supported: tree_shape computes the level count lg + rate_bits - cap_height unsigned, and lg + rate_bits >= 10
   if (cap_height < 1 || cap_height > 8) return fail(SBN_ERR_UNSUPPORTED, "cap_height must be 1..8");
   // a throw-away prover-like context built on the G1_OP shape would waste memory; build a minimal one
-  sbn_prover P{};
-  sbn_standard_fast_config(&P.cfg); P.cfg.cap_height = cap_height;
-  P.cfg.rate_bits = rate_bits;
-  P.degree_bits = lg; P.lde_log = lg + rate_bits; P.n = n; P.m = n << rate_bits; P.ntt_chunk = 64; P.device = g_device;
-  if (int rc = use_current_device("no CPU fallback")) return rc;
-  { int rc0 = ntt_fast_setup(); if (rc0) return rc0; }
-  { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
-  ntt_plan(&P);   // the transform kernels the prover picks at this size
-  HIPC(hipStreamCreate(&P.stream));
+  ScratchCtx sc;
+  sbn_prover& P = sc.P;
+  const size_t m = n << rate_bits;
   u64 *d_vals = nullptr, *d_coef = nullptr, *d_lde = nullptr;
-  int rc = 0;
-  rc |= dmalloc(&d_vals, ncols * n); rc |= dmalloc(&d_coef, ncols * n); rc |= dmalloc(&d_lde, ncols * P.m); rc |= dmalloc(&P.d_tmp, 64 * P.m);
-  if (P.ntt_fused || P.ntt_fused512) rc |= dmalloc(&P.d_tmp2, 64 * P.m);
-  if (P.ntt_fused512) rc |= dmalloc(&P.d_shift_odd, n);
-  if (P.lde_za_log) rc |= dmalloc(&P.d_shift_za, n << P.lde_za_log);
-  rc |= dmalloc(&P.d_tw_f, P.m); rc |= dmalloc(&P.d_tw_i, P.m); rc |= dmalloc(&P.d_shift, P.m);
-  rc |= tree_alloc(P.tree_t, P.m, cap_height);
-  if (!rc) {
-    auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
-    F w = f_root_of_unity(P.lde_log);
-    hipLaunchKernelGGL(pow_table_kernel, blocks(P.m), dim3(256), 0, P.stream, P.d_tw_f, P.m, w.v);
-    hipLaunchKernelGGL(pow_table_kernel, blocks(P.m), dim3(256), 0, P.stream, P.d_tw_i, P.m, f_inv(w).v);
-    hipLaunchKernelGGL(pow_table_kernel, blocks(P.m), dim3(256), 0, P.stream, P.d_shift, P.m, (u64)GL_GEN);
-    if (P.d_shift_odd) hipLaunchKernelGGL(shift_odd_table_kernel, blocks(n), dim3(256), 0, P.stream, P.d_shift_odd, n, P.d_shift, P.d_tw_f, 9u);
-    if (P.d_shift_za) lde_za_tables(&P);
-    if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess) rc = fail(SBN_ERR_HIP, "H2D failed");
-  }
-  for (size_t c0 = 0; !rc && c0 < ncols; c0 += P.ntt_chunk) rc = intt_lde_cols(&P, d_vals + c0 * n, d_coef + c0 * n, d_lde + c0 * P.m, std::min(P.ntt_chunk, ncols - c0));
-  if (!rc && ncols <= 4) rc = tree_from_matrix(&P, P.tree_t, d_lde, ncols);
-  if (!rc && ncols > 4) {  // same chunked sponge as the prover (chunks of 64 columns), on one stream
-    rc = dmalloc(&P.d_sponge, 12 * P.m);
-    for (size_t c0 = 0; !rc && c0 < ncols; c0 += 64) {
+  std::vector<BufReq> L{words_req(&d_vals, ncols * n), words_req(&d_coef, ncols * n), words_req(&d_lde, ncols * m)};
+  tree_shape(P.tree_t, m, cap_height);
+  L.push_back(words_req(&P.tree_t.d, 2 * m * 4));
+  if (ncols > 4) L.push_back(words_req(&P.d_sponge, 12 * m));
+  if (int rc = sc.open(lg, rate_bits, cap_height, true, L)) return rc;
+  if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess) return fail(SBN_ERR_HIP, "H2D failed");
+  for (size_t c0 = 0; c0 < ncols; c0 += P.ntt_chunk)
+    if (int rc = intt_lde_cols(&P, d_vals + c0 * n, d_coef + c0 * n, d_lde + c0 * m, std::min(P.ntt_chunk, ncols - c0))) return rc;
+  if (ncols <= 4) {
+    if (int rc = tree_from_matrix(&P, P.tree_t, d_lde, ncols)) return rc;
+  } else {  // same chunked sponge as the prover (chunks of 64 columns), on one stream
+    for (size_t c0 = 0; c0 < ncols; c0 += 64) {
       size_t nc = std::min<size_t>(64, ncols - c0);
-      hipLaunchKernelGGL(leaf_absorb_kernel, dim3((unsigned)((P.m + 255) / 256)), dim3(256), 0, P.stream, d_lde + c0 * P.m, P.m, P.lde_log, (u32)nc, P.d_sponge,
+      hipLaunchKernelGGL(leaf_absorb_kernel, blocks(m), dim3(256), 0, P.stream, d_lde + c0 * m, m, P.lde_log, (u32)nc, P.d_sponge,
                          c0 == 0 ? 1 : 0, c0 + 64 >= ncols ? 1 : 0, P.tree_t.d, (c0 + 64 < ncols && ncols - (c0 + 64) >= 8) ? 1 : 0);
     }
-    if (!rc) rc = tree_build_inner(&P, P.tree_t, P.stream);
+    if (int rc = tree_build_inner(&P, P.tree_t, P.stream)) return rc;
   }
   std::vector<u64> cap;
-  if (!rc) rc = tree_cap_to_host(&P, P.tree_t, cap);
-  if (!rc) memcpy(cap_out, cap.data(), cap.size() * sizeof(u64));
-  if (!rc && coeffs_out && hipMemcpy(coeffs_out, d_coef, ncols * n * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBN_ERR_HIP, "D2H failed");
-  if (!rc && lde_out && hipMemcpy(lde_out, d_lde, ncols * P.m * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBN_ERR_HIP, "D2H failed");
-  for (u64* b : {d_vals, d_coef, d_lde, P.d_tmp, P.d_tmp2, P.d_shift_odd, P.d_shift_za, P.d_tw_f, P.d_tw_i, P.d_shift, P.tree_t.d, P.d_sponge}) if (b) (void)hipFree(b);
-  (void)hipStreamDestroy(P.stream);
-  return rc;
+  if (int rc = tree_cap_to_host(&P, P.tree_t, cap)) return rc;
+  memcpy(cap_out, cap.data(), cap.size() * sizeof(u64));
+  if (coeffs_out && hipMemcpy(coeffs_out, d_coef, ncols * n * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) return fail(SBN_ERR_HIP, "D2H failed");
+  if (lde_out && hipMemcpy(lde_out, d_lde, ncols * m * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) return fail(SBN_ERR_HIP, "D2H failed");
+  return SBN_OK;
 }
 
 // The twin of sbn_commit_values for the compact storage: values -> coefficients through the transform plan of a prover of this
@@ -1641,49 +1705,38 @@ extern "C" int sbn_lde_rows(const uint64_t* cols, size_t ncols, uint32_t degree_
     return fail(SBN_ERR_UNSUPPORTED, "need rate_bits 1..3 and 9 <= degree_bits with degree_bits + rate_bits <= %u", SBN_MAX_LDE_BITS);
   const size_t n = (size_t)1 << degree_bits, m = n << rate_bits;
   for (size_t i = 0; i < count; i++) if (leaf_indices[i] >= m) return fail(SBN_ERR_BAD_ARG, "leaf index %zu is %u, beyond the %zu leaves", i, leaf_indices[i], m);
-  sbn_prover P{};
-  sbn_standard_fast_config(&P.cfg); P.cfg.rate_bits = rate_bits;
-  P.degree_bits = degree_bits; P.lde_log = degree_bits + rate_bits; P.n = n; P.m = m; P.ntt_chunk = 64;
-  if (int rc = use_current_device("no CPU fallback")) return rc;
-  P.device = g_device;
-  { int rc0 = ntt_fast_setup(); if (rc0) return rc0; }
-  { std::string serr; if (!P.set.load(serr)) return fail(SBN_ERR_BAD_ARG, "%s", serr.c_str()); }
-  ntt_plan(&P);   // the transform kernels the prover picks at this size
-  HIPC(hipStreamCreate(&P.stream));   // (nothing is allocated yet)
+  ScratchCtx sc;
+  sbn_prover& P = sc.P;
   u64 *d_vals = nullptr, *d_coef = nullptr, *d_table = nullptr, *d_out = nullptr; u32* d_index = nullptr;
-  int rc = 0;
-  rc |= dmalloc(&d_vals, ncols * n); rc |= dmalloc(&d_coef, ncols * n); rc |= dmalloc(&P.d_tmp, 64 * m); rc |= dmalloc(&d_table, 64 * n); rc |= dmalloc(&d_out, count * ncols);
-  rc |= dmalloc(&P.d_tw_f, m); rc |= dmalloc(&P.d_tw_i, m); rc |= dmalloc(&P.d_shift, m);
-  if (!rc && hipMalloc((void**)&d_index, count * sizeof(u32)) != hipSuccess) rc = fail(SBN_ERR_HIP, "hipMalloc failed");
-  if (!rc) {
-    auto blocks = [](size_t k) { return dim3((unsigned)((k + 255) / 256)); };
-    F w = f_root_of_unity(P.lde_log);
-    hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P.stream, P.d_tw_f, m, w.v);
-    hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P.stream, P.d_tw_i, m, f_inv(w).v);
-    hipLaunchKernelGGL(pow_table_kernel, blocks(m), dim3(256), 0, P.stream, P.d_shift, m, (u64)GL_GEN);
-    if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_index, leaf_indices, count * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess) rc = fail(SBN_ERR_HIP, "H2D failed");
-  }
-  if (!rc) rc = intt_values(&P, d_vals, d_coef, ncols);
-  if (!rc) rc = launch_query_rows(d_coef, ncols, n, P.lde_log, P.d_shift, P.d_tw_f, d_index, (u32)count, d_table, d_out, ncols, 0, P.stream);
-  if (!rc && hipStreamSynchronize(P.stream) != hipSuccess) rc = fail(SBN_ERR_HIP, "sbn_lde_rows: the kernels failed");
-  if (!rc && hipMemcpy(rows_out, d_out, count * ncols * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBN_ERR_HIP, "D2H failed");
-  for (u64* b : {d_vals, d_coef, d_table, d_out, P.d_tmp, P.d_tw_f, P.d_tw_i, P.d_shift}) if (b) (void)hipFree(b);
-  if (d_index) (void)hipFree(d_index);
-  (void)hipStreamDestroy(P.stream);
-  return rc;
+  if (int rc = sc.open(degree_bits, rate_bits, 1, false,   // (no tree is built: the cap height is not read)
+                       {words_req(&d_vals, ncols * n), words_req(&d_coef, ncols * n), words_req(&d_table, 64 * n), words_req(&d_out, count * ncols),
+                        BufReq{(void**)&d_index, count * sizeof(u32)}}))
+    return rc;
+  if (hipMemcpy(d_vals, cols, ncols * n * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_index, leaf_indices, count * sizeof(u32), hipMemcpyHostToDevice) != hipSuccess) return fail(SBN_ERR_HIP, "H2D failed");
+  if (int rc = intt_values(&P, d_vals, d_coef, ncols)) return rc;
+  if (int rc = launch_query_rows(d_coef, ncols, n, P.lde_log, P.d_shift, P.d_tw_f, d_index, (u32)count, d_table, d_out, ncols, 0, P.stream)) return rc;
+  if (hipStreamSynchronize(P.stream) != hipSuccess) return fail(SBN_ERR_HIP, "sbn_lde_rows: the kernels failed");
+  if (hipMemcpy(rows_out, d_out, count * ncols * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess) return fail(SBN_ERR_HIP, "D2H failed");
+  return SBN_OK;
 }
+
+// Device words that are freed on every return path: the buffer of the upload / run one kernel / download entry points below.
+struct DevWords {
+  u64* d = nullptr;
+  ~DevWords() { if (d) (void)hipFree(d); }
+  int alloc(size_t words) { HIPC(hipMalloc((void**)&d, words * sizeof(u64))); return 0; }
+};
 
 extern "C" int sbn_poseidon_permute_batch(uint64_t* states, size_t count) {
   if (!states) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (int rc = use_current_device("no CPU fallback")) return rc;
   for (size_t i = 0; i < count * 12; i++) if (states[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "state word %zu is not canonical", i);
-  u64* d = nullptr;
-  HIPC(hipMalloc((void**)&d, count * 12 * sizeof(u64)));
-  HIPC(hipMemcpy(d, states, count * 12 * sizeof(u64), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(poseidon_batch_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d, count);
-  HIPC(hipMemcpy(states, d, count * 12 * sizeof(u64), hipMemcpyDeviceToHost));
-  (void)hipFree(d);
+  DevWords w;
+  if (int rc = w.alloc(count * 12)) return rc;
+  HIPC(hipMemcpy(w.d, states, count * 12 * sizeof(u64), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(poseidon_batch_kernel, blocks(count), dim3(256), 0, 0, w.d, count);
+  HIPC(hipMemcpy(states, w.d, count * 12 * sizeof(u64), hipMemcpyDeviceToHost));
   return SBN_OK;
 }
 
@@ -1692,15 +1745,11 @@ extern "C" int sbn_poseidon_permute_coop_batch(uint64_t* states, size_t count) {
   for (size_t i = 0; i < count * 12; i++) if (states[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "state word %zu is not canonical", i);
   if (int rc = use_current_device("no CPU fallback")) return rc;
   if (count == 0) return SBN_OK;
-  u64* d = nullptr;
-  HIPC(hipMalloc((void**)&d, count * 12 * sizeof(u64)));
-  hipError_t e = hipMemcpy(d, states, count * 12 * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(poseidon_coop_batch_kernel, dim3((unsigned)((count * 16 + 255) / 256)), dim3(256), 0, 0, d, count);
-    e = hipMemcpy(states, d, count * 12 * sizeof(u64), hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_poseidon_permute_coop_batch: %s", hipGetErrorString(e));
+  DevWords w;
+  if (int rc = w.alloc(count * 12)) return rc;
+  HIPC(hipMemcpy(w.d, states, count * 12 * sizeof(u64), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(poseidon_coop_batch_kernel, blocks(count * 16), dim3(256), 0, 0, w.d, count);
+  HIPC(hipMemcpy(states, w.d, count * 12 * sizeof(u64), hipMemcpyDeviceToHost));
   return SBN_OK;
 }
 
@@ -1708,20 +1757,34 @@ extern "C" int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_
   if (!a || !b || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (int rc = use_current_device("no CPU fallback")) return rc;
   if (count == 0) return SBN_OK;
-  u64* d = nullptr;
-  HIPC(hipMalloc((void**)&d, 3 * count * sizeof(u64)));
-  hipError_t e = hipMemcpy(d, a, count * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + count, b, count * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(field_mul_batch_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d, d + count, d + 2 * count, count, mode);
-    e = hipMemcpy(out, d + 2 * count, count * sizeof(u64), hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_field_mul_batch: %s", hipGetErrorString(e));
+  DevWords w;
+  if (int rc = w.alloc(3 * count)) return rc;
+  u64* const d = w.d;
+  HIPC(hipMemcpy(d, a, count * sizeof(u64), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(d + count, b, count * sizeof(u64), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(field_mul_batch_kernel, blocks(count), dim3(256), 0, 0, d, d + count, d + 2 * count, count, mode);
+  HIPC(hipMemcpy(out, d + 2 * count, count * sizeof(u64), hipMemcpyDeviceToHost));
   return SBN_OK;
 }
 
 
+
+// The round trip of the scan (reduce: of its reducing twin, and the words come back too): words up, one launch, *result back.  The
+// device copy keeps the caller's offset from a 16-byte boundary, so the kernels' unaligned head is reachable from a test.
+static int scan_round_trip(const u64* words, u64* words_back, size_t count, unsigned long long* result) {
+  const size_t off = ((size_t)words & 8) ? 1 : 0;
+  DevWords w;   // d[0]: the result word (the first bad index, all ones: none; or the counter); the data from d + 2 + off
+  if (int rc = w.alloc(2 + off + count)) return rc;
+  u64* const data = w.d + 2 + off;
+  HIPC(hipMemset(w.d, words_back ? 0 : 0xff, sizeof(u64)));
+  HIPC(hipMemcpy(data, words, count * sizeof(u64), hipMemcpyHostToDevice));
+  if (words_back) launch_reduce_words(data, count, (unsigned long long*)w.d, 0);
+  else launch_first_non_canonical(data, count, 0, (unsigned long long*)w.d, 0);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpy(result, w.d, sizeof *result, hipMemcpyDeviceToHost));
+  if (words_back) HIPC(hipMemcpy(words_back, data, count * sizeof(u64), hipMemcpyDeviceToHost));
+  return 0;
+}
 // Index of the first word >= p, or `count`: the scan of sbn_prover_prove_host_trace as a building block (host in, host out).
 extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out) {
   if (!index_out || (!words && count)) return fail(SBN_ERR_BAD_ARG, "null argument");
@@ -1732,20 +1795,8 @@ extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int 
   }
   if (int rc = use_current_device("no CPU fallback")) return rc;
   if (count == 0) return SBN_OK;
-  // the device copy keeps the caller's offset from a 16-byte boundary, so the kernel's unaligned head is reachable from a test
-  const size_t off = ((size_t)words & 8) ? 1 : 0;
-  u64* d = nullptr;
-  HIPC(hipMalloc((void**)&d, (2 + off + count) * sizeof(u64)));   // d[0]: the result word; the data from d + 2 + off
   unsigned long long first = ~0ull;
-  hipError_t e = hipMemset(d, 0xff, sizeof(u64));
-  if (e == hipSuccess) e = hipMemcpy(d + 2 + off, words, count * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_first_non_canonical(d + 2 + off, count, 0, (unsigned long long*)d, 0);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(&first, d, sizeof first, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_first_non_canonical: %s", hipGetErrorString(e));
+  if (int rc = scan_round_trip(words, nullptr, count, &first)) return rc;
   if (first != ~0ull) *index_out = first;
   return SBN_OK;
 }
@@ -1772,21 +1823,8 @@ extern "C" int sbn_reduce_words(uint64_t* words, size_t count, int on_device, ui
   }
   if (int rc = use_current_device("no CPU fallback")) return rc;
   if (count == 0) return SBN_OK;
-  // the device copy keeps the caller's offset from a 16-byte boundary, so the kernel's unaligned head is reachable from a test
-  const size_t off = ((size_t)words & 8) ? 1 : 0;
-  u64* d = nullptr;
-  HIPC(hipMalloc((void**)&d, (2 + off + count) * sizeof(u64)));   // d[0]: the counter; the data from d + 2 + off
   unsigned long long changed = 0;
-  hipError_t e = hipMemset(d, 0, sizeof(u64));
-  if (e == hipSuccess) e = hipMemcpy(d + 2 + off, words, count * sizeof(u64), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_reduce_words(d + 2 + off, count, (unsigned long long*)d, 0);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(&changed, d, sizeof changed, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(words, d + 2 + off, count * sizeof(u64), hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(SBN_ERR_HIP, "sbn_reduce_words: %s", hipGetErrorString(e));
+  if (int rc = scan_round_trip(words, words, count, &changed)) return rc;
   if (reduced_out) *reduced_out = changed;
   return SBN_OK;
 }

@@ -1,6 +1,7 @@
 // The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
-// tracegen_device.hip (which fills the trace) and by trace_check.hip (which checks it); every other unit reaches the prover
-// through the C ABI of include/sbn.h.
+// tracegen_device.hip (which fills the trace), by trace_check.hip, trace_explain.hip and trace_explain_fq12.hip (which check it)
+// and by lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of
+// include/sbn.h.
 #pragma once
 #include "host_common.hpp"
 #include "settings.hpp"
@@ -142,7 +143,10 @@ struct sbn_prover {
   u64* h_open = nullptr;                     // pinned landing buffer of the opened values [(ncols + nzs + 4)][4]
   u64* h_open2 = nullptr;                    // second landing buffer: the values at g*zeta of the trace and Z columns (the host is still reading the first)
   u64* h_w = nullptr;                        // pinned source of the FRI combine weights (d_w, at most 4,096 words)
-  size_t dev_bytes = 0;                      // device memory this context allocated (what the one-shot cache of capi.hip counts)
+  // Every device allocation of this context, in allocation order: alloc_buffers (prover.hip) is the one place that allocates and
+  // pushes here, sbn_prover_destroy frees this list and names no device buffer.  The d_* members above are views of its entries.
+  std::vector<void*> owned;
+  size_t dev_bytes = 0;                      // their bytes (what sbn_prover_memory_plan predicts and the one-shot cache of capi.hip counts)
   // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
   hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk
   hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned

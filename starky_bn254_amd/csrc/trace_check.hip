@@ -21,7 +21,7 @@ static const char* SEGMENT_NAMES[QSEG] = {"air_head", "air_tail", "perm_lo", "pe
 extern "C" const char* sbn_trace_segment_name(int s) { return (s >= 0 && s < (int)QSEG) ? SEGMENT_NAMES[s] : ""; }
 
 // The challenges of a check: the transcript observes a tag, the seed, the table and the public inputs, then hands out the
-// permutation sets (tables with Z columns only) and the alphas in the order of prove_impl (prover.hip).
+// permutation sets (tables with Z columns only) as stage_perm_z draws them and the alphas as stage_quotient_eval does (prover.hip).
 void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]) {
   Challenger ch;
   ch.observe(F(0x4b4843544e4253ULL));   // "SBNTCHK"

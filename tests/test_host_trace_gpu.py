@@ -113,6 +113,40 @@ def test_prove_host_trace_gives_the_proof_of_load_trace_and_prove(gpu, O, golden
         p.close()
 
 
+# ---- device memory: one list allocates, plans and frees -------------------------------------------------------------------
+# LookupStark at 2^9 rows: 4 columns and 2 Z columns, the one-launch commitment (no chunk pipeline); FlagStark(16) at 2^13 rows: 81
+# columns in two chunks, and no Z (no permutation stage, no Z commitment).  One context per table.
+@pytest.mark.parametrize("name", ["LookupStark", "FlagStark16"])
+def test_dev_bytes_are_the_plan_and_the_lazy_scan_word_through_prove_host_trace(gpu, O, name):
+    """describe()["dev_bytes"] counts what the context allocated: the memory plan after creation, the plan + 8 after the first
+    prove_host_trace (d_first_bad, allocated by that call and outside the plan, include/sbn.h), and the same after the second; both
+    proofs are the words of load_trace + prove."""
+    S = gpu
+    if name == "LookupStark":
+        stark = S.LookupStark()
+        trace = stark.generate_trace(*O.lookup_inputs(512, 9))
+    else:
+        stark = S.FlagStark(16)
+        trace = stark.generate_trace(O.flags_inputs(16, 8)[0])
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    cfg = stark.config()
+    db = trace.shape[1].bit_length() - 1
+    assert (stark.num_columns, stark.num_permutation_zs(), db) == ((4, 2, 9) if name == "LookupStark" else (81, 0, 13))
+    plan = S.prover_memory_plan(stark, cfg, db)
+    p = S.Prover(stark, cfg, db)
+    try:
+        assert int(p.describe()["dev_bytes"]) == plan
+        first = p.prove_host_trace(trace, NO_PI).words
+        assert int(p.describe()["dev_bytes"]) == plan + 8
+        second = p.prove_host_trace(trace, NO_PI).words
+        assert int(p.describe()["dev_bytes"]) == plan + 8
+        p.load_trace(trace, NO_PI)
+        want = p.prove().words
+        assert np.array_equal(first, want) and np.array_equal(second, want)
+    finally:
+        p.close()
+
+
 # ---- refusal -----------------------------------------------------------------------------------------------------------
 def plant_sets(ncols, n, chunk):
     """Flat word indices to set to p: word 0; the last word; the first word of the last (partial) chunk; a chunk seam."""

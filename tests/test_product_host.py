@@ -511,6 +511,16 @@ def S_lib_path():
     return pkg.lib_path()
 
 
+def test_stage_names_pin_the_stage_and_extra_enums(S):
+    """sbn_prover_stage_name lists enum Stage (the ten stage functions of prove(), in proof order) and then enum Extra of
+    csrc/prover_ctx.hpp: the keys of stage_times() and of bench.py's stage split.  "" outside the sixteen."""
+    name = S.lib().sbn_prover_stage_name
+    assert [name(i).decode() for i in range(16)] == [
+        "trace_commit", "perm_z", "z_commit", "quotient_eval", "quotient_commit", "openings", "fri_combine", "fri_layers", "pow", "queries",
+        "trace_absorb_kernels_ms", "trace_absorb_launches", "z_absorb_kernels_ms", "z_absorb_launches", "device_tracegen_ms", "split_exchange_ms"]
+    assert name(16) == b"" and name(-1) == b""
+
+
 def test_unit_test_tables_shape_and_host_witness(S, O, golden):
     """The reference's two unit-test tables as product kinds: MyStark (lookup.rs:136-213; 4 columns, 2 pairs, 2 constraints)
     and FlagStark (flags.rs:379-547; 17 + 4 num_io columns, NO pairs): shapes, host witness == the oracle's, every constraint

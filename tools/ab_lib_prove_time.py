@@ -21,4 +21,5 @@ for _ in range(steps):
     for k, v in p.stage_times().items():
         acc[k] = acc.get(k, 0.0) + v / steps
 ms = (time.perf_counter() - t0) / steps * 1e3
-print(os.environ.get("SBN_LIB", "in-tree library"), "ms_per_proof %.3f" % ms, {k: round(acc[k], 3) for k in ("trace_commit", "z_commit", "trace_absorb_kernels_ms", "z_absorb_kernels_ms", "quotient_commit", "fri_layers")})
+STAGES = ("trace_commit", "perm_z", "z_commit", "quotient_eval", "quotient_commit", "openings", "fri_combine", "fri_layers", "pow", "queries")
+print(os.environ.get("SBN_LIB", "in-tree library"), "ms_per_proof %.3f" % ms, {k: round(acc[k], 3) for k in STAGES + ("trace_absorb_kernels_ms", "z_absorb_kernels_ms")})
