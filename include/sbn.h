@@ -251,8 +251,20 @@ int sbn_host_curve_chains(int E, const uint32_t* ios, size_t num_io, uint64_t* j
 int sbn_prover_describe(const sbn_prover* p, char* out, size_t cap);
 /* The same check without a prover or a device: SBN_OK and the resolved switches of the calling process, or SBN_ERR_BAD_ARG. */
 int sbn_settings_check(char* out, size_t cap);
-/* Raw device pointer of the loaded trace buffer (for callers that fill it on-device). */
+/* Raw device pointer of the loaded trace buffer (for callers that fill it on-device).  Words written through it count from the
+ * next sbn_prover_load_trace_device on this pointer: prove() may reuse what it derived from the trace it was last told about. */
 uint64_t* sbn_prover_trace_device_ptr(sbn_prover* p);
+/* The shape-constant columns [*first_out, *end_out) of a table: functions of the row, the height and num_io alone (the Exp tables'
+ * periodic pulse, io-pulse counter, io-pulse witness / pulse pairs and range-check table column; 0, 0 for every other table).  A
+ * single-GPU prover with whole LDEs keeps their coefficients and LDE between proofs and transforms them once: every load compares
+ * those columns of the trace with the generators' words on the device (a valid witness may differ there: such a trace is proved as
+ * before, and so is the one after it), sbn_prover_generate_trace* writes them itself.  SBN_FIXED_COLUMNS=0 transforms them in every
+ * proof.  Same proof words either way; sbn_prover_describe reports the switch, the range the context keeps and the columns the
+ * last prove() left untransformed (fixed_columns, fixed_columns_range, fixed_columns_skipped).  No device involved. */
+int sbn_fixed_columns_range(const sbn_air_desc* air, uint32_t* first_out, uint32_t* end_out);
+/* Building block: that comparison alone.  block = the columns above of a trace of 2^degree_bits rows, column-major, host memory;
+ * *match_out = 1 when every word is the generators', else 0. */
+int sbn_fixed_columns_check(const sbn_air_desc* air, uint32_t degree_bits, const uint64_t* block, int* match_out);
 /* Witness generation ON THE DEVICE, straight into the prover's trace buffer: G1ExpStark / G2ExpStark / Fq12ExpStark / FqExpStark
  * ::generate_trace + generate_public_inputs (src/curves/g1/exp.rs:255-327, src/curves/g2/exp.rs:271-342,
  * src/fields/fq12/exp.rs:283-319) without the trace ever crossing PCIe.  Same `ios` layout and the same resulting trace /

@@ -52,6 +52,7 @@ EXPORTS = [
     "sbn_verifier_create", "sbn_verifier_verify", "sbn_verifier_reason", "sbn_verifier_stage_times", "sbn_verifier_destroy",
     "sbn_prover_create_with", "sbn_batch_prover_create_with", "sbn_prover_memory_plan", "sbn_lde_rows",
     "sbn_prover_prove_host_columns", "sbn_prove_columns", "sbn_batch_prover_prove_host_columns", "sbn_gather_columns", "sbn_reduce_words",
+    "sbn_fixed_columns_range", "sbn_fixed_columns_check",
 ]
 
 
@@ -250,6 +251,9 @@ def lib():
         L.sbn_host_curve_chains.argtypes = [C.c_int, vp, sz, vp, vp, C.c_int]
         L.sbn_prover_describe.argtypes = [vp, C.c_char_p, sz]
         L.sbn_settings_check.argtypes = [C.c_char_p, sz]
+        if hasattr(L, "sbn_fixed_columns_range"):   # (a library named by SBN_LIB may predate them)
+            L.sbn_fixed_columns_range.argtypes = [vp, vp, vp]
+            L.sbn_fixed_columns_check.argtypes = [vp, C.c_uint32, vp, vp]
         _LIB = L
     return _LIB
 
@@ -940,6 +944,26 @@ def settings_check():
     buf = C.create_string_buffer(1024)
     _check(lib().sbn_settings_check(buf, 1024))
     return dict(kv.partition("=")[::2] for kv in buf.value.decode().split(" "))
+
+
+def fixed_columns_range(stark):
+    """The shape-constant columns [first, end) of a table (sbn_fixed_columns_range): the words a trace of this shape holds there do
+    not depend on the instances, and a Prover transforms them once.  (0, 0) for the tables without any.  Needs no device."""
+    f0, f1 = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().sbn_fixed_columns_range(C.byref(stark._d), C.byref(f0), C.byref(f1)))
+    return int(f0.value), int(f1.value)
+
+
+def fixed_columns_check(stark, degree_bits, block):
+    """Does `block`, the columns fixed_columns_range(stark) of a trace of 2^degree_bits rows, hold the generators' words?  The
+    comparison Prover.load_trace runs, on the device (sbn_fixed_columns_check)."""
+    f0, f1 = fixed_columns_range(stark)
+    block = np.ascontiguousarray(block, dtype=np.uint64)
+    if block.shape != (f1 - f0, 1 << degree_bits):
+        raise SbnError(-1, "block shape does not match the table's shape-constant columns")
+    match = C.c_int(0)
+    _check(lib().sbn_fixed_columns_check(C.byref(stark._d), degree_bits, _ptr(block), C.byref(match)))
+    return bool(match.value)
 
 
 _NO_ROW = (1 << 64) - 1   # UINT64_MAX: "no such row" in sbn_trace_report

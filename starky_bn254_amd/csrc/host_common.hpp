@@ -101,6 +101,19 @@ static inline size_t exp_io_words(int kind) {
   }
 }
 static inline ExpShape exp_shape(const AirShape& a) { return ExpShape(exp_e(a.kind), (int)a.num_io); }
+// The shape-constant columns [f0, f1) of a table: functions of the row index, the height and num_io alone, so every trace the
+// generators write for one shape holds the same words there.  Exp tables: the periodic pulse (counter and witness; absent in the u64
+// table), the io-pulse counter, 2 num_io (witness, pulse) pairs and the range check's table column -- what tg::periodic_kernel and
+// tg::io_pulse_kernel write without reading the instance list.  Every other table: empty.
+static inline void fixed_columns_range(const AirShape& a, size_t& f0, size_t& f1) {
+  f0 = f1 = 0;
+  if (!is_exp_air(a.kind)) return;
+  const ExpShape sh = exp_shape(a);
+  f0 = (size_t)(sh.start_periodic >= 0 ? sh.start_periodic : sh.start_io_pulses);
+  f1 = (size_t)sh.start_lookups + 1;
+}
+// the last entry of that table column (tracegen.hip: 0 .. max, then max repeated): the split range check's table has 256 entries
+static inline u64 exp_table_max(const ExpShape& sh) { return sh.split_rc ? 255 : 65535; }
 // rate_bits: 1 (standard_fast_config) and 3 (plonky2's standard_recursion_config, the blowup of 8).  The code is general in
 // rate_bits >= 1; 2 is exercised through sbn_commit_values only and stays refused here (include/sbn.h).
 static inline bool config_supported(const sbn_config* c) {

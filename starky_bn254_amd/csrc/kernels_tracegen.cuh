@@ -356,6 +356,32 @@ __global__ void io_pulse_kernel(const u64* __restrict__ inv, size_t n, size_t rp
   w[i] = i > pos ? inv[i - pos] : (i < pos ? (-F(inv[pos - i])).v : 0);
   w[n + i] = i == pos;
 }
+// Reads back what the two kernels above write: `block` = the gridDim.y columns [periodic counter, periodic witness (has_periodic
+// only)], io counter, (witness, pulse) of every io pulse, table column, n rows each; *mismatch becomes 1 unless every word is the
+// generators' word.  A valid witness may differ (a pulse witness at its own pulse row is unconstrained; the generators write 0),
+// so this is a comparison of words, not a constraint check.  No inverse table: a canonical w is 1/d exactly when w * d = 1.
+__global__ void fixed_columns_check_kernel(const u64* __restrict__ block, size_t n, int has_periodic, size_t rpb, u64 table_max, unsigned long long* __restrict__ mismatch) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int j = blockIdx.y;
+  const u64 w = block[(size_t)j * n + i];
+  auto inverse_of = [&](F d) { return w < GLP && (F(w) * d).v == 1; };   // d != 0
+  const u64 c = (i + 1) & 63;
+  bool ok;
+  if (j + 1 == (int)gridDim.y) ok = w == (i < table_max ? i : table_max);
+  else if (has_periodic && j == 0) ok = w == c;
+  else if (has_periodic && j == 1) ok = c == 63 ? w == 0 : inverse_of(-F(63 - c));
+  else {
+    j -= has_periodic ? 3 : 1;   // -1: the io counter; then witness_col(q) = 2 q, pulse_col(q) = 2 q + 1
+    if (j < 0) ok = w == i;
+    else {
+      const size_t q = (size_t)(j >> 1), pos = (q >> 1) * rpb + ((q & 1) ? rpb - 1 : 0);   // (io_pulse_kernel)
+      if (j & 1) ok = w == (i == pos ? 1u : 0u);
+      else ok = i == pos ? w == 0 : inverse_of(i > pos ? F(i - pos) : -F(pos - i));
+    }
+  }
+  if (!ok) *mismatch = 1;
+}
 
 // ---- Fq12ExpStark rows (src/fields/fq12/exp.rs:229-319) -----------------------------------------------------------------
 // One lane per row.  ca / cb: the square-and-multiply chains of every instance in standard form, [K][257][12][4]

@@ -345,10 +345,19 @@ static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0
 // k + ring_depth waits for it in front of that pass -- the one dependency of the transforms on the hash stream.  (The first
 // ring_depth chunks of a commitment need no wait: the main stream has waited for hash_done of the commitment before, and the
 // second transform stream starts every chunk behind an event of the main stream.)
+// [keep0, keep1) (stage_trace_commit; empty: none): columns whose coefficients and LDE an earlier proof left in `coef` and `lde`, the
+// same words this one would write.  Nothing transforms them: a chunk is transformed in the pieces that lie outside the range (the
+// transforms are per column, and the block is no multiple of the chunk at either end) -- one piece as always when it lies wholly
+// outside; its columns below keep0 and those from keep1 on, two pieces at most, when it straddles an end or holds the whole range;
+// none when it lies wholly inside.  The sponge launch of every chunk stays what it is and reads the LDE in place, behind
+// chunk_ready[k] where this proof records it (behind the last piece) and, for a chunk without a piece, behind the launch of the
+// chunk in front on the in-order hash stream alone.  keep0 > 0, so chunk 0 always has a piece and the hash stream enters the
+// commitment behind the main stream as before.  *kept (optional): the columns left untransformed.
 static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, size_t ncols, DevTree& t, int ex_ms, int ex_launches, const HostUpload* up = nullptr,
-                           u64* dense = nullptr) {
+                           u64* dense = nullptr, size_t keep0 = 0, size_t keep1 = 0, size_t* kept = nullptr) {
   size_t ch = P->ntt_chunk;
   const bool ring = dense != nullptr && ncols > 4;
+  if (keep1 > keep0 && (keep0 == 0 || ring || up)) return fail(SBN_ERR_HIP, "internal: resident transforms on a path that keeps none");
   const size_t qn = 2 * P->n;
   if (ring && (!P->d_ring || P->ring_depth == 0)) return fail(SBN_ERR_HIP, "internal: compact commitment without a chunk ring");
   size_t nchunks = (ncols + ch - 1) / ch;
@@ -369,36 +378,54 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
   // behind the LDE of chunk k -- 28.3 -> 29.6 ms per proof: the stage is bound by the VALU work of sponge + transforms
   // together, not by the latency of the transform stream, and more transform waves in flight only slow the sponge launches
   // (12.3 -> 14.8 ms of sponge kernel time).
+  size_t nt = 0, two_back[2] = {0, 0};   // pieces transformed so far; the chunks of the last two, [piece number & 1]
+  if (kept) *kept = 0;
   for (size_t k = 0; k < nchunks; k++) {
     size_t c0 = k * ch, nc = std::min(ch, ncols - c0);
     int rc;
     const u32 slot = ring ? (u32)(k % P->ring_depth) : 0;
     u64* const lde_k = ring ? P->d_ring + (size_t)slot * ch * P->m : lde + c0 * P->m;
     const hipEvent_t slot_free = (ring && k >= P->ring_depth) ? P->ring_free[k - P->ring_depth] : nullptr;
+    // the pieces [a, a + cnt) of this chunk that are transformed: all of it, or what [ka, kb), its share of the resident range, leaves
+    struct { size_t a, cnt; } piece[2] = {{c0, nc}, {0, 0}};
+    int npieces = 1;
+    const size_t ka = std::max(c0, keep0), kb = std::min(c0 + nc, keep1);
+    if (ka < kb) {
+      npieces = 0;
+      if (ka > c0) piece[npieces++] = {c0, ka - c0};
+      if (kb < c0 + nc) piece[npieces++] = {kb, c0 + nc - kb};
+      if (kept) *kept += kb - ka;
+    }
     if (up) {
       if ((rc = upload_chunk(P, *up, k, c0, nc))) return rc;
       HIPC(hipStreamWaitEvent(P->stream, up->done[k], 0));
     }
-    if (P->ntt_two_streams && (P->ntt_fused || P->ntt_fused512) && P->d_tmp3) {
-      // the fused kernel of chunk k writes buffer k & 1, which the LDE pass B of chunk k - 2 (second stream) must have left
-      if (k >= 2) HIPC(hipStreamWaitEvent(P->stream, P->chunk_ready[k - 2], 0));
-      rc = intt_lde_cols_fused(P, vals + c0 * P->n, coef + c0 * P->n, lde_k, nc, (k & 1) ? P->d_tmp3 : P->d_tmp2, P->nstream, P->intt_done[k], slot_free);
-      if (rc) return rc;
-      HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
-    } else if (P->ntt_two_streams && !P->ntt_fused && !P->ntt_fused512) {
-      rc = ntt_columns(P, vals + c0 * P->n, P->n, coef + c0 * P->n, P->n, P->d_tmp, P->m, nc, P->degree_bits, true, P->n, nullptr, nullptr, host_inv_pow2(P->degree_bits));
-      if (rc) return rc;
-      HIPC(hipEventRecord(P->intt_done[k], P->stream));
-      HIPC(hipStreamWaitEvent(P->nstream, P->intt_done[k], 0));
-      rc = lde_cols(P, coef + c0 * P->n, lde_k, P->d_tmp2, nc, P->nstream, slot_free);
-      if (rc) return rc;
-      HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
-    } else {
-      rc = intt_lde_cols(P, vals + c0 * P->n, coef + c0 * P->n, lde_k, nc, slot_free);
-      if (rc) return rc;
-      HIPC(hipEventRecord(P->chunk_ready[k], P->stream));
+    for (int pc = 0; pc < npieces; pc++) {
+      const size_t a = piece[pc].a, cnt = piece[pc].cnt;
+      const u64* const v_p = vals + a * P->n; u64* const cf_p = coef + a * P->n; u64* const lde_p = lde_k + (a - c0) * P->m;
+      if (P->ntt_two_streams && (P->ntt_fused || P->ntt_fused512) && P->d_tmp3) {
+        // the fused kernel of piece number nt writes buffer nt & 1, which the LDE pass B of piece nt - 2 (second stream) must have
+        // left: chunk_ready of that piece's chunk is recorded behind it.  (Without a resident range: chunk k - 2, buffer k & 1.)
+        if (nt >= 2) HIPC(hipStreamWaitEvent(P->stream, P->chunk_ready[two_back[nt & 1]], 0));
+        rc = intt_lde_cols_fused(P, v_p, cf_p, lde_p, cnt, (nt & 1) ? P->d_tmp3 : P->d_tmp2, P->nstream, P->intt_done[k], slot_free);
+        if (rc) return rc;
+        HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
+      } else if (P->ntt_two_streams && !P->ntt_fused && !P->ntt_fused512) {
+        rc = ntt_columns(P, v_p, P->n, cf_p, P->n, P->d_tmp, P->m, cnt, P->degree_bits, true, P->n, nullptr, nullptr, host_inv_pow2(P->degree_bits));
+        if (rc) return rc;
+        HIPC(hipEventRecord(P->intt_done[k], P->stream));
+        HIPC(hipStreamWaitEvent(P->nstream, P->intt_done[k], 0));
+        rc = lde_cols(P, cf_p, lde_p, P->d_tmp2, cnt, P->nstream, slot_free);
+        if (rc) return rc;
+        HIPC(hipEventRecord(P->chunk_ready[k], P->nstream));
+      } else {
+        rc = intt_lde_cols(P, v_p, cf_p, lde_p, cnt, slot_free);
+        if (rc) return rc;
+        HIPC(hipEventRecord(P->chunk_ready[k], P->stream));
+      }
+      two_back[nt & 1] = k; nt++;
     }
-    HIPC(hipStreamWaitEvent(P->hstream, P->chunk_ready[k], 0));
+    if (npieces) HIPC(hipStreamWaitEvent(P->hstream, P->chunk_ready[k], 0));   // (as recorded last: behind the chunk's last piece)
     HIPC(hipEventRecord(P->abs_ev[2 * k], P->hstream));
     hipLaunchKernelGGL(leaf_absorb_kernel, dim3((unsigned)((P->m + 255) / 256)), dim3(256), 0, P->hstream, lde_k, P->m, P->lde_log, (u32)nc,
                        P->d_sponge, k == 0 ? 1 : 0, k + 1 == nchunks ? 1 : 0, t.d,
@@ -681,6 +708,9 @@ static int ctx_shape(sbn_prover* P, const AirShape& as, const sbn_config* cfg, u
   P->lde_storage = lde_storage;
   P->compact = lde_storage == SBN_LDE_COMPACT && as.ncols > 4;
   P->ring_depth = P->compact ? LDE_RING_DEPTH : 0;
+  // the shape-constant columns whose transforms stay resident between proofs (stage_trace_commit): whole LDEs on one GPU only -- under
+  // compact storage a chunk's LDE lives in the ring, and create_ctx empties the range of a split context
+  if (set.fixed_columns && !P->compact) fixed_columns_range(as, P->fixed_f0, P->fixed_f1);
   P->apow_n = apow_len(as.nconstraints, as.nzs);
   // query section stride (words per query round)
   {
@@ -829,6 +859,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
       }
     }
     SplitCtx* S = P->sp = new SplitCtx();
+    P->fixed_f0 = P->fixed_f1 = 0;   // a rank keeps the LDE rows of its subtrees, not columns: every proof transforms every column
     for (auto& e : S->xchg_done) e = nullptr;
     S->comm = *comm; S->log_r = lr; S->rho = bitrev32(comm->rank, lr); S->ml = m >> lr; S->planes = R >= 4 ? 2 : 1;
     S->slot_words = slotw;
@@ -920,8 +951,23 @@ static int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi) {
   P->pi.assign(pi, pi + n_pi);
   return 0;
 }
+// Behind a copy into d_trace: do its shape-constant columns hold the generators' words (P->fixed_match)?  The caller owns the trace,
+// and a valid witness may hold other words there, so the device compares: one launch over (fixed_f1 - fixed_f0) n words and one
+// word back.  The mismatch word borrows the start of d_tmp, which only prove() and the checks use, none of them in flight here.
+static int fixed_columns_check(sbn_prover* P) {
+  P->fixed_match = false;
+  if (P->fixed_f1 <= P->fixed_f0) return 0;
+  unsigned long long* d_word = (unsigned long long*)P->d_tmp;
+  unsigned long long mismatch = 1;
+  if (int rc = launch_fixed_columns_check(P->d_trace + P->fixed_f0 * P->n, P->fixed_f1 - P->fixed_f0, P->n, exp_shape(P->air), d_word, P->stream)) return rc;
+  HIPC(hipMemcpyAsync(&mismatch, d_word, sizeof mismatch, hipMemcpyDeviceToHost, P->stream));
+  HIPC(hipStreamSynchronize(P->stream));
+  P->fixed_match = mismatch == 0;
+  return 0;
+}
 extern "C" int sbn_prover_load_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi) {
   if (!P || !trace) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->fixed_match = false;   // before any check: whatever this call leaves in d_trace, it is no longer known
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
   size_t words = P->air.ncols * P->n;
   {  // canonical-form check on several host threads (the copy below is the PCIe-bound part)
@@ -939,14 +985,17 @@ extern "C" int sbn_prover_load_trace(sbn_prover* P, const uint64_t* trace, const
   }
   HIPC(hipSetDevice(P->device));
   HIPC(hipMemcpy(P->d_trace, trace, words * sizeof(u64), hipMemcpyHostToDevice));
+  if ((rc = fixed_columns_check(P))) return rc;
   P->loaded = true;
   return SBN_OK;
 }
 extern "C" int sbn_prover_load_trace_device(sbn_prover* P, const uint64_t* d_trace, const uint64_t* pi, size_t n_pi) {
   if (!P || !d_trace) return fail(SBN_ERR_BAD_ARG, "null argument");
+  P->fixed_match = false;   // (the caller may have written through sbn_prover_trace_device_ptr already)
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
   HIPC(hipSetDevice(P->device));
   if (d_trace != P->d_trace) HIPC(hipMemcpy(P->d_trace, d_trace, P->air.ncols * P->n * sizeof(u64), hipMemcpyDeviceToDevice));
+  if ((rc = fixed_columns_check(P))) return rc;
   P->loaded = true;
   return SBN_OK;
 }
@@ -1070,6 +1119,7 @@ struct ProofRun {
   SplitCtx* S = nullptr;                      // prove_impl: P->sp, non-null: this rank's share of one trace split over S->comm.world GPUs; every stage
   const HostUpload* up = nullptr;             // prove_impl: null for sbn_prover_prove (the trace is resident), else the host trace streamed in; trace_commit
   Challenger ch;                              // the transcript: every stage observes into it and draws from it, in stage order
+  bool fills_fixed = false;                   // trace_commit: it transforms the generators' words of the shape-constant columns; prove_impl, behind the proof
   std::vector<u64> trace_cap, z_cap, q_cap;   // trace_commit, z_commit (Z > 0 only), quotient_commit; assemble_proof
   F gamma0, gamma1;                           // perm_z; quotient_eval
   F alphas[SBN_NCH];                          // quotient_eval draws them, for its own tables and kernels
@@ -1097,10 +1147,21 @@ struct ProofRun {
 static int stage_trace_commit(ProofRun& run) {
   sbn_prover* P = run.P; SplitCtx* S = run.S; const HostUpload* up = run.up;
   if (up) HIPC(hipMemsetAsync(P->d_first_bad, up->reduce ? 0 : 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
+  // The shape-constant columns (prover_ctx.hpp fixed_match / fixed_valid; the range is empty for the split, compact storage and the
+  // tables without one).  The resident trace holds the generators' words there and an earlier proof of them succeeded: their
+  // coefficients and LDE are in place, nothing transforms them.  It holds them and no such proof yet: everything is transformed, and
+  // prove_impl sets fixed_valid behind the proof.  Anything else -- other words, a trace that is still on the host -- is transformed
+  // whole, and d_coef / d_lde then hold the transforms of other words.
+  const bool canonical = !up && P->fixed_match && P->fixed_f1 > P->fixed_f0;
+  if (!canonical) P->fixed_valid = false;
+  run.fills_fixed = canonical && !P->fixed_valid;
+  const size_t keep0 = canonical && P->fixed_valid ? P->fixed_f0 : 0, keep1 = canonical && P->fixed_valid ? P->fixed_f1 : 0;
+  P->fixed_skipped = 0;
   if (S) {
     S->tev_used = 0;
     if (int rc = commit_split(P, S->cs, P->d_trace, true, P->d_coef, S->lde_l, S->lde_n, P->tree_t)) return rc;
-  } else if (int rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, P->air.ncols, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up, P->compact ? P->d_lde : nullptr)) return rc;
+  } else if (int rc = commit_pipeline(P, P->d_trace, P->d_coef, P->d_lde, P->air.ncols, P->tree_t, EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, up, P->compact ? P->d_lde : nullptr,
+                                      keep0, keep1, &P->fixed_skipped)) return rc;
   if (int rc = run.next_stage(ST_PERM_Z)) return rc;
   if (int rc = run.observe_cap(P->tree_t, run.trace_cap, S != nullptr, up != nullptr)) return rc;   // (the scans' word rides back behind the cap)
   if (up && !up->reduce && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
@@ -1576,7 +1637,9 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
       (rc = stage_pow(run)) || (rc = stage_queries(run)))
     return rc;
   for (int i = 0; i < ST_COUNT; i++) HIPC(hipEventElapsedTime(&P->stage_ms[i], P->ev[i], P->ev[i + 1]));
-  return assemble_proof(run, out);
+  if ((rc = assemble_proof(run, out))) return rc;
+  if (run.fills_fixed) P->fixed_valid = true;   // every stage has run and been waited for: d_coef and d_lde hold those transforms
+  return SBN_OK;
 }
 extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_impl(P, out, nullptr); }
 
@@ -1600,6 +1663,7 @@ extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace,
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   P->loaded = false;   // before any check: a refused call must not leave the previous trace provable
+  P->fixed_match = false;   // the upload writes d_trace and compares nothing
   if (!trace) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "sbn_prover_prove_host_trace covers single-GPU provers");
   int rc = check_pi(P, pi, n_pi); if (rc) return rc;
@@ -1612,6 +1676,7 @@ extern "C" int sbn_prover_prove_host_columns(sbn_prover* P, const uint64_t* cons
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   P->loaded = false;
+  P->fixed_match = false;
   if (reduced_out) *reduced_out = 0;
   if (n_columns != P->air.ncols) return fail(SBN_ERR_BAD_ARG, "expected %zu columns, got %zu", P->air.ncols, n_columns);
   if (!columns) return fail(SBN_ERR_BAD_ARG, "null argument");
@@ -1829,6 +1894,40 @@ extern "C" int sbn_reduce_words(uint64_t* words, size_t count, int on_device, ui
   return SBN_OK;
 }
 
+// The shape-constant columns [*first_out, *end_out) of a table (host_common.hpp fixed_columns_range; 0, 0: none).  No device involved.
+extern "C" int sbn_fixed_columns_range(const sbn_air_desc* air, uint32_t* first_out, uint32_t* end_out) {
+  if (!air || !first_out || !end_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  AirShape as;
+  if (!air_shape(air, nullptr, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
+  size_t f0, f1;
+  fixed_columns_range(as, f0, f1);
+  *first_out = (uint32_t)f0; *end_out = (uint32_t)f1;
+  return SBN_OK;
+}
+// The comparison behind sbn_prover_load_trace as a building block (host in, host out): `block` = those columns of a trace of
+// 2^degree_bits rows; *match_out = 1 when every word is the one the generators write, else 0.
+extern "C" int sbn_fixed_columns_check(const sbn_air_desc* air, uint32_t degree_bits, const uint64_t* block, int* match_out) {
+  if (!air || !block || !match_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  *match_out = 0;
+  AirShape as;
+  if (!air_shape(air, nullptr, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
+  size_t f0, f1;
+  fixed_columns_range(as, f0, f1);
+  if (f1 <= f0) return fail(SBN_ERR_UNSUPPORTED, "this table has no shape-constant columns");
+  if (degree_bits > SBN_MAX_LDE_BITS || (exp_rows_per_instance(as.kind) * as.num_io) != ((size_t)1 << degree_bits))
+    return fail(SBN_ERR_BAD_ARG, "the Exp tables need 512*num_io rows (FQ12_EXP_U64: 128*num_io)");
+  if (int rc = use_current_device("no CPU fallback")) return rc;
+  const size_t n = (size_t)1 << degree_bits, words = (f1 - f0) * n;
+  DevWords w;   // d[0]: the mismatch word; the block from d + 2
+  if (int rc = w.alloc(2 + words)) return rc;
+  HIPC(hipMemcpy(w.d + 2, block, words * sizeof(u64), hipMemcpyHostToDevice));
+  if (int rc = launch_fixed_columns_check(w.d + 2, f1 - f0, n, exp_shape(as), (unsigned long long*)w.d, 0)) return rc;
+  unsigned long long mismatch = 1;
+  HIPC(hipMemcpy(&mismatch, w.d, sizeof mismatch, hipMemcpyDeviceToHost));
+  *match_out = mismatch == 0;
+  return SBN_OK;
+}
+
 // The transcript's host permutation (sparse partial rounds) or, with use_definition != 0, the plain round-by-round
 // form it must agree with.  No device involved: this is the Fiat-Shamir hasher of prove() / verify().
 extern "C" int sbn_poseidon_permute_host(uint64_t* states, size_t count, int use_definition) {
@@ -1866,11 +1965,14 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
   char buf[1024];
   snprintf(buf, sizeof buf,
            "abi=%d device=%d dev_bytes=%zu ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d ntt_lde_zero_aware=%d "
-           "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d lde=%s lde_ring=%u lde_ring_bytes=%zu ignored=[%s]",
+           "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d lde=%s lde_ring=%u lde_ring_bytes=%zu "
+           "fixed_columns=%d fixed_columns_range=%zu:%zu fixed_columns_skipped=%zu ignored=[%s]",
            SBN_ABI_VERSION, P->device, P->dev_bytes, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0, P->d_shift_za ? 1 : 0,
            chain, tracegen_host_threads(), (int)s.fq12_host_chain,
            (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, P->lde_storage == SBN_LDE_COMPACT ? "compact" : "full", P->ring_depth,
-           P->d_ring ? (size_t)P->ring_depth * P->ntt_chunk * P->m * sizeof(u64) : (size_t)0, s.ignored.c_str());
+           P->d_ring ? (size_t)P->ring_depth * P->ntt_chunk * P->m * sizeof(u64) : (size_t)0,
+           // the switch; the columns whose transforms this context keeps between proofs (0:0 none); how many the last prove() left untransformed
+           (int)s.fixed_columns, P->fixed_f0, P->fixed_f1, P->fixed_skipped, s.ignored.c_str());
   snprintf(out, cap, "%s", buf);
   return SBN_OK;
 }

@@ -119,6 +119,13 @@ struct sbn_prover {
   u64 *d_qbuf = nullptr; size_t qstride = 0;
   std::vector<u64> pi;
   bool loaded = false;
+  // The shape-constant trace columns [fixed_f0, fixed_f1) of an Exp table (host_common.hpp fixed_columns_range; empty: none, or a
+  // context that never reuses them: the split, compact storage, SBN_FIXED_COLUMNS=0).  Their coefficients and LDE are the same words
+  // in every proof of this context, so stage_trace_commit leaves them where an earlier proof put them:
+  bool fixed_match = false;                  // those columns of the resident d_trace hold the generators' words (every writer of d_trace sets or clears it)
+  bool fixed_valid = false;                  // those columns of d_coef and d_lde hold the transforms of the generators' words (every writer of either keeps or clears it)
+  size_t fixed_f0 = 0, fixed_f1 = 0;
+  size_t fixed_skipped = 0;                  // trace columns the last prove() left untransformed (sbn_prover_describe)
   hipEvent_t ev[ST_COUNT + 1];
   float stage_ms[ST_COUNT + EX_COUNT];
   size_t ntt_chunk;
@@ -178,6 +185,9 @@ void launch_lde_keep_rows(const u64* slot, size_t m, u64* dense, size_t qn, u32 
 // x_q = 7 w_m^bitrev(idx[q]), q < nq, what gather_rows_kernel reads out of a resident LDE.  table: 64 n words of scratch.
 int launch_query_rows(const u64* coef, size_t ncols, size_t n, u32 lde_log, const u64* shift, const u64* tw_f, const u32* d_idx, u32 nq, u64* table,
                       u64* out, size_t qstride, size_t off, hipStream_t s);
+// tracegen_device.hip: *d_mismatch = 0, then 1 unless `block` -- the ncols columns of fixed_columns_range() of a trace of n rows --
+// holds the words the device witness writes there (kernels_tracegen.cuh fixed_columns_check_kernel).  Enqueues on `s`.
+int launch_fixed_columns_check(const u64* block, size_t ncols, size_t n, const ExpShape& sh, unsigned long long* d_mismatch, hipStream_t s);
 // trace_check.hip, shared with trace_explain.hip: the seed-to-challenge transcript of a check and the kernel that fills the tables
 // of the trace domain.
 void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]);

@@ -3,7 +3,7 @@
 // A prover reads the environment once, when it is created (create_ctx -> Settings::load), checks every value and keeps the
 // resolved set for its lifetime (sbn_prover_describe prints it; bench.py copies it into `config`).  Two classes:
 //   * production switches (host thread count, collective timeout, RCCL path, timing print, AVX-512 opt-out, chain placement of
-//     the curve witness) are always honoured;
+//     the curve witness, reuse of the shape-constant columns' transforms) are always honoured;
 //   * EXPERIMENT switches (A/B forms of kernels kept for measurement: every one of them yields the same proof bytes,
 //     profiles/r4_v5_switch_parity.txt) are honoured only when SBN_EXPERIMENTAL=1 is set as well -- a stale export in a
 //     production shell can then not change which kernels run or how long they take; without it they are reported as
@@ -26,6 +26,8 @@ struct Settings {
   bool no_avx512 = false;        // SBN_NO_AVX512: scalar host transcript permutation
   int device_chain = -1;         // SBN_TRACEGEN_DEVICE_CHAIN: -1 auto (host pool with >= 8 threads, else 2), 0 host pool,
                                  //   1 one lane per instance, 2 one wave per instance (tg::chain_coop_kernel)
+  bool fixed_columns = true;     // SBN_FIXED_COLUMNS=0: transform the shape-constant trace columns of an Exp table in every proof, as if
+                                 //   their transforms were never resident (prover.hip stage_trace_commit); the same proof words
   bool experimental = false;     // SBN_EXPERIMENTAL=1
   // ---- experiments (need SBN_EXPERIMENTAL=1) ----
   int ntt_chunk = 0;             // SBN_NTT_CHUNK: columns per commit-pipeline chunk (0 = size-dependent default)
@@ -59,6 +61,7 @@ struct Settings {
     trace_timing = get("SBN_TRACE_TIMING") != nullptr;
     no_avx512 = get("SBN_NO_AVX512") != nullptr;
     x = -1; if (!integer("SBN_TRACEGEN_DEVICE_CHAIN", 0, 2, &x)) return false; device_chain = (int)x;
+    x = 1; if (!integer("SBN_FIXED_COLUMNS", 0, 1, &x)) return false; fixed_columns = x == 1;
     x = 0; if (!integer("SBN_EXPERIMENTAL", 0, 1, &x)) return false; experimental = x == 1;
     static const char* const EXP[] = {"SBN_NTT_CHUNK", "SBN_FQ12_HOST_CHAIN", "SBN_FQ12_ROW_KERNEL", "SBN_RANGE_CHECK", "SBN_QUOTIENT_LOOKUPS"};
     if (!experimental) {

@@ -18,6 +18,16 @@ static int range_check_setup(int device) {
   }
   return 0;
 }
+// The words tg::periodic_kernel and tg::io_pulse_kernel write, compared with `block` = columns fixed_columns_range() of a trace of n
+// rows, on `s`: *d_mismatch (zeroed here, in front of the kernel) becomes 1 at the first other word.  The caller waits and reads it.
+int launch_fixed_columns_check(const u64* block, size_t ncols, size_t n, const ExpShape& sh, unsigned long long* d_mismatch, hipStream_t s) {
+  if (ncols != (size_t)(sh.start_periodic >= 0 ? 4 : 2) + 4 * (size_t)sh.num_io || ncols > 65535) return fail(SBN_ERR_BAD_ARG, "internal: not the shape-constant block of this table");
+  HIPC(hipMemsetAsync(d_mismatch, 0, sizeof *d_mismatch, s));
+  hipLaunchKernelGGL(tg::fixed_columns_check_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)ncols), dim3(256), 0, s, block, n, sh.start_periodic >= 0 ? 1 : 0, (size_t)sh.rpb,
+                     exp_table_max(sh), d_mismatch);
+  HIPC(hipGetLastError());
+  return 0;
+}
 // One step of the curve chains as levels of independent micro-operations for tg::chain_coop_kernel: the formulas of
 // bnw::jac_double / bnw::jac_add (bn254w.cuh) written once over builder values, Fq2 products expanded into four Fq products,
 // every value in a fresh slot (no hazards), level = 1 + the deepest operand.  Program 0: a <- 2a (exponent bit clear);
@@ -189,6 +199,7 @@ struct TraceJob {
   const ExpShape sh;
   u64* const wbase;   // scratch: the LDE buffer, not yet in use
   u64* w;
+  bool common_written = false;   // launch_common_columns ran: the shape-constant columns hold the generators' words (finish)
   struct Mark { hipEvent_t ev; const char* closes; };
   std::vector<Mark> marks;
   TraceJob(sbn_prover* P, size_t K, size_t IOW)
@@ -196,7 +207,14 @@ struct TraceJob {
 
   u64* take(size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; }
   unsigned int* take_histograms() { return n > 65536 ? (unsigned int*)take((size_t)sh.num_rc * 32768) : nullptr; }   // u32 histograms of the range-checked columns
-  int fits() const { return (size_t)(w - wbase) > P->lde_scratch_words ? fail(SBN_ERR_UNSUPPORTED, "scratch does not fit") : 0; }
+  // after the last take().  The scratch is about to be written: resident transforms of the shape-constant columns (prover_ctx.hpp
+  // fixed_valid; d_lde columns [fixed_f0, fixed_f1) of P->m words each) survive only if it ends in front of them.
+  int fits() {
+    const size_t used = (size_t)(w - wbase);
+    if (used > P->lde_scratch_words) return fail(SBN_ERR_UNSUPPORTED, "scratch does not fit");
+    if (P->sp || P->compact || used > P->fixed_f0 * P->m) P->fixed_valid = false;
+    return 0;
+  }
 
   // SBN_TRACE_TIMING: a point on the stream; `closes` names the span that ends here (begin() opens the first one)
   void mark(const char* closes) {
@@ -219,6 +237,7 @@ struct TraceJob {
     hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
     hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, table_max, P->d_trace);
     hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
+    common_written = true;
     mark("flags+pulses");
   }
   // the last launches of the u16 tables, then whatever a launch since begin() left as an error
@@ -257,6 +276,7 @@ struct TraceJob {
     P->pi.resize(P->air.npi);
     for (size_t k = 0; k < K; k++) pi(k, P->pi.data() + (size_t)sh.pi_per_io * k);
     if (pi_out) memcpy(pi_out, P->pi.data(), P->pi.size() * sizeof(u64));
+    P->fixed_match = common_written && P->fixed_f1 > P->fixed_f0;   // by construction: those very kernels wrote the columns
     P->loaded = true;
     return SBN_OK;
   }
@@ -729,6 +749,7 @@ static int fq_trace_explicit(sbn_prover* P, const uint32_t* ios, size_t K, uint6
 static int unload(sbn_prover* P) {
   if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
   P->loaded = false;
+  P->fixed_match = false;
   return 0;
 }
 static bool is_fq12(int kind) { return kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64; }
