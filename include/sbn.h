@@ -202,7 +202,8 @@ int sbn_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint3
 /* Device bytes sbn_prover_create_with allocates at creation (dev_bytes of sbn_prover_describe right after it), computed without a
  * device from the list of buffers the creation itself allocates from; the same argument checks.  Outside the plan, allocated by
  * the first call that needs them: 8 bytes of device memory for the canonical-form scan of sbn_prover_prove_host_trace (its upload
- * ring is pinned host memory, 64 MiB). */
+ * ring is pinned host memory, 64 MiB).  The row-major loads (sbn_prover_load_trace_rows) share that ring and allocate nothing more:
+ * their device staging is carved from the LDE buffer, which is in the plan. */
 int sbn_prover_memory_plan(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_prover_options* opt, uint64_t* bytes_out);
 void sbn_prover_destroy(sbn_prover* p);
 /* Host -> device copy of the trace (PCIe-inclusive path). */
@@ -236,6 +237,61 @@ int sbn_prover_prove_host_trace(sbn_prover* p, const uint64_t* trace_col_major, 
 #define SBN_TRACE_REDUCE 1u   /* flags bit 0: a word >= p is taken mod p on the device instead of refused */
 int sbn_prover_prove_host_columns(sbn_prover* p, const uint64_t* const* columns, size_t n_columns, uint32_t flags,
                                   const uint64_t* public_inputs, size_t n_pi, uint64_t* reduced_out, sbn_proof** out);
+/* ROW-major traces: what the reference's generators hold in front of their `transpose` (src/curves/g1/exp.rs:255-298 and the other
+ * generate_trace functions build `rows` row by row, transpose, and only then append the derived columns).  The library transposes
+ * on the device (csrc/kernels_rows.cuh) and, in main-row mode, writes the derived columns itself.
+ * Exactly one of flat / row_ptrs is set: flat = one allocation, row r at flat[r * row_stride .. + n_cols), row_stride >= n_cols
+ * (`Vec<[F; N]>`: row_stride = N); row_ptrs = one allocation per row, row_ptrs[r][0 .. n_cols) (`Vec<Vec<F>>`; row_stride is
+ * ignored).  8-byte alignment suffices; the memory is only read, and the words between n_cols and row_stride are never read.
+ * n_rows = 2^degree_bits.  n_cols selects the mode:
+ *   whole-row mode, n_cols = the table's column count, any table: the call transposes and checks, nothing else; the shape-constant
+ *     columns are compared as after sbn_prover_load_trace.
+ *   main-row mode, n_cols = sbn_air_num_main_columns, the five Exp tables: the rows hold the main columns only, and the columns
+ *     [num_main, num_columns) -- periodic pulse, io pulses, table column, range-check columns -- are written by the kernels of the
+ *     device witness (host twin: by the code the host generators end with).  G1_EXP / G2_EXP / FQ_EXP on the device: 2^16 .. 2^18
+ *     rows, as sbn_prover_generate_trace; beyond, sbn_trace_from_rows_host followed by sbn_prover_load_trace.  FQ12_EXP,
+ *     FQ12_EXP_U64: any size.
+ * flags: 0 or SBN_TRACE_REDUCE, as for sbn_prover_prove_host_columns (words and public inputs >= p are taken mod p; *reduced_out,
+ * optional, receives the number of trace words changed).
+ * Refused in this order, before any device work where a device is involved:
+ *   1. a null argument or struct_size != sizeof the struct; 2. both or neither of flat / row_ptrs; 3. n_rows != 2^degree_bits (the
+ *   calls without a prover: no power of two, or not the height the table's num_io fixes); 4. n_cols neither of the two counts, or
+ *   row_stride < n_cols; 5. flat or a row pointer null or not 8-byte aligned (the message names the row); 6. an unknown flag bit
+ *   -- all SBN_ERR_BAD_ARG; 7. the public-input checks of sbn_prover_load_trace; 8. main-row mode on a table or height it does not
+ *   cover (the main-column count of another table included): SBN_ERR_UNSUPPORTED; 9. a split prover: SBN_ERR_UNSUPPORTED.
+ * Data errors are found on the device, inside the transposition: a word >= p without the reduce flag gives SBN_ERR_NON_CANONICAL,
+ * "... row r, column c ..." being the first such word in row-major order; in main-row mode a word >= 2^16 (after the reduction)
+ * in a range-checked main column gives SBN_ERR_WITNESS, named the same way.  A failing call leaves NO trace loaded, the streams
+ * idle and the ring free. */
+typedef struct sbn_host_rows {
+  uint32_t struct_size, reserved;
+  const uint64_t* flat; size_t row_stride;
+  const uint64_t* const* row_ptrs;
+  size_t n_rows, n_cols;
+} sbn_host_rows;
+/* Columns of a row in front of the reference's `transpose`: G1_EXP 398, G2_EXP 782, FQ_EXP 158, FQ12_EXP 1742, FQ12_EXP_U64 1734
+ * (num_io does not enter); 0 for a table that is no Exp table. */
+size_t sbn_air_num_main_columns(const sbn_air_desc* air);
+/* Both modes on the host pool (SBN_HOST_THREADS), no device: trace_col_major_out[num_columns][n_rows] is the trace a prover would
+ * hold after sbn_prover_load_trace_rows.  The no-GPU fallback and the CPU-testable twin.  There are no public inputs here, so refusal
+ * 7 does not apply; main-row mode of the u16 tables takes any height from 2^16 rows. */
+int sbn_trace_from_rows_host(const sbn_air_desc* air, const sbn_host_rows* rows, uint32_t flags, uint64_t* trace_col_major_out, uint64_t* reduced_out);
+/* Rows in host memory -> the prover's trace buffer: pieces of whole rows cross PCIe through the pinned ring and the copy stream of
+ * sbn_prover_prove_host_trace, packed to n_cols words per row, and piece k + 1 is copied and sent while piece k is transposed.
+ * Afterwards the prover is loaded exactly as after sbn_prover_load_trace: sbn_prover_read_trace returns the full column-major
+ * trace, sbn_prover_prove, sbn_prover_check_trace and sbn_prover_explain_rows work.  The staging of the pieces in flight and the
+ * scratch of the derived columns are carved from the context's LDE buffer (resident transforms of the shape-constant columns are
+ * dropped when the carving reaches them), so the call allocates no device memory beyond the 8 bytes and the pinned ring named at
+ * sbn_prover_memory_plan. */
+int sbn_prover_load_trace_rows(sbn_prover* p, const sbn_host_rows* rows, uint32_t flags, const uint64_t* public_inputs, size_t n_pi, uint64_t* reduced_out);
+/* The same for rows already in HBM (a caller's own row-generating kernel): row r at d_rows + r * row_stride, 2^degree_bits rows.
+ * The same transposition kernel, no PCIe traffic.  d_rows must not overlap the prover's buffers. */
+int sbn_prover_load_trace_rows_device(sbn_prover* p, const uint64_t* d_rows, size_t row_stride, size_t n_cols, uint32_t flags,
+                                      const uint64_t* public_inputs, size_t n_pi, uint64_t* reduced_out);
+/* sbn_prover_load_trace_rows followed by sbn_prover_prove in one call (the commitment cannot start before the last row is in, so
+ * this is load, then the ordinary proof, not the streaming commitment of sbn_prover_prove_host_trace). */
+int sbn_prover_prove_host_rows(sbn_prover* p, const sbn_host_rows* rows, uint32_t flags, const uint64_t* public_inputs, size_t n_pi,
+                               uint64_t* reduced_out, sbn_proof** out);
 /* Per-stage device times (ms, HIP events on the prover's stream) of the last prove():
  * names via sbn_prover_stage_name(i); returns the number of stages written. */
 int sbn_prover_stage_times(const sbn_prover* p, float* ms_out, int cap);
@@ -417,6 +473,10 @@ int sbn_prove(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* tr
 /* sbn_prove with the argument list of sbn_prover_prove_host_columns: the same context cache, key and statistics. */
 int sbn_prove_columns(const sbn_air_desc* air, const sbn_config* cfg, const uint64_t* const* columns, size_t n_columns,
                       uint32_t degree_bits, uint32_t flags, const uint64_t* public_inputs, size_t n_pi, sbn_proof** out);
+/* sbn_prove for a row-major trace (sbn_prover_prove_host_rows; degree_bits = log2 of rows->n_rows): the same cache, key and
+ * statistics.  The refusals 1 .. 8 of the list at sbn_host_rows run before a device is looked for. */
+int sbn_prove_rows(const sbn_air_desc* air, const sbn_config* cfg, const sbn_host_rows* rows, uint32_t flags, const uint64_t* public_inputs,
+                   size_t n_pi, sbn_proof** out);
 
 /* sbn_prove keeps the device contexts it creates, keyed by (device, kind, num_io, degree_bits, every sbn_config field),
  * up to budget_bytes of device memory, least recently used evicted first.  0 (the default) = create and destroy per

@@ -53,6 +53,7 @@ EXPORTS = [
     "sbn_prover_create_with", "sbn_batch_prover_create_with", "sbn_prover_memory_plan", "sbn_lde_rows",
     "sbn_prover_prove_host_columns", "sbn_prove_columns", "sbn_batch_prover_prove_host_columns", "sbn_gather_columns", "sbn_reduce_words",
     "sbn_fixed_columns_range", "sbn_fixed_columns_check",
+    "sbn_air_num_main_columns", "sbn_trace_from_rows_host", "sbn_prover_load_trace_rows", "sbn_prover_load_trace_rows_device", "sbn_prover_prove_host_rows", "sbn_prove_rows",
 ]
 
 
@@ -96,6 +97,12 @@ def _prover_options(lde):
 
 def _opt_ref(opt):
     return C.byref(opt) if opt is not None else None
+
+
+class _HostRows(C.Structure):
+    """sbn_host_rows (include/sbn.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("flat", C.c_void_p), ("row_stride", C.c_size_t), ("row_ptrs", C.c_void_p),
+                ("n_rows", C.c_size_t), ("n_cols", C.c_size_t)]
 
 
 class _TraceReport(C.Structure):
@@ -254,6 +261,14 @@ def lib():
         if hasattr(L, "sbn_fixed_columns_range"):   # (a library named by SBN_LIB may predate them)
             L.sbn_fixed_columns_range.argtypes = [vp, vp, vp]
             L.sbn_fixed_columns_check.argtypes = [vp, C.c_uint32, vp, vp]
+        if hasattr(L, "sbn_prover_load_trace_rows"):   # (a library named by SBN_LIB may predate the row-major calls)
+            L.sbn_air_num_main_columns.restype = sz
+            L.sbn_air_num_main_columns.argtypes = [C.POINTER(_AirDesc)]
+            L.sbn_trace_from_rows_host.argtypes = [C.POINTER(_AirDesc), C.POINTER(_HostRows), u32, vp, vp]
+            L.sbn_prover_load_trace_rows.argtypes = [vp, C.POINTER(_HostRows), u32, vp, sz, vp]
+            L.sbn_prover_load_trace_rows_device.argtypes = [vp, vp, sz, sz, u32, vp, sz, vp]
+            L.sbn_prover_prove_host_rows.argtypes = [vp, C.POINTER(_HostRows), u32, vp, sz, vp, C.POINTER(vp)]
+            L.sbn_prove_rows.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), C.POINTER(_HostRows), u32, vp, sz, C.POINTER(vp)]
         _LIB = L
     return _LIB
 
@@ -313,6 +328,12 @@ class _Stark:
     @property
     def num_public_inputs(self):
         return lib().sbn_air_num_public_inputs(C.byref(self._d))
+
+    @property
+    def num_main_columns(self):
+        """Columns of a row in front of the reference's `transpose` (sbn_air_num_main_columns): what main-row mode of the row-major
+        calls takes; 0 for a table that is no Exp table."""
+        return lib().sbn_air_num_main_columns(C.byref(self._d))
 
     def num_permutation_zs(self, config=None):
         config = config or StarkConfig()
@@ -1240,6 +1261,56 @@ def reduce_words(words, on_device=True):
     return int(out.value)
 
 
+class RowTable:
+    """The sbn_host_rows of a ROW-major trace: a 2-D uint64 array whose rows are contiguous, with any stride between rows that is a
+    non-negative multiple of 8 bytes and at least a row (big[:, :398] of a wider matrix: the flat form), or a sequence of 1-D
+    uint64 arrays of one length (the pointer form, the reference's Vec<Vec<F>>).  Nothing is copied, and the table keeps the
+    references that keep the memory alive.  The row-major calls take a RowTable wherever they take rows."""
+
+    def __init__(self, rows):
+        r = _HostRows(struct_size=C.sizeof(_HostRows))
+        if isinstance(rows, np.ndarray) and rows.ndim == 2:
+            a = rows
+            if a.dtype != _U64 or (a.shape[1] > 1 and a.strides[1] != 8):
+                raise SbnError(-1, "rows must be uint64 with contiguous rows")
+            if a.shape[0] > 1 and (a.strides[0] % 8 or a.strides[0] < 8 * a.shape[1]):
+                raise SbnError(-1, "the row stride must be a multiple of 8 bytes and at least a row")
+            r.flat, r.row_stride = a.ctypes.data, (a.strides[0] // 8 if a.shape[0] > 1 else a.shape[1])
+            r.n_rows, r.n_cols = a.shape
+            self._keep = [a]
+        else:
+            keep = list(rows)
+            n_cols = len(keep[0]) if keep and isinstance(keep[0], np.ndarray) and keep[0].ndim == 1 else 0
+            addr = np.empty(len(keep), dtype=np.uint64)
+            for i, a in enumerate(keep):
+                if type(a) is not np.ndarray or (a.dtype is not _U64 and a.dtype != _U64) or a.shape != (n_cols,) or (n_cols > 1 and a.strides[0] != 8):
+                    raise SbnError(-1, f"row {i} must be a contiguous 1-D uint64 array of the first row's length")
+                addr[i] = a.__array_interface__["data"][0]
+            r.row_ptrs, r.n_rows, r.n_cols = addr.ctypes.data, len(keep), n_cols
+            self._keep = [keep, addr]
+        self.raw = r
+
+    @property
+    def shape(self):
+        return (self.raw.n_rows, self.raw.n_cols)
+
+
+def _row_table(rows):
+    return rows if isinstance(rows, RowTable) else RowTable(rows)
+
+
+def trace_from_rows_host(stark, rows, reduce=False):
+    """The column-major trace of a row-major one, on host threads (sbn_trace_from_rows_host; no device): `rows` as RowTable takes
+    them, num_columns wide (whole-row mode: transposed and checked) or num_main_columns wide (main-row mode, the five Exp tables:
+    the derived columns are appended as the host generators do).  reduce=True: words >= p are taken mod p instead of refused, and
+    (trace, number of words changed) is returned."""
+    t = _row_table(rows)
+    out = np.zeros((stark.num_columns, t.raw.n_rows), dtype=np.uint64)
+    reduced = C.c_uint64(0)
+    _check(lib().sbn_trace_from_rows_host(C.byref(stark._d), C.byref(t.raw), TRACE_REDUCE if reduce else 0, _ptr(out), C.byref(reduced)))
+    return (out, int(reduced.value)) if reduce else out
+
+
 def explain_rows_host(stark, trace, public_inputs, rows, seed=0):
     """Which constraint blocks and Z columns the listed rows of `trace` break, on host threads (sbn_explain_rows_host).  The
     same RowsExplanation, for the same seed, as Prover.explain_rows gives for the loaded trace."""
@@ -1403,6 +1474,33 @@ class Prover:
         pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
         h, reduced = C.c_void_p(), C.c_uint64(0)
         _check(lib().sbn_prover_prove_host_columns(self._h, _ptr(t.addr), len(t), TRACE_REDUCE if reduce else 0, _ptr(pi), len(pi), C.byref(reduced), C.byref(h)))
+        proof = _take_proof(h)
+        return (proof, int(reduced.value)) if reduce else proof
+
+    def load_trace_rows(self, rows, public_inputs, reduce=False):
+        """load_trace for a ROW-major trace (sbn_prover_load_trace_rows): `rows` as RowTable takes them, num_columns wide, or
+        num_main_columns wide on the Exp tables (the device then writes the derived columns itself).  The transposition and the
+        canonical-form check run on the device.  reduce=True returns the number of trace words taken mod p."""
+        t = _row_table(rows)
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        reduced = C.c_uint64(0)
+        _check(lib().sbn_prover_load_trace_rows(self._h, C.byref(t.raw), TRACE_REDUCE if reduce else 0, _ptr(pi), len(pi), C.byref(reduced)))
+        return int(reduced.value) if reduce else None
+
+    def load_trace_rows_device(self, device_ptr, row_stride, n_cols, public_inputs, reduce=False):
+        """The same for rows already in device memory (sbn_prover_load_trace_rows_device): row r at device_ptr + 8 * r * row_stride."""
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        reduced = C.c_uint64(0)
+        _check(lib().sbn_prover_load_trace_rows_device(self._h, C.c_void_p(device_ptr), row_stride, n_cols, TRACE_REDUCE if reduce else 0, _ptr(pi), len(pi),
+                                                       C.byref(reduced)))
+        return int(reduced.value) if reduce else None
+
+    def prove_host_rows(self, rows, public_inputs, reduce=False):
+        """load_trace_rows + prove in one call (sbn_prover_prove_host_rows).  reduce=True returns (Proof, words changed)."""
+        t = _row_table(rows)
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        h, reduced = C.c_void_p(), C.c_uint64(0)
+        _check(lib().sbn_prover_prove_host_rows(self._h, C.byref(t.raw), TRACE_REDUCE if reduce else 0, _ptr(pi), len(pi), C.byref(reduced), C.byref(h)))
         proof = _take_proof(h)
         return (proof, int(reduced.value)) if reduce else proof
 
@@ -1577,6 +1675,15 @@ def prove_columns(stark, config, columns, public_inputs, reduce=False):
     h = C.c_void_p()
     _check(lib().sbn_prove_columns(C.byref(stark._d), C.byref(config._c), _ptr(t.addr), len(t), n.bit_length() - 1, TRACE_REDUCE if reduce else 0,
                                    _ptr(pi), len(pi), C.byref(h)))
+    return _take_proof(h)
+
+
+def prove_rows(stark, config, rows, public_inputs, reduce=False):
+    """prove() for a ROW-major trace (Prover.load_trace_rows says which forms and widths), through the same context cache."""
+    t = _row_table(rows)
+    pi = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    h = C.c_void_p()
+    _check(lib().sbn_prove_rows(C.byref(stark._d), C.byref(config._c), C.byref(t.raw), TRACE_REDUCE if reduce else 0, _ptr(pi), len(pi), C.byref(h)))
     return _take_proof(h)
 
 

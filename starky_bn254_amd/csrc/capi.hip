@@ -161,6 +161,15 @@ int sbn_prove_columns(const sbn_air_desc* air, const sbn_config* cfg, const uint
                       const uint64_t* pi, size_t n_pi, sbn_proof** out) {
   return prove_one_shot(air, cfg, degree_bits, out, [&](sbn_prover* P) { return sbn_prover_prove_host_columns(P, columns, n_columns, flags, pi, n_pi, nullptr, out); });
 }
+// sbn_prove for a row-major trace (sbn_prover_prove_host_rows): the same cache, key and statistics; the refusals that need no prover
+// run first, so a bad call never creates a context (or looks for a device)
+int sbn_prove_rows(const sbn_air_desc* air, const sbn_config* cfg, const sbn_host_rows* rows, uint32_t flags, const uint64_t* pi, size_t n_pi, sbn_proof** out) {
+  if (out) *out = nullptr;
+  if (!air || !cfg || !rows || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  uint32_t degree_bits = 0;
+  if (int rc = host_rows_precheck(air, rows, flags, pi, n_pi, &degree_bits)) return rc;
+  return prove_one_shot(air, cfg, degree_bits, out, [&](sbn_prover* P) { return sbn_prover_prove_host_rows(P, rows, flags, pi, n_pi, nullptr, out); });
+}
 
 // ---- batch mode (BASELINE config[2]: a batch of independent proofs per GPU) -------------------------------------------
 // `inflight` prover contexts on the current GPU, one host thread each; every unit = one instance list of the table,

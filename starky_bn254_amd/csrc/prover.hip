@@ -296,7 +296,7 @@ static int tree_from_matrix(sbn_prover* P, DevTree& t, const u64* lde, size_t nc
 // the caller's trace; done[k]: chunk k is resident and scanned; reduce (SBN_TRACE_REDUCE): reduce_words_kernel takes the scan's
 // place, and d_first_bad counts the words it changed instead of holding the first one refused
 struct HostUpload { HostColumns src; hipEvent_t* done; bool reduce; };
-static int upload_setup(sbn_prover* P) {   // idempotent: a call that failed half way is completed by the next one
+int upload_setup(sbn_prover* P) {   // idempotent: a call that failed half way is completed by the next one
   if (!P->ustream) HIPC(hipStreamCreate(&P->ustream));
   for (auto& e : P->upload_done) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : P->slot_copied) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -944,7 +944,7 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   delete P;
 }
 
-static int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi) {
+int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi) {
   if (n_pi != P->air.npi) return fail(SBN_ERR_BAD_ARG, "expected %zu public inputs, got %zu", P->air.npi, n_pi);
   if (n_pi && !pi) return fail(SBN_ERR_BAD_ARG, "null public inputs");
   for (size_t i = 0; i < n_pi; i++) if (pi[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "public input %zu is not canonical", i);
@@ -954,7 +954,7 @@ static int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi) {
 // Behind a copy into d_trace: do its shape-constant columns hold the generators' words (P->fixed_match)?  The caller owns the trace,
 // and a valid witness may hold other words there, so the device compares: one launch over (fixed_f1 - fixed_f0) n words and one
 // word back.  The mismatch word borrows the start of d_tmp, which only prove() and the checks use, none of them in flight here.
-static int fixed_columns_check(sbn_prover* P) {
+int fixed_columns_check(sbn_prover* P) {
   P->fixed_match = false;
   if (P->fixed_f1 <= P->fixed_f0) return 0;
   unsigned long long* d_word = (unsigned long long*)P->d_tmp;

@@ -1,5 +1,5 @@
 // The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
-// tracegen_device.hip (which fills the trace), by trace_check.hip, trace_explain.hip and trace_explain_fq12.hip (which check it)
+// tracegen_device.hip and trace_rows.hip (which fill the trace), by trace_check.hip, trace_explain.hip and trace_explain_fq12.hip (which check it)
 // and by lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of
 // include/sbn.h.
 #pragma once
@@ -29,6 +29,11 @@ static constexpr int MAX_CHUNKS = 512;
 // the first call.  A piece of the trace never spans two column chunks; a chunk larger than a slot crosses in several pieces.
 static constexpr int UPLOAD_SLOTS = 4;
 static constexpr size_t UPLOAD_SLOT_WORDS = (size_t)2 << 20;
+// A row-major load (trace_rows.hip) has no column chunks and borrows four of their events for its two staging buffers: the copy into
+// buffer b has landed (copy stream), the transposition has left buffer b (main stream).  Both paths drain their streams before they
+// return, so neither ever sees an event the other recorded.
+static constexpr int ROWS_EV_COPIED = 0, ROWS_EV_TRANSPOSED = 2;
+static_assert(MAX_CHUNKS >= ROWS_EV_TRANSPOSED + 2, "a row-major load borrows upload_done[0 .. 4)");
 // Function attributes are per DEVICE: one flag per device of the process (sbn_set_device may select another GPU later).
 static constexpr int SBN_MAX_DEVICES = 64;
 // Compact LDE storage (include/sbn.h SBN_LDE_COMPACT): slots of the LDE chunk ring at most; create_ctx picks LDE_RING_DEPTH
@@ -156,7 +161,7 @@ struct sbn_prover {
   size_t dev_bytes = 0;                      // their bytes (what sbn_prover_memory_plan predicts and the one-shot cache of capi.hip counts)
   // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
   hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk
-  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned
+  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned (a row-major load, trace_rows.hip, borrows [0 .. 4): ROWS_EV_*)
   hipEvent_t slot_copied[UPLOAD_SLOTS];      // copy stream: the copy out of ring slot s has completed
   bool slot_used[UPLOAD_SLOTS] = {};
   unsigned slot_next = 0;
@@ -165,6 +170,24 @@ struct sbn_prover {
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
   float check_ms[4] = {};                    // sbn_prover_check_trace: permutation Z, constraint kernels, reduction, download
   float explain_ms[3] = {};                  // sbn_prover_explain_*: permutation Z, explain kernels, reduction / download
+};
+
+// Scratch of the calls that fill d_trace (the device witness generators of tracegen_device.hip, the row-major loads of
+// trace_rows.hip), carved from the front of the LDE buffer, which is not in use between proofs (a split prover: its receive buffer).
+struct LdeScratch {
+  sbn_prover* const P;
+  u64* const wbase;
+  u64* w;
+  explicit LdeScratch(sbn_prover* P) : P(P), wbase(P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde), w(wbase) {}
+  u64* take(size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; }
+  // after the last take().  The scratch is about to be written: resident transforms of the shape-constant columns (fixed_valid;
+  // d_lde columns [fixed_f0, fixed_f1) of P->m words each) survive only if it ends in front of them.
+  int fits() {
+    const size_t used = (size_t)(w - wbase);
+    if (!wbase || used > P->lde_scratch_words) return fail(SBN_ERR_UNSUPPORTED, "scratch does not fit");
+    if (P->sp || P->compact || used > P->fixed_f0 * P->m) P->fixed_valid = false;
+    return 0;
+  }
 };
 
 // prover.hip, shared with trace_check.hip: the pieces of the permutation and quotient stages that the trace check runs on the
@@ -188,6 +211,19 @@ int launch_query_rows(const u64* coef, size_t ncols, size_t n, u32 lde_log, cons
 // tracegen_device.hip: *d_mismatch = 0, then 1 unless `block` -- the ncols columns of fixed_columns_range() of a trace of n rows --
 // holds the words the device witness writes there (kernels_tracegen.cuh fixed_columns_check_kernel).  Enqueues on `s`.
 int launch_fixed_columns_check(const u64* block, size_t ncols, size_t n, const ExpShape& sh, unsigned long long* d_mismatch, hipStream_t s);
+// prover.hip, shared with trace_rows.hip (the row-major loads): the copy stream, the pinned ring and their events, created on first
+// use; the public-input checks of load_trace (P->pi on success); and, behind a copy into d_trace, the comparison of its
+// shape-constant columns with the generators' words (P->fixed_match; waits for P->stream).
+int upload_setup(sbn_prover* P);
+int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi);
+int fixed_columns_check(sbn_prover* P);
+// tracegen_device.hip: the columns [num_main, num_columns) of an Exp table from the main columns resident in d_trace, by the
+// kernels of the device witness (periodic pulse, io pulses, table column, then the table's range-check launches) on P->stream;
+// waits, and on success leaves the prover loaded with fixed_match set.  The caller has made sure that no range-checked main
+// column holds a word >= 2^16 (the range-check kernels index LDS by the value) and that the table and height are covered
+// (derived_columns_covered: SBN_OK, or SBN_ERR_UNSUPPORTED with the message).
+int derived_columns_covered(const AirShape& as, size_t n);
+int launch_derived_columns(sbn_prover* P);
 // trace_check.hip, shared with trace_explain.hip: the seed-to-challenge transcript of a check and the kernel that fills the tables
 // of the trace domain.
 void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]);

@@ -212,6 +212,29 @@ static bool fill_split_range_check(uint64_t* trace, size_t n, int table_col, int
   return !bad;
 }
 
+// u16 range check (range_check.rs:20-47): table 0..65535 then 65535; per target column its sorted column and permuted table
+static bool fill_u16_range_check(uint64_t* trace, size_t n, const ExpShape& sh) {
+  auto col = [&](int c) { return trace + (size_t)c * n; };
+  std::atomic<int> bad(0);
+  u64* table = col(sh.start_lookups);
+  for (size_t i = 0; i < n; i++) table[i] = i < 65536 ? i : 65535;
+  parallel_for((size_t)sh.num_rc, [&](size_t k) {
+    const u64* c = col(sh.rc_start + (int)k);
+    for (size_t i = 0; i < n; i++) if (c[i] >= 65536) { bad = 1; return; }
+    permuted_cols_u(c, n, 65536, col(sh.start_lookups + 1 + 2 * (int)k), col(sh.start_lookups + 2 + 2 * (int)k));
+  });
+  return !bad;
+}
+// The columns [num_main, num_columns) of an Exp table from its main columns, as every host generator below ends: the pulses, then
+// the table's range check (sbn_trace_from_rows_host, trace_rows.hip: the main columns came from the caller's rows).  false: a
+// range-checked column holds a word >= 2^16.
+namespace sbn {
+bool derived_columns_host(const ExpShape& sh, uint64_t* trace, size_t n) {
+  fill_pulses(trace, n, sh);
+  return sh.split_rc ? fill_split_range_check(trace, n, sh.start_lookups, sh.rc_start, sh.num_rc) : fill_u16_range_check(trace, n, sh);
+}
+}  // namespace sbn
+
 // Both curve chains of every instance on host threads (the sequential 0.1% of witness generation; the device does the
 // rest, see sbn_prover_generate_trace).  ja / jb: [K][257][3][E][4] u64 (bn254w.cuh jac_at).
 namespace sbn {
@@ -370,16 +393,7 @@ static int generate_exp_trace(const uint32_t* ios, size_t num_io, uint64_t* trac
   fill_pulses(trace, n, sh);
   tm.lap("pulses");
   // --- u16 range check (range_check.rs:20-47)
-  {
-    u64* table = col(sh.start_lookups);
-    for (size_t i = 0; i < n; i++) table[i] = i < 65536 ? i : 65535;
-    parallel_for((size_t)sh.num_rc, [&](size_t k) {
-      const u64* c = col((int)k);
-      for (size_t i = 0; i < n; i++) if (c[i] >= 65536) { bad = 1; return; }
-      permuted_cols_u(c, n, 65536, col(sh.start_lookups + 1 + 2 * (int)k), col(sh.start_lookups + 2 + 2 * (int)k));
-    });
-    if (bad) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
-  }
+  if (!fill_u16_range_check(trace, n, sh)) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
   tm.lap("range check");
   return SBN_OK;
 }
@@ -668,16 +682,7 @@ extern "C" int sbn_generate_trace_fq_exp(const uint32_t* ios, size_t num_io, uin
   });
   if (bad) return fail(SBN_ERR_WITNESS, "modular witness generation failed");
   fill_pulses(trace, n, sh);
-  {
-    u64* table = col(sh.start_lookups);
-    for (size_t i = 0; i < n; i++) table[i] = i < 65536 ? i : 65535;
-    parallel_for((size_t)sh.num_rc, [&](size_t k) {
-      const u64* c = col((int)k);
-      for (size_t i = 0; i < n; i++) if (c[i] >= 65536) { bad = 1; return; }
-      permuted_cols_u(c, n, 65536, col(sh.start_lookups + 1 + 2 * (int)k), col(sh.start_lookups + 2 + 2 * (int)k));
-    });
-    if (bad) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
-  }
+  if (!fill_u16_range_check(trace, n, sh)) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
   return SBN_OK;
 }
 

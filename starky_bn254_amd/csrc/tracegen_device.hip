@@ -192,29 +192,16 @@ static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, siz
 // The two jobs below add the buffers and the stages of their tables.  A stage launches what it always launched and never asks
 // which list source called it; one driver per source calls the stages top to bottom, carves what only its source needs behind
 // the shared buffers (which so stay where they were) and owns its staging layout, its output copies and its error naming.
-struct TraceJob {
-  sbn_prover* const P;
+struct TraceJob : LdeScratch {   // (the scratch carver: prover_ctx.hpp; the LDE buffer is not yet in use)
   const size_t K, IOW, n;   // K instances of IOW u32 words each
   const hipStream_t st;
   const ExpShape sh;
-  u64* const wbase;   // scratch: the LDE buffer, not yet in use
-  u64* w;
   bool common_written = false;   // launch_common_columns ran: the shape-constant columns hold the generators' words (finish)
   struct Mark { hipEvent_t ev; const char* closes; };
   std::vector<Mark> marks;
-  TraceJob(sbn_prover* P, size_t K, size_t IOW)
-      : P(P), K(K), IOW(IOW), n(P->n), st(P->stream), sh(exp_shape(P->air)), wbase(P->sp ? (u64*)P->sp->comm.recv_buf : P->d_lde), w(wbase) {}
+  TraceJob(sbn_prover* P, size_t K, size_t IOW) : LdeScratch(P), K(K), IOW(IOW), n(P->n), st(P->stream), sh(exp_shape(P->air)) {}
 
-  u64* take(size_t words) { u64* r = w; w += (words + 7) & ~(size_t)7; return r; }
   unsigned int* take_histograms() { return n > 65536 ? (unsigned int*)take((size_t)sh.num_rc * 32768) : nullptr; }   // u32 histograms of the range-checked columns
-  // after the last take().  The scratch is about to be written: resident transforms of the shape-constant columns (prover_ctx.hpp
-  // fixed_valid; d_lde columns [fixed_f0, fixed_f1) of P->m words each) survive only if it ends in front of them.
-  int fits() {
-    const size_t used = (size_t)(w - wbase);
-    if (used > P->lde_scratch_words) return fail(SBN_ERR_UNSUPPORTED, "scratch does not fit");
-    if (P->sp || P->compact || used > P->fixed_f0 * P->m) P->fixed_valid = false;
-    return 0;
-  }
 
   // SBN_TRACE_TIMING: a point on the stream; `closes` names the span that ends here (begin() opens the first one)
   void mark(const char* closes) {
@@ -234,11 +221,16 @@ struct TraceJob {
   template <typename FlagsKernel>
   void launch_common_columns(FlagsKernel flags, const uint32_t* d_ios, u64* inv, u64 table_max) {
     hipLaunchKernelGGL(flags, blocks(n, 256), dim3(256), 0, st, d_ios, IOW, n, sh.start_flags, P->d_trace);
+    launch_shape_columns(inv, table_max);
+    mark("flags+pulses");
+  }
+  // their part that reads no instance list: the inverse table, the periodic pulse, the io-pulse counter and pairs, the table column
+  // (launch_derived_columns runs it alone: the flags of a row-major load are the caller's)
+  void launch_shape_columns(u64* inv, u64 table_max) {
     hipLaunchKernelGGL(tg::small_inverse_kernel, blocks(n, 256), dim3(256), 0, st, inv, n);
     hipLaunchKernelGGL(tg::periodic_kernel, blocks(n, 256), dim3(256), 0, st, inv, n, sh.start_periodic, sh.start_io_pulses, sh.start_lookups, table_max, P->d_trace);
     hipLaunchKernelGGL(tg::io_pulse_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)(2 * K)), dim3(256), 0, st, inv, n, (size_t)sh.rpb, sh.witness_col(0), P->d_trace);
     common_written = true;
-    mark("flags+pulses");
   }
   // the last launches of the u16 tables, then whatever a launch since begin() left as an error
   int launch_u16_range_check(unsigned int* d_cnt, int* d_err) {
@@ -773,6 +765,44 @@ static int trace_from_host_list(sbn_prover* P, size_t num_io, uint64_t* pi_out, 
   const int rc = sbn_prover_generate_trace(P, ios.data(), num_io, pi_out);
   if (rc == SBN_OK && ios_out) memcpy(ios_out, ios.data(), ios.size() * sizeof(uint32_t));
   return rc;
+}
+
+// ---- the derived columns of a row-major load (trace_rows.hip; include/sbn.h sbn_prover_load_trace_rows, main-row mode) --------------
+// The main columns [0, num_main) are resident; everything behind them is a function of those and of the shape, written by the
+// kernels the generators above end with.  The same gate as trace_gate: the u16 tables at 2^16 .. 2^18 rows, the Fq12 kinds at any.
+int derived_columns_covered(const AirShape& as, size_t n) {
+  if (!is_exp_air(as.kind)) return fail(SBN_ERR_UNSUPPORTED, "main-row mode covers the five Exp tables (hand in whole rows)");
+  if (!is_fq12(as.kind) && (n < 65536 || n > 262144))
+    return fail(SBN_ERR_UNSUPPORTED, "main-row mode of the u16-range-check tables covers 2^16 .. 2^18 rows on the device (use sbn_trace_from_rows_host + sbn_prover_load_trace)");
+  return 0;
+}
+int launch_derived_columns(sbn_prover* P) {
+  if (int rc = derived_columns_covered(P->air, P->n)) return rc;
+  if (P->n != exp_rows_per_instance(P->air.kind) * P->air.num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
+  HIPC(hipSetDevice(P->device));
+  TraceJob J(P, P->air.num_io, 0);
+  u64* inv = J.take(J.n);
+  int* d_err = (int*)J.take(1);
+  unsigned int* d_cnt = J.sh.split_rc ? nullptr : J.take_histograms();   // carved exactly as the generators of the u16 tables do
+  if (int rc = J.fits()) return rc;
+  if (!J.sh.split_rc) if (int rc = range_check_setup(P->device)) return rc;
+  HIPC(hipEventRecord(P->abs_ev[0], J.st));
+  HIPC(hipMemsetAsync(d_err, 0, sizeof(int), J.st));
+  J.mark(nullptr);
+  J.launch_shape_columns(inv, exp_table_max(J.sh));
+  J.mark("pulses");
+  if (J.sh.split_rc) {
+    hipLaunchKernelGGL(tg::split_range_check_kernel, dim3((unsigned)J.sh.num_rc), dim3(256), 0, J.st, P->d_trace, J.n, J.sh.rc_start, J.sh.start_lookups, d_err);
+    J.mark("range_check");
+    HIPC(hipGetLastError());
+  } else if (int rc = J.launch_u16_range_check(d_cnt, d_err)) return rc;
+  int err = 0;
+  HIPC(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, J.st));
+  if (int rc = J.end()) return rc;
+  if (err & tg::TG_ERR_RANGE) return fail(SBN_ERR_WITNESS, "range-checked column holds a value >= 2^16");
+  P->fixed_match = P->fixed_f1 > P->fixed_f0;   // by construction, as TraceJob::finish: those very kernels wrote the columns
+  P->loaded = true;
+  return SBN_OK;
 }
 
 extern "C" int sbn_prover_generate_trace(sbn_prover* P, const uint32_t* ios, size_t num_io, uint64_t* pi_out) {
