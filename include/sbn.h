@@ -228,7 +228,7 @@ int sbn_prover_prove_host_trace(sbn_prover* p, const uint64_t* trace_col_major, 
  * flags = 0: exactly the call above on the flattened matrix -- same proof words, same refusal, same message ("trace word %zu is
  * not canonical" with the index c * n + row, smallest first).
  * flags = SBN_TRACE_REDUCE: the words may be any 64-bit representatives.  A trace word >= p becomes w - p on the device, behind the
- * upload, where the scan would have run (csrc/kernels.cuh reduce_words_kernel; one subtraction suffices, 2^64 - 1 - p < p), and
+ * upload, where the scan would have run (csrc/kernels_load.cuh reduce_words_kernel; one subtraction suffices, 2^64 - 1 - p < p), and
  * public inputs >= p are reduced on the host.  *reduced_out (optional) receives the number of trace words changed (0 without the
  * flag).  Afterwards the trace is resident in canonical form: read_trace returns the reduced words.
  * Refused before any device work, in this order: p or out null, n_columns other than the table's column count, columns[c] null or
@@ -239,7 +239,7 @@ int sbn_prover_prove_host_columns(sbn_prover* p, const uint64_t* const* columns,
                                   const uint64_t* public_inputs, size_t n_pi, uint64_t* reduced_out, sbn_proof** out);
 /* ROW-major traces: what the reference's generators hold in front of their `transpose` (src/curves/g1/exp.rs:255-298 and the other
  * generate_trace functions build `rows` row by row, transpose, and only then append the derived columns).  The library transposes
- * on the device (csrc/kernels_rows.cuh) and, in main-row mode, writes the derived columns itself.
+ * on the device (csrc/kernels_load.cuh) and, in main-row mode, writes the derived columns itself.
  * Exactly one of flat / row_ptrs is set: flat = one allocation, row r at flat[r * row_stride .. + n_cols), row_stride >= n_cols
  * (`Vec<[F; N]>`: row_stride = N); row_ptrs = one allocation per row, row_ptrs[r][0 .. n_cols) (`Vec<Vec<F>>`; row_stride is
  * ignored).  8-byte alignment suffices; the memory is only read, and the words between n_cols and row_stride are never read.
@@ -853,7 +853,7 @@ int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_t* out, siz
  * Parity tests only; host in/out. */
 int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device);
 /* Index of the first word >= p (the Goldilocks modulus) among words[0 .. count), or count when every word is canonical: the scan
- * sbn_prover_prove_host_trace runs behind each chunk it uploads (csrc/kernels.cuh first_non_canonical_kernel), host in/out.
+ * sbn_prover_prove_host_trace runs behind each chunk it uploads (csrc/kernels_load.cuh first_non_canonical_kernel), host in/out.
  * on_device = 0 runs a host loop and needs no device. */
 int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out);
 /* out[0 .. len) = the flat words [word0, word0 + len) of the column-major matrix [n_columns][n] whose column c is
@@ -861,7 +861,7 @@ int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, 
  * SBN_ERR_BAD_ARG when word0 + len > n_columns * n or a column pointer is null or not 8-byte aligned.  Host only. */
 int sbn_gather_columns(const uint64_t* const* columns, size_t n_columns, size_t n, size_t word0, size_t len, uint64_t* out);
 /* In place: every word >= p becomes w - p; *reduced_out (optional) = the number of words changed.  The kernel
- * SBN_TRACE_REDUCE runs behind each chunk it uploads (csrc/kernels.cuh reduce_words_kernel), host in/out; on_device = 0 runs a
+ * SBN_TRACE_REDUCE runs behind each chunk it uploads (csrc/kernels_load.cuh reduce_words_kernel), host in/out; on_device = 0 runs a
  * host loop and needs no device. */
 int sbn_reduce_words(uint64_t* words, size_t count, int on_device, uint64_t* reduced_out);
 /* The host permutation behind the Fiat-Shamir transcript of prove()/verify() (plonky2 Challenger's

@@ -142,7 +142,7 @@ void host_parallel_for(size_t n, const std::function<void(size_t)>& f);
 // the code the host generators end with: the pulses, then the u16 or the split range check.  false: a range-checked column holds a
 // word >= 2^16
 bool derived_columns_host(const ExpShape& sh, uint64_t* trace, size_t n);
-// trace_rows.hip: the refusals of sbn_prove_rows that need no prover (include/sbn.h, the list at sbn_host_rows, 1 .. 8), and
+// trace_load.hip: the refusals of sbn_prove_rows that need no prover (include/sbn.h, the list at sbn_host_rows, 1 .. 8), and
 // *degree_bits_out = log2 of the row count
 int host_rows_precheck(const sbn_air_desc* air, const sbn_host_rows* rows, uint32_t flags, const uint64_t* pi, size_t n_pi, uint32_t* degree_bits_out);
 // tracegen.hip: the curve chains run eight instances per AVX-512 IFMA register on this CPU (0.15 ms per group of eight)

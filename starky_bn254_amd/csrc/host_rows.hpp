@@ -2,7 +2,7 @@
 // `rows: Vec<[F; N]>` (one flat allocation, rows `row_stride` words apart) or `Vec<Vec<F>>` (one allocation per row).  The upload
 // of sbn_prover_load_trace_rows cuts the row range into ring pieces of whole rows and copies each piece PACKED -- n_cols words
 // per row, the stride padding dropped -- through copy_rows below; the transposition to the column-major trace runs on the
-// device (kernels_rows.cuh).  The twin of host_columns.hpp.  Plain C++ (no HIP): tests/sanitize/san_rows.cpp includes this
+// device (kernels_load.cuh).  The twin of host_columns.hpp.  Plain C++ (no HIP): tests/sanitize/san_rows.cpp includes this
 // header alone.
 #pragma once
 #include <cstddef>

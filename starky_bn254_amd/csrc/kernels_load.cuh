@@ -1,5 +1,5 @@
-// Row-major pieces of a trace -> the column-major d_trace (trace_rows.hip; include/sbn.h sbn_prover_load_trace_rows).  Included by
-// trace_rows.hip alone.
+// The kernels of the trace intake, included by trace_load.hip alone: row-major pieces of a trace -> the column-major d_trace
+// (include/sbn.h sbn_prover_load_trace_rows), and behind it the canonical-form scan of a column-major upload and its reducing twin.
 #pragma once
 #include "gl.cuh"
 
@@ -79,3 +79,60 @@ __global__ __launch_bounds__(RT_THREADS, 4) void rows_to_columns_kernel(const Ro
 }
 
 }  // namespace rowsk
+
+// Canonical-form scan of a host trace on its way in (trace_load.hip prove_host_trace; sbn_first_non_canonical): *first_bad =
+// min(*first_bad, base + i) over the words w[i] >= p.  Bandwidth-bound: 16-byte loads, grid-stride; a wave whose lanes all saw
+// canonical words issues no atomic (wave vote), any other wave issues one, after a min over its lanes.  `w` may sit 8 bytes
+// off a 16-byte boundary: lane 0 of the grid takes the word in front of the first whole vector and the one behind the last.
+typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));   // (a load of this type stays ONE global_load_dwordx4)
+__global__ __launch_bounds__(256) void first_non_canonical_kernel(const u64* __restrict__ w, size_t count, u64 base, unsigned long long* first_bad) {
+  const size_t head = (((size_t)w & 8) && count) ? 1 : 0;
+  const u64x2_t* __restrict__ v = reinterpret_cast<const u64x2_t*>(w + head);
+  const size_t nvec = (count - head) >> 1;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  u64 bad = ~(u64)0;
+#pragma unroll 4
+  for (size_t i = tid; i < nvec; i += stride) {
+    const u64x2_t x = v[i];
+    const bool b0 = x.x >= GLP, b1 = x.y >= GLP;
+    if (b0 | b1) { const u64 j = head + 2 * i + (b0 ? 0 : 1); bad = bad < j ? bad : j; }
+  }
+  if (tid == 0) {
+    const size_t last = head + 2 * nvec;   // < count iff one word is left behind the vectors
+    if (last < count && w[last] >= GLP) bad = bad < last ? bad : last;
+    if (head && w[0] >= GLP) bad = 0;
+  }
+  if (!__any(bad != ~(u64)0)) return;
+  for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor((unsigned long long)bad, d, 64); bad = o < bad ? o : bad; }
+  if ((threadIdx.x & 63) == 0) atomicMin(first_bad, (unsigned long long)(base + bad));
+}
+
+// The scan's twin for SBN_TRACE_REDUCE (trace_load.hip prove_host_columns; sbn_reduce_words): in place, w[i] >= p becomes w[i] - p
+// (one subtraction: 2^64 - 1 - p < p), and *reduced grows by the number of words changed.  Bandwidth-bound: 16-byte loads,
+// grid-stride, no LDS; a lane stores only a vector it changed, so a canonical trace costs what the scan costs (reads only).  The
+// loop is wave-uniform (a wave leaves it as a whole), so the changed words are counted from ballots, and a wave that changed
+// something issues one atomicAdd from its first lane.  Head and tail as in the scan: `w` may sit 8 bytes off a 16-byte boundary.
+__global__ __launch_bounds__(256) void reduce_words_kernel(u64* __restrict__ w, size_t count, unsigned long long* reduced) {
+  const size_t head = (((size_t)w & 8) && count) ? 1 : 0;
+  u64x2_t* __restrict__ v = reinterpret_cast<u64x2_t*>(w + head);
+  const size_t nvec = (count - head) >> 1;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t lane = threadIdx.x & 63;
+  unsigned long long changed = 0;   // wave-uniform
+  for (size_t i0 = tid - lane; i0 < nvec; i0 += stride) {
+    const size_t i = i0 + lane;
+    bool b0 = false, b1 = false;
+    if (i < nvec) {
+      u64x2_t x = v[i];
+      b0 = x.x >= GLP; b1 = x.y >= GLP;
+      if (b0 | b1) { if (b0) x.x -= GLP; if (b1) x.y -= GLP; v[i] = x; }
+    }
+    if (__any(b0 | b1)) changed += (unsigned long long)(__popcll(__ballot(b0)) + __popcll(__ballot(b1)));
+  }
+  if (tid == 0) {   // (lane 0 of the grid's first wave: what it adds here its atomicAdd below carries)
+    const size_t last = head + 2 * nvec;   // < count iff one word is left behind the vectors
+    if (last < count && w[last] >= GLP) { w[last] -= GLP; changed++; }
+    if (head && w[0] >= GLP) { w[0] -= GLP; changed++; }
+  }
+  if (lane == 0 && changed) atomicAdd(reduced, changed);
+}

@@ -4,7 +4,6 @@
 // stage runs in the kernels of kernels.cuh on one HIP stream.
 #include "prover_ctx.hpp"
 #include "kernels.cuh"
-#include "host_columns.hpp"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -43,11 +42,10 @@ static const char* STAGE_NAMES[ST_COUNT + EX_COUNT] = {
 static inline dim3 blocks(size_t k) { return dim3((unsigned)((k + 255) / 256)); }   // workgroups of 256 threads over k items
 
 // ---- device memory of a context ---------------------------------------------------------------------
-// Every device buffer of a context -- the list of ctx_buffers, the lazy d_first_bad of prove_host_trace, the buffers of a scratch
+// Every device buffer of a context -- the list of ctx_buffers, the lazy scan word of prove_host_trace (trace_load.hip), the buffers of a scratch
 // context -- is allocated here and nowhere else: the pointer joins P->owned, which is all that sbn_prover_destroy frees, and the
 // bytes join P->dev_bytes.  Stops at the first failure; what was allocated until then is in `owned` already.
-struct BufReq { void** slot; size_t bytes; };
-static int alloc_buffers(sbn_prover* P, const std::vector<BufReq>& L) {
+int alloc_buffers(sbn_prover* P, const std::vector<BufReq>& L) {
   for (const BufReq& b : L) {
     const hipError_t e = hipMalloc(b.slot, b.bytes);
     if (e != hipSuccess) { *b.slot = nullptr; return fail(SBN_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
@@ -286,59 +284,12 @@ static int tree_from_matrix(sbn_prover* P, DevTree& t, const u64* lde, size_t nc
   hipLaunchKernelGGL(leaf_hash_kernel, dim3((unsigned)((P->m + 255) / 256)), dim3(256), 0, P->stream, lde, P->m, P->lde_log, (u32)ncols, t.d);
   return tree_build_inner(P, t, P->stream);
 }
-// ---- prove_host_trace: the upload side ------------------------------------------------------------------------------
-// The trace of sbn_prover_prove_host_trace crosses PCIe in the commit pipeline's own column chunks: host threads copy a piece of
-// the caller's (pageable, possibly read-only) matrix into a pinned ring slot (through gather_columns of host_columns.hpp: the matrix
-// may be one flat allocation or one allocation per column), a hipMemcpyAsync on the copy stream moves it to its
-// place in d_trace, and after the last piece of chunk k the copy stream scans the chunk for words >= p and records
-// upload_done[k].  A slot is refilled only once the event of its previous copy has completed, so the host runs at most
-// UPLOAD_SLOTS pieces ahead of the copy engine.
-// the caller's trace; done[k]: chunk k is resident and scanned; reduce (SBN_TRACE_REDUCE): reduce_words_kernel takes the scan's
-// place, and d_first_bad counts the words it changed instead of holding the first one refused
-struct HostUpload { HostColumns src; hipEvent_t* done; bool reduce; };
-int upload_setup(sbn_prover* P) {   // idempotent: a call that failed half way is completed by the next one
-  if (!P->ustream) HIPC(hipStreamCreate(&P->ustream));
-  for (auto& e : P->upload_done) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : P->slot_copied) if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (!P->h_ring) HIPC(hipHostMalloc((void**)&P->h_ring, UPLOAD_SLOTS * UPLOAD_SLOT_WORDS * sizeof(u64), hipHostMallocDefault));
-  if (!P->h_first_bad) HIPC(hipHostMalloc((void**)&P->h_first_bad, sizeof(unsigned long long), hipHostMallocDefault));
-  if (!P->d_first_bad) return alloc_buffers(P, {BufReq{(void**)&P->d_first_bad, sizeof(unsigned long long)}});   // lazy, outside the plan (include/sbn.h)
-  return 0;
-}
-// the grid of the scan and of its reducing twin: two words per thread, grid-stride beyond 8 waves per CU
-static inline dim3 scan_grid(size_t count) { return dim3((unsigned)std::min<size_t>(std::max<size_t>((count / 2 + 255) / 256, 1), 2048)); }
-static void launch_first_non_canonical(const u64* d_words, size_t count, u64 base, unsigned long long* d_first_bad, hipStream_t st) {
-  hipLaunchKernelGGL(first_non_canonical_kernel, scan_grid(count), dim3(256), 0, st, d_words, count, base, d_first_bad);
-}
-static void launch_reduce_words(u64* d_words, size_t count, unsigned long long* d_reduced, hipStream_t st) {
-  hipLaunchKernelGGL(reduce_words_kernel, scan_grid(count), dim3(256), 0, st, d_words, count, d_reduced);
-}
-static int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0, size_t nc) {
-  const size_t w0 = c0 * P->n, w1 = w0 + nc * P->n;
-  const size_t threads = std::min<size_t>(tracegen_host_threads(), 16);
-  for (size_t a = w0; a < w1; a += UPLOAD_SLOT_WORDS) {
-    const size_t len = std::min(UPLOAD_SLOT_WORDS, w1 - a);
-    const unsigned s = P->slot_next; P->slot_next = (s + 1) % UPLOAD_SLOTS;
-    if (P->slot_used[s]) HIPC(hipEventSynchronize(P->slot_copied[s]));
-    u64* slot = P->h_ring + (size_t)s * UPLOAD_SLOT_WORDS;
-    const size_t parts = std::max<size_t>(1, std::min(threads, len >> 15)), per = (len + parts - 1) / parts;   // >= 256 KiB per thread
-    host_parallel_for(parts, [&](size_t t) { const size_t b0 = t * per, b1 = std::min(len, b0 + per); if (b0 < b1) gather_columns(up.src, a + b0, b1 - b0, slot + b0); });
-    HIPC(hipMemcpyAsync(P->d_trace + a, slot, len * sizeof(u64), hipMemcpyHostToDevice, P->ustream));
-    HIPC(hipEventRecord(P->slot_copied[s], P->ustream));
-    P->slot_used[s] = true;
-  }
-  if (up.reduce) launch_reduce_words(P->d_trace + w0, w1 - w0, P->d_first_bad, P->ustream);
-  else launch_first_non_canonical(P->d_trace + w0, w1 - w0, (u64)w0, P->d_first_bad, P->ustream);
-  HIPC(hipGetLastError());
-  HIPC(hipEventRecord(up.done[k], P->ustream));
-  return 0;
-}
 
 // PolynomialBatch::from_values for a wide matrix: per column chunk iNTT + coset LDE on the main stream,
 // sponge absorption of that chunk on the hash stream, then the Merkle levels; main waits at the end.
 // up (prove_host_trace only; null: nothing below is enqueued that was not before): `vals` is still on the host.  Chunk k is sent
-// on its way right before its transforms are enqueued, and the main stream -- which runs the first transform pass of a chunk in
-// all three branches below (fused two-stream, plain two-stream, one stream) -- waits for upload_done[k] first.
+// on its way right before its transforms are enqueued (trace_load.hip upload_chunk), and the main stream -- which runs the first
+// transform pass of a chunk in all three branches below (fused two-stream, plain two-stream, one stream) -- waits for it first.
 // dense (compact storage of a wide matrix; null: the LDE stays whole in `lde`): [ncols][qn], the quotient's rows.  The last LDE pass
 // of chunk k then writes ring slot k % ring_depth, the sponge reads the slot, lde_keep_rows_kernel behind it copies the slot's
 // quotient rows to `dense`, and ring_free[k] is recorded behind that; the stream that runs the writing pass of chunk
@@ -364,9 +315,7 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
   if (nchunks > (size_t)MAX_CHUNKS) return fail(SBN_ERR_UNSUPPORTED, "too many column chunks");
   if (ncols <= 4) {   // hash_or_noop: a leaf of at most 4 elements is its own digest (MyStark's 4 columns and its 2 Z columns)
     if (up) {   // the whole matrix as one upload
-      int rc = upload_chunk(P, *up, 0, 0, ncols);
-      if (rc) return rc;
-      HIPC(hipStreamWaitEvent(P->stream, up->done[0], 0));
+      if (int rc = upload_chunk(P, *up, 0, 0, ncols)) return rc;
     }
     int rc = intt_then_lde(P, vals, coef, lde, ncols);
     if (rc) return rc;
@@ -396,10 +345,7 @@ static int commit_pipeline(sbn_prover* P, const u64* vals, u64* coef, u64* lde, 
       if (kb < c0 + nc) piece[npieces++] = {kb, c0 + nc - kb};
       if (kept) *kept += kb - ka;
     }
-    if (up) {
-      if ((rc = upload_chunk(P, *up, k, c0, nc))) return rc;
-      HIPC(hipStreamWaitEvent(P->stream, up->done[k], 0));
-    }
+    if (up && (rc = upload_chunk(P, *up, k, c0, nc))) return rc;
     for (int pc = 0; pc < npieces; pc++) {
       const size_t a = piece[pc].a, cnt = piece[pc].cnt;
       const u64* const v_p = vals + a * P->n; u64* const cf_p = coef + a * P->n; u64* const lde_p = lde_k + (a - c0) * P->m;
@@ -614,12 +560,12 @@ static int absorb_times(sbn_prover* P, size_t ncols, int ex_ms) {
   P->stage_ms[ST_COUNT + ex_ms] = tot;
   return 0;
 }
-// first_bad (prove_host_trace): the word the upload's scans folded rides back behind the cap, under the same wait
-static int tree_cap_to_host(sbn_prover* P, const DevTree& t, std::vector<u64>& cap, bool first_bad = false) {
+// upload_result (prove_host_trace): the word the upload's scans folded rides back behind the cap, under the same wait
+static int tree_cap_to_host(sbn_prover* P, const DevTree& t, std::vector<u64>& cap, bool upload_result = false) {
   size_t capn = (size_t)1 << P->cfg.cap_height;
   cap.resize(capn * 4);
   HIPC(hipMemcpyAsync(cap.data(), t.level(t.nlevels), capn * 4 * sizeof(u64), hipMemcpyDeviceToHost, P->stream));
-  if (first_bad) HIPC(hipMemcpyAsync(P->h_first_bad, P->d_first_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, P->stream));
+  if (upload_result) if (int rc = upload_result_to_host(P)) return rc;
   HIPC(stream_wait(P->stream));
   return 0;
 }
@@ -921,7 +867,7 @@ namespace sbn { size_t prover_device_bytes(const sbn_prover* P) { return P ? P->
 extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (!P) return;
   (void)hipSetDevice(P->device);
-  if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // in front of the frees: it writes d_trace and d_first_bad (a refused call drained it already)
+  if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // in front of the frees: the copy stream writes d_trace and its scan word (a refused call drained it already)
   for (void* b : P->owned) (void)hipFree(b);                 // every device buffer of the context (alloc_buffers)
   if (P->sp) {
     for (auto& e : P->sp->xchg_done) if (e) (void)hipEventDestroy(e);
@@ -934,83 +880,12 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
   for (auto& e : P->chunk_ready) if (e) (void)hipEventDestroy(e);
   if (P->hash_done) (void)hipEventDestroy(P->hash_done);
   for (auto& e : P->ring_free) if (e) (void)hipEventDestroy(e);
-  for (void* h : {(void*)P->h_chain, (void*)P->h_io, (void*)P->h_open, (void*)P->h_open2, (void*)P->h_w, (void*)P->h_ring, (void*)P->h_first_bad}) if (h) (void)hipHostFree(h);   // pinned
-  for (auto& e : P->upload_done) if (e) (void)hipEventDestroy(e);
-  for (auto& e : P->slot_copied) if (e) (void)hipEventDestroy(e);
-  if (P->ustream) (void)hipStreamDestroy(P->ustream);
+  for (void* h : {(void*)P->h_chain, (void*)P->h_io, (void*)P->h_open, (void*)P->h_open2, (void*)P->h_w}) if (h) (void)hipHostFree(h);   // pinned
+  upload_destroy(P);   // trace_load.hip: the pinned ring, the upload events, the copy stream
   if (P->hstream) (void)hipStreamDestroy(P->hstream);
   if (P->nstream) { (void)hipStreamDestroy(P->nstream); for (auto& e : P->intt_done) if (e) (void)hipEventDestroy(e); }
   if (P->stream) (void)hipStreamDestroy(P->stream);
   delete P;
-}
-
-int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi) {
-  if (n_pi != P->air.npi) return fail(SBN_ERR_BAD_ARG, "expected %zu public inputs, got %zu", P->air.npi, n_pi);
-  if (n_pi && !pi) return fail(SBN_ERR_BAD_ARG, "null public inputs");
-  for (size_t i = 0; i < n_pi; i++) if (pi[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "public input %zu is not canonical", i);
-  P->pi.assign(pi, pi + n_pi);
-  return 0;
-}
-// Behind a copy into d_trace: do its shape-constant columns hold the generators' words (P->fixed_match)?  The caller owns the trace,
-// and a valid witness may hold other words there, so the device compares: one launch over (fixed_f1 - fixed_f0) n words and one
-// word back.  The mismatch word borrows the start of d_tmp, which only prove() and the checks use, none of them in flight here.
-int fixed_columns_check(sbn_prover* P) {
-  P->fixed_match = false;
-  if (P->fixed_f1 <= P->fixed_f0) return 0;
-  unsigned long long* d_word = (unsigned long long*)P->d_tmp;
-  unsigned long long mismatch = 1;
-  if (int rc = launch_fixed_columns_check(P->d_trace + P->fixed_f0 * P->n, P->fixed_f1 - P->fixed_f0, P->n, exp_shape(P->air), d_word, P->stream)) return rc;
-  HIPC(hipMemcpyAsync(&mismatch, d_word, sizeof mismatch, hipMemcpyDeviceToHost, P->stream));
-  HIPC(hipStreamSynchronize(P->stream));
-  P->fixed_match = mismatch == 0;
-  return 0;
-}
-extern "C" int sbn_prover_load_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi) {
-  if (!P || !trace) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->fixed_match = false;   // before any check: whatever this call leaves in d_trace, it is no longer known
-  int rc = check_pi(P, pi, n_pi); if (rc) return rc;
-  size_t words = P->air.ncols * P->n;
-  {  // canonical-form check on several host threads (the copy below is the PCIe-bound part)
-    unsigned nt = tracegen_host_threads(); if (nt == 0) nt = 1; if (nt > 16) nt = 16;   // (honours SBN_HOST_THREADS)
-    std::atomic<size_t> bad(words);
-    std::vector<std::thread> th;
-    size_t per = (words + nt - 1) / nt;
-    for (unsigned t = 0; t < nt; t++)
-      th.emplace_back([&, t] {
-        size_t a = t * per, b = std::min(words, a + per);
-        for (size_t i = a; i < b; i++) if (trace[i] >= GLP) { size_t cur = bad.load(); while (i < cur && !bad.compare_exchange_weak(cur, i)) {} break; }
-      });
-    for (auto& x : th) x.join();
-    if (bad.load() < words) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", bad.load());
-  }
-  HIPC(hipSetDevice(P->device));
-  HIPC(hipMemcpy(P->d_trace, trace, words * sizeof(u64), hipMemcpyHostToDevice));
-  if ((rc = fixed_columns_check(P))) return rc;
-  P->loaded = true;
-  return SBN_OK;
-}
-extern "C" int sbn_prover_load_trace_device(sbn_prover* P, const uint64_t* d_trace, const uint64_t* pi, size_t n_pi) {
-  if (!P || !d_trace) return fail(SBN_ERR_BAD_ARG, "null argument");
-  P->fixed_match = false;   // (the caller may have written through sbn_prover_trace_device_ptr already)
-  int rc = check_pi(P, pi, n_pi); if (rc) return rc;
-  HIPC(hipSetDevice(P->device));
-  if (d_trace != P->d_trace) HIPC(hipMemcpy(P->d_trace, d_trace, P->air.ncols * P->n * sizeof(u64), hipMemcpyDeviceToDevice));
-  if ((rc = fixed_columns_check(P))) return rc;
-  P->loaded = true;
-  return SBN_OK;
-}
-
-extern "C" int sbn_prover_read_trace(sbn_prover* P, uint64_t* out) {
-  if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (!P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
-  HIPC(hipSetDevice(P->device));
-  HIPC(hipMemcpy(out, P->d_trace, P->air.ncols * P->n * sizeof(u64), hipMemcpyDeviceToHost));
-  return SBN_OK;
-}
-extern "C" uint64_t* sbn_prover_trace_device_ptr(sbn_prover* P) {
-  if (!P) return nullptr;
-  (void)hipSetDevice(P->device);
-  return P->d_trace;
 }
 
 extern "C" int sbn_prover_stage_times(const sbn_prover* P, float* ms, int cap) {
@@ -1115,11 +990,11 @@ void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientPar
 // wait (cap download, opening slices, stream_wait), so that round trip is not in the time it reports.  (fri_layers and pow wait
 // inside their loops: their event follows the last wait.)
 struct ProofRun {
-  sbn_prover* P = nullptr;                    // prove_impl; read by every stage
-  SplitCtx* S = nullptr;                      // prove_impl: P->sp, non-null: this rank's share of one trace split over S->comm.world GPUs; every stage
-  const HostUpload* up = nullptr;             // prove_impl: null for sbn_prover_prove (the trace is resident), else the host trace streamed in; trace_commit
+  sbn_prover* P = nullptr;                    // prove_streamed; read by every stage
+  SplitCtx* S = nullptr;                      // prove_streamed: P->sp, non-null: this rank's share of one trace split over S->comm.world GPUs; every stage
+  const HostUpload* up = nullptr;             // prove_streamed: null for sbn_prover_prove (the trace is resident), else the host trace streamed in; trace_commit
   Challenger ch;                              // the transcript: every stage observes into it and draws from it, in stage order
-  bool fills_fixed = false;                   // trace_commit: it transforms the generators' words of the shape-constant columns; prove_impl, behind the proof
+  bool fills_fixed = false;                   // trace_commit: it transforms the generators' words of the shape-constant columns; prove_streamed, behind the proof
   std::vector<u64> trace_cap, z_cap, q_cap;   // trace_commit, z_commit (Z > 0 only), quotient_commit; assemble_proof
   F gamma0, gamma1;                           // perm_z; quotient_eval
   F alphas[SBN_NCH];                          // quotient_eval draws them, for its own tables and kernels
@@ -1134,8 +1009,8 @@ struct ProofRun {
 
   size_t capw() const { return ((size_t)1 << P->cfg.cap_height) * 4; }   // words of a Merkle cap
   // the cap of a commitment to the host -- a host wait -- and into the transcript (sharded: a row-sharded tree of the split)
-  int observe_cap(const DevTree& t, std::vector<u64>& cap, bool sharded, bool first_bad = false) {
-    if (int rc = sharded ? split_cap_to_host(P, t, cap) : tree_cap_to_host(P, t, cap, first_bad)) return rc;
+  int observe_cap(const DevTree& t, std::vector<u64>& cap, bool sharded, bool upload_result = false) {
+    if (int rc = sharded ? split_cap_to_host(P, t, cap) : tree_cap_to_host(P, t, cap, upload_result)) return rc;
     ch.observe_words(cap.data(), capw());
     return 0;
   }
@@ -1146,11 +1021,11 @@ struct ProofRun {
 // P1 trace commitment ---------------------------------------------------------------------------
 static int stage_trace_commit(ProofRun& run) {
   sbn_prover* P = run.P; SplitCtx* S = run.S; const HostUpload* up = run.up;
-  if (up) HIPC(hipMemsetAsync(P->d_first_bad, up->reduce ? 0 : 0xff, sizeof(unsigned long long), P->ustream));   // in front of the first scan
+  if (up) if (int rc = upload_begin(P, *up)) return rc;   // in front of the first scan
   // The shape-constant columns (prover_ctx.hpp fixed_match / fixed_valid; the range is empty for the split, compact storage and the
   // tables without one).  The resident trace holds the generators' words there and an earlier proof of them succeeded: their
   // coefficients and LDE are in place, nothing transforms them.  It holds them and no such proof yet: everything is transformed, and
-  // prove_impl sets fixed_valid behind the proof.  Anything else -- other words, a trace that is still on the host -- is transformed
+  // prove_streamed sets fixed_valid behind the proof.  Anything else -- other words, a trace that is still on the host -- is transformed
   // whole, and d_coef / d_lde then hold the transforms of other words.
   const bool canonical = !up && P->fixed_match && P->fixed_f1 > P->fixed_f0;
   if (!canonical) P->fixed_valid = false;
@@ -1164,8 +1039,7 @@ static int stage_trace_commit(ProofRun& run) {
                                       keep0, keep1, &P->fixed_skipped)) return rc;
   if (int rc = run.next_stage(ST_PERM_Z)) return rc;
   if (int rc = run.observe_cap(P->tree_t, run.trace_cap, S != nullptr, up != nullptr)) return rc;   // (the scans' word rides back behind the cap)
-  if (up && !up->reduce && *P->h_first_bad != ~0ull) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", (size_t)*P->h_first_bad);
-  return 0;
+  return up ? upload_verdict(P, *up) : 0;
 }
 
 // P2 permutation argument -------------------------------------------------------------------------
@@ -1611,8 +1485,8 @@ static int assemble_proof(const ProofRun& run, sbn_proof** out) {
   *out = pr;
   return SBN_OK;
 }
-// up: null for sbn_prover_prove (the trace is resident); else the host trace sbn_prover_prove_host_trace streams in
-static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
+// up: null for sbn_prover_prove (the trace is resident); else the host trace sbn_prover_prove_host_trace streams in (trace_load.hip)
+int prove_streamed(sbn_prover* P, const HostUpload* up, sbn_proof** out) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   if (!up && !P->loaded && !(P->sp && P->sp->comm.world > 1)) return fail(SBN_ERR_BAD_ARG, "no trace loaded");   // (split: agreed with the other ranks below)
@@ -1641,59 +1515,8 @@ static int prove_impl(sbn_prover* P, sbn_proof** out, const HostUpload* up) {
   if (run.fills_fixed) P->fixed_valid = true;   // every stage has run and been waited for: d_coef and d_lde hold those transforms
   return SBN_OK;
 }
-extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_impl(P, out, nullptr); }
+extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_streamed(P, nullptr, out); }
 
-// load + prove in one call (include/sbn.h): the upload runs inside the trace commitment, the canonical-form check on the device
-static int prove_upload(sbn_prover* P, const HostColumns& src, bool reduce, uint64_t* reduced_out, sbn_proof** out) {
-  HIPC(hipSetDevice(P->device));
-  int rc;
-  if ((rc = upload_setup(P))) return rc;
-  const HostUpload up{src, P->upload_done, reduce};
-  if ((rc = prove_impl(P, out, &up))) {
-    // whatever was enqueued (the rest of an upload, transforms of a refused trace) ends before the caller sees the error:
-    // the next call finds idle streams and a free ring
-    for (hipStream_t s : {P->ustream, P->stream, P->hstream, P->nstream}) if (s) (void)hipStreamSynchronize(s);
-    return rc;
-  }
-  if (reduce && reduced_out) *reduced_out = *P->h_first_bad;   // (the counter came back with the trace cap)
-  P->loaded = true;
-  return SBN_OK;
-}
-extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi, sbn_proof** out) {
-  if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  *out = nullptr;
-  P->loaded = false;   // before any check: a refused call must not leave the previous trace provable
-  P->fixed_match = false;   // the upload writes d_trace and compares nothing
-  if (!trace) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "sbn_prover_prove_host_trace covers single-GPU provers");
-  int rc = check_pi(P, pi, n_pi); if (rc) return rc;
-  return prove_upload(P, HostColumns{nullptr, trace, P->n}, false, nullptr, out);
-}
-// the same for a trace held as one allocation per column (csrc/host_columns.hpp); SBN_TRACE_REDUCE: words and public inputs >= p
-// are taken mod p (the words on the device, behind the upload) instead of refused
-extern "C" int sbn_prover_prove_host_columns(sbn_prover* P, const uint64_t* const* columns, size_t n_columns, uint32_t flags, const uint64_t* pi, size_t n_pi,
-                                             uint64_t* reduced_out, sbn_proof** out) {
-  if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  *out = nullptr;
-  P->loaded = false;
-  P->fixed_match = false;
-  if (reduced_out) *reduced_out = 0;
-  if (n_columns != P->air.ncols) return fail(SBN_ERR_BAD_ARG, "expected %zu columns, got %zu", P->air.ncols, n_columns);
-  if (!columns) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (const size_t bad = gather_columns_refused(columns, n_columns, P->n, 0, n_columns * P->n))
-    return fail(SBN_ERR_BAD_ARG, "column %zu is null or not 8-byte aligned", bad - 2);
-  if (flags & ~SBN_TRACE_REDUCE) return fail(SBN_ERR_BAD_ARG, "unknown flag bits 0x%x", flags & ~SBN_TRACE_REDUCE);
-  const bool reduce = (flags & SBN_TRACE_REDUCE) != 0;
-  int rc;
-  if (reduce && pi && n_pi == P->air.npi) {   // (a wrong count or a null pointer: check_pi below says so)
-    std::vector<u64> red(pi, pi + n_pi);
-    reduce_words_host(red.data(), n_pi);
-    rc = check_pi(P, red.data(), n_pi);
-  } else rc = check_pi(P, pi, n_pi);
-  if (rc) return rc;
-  if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "sbn_prover_prove_host_columns covers single-GPU provers");
-  return prove_upload(P, HostColumns{columns, nullptr, P->n}, reduce, reduced_out, out);
-}
 
 // ---- building blocks for parity tests ---------------------------------------------------------------
 // A stub context for the transforms of one (degree_bits, rate_bits, cap_height): the shape fields, the switches, the transform plan
@@ -1786,13 +1609,6 @@ extern "C" int sbn_lde_rows(const uint64_t* cols, size_t ncols, uint32_t degree_
   return SBN_OK;
 }
 
-// Device words that are freed on every return path: the buffer of the upload / run one kernel / download entry points below.
-struct DevWords {
-  u64* d = nullptr;
-  ~DevWords() { if (d) (void)hipFree(d); }
-  int alloc(size_t words) { HIPC(hipMalloc((void**)&d, words * sizeof(u64))); return 0; }
-};
-
 extern "C" int sbn_poseidon_permute_batch(uint64_t* states, size_t count) {
   if (!states) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (int rc = use_current_device("no CPU fallback")) return rc;
@@ -1829,68 +1645,6 @@ extern "C" int sbn_field_mul_batch(const uint64_t* a, const uint64_t* b, uint64_
   HIPC(hipMemcpy(d + count, b, count * sizeof(u64), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(field_mul_batch_kernel, blocks(count), dim3(256), 0, 0, d, d + count, d + 2 * count, count, mode);
   HIPC(hipMemcpy(out, d + 2 * count, count * sizeof(u64), hipMemcpyDeviceToHost));
-  return SBN_OK;
-}
-
-
-
-// The round trip of the scan (reduce: of its reducing twin, and the words come back too): words up, one launch, *result back.  The
-// device copy keeps the caller's offset from a 16-byte boundary, so the kernels' unaligned head is reachable from a test.
-static int scan_round_trip(const u64* words, u64* words_back, size_t count, unsigned long long* result) {
-  const size_t off = ((size_t)words & 8) ? 1 : 0;
-  DevWords w;   // d[0]: the result word (the first bad index, all ones: none; or the counter); the data from d + 2 + off
-  if (int rc = w.alloc(2 + off + count)) return rc;
-  u64* const data = w.d + 2 + off;
-  HIPC(hipMemset(w.d, words_back ? 0 : 0xff, sizeof(u64)));
-  HIPC(hipMemcpy(data, words, count * sizeof(u64), hipMemcpyHostToDevice));
-  if (words_back) launch_reduce_words(data, count, (unsigned long long*)w.d, 0);
-  else launch_first_non_canonical(data, count, 0, (unsigned long long*)w.d, 0);
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpy(result, w.d, sizeof *result, hipMemcpyDeviceToHost));
-  if (words_back) HIPC(hipMemcpy(words_back, data, count * sizeof(u64), hipMemcpyDeviceToHost));
-  return 0;
-}
-// Index of the first word >= p, or `count`: the scan of sbn_prover_prove_host_trace as a building block (host in, host out).
-extern "C" int sbn_first_non_canonical(const uint64_t* words, size_t count, int on_device, uint64_t* index_out) {
-  if (!index_out || (!words && count)) return fail(SBN_ERR_BAD_ARG, "null argument");
-  *index_out = count;
-  if (!on_device) {
-    for (size_t i = 0; i < count; i++) if (words[i] >= GLP) { *index_out = i; break; }
-    return SBN_OK;
-  }
-  if (int rc = use_current_device("no CPU fallback")) return rc;
-  if (count == 0) return SBN_OK;
-  unsigned long long first = ~0ull;
-  if (int rc = scan_round_trip(words, nullptr, count, &first)) return rc;
-  if (first != ~0ull) *index_out = first;
-  return SBN_OK;
-}
-
-// gather_columns of csrc/host_columns.hpp as a building block: what the upload of sbn_prover_prove_host_columns copies into a ring piece
-extern "C" int sbn_gather_columns(const uint64_t* const* columns, size_t n_columns, size_t n, size_t word0, size_t len, uint64_t* out) {
-  if (const size_t bad = gather_columns_refused(columns, n_columns, n, word0, len)) {
-    if (bad == 1) return fail(SBN_ERR_BAD_ARG, "words %zu + %zu lie beyond the %zu x %zu matrix", word0, len, n_columns, n);
-    return fail(SBN_ERR_BAD_ARG, "column %zu is null or not 8-byte aligned", bad - 2);
-  }
-  if (len && !out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  gather_columns(HostColumns{columns, nullptr, n}, word0, len, out);
-  return SBN_OK;
-}
-// In place: words >= p become w - p; *reduced_out (optional) = how many changed.  reduce_words_kernel of SBN_TRACE_REDUCE as a
-// building block (host in, host out), or the host loop.
-extern "C" int sbn_reduce_words(uint64_t* words, size_t count, int on_device, uint64_t* reduced_out) {
-  if (!words && count) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (reduced_out) *reduced_out = 0;
-  if (!on_device) {
-    const uint64_t changed = reduce_words_host(words, count);
-    if (reduced_out) *reduced_out = changed;
-    return SBN_OK;
-  }
-  if (int rc = use_current_device("no CPU fallback")) return rc;
-  if (count == 0) return SBN_OK;
-  unsigned long long changed = 0;
-  if (int rc = scan_round_trip(words, words, count, &changed)) return rc;
-  if (reduced_out) *reduced_out = changed;
   return SBN_OK;
 }
 

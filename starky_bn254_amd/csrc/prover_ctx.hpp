@@ -1,10 +1,11 @@
 // The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
-// tracegen_device.hip and trace_rows.hip (which fill the trace), by trace_check.hip, trace_explain.hip and trace_explain_fq12.hip (which check it)
+// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip and trace_explain_fq12.hip (which check it)
 // and by lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of
 // include/sbn.h.
 #pragma once
 #include "host_common.hpp"
 #include "settings.hpp"
+#include "pinned_ring.hpp"
 #include <algorithm>
 
 using namespace sbn;
@@ -25,15 +26,10 @@ enum Stage {
 };
 enum Extra { EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, EX_TRACEGEN_MS, EX_COMM_MS, EX_COUNT };
 static constexpr int MAX_CHUNKS = 512;
-// prove_host_trace: the pinned staging ring of one prover, 4 slots of 16 MiB = 64 MiB of pinned host memory at most, allocated on
-// the first call.  A piece of the trace never spans two column chunks; a chunk larger than a slot crosses in several pieces.
-static constexpr int UPLOAD_SLOTS = 4;
+// The pinned staging ring of one prover (pinned_ring.hpp; trace_load.hip): 4 slots of 16 MiB = 64 MiB of pinned host memory,
+// allocated by the first call that uploads a host trace.
+static constexpr unsigned UPLOAD_SLOTS = 4;
 static constexpr size_t UPLOAD_SLOT_WORDS = (size_t)2 << 20;
-// A row-major load (trace_rows.hip) has no column chunks and borrows four of their events for its two staging buffers: the copy into
-// buffer b has landed (copy stream), the transposition has left buffer b (main stream).  Both paths drain their streams before they
-// return, so neither ever sees an event the other recorded.
-static constexpr int ROWS_EV_COPIED = 0, ROWS_EV_TRANSPOSED = 2;
-static_assert(MAX_CHUNKS >= ROWS_EV_TRANSPOSED + 2, "a row-major load borrows upload_done[0 .. 4)");
 // Function attributes are per DEVICE: one flag per device of the process (sbn_set_device may select another GPU later).
 static constexpr int SBN_MAX_DEVICES = 64;
 // Compact LDE storage (include/sbn.h SBN_LDE_COMPACT): slots of the LDE chunk ring at most; create_ctx picks LDE_RING_DEPTH
@@ -159,13 +155,13 @@ struct sbn_prover {
   // pushes here, sbn_prover_destroy frees this list and names no device buffer.  The d_* members above are views of its entries.
   std::vector<void*> owned;
   size_t dev_bytes = 0;                      // their bytes (what sbn_prover_memory_plan predicts and the one-shot cache of capi.hip counts)
-  // prove_host_trace, created on its first call: the trace crosses PCIe on the copy stream through a ring of pinned slots
+  // The host-trace uploads (trace_load.hip), created by the first of them (upload_setup): the trace crosses PCIe on the copy stream
+  // through a ring of pinned slots
   hipStream_t ustream = nullptr;             // copy stream: pieces of the trace, then the canonical-form scan of each chunk
-  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: chunk k is resident and scanned (a row-major load, trace_rows.hip, borrows [0 .. 4): ROWS_EV_*)
-  hipEvent_t slot_copied[UPLOAD_SLOTS];      // copy stream: the copy out of ring slot s has completed
-  bool slot_used[UPLOAD_SLOTS] = {};
-  unsigned slot_next = 0;
-  u64* h_ring = nullptr;                     // [UPLOAD_SLOTS][UPLOAD_SLOT_WORDS], pinned
+  PinnedRing upload_ring;
+  hipEvent_t upload_done[MAX_CHUNKS];        // copy stream: column chunk k is resident and scanned (prove_host_trace, prove_host_columns)
+  hipEvent_t rows_copied[2] = {};            // copy stream: a piece of a row-major load has landed in staging buffer b
+  hipEvent_t rows_transposed[2] = {};        // main stream: its transposition has left staging buffer b
   unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
   float check_ms[4] = {};                    // sbn_prover_check_trace: permutation Z, constraint kernels, reduction, download
@@ -173,7 +169,7 @@ struct sbn_prover {
 };
 
 // Scratch of the calls that fill d_trace (the device witness generators of tracegen_device.hip, the row-major loads of
-// trace_rows.hip), carved from the front of the LDE buffer, which is not in use between proofs (a split prover: its receive buffer).
+// trace_load.hip), carved from the front of the LDE buffer, which is not in use between proofs (a split prover: its receive buffer).
 struct LdeScratch {
   sbn_prover* const P;
   u64* const wbase;
@@ -211,12 +207,27 @@ int launch_query_rows(const u64* coef, size_t ncols, size_t n, u32 lde_log, cons
 // tracegen_device.hip: *d_mismatch = 0, then 1 unless `block` -- the ncols columns of fixed_columns_range() of a trace of n rows --
 // holds the words the device witness writes there (kernels_tracegen.cuh fixed_columns_check_kernel).  Enqueues on `s`.
 int launch_fixed_columns_check(const u64* block, size_t ncols, size_t n, const ExpShape& sh, unsigned long long* d_mismatch, hipStream_t s);
-// prover.hip, shared with trace_rows.hip (the row-major loads): the copy stream, the pinned ring and their events, created on first
-// use; the public-input checks of load_trace (P->pi on success); and, behind a copy into d_trace, the comparison of its
-// shape-constant columns with the generators' words (P->fixed_match; waits for P->stream).
-int upload_setup(sbn_prover* P);
-int check_pi(sbn_prover* P, const uint64_t* pi, size_t n_pi);
-int fixed_columns_check(sbn_prover* P);
+// prover.hip, for trace_load.hip.  alloc_buffers: the one place that allocates device memory of a context (P->owned, P->dev_bytes).
+// prove_streamed: sbn_prover_prove with the trace still on the host (up != null): the trace commitment streams it in.
+struct BufReq { void** slot; size_t bytes; };
+int alloc_buffers(sbn_prover* P, const std::vector<BufReq>& L);
+struct HostUpload;   // trace_load.hip
+int prove_streamed(sbn_prover* P, const HostUpload* up, sbn_proof** out);
+// trace_load.hip, for the trace commitment of prover.hip -- all it sees of a streamed upload, in this order: the result word reset
+// (copy stream); per column chunk k = columns [c0, c0 + nc), its pieces sent and scanned (copy stream) and the main stream made to
+// wait for them; the result word on its way back (main stream, behind the cap's copy); and, behind the host wait, the verdict:
+// SBN_ERR_NON_CANONICAL naming the first word refused, or 0.  upload_destroy: sbn_prover_destroy's share (ring, events, copy stream).
+int upload_begin(sbn_prover* P, const HostUpload& up);
+int upload_chunk(sbn_prover* P, const HostUpload& up, size_t k, size_t c0, size_t nc);
+int upload_result_to_host(sbn_prover* P);
+int upload_verdict(const sbn_prover* P, const HostUpload& up);
+void upload_destroy(sbn_prover* P);
+// Device words that are freed on every return path: the buffer of the upload / run one kernel / download entry points.
+struct DevWords {
+  u64* d = nullptr;
+  ~DevWords() { if (d) (void)hipFree(d); }
+  int alloc(size_t words) { HIPC(hipMalloc((void**)&d, words * sizeof(u64))); return 0; }
+};
 // tracegen_device.hip: the columns [num_main, num_columns) of an Exp table from the main columns resident in d_trace, by the
 // kernels of the device witness (periodic pulse, io pulses, table column, then the table's range-check launches) on P->stream;
 // waits, and on success leaves the prover loaded with fixed_match set.  The caller has made sure that no range-checked main

@@ -226,7 +226,7 @@ static bool fill_u16_range_check(uint64_t* trace, size_t n, const ExpShape& sh) 
   return !bad;
 }
 // The columns [num_main, num_columns) of an Exp table from its main columns, as every host generator below ends: the pulses, then
-// the table's range check (sbn_trace_from_rows_host, trace_rows.hip: the main columns came from the caller's rows).  false: a
+// the table's range check (sbn_trace_from_rows_host, trace_load.hip: the main columns came from the caller's rows).  false: a
 // range-checked column holds a word >= 2^16.
 namespace sbn {
 bool derived_columns_host(const ExpShape& sh, uint64_t* trace, size_t n) {

@@ -767,7 +767,7 @@ static int trace_from_host_list(sbn_prover* P, size_t num_io, uint64_t* pi_out, 
   return rc;
 }
 
-// ---- the derived columns of a row-major load (trace_rows.hip; include/sbn.h sbn_prover_load_trace_rows, main-row mode) --------------
+// ---- the derived columns of a row-major load (trace_load.hip; include/sbn.h sbn_prover_load_trace_rows, main-row mode) --------------
 // The main columns [0, num_main) are resident; everything behind them is a function of those and of the shape, written by the
 // kernels the generators above end with.  The same gate as trace_gate: the u16 tables at 2^16 .. 2^18 rows, the Fq12 kinds at any.
 int derived_columns_covered(const AirShape& as, size_t n) {

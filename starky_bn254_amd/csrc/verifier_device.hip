@@ -13,6 +13,7 @@
 // sources (the same verdict; nothing of it is uploaded).
 #include "verifier_core.hpp"
 #include "kernels_verify.cuh"
+#include "pinned_ring.hpp"
 #include <cstring>
 #include <thread>
 
@@ -34,10 +35,9 @@ struct sbn_verifier {
   int device = 0;
   VerifyLayout L;
   hipStream_t stream = nullptr;
-  hipEvent_t slot_copied[VERIFY_SLOTS] = {}, ev[4] = {};
-  bool slot_used[VERIFY_SLOTS] = {};
-  unsigned slot_next = 0;
-  u64 *d_proofs = nullptr, *d_alpha = nullptr, *d_psum = nullptr, *h_ring = nullptr, *h_alpha = nullptr, *h_psum = nullptr;
+  hipEvent_t ev[4] = {};
+  PinnedRing ring;   // the proofs' way up (pinned_ring.hpp)
+  u64 *d_proofs = nullptr, *d_alpha = nullptr, *d_psum = nullptr, *h_alpha = nullptr, *h_psum = nullptr;
   u32 *d_idx = nullptr, *h_idx = nullptr;
   unsigned char *d_ok = nullptr, *h_ok = nullptr;
   VerifyTreeDev* d_trees = nullptr;
@@ -60,13 +60,11 @@ int upload_proofs(sbn_verifier* V, const uint8_t* const* proofs, const std::vect
   for (size_t a = 0; a < act.size(); a++)
     for (size_t w0 = 0; w0 < pw; w0 += VERIFY_SLOT_WORDS) {
       const size_t len = std::min(VERIFY_SLOT_WORDS, pw - w0);
-      const unsigned s = V->slot_next; V->slot_next = (s + 1) % VERIFY_SLOTS;
-      if (V->slot_used[s]) VHIPC(hipEventSynchronize(V->slot_copied[s]));
-      u64* slot = V->h_ring + (size_t)s * VERIFY_SLOT_WORDS;
+      u64* slot; unsigned s;
+      VHIPC(V->ring.claim(&slot, &s));
       memcpy(slot, proofs[act[a]] + w0 * 8, len * 8);
       VHIPC(hipMemcpyAsync(V->d_proofs + a * pw + w0, slot, len * 8, hipMemcpyHostToDevice, V->stream));
-      VHIPC(hipEventRecord(V->slot_copied[s], V->stream));
-      V->slot_used[s] = true;
+      VHIPC(V->ring.sent(s, V->stream));
     }
   return 0;
 }
@@ -77,11 +75,11 @@ extern "C" {
 
 void sbn_verifier_destroy(sbn_verifier* V) {
   if (!V) return;
-  if (V->stream || V->d_proofs || V->h_ring) {
+  if (V->stream || V->d_proofs || V->ring.base) {
     (void)hipSetDevice(V->device);
     if (V->stream) (void)hipStreamSynchronize(V->stream);
   }
-  for (auto e : V->slot_copied) if (e) (void)hipEventDestroy(e);
+  V->ring.destroy();
   for (auto e : V->ev) if (e) (void)hipEventDestroy(e);
   if (V->d_proofs) (void)hipFree(V->d_proofs);
   if (V->d_alpha) (void)hipFree(V->d_alpha);
@@ -89,7 +87,6 @@ void sbn_verifier_destroy(sbn_verifier* V) {
   if (V->d_idx) (void)hipFree(V->d_idx);
   if (V->d_ok) (void)hipFree(V->d_ok);
   if (V->d_trees) (void)hipFree(V->d_trees);
-  if (V->h_ring) (void)hipHostFree(V->h_ring);
   if (V->h_alpha) (void)hipHostFree(V->h_alpha);
   if (V->h_psum) (void)hipHostFree(V->h_psum);
   if (V->h_idx) (void)hipHostFree(V->h_idx);
@@ -117,7 +114,6 @@ int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t
   auto hipc = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(SBN_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
   const size_t B = max_batch, nq = L.nqueries, nt = L.trees.size();
   hipc(hipStreamCreate(&V->stream), "hipStreamCreate");
-  for (auto& e : V->slot_copied) hipc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
   for (auto& e : V->ev) hipc(hipEventCreate(&e), "hipEventCreate");
   hipc(hipMalloc((void**)&V->d_proofs, B * L.proof_words * sizeof(u64)), "hipMalloc (proofs)");
   hipc(hipMalloc((void**)&V->d_alpha, B * 4 * sizeof(u64)), "hipMalloc");
@@ -125,7 +121,7 @@ int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t
   hipc(hipMalloc((void**)&V->d_idx, B * nq * sizeof(u32)), "hipMalloc");
   hipc(hipMalloc((void**)&V->d_ok, B * nq * nt), "hipMalloc");
   hipc(hipMalloc((void**)&V->d_trees, nt * sizeof(VerifyTreeDev)), "hipMalloc");
-  hipc(hipHostMalloc((void**)&V->h_ring, VERIFY_SLOTS * VERIFY_SLOT_WORDS * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
+  hipc(V->ring.create(VERIFY_SLOTS, VERIFY_SLOT_WORDS), "the pinned ring");
   hipc(hipHostMalloc((void**)&V->h_alpha, B * 4 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
   hipc(hipHostMalloc((void**)&V->h_psum, B * nq * L.ninit * 2 * sizeof(u64), hipHostMallocDefault), "hipHostMalloc");
   hipc(hipHostMalloc((void**)&V->h_idx, B * nq * sizeof(u32), hipHostMallocDefault), "hipHostMalloc");

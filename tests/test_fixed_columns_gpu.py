@@ -1,5 +1,5 @@
-"""The shape-constant trace columns on the device (include/sbn.h sbn_fixed_columns_range; csrc/prover.hip stage_trace_commit): a
-prover transforms them in its first proof of a trace that holds the generators' words there and leaves them alone afterwards.
+"""The shape-constant trace columns on the device (include/sbn.h sbn_fixed_columns_range; csrc/prover.hip stage_trace_commit, and
+csrc/trace_load.hip fixed_columns_check for the comparison behind a load): a prover transforms them in its first proof of a trace that holds the generators' words there and leaves them alone afterwards.
 Every proof stays the same words: against the committed oracle digests, against fresh provers, against SBN_FIXED_COLUMNS=0, at
 every chunking; describe()["fixed_columns_skipped"] shows that the short path ran where it should and only there."""
 import hashlib

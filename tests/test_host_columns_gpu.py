@@ -404,7 +404,7 @@ def test_batch_prover_proves_host_traces_of_an_exp_table(gpu, fq12exp_case):
 def test_split_prover_refuses_host_columns(gpu, fq12exp_case):
     """A split prover at local world 1: SBN_ERR_UNSUPPORTED, as sbn_prover_prove_host_trace.  The split handle has no call of its
     own for host traces, so the test reaches the prover context it wraps (the handle's first word, csrc/prover.hip
-    sbn_split_prover)."""
+    sbn_split_prover); the refusal is that of csrc/trace_load.hip sbn_prover_prove_host_columns."""
     from starky_bn254_amd import split
     S = gpu
     L = S.lib()

@@ -280,3 +280,49 @@ def test_refusals_on_a_real_prover(gpu, fq12expu64_case, g1op_case):
     finally:
         sp.close()
         grp.close()
+
+
+# ---- every intake path in turn on one prover ---------------------------------------------------------------------------------
+def test_intake_paths_alternate_on_one_prover(gpu, fq12expu64_case):
+    """All the calls that make a trace resident share one pinned ring, one copy stream and its events (csrc/trace_load.hip).  On
+    Fq12ExpU64Stark(16) -- 2^11 rows x 9,792 columns, 160 MB: the smallest table at which both upload forms go round the ring (one
+    piece per 64-column chunk for the column forms; more than four 16 MiB pieces of whole rows, so the row form reuses all four
+    slots and both staging buffers) -- six loads of the same trace through five entry points give the same proof words, with a
+    refused prove_host_trace in the middle that must leave nothing provable and the ring and events usable."""
+    S = gpu
+    stark = S.Fq12ExpU64Stark(16)
+    trace = np.ascontiguousarray(fq12expu64_case["trace"], dtype=np.uint64)
+    pi = fq12expu64_case["pi"]
+    n, ncols = 1 << 11, stark.num_columns
+    assert trace.shape == (ncols, n)
+    assert n * ncols > 4 * (1 << 21)                # more than four ring slots of whole rows ...
+    assert (ncols + 63) // 64 > 4                   # ... and more than four column chunks
+    rows = np.ascontiguousarray(trace.T)
+    p = S.Prover(stark, stark.config(), 11)
+    try:
+        words = [p.prove_host_rows(rows, pi).words]                               # whole rows, flat
+        words.append(p.prove_host_trace(trace, pi).words)
+        p.load_trace_rows([rows[r] for r in range(n)], pi)                        # whole rows, one pointer per row
+        words.append(p.prove().words)
+        # a refused call in the middle: one word = p in a late chunk, found by the device scan behind the upload
+        col, row = 5000, 1234
+        bad = trace.copy()
+        bad[col, row] = GL_P
+        with pytest.raises(S.SbnError) as e:
+            p.prove_host_trace(bad, pi)
+        assert e.value.code == NON_CANONICAL and f"trace word {col * n + row} is not canonical" in str(e.value), str(e.value)
+        del bad
+        with pytest.raises(S.SbnError) as e:
+            p.prove()
+        assert "no trace loaded" in str(e.value)
+        proof, reduced = p.prove_host_columns(trace, pi, reduce=True)             # (a 2-D array: its rows are the columns)
+        assert reduced == 0
+        words.append(proof.words)
+        p.load_trace(trace, pi)
+        words.append(p.prove().words)
+        words.append(p.prove_host_rows(rows, pi).words)
+        assert len(words) == 6
+        for k in range(1, 6):
+            assert np.array_equal(words[k], words[0]), k
+    finally:
+        p.close()

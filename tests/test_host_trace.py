@@ -98,3 +98,43 @@ def test_prove_host_trace_refuses_a_null_prover(S):
     h = C.c_void_p(1)
     assert L.sbn_prover_prove_host_trace(None, w.ctypes.data_as(C.c_void_p), None, 0, C.byref(h)) == -1
     assert L.sbn_prover_prove_host_trace(None, w.ctypes.data_as(C.c_void_p), None, 0, None) == -1
+
+
+def test_public_input_refusals_read_the_same_without_a_prover(S, fq12expu64_case):
+    """One routine takes the public inputs of every intake call (csrc/trace_load.hip take_public_inputs): the count, the pointer,
+    then canonical form, in that order and with these exact words.  The calls with a prover need a device; sbn_prove_rows reaches
+    the routine through its precheck, in front of any device, and sbn_trace_from_rows_host shares its flag check."""
+    L = S.lib()
+    stark = S.Fq12ExpU64Stark(16)
+    cfg = stark.config()
+    pi = np.ascontiguousarray(fq12expu64_case["pi"], dtype=np.uint64)
+    npi = len(pi)
+    assert npi == stark.num_public_inputs and npi > 3
+    rows = np.ascontiguousarray(fq12expu64_case["trace"][:stark.num_main_columns].T)
+    n, nc = rows.shape
+    table = S.api._HostRows(C.sizeof(S.api._HostRows), 0, rows.ctypes.data, nc, None, n, nc)
+
+    def prove_rows(pis, n_pi, flags=0):
+        h = C.c_void_p(1)
+        rc = L.sbn_prove_rows(C.byref(stark._d), C.byref(cfg._c), C.byref(table), flags, pis.ctypes.data_as(C.c_void_p) if pis is not None else None, n_pi, C.byref(h))
+        assert h.value is None
+        return rc, L.sbn_last_error().decode()
+
+    two_bad = pi.copy(); two_bad[npi - 1] = 2**64 - 1; two_bad[2] += np.uint64(GL_P)
+    for flags in (0, 1):   # SBN_TRACE_REDUCE changes nothing in front of the canonical-form check
+        assert prove_rows(pi, npi - 1, flags) == (-1, f"expected {npi} public inputs, got {npi - 1}")
+        assert prove_rows(pi, npi + 1, flags) == (-1, f"expected {npi} public inputs, got {npi + 1}")
+        assert prove_rows(None, npi, flags) == (-1, "null public inputs")
+        assert prove_rows(None, npi - 1, flags) == (-1, f"expected {npi} public inputs, got {npi - 1}")   # the count comes first
+        assert prove_rows(two_bad, npi + 1, flags) == (-1, f"expected {npi} public inputs, got {npi + 1}")
+    for i in (0, 3, npi - 1):
+        bad = pi.copy(); bad[i] = GL_P
+        assert prove_rows(bad, npi) == (-2, f"public input {i} is not canonical")
+    assert prove_rows(two_bad, npi) == (-2, "public input 2 is not canonical")      # the smallest index
+    # the flag check stands in front of the public inputs, and reads the same where there are none
+    assert prove_rows(None, npi - 1, flags=6) == (-1, "unknown flag bits 0x6")
+    out = np.zeros(1, dtype=np.uint64)
+    assert L.sbn_trace_from_rows_host(C.byref(stark._d), C.byref(table), 6, out.ctypes.data_as(C.c_void_p), None) == -1
+    assert L.sbn_last_error() == b"unknown flag bits 0x6"
+    if L.sbn_device_count() == 0:   # under the flag the words are reduced, not refused: the call gets as far as the device
+        assert prove_rows(two_bad, npi, flags=1)[0] == -3   # SBN_ERR_NO_DEVICE
