@@ -373,7 +373,8 @@ int sbn_prover_read_trace(sbn_prover* p, uint64_t* trace_out);
  * The segments are the four of the quotient stage: 0 = AIR head (public inputs, transitions, flags, gadgets; everything of the
  * non-Exp tables), 1 = AIR tail of the Exp tables (io pulses, range check), 2 / 3 = the permutation checks of the Z columns
  * [0, z_split) / [z_split, num_zs).  A wrong cell of a permuted column shows in segment 2 or 3 on row N - 1 only: Z is the
- * running product, so only its closing row can break. */
+ * running product, so only its closing row can break.  WHICH values and rows are behind such a failure is the answer of
+ * sbn_explain_permutations_host / sbn_prover_explain_permutations below: the exact multiset difference of the pair's columns. */
 typedef struct sbn_trace_report {
   uint32_t struct_size;          /* caller sets sizeof(sbn_trace_report) */
   uint32_t num_segments;         /* 4 */
@@ -463,6 +464,39 @@ int sbn_prover_explain_trace(sbn_prover* p, uint64_t seed, sbn_block_stat* block
 /* Device times of the last explain call (ms, HIP events): permutation Z, explain kernels (with the tables of H and the upload of
  * the alpha powers), reduction / download; returns the number written. */
 int sbn_prover_explain_times(const sbn_prover* p, float* ms_out, int cap);
+
+/* Explain: the values and rows behind a failing permutation pair --------------------------------------- */
+/* Z column z checks the MULTISET of trace column lhs_z against that of column rhs_z (sbn_air_permutation_pair); the running
+ * product hides where they differ.  These calls compare the two columns of every chosen pair directly, as multisets of canonical
+ * 64-bit words: exact, no challenge, no seed, and the trace need not satisfy the AIR -- only the pair structure of the table is
+ * used.  Per pair, exact whatever per_pair is: differing_values = distinct values v with count_lhs(v) != count_rhs(v);
+ * excess_lhs = sum of max(count_lhs - count_rhs, 0), excess_rhs the same the other way; entries = min(differing_values,
+ * per_pair).  The differing values are listed SMALLEST first, ascending, at most per_pair of them; first_row_* is the smallest
+ * row that holds the value in that column, UINT64_MAX when the count is 0.  A table without Z columns gives nothing to write. */
+typedef struct sbn_perm_pair_stat { uint64_t differing_values, excess_lhs, excess_rhs, entries; } sbn_perm_pair_stat;
+typedef struct sbn_perm_diff_entry { uint64_t value, count_lhs, count_rhs, first_row_lhs, first_row_rhs; } sbn_perm_diff_entry;
+/* Host threads (SBN_HOST_THREADS; csrc/perm_diff.hpp: values below 2^16 in a signed histogram, the others sorted), one pair per
+ * task, no device looked for.  zs == NULL: all pairs (n_zs ignored), output index = z; else output index k is pair zs[k]
+ * (z >= num_zs: SBN_ERR_BAD_ARG).  stats_out: [n_out]; entries_out: [n_out][per_pair], may be NULL when per_pair == 0; of pair
+ * k's per_pair slots the first stats_out[k].entries are written.  Null arguments, tables and heights, and the canonical-form
+ * refusal (SBN_ERR_NON_CANONICAL naming the smallest index) as sbn_explain_rows_host. */
+int sbn_explain_permutations_host(const sbn_air_desc* air, const uint64_t* trace_col_major, uint32_t degree_bits,
+                                  const uint32_t* zs, size_t n_zs, size_t per_pair,
+                                  sbn_perm_pair_stat* stats_out, sbn_perm_diff_entry* entries_out);
+/* The same bytes for the loaded trace of a single-GPU prover (csrc/perm_diff.hip, csrc/kernels_permdiff.cuh): two workgroups per
+ * pair hold signed 32-bit histograms of half of [0, 2^16) each in 128 KiB of LDS, a second kernel re-reads the columns of the
+ * pairs that differ for counts and first rows.  A pair ends on one of three routes, all exact: BINS, every cell below 2^16 (the
+ * kernels alone); LIST, the cells >= 2^16 of the launch fitted a bounded list (4,096 cells) that the host diffs behind the binned
+ * values; DOWNLOAD, the list overflowed -- LookupStark at large heights always -- or per_pair > 1,024 and more binned values
+ * differ: the two columns come back and the host routine diffs them.  sbn_prover_describe reports the pairs of the last call by
+ * route as perm_diff_routes=bins:list:download.  SBN_ERR_BAD_ARG: a null argument, z >= num_zs, no trace loaded;
+ * SBN_ERR_UNSUPPORTED: the context of a split prover with world > 1.  Only per-proof scratch is overwritten: sbn_prover_prove
+ * gives the same words before and after. */
+int sbn_prover_explain_permutations(sbn_prover* p, const uint32_t* zs, size_t n_zs, size_t per_pair,
+                                    sbn_perm_pair_stat* stats_out, sbn_perm_diff_entry* entries_out);
+/* Times of the last sbn_prover_explain_permutations (ms): histogram kernel, rows pass (HIP events), download + host merge (host
+ * clock); returns the number written. */
+int sbn_prover_explain_permutation_times(const sbn_prover* p, float* ms_out, int cap);
 
 /* One-shot convenience with the reference's argument list:
  * prove(stark, &config, trace_poly_values, public_inputs) (src/curves/g1/exp.rs:818-825): a device context, then

@@ -8,6 +8,7 @@ from .api import (  # noqa: F401
     AIR_G1_OP, AIR_G1_EXP, AIR_G2_EXP, AIR_FQ12_EXP, AIR_FQ_EXP, AIR_FQ12_EXP_U64, AIR_MODULAR, AIR_FQ12_MUL, AIR_LOOKUP, AIR_FLAGS, AIR_FLAGS_U64, LookupStark, MyStark, FlagStark, FlagU64Stark, SbnError, StarkConfig, G1Stark, ModularStark, Fq12Stark, G1ExpStark, G2ExpStark, Fq12ExpStark,
     FqExpStark, Fq12ExpU64Stark, Prover, BatchProver, Verifier, Proof, TraceReport, check_trace_host,
     ConstraintBlock, RowExplanation, RowsExplanation, TraceExplanation, explain_rows_host, explain_trace_host,
+    PermutationExplanation, explain_permutations_host, PERM_PAIR_STAT, PERM_DIFF_ENTRY,
     prove, prove_cache_configure, prove_cache_stats, first_non_canonical, verify_stark_proof, commit_values, eval_constraints_host, poseidon_permute_batch, poseidon_permute_coop_batch, poseidon_permute_host, field_mul_batch, bn254_fq_batch, chain_instances, msm_num_units, msm_instances, msm_check_links, verify_msm, lib, lib_path, EXPORTS,
     G2_COFACTOR, generator, scalar_mul_instances, scalar_mul_check, mul_by_cofactor_check, verify_scalar_muls, verify_mul_by_cofactor,
     msm_batch_instances, msm_batch_check, verify_msms,

@@ -37,6 +37,7 @@ EXPORTS = [
     "sbn_prover_check_trace", "sbn_prover_check_times", "sbn_check_trace_host", "sbn_trace_segment_name",
     "sbn_air_constraint_blocks", "sbn_constraint_section_name", "sbn_air_permutation_pair", "sbn_explain_rows_host", "sbn_explain_trace_host",
     "sbn_prover_explain_rows", "sbn_prover_explain_trace", "sbn_prover_explain_times", "sbn_split_prover_explain_rows", "sbn_split_prover_explain_trace",
+    "sbn_explain_permutations_host", "sbn_prover_explain_permutations", "sbn_prover_explain_permutation_times",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_msm_num_units", "sbn_msm_instances", "sbn_batch_prover_prove_msm", "sbn_msm_check_links",
     "sbn_curve_generator", "sbn_g2_cofactor", "sbn_scalar_mul_instances", "sbn_prover_generate_trace_scalar_muls",
@@ -202,6 +203,9 @@ def lib():
         L.sbn_prover_explain_rows.argtypes = [vp, C.c_uint64, vp, sz, vp, vp]
         L.sbn_prover_explain_trace.argtypes = [vp, C.c_uint64, vp, vp]
         L.sbn_prover_explain_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+        L.sbn_explain_permutations_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, sz, vp, vp]
+        L.sbn_prover_explain_permutations.argtypes = [vp, vp, sz, sz, vp, vp]
+        L.sbn_prover_explain_permutation_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
         L.sbn_split_prover_explain_rows.argtypes = [vp, C.c_uint64, vp, sz, vp, vp]
         L.sbn_split_prover_explain_trace.argtypes = [vp, C.c_uint64, vp, vp]
         L.sbn_batch_prover_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(vp)]
@@ -1179,6 +1183,79 @@ class TraceExplanation:
         return all(np.array_equal(getattr(self, f), getattr(other, f)) for f in ("block_failing_rows", "block_first_row", "z_failing_rows", "z_first_row"))
 
 
+PERM_PAIR_STAT = np.dtype([(f, np.uint64) for f in ("differing_values", "excess_lhs", "excess_rhs", "entries")])                  # sbn_perm_pair_stat
+PERM_DIFF_ENTRY = np.dtype([(f, np.uint64) for f in ("value", "count_lhs", "count_rhs", "first_row_lhs", "first_row_rhs")])     # sbn_perm_diff_entry
+_NO_ROW = (1 << 64) - 1
+
+
+class PermutationExplanation:
+    """What explain_permutations found: the lhs column of every chosen permutation pair against its rhs column as multisets.
+    zs [n_out] is the pair of every output index, stats [n_out] a structured array (differing_values, excess_lhs, excess_rhs,
+    entries: exact whatever per_pair was), entries [n_out][per_pair] the differing values of each pair, smallest first (value,
+    count_lhs, count_rhs, first_row_lhs, first_row_rhs; a first row of 2^64 - 1 = the value is not in that column), of which
+    the first stats["entries"] are meaningful.  pairs lists the failing pairs in ascending z as dicts."""
+
+    def __init__(self, stark, zs, stats, entries):
+        self.stark, self.zs, self.stats, self.entries = stark, zs, stats, entries
+
+    @property
+    def ok(self):
+        return not self.stats["differing_values"].any()
+
+    @property
+    def pairs(self):
+        out = []
+        for k in sorted(np.nonzero(self.stats["differing_values"])[0], key=lambda k: int(self.zs[k])):
+            st, z = self.stats[k], int(self.zs[k])
+            lhs, rhs = self.stark.permutation_pair(z)
+            ents = [{f: (None if f.startswith("first_row") and int(e[f]) == _NO_ROW else int(e[f])) for f in PERM_DIFF_ENTRY.names}
+                    for e in self.entries[k, :int(st["entries"])]]
+            out.append({"z": z, "lhs_col": lhs, "rhs_col": rhs, "differing_values": int(st["differing_values"]),
+                        "excess_lhs": int(st["excess_lhs"]), "excess_rhs": int(st["excess_rhs"]), "entries": ents})
+        return out
+
+    def __str__(self):
+        if self.ok:
+            return "ok: the two columns of every permutation pair hold the same values"
+        cells = lambda k: f"{k:,} cell{'s' if k != 1 else ''}"   # noqa: E731
+        side = lambda c, r, name: f"{c:,} x {name}" + (f" (first row {r})" if r is not None else "")   # noqa: E731
+        lines = []
+        for q in self.pairs:
+            d, el, er = q["differing_values"], q["excess_lhs"], q["excess_rhs"]
+            more = f"{cells(el)} more on each side" if el == er else f"{cells(el)} more on lhs, {er:,} on rhs"
+            parts = ["Z %d (cols %d, %d): %s value%s differ%s, %s" % (q["z"], q["lhs_col"], q["rhs_col"], f"{d:,}", "" if d == 1 else "s", "s" if d == 1 else "", more)]
+            parts += ["%d: %s, %s" % (e["value"], side(e["count_lhs"], e["first_row_lhs"], "lhs"), side(e["count_rhs"], e["first_row_rhs"], "rhs")) for e in q["entries"]]
+            if len(q["entries"]) < d:
+                parts.append(f"{d - len(q['entries']):,} more not listed")
+            lines.append("; ".join(parts))
+        return "\n".join(lines)
+
+    def __repr__(self):
+        return f"<PermutationExplanation {int(np.count_nonzero(self.stats['differing_values']))} of {len(self.zs)} pairs differ>"
+
+    def __eq__(self, other):
+        if not isinstance(other, PermutationExplanation):
+            return NotImplemented
+        if not (np.array_equal(self.zs, other.zs) and np.array_equal(self.stats, other.stats)):
+            return False
+        return all(np.array_equal(self.entries[k, :int(m)], other.entries[k, :int(m)]) for k, m in enumerate(self.stats["entries"]))
+
+
+def _explain_permutations_buffers(stark, zs, per_pair):
+    """zs as the C calls take it (None: all pairs), the pair of every output index, and the two output arrays."""
+    Z = stark.num_permutation_zs()
+    zs = None if zs is None else np.ascontiguousarray(zs, dtype=np.uint32).reshape(-1)
+    which = np.arange(Z, dtype=np.uint32) if zs is None else zs
+    per_pair = int(per_pair)
+    if per_pair < 0:
+        raise SbnError(-1, "per_pair is negative")
+    return zs, which, per_pair, np.zeros(len(which), dtype=PERM_PAIR_STAT), np.zeros((len(which), per_pair), dtype=PERM_DIFF_ENTRY)
+
+
+def _opt_ptr(a):
+    return None if a is None or a.size == 0 else _ptr(a)
+
+
 def _explain_rows_buffers(stark, rows):
     rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
     B, Z = len(stark.constraint_blocks()), stark.num_permutation_zs()
@@ -1328,6 +1405,17 @@ def explain_trace_host(stark, trace, public_inputs, seed=0):
     return TraceExplanation(stark, bs, zs)
 
 
+def explain_permutations_host(stark, trace, zs=None, per_pair=8):
+    """The values and rows behind failing permutation pairs of `trace`, on host threads (sbn_explain_permutations_host): per
+    pair of zs (None: all) the exact multiset difference of its two columns, the per_pair smallest differing values listed.
+    The same PermutationExplanation as Prover.explain_permutations gives for the loaded trace."""
+    trace, _, bits = _host_trace_args(stark, trace, np.zeros(0, dtype=np.uint64))
+    zs, which, per_pair, st, en = _explain_permutations_buffers(stark, zs, per_pair)
+    _check(lib().sbn_explain_permutations_host(C.byref(stark._d), _ptr(trace), bits, None if zs is None else _ptr(zs), len(which), per_pair,
+                                               _opt_ptr(st), _opt_ptr(en)))
+    return PermutationExplanation(stark, which, st, en)
+
+
 class Prover:
     """Device context for one (table, degree_bits): buffers stay allocated across proofs.  lde="compact" (rate_bits > 1): the
     LDEs of the wide matrices are not kept, the opened rows are recomputed from the coefficients (include/sbn.h SBN_LDE_COMPACT);
@@ -1446,6 +1534,19 @@ class Prover:
         buf = (C.c_float * 3)()
         k = lib().sbn_prover_explain_times(self._h, buf, 3)
         return dict(zip(("perm_z", "explain", "download"), (float(buf[i]) for i in range(k))))
+
+    def explain_permutations(self, zs=None, per_pair=8):
+        """The values and rows behind failing permutation pairs of the loaded trace (sbn_prover_explain_permutations): signed
+        histograms in LDS, bit for bit what explain_permutations_host gives."""
+        zs, which, per_pair, st, en = _explain_permutations_buffers(self.stark, zs, per_pair)
+        _check(lib().sbn_prover_explain_permutations(self._h, None if zs is None else _ptr(zs), len(which), per_pair, _opt_ptr(st), _opt_ptr(en)))
+        return PermutationExplanation(self.stark, which, st, en)
+
+    def explain_permutation_times(self):
+        """Times of the last explain_permutations() in ms: the two kernels (HIP events), download + host merge (host clock)."""
+        buf = (C.c_float * 3)()
+        k = lib().sbn_prover_explain_permutation_times(self._h, buf, 3)
+        return dict(zip(("histogram", "rows", "download_merge"), (float(buf[i]) for i in range(k))))
 
     def prove(self):
         h = C.c_void_p()

@@ -1720,13 +1720,15 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
   snprintf(buf, sizeof buf,
            "abi=%d device=%d dev_bytes=%zu ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d ntt_lde_zero_aware=%d "
            "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d lde=%s lde_ring=%u lde_ring_bytes=%zu "
-           "fixed_columns=%d fixed_columns_range=%zu:%zu fixed_columns_skipped=%zu ignored=[%s]",
+           "fixed_columns=%d fixed_columns_range=%zu:%zu fixed_columns_skipped=%zu perm_diff_routes=%zu:%zu:%zu ignored=[%s]",
            SBN_ABI_VERSION, P->device, P->dev_bytes, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0, P->d_shift_za ? 1 : 0,
            chain, tracegen_host_threads(), (int)s.fq12_host_chain,
            (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, P->lde_storage == SBN_LDE_COMPACT ? "compact" : "full", P->ring_depth,
            P->d_ring ? (size_t)P->ring_depth * P->ntt_chunk * P->m * sizeof(u64) : (size_t)0,
            // the switch; the columns whose transforms this context keeps between proofs (0:0 none); how many the last prove() left untransformed
-           (int)s.fixed_columns, P->fixed_f0, P->fixed_f1, P->fixed_skipped, s.ignored.c_str());
+           (int)s.fixed_columns, P->fixed_f0, P->fixed_f1, P->fixed_skipped,
+           // pairs of the last sbn_prover_explain_permutations by route: bins alone, overflow list, downloaded columns (perm_diff.hip)
+           P->permdiff_routes[0], P->permdiff_routes[1], P->permdiff_routes[2], s.ignored.c_str());
   snprintf(out, cap, "%s", buf);
   return SBN_OK;
 }

@@ -1,5 +1,5 @@
 // The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
-// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip and trace_explain_fq12.hip (which check it)
+// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip, trace_explain_fq12.hip and perm_diff.hip (which check it)
 // and by lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of
 // include/sbn.h.
 #pragma once
@@ -166,6 +166,8 @@ struct sbn_prover {
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
   float check_ms[4] = {};                    // sbn_prover_check_trace: permutation Z, constraint kernels, reduction, download
   float explain_ms[3] = {};                  // sbn_prover_explain_*: permutation Z, explain kernels, reduction / download
+  float permdiff_ms[3] = {};                 // sbn_prover_explain_permutations: histogram, rows pass, download + host merge
+  size_t permdiff_routes[3] = {};            // ... pairs of its last call answered by the bins alone, with the overflow list, from downloaded columns
 };
 
 // Scratch of the calls that fill d_trace (the device witness generators of tracegen_device.hip, the row-major loads of
@@ -239,3 +241,8 @@ int launch_derived_columns(sbn_prover* P);
 // of the trace domain.
 void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]);
 void launch_trace_domain_tables(u64* xs, u64* lag_first, u64* lag_last, size_t n, u32 degree_bits, hipStream_t s);
+// trace_check.hip, shared with perm_diff.hip: the columns of permutation pair z; the tables and heights the host forms accept (as
+// sbn_prover_create); the canonical-form scan on the host pool, SBN_ERR_NON_CANONICAL naming the smallest index.
+void air_pair(const AirShape& as, size_t z, int& l, int& r);
+int host_table_check(const sbn_air_desc* air, uint32_t degree_bits, AirShape& as);
+int host_canonical_check(const uint64_t* trace, size_t words);

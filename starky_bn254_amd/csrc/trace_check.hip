@@ -278,12 +278,8 @@ static void host_perm_z(const HostCheck& hc, size_t z, int lc, int rc, u64* out)
 
 // What a host form owns while it runs: the alpha powers, the public-input constants of the Exp tables, the Z columns.
 struct HostStore { std::vector<F> apow[SBN_NCH]; std::vector<ExpPiConsts<F>> pic; std::vector<u64> zval; };
-// The argument checks of the host forms after their own null checks (tables and heights as sbn_prover_create accepts them, canonical
-// form), then the challenges, the tables and Z.
-static int host_setup(const sbn_air_desc* air, const uint64_t* trace, uint32_t degree_bits, const uint64_t* pi, size_t n_pi, uint64_t seed,
-                      HostCheck& hc, HostStore& hs) {
-  AirShape& as = hc.as;
-  // tables and heights as sbn_prover_create accepts them
+// Shared with perm_diff.hip (prover_ctx.hpp).  Tables and heights as sbn_prover_create accepts them:
+int host_table_check(const sbn_air_desc* air, uint32_t degree_bits, AirShape& as) {
   if (!air_shape(air, nullptr, as)) return fail(SBN_ERR_BAD_ARG, "unknown air kind / num_io");
   if (degree_bits < 9 || degree_bits > 22) return fail(SBN_ERR_UNSUPPORTED, "degree_bits out of range");
   const size_t n = (size_t)1 << degree_bits;
@@ -294,19 +290,31 @@ static int host_setup(const sbn_air_desc* air, const uint64_t* trace, uint32_t d
     if (as.kind != SBN_AIR_FQ12_EXP && as.kind != SBN_AIR_FQ12_EXP_U64 && degree_bits < 16)
       return fail(SBN_ERR_UNSUPPORTED, "G1_EXP / G2_EXP / FQ_EXP need >= 2^16 rows (u16 range check, range_check.rs:26)");
   }
+  return SBN_OK;
+}
+// canonical form, on the pool; the smallest bad index wins
+int host_canonical_check(const uint64_t* trace, size_t words) {
+  const size_t pieces = std::max<size_t>(1, std::min<size_t>(words >> 16, 256)), per = (words + pieces - 1) / pieces;
+  std::atomic<size_t> bad(words);
+  host_parallel_for(pieces, [&](size_t t) {
+    const size_t a = t * per, b = std::min(words, a + per);
+    for (size_t i = a; i < b; i++) if (trace[i] >= GLP) { size_t cur = bad.load(); while (i < cur && !bad.compare_exchange_weak(cur, i)) {} break; }
+  });
+  if (bad.load() < words) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", bad.load());
+  return SBN_OK;
+}
+// The argument checks of the host forms after their own null checks (tables and heights as sbn_prover_create accepts them, canonical
+// form), then the challenges, the tables and Z.
+static int host_setup(const sbn_air_desc* air, const uint64_t* trace, uint32_t degree_bits, const uint64_t* pi, size_t n_pi, uint64_t seed,
+                      HostCheck& hc, HostStore& hs) {
+  AirShape& as = hc.as;
+  if (int rc = host_table_check(air, degree_bits, as)) return rc;
+  const size_t n = (size_t)1 << degree_bits;
   if (n_pi != as.npi) return fail(SBN_ERR_BAD_ARG, "expected %zu public inputs, got %zu", as.npi, n_pi);
   if (n_pi && !pi) return fail(SBN_ERR_BAD_ARG, "null public inputs");
   for (size_t i = 0; i < n_pi; i++) if (pi[i] >= GLP) return fail(SBN_ERR_NON_CANONICAL, "public input %zu is not canonical", i);
   const size_t C = as.ncols, Z = as.nzs, words = C * n;
-  {  // canonical form, on the pool; the smallest bad index wins
-    const size_t pieces = std::max<size_t>(1, std::min<size_t>(words >> 16, 256)), per = (words + pieces - 1) / pieces;
-    std::atomic<size_t> bad(words);
-    host_parallel_for(pieces, [&](size_t t) {
-      const size_t a = t * per, b = std::min(words, a + per);
-      for (size_t i = a; i < b; i++) if (trace[i] >= GLP) { size_t cur = bad.load(); while (i < cur && !bad.compare_exchange_weak(cur, i)) {} break; }
-    });
-    if (bad.load() < words) return fail(SBN_ERR_NON_CANONICAL, "trace word %zu is not canonical", bad.load());
-  }
+  if (int rc = host_canonical_check(trace, words)) return rc;
   hc.n = n; hc.degree_bits = degree_bits; hc.trace = trace;
   check_challenges(as, degree_bits, pi, n_pi, seed, hc.gamma0, hc.gamma1, hc.alpha);
   std::vector<F>* apow = hs.apow;
@@ -397,7 +405,7 @@ static const char* SECTION_NAMES[BS_COUNT] = {
   "range_check_lookup", "range_table", "lookup"};
 extern "C" const char* sbn_constraint_section_name(int s) { return (s >= 0 && s < (int)BS_COUNT) ? SECTION_NAMES[s] : ""; }
 
-static void air_pair(const AirShape& as, size_t z, int& l, int& r) {
+void air_pair(const AirShape& as, size_t z, int& l, int& r) {
   if (as.kind == SBN_AIR_G1_OP) G1OpShape::pair((int)z, l, r);
   else if (as.kind == SBN_AIR_LOOKUP) LookupShape().pair((int)z, l, r);
   else if (is_op_air(as.kind)) OpShape(as.kind).pair((int)z, l, r);
