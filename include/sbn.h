@@ -498,6 +498,65 @@ int sbn_prover_explain_permutations(sbn_prover* p, const uint32_t* zs, size_t n_
  * clock); returns the number written. */
 int sbn_prover_explain_permutation_times(const sbn_prover* p, float* ms_out, int cap);
 
+/* Name the cells: a loaded trace against its canonical witness ----------------------------------------- */
+/* A block is the finest unit the explain calls above reach.  For the five Exp tables the library knows more: the witness is a
+ * function of the instance list, and the instance list sits in the public inputs.  The CANONICAL WITNESS of a list is the trace the
+ * five Exp generators of sbn_generate_trace_* write for it -- bit for bit what sbn_prover_generate_trace produces.  These calls
+ * compare a trace with it word by word: exact, no challenge, no seed, deterministic, and every count is exact whatever cells_cap is.
+ *   cells, main_cells       the differing cells over all columns, and those of them in columns [0, sbn_air_num_main_columns)
+ *   rows, columns           the rows and the columns that hold at least one differing cell
+ *   first_row, first_column the smallest (row, column), row first, over the main columns; over the derived columns when no main
+ *                           cell differs; UINT64_MAX when none does
+ *   listed                  entries written to cells_out = min(cells, cells_cap): ascending (row, column) over the MAIN columns, and
+ *                           only once those are exhausted the same order over the derived columns.  Main columns come first because
+ *                           the chains make every later row depend on earlier ones: the first main cell is the cause, while a sorted
+ *                           range-check column may differ on much earlier rows as a consequence.
+ *   pi_words, first_pi_word the loaded public-input words that differ from the public inputs the instances determine (in practice
+ *                           wrong outputs; with a given `ios` also input words); UINT64_MAX when none does
+ * column_cells_out, column_first_row_out (both optional): [sbn_air_num_columns] words, the differing cells of each column and its
+ * first differing row (all ones when it has none).  cells_cap: 0 .. 65536, 0 asks for the statistics only (cells_out may be NULL). */
+typedef struct sbn_witness_diff {
+  uint32_t struct_size;          /* caller sets sizeof(sbn_witness_diff) */
+  uint32_t reserved;
+  uint64_t cells, main_cells, rows, columns;
+  uint64_t first_row, first_column;
+  uint64_t listed;
+  uint64_t pi_words, first_pi_word;
+} sbn_witness_diff;
+typedef struct sbn_witness_cell { uint64_t row, column, got, want; } sbn_witness_cell;
+/* The instance list the public inputs of an Exp table carry: the inverse of the tables' generate_public_inputs, on the host.  Per
+ * instance the public inputs are x, offset, exponent, output; limbs are u32 on the curves and in FQ_EXP, 16-bit in the Fq12 tables,
+ * the FQ12_EXP_U64 exponent is one word.  ios_out: [num_io] rows in the layout sbn_generate_trace_* takes; outputs_out (optional):
+ * [num_io] values in the word shape of x.  SBN_ERR_BAD_ARG: a null argument, a kind that is no Exp table, n_pi that is not num_io
+ * instances, or a limb out of its range, naming the public-input index. */
+int sbn_instances_from_public_inputs(int32_t kind, const uint64_t* public_inputs, size_t n_pi, size_t num_io,
+                                     uint32_t* ios_out, uint32_t* outputs_out);
+/* The loaded trace of a single-GPU prover against the canonical witness of `ios` (csrc/witness_diff.hip,
+ * csrc/kernels_witdiff.cuh).  ios == NULL: the instances are taken from the loaded public inputs; a given ios is compared as given.
+ * The witness is generated on the device into the coefficient buffer, which is idle between proofs; one kernel compares the two
+ * matrices, a second lists the cells of the chosen rows.  Refusals, in this order, the argument checks before a device is looked for:
+ *   1. SBN_ERR_BAD_ARG: a null p or report, a wrong struct_size, cells_cap > 65536, cells_out NULL with a cap, num_io not the table's;
+ *   2. SBN_ERR_BAD_ARG: no trace loaded;  3. SBN_ERR_UNSUPPORTED: a table that is no Exp table (no instance list in its public
+ *   inputs);  4. SBN_ERR_UNSUPPORTED: the context of a split prover;  5. SBN_ERR_UNSUPPORTED: a height the device witness does not
+ *   cover (G1 / G2 / FQ_EXP outside 2^16 .. 2^18 rows: use sbn_diff_witness_host);  6. what the generator says about the list (a value
+ *   >= p, a non-canonical exponent, SBN_ERR_WITNESS), behind "no canonical witness: ".
+ * SBN_OK = the diff ran; whether anything differs is in the report.  On EVERY path the loaded trace, its public inputs and the
+ * loaded state come out as they went in -- also after a refused list: sbn_prover_prove gives the same words before and after. */
+int sbn_prover_diff_witness(sbn_prover* p, const uint32_t* ios, size_t num_io, sbn_witness_diff* report,
+                            uint64_t* column_cells_out, uint64_t* column_first_row_out,
+                            sbn_witness_cell* cells_out, size_t cells_cap);
+/* Times of the last sbn_prover_diff_witness (ms): the device witness, the compare kernel (HIP events), listing + downloads (host
+ * clock); returns the number written. */
+int sbn_prover_diff_witness_times(const sbn_prover* p, float* ms_out, int cap);
+/* The host twin, no device looked for: the host generator runs on the host pool (SBN_HOST_THREADS) into a temporary of the trace's
+ * size and the matrices are compared in tiles of 64 x 64.  The same report, arrays and list.  Any height the host generators take,
+ * so also G1 / G2 / FQ_EXP above 2^18 rows.  Refusals as above without 2, 4 and 5; degree_bits or n_pi that do not match the table:
+ * SBN_ERR_BAD_ARG. */
+int sbn_diff_witness_host(const sbn_air_desc* air, const uint64_t* trace_col_major, uint32_t degree_bits,
+                          const uint64_t* public_inputs, size_t n_pi, const uint32_t* ios, size_t num_io,
+                          sbn_witness_diff* report, uint64_t* column_cells_out, uint64_t* column_first_row_out,
+                          sbn_witness_cell* cells_out, size_t cells_cap);
+
 /* One-shot convenience with the reference's argument list:
  * prove(stark, &config, trace_poly_values, public_inputs) (src/curves/g1/exp.rs:818-825): a device context, then
  * sbn_prover_prove_host_trace.  The context is created and destroyed per call unless sbn_prove_cache_configure keeps it. */

@@ -88,6 +88,33 @@ pub struct sbn_block_stat {
     pub first_row: u64,
 }
 
+/// include/sbn.h `sbn_witness_diff`: the loaded trace against the canonical witness of its instance list (`u64::MAX` = none).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct sbn_witness_diff {
+    pub struct_size: u32,
+    pub reserved: u32,
+    pub cells: u64,
+    pub main_cells: u64,
+    pub rows: u64,
+    pub columns: u64,
+    pub first_row: u64,
+    pub first_column: u64,
+    pub listed: u64,
+    pub pi_words: u64,
+    pub first_pi_word: u64,
+}
+
+/// include/sbn.h `sbn_witness_cell`: one differing cell, the loaded word and the canonical one.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct sbn_witness_cell {
+    pub row: u64,
+    pub column: u64,
+    pub got: u64,
+    pub want: u64,
+}
+
 pub const SBN_AIR_G1_OP: i32 = 1;
 pub const SBN_AIR_G1_EXP: i32 = 2;
 pub const SBN_AIR_G2_EXP: i32 = 3;
@@ -143,6 +170,10 @@ extern "C" {
     pub fn sbn_prover_explain_rows(p: *mut sbn_prover, seed: u64, rows: *const u64, n_rows: usize, block_flags_out: *mut u8, z_flags_out: *mut u8) -> i32;
     pub fn sbn_prover_explain_trace(p: *mut sbn_prover, seed: u64, block_stats_out: *mut sbn_block_stat, z_stats_out: *mut sbn_block_stat) -> i32;
     pub fn sbn_prover_explain_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
+    pub fn sbn_instances_from_public_inputs(kind: i32, public_inputs: *const u64, n_pi: usize, num_io: usize, ios_out: *mut u32, outputs_out: *mut u32) -> i32;
+    pub fn sbn_prover_diff_witness(p: *mut sbn_prover, ios: *const u32, num_io: usize, report: *mut sbn_witness_diff, column_cells_out: *mut u64, column_first_row_out: *mut u64, cells_out: *mut sbn_witness_cell, cells_cap: usize) -> i32;
+    pub fn sbn_prover_diff_witness_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
+    pub fn sbn_diff_witness_host(air: *const sbn_air_desc, trace_col_major: *const u64, degree_bits: u32, public_inputs: *const u64, n_pi: usize, ios: *const u32, num_io: usize, report: *mut sbn_witness_diff, column_cells_out: *mut u64, column_first_row_out: *mut u64, cells_out: *mut sbn_witness_cell, cells_cap: usize) -> i32;
     pub fn sbn_prover_stage_times(p: *const sbn_prover, ms_out: *mut f32, cap: i32) -> i32;
     pub fn sbn_prover_stage_name(i: i32) -> *const c_char;
     pub fn sbn_prover_describe(p: *const sbn_prover, out: *mut c_char, cap: usize) -> i32;

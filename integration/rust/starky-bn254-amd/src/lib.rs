@@ -349,6 +349,35 @@ impl Prover {
         })
     }
 
+    /// The loaded trace against the canonical witness of its instance list, cell by cell (sbn_prover_diff_witness): the witness is
+    /// rebuilt on the device from `ios` (`num_io` rows in the layout `prove_ios` takes), or with `None` from the instances the
+    /// loaded public inputs carry; up to `cells` (at most 65,536) differing cells are listed, main columns first.  For the trace
+    /// of the reference's own `generate_trace`, loaded by `prove` / `prove_host_trace`, this names the cell where the two
+    /// generators part.  `Ok` means the diff ran; the verdict is `WitnessDiff::ok()`.  The trace stays loaded, also after a refusal.
+    pub fn diff_witness(&mut self, ios: Option<&[u32]>, num_io: usize, cells: usize) -> Result<WitnessDiff> {
+        let mut raw = ffi::sbn_witness_diff { struct_size: std::mem::size_of::<ffi::sbn_witness_diff>() as u32, ..Default::default() };
+        let mut listed = vec![ffi::sbn_witness_cell::default(); cells];
+        let list_ptr = if cells == 0 { ptr::null_mut() } else { listed.as_mut_ptr() };
+        let ios_ptr = ios.map_or(ptr::null(), |w| w.as_ptr());
+        check(
+            unsafe { ffi::sbn_prover_diff_witness(self.raw, ios_ptr, num_io, &mut raw, ptr::null_mut(), ptr::null_mut(), list_ptr, cells) },
+            "sbn_prover_diff_witness",
+        )?;
+        listed.truncate(raw.listed as usize);
+        let at = |r: u64| if r == u64::MAX { None } else { Some(r as usize) };
+        Ok(WitnessDiff {
+            cells: raw.cells as usize,
+            main_cells: raw.main_cells as usize,
+            rows: raw.rows as usize,
+            columns: raw.columns as usize,
+            first_row: at(raw.first_row),
+            first_column: at(raw.first_column),
+            pi_words: raw.pi_words as usize,
+            first_pi_word: at(raw.first_pi_word),
+            listed,
+        })
+    }
+
     /// Per-stage device times of the last prove() in milliseconds (sbn_prover_stage_times / sbn_prover_stage_name).
     pub fn stage_times(&self) -> Vec<(String, f32)> {
         let mut ms = [0f32; 32];
@@ -380,6 +409,29 @@ pub struct TraceReport {
 impl TraceReport {
     pub fn ok(&self) -> bool {
         self.failing_rows == 0
+    }
+}
+
+/// `Prover::diff_witness`: how the loaded trace differs from the canonical witness of its instances.  The counts are exact whatever
+/// the cap; `listed` holds the first differing cells in ascending (row, column) order over the main columns, the derived columns
+/// only behind them -- the first listed main cell is the cause, what follows it the consequence.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct WitnessDiff {
+    pub cells: usize,
+    pub main_cells: usize,
+    pub rows: usize,
+    pub columns: usize,
+    pub first_row: Option<usize>,
+    pub first_column: Option<usize>,
+    /// loaded public inputs that differ from those the instances determine (in practice wrong outputs)
+    pub pi_words: usize,
+    pub first_pi_word: Option<usize>,
+    pub listed: Vec<ffi::sbn_witness_cell>,
+}
+
+impl WitnessDiff {
+    pub fn ok(&self) -> bool {
+        self.cells == 0 && self.pi_words == 0
     }
 }
 

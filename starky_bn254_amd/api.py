@@ -38,6 +38,7 @@ EXPORTS = [
     "sbn_air_constraint_blocks", "sbn_constraint_section_name", "sbn_air_permutation_pair", "sbn_explain_rows_host", "sbn_explain_trace_host",
     "sbn_prover_explain_rows", "sbn_prover_explain_trace", "sbn_prover_explain_times", "sbn_split_prover_explain_rows", "sbn_split_prover_explain_trace",
     "sbn_explain_permutations_host", "sbn_prover_explain_permutations", "sbn_prover_explain_permutation_times",
+    "sbn_instances_from_public_inputs", "sbn_prover_diff_witness", "sbn_prover_diff_witness_times", "sbn_diff_witness_host",
     "sbn_batch_prover_create", "sbn_batch_prover_prove_ios", "sbn_batch_prover_destroy",
     "sbn_msm_num_units", "sbn_msm_instances", "sbn_batch_prover_prove_msm", "sbn_msm_check_links",
     "sbn_curve_generator", "sbn_g2_cofactor", "sbn_scalar_mul_instances", "sbn_prover_generate_trace_scalar_muls",
@@ -111,6 +112,12 @@ class _TraceReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_segments", C.c_uint32), ("rows", C.c_uint64), ("failing_rows", C.c_uint64),
                 ("first_failing_row", C.c_uint64), ("seg_failing_rows", C.c_uint64 * 4), ("seg_first_row", C.c_uint64 * 4),
                 ("num_zs", C.c_uint32), ("z_split", C.c_uint32)]
+
+
+class _WitnessDiff(C.Structure):
+    """sbn_witness_diff (include/sbn.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(n, C.c_uint64) for n in (
+        "cells", "main_cells", "rows", "columns", "first_row", "first_column", "listed", "pi_words", "first_pi_word")]
 
 
 class _ConstraintBlock(C.Structure):
@@ -206,6 +213,11 @@ def lib():
         L.sbn_explain_permutations_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, sz, vp, vp]
         L.sbn_prover_explain_permutations.argtypes = [vp, vp, sz, sz, vp, vp]
         L.sbn_prover_explain_permutation_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+        if hasattr(L, "sbn_prover_diff_witness"):   # (a library named by SBN_LIB may predate the witness diff)
+            L.sbn_instances_from_public_inputs.argtypes = [C.c_int32, vp, sz, sz, vp, vp]
+            L.sbn_prover_diff_witness.argtypes = [vp, vp, sz, C.POINTER(_WitnessDiff), vp, vp, vp, sz]
+            L.sbn_prover_diff_witness_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+            L.sbn_diff_witness_host.argtypes = [C.POINTER(_AirDesc), vp, u32, vp, sz, vp, sz, C.POINTER(_WitnessDiff), vp, vp, vp, sz]
         L.sbn_split_prover_explain_rows.argtypes = [vp, C.c_uint64, vp, sz, vp, vp]
         L.sbn_split_prover_explain_trace.argtypes = [vp, C.c_uint64, vp, vp]
         L.sbn_batch_prover_create.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), u32, u32, C.POINTER(vp)]
@@ -1416,6 +1428,124 @@ def explain_permutations_host(stark, trace, zs=None, per_pair=8):
     return PermutationExplanation(stark, which, st, en)
 
 
+_EXP_IO_WORDS = {AIR_G1_EXP: (16, 8), AIR_G2_EXP: (32, 8), AIR_FQ_EXP: (8, 8), AIR_FQ12_EXP: (96, 8), AIR_FQ12_EXP_U64: (96, 2)}   # u32 words of x and of the exponent
+WITNESS_CELL = np.dtype([(f, np.uint64) for f in ("row", "column", "got", "want")])   # sbn_witness_cell
+
+
+class WitnessDiff:
+    """What diff_witness found (sbn_witness_diff): the trace against the canonical witness of its instance list, cell by cell.
+    cells, main_cells, rows, columns and pi_words are exact whatever the cap was; first_row, first_column and first_pi_word are None
+    when nothing differs there; column_cells / column_first_row [num_columns] are the per-column counts and first differing rows
+    (2^64 - 1: none); raw_cells is the list as the library wrote it (WITNESS_CELL), `listed` the same cells as dicts: ascending
+    (row, column) over the main columns, the derived columns only behind them.  Each listed cell carries its instance and its row
+    inside the instance and names what checks it: the constraint blocks whose column range holds the column, or the permutation
+    pairs of a permuted column."""
+
+    def __init__(self, stark, raw, column_cells, column_first_row, cells):
+        self.stark = stark
+        none = lambda v: None if v == _NO_ROW else int(v)   # noqa: E731
+        self.cells, self.main_cells, self.rows, self.columns = int(raw.cells), int(raw.main_cells), int(raw.rows), int(raw.columns)
+        self.first_row, self.first_column = none(raw.first_row), none(raw.first_column)
+        self.pi_words, self.first_pi_word = int(raw.pi_words), none(raw.first_pi_word)
+        self.column_cells, self.column_first_row = column_cells, column_first_row
+        self.raw_cells = cells[:int(raw.listed)]
+        self.rows_per_instance = _rows_per_instance(stark)
+
+    @property
+    def ok(self):
+        return self.cells == 0 and self.pi_words == 0
+
+    def checked_by(self, column):
+        """Names of what checks `column`: the constraint blocks whose column range holds it, else its permutation pairs."""
+        names = getattr(self.stark, "_column_checks", None)
+        if names is None:   # once per table: a wide trace lists thousands of cells
+            by_block, by_pair = {}, {}
+            for b in self.stark.constraint_blocks():
+                for c in range(b.col_first, b.col_first + b.col_count):
+                    by_block.setdefault(c, {})[str(b).split(" [")[0].split(" cols ")[0]] = None   # (a lookup pair's two constraints are two blocks of one name)
+            for z in range(self.stark.num_permutation_zs()):
+                l, r = self.stark.permutation_pair(z)
+                for c in {l, r}:
+                    by_pair.setdefault(c, []).append("Z %d (cols %d, %d)" % (z, l, r))
+            names = self.stark._column_checks = (by_block, by_pair)
+        return list(names[0].get(column, ())) or list(names[1].get(column, ()))
+
+    @property
+    def listed(self):
+        rpi = self.rows_per_instance
+        return [{"row": int(c["row"]), "column": int(c["column"]), "got": int(c["got"]), "want": int(c["want"]), "instance": int(c["row"]) // rpi,
+                 "instance_row": int(c["row"]) % rpi, "main": int(c["column"]) < self.stark.num_main_columns, "checked_by": self.checked_by(int(c["column"]))}
+                for c in self.raw_cells]
+
+    def __str__(self):
+        if self.ok:
+            return "ok: the trace is the canonical witness of its instances"
+        plural = lambda k, w: f"{k:,} {w}{'' if k == 1 else 's'}"   # noqa: E731
+        parts = []
+        if self.cells:
+            parts.append(f"{plural(self.cells, 'cell')} differ{'s' if self.cells == 1 else ''} in {plural(self.columns, 'column')} on {plural(self.rows, 'row')} "
+                         f"({self.main_cells:,} in the main columns)")
+        for c in self.listed:
+            by = ", ".join(c["checked_by"])
+            parts.append(f"row {c['row']} (instance {c['instance']}, row {c['instance_row']} of {self.rows_per_instance}) col {c['column']} [{by}]: "
+                         f"got {c['got']:#x}, canonical {c['want']:#x}")
+        if len(self.raw_cells) < self.cells:
+            parts.append(f"{self.cells - len(self.raw_cells):,} more not listed")
+        if self.pi_words:
+            parts.append(f"{plural(self.pi_words, 'public input')} differ{'s' if self.pi_words == 1 else ''}, first word {self.first_pi_word}")
+        return "; ".join(parts)
+
+    def __repr__(self):
+        return f"<WitnessDiff {self.cells} cells, {self.pi_words} public inputs differ>"
+
+    def _key(self):
+        return (self.cells, self.main_cells, self.rows, self.columns, self.first_row, self.first_column, self.pi_words, self.first_pi_word)
+
+    def __eq__(self, other):
+        if not isinstance(other, WitnessDiff):
+            return NotImplemented
+        return self._key() == other._key() and np.array_equal(self.column_cells, other.column_cells) and \
+            np.array_equal(self.column_first_row, other.column_first_row) and np.array_equal(self.raw_cells, other.raw_cells)
+
+
+def _diff_witness_buffers(stark, ios, cells):
+    """ios as the C calls take it (None: from the public inputs), the report, the two per-column arrays and the list."""
+    cells = int(cells)
+    if cells < 0:
+        raise SbnError(-1, "cells is negative")
+    ios = None if ios is None else np.ascontiguousarray(ios, dtype=np.uint32)
+    words = _EXP_IO_WORDS.get(stark.kind)
+    if ios is not None and words is not None and ios.shape != (stark.num_io, 2 * words[0] + words[1]):
+        raise SbnError(-1, f"ios must be {stark.num_io} rows of {2 * words[0] + words[1]} u32 words")
+    C_ = stark.num_columns
+    return ios, cells, _WitnessDiff(struct_size=C.sizeof(_WitnessDiff)), np.zeros(C_, dtype=np.uint64), np.zeros(C_, dtype=np.uint64), np.zeros(cells, dtype=WITNESS_CELL)
+
+
+def diff_witness_host(stark, trace, public_inputs, ios=None, cells=16):
+    """`trace` against the canonical witness of its instance list, cell by cell, on host threads (sbn_diff_witness_host): the
+    instances are `ios`, or those the public inputs carry.  The same WitnessDiff as Prover.diff_witness gives for the loaded trace;
+    any height the host generators take."""
+    trace, pi, bits = _host_trace_args(stark, trace, public_inputs)
+    ios, cells, raw, cc, cf, ce = _diff_witness_buffers(stark, ios, cells)
+    _check(lib().sbn_diff_witness_host(C.byref(stark._d), _ptr(trace), bits, _ptr(pi), len(pi), None if ios is None else _ptr(ios), stark.num_io,
+                                       C.byref(raw), _ptr(cc), _ptr(cf), _opt_ptr(ce), cells))
+    return WitnessDiff(stark, raw, cc, cf, ce)
+
+
+def instances_from_public_inputs(stark, pi):
+    """(ios, outputs) of the public inputs of an Exp table (sbn_instances_from_public_inputs): the instance rows generate_trace
+    takes, [num_io][2 xw + ew] u32, and the outputs in the word shape of x, [num_io][xw] u32."""
+    pi = np.ascontiguousarray(pi, dtype=np.uint64).reshape(-1)
+    iow = _EXP_IO_WORDS.get(stark.kind)
+    if iow is None:
+        raise SbnError(-1, "not an Exp table")
+    xw, ew = iow
+    ios = np.zeros((stark.num_io, 2 * xw + ew), dtype=np.uint32)
+    outs = np.zeros((stark.num_io, xw), dtype=np.uint32)
+    _check(lib().sbn_instances_from_public_inputs(stark.kind, _ptr(pi), len(pi), stark.num_io, _ptr(ios), _ptr(outs)))
+    return ios, outs
+
+
 class Prover:
     """Device context for one (table, degree_bits): buffers stay allocated across proofs.  lde="compact" (rate_bits > 1): the
     LDEs of the wide matrices are not kept, the opened rows are recomputed from the coefficients (include/sbn.h SBN_LDE_COMPACT);
@@ -1547,6 +1677,20 @@ class Prover:
         buf = (C.c_float * 3)()
         k = lib().sbn_prover_explain_permutation_times(self._h, buf, 3)
         return dict(zip(("histogram", "rows", "download_merge"), (float(buf[i]) for i in range(k))))
+
+    def diff_witness(self, ios=None, cells=16):
+        """The loaded trace against the canonical witness of its instance list, cell by cell (sbn_prover_diff_witness): the
+        witness is rebuilt on the device from `ios`, or from the instances the loaded public inputs carry; `cells` differing
+        cells are listed (0 .. 65536).  The trace stays loaded, also after a refused list."""
+        ios, cells, raw, cc, cf, ce = _diff_witness_buffers(self.stark, ios, cells)
+        _check(lib().sbn_prover_diff_witness(self._h, None if ios is None else _ptr(ios), self.stark.num_io, C.byref(raw), _ptr(cc), _ptr(cf), _opt_ptr(ce), cells))
+        return WitnessDiff(self.stark, raw, cc, cf, ce)
+
+    def diff_times(self):
+        """Times of the last diff_witness() in ms: device witness, compare kernel (HIP events), listing + downloads (host clock)."""
+        buf = (C.c_float * 3)()
+        k = lib().sbn_prover_diff_witness_times(self._h, buf, 3)
+        return dict(zip(("witness", "compare", "list_download"), (float(buf[i]) for i in range(k))))
 
     def prove(self):
         h = C.c_void_p()

@@ -100,6 +100,47 @@ static inline size_t exp_io_words(int kind) {
     case SBN_AIR_FQ12_EXP_U64: return 194; default: return 0;
   }
 }
+// The public inputs of one instance of an Exp table (g1_exp_io_to_columns, src/curves/g1/exp.rs:124-135, and its twins): x[W]
+// offset[W] exp[EW] output[W]; u32 limbs on the curves and in Fq, 16-bit limbs in Fq12 (exponent: eight u32 limbs, or one u64 in
+// FQ12_EXP_U64).  Read by the link checks of msm.hip, msm_batch.hip and powers.hip and by witness_diff.hip, which inverts it.
+struct PiLayout {
+  size_t W, EW, xw, ew;   // W / EW: public inputs per value / exponent; xw / ew: u32 words of the same in an instance row of `ios`
+  bool limb16;
+  size_t per() const { return 3 * W + EW; }
+};
+static inline bool pi_layout(int kind, PiLayout& L) {
+  switch (kind) {
+    case SBN_AIR_G1_EXP: L = {16, 8, 16, 8, false}; return true;
+    case SBN_AIR_G2_EXP: L = {32, 8, 32, 8, false}; return true;
+    case SBN_AIR_FQ_EXP: L = {8, 8, 8, 8, false}; return true;
+    case SBN_AIR_FQ12_EXP: L = {192, 8, 96, 8, true}; return true;
+    case SBN_AIR_FQ12_EXP_U64: L = {192, 1, 96, 2, true}; return true;
+    default: L = {0, 0, 0, 0, false}; return false;
+  }
+}
+static inline PiLayout pi_layout(int kind) { PiLayout L; pi_layout(kind, L); return L; }
+// a value (xw u32 words) as the W public inputs that carry it, and an exponent (ew words) as its EW
+static inline void value_to_pi(const PiLayout& L, const uint32_t* w, uint64_t* out) {
+  if (!L.limb16) { for (size_t i = 0; i < L.W; i++) out[i] = w[i]; return; }
+  for (size_t i = 0; i < L.W; i++) out[i] = (w[i >> 1] >> (16 * (i & 1))) & 0xffff;
+}
+static inline void exp_to_pi(const PiLayout& L, const uint32_t* w, uint64_t* out) {
+  if (L.EW == 1) { out[0] = (uint64_t)w[0] | ((uint64_t)w[1] << 32); return; }
+  for (size_t i = 0; i < L.EW; i++) out[i] = w[i];
+}
+// the inverses: false and *bad = the index of the first public input wider than its limb (a u64 exponent takes any word)
+static inline bool value_from_pi(const PiLayout& L, const uint64_t* p, uint32_t* w, size_t* bad) {
+  const uint64_t lim = L.limb16 ? 0xffffULL : 0xffffffffULL;
+  for (size_t i = 0; i < L.W; i++) if (p[i] > lim) { *bad = i; return false; }
+  if (!L.limb16) for (size_t i = 0; i < L.W; i++) w[i] = (uint32_t)p[i];
+  else for (size_t i = 0; i < L.xw; i++) w[i] = (uint32_t)(p[2 * i] | (p[2 * i + 1] << 16));
+  return true;
+}
+static inline bool exp_from_pi(const PiLayout& L, const uint64_t* p, uint32_t* w, size_t* bad) {
+  if (L.EW == 1) { w[0] = (uint32_t)p[0]; w[1] = (uint32_t)(p[0] >> 32); return true; }
+  for (size_t i = 0; i < L.EW; i++) { if (p[i] > 0xffffffffULL) { *bad = i; return false; } w[i] = (uint32_t)p[i]; }
+  return true;
+}
 static inline ExpShape exp_shape(const AirShape& a) { return ExpShape(exp_e(a.kind), (int)a.num_io); }
 // The shape-constant columns [f0, f1) of a table: functions of the row index, the height and num_io alone, so every trace the
 // generators write for one shape holds the same words there.  Exp tables: the periodic pulse (counter and witness; absent in the u64

@@ -12,32 +12,7 @@
 using namespace sbn;
 
 namespace {
-// the public inputs of one instance (g1_exp_io_to_columns, src/curves/g1/exp.rs:124-135, and its twins): x[W] offset[W] exp[EW]
-// output[W]; u32 limbs on the curves and in Fq, 16-bit limbs in Fq12 (exponent: eight u32 limbs, or one u64 in FQ12_EXP_U64)
-struct PiLayout {
-  size_t W, EW, xw, ew;   // W / EW: public inputs per value / exponent; xw / ew: u32 words of the same in `terms` and `start`
-  bool limb16;
-  size_t per() const { return 3 * W + EW; }
-};
-bool pi_layout(int kind, PiLayout& L) {
-  switch (kind) {
-    case SBN_AIR_G1_EXP: L = {16, 8, 16, 8, false}; return true;
-    case SBN_AIR_G2_EXP: L = {32, 8, 32, 8, false}; return true;
-    case SBN_AIR_FQ_EXP: L = {8, 8, 8, 8, false}; return true;
-    case SBN_AIR_FQ12_EXP: L = {192, 8, 96, 8, true}; return true;
-    case SBN_AIR_FQ12_EXP_U64: L = {192, 1, 96, 2, true}; return true;
-    default: return false;
-  }
-}
-// a value of `start` / `terms` (xw u32 words) as the W public inputs that carry it
-void value_to_pi(const PiLayout& L, const uint32_t* w, uint64_t* out) {
-  if (!L.limb16) { for (size_t i = 0; i < L.W; i++) out[i] = w[i]; return; }
-  for (size_t i = 0; i < L.W; i++) out[i] = (w[i >> 1] >> (16 * (i & 1))) & 0xffff;
-}
-void exp_to_pi(const PiLayout& L, const uint32_t* w, uint64_t* out) {
-  if (L.EW == 1) { out[0] = (uint64_t)w[0] | ((uint64_t)w[1] << 32); return; }
-  for (size_t i = 0; i < L.EW; i++) out[i] = w[i];
-}
+// (the public inputs of one instance: PiLayout, host_common.hpp)
 bool same(const uint64_t* a, const uint64_t* b, size_t n) { return memcmp(a, b, n * sizeof(uint64_t)) == 0; }
 }  // namespace
 

@@ -181,21 +181,9 @@ int derive_field(const Tab& t, const uint32_t* terms, size_t M, const Layout& L,
   return SBN_OK;
 }
 
-// ---- sbn_msm_batch_check: the public inputs of one instance are x[PW] offset[PW] exp[EW] output[PW] (g1_exp_io_to_columns,
+// ---- sbn_msm_batch_check: the public inputs of one instance are x[W] offset[W] exp[EW] output[W] (g1_exp_io_to_columns,
 // src/curves/g1/exp.rs:124-135, and its twins): u32 limbs on the curves and in Fq, 16-bit limbs in Fq12 -----------------------------
-struct PiLayout {
-  size_t PW, EW;
-  bool limb16;
-  size_t per() const { return 3 * PW + EW; }
-};
-PiLayout pi_layout(int kind, const Tab& t) {
-  if (t.xw == 96) return {192, kind == SBN_AIR_FQ12_EXP_U64 ? (size_t)1 : (size_t)8, true};
-  return {t.xw, 8, false};
-}
-void value_to_pi(const PiLayout& P, const uint32_t* w, uint64_t* out) {
-  if (!P.limb16) { for (size_t i = 0; i < P.PW; i++) out[i] = w[i]; return; }
-  for (size_t i = 0; i < P.PW; i++) out[i] = (w[i >> 1] >> (16 * (i & 1))) & 0xffff;
-}
+// (PiLayout: host_common.hpp)
 bool same(const uint64_t* a, const uint64_t* b, size_t n) { return memcmp(a, b, n * sizeof(uint64_t)) == 0; }
 
 template <int E>
@@ -285,18 +273,18 @@ extern "C" int sbn_msm_batch_check(int32_t kind, size_t num_io, const uint64_t* 
   for (size_t u = 0; u < units; u++) if (!public_inputs[u]) return fail(SBN_ERR_BAD_ARG, "null public inputs (unit %zu)", u);
   if (!below_p(starts, t.values() * (int)start_count)) return fail(SBN_ERR_BAD_ARG, "%s >= p (starts)", t.E ? "coordinate" : "coefficient");
   const Layout L(lengths, segments, M);
-  const PiLayout P = pi_layout((int)kind, t);
-  const size_t per = P.per(), oX = 0, oOff = P.PW, oExp = 2 * P.PW, oOut = 2 * P.PW + P.EW;
+  const PiLayout P = pi_layout((int)kind);
+  const size_t per = P.per(), oX = 0, oOff = P.W, oExp = 2 * P.W, oOut = 2 * P.W + P.EW;
   auto inst = [&](size_t g) { return public_inputs[g / num_io] + per * (g % num_io); };
   const uint64_t lim = P.limb16 ? 0xffffULL : 0xffffffffULL;
   const uint64_t* last = inst(M - 1);
-  std::vector<uint64_t> want(P.PW);
+  std::vector<uint64_t> want(P.W);
   std::vector<uint32_t> outs(t.xw * M);
   for (size_t g = 0; g < units * num_io; g++) {
     const uint64_t* p = inst(g);
     if (g >= M) {   // a pad instance is instance M - 1 again
       static const char* const field[4] = {"x", "offset", "exponent", "output"};
-      const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {P.PW, P.PW, P.EW, P.PW};
+      const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {P.W, P.W, P.EW, P.W};
       for (int f = 0; f < 4; f++)
         if (!same(p + at[f], last + at[f], len[f])) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (pad): %s differs from instance %zu", g, field[f], M - 1);
       continue;
@@ -304,19 +292,19 @@ extern "C" int sbn_msm_batch_check(int32_t kind, size_t num_io, const uint64_t* 
     const size_t s = L.seg[g];
     if (terms) {
       value_to_pi(P, terms + t.T() * g, want.data());
-      if (!same(p + oX, want.data(), P.PW)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): x differs from the caller's term", g, s);
+      if (!same(p + oX, want.data(), P.W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): x differs from the caller's term", g, s);
       const uint32_t* e = terms + t.T() * g + t.xw;
       uint64_t ep[8];
-      if (P.EW == 1) ep[0] = (uint64_t)e[0] | ((uint64_t)e[1] << 32); else for (int i = 0; i < 8; i++) ep[i] = e[i];
+      exp_to_pi(P, e, ep);
       if (!same(p + oExp, ep, P.EW)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): exponent differs from the caller's term", g, s);
     }
     if (g == L.head[s]) {
       value_to_pi(P, starts + (start_count == 1 ? 0 : t.xw * s), want.data());
-      if (!same(p + oOff, want.data(), P.PW)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): offset differs from the start of the segment", g, s);
-    } else if (!same(p + oOff, inst(g - 1) + oOut, P.PW))
+      if (!same(p + oOff, want.data(), P.W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): offset differs from the start of the segment", g, s);
+    } else if (!same(p + oOff, inst(g - 1) + oOut, P.W))
       return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): offset differs from the output of instance %zu", g, s, g - 1);
     // a limb wider than its slot is no output of the table
-    for (size_t i = 0; i < P.PW; i++)
+    for (size_t i = 0; i < P.W; i++)
       if (p[oOut + i] > lim) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): output limb %zu is out of range", g, s, i);
     uint32_t* o = outs.data() + t.xw * g;
     if (!P.limb16) for (size_t i = 0; i < t.xw; i++) o[i] = (uint32_t)p[oOut + i];

@@ -55,21 +55,7 @@ void towers(const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_
   });
 }
 
-// the public inputs of one instance: x[PW] offset[PW] exp[EW] output[PW]; u32 limbs in Fq, 16-bit limbs in Fq12 (exponent: eight
-// u32 limbs, or one u64 in FQ12_EXP_U64)
-struct PiLayout {
-  size_t PW, EW;
-  bool limb16;
-  size_t per() const { return 3 * PW + EW; }
-};
-PiLayout pi_layout(int kind) {
-  if (kind == SBN_AIR_FQ_EXP) return {8, 8, false};
-  return {192, kind == SBN_AIR_FQ12_EXP_U64 ? (size_t)1 : (size_t)8, true};
-}
-void value_to_pi(const PiLayout& L, const uint32_t* w, uint64_t* out) {
-  if (!L.limb16) { for (size_t i = 0; i < L.PW; i++) out[i] = w[i]; return; }
-  for (size_t i = 0; i < L.PW; i++) out[i] = (w[i >> 1] >> (16 * (i & 1))) & 0xffff;
-}
+// (the public inputs of one instance: PiLayout, host_common.hpp)
 bool same(const uint64_t* a, const uint64_t* b, size_t n) { return memcmp(a, b, n * sizeof(uint64_t)) == 0; }
 
 // kind, then the arguments every entry point shares, in the order of the header's refusals
@@ -124,34 +110,34 @@ extern "C" int sbn_power_check(int32_t kind, size_t num_io, const uint64_t* cons
     return fail(SBN_ERR_VERIFY_FAILED, "%zu units given, %zu towers of depth %zu in tables of %zu have %zu units", units, count, depth, num_io, sbn_msm_num_units(M, num_io));
   for (size_t u = 0; u < units; u++) if (!public_inputs[u]) return fail(SBN_ERR_BAD_ARG, "null public inputs (unit %zu)", u);
   auto inst = [&](size_t g) { return public_inputs[g / num_io] + per * (g % num_io); };
-  const size_t oX = 0, oOff = L.PW, oExp = 2 * L.PW, oOut = 2 * L.PW + L.EW;
+  const size_t oX = 0, oOff = L.W, oExp = 2 * L.W, oOut = 2 * L.W + L.EW;
   const uint64_t lim = L.limb16 ? 0xffffULL : 0xffffffffULL;
   const uint64_t* last = inst(M - 1);
-  std::vector<uint64_t> want(L.PW);
+  std::vector<uint64_t> want(L.W);
   std::vector<uint32_t> out(W);
   for (size_t g = 0; g < units * num_io; g++) {
     const uint64_t* p = inst(g);
     if (g >= M) {   // a pad instance is instance M - 1 again
       static const char* const field[4] = {"x", "offset", "exponent", "output"};
-      const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {L.PW, L.PW, L.EW, L.PW};
+      const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {L.W, L.W, L.EW, L.W};
       for (int f = 0; f < 4; f++)
         if (!same(p + at[f], last + at[f], len[f])) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (pad): %s differs from instance %zu", g, field[f], M - 1);
       continue;
     }
     const size_t k = g / depth, l = g % depth;
-    for (size_t i = 0; i < L.PW; i++)
+    for (size_t i = 0; i < L.W; i++)
       if (p[oOff + i] != (i == 0 ? 1u : 0u)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (tower %zu, level %zu): offset is not one", g, k, l);
     const uint32_t* e = exps + (exp_count == 1 ? 0 : ew * k);
     uint64_t ep[8];
-    if (L.EW == 1) ep[0] = (uint64_t)e[0] | ((uint64_t)e[1] << 32); else for (int i = 0; i < 8; i++) ep[i] = e[i];
+    exp_to_pi(L, e, ep);
     if (!same(p + oExp, ep, L.EW)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (tower %zu, level %zu): exponent differs from the caller's", g, k, l);
     if (l == 0) {
       value_to_pi(L, bases + W * k, want.data());
-      if (!same(p + oX, want.data(), L.PW)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (tower %zu, level 0): x differs from the caller's base", g, k);
-    } else if (!same(p + oX, inst(g - 1) + oOut, L.PW))
+      if (!same(p + oX, want.data(), L.W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (tower %zu, level 0): x differs from the caller's base", g, k);
+    } else if (!same(p + oX, inst(g - 1) + oOut, L.W))
       return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (tower %zu, level %zu): x differs from the output of instance %zu", g, k, l, g - 1);
     // a limb wider than its slot, or a coefficient >= p, is no output of the table
-    for (size_t i = 0; i < L.PW; i++)
+    for (size_t i = 0; i < L.W; i++)
       if (p[oOut + i] > lim) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (tower %zu, level %zu): output limb %zu is out of range", g, k, l, i);
     if (!L.limb16) for (size_t i = 0; i < W; i++) out[i] = (uint32_t)p[oOut + i];
     else for (size_t i = 0; i < W; i++) out[i] = (uint32_t)(p[oOut + 2 * i] | (p[oOut + 2 * i + 1] << 16));

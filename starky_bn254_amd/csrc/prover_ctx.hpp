@@ -1,5 +1,5 @@
 // The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
-// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip, trace_explain_fq12.hip and perm_diff.hip (which check it)
+// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip, trace_explain_fq12.hip, perm_diff.hip and witness_diff.hip (which check it)
 // and by lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of
 // include/sbn.h.
 #pragma once
@@ -168,6 +168,7 @@ struct sbn_prover {
   float explain_ms[3] = {};                  // sbn_prover_explain_*: permutation Z, explain kernels, reduction / download
   float permdiff_ms[3] = {};                 // sbn_prover_explain_permutations: histogram, rows pass, download + host merge
   size_t permdiff_routes[3] = {};            // ... pairs of its last call answered by the bins alone, with the overflow list, from downloaded columns
+  float witdiff_ms[3] = {};                  // sbn_prover_diff_witness: device witness, compare kernel, listing + downloads
 };
 
 // Scratch of the calls that fill d_trace (the device witness generators of tracegen_device.hip, the row-major loads of
