@@ -1003,7 +1003,7 @@ def fixed_columns_check(stark, degree_bits, block):
     return bool(match.value)
 
 
-_NO_ROW = (1 << 64) - 1   # UINT64_MAX: "no such row" in sbn_trace_report
+_NO_ROW = (1 << 64) - 1   # UINT64_MAX: "no such row" in the reports of the trace diagnostics
 
 
 class TraceReport:
@@ -1197,7 +1197,6 @@ class TraceExplanation:
 
 PERM_PAIR_STAT = np.dtype([(f, np.uint64) for f in ("differing_values", "excess_lhs", "excess_rhs", "entries")])                  # sbn_perm_pair_stat
 PERM_DIFF_ENTRY = np.dtype([(f, np.uint64) for f in ("value", "count_lhs", "count_rhs", "first_row_lhs", "first_row_rhs")])     # sbn_perm_diff_entry
-_NO_ROW = (1 << 64) - 1
 
 
 class PermutationExplanation:
@@ -1641,11 +1640,15 @@ class Prover:
         _check(lib().sbn_prover_check_trace(self._h, seed, C.byref(raw), _ptr(row_flags)))
         return TraceReport(raw, row_flags, _rows_per_instance(self.stark))
 
+    def _times(self, getter, keys):
+        """What a *_times getter of the C ABI wrote, under `keys` in their order."""
+        buf = (C.c_float * len(keys))()
+        k = getter(self._h, buf, len(keys))
+        return dict(zip(keys, (float(buf[i]) for i in range(k))))
+
     def check_times(self):
         """Device times of the last check_trace() in ms (HIP events)."""
-        buf = (C.c_float * 4)()
-        k = lib().sbn_prover_check_times(self._h, buf, 4)
-        return dict(zip(("perm_z", "constraints", "reduction", "download"), (float(buf[i]) for i in range(k))))
+        return self._times(lib().sbn_prover_check_times, ("perm_z", "constraints", "reduction", "download"))
 
     def explain_rows(self, rows, seed=0):
         """Which constraint blocks and Z columns the listed rows of the loaded trace break (sbn_prover_explain_rows)."""
@@ -1661,9 +1664,7 @@ class Prover:
 
     def explain_times(self):
         """Device times of the last explain_rows() / explain_trace() in ms (HIP events)."""
-        buf = (C.c_float * 3)()
-        k = lib().sbn_prover_explain_times(self._h, buf, 3)
-        return dict(zip(("perm_z", "explain", "download"), (float(buf[i]) for i in range(k))))
+        return self._times(lib().sbn_prover_explain_times, ("perm_z", "explain", "download"))
 
     def explain_permutations(self, zs=None, per_pair=8):
         """The values and rows behind failing permutation pairs of the loaded trace (sbn_prover_explain_permutations): signed
@@ -1674,9 +1675,7 @@ class Prover:
 
     def explain_permutation_times(self):
         """Times of the last explain_permutations() in ms: the two kernels (HIP events), download + host merge (host clock)."""
-        buf = (C.c_float * 3)()
-        k = lib().sbn_prover_explain_permutation_times(self._h, buf, 3)
-        return dict(zip(("histogram", "rows", "download_merge"), (float(buf[i]) for i in range(k))))
+        return self._times(lib().sbn_prover_explain_permutation_times, ("histogram", "rows", "download_merge"))
 
     def diff_witness(self, ios=None, cells=16):
         """The loaded trace against the canonical witness of its instance list, cell by cell (sbn_prover_diff_witness): the
@@ -1688,9 +1687,7 @@ class Prover:
 
     def diff_times(self):
         """Times of the last diff_witness() in ms: device witness, compare kernel (HIP events), listing + downloads (host clock)."""
-        buf = (C.c_float * 3)()
-        k = lib().sbn_prover_diff_witness_times(self._h, buf, 3)
-        return dict(zip(("witness", "compare", "list_download"), (float(buf[i]) for i in range(k))))
+        return self._times(lib().sbn_prover_diff_witness_times, ("witness", "compare", "list_download"))
 
     def prove(self):
         h = C.c_void_p()

@@ -17,6 +17,7 @@
 // limb convolutions need no per-thread arrays -- operands stream from L1/L2.
 #pragma once
 #include "gl.cuh"
+#include <type_traits>
 
 static constexpr int SBN_NCH = 2;              // StarkConfig.num_challenges (standard_fast_config)
 // alpha^k tables are sized per table at run time: one entry per constraint of the whole stream (AIR + permutation checks:
@@ -1005,4 +1006,27 @@ GL_HD void permutation_checks(Cons<P>& cs, const Row& row, const ZRow& zrow, con
     }
   }
   if (z0 == 0 && z1 == num_zs) cs.rem = base;
+}
+
+// ---- which table ------------------------------------------------------------------------------------------------------------------
+// The one description of the eleven tables by kind (the sbn_air_kind values of include/sbn.h, 1 .. 11, as OpShape and the KIND
+// template arguments of the evaluators' callers spell them).  An unknown kind never gets here: air_shape (host_common.hpp) refuses it.
+// E of the ExpShape of an Exp table (kinds 2 .. 6)
+GL_HD constexpr int air_exp_e(int kind) { return kind == 4 ? 12 : (kind == 6 ? 13 : (kind == 3 ? 2 : (kind == 5 ? 0 : 1))); }
+// the lhs / rhs columns of permutation pair z; es: the table's ExpShape, built once by the caller and read for the Exp tables only
+GL_HD void air_pair(int kind, const ExpShape& es, int z, int& lhs, int& rhs) {
+  if (kind == 1) G1OpShape::pair(z, lhs, rhs);
+  else if (kind == 9) LookupShape().pair(z, lhs, rhs);
+  else if (kind == 7 || kind == 8) OpShape(kind).pair(z, lhs, rhs);
+  else es.pair(z, lhs, rhs);
+}
+// f(std::integral_constant<int, KIND>{}) for the table's kind: the one switch from a run-time kind to a template argument
+template <class Fn>
+inline void for_air_kind(int kind, Fn&& f) {
+  switch (kind) {
+#define SBN_AIR_KIND(K) case K: f(std::integral_constant<int, K>{}); break;
+    SBN_AIR_KIND(1) SBN_AIR_KIND(2) SBN_AIR_KIND(3) SBN_AIR_KIND(4) SBN_AIR_KIND(5) SBN_AIR_KIND(6)
+    SBN_AIR_KIND(7) SBN_AIR_KIND(8) SBN_AIR_KIND(9) SBN_AIR_KIND(10) SBN_AIR_KIND(11)
+#undef SBN_AIR_KIND
+  }
 }

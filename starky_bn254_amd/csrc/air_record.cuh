@@ -87,7 +87,7 @@ GL_HD void record_row(Cons<RF>& cs, const Row& row, int num_io, int nconstraints
   else if (KIND == 11) flag_u64_eval(cs, row, FlagU64Shape(num_io));
   else if (KIND == 7 || KIND == 8) op_eval<KIND>(cs, row, OpShape(KIND));
   else {
-    constexpr int E = KIND == 4 ? 12 : (KIND == 6 ? 13 : (KIND == 3 ? 2 : (KIND == 5 ? 0 : 1)));
+    constexpr int E = air_exp_e(KIND);
     exp_eval<E>(cs, row, ExpShape(E, num_io), (const ExpPiConsts<RF>*)pic, 0);
   }
 }

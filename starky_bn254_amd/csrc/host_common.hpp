@@ -61,7 +61,6 @@ struct AirShape {
   int kind; u32 num_io;
   size_t ncols, npi, npairs, nzs, nconstraints;
 };
-static inline int exp_e(int kind) { return kind == SBN_AIR_FQ12_EXP ? 12 : (kind == SBN_AIR_FQ12_EXP_U64 ? 13 : (kind == SBN_AIR_G2_EXP ? 2 : (kind == SBN_AIR_FQ_EXP ? 0 : 1))); }
 static inline bool air_shape(const sbn_air_desc* air, const sbn_config* cfg, AirShape& s) {
   if (!air) return false;
   s.kind = air->kind; s.num_io = air->num_io;
@@ -83,7 +82,7 @@ static inline bool air_shape(const sbn_air_desc* air, const sbn_config* cfg, Air
     s.ncols = sh.num_cols(); s.npi = 0; s.npairs = 0; s.nconstraints = sh.num_constraints();
   } else if (air->kind == SBN_AIR_G1_EXP || air->kind == SBN_AIR_G2_EXP || air->kind == SBN_AIR_FQ12_EXP || air->kind == SBN_AIR_FQ_EXP || air->kind == SBN_AIR_FQ12_EXP_U64) {
     if (air->num_io == 0 || air->num_io > (u32)G1EXP_MAX_IO || (air->num_io & (air->num_io - 1))) return false;
-    ExpShape sh(exp_e(air->kind), (int)air->num_io);
+    ExpShape sh(air_exp_e(air->kind), (int)air->num_io);
     s.ncols = sh.num_cols; s.npi = sh.num_pi; s.npairs = sh.num_pairs(); s.nconstraints = sh.num_constraints();
   } else return false;
   // num_permutation_batches = ceil(pairs*num_challenges / (constraint_degree-1)), constraint_degree = 3
@@ -141,7 +140,9 @@ static inline bool exp_from_pi(const PiLayout& L, const uint64_t* p, uint32_t* w
   for (size_t i = 0; i < L.EW; i++) { if (p[i] > 0xffffffffULL) { *bad = i; return false; } w[i] = (uint32_t)p[i]; }
   return true;
 }
-static inline ExpShape exp_shape(const AirShape& a) { return ExpShape(exp_e(a.kind), (int)a.num_io); }
+static inline ExpShape exp_shape(const AirShape& a) { return ExpShape(air_exp_e(a.kind), (int)a.num_io); }
+// the columns of permutation pair z of a table (air.cuh air_pair)
+static inline void air_pair(const AirShape& a, size_t z, int& l, int& r) { air_pair(a.kind, exp_shape(a), (int)z, l, r); }
 // The shape-constant columns [f0, f1) of a table: functions of the row index, the height and num_io alone, so every trace the
 // generators write for one shape holds the same words there.  Exp tables: the periodic pulse (counter and witness; absent in the u64
 // table), the io-pulse counter, 2 num_io (witness, pulse) pairs and the range check's table column -- what tg::periodic_kernel and

@@ -10,6 +10,7 @@
 //                differing values than the rows pass holds: both columns are downloaded and diffed by diff_columns.
 // Every route is exact.  Scratch is P->d_part alone (per-proof scratch, 64 n words): the pairs are taken in chunks that fit it.
 #include "prover_ctx.hpp"
+#include "trace_host.hpp"
 #include "perm_diff.hpp"
 #include "kernels_permdiff.cuh"
 #include <atomic>
@@ -60,19 +61,17 @@ extern "C" int sbn_explain_permutations_host(const sbn_air_desc* air, const uint
 
 extern "C" int sbn_prover_explain_permutations(sbn_prover* P, const uint32_t* zs, size_t n_zs, size_t per_pair, sbn_perm_pair_stat* stats_out,
                                                sbn_perm_diff_entry* entries_out) {
-  if (!P) return fail(SBN_ERR_BAD_ARG, "null argument");
-  if (P->sp && P->sp->comm.world > 1) return fail(SBN_ERR_UNSUPPORTED, "explain runs on single-GPU provers (this one is rank %u of %u)", P->sp->comm.rank, P->sp->comm.world);
-  if (!P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
+  if (int rc = diag_enter(P, "explain", false)) return rc;
   std::vector<pd::Cols> cols;
   if (int rc = chosen_pairs(P->air, zs, n_zs, cols)) return rc;
   const size_t K = cols.size(), n = P->n;
   if (K && (!stats_out || (per_pair && !entries_out))) return fail(SBN_ERR_BAD_ARG, "null argument");
-  for (int i = 0; i < 3; i++) { P->permdiff_ms[i] = 0; P->permdiff_routes[i] = 0; }
+  float* const times = P->diag_ms[DIAG_PERMDIFF];
+  for (int i = 0; i < 3; i++) { times[i] = 0; P->permdiff_routes[i] = 0; }
   if (!K) return SBN_OK;
-  HIPC(hipSetDevice(P->device));
   if (int rc = perm_hist_setup(P->device)) return rc;
   hipStream_t st = P->stream;
-  hipEvent_t* ev = P->ev;   // the stage events are idle outside prove()
+  hipEvent_t* ev = P->ev;
 
   // d_part: [list count, 16 bytes][statistics][half counts][entries] -- the block that comes back -- then the list, the candidate
   // slots and the columns of the pairs
@@ -115,7 +114,7 @@ extern "C" int sbn_prover_explain_permutations(sbn_prover* P, const uint32_t* zs
     HIPC(hipEventRecord(ev[2], st));
     HIPC(hipStreamSynchronize(st));
     float ms;
-    for (int i = 0; i < 2; i++) { HIPC(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); P->permdiff_ms[i] += ms; }
+    for (int i = 0; i < 2; i++) { HIPC(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); times[i] += ms; }
 
     const auto t0 = std::chrono::steady_clock::now();
     // the count, the statistics and the half counts lie together; the caller's memory and these vectors are pageable: plain copies
@@ -161,14 +160,9 @@ extern "C" int sbn_prover_explain_permutations(sbn_prover* P, const uint32_t* zs
       P->permdiff_routes[1]++;
     }
     h_list.clear();
-    P->permdiff_ms[2] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    times[2] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return SBN_OK;
 }
 
-extern "C" int sbn_prover_explain_permutation_times(const sbn_prover* P, float* ms, int cap) {
-  if (!P || !ms) return 0;
-  const int k = std::min(cap, 3);
-  for (int i = 0; i < k; i++) ms[i] = P->permdiff_ms[i];
-  return k;
-}
+extern "C" int sbn_prover_explain_permutation_times(const sbn_prover* P, float* ms, int cap) { return P ? copy_times(P->diag_ms[DIAG_PERMDIFF], 3, ms, cap) : 0; }

@@ -842,10 +842,7 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
     std::vector<PairCols> pairs(Z);
     for (size_t z = 0; z < Z; z++) {
       int l, r;
-      if (as.kind == SBN_AIR_G1_OP) G1OpShape::pair((int)z, l, r);
-      else if (as.kind == SBN_AIR_LOOKUP) LookupShape().pair((int)z, l, r);
-      else if (is_op_air(as.kind)) OpShape(as.kind).pair((int)z, l, r);
-      else exp_shape(as).pair((int)z, l, r);
+      air_pair(as, z, l, r);
       pairs[z].lhs = l; pairs[z].rhs = r;
     }
     if (!rc && Z) hipc(hipMemcpy(P->d_pairs, pairs.data(), Z * sizeof(PairCols), hipMemcpyHostToDevice), "hipMemcpy");
@@ -889,10 +886,7 @@ extern "C" void sbn_prover_destroy(sbn_prover* P) {
 }
 
 extern "C" int sbn_prover_stage_times(const sbn_prover* P, float* ms, int cap) {
-  if (!P || !ms) return 0;
-  int k = std::min(cap, (int)(ST_COUNT + EX_COUNT));
-  for (int i = 0; i < k; i++) ms[i] = P->stage_ms[i];
-  return k;
+  return P ? copy_times(P->stage_ms, ST_COUNT + EX_COUNT, ms, cap) : 0;
 }
 extern "C" const char* sbn_prover_stage_name(int i) { return (i >= 0 && i < ST_COUNT + EX_COUNT) ? STAGE_NAMES[i] : ""; }
 
@@ -906,19 +900,7 @@ static void launch_quotient_kind(sbn_prover* P, const QuotientParams& qp, size_t
   if (qp.seg_mask & 2u) hipLaunchKernelGGL((quotient_kernel<KIND, 1>), g1, dim3(256), 0, P->stream, qp, qp.apow[0], qp.apow[1], qp.pic);
 }
 int launch_quotient_parts(sbn_prover* P, const QuotientParams& qp, size_t qblocks) {
-  switch (P->air.kind) {
-    case SBN_AIR_G1_OP: launch_quotient_kind<1>(P, qp, qblocks); break;
-    case SBN_AIR_G1_EXP: launch_quotient_kind<2>(P, qp, qblocks); break;
-    case SBN_AIR_G2_EXP: launch_quotient_kind<3>(P, qp, qblocks); break;
-    case SBN_AIR_FQ_EXP: launch_quotient_kind<5>(P, qp, qblocks); break;
-    case SBN_AIR_FQ12_EXP_U64: launch_quotient_kind<6>(P, qp, qblocks); break;
-    case SBN_AIR_MODULAR: launch_quotient_kind<7>(P, qp, qblocks); break;
-    case SBN_AIR_FQ12_MUL: launch_quotient_kind<8>(P, qp, qblocks); break;
-    case SBN_AIR_LOOKUP: launch_quotient_kind<9>(P, qp, qblocks); break;
-    case SBN_AIR_FLAGS: launch_quotient_kind<10>(P, qp, qblocks); break;
-    case SBN_AIR_FLAGS_U64: launch_quotient_kind<11>(P, qp, qblocks); break;
-    default: launch_quotient_kind<4>(P, qp, qblocks); break;
-  }
+  for_air_kind(P->air.kind, [&](auto K) { launch_quotient_kind<decltype(K)::value>(P, qp, qblocks); });
   HIPC(hipGetLastError());
   return 0;
 }
@@ -975,7 +957,7 @@ void quotient_segments(const sbn_prover* P, const F alphas[SBN_NCH], QuotientPar
   // (Measured and dropped: the AIR tail on a third stream beside the other two -- 1.22 -> 1.32 ms for the stage, G2 2.0 -> 2.3.)
   qp.zsplit = (int)(Z / 2);
   qp.lookups_in_perm = P->set.quotient_lookups == 1;   // measured slower (quotient stage 1.18 -> 1.25 ms for G1): an experiment switch only
-  const u64 n_tail = is_exp_air(P->air.kind) ? (u64)ExpShape(exp_e(P->air.kind), (int)P->air.num_io).num_tail_constraints() : 0;
+  const u64 n_tail = is_exp_air(P->air.kind) ? (u64)exp_shape(P->air).num_tail_constraints() : 0;
   const u64 after[4] = {n_tail + 2 * (u64)Z, 2 * (u64)Z, 0, 0};
   qp.seg_count[0] = (int)(P->air.nconstraints - n_tail); qp.seg_count[1] = (int)n_tail;
   qp.seg_count[2] = qp.seg_count[3] = 2 * (int)Z;

@@ -1,7 +1,7 @@
 // The prover context, declarations only: what one sbn_prover holds between create and destroy.  Included by prover.hip, by
-// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip, trace_explain_fq12.hip, perm_diff.hip and witness_diff.hip (which check it)
-// and by lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of
-// include/sbn.h.
+// tracegen_device.hip and trace_load.hip (which fill the trace), by trace_check.hip, trace_explain.hip, trace_explain_fq12.hip,
+// perm_diff.hip and witness_diff.hip (the diagnostics of a loaded trace; what their host forms share is trace_host.hpp) and by
+// lde_compact.hip (the launchers of the compact storage); every other unit reaches the prover through the C ABI of include/sbn.h.
 #pragma once
 #include "host_common.hpp"
 #include "settings.hpp"
@@ -25,6 +25,12 @@ enum Stage {
   ST_OPENINGS, ST_FRI_COMBINE, ST_FRI_LAYERS, ST_POW, ST_QUERIES, ST_COUNT
 };
 enum Extra { EX_TRACE_ABSORB_MS, EX_TRACE_ABSORB_LAUNCHES, EX_Z_ABSORB_MS, EX_Z_ABSORB_LAUNCHES, EX_TRACEGEN_MS, EX_COMM_MS, EX_COUNT };
+// The diagnostics of a loaded trace and the times each keeps of its last call (sbn_prover.diag_ms):
+//   DIAG_CHECK    sbn_prover_check_trace           4: permutation Z, constraint kernels, reduction, download
+//   DIAG_EXPLAIN  sbn_prover_explain_*             3: permutation Z, explain kernels, reduction / download
+//   DIAG_PERMDIFF sbn_prover_explain_permutations  3: histogram, rows pass, download + host merge
+//   DIAG_WITDIFF  sbn_prover_diff_witness          3: device witness, compare kernel, listing + downloads
+enum Diag { DIAG_CHECK, DIAG_EXPLAIN, DIAG_PERMDIFF, DIAG_WITDIFF, DIAG_COUNT };
 static constexpr int MAX_CHUNKS = 512;
 // The pinned staging ring of one prover (pinned_ring.hpp; trace_load.hip): 4 slots of 16 MiB = 64 MiB of pinned host memory,
 // allocated by the first call that uploads a host trace.
@@ -164,11 +170,8 @@ struct sbn_prover {
   hipEvent_t rows_transposed[2] = {};        // main stream: its transposition has left staging buffer b
   unsigned long long* d_first_bad = nullptr; // smallest index of a trace word >= p (all ones: none), folded by the scans
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
-  float check_ms[4] = {};                    // sbn_prover_check_trace: permutation Z, constraint kernels, reduction, download
-  float explain_ms[3] = {};                  // sbn_prover_explain_*: permutation Z, explain kernels, reduction / download
-  float permdiff_ms[3] = {};                 // sbn_prover_explain_permutations: histogram, rows pass, download + host merge
-  size_t permdiff_routes[3] = {};            // ... pairs of its last call answered by the bins alone, with the overflow list, from downloaded columns
-  float witdiff_ms[3] = {};                  // sbn_prover_diff_witness: device witness, compare kernel, listing + downloads
+  float diag_ms[DIAG_COUNT][4] = {};         // the times of the last call of each diagnostic (enum Diag), what its *_times getter copies
+  size_t permdiff_routes[3] = {};            // sbn_prover_explain_permutations: pairs of its last call answered by the bins alone, with the overflow list, from downloaded columns
 };
 
 // Scratch of the calls that fill d_trace (the device witness generators of tracegen_device.hip, the row-major loads of
@@ -238,12 +241,25 @@ struct DevWords {
 // (derived_columns_covered: SBN_OK, or SBN_ERR_UNSUPPORTED with the message).
 int derived_columns_covered(const AirShape& as, size_t n);
 int launch_derived_columns(sbn_prover* P);
-// trace_check.hip, shared with trace_explain.hip: the seed-to-challenge transcript of a check and the kernel that fills the tables
-// of the trace domain.
-void check_challenges(const AirShape& as, u32 degree_bits, const u64* pi, size_t n_pi, u64 seed, F& gamma0, F& gamma1, F alphas[SBN_NCH]);
-void launch_trace_domain_tables(u64* xs, u64* lag_first, u64* lag_last, size_t n, u32 degree_bits, hipStream_t s);
-// trace_check.hip, shared with perm_diff.hip: the columns of permutation pair z; the tables and heights the host forms accept (as
-// sbn_prover_create); the canonical-form scan on the host pool, SBN_ERR_NON_CANONICAL naming the smallest index.
-void air_pair(const AirShape& as, size_t z, int& l, int& r);
-int host_table_check(const sbn_air_desc* air, uint32_t degree_bits, AirShape& as);
-int host_canonical_check(const uint64_t* trace, size_t words);
+// What every *_times getter of the C ABI does: the first min(cap, count) of src into ms_out; returns the number written.
+static inline int copy_times(const float* src, int count, float* ms_out, int cap) {
+  if (!ms_out) return 0;
+  const int k = std::min(cap, count);
+  for (int i = 0; i < k; i++) ms_out[i] = src[i];
+  return k;
+}
+// trace_check.hip: the way into a device diagnostic of the loaded trace.  diag_refuse_split: SBN_ERR_UNSUPPORTED "<what> runs on
+// single-GPU provers ..." for a split context of more than one rank, with any_split of any size.  diag_enter: the refusals the
+// diagnostics share, in this order -- a null context, the split as above, no trace loaded -- then the context's device made current;
+// the caller goes on with P->stream and P->ev (the stage events are idle outside prove()).
+int diag_refuse_split(const sbn_prover* P, const char* what, bool any_split);
+int diag_enter(sbn_prover* P, const char* what, bool any_split);
+// trace_check.hip: what the trace check and explain set up on the device before their own kernels.  The challenges of `seed`; Z of
+// the loaded trace into P->d_zval between ev[0] and ev[1]; the tables of H (g^i, [i == 0], [i == n - 1]) in the first three planes
+// of P->d_zpow; the alpha tables (upload_alpha_tables); last = 1 / g.  All on P->stream.
+struct TraceDomain {
+  F gamma0, gamma1, alphas[SBN_NCH];
+  const u64 *xs, *lag_first, *lag_last;
+  u64 last;
+};
+int trace_domain_setup(sbn_prover* P, uint64_t seed, TraceDomain& td);

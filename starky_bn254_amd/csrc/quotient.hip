@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void quotient_kernel(QuotientParams p, cons
       else permutation_checks(cs, row, zrow, sh, p.num_zs, F(p.gamma0), F(p.gamma1), p.zsplit, p.num_zs);
     }
   } else {
-    constexpr int E = KIND == 4 ? 12 : (KIND == 6 ? 13 : (KIND == 3 ? 2 : (KIND == 5 ? 0 : 1)));
+    constexpr int E = air_exp_e(KIND);
     ExpShape sh(E, p.num_io);
     // u16 range check (G1 / G2 / Fq tables), SBN_QUOTIENT_LOOKUPS=1 (experiment switch): the lookup constraints beside the permutation
     // checks, which load the same columns (air.cuh lookups_beside_permutation).  Measured in round 4: the tail segment loses 0.8 GB of

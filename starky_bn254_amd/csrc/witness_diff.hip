@@ -160,14 +160,15 @@ extern "C" int sbn_prover_diff_witness(sbn_prover* P, const uint32_t* ios, size_
   if (!P->loaded) return fail(SBN_ERR_BAD_ARG, "no trace loaded");
   const int kind = P->air.kind;
   if (!is_exp_air(kind)) return fail(SBN_ERR_UNSUPPORTED, "%s", NOT_EXP);
-  if (P->sp) return fail(SBN_ERR_UNSUPPORTED, "the witness diff runs on single-GPU provers (this one is rank %u of %u)", P->sp->comm.rank, P->sp->comm.world);
+  if (int rc = diag_refuse_split(P, "the witness diff", true)) return rc;
   const size_t n = P->n, C = P->air.ncols, num_main = (size_t)exp_shape(P->air).num_main;
   const bool fq12 = kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64;
   if (!fq12 && (n < 65536 || n > 262144))
     return fail(SBN_ERR_UNSUPPORTED, "the device witness of the u16-range-check tables covers 2^16 .. 2^18 rows, this context has %zu (sbn_diff_witness_host takes any height)", n);
   if (n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
   if (P->pi.size() != P->air.npi) return fail(SBN_ERR_BAD_ARG, "the loaded trace carries %zu public inputs, the table has %zu", P->pi.size(), P->air.npi);
-  for (int i = 0; i < 3; i++) P->witdiff_ms[i] = 0;
+  float* const times = P->diag_ms[DIAG_WITDIFF];
+  for (int i = 0; i < 3; i++) times[i] = 0;
   std::vector<uint32_t> own;
   if (!ios) {
     own.resize(exp_io_words(kind) * num_io);
@@ -180,7 +181,7 @@ extern "C" int sbn_prover_diff_witness(sbn_prover* P, const uint32_t* ios, size_
     return fail(SBN_ERR_UNSUPPORTED, "internal: the counters of this table do not fit the scratch");
 
   std::vector<u64> pi;
-  if (int rc = canonical_witness(P, ios, num_io, pi, &P->witdiff_ms[0])) return no_witness(rc);
+  if (int rc = canonical_witness(P, ios, num_io, pi, &times[0])) return no_witness(rc);
   HIPC(hipSetDevice(P->device));
   hipStream_t st = P->stream;
   hipEvent_t* ev = P->ev;   // the stage events are idle outside prove()
@@ -195,7 +196,7 @@ extern "C" int sbn_prover_diff_witness(sbn_prover* P, const uint32_t* ios, size_
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(ev[1], st));
   HIPC(hipStreamSynchronize(st));
-  HIPC(hipEventElapsedTime(&P->witdiff_ms[1], ev[0], ev[1]));
+  HIPC(hipEventElapsedTime(&times[1], ev[0], ev[1]));
 
   const auto t0 = std::chrono::steady_clock::now();
   // the column counters first: of a clean trace nothing else comes back (the caller's memory and these vectors are pageable: plain copies)
@@ -229,13 +230,8 @@ extern "C" int sbn_prover_diff_witness(sbn_prover* P, const uint32_t* ios, size_
   pi_difference(P->pi.data(), pi.data(), pi.size(), d);
   write_columns(col.data(), col.data() + C, C, column_cells_out, column_first_row_out);
   memcpy(report, &d, sizeof d);
-  P->witdiff_ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  times[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return SBN_OK;
 }
 
-extern "C" int sbn_prover_diff_witness_times(const sbn_prover* P, float* ms, int cap) {
-  if (!P || !ms) return 0;
-  const int k = std::min(cap, 3);
-  for (int i = 0; i < k; i++) ms[i] = P->witdiff_ms[i];
-  return k;
-}
+extern "C" int sbn_prover_diff_witness_times(const sbn_prover* P, float* ms, int cap) { return P ? copy_times(P->diag_ms[DIAG_WITDIFF], 3, ms, cap) : 0; }
