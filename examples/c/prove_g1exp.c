@@ -25,6 +25,7 @@ int main(int argc, char** argv) {
   size_t n_pi = sbn_air_num_public_inputs(&air);
   uint64_t* pi = malloc(n_pi * sizeof *pi);
   int rc = sbn_prover_create(&air, &cfg, 16, &prover);
+  if (!rc) rc = sbn_prover_set_guard(prover, SBN_GUARD_DEVICE);    /* run_once: no proof is used unverified   circuit.rs:187-201 */
   if (!rc) rc = sbn_prover_generate_trace(prover, ios, 128, pi);   /* generate_trace + generate_public_inputs  exp.rs:816-817, on the device */
   if (!rc) rc = sbn_prover_prove(prover, &proof);                  /* prove::<F, C, _, D>(...)                 exp.rs:818-825 */
   if (rc) { fprintf(stderr, "failed (%d): %s\n", rc, sbn_last_error()); return 1; }

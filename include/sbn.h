@@ -197,7 +197,8 @@ typedef struct sbn_prover_options { uint32_t struct_size; uint32_t lde_storage; 
  * table has that shape; its quotient would need two row strides): SBN_ERR_UNSUPPORTED.  sbn_prover_describe reports
  * lde=full|compact, the ring depth and its bytes.
  * Known defect, in both storage modes and older than this option: a batch prover with three contexts in
- * flight has returned wrong proofs for units after a context's first; one and two contexts in flight have not. */
+ * flight has returned wrong proofs for units after a context's first; one and two contexts in flight have not.  A guarded batch
+ * prover (sbn_batch_prover_set_guard) turns that defect from a wrong result with status 0 into SBN_ERR_VERIFY_FAILED naming the unit. */
 int sbn_prover_create_with(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, const sbn_prover_options* opt, sbn_prover** out);
 /* Device bytes sbn_prover_create_with allocates at creation (dev_bytes of sbn_prover_describe right after it), computed without a
  * device from the list of buffers the creation itself allocates from; the same argument checks.  Outside the plan, allocated by
@@ -604,6 +605,44 @@ int sbn_batch_prover_prove_host_columns(sbn_batch_prover* b, const uint64_t* con
                                         sbn_proof** proofs_out);
 void sbn_batch_prover_destroy(sbn_batch_prover* b);
 
+/* Verified proving: no proof leaves a guarded context unless it verifies ------------------------------ */
+/* The reference never uses a proof it has not verified: G1ExpStarkyProofGenerator::run_once (src/curves/g1/circuit.rs:187-201) calls
+ * prove(...) and, on the next line, verify_stark_proof(stark, inner_proof.clone(), &inner_config).unwrap(); the G2, Fq, Fq12 and
+ * Fq12-u64 generators do the same.  A guard joins the two halves inside the library.  THE PROMISE of a guarded context: a proof it
+ * returns has passed the verifier the caller's consumer will run.
+ * With a guard set, every call that returns an sbn_proof from the context -- sbn_prover_prove, sbn_prover_prove_host_trace,
+ * sbn_prover_prove_host_columns, sbn_prover_prove_host_rows, every sbn_batch_prover_prove_* call, and sbn_prove / sbn_prove_columns /
+ * sbn_prove_rows under sbn_prove_set_guard -- verifies the assembled WORDS, the array sbn_proof_serialize would write (not the device
+ * buffers they came from), before it returns.
+ *   SBN_GUARD_HOST    sbn_verify on the calling thread.
+ *   SBN_GUARD_DEVICE  a device verifier of batch 1 (sbn_verifier_create) that the context owns: created by the first guarded proof,
+ *                     on the context's device, for the context's (air, cfg, degree_bits); destroyed with the context; kept when the
+ *                     mode goes back to SBN_GUARD_OFF.  Its device bytes are outside sbn_prover_memory_plan (as the 8 bytes of the
+ *                     canonical-form scan are); sbn_prover_describe reports them as guard_bytes, the stats as out[3], and the
+ *                     one-shot context cache counts them against its budget.
+ * A proof that verifies: the words are those of the unguarded call; the trace stays loaded, sbn_prover_prove can be repeated.
+ * A proof that does not: SBN_ERR_VERIFY_FAILED, sbn_last_error() = the verifier's own reason (the same text in both modes, the one
+ * sbn_verify leaves), *out null, and the trace STAYS LOADED -- also after the load-and-prove calls, which otherwise leave none behind
+ * a failure -- so that sbn_prover_check_trace, sbn_prover_explain_* and sbn_prover_diff_witness can name the cause.  There is no retry:
+ * a unit that fails is reported, and the stats count it.  The batch calls keep their failure rule (every proof slot null, the batch
+ * prover usable): the status and the message of the failing unit with the smallest index, behind "unit %zu: ".  In a batch every
+ * context checks its own proof on its own worker thread with its own verifier; no verifier is shared, no lock is taken, and the other
+ * contexts keep proving meanwhile.  The guard enqueues nothing on the prover's streams: the device verifier has its own.
+ * Refused before any device is looked for, in this order: a null handle, then an unknown mode: SBN_ERR_BAD_ARG; the context of a
+ * split prover, whatever its world size and whatever the mode: SBN_ERR_UNSUPPORTED (the ranks would have to agree on the verdict).
+ * Setting the mode a context already has changes nothing.  With SBN_GUARD_OFF, the default, every call is exactly the unguarded one. */
+enum { SBN_GUARD_OFF = 0, SBN_GUARD_DEVICE = 1, SBN_GUARD_HOST = 2 };
+int sbn_prover_set_guard(sbn_prover* p, uint32_t mode);
+int sbn_batch_prover_set_guard(sbn_batch_prover* b, uint32_t mode);   /* every context of the batch */
+/* The one-shot calls sbn_prove / sbn_prove_columns / sbn_prove_rows, process-wide, as sbn_prove_cache_configure: the context of a
+ * call, cached or fresh, is given this mode before it proves.  A refused mode leaves the setting as it was. */
+int sbn_prove_set_guard(uint32_t mode);
+/* out[0..3] = proofs checked, proofs rejected, nanoseconds spent checking (host clock, the lazy creation of the device verifier
+ * included), device bytes of the guard (0 until a device guard has checked its first proof).  Plain counters of the context: read
+ * them between calls, not while another thread proves on it. */
+int sbn_prover_guard_stats(const sbn_prover* p, uint64_t out[4]);
+int sbn_batch_prover_guard_stats(const sbn_batch_prover* b, uint64_t out[4]);   /* summed over its contexts */
+
 /* Long chained lists ------------------------------------------------------------------------------- */
 /* An MSM / multi-exponentiation of ANY length as proofs of one table: the chained list of sbn_chain_instances cut into units of
  * num_io instances, the last unit padded as the reference's g1_exp_circuit pads a short list (src/curves/g1/circuit.rs:273-277,
@@ -852,6 +891,9 @@ int sbn_split_prover_load_trace(sbn_split_prover* p, const uint64_t* trace_col_m
 /* The proof of the whole trace, on every rank, word for word the proof sbn_prover_prove gives on one GPU. */
 int sbn_split_prover_prove(sbn_split_prover* p, sbn_proof** out);
 int sbn_split_prover_stage_times(const sbn_split_prover* p, float* ms_out, int cap);
+/* sbn_prover_set_guard on this rank's context: a null handle or an unknown mode SBN_ERR_BAD_ARG, otherwise SBN_ERR_UNSUPPORTED for
+ * every mode and every world size, 1 included (verify what sbn_split_prover_prove returns with sbn_verify or a sbn_verifier). */
+int sbn_split_prover_set_guard(sbn_split_prover* p, uint32_t mode);
 /* sbn_prover_check_trace on this rank's loaded trace, world = 1 only: with more ranks the Z columns and the rows are shared out
  * and this returns SBN_ERR_UNSUPPORTED (every rank holds the whole trace: check it with sbn_check_trace_host or on a single-GPU
  * prover). */

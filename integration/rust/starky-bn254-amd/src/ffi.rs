@@ -34,6 +34,11 @@ pub struct sbn_prover_options {
     pub lde_storage: u32,
 }
 
+/// the modes of sbn_prover_set_guard / sbn_batch_prover_set_guard / sbn_prove_set_guard
+pub const SBN_GUARD_OFF: u32 = 0;
+pub const SBN_GUARD_DEVICE: u32 = 1;
+pub const SBN_GUARD_HOST: u32 = 2;
+
 #[repr(C)]
 pub struct sbn_prover {
     _opaque: [u8; 0],
@@ -184,6 +189,12 @@ extern "C" {
     pub fn sbn_lde_rows(values_col_major: *const u64, ncols: usize, degree_bits: u32, rate_bits: u32, leaf_indices: *const u32, count: usize, rows_out: *mut u64) -> i32;
     pub fn sbn_batch_prover_prove_ios(b: *mut sbn_batch_prover, ios: *const u32, ios_words_per_unit: usize, num_io: usize, count: usize, proofs_out: *mut *mut sbn_proof) -> i32;
     pub fn sbn_batch_prover_destroy(b: *mut sbn_batch_prover);
+    /// verified proving (include/sbn.h): mode = SBN_GUARD_OFF / SBN_GUARD_DEVICE / SBN_GUARD_HOST
+    pub fn sbn_prover_set_guard(p: *mut sbn_prover, mode: u32) -> i32;
+    pub fn sbn_batch_prover_set_guard(b: *mut sbn_batch_prover, mode: u32) -> i32;
+    pub fn sbn_prove_set_guard(mode: u32) -> i32;
+    pub fn sbn_prover_guard_stats(p: *const sbn_prover, out: *mut u64) -> i32;
+    pub fn sbn_batch_prover_guard_stats(b: *const sbn_batch_prover, out: *mut u64) -> i32;
     pub fn sbn_msm_num_units(count: usize, num_io: usize) -> usize;
     pub fn sbn_msm_instances(kind: i32, terms: *const u32, count: usize, num_io: usize, start: *const u32, ios_out: *mut u32, final_out: *mut u32) -> i32;
     pub fn sbn_batch_prover_prove_msm(b: *mut sbn_batch_prover, terms: *const u32, count: usize, start: *const u32, proofs_out: *mut *mut sbn_proof, final_out: *mut u32, ios_out: *mut u32) -> i32;

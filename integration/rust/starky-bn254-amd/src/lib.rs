@@ -115,6 +115,28 @@ pub enum LdeStorage {
     Compact,
 }
 
+/// Which verifier a prover runs on every proof before it returns it (include/sbn.h, sbn_prover_set_guard).
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)]
+pub enum Guard {
+    /// no check: the proof is returned as assembled
+    #[default]
+    Off,
+    /// a device verifier of batch 1 that the prover owns, created by its first guarded proof
+    Device,
+    /// the host verifier (sbn_verify) on the calling thread
+    Host,
+}
+
+impl Guard {
+    fn raw(self) -> u32 {
+        match self {
+            Guard::Off => ffi::SBN_GUARD_OFF,
+            Guard::Device => ffi::SBN_GUARD_DEVICE,
+            Guard::Host => ffi::SBN_GUARD_HOST,
+        }
+    }
+}
+
 #[derive(Clone, Copy, Debug, Default)]
 pub struct ProverOptions {
     pub lde_storage: LdeStorage,
@@ -276,6 +298,34 @@ impl Prover {
         let mut pi = vec![0u64; self.n_pi];
         check(unsafe { ffi::sbn_prover_generate_trace(self.raw, ios.as_ptr(), self.num_io, pi.as_mut_ptr()) }, "sbn_prover_generate_trace")?;
         self.finish::<F, C, D>()
+    }
+
+    /// Verified proving (sbn_prover_set_guard): with `Guard::Device` or `Guard::Host` every proof this prover returns has passed
+    /// that verifier first; a proof it rejects is an `Err` carrying status -6 and the verifier's own reason, and the trace stays
+    /// loaded, so `check_trace`, `explain_*` and `diff_witness` can name the cause.  The words of an accepted proof are those of
+    /// the unguarded call.
+    pub fn set_guard(&mut self, guard: Guard) -> Result<()> {
+        check(unsafe { ffi::sbn_prover_set_guard(self.raw, guard.raw()) }, "sbn_prover_set_guard")
+    }
+
+    /// (proofs checked, proofs rejected, nanoseconds spent checking, device bytes of the guard) (sbn_prover_guard_stats).
+    pub fn guard_stats(&self) -> Result<[u64; 4]> {
+        let mut out = [0u64; 4];
+        check(unsafe { ffi::sbn_prover_guard_stats(self.raw, out.as_mut_ptr()) }, "sbn_prover_guard_stats")?;
+        Ok(out)
+    }
+
+    /// The shape of the reference's `G1ExpStarkyProofGenerator::run_once` (src/curves/g1/circuit.rs:187-201), which calls
+    /// `prove(...)` and on the next line `verify_stark_proof(stark, inner_proof.clone(), &inner_config).unwrap()`: `prove_ios`
+    /// under the device guard.  The proof that comes back has passed the verifier the consumer will run; one that does not
+    /// verify is an `Err`, never a value.  The guard stays set on this prover.
+    pub fn prove_ios_verified<F, C, const D: usize>(&mut self, ios: &[u32]) -> Result<StarkProofWithPublicInputs<F, C, D>>
+    where
+        F: RichField + Extendable<D>,
+        C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+    {
+        self.set_guard(Guard::Device)?;
+        self.prove_ios::<F, C, D>(ios)
     }
 
     /// The reference's `*_msm` call shape (`test_g1_msm`, src/curves/g1/circuit.rs:459-509): `terms` holds the instance rows

@@ -17,4 +17,5 @@ from .api import (  # noqa: F401
     TRACE_REDUCE, ColumnTable, prove_columns, gather_columns, reduce_words,
     RowTable, trace_from_rows_host, prove_rows,
     WitnessDiff, WITNESS_CELL, diff_witness_host, instances_from_public_inputs,
+    GUARD, GuardStats, prove_set_guard,
 )

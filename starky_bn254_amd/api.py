@@ -6,6 +6,7 @@ Names follow the reference (src/curves/g1/exp.rs:232-328, :811-826):
     proof = prove(stark, config, trace, pi);  verify_stark_proof(stark, proof, config)
 Errors surface as SbnError (the reference returns anyhow::Result and callers unwrap).
 """
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -56,6 +57,7 @@ EXPORTS = [
     "sbn_prover_prove_host_columns", "sbn_prove_columns", "sbn_batch_prover_prove_host_columns", "sbn_gather_columns", "sbn_reduce_words",
     "sbn_fixed_columns_range", "sbn_fixed_columns_check",
     "sbn_air_num_main_columns", "sbn_trace_from_rows_host", "sbn_prover_load_trace_rows", "sbn_prover_load_trace_rows_device", "sbn_prover_prove_host_rows", "sbn_prove_rows",
+    "sbn_prover_set_guard", "sbn_batch_prover_set_guard", "sbn_prove_set_guard", "sbn_prover_guard_stats", "sbn_batch_prover_guard_stats", "sbn_split_prover_set_guard",
 ]
 
 
@@ -63,6 +65,7 @@ class SbnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"sbn error {code}: {msg}")
         self.code = code
+        self.reason = msg   # sbn_last_error() as it was: behind code -6 the verifier's own reason
 
 
 class _AirDesc(C.Structure):
@@ -285,6 +288,12 @@ def lib():
             L.sbn_prover_load_trace_rows_device.argtypes = [vp, vp, sz, sz, u32, vp, sz, vp]
             L.sbn_prover_prove_host_rows.argtypes = [vp, C.POINTER(_HostRows), u32, vp, sz, vp, C.POINTER(vp)]
             L.sbn_prove_rows.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), C.POINTER(_HostRows), u32, vp, sz, C.POINTER(vp)]
+        if hasattr(L, "sbn_prover_set_guard"):
+            for f in ("sbn_prover_set_guard", "sbn_batch_prover_set_guard", "sbn_split_prover_set_guard"):
+                getattr(L, f).argtypes = [vp, u32]
+            L.sbn_prove_set_guard.argtypes = [u32]
+            L.sbn_prover_guard_stats.argtypes = [vp, vp]
+            L.sbn_batch_prover_guard_stats.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -296,6 +305,35 @@ def _check(rc):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+GUARD = {None: 0, "off": 0, "device": 1, "host": 2}   # SBN_GUARD_OFF, SBN_GUARD_DEVICE, SBN_GUARD_HOST
+
+
+def _guard_mode(guard):
+    """The mode of a `guard=` argument: None / "off", "device", "host", or an integer for itself (so that a caller can hand the
+    library a mode it does not know)."""
+    if guard is None or isinstance(guard, str):
+        if guard not in GUARD:
+            raise ValueError(f"guard must be None, 'device' or 'host', not {guard!r}")
+        return GUARD[guard]
+    return int(guard)
+
+
+GuardStats = collections.namedtuple("GuardStats", ("checked", "rejected", "ns", "device_bytes"))
+
+
+def _guard_stats(getter, h):
+    out = (C.c_uint64 * 4)()
+    _check(getter(h, out))
+    return GuardStats(*(int(v) for v in out))
+
+
+def prove_set_guard(guard):
+    """Verified proving for the one-shot calls prove() / prove_columns() / prove_rows(), process-wide (sbn_prove_set_guard): with
+    "device" or "host" a proof that its verifier rejects is an SbnError with code -6 and the verifier's reason; None restores the
+    unguarded calls."""
+    _check(lib().sbn_prove_set_guard(_guard_mode(guard)))
 
 
 class StarkConfig:
@@ -1548,18 +1586,32 @@ def instances_from_public_inputs(stark, pi):
 class Prover:
     """Device context for one (table, degree_bits): buffers stay allocated across proofs.  lde="compact" (rate_bits > 1): the
     LDEs of the wide matrices are not kept, the opened rows are recomputed from the coefficients (include/sbn.h SBN_LDE_COMPACT);
-    the proofs are the same words."""
+    the proofs are the same words.  guard="device" | "host": verified proving (set_guard)."""
 
-    def __init__(self, stark, config, degree_bits, lde="full"):
+    def __init__(self, stark, config, degree_bits, lde="full", guard=None):
         self.stark, self.config, self.degree_bits = stark, config, degree_bits
         self._h = C.c_void_p()
         opt = _prover_options(lde)
+        mode = _guard_mode(guard)
         # by the header's contract the same call; so the "full" path of this class never enters sbn_prover_create_with (a GPU test calls
         # it with SBN_LDE_FULL through ctypes), and a library named by SBN_LIB that lacks the new entry points still serves it
         if opt is None or opt.lde_storage == LDE_STORAGE["full"]:
             _check(lib().sbn_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, C.byref(self._h)))
         else:
             _check(lib().sbn_prover_create_with(C.byref(stark._d), C.byref(config._c), degree_bits, C.byref(opt), C.byref(self._h)))
+        if mode:   # (guard=None never enters the new entry point, as lde="full" above)
+            self.set_guard(mode)
+
+    def set_guard(self, guard):
+        """Verified proving (sbn_prover_set_guard): with "device" or "host" every proof this context returns has passed that
+        verifier first -- the words are those of the unguarded call; a proof the verifier rejects is an SbnError with code -6 whose
+        .reason is the verifier's own text, and the trace stays loaded for check_trace / explain_* / diff_witness.  None: off."""
+        _check(lib().sbn_prover_set_guard(self._h, _guard_mode(guard)))
+
+    def guard_stats(self):
+        """GuardStats(checked, rejected, ns, device_bytes): proofs the guard checked and rejected, host nanoseconds spent checking,
+        device bytes of the guard's verifier."""
+        return _guard_stats(lib().sbn_prover_guard_stats, self._h)
 
     def load_trace(self, trace, public_inputs):
         trace = np.ascontiguousarray(trace, dtype=np.uint64)
@@ -1776,14 +1828,27 @@ class Prover:
 class BatchProver:
     """`inflight` prover contexts on one GPU: proves a batch of instance lists (witness generated on the device)."""
 
-    def __init__(self, stark, config, degree_bits, inflight=3, lde="full"):
+    def __init__(self, stark, config, degree_bits, inflight=3, lde="full", guard=None):
         self.stark, self.config, self.degree_bits = stark, config, degree_bits
         self._h = C.c_void_p()
         opt = _prover_options(lde)
+        mode = _guard_mode(guard)
         if opt is None or opt.lde_storage == LDE_STORAGE["full"]:
             _check(lib().sbn_batch_prover_create(C.byref(stark._d), C.byref(config._c), degree_bits, inflight, C.byref(self._h)))
         else:
             _check(lib().sbn_batch_prover_create_with(C.byref(stark._d), C.byref(config._c), degree_bits, inflight, C.byref(opt), C.byref(self._h)))
+        if mode:
+            self.set_guard(mode)
+
+    def set_guard(self, guard):
+        """Prover.set_guard for every context of the batch (sbn_batch_prover_set_guard): each checks its own proofs on its own
+        worker thread with its own verifier.  A unit whose proof is rejected fails the call with code -6, "unit <u>: " and the
+        verifier's reason; no proof is returned."""
+        _check(lib().sbn_batch_prover_set_guard(self._h, _guard_mode(guard)))
+
+    def guard_stats(self):
+        """Prover.guard_stats summed over the contexts."""
+        return _guard_stats(lib().sbn_batch_prover_guard_stats, self._h)
 
     def _unit_buffers(self, count, words):
         """(ios, out) for `count` instances of `words` u32 each cut into units: the (units, num_io, words) list buffer and the

@@ -31,6 +31,8 @@ struct ProveCache {
   uint64_t budget = 0, bytes = 0, hits = 0, misses = 0, evictions = 0;
 };
 ProveCache& prove_cache() { static ProveCache* c = new ProveCache(); return *c; }
+// the guard of the one-shot calls (include/sbn.h sbn_prove_set_guard): process-wide, given to the context of every call
+std::atomic<uint32_t> g_one_shot_guard{SBN_GUARD_OFF};
 
 // an idle context of this key, or null (counted as a miss: the caller creates one)
 sbn_prover* cache_take(const CacheKey& key) {
@@ -92,6 +94,12 @@ int sbn_prove_cache_stats(uint64_t out[6]) {
   return SBN_OK;
 }
 
+int sbn_prove_set_guard(uint32_t mode) {
+  if (mode > SBN_GUARD_HOST) return fail(SBN_ERR_BAD_ARG, "unknown guard mode %u (0 off, 1 device, 2 host)", mode);
+  g_one_shot_guard.store(mode);
+  return SBN_OK;
+}
+
 const char* sbn_version(void) { return "starky-bn254-amd 0.3 (gfx950)"; }
 int sbn_abi_version(void) { return SBN_ABI_VERSION; }
 const char* sbn_last_error(void) { return g_last_error.c_str(); }
@@ -139,7 +147,8 @@ static int prove_one_shot(const sbn_air_desc* air, const sbn_config* cfg, uint32
   sbn_prover* P = keyed ? cache_take(key) : nullptr;
   int rc = 0;
   if (!P && (rc = sbn_prover_create(air, cfg, degree_bits, &P))) return rc;
-  rc = call(P);
+  rc = sbn_prover_set_guard(P, g_one_shot_guard.load());   // (a cached context may carry the mode of an earlier call; its verifier stays)
+  if (!rc) rc = call(P);
   if (rc) {   // a context whose call failed is not kept (destroy leaves the message of the failure in place)
     const std::string msg = g_last_error;
     sbn_prover_destroy(P);
@@ -207,23 +216,42 @@ int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t 
   for (size_t i = 0; i < count; i++) proofs_out[i] = nullptr;
   if (exp_io_words(B->kind) == 0 || ios_words_per_unit != exp_io_words(B->kind) * num_io)
     return fail(SBN_ERR_BAD_ARG, "ios_words_per_unit must be %zu u32 words per instance times num_io", exp_io_words(B->kind));
-  std::atomic<size_t> next(0);
-  std::atomic<int> first_rc(0);
-  std::mutex m; std::string msg;
+  // (the failure rule of the host-columns loop below: the failing unit with the smallest index, its message behind "unit %zu: ";
+  // a guarded context fails a unit whose proof its verifier rejects, on the thread that proved it)
+  std::atomic<size_t> next(0), first_unit(count);
+  std::mutex m; int first_rc = 0; std::string msg;
   auto work = [&](sbn_prover* P) {
-    for (size_t u; (u = next.fetch_add(1)) < count && first_rc.load() == 0;) {
+    for (size_t u; (u = next.fetch_add(1)) < count && first_unit.load() == count;) {
       int rc = sbn_prover_generate_trace(P, ios + u * ios_words_per_unit, num_io, nullptr);
       if (!rc) rc = sbn_prover_prove(P, &proofs_out[u]);
-      if (rc) { std::lock_guard<std::mutex> g(m); if (first_rc.load() == 0) { first_rc = rc; msg = g_last_error; } }
+      if (rc) { std::lock_guard<std::mutex> g(m); if (u < first_unit.load()) { first_unit = u; first_rc = rc; msg = g_last_error; } }
     }
   };
   std::vector<std::thread> th;
   for (size_t i = 1; i < B->provers.size() && i < count; i++) th.emplace_back(work, B->provers[i]);
   work(B->provers[0]);
   for (auto& t : th) t.join();
-  if (first_rc.load()) {
+  if (first_rc) {
     for (size_t i = 0; i < count; i++) { delete proofs_out[i]; proofs_out[i] = nullptr; }
-    return fail(first_rc.load(), "%s", msg.c_str());
+    return fail(first_rc, "unit %zu: %s", first_unit.load(), msg.c_str());
+  }
+  return SBN_OK;
+}
+
+// Verified proving (include/sbn.h): the mode of every context; each owns its verifier and checks on its own worker thread
+int sbn_batch_prover_set_guard(sbn_batch_prover* B, uint32_t mode) {
+  if (!B) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (mode > SBN_GUARD_HOST) return fail(SBN_ERR_BAD_ARG, "unknown guard mode %u (0 off, 1 device, 2 host)", mode);
+  for (sbn_prover* P : B->provers) if (int rc = sbn_prover_set_guard(P, mode)) return rc;
+  return SBN_OK;
+}
+int sbn_batch_prover_guard_stats(const sbn_batch_prover* B, uint64_t out[4]) {
+  if (!B || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  for (int i = 0; i < 4; i++) out[i] = 0;
+  for (const sbn_prover* P : B->provers) {
+    uint64_t s[4];
+    if (int rc = sbn_prover_guard_stats(P, s)) return rc;
+    for (int i = 0; i < 4; i++) out[i] += s[i];
   }
   return SBN_OK;
 }

@@ -860,10 +860,11 @@ static int create_ctx(const sbn_air_desc* air, const sbn_config* cfg, uint32_t d
   return SBN_OK;
 }
 
-namespace sbn { size_t prover_device_bytes(const sbn_prover* P) { return P ? P->dev_bytes : 0; } }   // capi.hip: the one-shot cache
+namespace sbn { size_t prover_device_bytes(const sbn_prover* P) { return P ? P->dev_bytes + guard_device_bytes(P) : 0; } }   // capi.hip: the one-shot cache (the guard's verifier counts)
 extern "C" void sbn_prover_destroy(sbn_prover* P) {
   if (!P) return;
   (void)hipSetDevice(P->device);
+  guard_destroy(P);   // guard.hip: the device verifier of a guarded context, if one was created
   if (P->ustream) (void)hipStreamSynchronize(P->ustream);   // in front of the frees: the copy stream writes d_trace and its scan word (a refused call drained it already)
   for (void* b : P->owned) (void)hipFree(b);                 // every device buffer of the context (alloc_buffers)
   if (P->sp) {
@@ -1495,6 +1496,7 @@ int prove_streamed(sbn_prover* P, const HostUpload* up, sbn_proof** out) {
   for (int i = 0; i < ST_COUNT; i++) HIPC(hipEventElapsedTime(&P->stage_ms[i], P->ev[i], P->ev[i + 1]));
   if ((rc = assemble_proof(run, out))) return rc;
   if (run.fills_fixed) P->fixed_valid = true;   // every stage has run and been waited for: d_coef and d_lde hold those transforms
+  if (P->guard_mode) return guard_check(P, out);   // include/sbn.h sbn_prover_set_guard (guard.hip): the streams are idle, the words final
   return SBN_OK;
 }
 extern "C" int sbn_prover_prove(sbn_prover* P, sbn_proof** out) { return prove_streamed(P, nullptr, out); }
@@ -1702,7 +1704,7 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
   snprintf(buf, sizeof buf,
            "abi=%d device=%d dev_bytes=%zu ntt_chunk=%zu ntt_fused=%d ntt_streams=%d ntt_split1024=%d ntt_lde_zero_aware=%d "
            "curve_chains=%s host_threads=%u fq12_host_chain=%d fq12_row_kernel=%d range_check=%d quotient_lookups=%d comm_timeout_s=%g experimental=%d lde=%s lde_ring=%u lde_ring_bytes=%zu "
-           "fixed_columns=%d fixed_columns_range=%zu:%zu fixed_columns_skipped=%zu perm_diff_routes=%zu:%zu:%zu ignored=[%s]",
+           "fixed_columns=%d fixed_columns_range=%zu:%zu fixed_columns_skipped=%zu perm_diff_routes=%zu:%zu:%zu guard=%s guard_bytes=%zu ignored=[%s]",
            SBN_ABI_VERSION, P->device, P->dev_bytes, P->ntt_chunk, (int)(P->ntt_fused || P->ntt_fused512), P->ntt_two_streams ? 2 : 1, P->d_shift_odd ? 1 : 0, P->d_shift_za ? 1 : 0,
            chain, tracegen_host_threads(), (int)s.fq12_host_chain,
            (int)s.fq12_row_kernel, s.range_check, s.quotient_lookups, s.comm_timeout_s, (int)s.experimental, P->lde_storage == SBN_LDE_COMPACT ? "compact" : "full", P->ring_depth,
@@ -1710,7 +1712,9 @@ extern "C" int sbn_prover_describe(const sbn_prover* P, char* out, size_t cap) {
            // the switch; the columns whose transforms this context keeps between proofs (0:0 none); how many the last prove() left untransformed
            (int)s.fixed_columns, P->fixed_f0, P->fixed_f1, P->fixed_skipped,
            // pairs of the last sbn_prover_explain_permutations by route: bins alone, overflow list, downloaded columns (perm_diff.hip)
-           P->permdiff_routes[0], P->permdiff_routes[1], P->permdiff_routes[2], s.ignored.c_str());
+           P->permdiff_routes[0], P->permdiff_routes[1], P->permdiff_routes[2],
+           // verified proving (sbn_prover_set_guard): the mode, and the device bytes of the guard's verifier (outside dev_bytes)
+           P->guard_mode == SBN_GUARD_DEVICE ? "device" : P->guard_mode == SBN_GUARD_HOST ? "host" : "off", guard_device_bytes(P), s.ignored.c_str());
   snprintf(out, cap, "%s", buf);
   return SBN_OK;
 }
@@ -1752,6 +1756,10 @@ extern "C" int sbn_split_prover_load_trace(sbn_split_prover* sp, const uint64_t*
 extern "C" int sbn_split_prover_prove(sbn_split_prover* sp, sbn_proof** out) {
   if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
   return sbn_prover_prove(sp->P, out);
+}
+extern "C" int sbn_split_prover_set_guard(sbn_split_prover* sp, uint32_t mode) {
+  if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");
+  return sbn_prover_set_guard(sp->P, mode);   // (guard.hip refuses the context of a split prover behind the mode check)
 }
 extern "C" int sbn_split_prover_check_trace(sbn_split_prover* sp, uint64_t seed, sbn_trace_report* rep, uint8_t* row_flags_out) {
   if (!sp) return fail(SBN_ERR_BAD_ARG, "null argument");

@@ -172,7 +172,22 @@ struct sbn_prover {
   unsigned long long* h_first_bad = nullptr; // its pinned landing word
   float diag_ms[DIAG_COUNT][4] = {};         // the times of the last call of each diagnostic (enum Diag), what its *_times getter copies
   size_t permdiff_routes[3] = {};            // sbn_prover_explain_permutations: pairs of its last call answered by the bins alone, with the overflow list, from downloaded columns
+  // Verified proving (include/sbn.h sbn_prover_set_guard; guard.hip): with a mode set, prove_streamed hands the assembled proof to
+  // guard_check before it returns.  The device verifier (batch 1, its own stream and buffers, outside `owned` and the memory plan)
+  // is created by the first proof a device guard checks and lives until the context is destroyed.
+  u32 guard_mode = 0;                        // SBN_GUARD_OFF / _DEVICE / _HOST
+  sbn_verifier* guard_verifier = nullptr;
+  uint64_t guard_checked = 0, guard_rejected = 0, guard_ns = 0;
 };
+
+// guard.hip: the guard of a context whose guard_mode is set, on the proof prove_streamed has just assembled.  SBN_OK: *out verified.
+// Otherwise *out is freed and nulled; SBN_ERR_VERIFY_FAILED carries the verifier's reason as the message.  Touches no stream of P.
+int guard_check(sbn_prover* P, sbn_proof** out);
+// the guard refused a finished proof: every stage ran, so the trace the call loaded is resident and stays loaded (trace_load.hip)
+static inline bool guard_refused(const sbn_prover* P, int rc) { return rc == SBN_ERR_VERIFY_FAILED && P->guard_mode != SBN_GUARD_OFF; }
+// guard.hip: device bytes of the context's guard; sbn_prover_destroy's share
+size_t guard_device_bytes(const sbn_prover* P);
+void guard_destroy(sbn_prover* P);
 
 // Scratch of the calls that fill d_trace (the device witness generators of tracegen_device.hip, the row-major loads of
 // trace_load.hip), carved from the front of the LDE buffer, which is not in use between proofs (a split prover: its receive buffer).

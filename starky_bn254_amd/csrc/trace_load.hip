@@ -191,10 +191,11 @@ static int prove_upload(sbn_prover* P, const HostColumns& src, bool reduce, uint
   HIPC(hipSetDevice(P->device));
   if (int rc = upload_setup(P)) return rc;
   const HostUpload up{src, reduce};
-  if (int rc = prove_streamed(P, &up, out)) { abandon_load(P); return rc; }
+  const int rc = prove_streamed(P, &up, out);
+  if (rc && !guard_refused(P, rc)) { abandon_load(P); return rc; }
   if (reduce && reduced_out) *reduced_out = *P->h_first_bad;   // (the counter came back with the trace cap)
-  P->loaded = true;
-  return SBN_OK;
+  P->loaded = true;   // (also behind a guard's refusal: the upload and every stage ran, the trace is there for the diagnostics)
+  return rc;
 }
 extern "C" int sbn_prover_prove_host_trace(sbn_prover* P, const uint64_t* trace, const uint64_t* pi, size_t n_pi, sbn_proof** out) {
   if (!P || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
@@ -475,7 +476,7 @@ extern "C" int sbn_prover_prove_host_rows(sbn_prover* P, const sbn_host_rows* ro
   if (!out) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (int rc = sbn_prover_load_trace_rows(P, rows, flags, pi, n_pi, reduced_out)) return rc;
   const int rc = sbn_prover_prove(P, out);
-  if (rc) abandon_load(P);   // a failing call leaves no trace loaded
+  if (rc && !guard_refused(P, rc)) abandon_load(P);   // a failing call leaves no trace loaded, but for a guard's refusal of the finished proof
   return rc;
 }
 

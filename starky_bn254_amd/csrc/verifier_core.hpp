@@ -65,4 +65,9 @@ struct VerifyLayout {
 };
 bool verify_layout(const AirShape& as, const sbn_config& cfg, u32 degree_bits, VerifyLayout& L);
 
+// verifier_device.hip, for the guard of a prover context (guard.hip): sbn_verifier_create on `device` instead of the calling
+// thread's (device < 0: the calling thread's, which is what the C ABI passes), and the device memory the verifier allocated
+int verifier_create_on(int device, const sbn_air_desc* air, const sbn_config* cfg, u32 degree_bits, u32 max_batch, sbn_verifier** out);
+size_t verifier_device_bytes(const sbn_verifier* v);
+
 }  // namespace sbn

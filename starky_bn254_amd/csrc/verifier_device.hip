@@ -42,6 +42,7 @@ struct sbn_verifier {
   unsigned char *d_ok = nullptr, *h_ok = nullptr;
   VerifyTreeDev* d_trees = nullptr;
   float stage_ms[3] = {0, 0, 0};   // upload, kernels, download of the last call
+  size_t dev_bytes = 0;            // device memory of the buffers above
   std::vector<std::string> reasons;
 };
 
@@ -96,6 +97,14 @@ void sbn_verifier_destroy(sbn_verifier* V) {
 }
 
 int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t degree_bits, uint32_t max_batch, sbn_verifier** out) {
+  return verifier_create_on(-1, air, cfg, degree_bits, max_batch, out);
+}
+
+}  // extern "C"
+
+size_t sbn::verifier_device_bytes(const sbn_verifier* V) { return V ? V->dev_bytes : 0; }
+
+int sbn::verifier_create_on(int device, const sbn_air_desc* air, const sbn_config* cfg, u32 degree_bits, u32 max_batch, sbn_verifier** out) {
   if (!air || !cfg || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
   *out = nullptr;
   if (!config_supported(cfg)) return fail(SBN_ERR_UNSUPPORTED, "unsupported StarkConfig");
@@ -108,11 +117,13 @@ int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t
   VerifyLayout L;
   if (!verify_layout(as, *cfg, degree_bits, L)) return fail(SBN_ERR_UNSUPPORTED, "degree too small for the FRI parameters");
   if (int rc = use_current_device("sbn_verify is the host verifier")) return rc;
+  if (device >= 0) VHIPC(hipSetDevice(device));   // (a prover context's guard: the context's device, whatever the calling thread selected)
   sbn_verifier* V = new sbn_verifier();
-  V->air = *air; V->cfg = *cfg; V->as = as; V->degree_bits = degree_bits; V->max_batch = max_batch; V->device = current_device(); V->L = L;
+  V->air = *air; V->cfg = *cfg; V->as = as; V->degree_bits = degree_bits; V->max_batch = max_batch; V->device = device >= 0 ? device : current_device(); V->L = L;
   int rc = 0;
   auto hipc = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(SBN_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
   const size_t B = max_batch, nq = L.nqueries, nt = L.trees.size();
+  V->dev_bytes = B * L.proof_words * sizeof(u64) + B * 4 * sizeof(u64) + B * nq * L.ninit * 2 * sizeof(u64) + B * nq * sizeof(u32) + B * nq * nt + nt * sizeof(VerifyTreeDev);   // the six hipMallocs below
   hipc(hipStreamCreate(&V->stream), "hipStreamCreate");
   for (auto& e : V->ev) hipc(hipEventCreate(&e), "hipEventCreate");
   hipc(hipMalloc((void**)&V->d_proofs, B * L.proof_words * sizeof(u64)), "hipMalloc (proofs)");
@@ -135,6 +146,8 @@ int sbn_verifier_create(const sbn_air_desc* air, const sbn_config* cfg, uint32_t
   *out = V;
   return SBN_OK;
 }
+
+extern "C" {
 
 int sbn_verifier_verify(sbn_verifier* V, const uint8_t* const* proofs, const size_t* lens, size_t count, int32_t* status_out) {
   if (!V || !proofs || !lens || !status_out) return fail(SBN_ERR_BAD_ARG, "null argument");

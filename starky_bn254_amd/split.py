@@ -324,6 +324,11 @@ class SplitProver:
         self._checked(api.lib().sbn_split_prover_prove(self._h, C.byref(h)))
         return api._take_proof(h)
 
+    def set_guard(self, guard):
+        """Prover.set_guard is refused on a split prover, whatever the world size: SbnError(-7) (the ranks would have to agree on
+        the verdict); verify what prove() returns with verify_stark_proof or a Verifier."""
+        api._check(api.lib().sbn_split_prover_set_guard(self._h, api._guard_mode(guard)))
+
     def check_trace(self, seed=0, flags=False):
         """Prover.check_trace on this rank's loaded trace; a world of one rank only (SbnError(-7) otherwise)."""
         raw = api._TraceReport(struct_size=C.sizeof(api._TraceReport))
