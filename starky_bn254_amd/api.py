@@ -620,11 +620,14 @@ class Fq12ExpU64Stark(_Stark):
         return self.generate_trace_and_public_inputs(ios)[1]
 
 
+# u32 words of x and of the exponent in an instance row of an Exp table: the one table of them on this side (csrc: PiLayout)
+_EXP_IO_WORDS = {AIR_G1_EXP: (16, 8), AIR_G2_EXP: (32, 8), AIR_FQ_EXP: (8, 8), AIR_FQ12_EXP: (96, 8), AIR_FQ12_EXP_U64: (96, 2)}
+
+
 def _chain_words(stark):
     """(u32 words of x, of the exponent) in an instance row of the Exp table `stark`."""
     try:
-        return {G1ExpStark.kind: (16, 8), G2ExpStark.kind: (32, 8), FqExpStark.kind: (8, 8), Fq12ExpStark.kind: (96, 8),
-                Fq12ExpU64Stark.kind: (96, 2)}[stark.kind]
+        return _EXP_IO_WORDS[stark.kind]
     except KeyError:
         raise SbnError(-1, "chained instance lists cover the Exp tables") from None
 
@@ -702,10 +705,9 @@ G2_COFACTOR = 218882428718392752222464057452572750888442579141796129816798716027
 
 def _curve_words(stark):
     """u32 words of a point of the curve table `stark` (16 on G1, 32 on the twist)."""
-    try:
-        return {AIR_G1_EXP: 16, AIR_G2_EXP: 32}[stark.kind]
-    except KeyError:
-        raise SbnError(-7, "scalar multiplications cover the curve tables G1ExpStark and G2ExpStark") from None
+    if stark.kind not in (AIR_G1_EXP, AIR_G2_EXP):
+        raise SbnError(-7, "scalar multiplications cover the curve tables G1ExpStark and G2ExpStark")
+    return _EXP_IO_WORDS[stark.kind][0]
 
 
 def generator(stark):
@@ -857,10 +859,9 @@ FQ_SQRT_EXP = (BN_P + 1) // 4             # a square root of x when x is a squar
 
 def _power_words(stark):
     """(u32 words of a field element, of the exponent) in an instance row of the field Exp table `stark`."""
-    try:
-        return {AIR_FQ_EXP: (8, 8), AIR_FQ12_EXP: (96, 8), AIR_FQ12_EXP_U64: (96, 2)}[stark.kind]
-    except (KeyError, AttributeError):
-        raise SbnError(-7, "field powers cover the field tables FqExpStark, Fq12ExpStark and Fq12ExpU64Stark") from None
+    if getattr(stark, "kind", None) not in (AIR_FQ_EXP, AIR_FQ12_EXP, AIR_FQ12_EXP_U64):
+        raise SbnError(-7, "field powers cover the field tables FqExpStark, Fq12ExpStark and Fq12ExpU64Stark")
+    return _EXP_IO_WORDS[stark.kind]
 
 
 def _int_limbs(v, n):
@@ -1465,7 +1466,6 @@ def explain_permutations_host(stark, trace, zs=None, per_pair=8):
     return PermutationExplanation(stark, which, st, en)
 
 
-_EXP_IO_WORDS = {AIR_G1_EXP: (16, 8), AIR_G2_EXP: (32, 8), AIR_FQ_EXP: (8, 8), AIR_FQ12_EXP: (96, 8), AIR_FQ12_EXP_U64: (96, 2)}   # u32 words of x and of the exponent
 WITNESS_CELL = np.dtype([(f, np.uint64) for f in ("row", "column", "got", "want")])   # sbn_witness_cell
 
 

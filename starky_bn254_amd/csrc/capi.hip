@@ -211,19 +211,16 @@ void sbn_batch_prover_destroy(sbn_batch_prover* B) {
   for (auto q : B->provers) sbn_prover_destroy(q);
   delete B;
 }
-int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t ios_words_per_unit, size_t num_io, size_t count, sbn_proof** proofs_out) {
-  if (!B || !ios || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  for (size_t i = 0; i < count; i++) proofs_out[i] = nullptr;
-  if (exp_io_words(B->kind) == 0 || ios_words_per_unit != exp_io_words(B->kind) * num_io)
-    return fail(SBN_ERR_BAD_ARG, "ios_words_per_unit must be %zu u32 words per instance times num_io", exp_io_words(B->kind));
-  // (the failure rule of the host-columns loop below: the failing unit with the smallest index, its message behind "unit %zu: ";
-  // a guarded context fails a unit whose proof its verifier rejects, on the thread that proved it)
+// The unit loop of the batch calls: context 0 works on the caller's thread, context i on thread i (min(contexts, count) threads),
+// and each takes the next unit -- unit(P, u) is witness, then proof, of unit u on context P -- until one fails.  The failure
+// rule: the failing unit with the smallest index, its message behind "unit %zu: ", and every proof slot nulled (a guarded context
+// fails a unit whose proof its verifier rejects, on the thread that proved it).
+static int prove_units(sbn_batch_prover* B, size_t count, sbn_proof** proofs_out, const std::function<int(sbn_prover*, size_t)>& unit) {
   std::atomic<size_t> next(0), first_unit(count);
   std::mutex m; int first_rc = 0; std::string msg;
   auto work = [&](sbn_prover* P) {
     for (size_t u; (u = next.fetch_add(1)) < count && first_unit.load() == count;) {
-      int rc = sbn_prover_generate_trace(P, ios + u * ios_words_per_unit, num_io, nullptr);
-      if (!rc) rc = sbn_prover_prove(P, &proofs_out[u]);
+      const int rc = unit(P, u);
       if (rc) { std::lock_guard<std::mutex> g(m); if (u < first_unit.load()) { first_unit = u; first_rc = rc; msg = g_last_error; } }
     }
   };
@@ -236,6 +233,16 @@ int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t 
     return fail(first_rc, "unit %zu: %s", first_unit.load(), msg.c_str());
   }
   return SBN_OK;
+}
+int sbn_batch_prover_prove_ios(sbn_batch_prover* B, const uint32_t* ios, size_t ios_words_per_unit, size_t num_io, size_t count, sbn_proof** proofs_out) {
+  if (!B || !ios || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  for (size_t i = 0; i < count; i++) proofs_out[i] = nullptr;
+  if (exp_io_words(B->kind) == 0 || ios_words_per_unit != exp_io_words(B->kind) * num_io)
+    return fail(SBN_ERR_BAD_ARG, "ios_words_per_unit must be %zu u32 words per instance times num_io", exp_io_words(B->kind));
+  return prove_units(B, count, proofs_out, [&](sbn_prover* P, size_t u) {
+    const int rc = sbn_prover_generate_trace(P, ios + u * ios_words_per_unit, num_io, nullptr);
+    return rc ? rc : sbn_prover_prove(P, &proofs_out[u]);
+  });
 }
 
 // Verified proving (include/sbn.h): the mode of every context; each owns its verifier and checks on its own worker thread
@@ -265,23 +272,9 @@ int sbn_batch_prover_prove_host_columns(sbn_batch_prover* B, const uint64_t* con
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
   for (size_t i = 0; i < count; i++) proofs_out[i] = nullptr;
   if (count && (!columns || (n_pi && !public_inputs))) return fail(SBN_ERR_BAD_ARG, "null argument");
-  std::atomic<size_t> next(0), first_unit(count);
-  std::mutex m; int first_rc = 0; std::string msg;
-  auto work = [&](sbn_prover* P) {
-    for (size_t u; (u = next.fetch_add(1)) < count && first_unit.load() == count;) {
-      const int rc = sbn_prover_prove_host_columns(P, columns + u * n_columns, n_columns, flags, n_pi ? public_inputs[u] : nullptr, n_pi, nullptr, &proofs_out[u]);
-      if (rc) { std::lock_guard<std::mutex> g(m); if (u < first_unit.load()) { first_unit = u; first_rc = rc; msg = g_last_error; } }
-    }
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 1; i < B->provers.size() && i < count; i++) th.emplace_back(work, B->provers[i]);
-  work(B->provers[0]);
-  for (auto& t : th) t.join();
-  if (first_rc) {
-    for (size_t i = 0; i < count; i++) { delete proofs_out[i]; proofs_out[i] = nullptr; }
-    return fail(first_rc, "unit %zu: %s", first_unit.load(), msg.c_str());
-  }
-  return SBN_OK;
+  return prove_units(B, count, proofs_out, [&](sbn_prover* P, size_t u) {
+    return sbn_prover_prove_host_columns(P, columns + u * n_columns, n_columns, flags, n_pi ? public_inputs[u] : nullptr, n_pi, nullptr, &proofs_out[u]);
+  });
 }
 
 // What the four calls below share: every proof slot of the `units` units is nulled; `derive(ios)` checks what is left to check and

@@ -1,6 +1,6 @@
-// Host helpers over bn254w.cuh shared by the units that derive instance lists on the host pool (chain_instances.hip,
-// scalar_mul.hip, powers.hip, msm_batch.hip): u32-limb loads and stores, the curve constants, the on-curve test, the norm-based
-// inversion of a Z, and the batched affine form of a list of Jacobian points that may hold the point at infinity.
+// Host helpers over bn254w.cuh shared by the units that derive instance lists on the host pool (through instance_lists.hpp):
+// u32-limb loads and stores, the curve constants, the on-curve test, the norm-based inversion of a Z, and the batched affine form
+// of a list of Jacobian points that may hold the point at infinity.
 #pragma once
 #include "host_common.hpp"
 #include "bn254w.cuh"
@@ -44,23 +44,6 @@ template <int E> Jac<E> ld_point(const uint32_t* w) {
   for (int q = 0; q < E; q++) { ld_u32(w + 8 * q, t); p.X.c[q] = to_m(t); ld_u32(w + 8 * (E + q), t); p.Y.c[q] = to_m(t); }
   p.Z = cone<E>();
   return p;
-}
-
-// The refusals of a curve list: `start` (named `start_name` in the message) and the K points at pts + stride * k have coordinates
-// below p and lie on the table's curve; the first offending instance is named.
-template <int E> int check_curve_points(const uint32_t* pts, size_t stride, size_t K, const uint32_t* start, const char* start_name) {
-  if (!below_p(start, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (%s)", start_name);
-  for (size_t k = 0; k < K; k++) if (!below_p(pts + stride * k, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (instance %zu)", k);
-  const Co<E> b = curve_b<E>();
-  const Jac<E> s = ld_point<E>(start);
-  if (!on_curve<E>(s.X, s.Y, b)) return fail(SBN_ERR_BAD_ARG, "%s is not a point of the curve", start_name);
-  std::atomic<size_t> bad(K);
-  host_parallel_for(K, [&](size_t k) {
-    const Jac<E> p = ld_point<E>(pts + stride * k);
-    if (!on_curve<E>(p.X, p.Y, b)) { size_t cur = bad.load(); while (k < cur && !bad.compare_exchange_weak(cur, k)) {} }
-  });
-  if (bad.load() < K) return fail(SBN_ERR_BAD_ARG, "x of instance %zu is not a point of the curve", bad.load());
-  return SBN_OK;
 }
 
 // e x for a 256-bit e (eight u32 limbs, not reduced), most significant bit first, with the complete addition

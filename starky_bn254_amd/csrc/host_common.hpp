@@ -92,32 +92,34 @@ static inline bool air_shape(const sbn_air_desc* air, const sbn_config* cfg, Air
 static inline bool is_op_air(int kind) { return kind == SBN_AIR_MODULAR || kind == SBN_AIR_FQ12_MUL; }   // OpShape tables (air.cuh)
 static inline bool is_exp_air(int kind) { return kind == SBN_AIR_G1_EXP || kind == SBN_AIR_G2_EXP || kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ_EXP || kind == SBN_AIR_FQ12_EXP_U64; }
 static inline size_t exp_rows_per_instance(int kind) { return (kind == SBN_AIR_FQ12_EXP_U64 || kind == SBN_AIR_FLAGS_U64) ? 128 : 512; }   // (FLAGS: 512)
-// u32 words of one instance in the `ios` arrays of include/sbn.h (x, offset, exp_val)
-static inline size_t exp_io_words(int kind) {
-  switch (kind) {
-    case SBN_AIR_G1_EXP: return 40; case SBN_AIR_G2_EXP: return 72; case SBN_AIR_FQ12_EXP: return 200; case SBN_AIR_FQ_EXP: return 24;
-    case SBN_AIR_FQ12_EXP_U64: return 194; default: return 0;
-  }
-}
-// The public inputs of one instance of an Exp table (g1_exp_io_to_columns, src/curves/g1/exp.rs:124-135, and its twins): x[W]
-// offset[W] exp[EW] output[W]; u32 limbs on the curves and in Fq, 16-bit limbs in Fq12 (exponent: eight u32 limbs, or one u64 in
-// FQ12_EXP_U64).  Read by the link checks of msm.hip, msm_batch.hip and powers.hip and by witness_diff.hip, which inverts it.
+// The word counts of an Exp table, the only place that states them.  An instance row of the `ios` arrays of include/sbn.h is x[xw]
+// offset[xw] exp_val[ew] u32 words; a term (`terms`, `starts`) is such a row without its offset.  The public inputs of one instance
+// (g1_exp_io_to_columns, src/curves/g1/exp.rs:124-135, and its twins) are x[W] offset[W] exp[EW] output[W]: u32 limbs on the curves
+// and in Fq, 16-bit limbs in Fq12 (exponent: eight u32 limbs, or one u64 in FQ12_EXP_U64).
 struct PiLayout {
   size_t W, EW, xw, ew;   // W / EW: public inputs per value / exponent; xw / ew: u32 words of the same in an instance row of `ios`
   bool limb16;
+  int E;                  // 1 / 2 on the curves (G1 / the twist), 0 in the fields
   size_t per() const { return 3 * W + EW; }
+  size_t T() const { return xw + ew; }
+  size_t IOW() const { return 2 * xw + ew; }
+  int values() const { return (int)(xw / 8); }   // Fq elements of a value
+  bool field() const { return xw && !E; }        // a field Exp table (FQ_EXP, FQ12_EXP, FQ12_EXP_U64)
 };
 static inline bool pi_layout(int kind, PiLayout& L) {
   switch (kind) {
-    case SBN_AIR_G1_EXP: L = {16, 8, 16, 8, false}; return true;
-    case SBN_AIR_G2_EXP: L = {32, 8, 32, 8, false}; return true;
-    case SBN_AIR_FQ_EXP: L = {8, 8, 8, 8, false}; return true;
-    case SBN_AIR_FQ12_EXP: L = {192, 8, 96, 8, true}; return true;
-    case SBN_AIR_FQ12_EXP_U64: L = {192, 1, 96, 2, true}; return true;
-    default: L = {0, 0, 0, 0, false}; return false;
+    case SBN_AIR_G1_EXP: L = {16, 8, 16, 8, false, 1}; return true;
+    case SBN_AIR_G2_EXP: L = {32, 8, 32, 8, false, 2}; return true;
+    case SBN_AIR_FQ_EXP: L = {8, 8, 8, 8, false, 0}; return true;
+    case SBN_AIR_FQ12_EXP: L = {192, 8, 96, 8, true, 0}; return true;
+    case SBN_AIR_FQ12_EXP_U64: L = {192, 1, 96, 2, true, 0}; return true;
+    default: L = {0, 0, 0, 0, false, 0}; return false;
   }
 }
 static inline PiLayout pi_layout(int kind) { PiLayout L; pi_layout(kind, L); return L; }
+static inline PiLayout curve_layout(int E) { return pi_layout(E == 1 ? SBN_AIR_G1_EXP : SBN_AIR_G2_EXP); }   // E = 1 / 2
+// u32 words of one instance in `ios` (0: not an Exp table)
+static inline size_t exp_io_words(int kind) { return pi_layout(kind).IOW(); }
 // a value (xw u32 words) as the W public inputs that carry it, and an exponent (ew words) as its EW
 static inline void value_to_pi(const PiLayout& L, const uint32_t* w, uint64_t* out) {
   if (!L.limb16) { for (size_t i = 0; i < L.W; i++) out[i] = w[i]; return; }
@@ -189,14 +191,13 @@ bool derived_columns_host(const ExpShape& sh, uint64_t* trace, size_t n);
 int host_rows_precheck(const sbn_air_desc* air, const sbn_host_rows* rows, uint32_t flags, const uint64_t* pi, size_t n_pi, uint32_t* degree_bits_out);
 // tracegen.hip: the curve chains run eight instances per AVX-512 IFMA register on this CPU (0.15 ms per group of eight)
 bool tracegen_host_chains_vectorized();
-// chain_instances.hip: sbn_chain_instances behind its argument checks (kind: sbn_air_kind of an Exp table), and its refusals alone
-// for the curve tables (a coordinate >= p, a point off the curve): what the device derivation of tracegen_device.hip checks first
+// The instance-list units (instance_lists.hpp says what they share), as tracegen_device.hip and capi.hip call them.
+// chain_instances.hip: sbn_chain_instances behind its argument checks, and its refusals alone for the curve tables
 int chain_instances_host(int kind, const uint32_t* terms, size_t K, const uint32_t* start, uint32_t* ios, uint32_t* final_out);
 int chain_terms_check_curve(int E, const uint32_t* terms, size_t K, const uint32_t* start);
-// scalar_mul.hip (independent scalar multiplications on the curve tables, E = 1 / 2): the generator words ([16E] u32) and 2p - r;
-// the refusals of the points and the offset (>= p, off the curve); the explicit list of `total` >= count rows (x, offset, scalar;
-// rows past count repeat row count - 1); SBN_ERR_WITNESS naming the first of K instances the table cannot walk (SBN_OK: none);
-// product = output + (-offset) by the complete addition for K affine outputs ([K][16E] u32; flag 1 and zero words = infinity)
+// scalar_mul.hip (E = 1 / 2): the generator ([16E] u32) and 2p - r; the refusals of the points and the offset; the explicit list of
+// `total` >= count rows; SBN_ERR_WITNESS naming the first of K instances the table cannot walk (SBN_OK: none); product = output +
+// (-offset) for K affine outputs ([K][16E] u32; flag 1 and zero words = infinity)
 const uint32_t* curve_generator_words(int E);
 const uint32_t* g2_cofactor_words();
 int scalar_mul_check_points(int E, const uint32_t* points, size_t count, const uint32_t* offset);
@@ -204,18 +205,19 @@ void scalar_mul_explicit_list(int E, const uint32_t* points, const uint32_t* sca
                               const uint32_t* offset, uint32_t* ios);
 int scalar_mul_name_degenerate(int E, const uint32_t* ios, size_t K);
 void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* offset, size_t K, uint32_t* products, uint8_t* infinity);
-// powers.hip (field powers and power towers on the field Exp tables): u32 words of one field element in `ios` (8 / 96; 0: not a
-// field Exp table); the refusals of the bases and exponents (a coefficient >= p, a u64 exponent that is no canonical field element),
-// naming the tower
-size_t power_elem_words(int kind);
+// powers.hip: the refusals of the bases and exponents of a field Exp table, naming the tower
 int power_check_inputs(int kind, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count);
-// msm_batch.hip (segmented chained lists on the five Exp tables): the argument refusals every entry point shares, in the header's
-// order (a null `*starts` becomes the generator / one with *start_count = 1; *M_out = the sum of the lengths); the refusals of the
-// values (>= p, off the curve, a non-canonical u64 exponent), naming the global instance and its segment; and the derivation behind
-// both: `total` >= M rows of ios (rows past M repeat row M - 1), the finals, and on the curves the sums and their infinity flags
+// msm_batch.hip (segmented chained lists; a chained list is one segment): the argument refusals in the header's order (a null
+// `*starts` becomes the generator / one with *start_count = 1; *M_out = the sum of the lengths); the refusals of the values, naming
+// the global instance and its segment; the derivation of `total` >= M rows of ios (rows past M repeat row M - 1), the finals and on
+// the curves the sums and their flags -- segmented_derive sets NO message: false and *why = what it cannot derive and the global
+// instance, for the entry point to word; msm_batch_derive = the refusals of the values, the derivation and the segmented wording
+struct ListRefusal { enum What { OFFSET_AT_INFINITY = 1, OUTPUT_AT_INFINITY, DEGENERATE_WALK, UNNAMED_WALK } what; size_t at; };
 int msm_batch_check_args(int kind, const void* terms, const uint64_t* lengths, size_t segments, const uint32_t** starts, size_t* start_count, size_t num_io,
                          const void* sums_out, const void* infinity_out, size_t* M_out);
 int msm_batch_check_inputs(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M);
+bool segmented_derive(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M,
+                      size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, ListRefusal* why);
 int msm_batch_derive(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M,
                      size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out);
 // prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)

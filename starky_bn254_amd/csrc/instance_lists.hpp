@@ -1,0 +1,111 @@
+// What the five units that turn application inputs into an explicit `ios` list share (chain_instances.hip, msm.hip, scalar_mul.hip,
+// powers.hip, msm_batch.hip): the search for the first offending instance on the host pool, the refusals of a curve list, the
+// field tables' square-and-multiply, the pad rule, the table's own walk of an explicit curve list, and the reader of the per-unit
+// public inputs behind the four *_check calls.  Host code only.  (The word counts of a table: PiLayout, host_common.hpp.)
+#pragma once
+#include "curve_host.hpp"
+#include <vector>
+
+namespace sbn {
+namespace curve_host {
+
+// the smallest index in [0, K) for which bad(k) holds, on the host pool; K when there is none
+template <typename F> size_t first_bad(size_t K, F bad) {
+  std::atomic<size_t> at(K);
+  host_parallel_for(K, [&](size_t k) {
+    if (k > at.load() || !bad(k)) return;
+    size_t cur = at.load(); while (k < cur && !at.compare_exchange_weak(cur, k)) {}
+  });
+  return at.load();
+}
+
+// The refusals of a curve list: `start` (named `start_name` in the message) and the K points at pts + stride * k have coordinates
+// below p and lie on the table's curve; the first offending instance is named.
+template <int E> int check_curve_points(const uint32_t* pts, size_t stride, size_t K, const uint32_t* start, const char* start_name) {
+  if (!below_p(start, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (%s)", start_name);
+  for (size_t k = 0; k < K; k++) if (!below_p(pts + stride * k, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (instance %zu)", k);
+  const Co<E> b = curve_b<E>();
+  const Jac<E> s = ld_point<E>(start);
+  if (!on_curve<E>(s.X, s.Y, b)) return fail(SBN_ERR_BAD_ARG, "%s is not a point of the curve", start_name);
+  const size_t bad = first_bad(K, [&](size_t k) { const Jac<E> p = ld_point<E>(pts + stride * k); return !on_curve<E>(p.X, p.Y, b); });
+  if (bad < K) return fail(SBN_ERR_BAD_ARG, "x of instance %zu is not a point of the curve", bad);
+  return SBN_OK;
+}
+
+// N Montgomery coefficients of a field element: 1 in Fq, 12 in Fq12 (the flat basis of the field tables); out may be a or b
+template <int N> void field_load(const uint32_t* w, Fq* out) { for (int c = 0; c < N; c++) { u64 t[4]; ld_u32(w + 8 * c, t); out[c] = to_m(t); } }
+template <int N> void field_store(const Fq* v, uint32_t* w) { for (int c = 0; c < N; c++) st_u32(v[c], w + 8 * c); }
+template <int N> void field_mul(const Fq* a, const Fq* b, Fq* out) {
+  if (N == 1) { out[0] = mmul(a[0], b[0]); return; }
+  Fq prod[12]; fq12_mul_m(a, b, prod); memcpy(out, prod, N * sizeof(Fq));
+}
+// x^e by the table's walk (a = x, b = 1; bit t set: b = a b; a = a a), `bits` exponent bits, least significant first
+template <int N> void field_power(const Fq* x, const uint32_t* e, int bits, Fq* out) {
+  Fq a[N], b[N];
+  for (int c = 0; c < N; c++) { a[c] = x[c]; b[c] = Fq{{0, 0, 0, 0}}; }
+  b[0] = fq_one();
+  for (int t = 0; t < bits; t++) { if ((e[t >> 5] >> (t & 31)) & 1) field_mul<N>(a, b, b); field_mul<N>(a, a, a); }
+  memcpy(out, b, sizeof b);
+}
+
+// rows [M, total) <- row M - 1: the reference's resize rule (src/curves/g1/circuit.rs:273-277), a pad row is the last row again
+inline void pad_rows(uint32_t* ios, size_t IOW, size_t M, size_t total) {
+  for (size_t g = M; g < total; g++) memcpy(ios + IOW * g, ios + IOW * (M - 1), IOW * sizeof(uint32_t));
+}
+
+inline bool same(const uint64_t* a, const uint64_t* b, size_t n) { return memcmp(a, b, n * sizeof(uint64_t)) == 0; }
+
+// The table's own walk (g1/exp.rs:165-230) of the K instances of an explicit curve list, B[t] = +-A[t] at an addition refuses it.
+// first_unwalkable: one instance at a time, the first one the table cannot walk (K: none).  walk_curve_list: with the chains the
+// witness generators use (tracegen_host_chains), 512 instances per pass to bound the chain storage (49 KB E per instance); WALKS
+// when the table walks them all, the first instance it cannot walk, or UNNAMED when a pass fails and no instance of it does.
+static constexpr size_t WALKS = (size_t)-1, UNNAMED = (size_t)-2;
+template <int E> size_t first_unwalkable(const uint32_t* ios, size_t K) {
+  return first_bad(K, [&](size_t k) {
+    std::vector<u64> ja(257 * 12 * E), jb(257 * 12 * E);
+    return exp_chains<E>(ios + curve_layout(E).IOW() * k, 0, ja.data(), jb.data()) != 0;
+  });
+}
+template <int E> size_t walk_curve_list(const uint32_t* ios, size_t K) {
+  const size_t CH = 512, IOW = curve_layout(E).IOW();
+  std::vector<u64> chains(2 * 257 * 12 * E * (K < CH ? K : CH));
+  for (size_t at = 0; at < K; at += CH) {
+    const size_t k = K - at < CH ? K - at : CH, cw = 257 * 12 * E * k;
+    if (!tracegen_host_chains(E, ios + IOW * at, k, chains.data(), chains.data() + cw)) continue;
+    const size_t bad = first_unwalkable<E>(ios + IOW * at, k);
+    return bad == k ? UNNAMED : at + bad;
+  }
+  return WALKS;
+}
+static constexpr const char* UNNAMED_WALK_TEXT = "degenerate affine operation (x1 == x2 or y == 0)";
+
+// The public inputs of the unit proofs of one list, as the link checks read them: instance g is row g % num_io of unit g / num_io.
+struct UnitInputs {
+  const PiLayout L;
+  const size_t num_io, units, oX, oOff, oExp, oOut;   // the four values of an instance start at these public inputs
+  const uint64_t* const* const pi;
+  UnitInputs(int kind, size_t num_io, const uint64_t* const* public_inputs, size_t units)
+      : L(pi_layout(kind)), num_io(num_io), units(units), oX(0), oOff(L.W), oExp(2 * L.W), oOut(2 * L.W + L.EW), pi(public_inputs) {}
+  size_t rows() const { return units * num_io; }
+  int null_unit() const {
+    for (size_t u = 0; u < units; u++) if (!pi[u]) return fail(SBN_ERR_BAD_ARG, "null public inputs (unit %zu)", u);
+    return SBN_OK;
+  }
+  const uint64_t* inst(size_t g) const { return pi[g / num_io] + L.per() * (g % num_io); }
+  // a pad instance g is instance `last` again
+  int pad(size_t g, size_t last) const {
+    static const char* const field[4] = {"x", "offset", "exponent", "output"};
+    const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {L.W, L.W, L.EW, L.W};
+    for (int f = 0; f < 4; f++)
+      if (!same(inst(g) + at[f], inst(last) + at[f], len[f])) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (pad): %s differs from instance %zu", g, field[f], last);
+    return SBN_OK;
+  }
+  // the value at oX / oOff, and the exponent, of instance g are the caller's u32 words
+  bool value_is(size_t g, size_t at, const uint32_t* w) const { std::vector<uint64_t> want(L.W); value_to_pi(L, w, want.data()); return same(inst(g) + at, want.data(), L.W); }
+  bool exp_is(size_t g, const uint32_t* w) const { uint64_t e[8]; exp_to_pi(L, w, e); return same(inst(g) + oExp, e, L.EW); }
+  // the output of instance g as the L.xw u32 words of a value; false and *limb = the first limb wider than its slot: no output of the table
+  bool output(size_t g, uint32_t* w, size_t* limb) const { return value_from_pi(L, inst(g) + oOut, w, limb); }
+};
+
+}  // namespace curve_host
+}  // namespace sbn

@@ -1,16 +1,19 @@
 // Batches of short MSMs (include/sbn.h, "Batches of short MSMs"): SEGMENTED chained lists packed into shared units.  The
 // reference's g1_exp_circuit (src/curves/g1/circuit.rs:262-304) takes any list of inputs and the caller wires the offsets: some
 // inputs continue a chain, others start a new one -- one public-key aggregation per signature, one product of a few x_k^e_k per
-// pairing check.  sbn_msm_instances is one segment, sbn_scalar_mul_instances is segments of length 1 with a shared start; here
-//  * sbn_msm_batch_instances derives the whole explicit list on the host pool by the scheme of chain_instances.hip: the terms
-//    e_k x_k (x_k^e_k) in parallel, one pass of complete additions (products) per segment from the segment's own start, ONE
-//    inversion for the affine form of every offset, final and sum, then the table's own walk of the explicit list;
+// pairing check.  sbn_chain_instances / sbn_msm_instances is one segment (and derived here: segmented_derive),
+// sbn_scalar_mul_instances is segments of length 1 with a shared start; here
+//  * sbn_msm_batch_instances derives the whole explicit list on the host pool: the terms e_k x_k (x_k^e_k) in parallel, one pass
+//    of complete additions (products) per segment from the segment's own start, ONE inversion for the affine form of every
+//    offset, final and sum, then the table's own walk of the explicit list.  On the curves the terms run in Jacobian coordinates
+//    with the COMPLETE addition of bn254w.cuh (a term may be the identity, and the double-and-add inside a term meets equal
+//    operands when e has a leading 1 only): a collision in this derivation says nothing about the table's own walk and is not
+//    an error; only that walk, or an offset at infinity, refuses a list;
 //  * sbn_msm_batch_check is what the `connect` calls of a circuit are: it reads the public inputs of the unit proofs and checks that
 //    every head starts from its start, that every other offset is the output before it, and that the pads repeat the last instance.
 //    It verifies no proof.
 // Host code only: no kernel is launched from this unit (tracegen_device.hip holds the device form of the derivation).
-#include "curve_host.hpp"
-#include <cstring>
+#include "instance_lists.hpp"
 
 using namespace sbn;
 
@@ -18,24 +21,6 @@ namespace {
 using namespace bnw;
 using namespace sbn::curve_host;
 
-// word counts of a table: x / offset value (xw), exponent (ew), in `terms`, `starts` and `ios`; N = Fq components of a value
-struct Tab {
-  int E;          // 1 / 2 on the curves, 0 in the fields
-  size_t xw, ew;
-  size_t T() const { return xw + ew; }
-  size_t IOW() const { return 2 * xw + ew; }
-  int values() const { return (int)(xw / 8); }
-};
-bool table_of(int kind, Tab& t) {
-  switch (kind) {
-    case SBN_AIR_G1_EXP: t = {1, 16, 8}; return true;
-    case SBN_AIR_G2_EXP: t = {2, 32, 8}; return true;
-    case SBN_AIR_FQ_EXP: t = {0, 8, 8}; return true;
-    case SBN_AIR_FQ12_EXP: t = {0, 96, 8}; return true;
-    case SBN_AIR_FQ12_EXP_U64: t = {0, 96, 2}; return true;
-    default: return false;
-  }
-}
 const uint32_t FIELD_ONE[96] = {1};
 
 // head[s] = the global index of the first instance of segment s (head[segments] = M); seg[g] = the segment of instance g
@@ -49,33 +34,23 @@ struct Layout {
   }
 };
 
-// the smallest index in [0, K) for which bad(k) holds, on the host pool; K when there is none
-template <typename F> size_t first_bad(size_t K, F bad) {
-  std::atomic<size_t> at(K);
-  host_parallel_for(K, [&](size_t k) {
-    if (k > at.load() || !bad(k)) return;
-    size_t cur = at.load(); while (k < cur && !at.compare_exchange_weak(cur, k)) {}
-  });
-  return at.load();
-}
-
 // ---- the refusals of the inputs, in the header's order: >= p, off the curve, a non-canonical u64 exponent --------------------------
-template <int E> int check_curve_inputs(const uint32_t* terms, size_t M, const Layout& L, const uint32_t* starts, size_t start_count) {
-  const size_t T = 16 * E + 8;
+template <int E> int check_curve_inputs(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, const uint32_t* starts, size_t start_count) {
+  const size_t T = t.T();
   for (size_t s = 0; s < start_count; s++)
-    if (!below_p(starts + 16 * E * s, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (start %zu)", s);
+    if (!below_p(starts + t.xw * s, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (start %zu)", s);
   for (size_t g = 0; g < M; g++)
     if (!below_p(terms + T * g, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (instance %zu, segment %u)", g, L.seg[g]);
   const Co<E> b = curve_b<E>();
   for (size_t s = 0; s < start_count; s++) {
-    const Jac<E> p = ld_point<E>(starts + 16 * E * s);
+    const Jac<E> p = ld_point<E>(starts + t.xw * s);
     if (!on_curve<E>(p.X, p.Y, b)) return fail(SBN_ERR_BAD_ARG, "start %zu is not a point of the curve", s);
   }
   const size_t bad = first_bad(M, [&](size_t g) { const Jac<E> p = ld_point<E>(terms + T * g); return !on_curve<E>(p.X, p.Y, b); });
   if (bad < M) return fail(SBN_ERR_BAD_ARG, "x of instance %zu (segment %u) is not a point of the curve", bad, L.seg[bad]);
   return SBN_OK;
 }
-int check_field_inputs(const Tab& t, const uint32_t* terms, size_t M, const Layout& L, const uint32_t* starts, size_t start_count) {
+int check_field_inputs(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, const uint32_t* starts, size_t start_count) {
   const char* what = t.xw == 8 ? "value" : "coefficient";
   for (size_t s = 0; s < start_count; s++)
     if (!below_p(starts + t.xw * s, t.values())) return fail(SBN_ERR_BAD_ARG, "%s >= p (start %zu)", what, s);
@@ -87,18 +62,17 @@ int check_field_inputs(const Tab& t, const uint32_t* terms, size_t M, const Layo
         return fail(SBN_ERR_NON_CANONICAL, "exponent of instance %zu (segment %u) is not a canonical field element", g, L.seg[g]);
   return SBN_OK;
 }
-
-// rows [M, total) <- row M - 1: the reference's resize rule (src/curves/g1/circuit.rs:273-277)
-void pad_rows(uint32_t* ios, size_t IOW, size_t M, size_t total) {
-  for (size_t g = M; g < total; g++) memcpy(ios + IOW * g, ios + IOW * (M - 1), IOW * sizeof(uint32_t));
+int check_inputs(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, const uint32_t* starts, size_t start_count) {
+  if (t.E == 1) return check_curve_inputs<1>(t, terms, M, L, starts, start_count);
+  if (t.E == 2) return check_curve_inputs<2>(t, terms, M, L, starts, start_count);
+  return check_field_inputs(t, terms, M, L, starts, start_count);
 }
 
-// ---- the curve tables ------------------------------------------------------------------------------------------------------------
+// ---- the derivation: what it cannot derive goes into `why`, worded by the entry point; it asks no one who called ------------------
 template <int E>
-int derive_curve(const uint32_t* terms, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count, size_t total,
-                 uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out) {
-  const size_t T = 16 * E + 8, IOW = 32 * E + 8, W = 16 * E;
-  if (int rc = check_curve_inputs<E>(terms, M, L, starts, start_count)) return rc;
+bool derive_curve(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count, size_t total,
+                  uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, ListRefusal* why) {
+  const size_t T = t.T(), IOW = t.IOW(), W = t.xw;
   std::vector<Jac<E>> term(M);
   host_parallel_for(M, [&](size_t g) { term[g] = scalar_mul_jac<E>(ld_point<E>(terms + T * g), terms + T * g + W); });
   // pts: the M offsets, then the finals, then the sums final + (-start) of every segment
@@ -112,8 +86,8 @@ int derive_curve(const uint32_t* terms, size_t M, const Layout& L, size_t segmen
   });
   for (size_t g = 0; g < M; g++) {   // in instance order: the table cannot hold the point at infinity
     const size_t s = L.seg[g];
-    if (czero<E>(pts[g].Z)) return fail(SBN_ERR_WITNESS, "the offset of instance %zu (segment %zu) is the point at infinity", g, s);
-    if (g + 1 == L.head[s + 1] && czero<E>(pts[M + s].Z)) return fail(SBN_ERR_WITNESS, "the output of instance %zu (segment %zu) is the point at infinity", g, s);
+    if (czero<E>(pts[g].Z)) { *why = {ListRefusal::OFFSET_AT_INFINITY, g}; return false; }
+    if (g + 1 == L.head[s + 1] && czero<E>(pts[M + s].Z)) { *why = {ListRefusal::OUTPUT_AT_INFINITY, g}; return false; }
   }
   std::vector<uint32_t> aff(W * pts.size());
   std::vector<uint8_t> inf(pts.size());
@@ -122,74 +96,60 @@ int derive_curve(const uint32_t* terms, size_t M, const Layout& L, size_t segmen
     uint32_t* io = ios + IOW * g;
     memcpy(io, terms + T * g, W * sizeof(uint32_t));
     memcpy(io + W, aff.data() + W * g, W * sizeof(uint32_t));
-    memcpy(io + 2 * W, terms + T * g + W, 8 * sizeof(uint32_t));
+    memcpy(io + 2 * W, terms + T * g + W, t.ew * sizeof(uint32_t));
   }
   pad_rows(ios, IOW, M, total);
   if (finals_out) memcpy(finals_out, aff.data() + W * M, W * segments * sizeof(uint32_t));
   if (sums_out) memcpy(sums_out, aff.data() + W * (M + segments), W * segments * sizeof(uint32_t));
   if (infinity_out) memcpy(infinity_out, inf.data() + M + segments, segments);
-  // the table's own walk of the real instances (g1/exp.rs:165-230), 512 at a time to bound the chain storage; the first instance it
-  // cannot walk is named through the one-instance form of the same walk
-  const size_t CH = 512;
-  std::vector<u64> chains(2 * 257 * 12 * E * (M < CH ? M : CH));
-  for (size_t at = 0; at < M; at += CH) {
-    const size_t k = M - at < CH ? M - at : CH, cw = 257 * 12 * E * k;
-    if (!tracegen_host_chains(E, ios + IOW * at, k, chains.data(), chains.data() + cw)) continue;
-    const size_t bad = first_bad(k, [&](size_t i) {
-      std::vector<u64> ja(257 * 12 * E), jb(257 * 12 * E);
-      return exp_chains<E>(ios + IOW * (at + i), 0, ja.data(), jb.data()) != 0;
-    });
-    if (bad == k) return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
-    return fail(SBN_ERR_WITNESS, "instance %zu (segment %u): degenerate affine operation in the table's walk (B[t] = +-2^t x at a set bit): pick another start",
-                at + bad, L.seg[at + bad]);
-  }
-  return SBN_OK;
+  const size_t bad = walk_curve_list<E>(ios, M);   // the real instances: the pads repeat the last one
+  if (bad == WALKS) return true;
+  *why = {bad == UNNAMED ? ListRefusal::UNNAMED_WALK : ListRefusal::DEGENERATE_WALK, bad};
+  return false;
 }
 
-// ---- the field tables: N = 1 (FQ_EXP) or 12 (the flat basis of the Fq12 tables) ------------------------------------------------------
-template <int N> void fmul(const Fq* a, const Fq* b, Fq* out) {
-  if (N == 1) { out[0] = mmul(a[0], b[0]); return; }
-  Fq prod[12]; fq12_mul_m(a, b, prod); memcpy(out, prod, N * sizeof(Fq));
-}
+// the field tables: N = 1 (FQ_EXP) or 12 (the flat basis of the Fq12 tables); an Fq power is short, so a pool task takes eight
 template <int N>
-int derive_field(const Tab& t, const uint32_t* terms, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count, size_t total,
-                 uint32_t* ios, uint32_t* finals_out) {
-  const size_t W = 8 * N, T = t.T(), IOW = t.IOW();
-  if (int rc = check_field_inputs(t, terms, M, L, starts, start_count)) return rc;
+void derive_field(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count, size_t total,
+                  uint32_t* ios, uint32_t* finals_out) {
+  const size_t W = 8 * N, T = t.T(), IOW = t.IOW(), G = N == 1 ? 8 : 1;
   std::vector<Fq> term((size_t)N * M);
-  host_parallel_for(M, [&](size_t g) {   // x^e by the table's square-and-multiply, least significant bit first
-    Fq a[N], b[N];
-    for (int c = 0; c < N; c++) { u64 t4[4]; ld_u32(terms + T * g + 8 * c, t4); a[c] = to_m(t4); b[c] = Fq{{0, 0, 0, 0}}; }
-    b[0] = fq_one();
-    const uint32_t* e = terms + T * g + W;
-    for (int i = 0; i < (int)(32 * t.ew); i++) { if ((e[i >> 5] >> (i & 31)) & 1) fmul<N>(a, b, b); fmul<N>(a, a, a); }
-    memcpy(&term[(size_t)N * g], b, sizeof b);
+  host_parallel_for((M + G - 1) / G, [&](size_t i) {
+    for (size_t g = G * i; g < M && g < G * i + G; g++) {
+      Fq x[N];
+      field_load<N>(terms + T * g, x);
+      field_power<N>(x, terms + T * g + W, (int)(32 * t.ew), &term[(size_t)N * g]);
+    }
   });
   host_parallel_for(segments, [&](size_t s) {
     Fq off[N];
-    for (int c = 0; c < N; c++) { u64 t4[4]; ld_u32(starts + (start_count == 1 ? 0 : W * s) + 8 * c, t4); off[c] = to_m(t4); }
+    field_load<N>(starts + (start_count == 1 ? 0 : W * s), off);
     for (size_t g = L.head[s]; g < L.head[s + 1]; g++) {
       uint32_t* io = ios + IOW * g;
       memcpy(io, terms + T * g, W * sizeof(uint32_t));
-      for (int c = 0; c < N; c++) st_u32(off[c], io + W + 8 * c);
+      field_store<N>(off, io + W);
       memcpy(io + 2 * W, terms + T * g + W, t.ew * sizeof(uint32_t));
-      fmul<N>(off, &term[(size_t)N * g], off);
+      field_mul<N>(off, &term[(size_t)N * g], off);
     }
-    if (finals_out) for (int c = 0; c < N; c++) st_u32(off[c], finals_out + W * s + 8 * c);
+    if (finals_out) field_store<N>(off, finals_out + W * s);
   });
   pad_rows(ios, IOW, M, total);
-  return SBN_OK;
 }
 
-// ---- sbn_msm_batch_check: the public inputs of one instance are x[W] offset[W] exp[EW] output[W] (g1_exp_io_to_columns,
-// src/curves/g1/exp.rs:124-135, and its twins): u32 limbs on the curves and in Fq, 16-bit limbs in Fq12 -----------------------------
-// (PiLayout: host_common.hpp)
-bool same(const uint64_t* a, const uint64_t* b, size_t n) { return memcmp(a, b, n * sizeof(uint64_t)) == 0; }
+bool derive(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count, size_t total,
+            uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, ListRefusal* why) {
+  if (t.E == 1) return derive_curve<1>(t, terms, M, L, segments, starts, start_count, total, ios, finals_out, sums_out, infinity_out, why);
+  if (t.E == 2) return derive_curve<2>(t, terms, M, L, segments, starts, start_count, total, ios, finals_out, sums_out, infinity_out, why);
+  if (t.xw == 8) derive_field<1>(t, terms, M, L, segments, starts, start_count, total, ios, finals_out);
+  else derive_field<12>(t, terms, M, L, segments, starts, start_count, total, ios, finals_out);
+  return true;
+}
 
+// ---- sbn_msm_batch_check on the curves: the outputs are points, and final + (-start) per segment -------------------------------------
 template <int E>
-int check_curve_outputs(const std::vector<uint32_t>& outs, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count,
+int check_curve_outputs(const PiLayout& t, const std::vector<uint32_t>& outs, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count,
                         uint32_t* sums_out, uint8_t* infinity_out) {
-  const size_t W = 16 * E;
+  const size_t W = t.xw;
   const Co<E> b = curve_b<E>();
   for (size_t g = 0; g < M; g++) {
     const uint32_t* o = outs.data() + W * g;
@@ -209,8 +169,8 @@ int check_curve_outputs(const std::vector<uint32_t>& outs, size_t M, const Layou
 namespace sbn {
 int msm_batch_check_args(int kind, const void* terms, const uint64_t* lengths, size_t segments, const uint32_t** starts, size_t* start_count, size_t num_io,
                          const void* sums_out, const void* infinity_out, size_t* M_out) {
-  Tab t;
-  if (!table_of(kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table: segmented lists cover the five Exp tables", kind);
+  PiLayout t;
+  if (!pi_layout(kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table: segmented lists cover the five Exp tables", kind);
   if (!terms || !lengths) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (segments == 0) return fail(SBN_ERR_BAD_ARG, "no segment");
   size_t M = 0;
@@ -229,23 +189,32 @@ int msm_batch_check_args(int kind, const void* terms, const uint64_t* lengths, s
 }
 
 int msm_batch_check_inputs(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M) {
-  Tab t;
-  if (!table_of(kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table", kind);
-  const Layout L(lengths, segments, M);
-  if (t.E == 1) return check_curve_inputs<1>(terms, M, L, starts, start_count);
-  if (t.E == 2) return check_curve_inputs<2>(terms, M, L, starts, start_count);
-  return check_field_inputs(t, terms, M, L, starts, start_count);
+  PiLayout t;
+  if (!pi_layout(kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table", kind);
+  return check_inputs(t, terms, M, Layout(lengths, segments, M), starts, start_count);
+}
+
+bool segmented_derive(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M,
+                      size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, ListRefusal* why) {
+  return derive(pi_layout(kind), terms, M, Layout(lengths, segments, M), segments, starts, start_count, total, ios, finals_out, sums_out, infinity_out, why);
 }
 
 int msm_batch_derive(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M,
                      size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out) {
-  Tab t;
-  if (!table_of(kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table", kind);
+  PiLayout t;
+  if (!pi_layout(kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table", kind);
   const Layout L(lengths, segments, M);
-  if (t.E == 1) return derive_curve<1>(terms, M, L, segments, starts, start_count, total, ios, finals_out, sums_out, infinity_out);
-  if (t.E == 2) return derive_curve<2>(terms, M, L, segments, starts, start_count, total, ios, finals_out, sums_out, infinity_out);
-  if (t.xw == 8) return derive_field<1>(t, terms, M, L, segments, starts, start_count, total, ios, finals_out);
-  return derive_field<12>(t, terms, M, L, segments, starts, start_count, total, ios, finals_out);
+  if (int rc = check_inputs(t, terms, M, L, starts, start_count)) return rc;
+  ListRefusal why;
+  if (derive(t, terms, M, L, segments, starts, start_count, total, ios, finals_out, sums_out, infinity_out, &why)) return SBN_OK;
+  const size_t g = why.at, s = why.what == ListRefusal::UNNAMED_WALK ? 0 : L.seg[g];
+  switch (why.what) {
+    case ListRefusal::OFFSET_AT_INFINITY: return fail(SBN_ERR_WITNESS, "the offset of instance %zu (segment %zu) is the point at infinity", g, s);
+    case ListRefusal::OUTPUT_AT_INFINITY: return fail(SBN_ERR_WITNESS, "the output of instance %zu (segment %zu) is the point at infinity", g, s);
+    case ListRefusal::DEGENERATE_WALK:
+      return fail(SBN_ERR_WITNESS, "instance %zu (segment %zu): degenerate affine operation in the table's walk (B[t] = +-2^t x at a set bit): pick another start", g, s);
+    default: return fail(SBN_ERR_WITNESS, UNNAMED_WALK_TEXT);
+  }
 }
 }  // namespace sbn
 
@@ -264,54 +233,34 @@ extern "C" int sbn_msm_batch_check(int32_t kind, size_t num_io, const uint64_t* 
                                    const uint32_t* terms /*optional*/, const uint32_t* starts, size_t start_count, uint32_t* finals_out, uint32_t* sums_out,
                                    uint8_t* infinity_out) {
   size_t M = 0;
-  Tab t;
-  if (!table_of((int)kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table: segmented lists cover the five Exp tables", (int)kind);
+  PiLayout t;
+  if (!pi_layout((int)kind, t)) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not an Exp table: segmented lists cover the five Exp tables", (int)kind);
   if (!public_inputs) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (int rc = msm_batch_check_args((int)kind, public_inputs, lengths, segments, &starts, &start_count, num_io, sums_out, infinity_out, &M)) return rc;
   if (units != sbn_msm_num_units(M, num_io))
     return fail(SBN_ERR_VERIFY_FAILED, "%zu units given, %zu segments of %zu instances in tables of %zu have %zu units", units, segments, M, num_io, sbn_msm_num_units(M, num_io));
-  for (size_t u = 0; u < units; u++) if (!public_inputs[u]) return fail(SBN_ERR_BAD_ARG, "null public inputs (unit %zu)", u);
+  const UnitInputs U((int)kind, num_io, public_inputs, units);
+  if (int rc = U.null_unit()) return rc;
   if (!below_p(starts, t.values() * (int)start_count)) return fail(SBN_ERR_BAD_ARG, "%s >= p (starts)", t.E ? "coordinate" : "coefficient");
   const Layout L(lengths, segments, M);
-  const PiLayout P = pi_layout((int)kind);
-  const size_t per = P.per(), oX = 0, oOff = P.W, oExp = 2 * P.W, oOut = 2 * P.W + P.EW;
-  auto inst = [&](size_t g) { return public_inputs[g / num_io] + per * (g % num_io); };
-  const uint64_t lim = P.limb16 ? 0xffffULL : 0xffffffffULL;
-  const uint64_t* last = inst(M - 1);
-  std::vector<uint64_t> want(P.W);
   std::vector<uint32_t> outs(t.xw * M);
-  for (size_t g = 0; g < units * num_io; g++) {
-    const uint64_t* p = inst(g);
-    if (g >= M) {   // a pad instance is instance M - 1 again
-      static const char* const field[4] = {"x", "offset", "exponent", "output"};
-      const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {P.W, P.W, P.EW, P.W};
-      for (int f = 0; f < 4; f++)
-        if (!same(p + at[f], last + at[f], len[f])) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (pad): %s differs from instance %zu", g, field[f], M - 1);
-      continue;
-    }
+  for (size_t g = 0; g < U.rows(); g++) {
+    if (g >= M) { if (int rc = U.pad(g, M - 1)) return rc; continue; }
     const size_t s = L.seg[g];
     if (terms) {
-      value_to_pi(P, terms + t.T() * g, want.data());
-      if (!same(p + oX, want.data(), P.W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): x differs from the caller's term", g, s);
-      const uint32_t* e = terms + t.T() * g + t.xw;
-      uint64_t ep[8];
-      exp_to_pi(P, e, ep);
-      if (!same(p + oExp, ep, P.EW)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): exponent differs from the caller's term", g, s);
+      if (!U.value_is(g, U.oX, terms + t.T() * g)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): x differs from the caller's term", g, s);
+      if (!U.exp_is(g, terms + t.T() * g + t.xw)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): exponent differs from the caller's term", g, s);
     }
     if (g == L.head[s]) {
-      value_to_pi(P, starts + (start_count == 1 ? 0 : t.xw * s), want.data());
-      if (!same(p + oOff, want.data(), P.W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): offset differs from the start of the segment", g, s);
-    } else if (!same(p + oOff, inst(g - 1) + oOut, P.W))
+      if (!U.value_is(g, U.oOff, starts + (start_count == 1 ? 0 : t.xw * s)))
+        return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): offset differs from the start of the segment", g, s);
+    } else if (!same(U.inst(g) + U.oOff, U.inst(g - 1) + U.oOut, t.W))
       return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): offset differs from the output of instance %zu", g, s, g - 1);
-    // a limb wider than its slot is no output of the table
-    for (size_t i = 0; i < P.W; i++)
-      if (p[oOut + i] > lim) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): output limb %zu is out of range", g, s, i);
-    uint32_t* o = outs.data() + t.xw * g;
-    if (!P.limb16) for (size_t i = 0; i < t.xw; i++) o[i] = (uint32_t)p[oOut + i];
-    else for (size_t i = 0; i < t.xw; i++) o[i] = (uint32_t)(p[oOut + 2 * i] | (p[oOut + 2 * i + 1] << 16));
+    size_t limb;
+    if (!U.output(g, outs.data() + t.xw * g, &limb)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (segment %zu): output limb %zu is out of range", g, s, limb);
   }
-  if (t.E == 1) { if (int rc = check_curve_outputs<1>(outs, M, L, segments, starts, start_count, sums_out, infinity_out)) return rc; }
-  else if (t.E == 2) { if (int rc = check_curve_outputs<2>(outs, M, L, segments, starts, start_count, sums_out, infinity_out)) return rc; }
+  if (t.E == 1) { if (int rc = check_curve_outputs<1>(t, outs, M, L, segments, starts, start_count, sums_out, infinity_out)) return rc; }
+  else if (t.E == 2) { if (int rc = check_curve_outputs<2>(t, outs, M, L, segments, starts, start_count, sums_out, infinity_out)) return rc; }
   if (finals_out) for (size_t s = 0; s < segments; s++) memcpy(finals_out + t.xw * s, outs.data() + t.xw * (L.head[s + 1] - 1), t.xw * sizeof(uint32_t));
   return SBN_OK;
 }

@@ -10,8 +10,7 @@
 //    x, exponents and offset are the caller's, the pads repeat the last instance, and product = output + (-offset) by the complete
 //    addition (output = offset gives the point at infinity: not an error).  It verifies no proof.
 // Host code only: no kernel is launched from this unit (tracegen_device.hip holds the device form of the list and the un-offset).
-#include "curve_host.hpp"
-#include <cstring>
+#include "instance_lists.hpp"
 
 using namespace sbn;
 
@@ -29,78 +28,49 @@ const uint32_t G2_GEN[32] = {
 // 2p - r: the twist's group has order r (2p - r)
 const uint32_t G2_COFACTOR[8] = {0xc0f9fa8du, 0x345f2299u, 0x572a2489u, 0x06ceecdau, 0x8181585eu, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
 
-inline int curve_e(int kind) { return kind == SBN_AIR_G1_EXP ? 1 : (kind == SBN_AIR_G2_EXP ? 2 : 0); }
-
-// the table's own walk (g1/exp.rs:165-230) of the K instances of an explicit list, one at a time: the first one it cannot walk
-template <int E> int name_degenerate(const uint32_t* ios, size_t K, size_t base = 0) {
-  const size_t IOW = 32 * E + 8;
-  std::atomic<size_t> bad(K);
-  host_parallel_for(K, [&](size_t k) {
-    if (k > bad.load()) return;
-    std::vector<u64> ja(257 * 12 * E), jb(257 * 12 * E);
-    if (exp_chains<E>(ios + IOW * k, 0, ja.data(), jb.data())) { size_t cur = bad.load(); while (k < cur && !bad.compare_exchange_weak(cur, k)) {} }
-  });
-  if (bad.load() == K) return SBN_OK;
-  return fail(SBN_ERR_WITNESS, "instance %zu: degenerate affine operation in the table's walk (B[t] = +-2^t x at a set bit, or an output at infinity): pick another offset",
-              base + bad.load());
+// the first of K instances the table cannot walk, as the scalar-multiplication calls word it
+int degenerate_at(size_t k) {
+  return fail(SBN_ERR_WITNESS, "instance %zu: degenerate affine operation in the table's walk (B[t] = +-2^t x at a set bit, or an output at infinity): pick another offset", k);
 }
 
 template <int E>
 int instances(const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count, size_t num_io, const uint32_t* offset,
               uint32_t* ios_out, uint32_t* products_out, uint8_t* infinity_out) {
-  const size_t IOW = 32 * E + 8, total = sbn_msm_num_units(count, num_io) * num_io;
-  if (int rc = check_curve_points<E>(points, 16 * E, count, offset, "offset")) return rc;
+  const PiLayout t = curve_layout(E);
+  const size_t total = sbn_msm_num_units(count, num_io) * num_io;
+  if (int rc = check_curve_points<E>(points, t.xw, count, offset, "offset")) return rc;
   std::vector<uint32_t> own;
   uint32_t* ios = ios_out;
-  if (!ios) { own.resize(IOW * total); ios = own.data(); }
+  if (!ios) { own.resize(t.IOW() * total); ios = own.data(); }
   scalar_mul_explicit_list(E, points, scalars, scalar_count, count, total, offset, ios);
   if (products_out || infinity_out) {
     std::vector<Jac<E>> term(count);
-    host_parallel_for(count, [&](size_t k) { term[k] = scalar_mul_jac<E>(ld_point<E>(points + 16 * E * k), scalars + (scalar_count == 1 ? 0 : 8 * k)); });
+    host_parallel_for(count, [&](size_t k) { term[k] = scalar_mul_jac<E>(ld_point<E>(points + t.xw * k), scalars + (scalar_count == 1 ? 0 : t.ew * k)); });
     affine_or_infinity<E>(term, products_out, infinity_out);
   }
-  // the table's own walk of the real instances (the pads repeat the last one), 512 instances at a time to bound the chain storage
-  const size_t CH = 512;
-  std::vector<u64> chains(2 * 257 * 12 * E * (count < CH ? count : CH));
-  for (size_t at = 0; at < count; at += CH) {
-    const size_t k = count - at < CH ? count - at : CH, cw = 257 * 12 * E * k;
-    if (!tracegen_host_chains(E, ios + IOW * at, k, chains.data(), chains.data() + cw)) continue;
-    if (int rc = name_degenerate<E>(ios + IOW * at, k, at)) return rc;
-    return fail(SBN_ERR_WITNESS, "degenerate affine operation (x1 == x2 or y == 0)");
-  }
-  return SBN_OK;
+  const size_t bad = walk_curve_list<E>(ios, count);   // the real instances: the pads repeat the last one
+  if (bad == WALKS) return SBN_OK;
+  return bad == UNNAMED ? fail(SBN_ERR_WITNESS, UNNAMED_WALK_TEXT) : degenerate_at(bad);
 }
 
 template <int E>
 int check(size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, const uint32_t* points, const uint32_t* scalars,
           size_t scalar_count, const uint32_t* offset, uint32_t* products_out, uint8_t* infinity_out) {
-  const size_t W = 16 * E, per = 3 * W + 8, oX = 0, oOff = W, oExp = 2 * W, oOut = 2 * W + 8;
   if (units != sbn_msm_num_units(count, num_io))
     return fail(SBN_ERR_VERIFY_FAILED, "%zu units given, a list of %zu instances in tables of %zu has %zu units", units, count, num_io, sbn_msm_num_units(count, num_io));
-  for (size_t u = 0; u < units; u++) if (!public_inputs[u]) return fail(SBN_ERR_BAD_ARG, "null public inputs (unit %zu)", u);
-  auto inst = [&](size_t g) { return public_inputs[g / num_io] + per * (g % num_io); };
-  auto same = [](const uint64_t* p, const uint32_t* w, size_t n) { for (size_t i = 0; i < n; i++) if (p[i] != w[i]) return false; return true; };
-  const uint64_t* last = inst(count - 1);
+  const UnitInputs U(E == 1 ? SBN_AIR_G1_EXP : SBN_AIR_G2_EXP, num_io, public_inputs, units);
+  if (int rc = U.null_unit()) return rc;
+  const size_t W = U.L.xw;
   const Co<E> b = curve_b<E>();
   std::vector<uint32_t> outs(W * count);
-  for (size_t g = 0; g < units * num_io; g++) {
-    const uint64_t* p = inst(g);
-    if (g >= count) {   // a pad instance is instance count - 1 again
-      static const char* const field[4] = {"x", "offset", "exponent", "output"};
-      const size_t at[4] = {oX, oOff, oExp, oOut}, len[4] = {W, W, 8, W};
-      for (int f = 0; f < 4; f++)
-        if (memcmp(p + at[f], last + at[f], len[f] * sizeof(uint64_t)))
-          return fail(SBN_ERR_VERIFY_FAILED, "instance %zu (pad): %s differs from instance %zu", g, field[f], count - 1);
-      continue;
-    }
-    if (!same(p + oX, points + W * g, W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: x differs from the caller's point", g);
-    if (!same(p + oExp, scalars + (scalar_count == 1 ? 0 : 8 * g), 8)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: exponent differs from the caller's scalar", g);
-    if (!same(p + oOff, offset, W)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: offset differs from the offset of the call", g);
-    for (size_t i = 0; i < W; i++) {
-      if (p[oOut + i] > 0xffffffffULL) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output limb %zu is out of range", g, i);
-      outs[W * g + i] = (uint32_t)p[oOut + i];
-    }
-    const uint32_t* o = outs.data() + W * g;
+  for (size_t g = 0; g < U.rows(); g++) {
+    if (g >= count) { if (int rc = U.pad(g, count - 1)) return rc; continue; }
+    if (!U.value_is(g, U.oX, points + W * g)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: x differs from the caller's point", g);
+    if (!U.exp_is(g, scalars + (scalar_count == 1 ? 0 : U.L.ew * g))) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: exponent differs from the caller's scalar", g);
+    if (!U.value_is(g, U.oOff, offset)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: offset differs from the offset of the call", g);
+    uint32_t* o = outs.data() + W * g;
+    size_t limb;
+    if (!U.output(g, o, &limb)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output limb %zu is out of range", g, limb);
     if (!below_p(o, 2 * E)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output has a coordinate >= p", g);
     const Jac<E> q = ld_point<E>(o);
     if (!on_curve<E>(q.X, q.Y, b)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output is not a point of the curve", g);
@@ -111,7 +81,7 @@ int check(size_t num_io, const uint64_t* const* public_inputs, size_t units, siz
 
 // kind, then the arguments every entry point shares, in the order of the header's refusals
 int check_args(int32_t kind, const void* points, const void* scalars, size_t scalar_count, size_t count, size_t num_io) {
-  if (!curve_e((int)kind)) return fail(SBN_ERR_UNSUPPORTED, "scalar multiplications cover the curve tables G1_EXP and G2_EXP (a field table takes offset = 1 as it is)");
+  if (!pi_layout((int)kind).E) return fail(SBN_ERR_UNSUPPORTED, "scalar multiplications cover the curve tables G1_EXP and G2_EXP (a field table takes offset = 1 as it is)");
   if (!points || !scalars || count == 0 || num_io == 0) return fail(SBN_ERR_BAD_ARG, "null argument, no instance or num_io = 0");
   if (scalar_count != 1 && scalar_count != count) return fail(SBN_ERR_BAD_ARG, "scalar_count must be 1 (one shared scalar) or count = %zu, got %zu", count, scalar_count);
   return SBN_OK;
@@ -123,26 +93,32 @@ const uint32_t* curve_generator_words(int E) { return E == 1 ? G1_GEN : G2_GEN; 
 const uint32_t* g2_cofactor_words() { return G2_COFACTOR; }
 
 int scalar_mul_check_points(int E, const uint32_t* points, size_t count, const uint32_t* offset) {
-  return E == 1 ? check_curve_points<1>(points, 16, count, offset, "offset") : check_curve_points<2>(points, 32, count, offset, "offset");
+  const size_t W = curve_layout(E).xw;
+  return E == 1 ? check_curve_points<1>(points, W, count, offset, "offset") : check_curve_points<2>(points, W, count, offset, "offset");
 }
 
 void scalar_mul_explicit_list(int E, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count, size_t total,
                               const uint32_t* offset, uint32_t* ios) {
-  const size_t W = 16 * (size_t)E, IOW = 2 * W + 8;
-  for (size_t g = 0; g < total; g++) {
-    const size_t k = g < count ? g : count - 1;   // the reference's resize rule: a pad row is the last row again
-    memcpy(ios + IOW * g, points + W * k, W * sizeof(uint32_t));
+  const PiLayout t = curve_layout(E);
+  const size_t W = t.xw, IOW = t.IOW();
+  for (size_t g = 0; g < count; g++) {
+    memcpy(ios + IOW * g, points + W * g, W * sizeof(uint32_t));
     memcpy(ios + IOW * g + W, offset, W * sizeof(uint32_t));
-    memcpy(ios + IOW * g + 2 * W, scalars + (scalar_count == 1 ? 0 : 8 * k), 8 * sizeof(uint32_t));
+    memcpy(ios + IOW * g + 2 * W, scalars + (scalar_count == 1 ? 0 : t.ew * g), t.ew * sizeof(uint32_t));
   }
+  pad_rows(ios, IOW, count, total);
 }
 
-int scalar_mul_name_degenerate(int E, const uint32_t* ios, size_t K) { return E == 1 ? name_degenerate<1>(ios, K) : name_degenerate<2>(ios, K); }
+int scalar_mul_name_degenerate(int E, const uint32_t* ios, size_t K) {
+  const size_t bad = E == 1 ? first_unwalkable<1>(ios, K) : first_unwalkable<2>(ios, K);
+  return bad == K ? SBN_OK : degenerate_at(bad);
+}
 
 template <int E> static void unoffset(const uint32_t* outputs, const uint32_t* offset, size_t K, uint32_t* products, uint8_t* infinity) {
   const Jac<E> noff = neg_point<E>(ld_point<E>(offset));
+  const size_t W = curve_layout(E).xw;
   std::vector<Jac<E>> prod(K);
-  for (size_t k = 0; k < K; k++) prod[k] = jac_add_complete<E>(ld_point<E>(outputs + 16 * E * k), noff);
+  for (size_t k = 0; k < K; k++) prod[k] = jac_add_complete<E>(ld_point<E>(outputs + W * k), noff);
   affine_or_infinity<E>(prod, products, infinity);
 }
 void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* offset, size_t K, uint32_t* products, uint8_t* infinity) {
@@ -151,10 +127,10 @@ void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* of
 }  // namespace sbn
 
 extern "C" int sbn_curve_generator(int32_t kind, uint32_t* out) {
-  const int E = curve_e((int)kind);
+  const int E = pi_layout((int)kind).E;
   if (!E) return fail(SBN_ERR_UNSUPPORTED, "kind %d is not a curve table", (int)kind);
   if (!out) return fail(SBN_ERR_BAD_ARG, "null argument");
-  memcpy(out, curve_generator_words(E), 16 * E * sizeof(uint32_t));
+  memcpy(out, curve_generator_words(E), curve_layout(E).xw * sizeof(uint32_t));
   return SBN_OK;
 }
 
@@ -167,7 +143,7 @@ extern "C" int sbn_g2_cofactor(uint32_t out[8]) {
 extern "C" int sbn_scalar_mul_instances(int32_t kind, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count, size_t num_io,
                                         const uint32_t* offset, uint32_t* ios_out, uint32_t* products_out, uint8_t* infinity_out) {
   if (int rc = check_args(kind, points, scalars, scalar_count, count, num_io)) return rc;
-  const int E = curve_e((int)kind);
+  const int E = pi_layout((int)kind).E;
   if (!offset) offset = curve_generator_words(E);
   return E == 1 ? instances<1>(points, scalars, scalar_count, count, num_io, offset, ios_out, products_out, infinity_out)
                 : instances<2>(points, scalars, scalar_count, count, num_io, offset, ios_out, products_out, infinity_out);
@@ -177,7 +153,7 @@ extern "C" int sbn_scalar_mul_check(int32_t kind, size_t num_io, const uint64_t*
                                     const uint32_t* scalars, size_t scalar_count, const uint32_t* offset, uint32_t* products_out, uint8_t* infinity_out) {
   if (int rc = check_args(kind, points, scalars, scalar_count, count, num_io)) return rc;
   if (!public_inputs) return fail(SBN_ERR_BAD_ARG, "null argument");
-  const int E = curve_e((int)kind);
+  const int E = pi_layout((int)kind).E;
   if (!offset) offset = curve_generator_words(E);
   if (!below_p(offset, 2 * E)) return fail(SBN_ERR_BAD_ARG, "coordinate >= p (offset)");
   return E == 1 ? check<1>(num_io, public_inputs, units, count, points, scalars, scalar_count, offset, products_out, infinity_out)

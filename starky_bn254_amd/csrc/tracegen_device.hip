@@ -2,6 +2,7 @@
 // (sbn_bn254_fq_batch): the one unit that includes kernels_tracegen.cuh, whose kernels are ordinary external definitions.
 #include "prover_ctx.hpp"
 #include "kernels_tracegen.cuh"
+#include "instance_lists.hpp"
 #include <atomic>
 #include <cstring>
 
@@ -117,10 +118,7 @@ static dim3 blocks(size_t k, unsigned b) { return dim3((unsigned)((k + b - 1) / 
 // the first `values` Fq elements of every instance (eight u32 words each) are below p
 static int check_below_p(const uint32_t* ios, size_t IOW, int values, size_t K, const char* what) {
   for (size_t k = 0; k < K; k++)
-    for (int v = 0; v < values; v++) {
-      u64 t[4]; for (int i = 0; i < 4; i++) t[i] = (u64)ios[IOW * k + 8 * v + 2 * i] | ((u64)ios[IOW * k + 8 * v + 2 * i + 1] << 32);
-      if (bnw::geq_p(t)) return fail(SBN_ERR_BAD_ARG, "%s >= p (instance %zu)", what, k);
-    }
+    if (!curve_host::below_p(ios + IOW * k, values)) return fail(SBN_ERR_BAD_ARG, "%s >= p (instance %zu)", what, k);
   return 0;
 }
 
@@ -175,10 +173,8 @@ static std::vector<uint32_t> preliminary_list(const uint32_t* terms, const uint6
       if (head_of) (*head_of)[g] = seg_head[s];
     }
   }
-  for (; g < K; g++) {   // the reference's resize rule: a pad row is the last row again
-    memcpy(ios.data() + (2 * xw + ew) * g, ios.data() + (2 * xw + ew) * (M - 1), (2 * xw + ew) * sizeof(uint32_t));
-    if (head_of) (*head_of)[g] = (uint32_t)g;   // (never read: the scan's lanes stop at M)
-  }
+  curve_host::pad_rows(ios.data(), 2 * xw + ew, M, K);
+  for (; head_of && g < K; g++) (*head_of)[g] = (uint32_t)g;   // (never read: the scan's lanes stop at M)
   return ios;
 }
 static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, size_t xw, size_t ew, const uint32_t* offset) {
@@ -875,7 +871,7 @@ extern "C" int sbn_prover_generate_trace_powers(sbn_prover* P, const uint32_t* b
                                                 uint64_t* pi_out, uint32_t* powers_out, uint32_t* ios_out) {
   if (int rc = unload(P)) return rc;
   const int kind = P->air.kind;
-  if (!power_elem_words(kind)) return fail(SBN_ERR_UNSUPPORTED, "field powers cover the field tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64");
+  if (!pi_layout(kind).field()) return fail(SBN_ERR_UNSUPPORTED, "field powers cover the field tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64");
   if (!bases || !exps || count == 0 || depth == 0) return fail(SBN_ERR_BAD_ARG, "null argument, no tower or depth = 0");
   if (exp_count != 1 && exp_count != count) return fail(SBN_ERR_BAD_ARG, "exp_count must be 1 (one shared exponent) or count = %zu, got %zu", count, exp_count);
   const size_t num_io = P->air.num_io;
