@@ -249,8 +249,8 @@ int sbn_prover_prove_host_columns(sbn_prover* p, const uint64_t* const* columns,
  *     columns are compared as after sbn_prover_load_trace.
  *   main-row mode, n_cols = sbn_air_num_main_columns, the five Exp tables: the rows hold the main columns only, and the columns
  *     [num_main, num_columns) -- periodic pulse, io pulses, table column, range-check columns -- are written by the kernels of the
- *     device witness (host twin: by the code the host generators end with).  G1_EXP / G2_EXP / FQ_EXP on the device: 2^16 .. 2^18
- *     rows, as sbn_prover_generate_trace; beyond, sbn_trace_from_rows_host followed by sbn_prover_load_trace.  FQ12_EXP,
+ *     device witness (host twin: by the code the host generators end with).  G1_EXP / G2_EXP / FQ_EXP on the device: 2^16 .. 2^20
+ *     rows, as sbn_prover_generate_trace: every height these tables have (num_io <= 2,048).  FQ12_EXP,
  *     FQ12_EXP_U64: any size.
  * flags: 0 or SBN_TRACE_REDUCE, as for sbn_prover_prove_host_columns (words and public inputs >= p are taken mod p; *reduced_out,
  * optional, receives the number of trace words changed).
@@ -326,9 +326,9 @@ int sbn_fixed_columns_check(const sbn_air_desc* air, uint32_t degree_bits, const
  * ::generate_trace + generate_public_inputs (src/curves/g1/exp.rs:255-327, src/curves/g2/exp.rs:271-342,
  * src/fields/fq12/exp.rs:283-319) without the trace ever crossing PCIe.  Same `ios` layout and the same resulting trace /
  * public inputs, bit for bit, as sbn_generate_trace_{g1,g2,fq12}_exp; afterwards the prover is loaded and
- * sbn_prover_prove can run.  pi_out (optional): [num_public_inputs].  G1_EXP / G2_EXP / FQ_EXP: 2^16 .. 2^18 rows (the
- * reference pads to any power of two >= 128 instances, src/curves/g1/circuit.rs:273-277; SBN_ERR_UNSUPPORTED beyond: use
- * the host generators + sbn_prover_load_trace); FQ12_EXP, FQ12_EXP_U64: any size.  A call that fails, for whatever reason
+ * sbn_prover_prove can run.  pi_out (optional): [num_public_inputs].  G1_EXP / G2_EXP / FQ_EXP: 2^16 .. 2^20 rows, 128 .. 2,048 instances (the
+ * reference pads to any power of two >= 128 instances, src/curves/g1/circuit.rs:273-277; 2,048 is the largest num_io an Exp
+ * table is created with: at 4,096 the 4 num_io pulse columns alone are 275 GB of trace); FQ12_EXP, FQ12_EXP_U64: any size.  A call that fails, for whatever reason
  * (a coordinate >= p, a degenerate instance, a non-canonical exponent), leaves NO trace loaded: sbn_prover_prove then fails
  * with SBN_ERR_BAD_ARG until a trace is generated or loaded again. */
 int sbn_prover_generate_trace(sbn_prover* p, const uint32_t* ios, size_t num_io, uint64_t* pi_out);
@@ -539,7 +539,7 @@ int sbn_instances_from_public_inputs(int32_t kind, const uint64_t* public_inputs
  *   1. SBN_ERR_BAD_ARG: a null p or report, a wrong struct_size, cells_cap > 65536, cells_out NULL with a cap, num_io not the table's;
  *   2. SBN_ERR_BAD_ARG: no trace loaded;  3. SBN_ERR_UNSUPPORTED: a table that is no Exp table (no instance list in its public
  *   inputs);  4. SBN_ERR_UNSUPPORTED: the context of a split prover;  5. SBN_ERR_UNSUPPORTED: a height the device witness does not
- *   cover (G1 / G2 / FQ_EXP outside 2^16 .. 2^18 rows: use sbn_diff_witness_host);  6. what the generator says about the list (a value
+ *   cover (G1 / G2 / FQ_EXP below 2^16 rows: no such table);  6. what the generator says about the list (a value
  *   >= p, a non-canonical exponent, SBN_ERR_WITNESS), behind "no canonical witness: ".
  * SBN_OK = the diff ran; whether anything differs is in the report.  On EVERY path the loaded trace, its public inputs and the
  * loaded state come out as they went in -- also after a refused list: sbn_prover_prove gives the same words before and after. */
@@ -551,7 +551,7 @@ int sbn_prover_diff_witness(sbn_prover* p, const uint32_t* ios, size_t num_io, s
 int sbn_prover_diff_witness_times(const sbn_prover* p, float* ms_out, int cap);
 /* The host twin, no device looked for: the host generator runs on the host pool (SBN_HOST_THREADS) into a temporary of the trace's
  * size and the matrices are compared in tiles of 64 x 64.  The same report, arrays and list.  Any height the host generators take,
- * so also G1 / G2 / FQ_EXP above 2^18 rows.  Refusals as above without 2, 4 and 5; degree_bits or n_pi that do not match the table:
+ * as the device form.  Refusals as above without 2, 4 and 5; degree_bits or n_pi that do not match the table:
  * SBN_ERR_BAD_ARG. */
 int sbn_diff_witness_host(const sbn_air_desc* air, const uint64_t* trace_col_major, uint32_t degree_bits,
                           const uint64_t* public_inputs, size_t n_pi, const uint32_t* ios, size_t num_io,

@@ -23,7 +23,9 @@ static constexpr int SBN_NCH = 2;              // StarkConfig.num_challenges (st
 // alpha^k tables are sized per table at run time: one entry per constraint of the whole stream (AIR + permutation checks:
 // a constraint's weight is alpha^(number of constraints after it)), at least 1,025.
 GL_HD size_t apow_len(size_t nconstraints, size_t nzs) { size_t m = nconstraints + 2 * nzs; return (m > 1024 ? m : 1024) + 1; }
-static constexpr int G1EXP_MAX_IO = 512;        // largest num_io of any Exp table (Fq12ExpStark(512) = 2^18 rows)
+// largest num_io of any Exp table: 2,048 instances = 2^20 rows (1,024 and 2,048 on G1 / G2 / Fq; Fq12ExpStark(512) = 2^18 rows fills
+// the card already).  The io pulses are 4 num_io columns, so at 4,096 instances they alone are 2^14 x 2^21 words = 275 GB of trace.
+static constexpr int G1EXP_MAX_IO = 2048;
 
 // BN254 base-field modulus in 16-bit limbs (src/modular/modular.rs:298-309).
 GL_HD u64 bn254_modulus_limb(int j) {

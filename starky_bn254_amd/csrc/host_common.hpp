@@ -168,6 +168,11 @@ static inline bool config_supported(const sbn_config* c) {
 // The largest LDE a prover or a device verifier is created for: 2^23 points (2^22 rows at rate_bits 1, 2^20 at rate_bits 3).
 static constexpr u32 SBN_MAX_LDE_BITS = 23;
 static inline bool height_supported(const sbn_config* c, u32 degree_bits) { return degree_bits >= 9 && degree_bits + c->rate_bits <= SBN_MAX_LDE_BITS; }
+// Device witness generation of the u16-range-check tables (G1_EXP, G2_EXP, FQ_EXP): the table column 0..65535 needs 2^16 rows; above
+// that every height a context can be created for (the kernels are written for n <= 2^22, the largest trace any config admits).  The
+// one predicate of trace_gate, derived_columns_covered (tracegen_device.hip) and sbn_prover_diff_witness (witness_diff.hip).
+static inline bool u16_device_witness_covers(size_t n) { return n >= 65536 && n <= ((size_t)1 << (SBN_MAX_LDE_BITS - 1)); }
+static constexpr const char* U16_DEVICE_WITNESS_ROWS = "covers 2^16 .. 2^22 rows";
 static constexpr const char* HEIGHT_REFUSAL = "degree_bits out of range (9 <= degree_bits and degree_bits + rate_bits <= 23: the largest LDE is 2^23 points)";
 // sbn_config.fri_variant: 0 selects the default (the 0.1.x line: final polynomial times X)
 static inline u32 fri_times_x(const sbn_config& c) { return c.fri_variant == SBN_FRI_PLAIN ? 0u : 1u; }

@@ -670,14 +670,27 @@ __device__ unsigned long long g_rc_prof[16];
 #define RC_MARK(k) do { } while (0)
 #endif
 static constexpr int RC_THREADS = 1024;
-static constexpr int RC_HEAVY_MAX = 1024;  // values with more than 64 (BIG: 256) occurrences are expanded by the whole block
+// heavy[]: values with more than HEAVY occurrences are expanded by the whole block.  HEAVY = 64, 256 for BIG (n <= 2^18) and
+// n / RC_HEAVY_MAX for TALL.  INVARIANT: a column of n rows has at most floor(n / (HEAVY + 1)) values with more than HEAVY occurrences;
+// that is 1,008 at n = 2^16, 1,020 at n = 2^18 and, with HEAVY = n / 1,024, at most 1,023 at any n: the list cannot overflow whatever
+// the histogram is.  (A fixed cut of 256 would meet up to 2,040 such values at 2^19 rows.)
+static constexpr int RC_HEAVY_MAX = 1024;
 static constexpr size_t RC_LDS_BYTES = 65536 * 2 + 2 * 2048 * 4 + 64 * 4 + 64 * 4 + RC_HEAVY_MAX * 8;
+// TALL (n > 2^18): the values at which T crosses a multiple of 2^16 no longer fit misc[40..42] (7 crossings at 2^19 rows, 63 at 2^22):
+// thr[k - 1], k = 1..63, behind heavy[]; thr[63] stays 65536, the end mark of a walk along the thresholds
+static constexpr int RC_THR_MAX = 64;
+static constexpr size_t RC_TALL_LDS_BYTES = RC_LDS_BYTES + RC_THR_MAX * 4;
 
 // Tables with MORE than 2^16 rows (G1ExpStark(256) ... : the reference pads to any power of two >= 128 instances,
 // src/curves/g1/circuit.rs:273-277): multiplicities no longer fit the u16 LDS counters, so range_count_kernel builds
 // the histogram of every target column in HBM (u32, one atomic per row) and the BIG variant of range_check_kernel reads
 // it.  The prefix counts T[v] <= n stay in LDS as T mod 2^16 (u16) plus the <= 3 values at which T crosses a multiple
 // of 2^16 (T is monotone, so the high part is the number of those thresholds <= v).
+// Tables with more than 2^18 rows (G1ExpStark(1024) ...) take the TALL variant of the BIG form: up to 63 thresholds, sorted in LDS
+// (thr[k - 1] = the first value at which T >= k 2^16; several k may share one value when its count carries T over more than one
+// multiple), the high part of T(v) = 2^16 x the number of thresholds <= v: a binary search for a lone T(v), a cursor along the
+// thresholds where consecutive values are read; and the cut of heavy[] grows with n (RC_HEAVY_MAX above).  The forms of
+// 2^16 .. 2^18 rows are the instantiations <false> and <true> as before: everything TALL adds sits behind that compile-time constant.
 __global__ void range_count_kernel(const u64* __restrict__ trace, size_t n, int first_col, unsigned int* __restrict__ cnt, int* __restrict__ err) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -689,7 +702,7 @@ __global__ void range_count_kernel(const u64* __restrict__ trace, size_t n, int 
 // The table column is 0..65534 once each, then 65535 K = n - 65535 times (range_check.rs:20-47: min(i, 65535)); the merge
 // gives the first min(c, K) occurrences of 65535 their own table entry (Ordering::Equal), further occurrences run off
 // the table and are deferred, and table copies left over when the inputs end are appended to the pool (lookup.rs:100-101).
-template <bool BIG>
+template <bool BIG, bool TALL = false>
 __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) range_check_kernel(u64* __restrict__ trace, size_t n, int first_col, int start_lookups, int* __restrict__ err,
                                                                  const unsigned int* __restrict__ cnt, int old_form) {
   extern __shared__ unsigned int lds[];
@@ -700,17 +713,20 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
   int* L2 = SM1 + 2048;                                                     // min over 32 L1 entries
   unsigned int* misc = reinterpret_cast<unsigned int*>(L2 + 64);            // [0..15] wave sums, [32] differs, [33] vmax, [34] heavy count, [40..42] thresholds
   uint2* heavy = reinterpret_cast<uint2*>(misc + 64);                       // (value, start) of values with many occurrences
+  [[maybe_unused]] unsigned int* thr = reinterpret_cast<unsigned int*>(heavy + RC_HEAVY_MAX);   // TALL only (RC_TALL_LDS_BYTES)
+  static_assert(BIG || !TALL, "the tall form reads the HBM histogram");
   const int tid = threadIdx.x, kcol = blockIdx.x;
   const u64* col = trace + (size_t)(first_col + kcol) * n;
   u64* sorted_out = trace + (size_t)(start_lookups + 1 + 2 * kcol) * n;
   u64* perm_out = sorted_out + n;
   constexpr int INF = 0x3fffffff;
   const int N = (int)n, KT = N - 65535;             // rows; copies of 65535 in the table
-  constexpr int HEAVY = BIG ? 256 : 64;
+  const int HEAVY = TALL ? N / RC_HEAVY_MAX : (BIG ? 256 : 64);   // (a constant unless TALL)
 
   RC_MARK(0);
   for (int i = tid; i < 32768; i += RC_THREADS) t32[i] = 0;
   if (tid < 64) misc[tid] = tid >= 40 && tid < 44 ? 65536u : 0u;
+  if constexpr (TALL) { if (tid < RC_THR_MAX) thr[tid] = 65536u; }
   __syncthreads();
   RC_MARK(1);
   if constexpr (!BIG) {
@@ -772,15 +788,31 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
       run = hi;
       t32[32 * tid + j] = (lo & 0xffff) | (hi << 16);
       // thresholds: the first value at which T reaches k * 2^16 (k = 1..3)
-      for (unsigned k = (before >> 16) + 1; k <= (lo >> 16) && k < 4; k++) atomicMin(&misc[39 + k], (unsigned)(64 * tid + 2 * j));
-      for (unsigned k = (lo >> 16) + 1; k <= (hi >> 16) && k < 4; k++) atomicMin(&misc[39 + k], (unsigned)(64 * tid + 2 * j + 1));
+      if constexpr (!TALL) {
+        for (unsigned k = (before >> 16) + 1; k <= (lo >> 16) && k < 4; k++) atomicMin(&misc[39 + k], (unsigned)(64 * tid + 2 * j));
+        for (unsigned k = (lo >> 16) + 1; k <= (hi >> 16) && k < 4; k++) atomicMin(&misc[39 + k], (unsigned)(64 * tid + 2 * j + 1));
+      } else {   // k = 1..63: every k is reached at exactly one value, so one lane stores it (T = n = 64 x 2^16 only at vmax, where T is n by rule)
+        for (unsigned k = (before >> 16) + 1; k <= (lo >> 16) && k < RC_THR_MAX; k++) thr[k - 1] = (unsigned)(64 * tid + 2 * j);
+        for (unsigned k = (lo >> 16) + 1; k <= (hi >> 16) && k < RC_THR_MAX; k++) thr[k - 1] = (unsigned)(64 * tid + 2 * j + 1);
+      }
     }
   }
   __syncthreads();
   RC_MARK(3);
   const int vmax = (int)misc[33];
   const int thr1 = (int)misc[40], thr2 = (int)misc[41], thr3 = (int)misc[42];
-  auto Thi = [&](int v) __attribute__((always_inline)) -> int { return BIG ? ((v >= thr1) + (v >= thr2) + (v >= thr3)) << 16 : 0; };
+  auto Thi = [&](int v) __attribute__((always_inline)) -> int {
+    if constexpr (TALL) {   // the number of thresholds <= v: thr[0..62] ascend, never-reached ones are 65536 > v
+      int c = 0;
+      for (int s = RC_THR_MAX / 2; s; s >>= 1) if ((int)thr[c + s - 1] <= v) c += s;
+      return c << 16;
+    } else return BIG ? ((v >= thr1) + (v >= thr2) + (v >= thr3)) << 16 : 0;
+  };
+  // TALL, consecutive values: `hic` thresholds are <= the last value asked for, `nx` is the next one (thr[63] = 65536 ends the walk)
+  auto Thi_next = [&](int v, int& hic, int& nx) __attribute__((always_inline)) -> int {
+    while (nx <= v) { hic++; nx = (int)thr[hic]; }
+    return hic << 16;
+  };
   auto T = [&](int v) __attribute__((always_inline)) -> int { return v < 0 ? 0 : (v >= vmax ? N : (int)t16[v] + Thi(v)); };
   auto S = [&](int v) __attribute__((always_inline)) -> int { return v >= 65535 ? INF : v + 1 - T(v); };
   unsigned long long pool = 0;   // two-pass form: the unused table values of this lane's segment that nothing inside the segment took
@@ -803,10 +835,12 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int j = 0; j < 8; j++) { const uint4 q = p[j]; cw[4 * j] = q.x; cw[4 * j + 1] = q.y; cw[4 * j + 2] = q.z; cw[4 * j + 3] = q.w; }
     int tprev = T(tid * 64 - 1), m0 = INF, m1 = INF;
+    [[maybe_unused]] int hic = 0, nx = 0;
+    if constexpr (TALL) { hic = Thi(tid * 64 - 1) >> 16; nx = (int)thr[hic]; }
 #pragma unroll
     for (int j = 0; j < 64; j++) {
       const int v = tid * 64 + j;
-      const int tv = v >= vmax ? N : (int)((cw[j >> 1] >> (16 * (j & 1))) & 0xffff) + Thi(v);
+      const int tv = v >= vmax ? N : (int)((cw[j >> 1] >> (16 * (j & 1))) & 0xffff) + (TALL ? Thi_next(v, hic, nx) : Thi(v));
       if (v < 65535) {
         const int sv = v + 1 - tv;
         if (j < 32) m0 = sv < m0 ? sv : m0; else m1 = sv < m1 ? sv : m1;
@@ -842,12 +876,14 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
   // first x in [from, from | 31] with S(x) < target, or -1 (8 prefix counts per LDS read)
   auto scan32 = [&](int from, int target) __attribute__((always_inline)) -> int {
     const int hi = from | 31;
+    [[maybe_unused]] int hic = 0, nx = 0;
+    if constexpr (TALL) { hic = Thi((from & ~7) - 1) >> 16; nx = (int)thr[hic]; }
     for (int a = from & ~7; a <= hi; a += 8) {
       const uint4 q = *reinterpret_cast<const uint4*>(t16 + a);
       const unsigned w[4] = {q.x, q.y, q.z, q.w};
       for (int e = 0; e < 8; e++) {
         const int x = a + e;
-        const int tv = x >= vmax ? N : (int)((w[e >> 1] >> (16 * (e & 1))) & 0xffff) + Thi(x);
+        const int tv = x >= vmax ? N : (int)((w[e >> 1] >> (16 * (e & 1))) & 0xffff) + (TALL ? Thi_next(x, hic, nx) : Thi(x));
         const int sx = x >= 65535 ? INF : x + 1 - tv;
         if (x >= from && sx < target) return x;
       }
@@ -1022,7 +1058,10 @@ __global__ void chain_rebase_kernel(const uint32_t* __restrict__ ios, size_t K, 
   st_jac<E>(jb + jac_at<E>(k, t, 0), b);
 }
 
-static constexpr int CS_LANES = 512;   // >= K: the u16-range-check tables stop at 2^18 rows = 512 instances
+// Lanes of one scan workgroup.  Lists of K <= CS_LANES instances (tables up to 2^18 rows) are scanned by ONE workgroup
+// (chain_scan_kernel, chain_seg_scan_kernel); longer ones (K <= 8,192: 2^22 rows) in blocks of CS_LANES instances by the three
+// chain_block_* kernels behind chain_seg_scan_kernel, ordered by their kernel boundaries.
+static constexpr int CS_LANES = 512;
 template <int E>
 __global__ void __launch_bounds__(CS_LANES) chain_scan_kernel(uint32_t* ios, size_t K, const u64* __restrict__ terms, u64* s0, u64* s1, int* __restrict__ err) {
   const size_t IOW = 8 * (4 * E + 1);
@@ -1242,6 +1281,93 @@ __global__ void __launch_bounds__(CS_LANES) chain_seg_scan_kernel(uint32_t* ios,
     const size_t i = k + (size_t)j * NL;
     if (i >= K) continue;
     const Jac<E> p = ld_jac<E>(sum + 12 * E * (i < M ? i : M - 1));   // a pad row carries the offset of row M - 1
+    Co<E> v[2];
+    if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
+    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        u64 s[4]; from_m(v[c].c[q], s);
+        for (int w = 0; w < 8; w++) ios[IOW * i + 8 * ((2 + c) * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+      }
+  }
+}
+// ---- lists of more than CS_LANES instances: the same scan in blocks of CS_LANES, chained and segmented alike --------------------------
+// `head` is null for a chained list (one segment: every head is 0, M = K).  Three kernels; what one stores another reads only behind
+// the kernel boundary between them, and no workgroup waits for another one.
+//   chain_block_scan_kernel   grid = the blocks that hold a real instance: the Hillis-Steele scan of chain_seg_scan_kernel INSIDE
+//                             block b, the partner k - d taken only while k - d >= max(head[k], first lane of b).  Lane k ends with
+//                             the sum over [max(head[k], first lane of b), k] in `local` (the buffer of the last level, 9 levels
+//                             whatever M is: the barrier count is uniform).
+//   chain_block_carry_kernel  one lane, at most 15 dependent additions: in[b] = what the lanes of block b whose segment began in an
+//                             earlier block still lack = the sum from their head to the last lane of block b - 1.  Those lanes are a
+//                             prefix of the block and share one head (a later head closes the segment).  With t = the local sum of
+//                             block b - 1's last lane: in[b] = t when that lane's head lies inside block b - 1 (or b = 1), else
+//                             in[b - 1] + t.  A head ON the first lane of a block takes no carry (head >= first lane), a head on the
+//                             last lane of a block starts the carry anew: no sum ever crosses a segment head.
+//   chain_block_tail_kernel   the batched-inversion tail of chain_seg_scan_kernel as a grid: sum(i) = local[j] or in[block of j] +
+//                             local[j], j = min(i, M - 1) (the pads), kept in `sum` between the two passes of a lane (its own slots);
+//                             TG_ERR_INFINITY and the offset words as there.
+template <int E>
+__global__ void __launch_bounds__(CS_LANES) chain_block_scan_kernel(const uint32_t* __restrict__ ios, size_t M, const uint32_t* __restrict__ head,
+                                                                    const u64* __restrict__ terms, u64* s0, u64* s1) {
+  const size_t IOW = 8 * (4 * E + 1);
+  const size_t first = (size_t)blockIdx.x * CS_LANES, k = first + threadIdx.x;
+  Jac<E> cur = jac_infinity<E>();
+  size_t lo = first;   // the lowest partner of this lane
+  if (k < M) {
+    const size_t hd = head ? head[k] : 0;
+    lo = hd > first ? hd : first;
+    if (hd == k) {   // a head: the start of its segment, in the offset words of its preliminary row
+      u64 t4[4];
+      for (int q = 0; q < E; q++) { u32x8_to_u64x4(ios + IOW * k + 8 * (2 * E + q), t4); cur.X.c[q] = to_m(t4); u32x8_to_u64x4(ios + IOW * k + 8 * (3 * E + q), t4); cur.Y.c[q] = to_m(t4); }
+      cur.Z = cone<E>();
+    } else cur = ld_jac<E>(terms + 12 * E * (k - 1));   // (hd < k here, so k >= 1)
+  }
+  u64* buf[2] = {s0, s1};
+  int par = 0;
+  for (size_t d = 1; d < (size_t)CS_LANES; d <<= 1, par ^= 1) {
+    if (k < M) st_jac<E>(buf[par] + 12 * E * k, cur);
+    __syncthreads();                                    // the partner is in this workgroup: the barrier orders its global stores and loads
+    if (k < M && k >= lo + d) cur = jac_add_complete<E>(ld_jac<E>(buf[par] + 12 * E * (k - d)), cur);
+  }
+  if (k < M) st_jac<E>(buf[par] + 12 * E * k, cur);   // nine levels: par = 1, `local` is s1
+}
+template <int E>
+__global__ void chain_block_carry_kernel(size_t M, const uint32_t* __restrict__ head, const u64* __restrict__ local, u64* __restrict__ in) {
+  if (blockIdx.x || threadIdx.x) return;
+  Jac<E> run = jac_infinity<E>();
+  for (size_t b = 1; b * CS_LANES < M; b++) {
+    const size_t last = b * CS_LANES - 1;   // the last lane of block b - 1 (< M)
+    const Jac<E> t = ld_jac<E>(local + 12 * E * last);
+    const bool fresh = b == 1 || (head && head[last] >= (b - 1) * CS_LANES);
+    run = fresh ? t : jac_add_complete<E>(run, t);
+    st_jac<E>(in + 12 * E * b, run);
+  }
+}
+template <int E>
+__global__ void chain_block_tail_kernel(uint32_t* ios, size_t K, size_t M, const uint32_t* __restrict__ head, const u64* __restrict__ local,
+                                        const u64* __restrict__ in, u64* __restrict__ sum, int* __restrict__ err) {
+  const size_t IOW = 8 * (4 * E + 1);
+  const size_t L = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
+  if (L >= NL) return;
+  Fq nrm[TG_INV_BATCH];
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = L + (size_t)j * NL;
+    nrm[j] = fq_one();
+    if (i >= K) continue;
+    const size_t src = i < M ? i : M - 1, b = src / CS_LANES;   // a pad row carries the offset of row M - 1
+    Jac<E> p = ld_jac<E>(local + 12 * E * src);
+    if (b && (head ? head[src] : 0) < b * CS_LANES) p = jac_add_complete<E>(ld_jac<E>(in + 12 * E * b), p);
+    st_jac<E>(sum + 12 * E * i, p);
+    if (czero<E>(p.Z)) { atomicOr(err, TG_ERR_INFINITY); continue; }
+    nrm[j] = cnorm(p.Z);
+  }
+  batch_inverse(nrm);
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = L + (size_t)j * NL;
+    if (i >= K) continue;
+    const Jac<E> p = ld_jac<E>(sum + 12 * E * i);
     Co<E> v[2];
     if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
     else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }

@@ -939,7 +939,7 @@ int upload_alpha_tables(sbn_prover* P, const F alphas[SBN_NCH]) {
   }
   HIPC(hipMemcpyAsync(P->d_apow, apow.data(), apow.size() * sizeof(u64), hipMemcpyHostToDevice, st));
   if (is_exp_air(P->air.kind)) {
-    static thread_local ExpPiConsts<F> pic;  // 3 x 2 x 512 field elements
+    static thread_local ExpPiConsts<F> pic;  // 3 x 2 x G1EXP_MAX_IO field elements
     const F* app[SBN_NCH] = {ap[0].data(), ap[1].data()};
     std::vector<F> pif(P->pi.size());
     for (size_t i = 0; i < pif.size(); i++) pif[i] = F(P->pi[i]);

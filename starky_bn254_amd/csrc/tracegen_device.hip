@@ -15,6 +15,7 @@ static int range_check_setup(int device) {
   if (!done[d].load()) {
     HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_LDS_BYTES));
     HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_LDS_BYTES));
+    HIPC(hipFuncSetAttribute((const void*)tg::range_check_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg::RC_TALL_LDS_BYTES));
     done[d].store(true);
   }
   return 0;
@@ -233,7 +234,10 @@ struct TraceJob : LdeScratch {   // (the scratch carver: prover_ctx.hpp; the LDE
     if (n > 65536) {   // multiplicities beyond u16: histogram of every target column in HBM first (kernels_tracegen.cuh)
       HIPC(hipMemsetAsync(d_cnt, 0, (size_t)sh.num_rc * 65536 * sizeof(unsigned int), st));
       hipLaunchKernelGGL(tg::range_count_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)sh.num_rc), dim3(256), 0, st, P->d_trace, n, sh.rc_start, d_cnt, d_err);
-      hipLaunchKernelGGL(tg::range_check_kernel<true>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
+      if (n > 262144)   // more crossings of 2^16 than the BIG form keeps, a cut of heavy[] that grows with n (kernels_tracegen.cuh)
+        hipLaunchKernelGGL((tg::range_check_kernel<true, true>), dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_TALL_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
+      else
+        hipLaunchKernelGGL(tg::range_check_kernel<true>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, d_cnt, P->set.range_check);
     } else {
       hipLaunchKernelGGL(tg::range_check_kernel<false>, dim3((unsigned)sh.num_rc), dim3(tg::RC_THREADS), tg::RC_LDS_BYTES, st, P->d_trace, n, sh.rc_start, sh.start_lookups, d_err, (const unsigned int*)nullptr, P->set.range_check);
     }
@@ -281,7 +285,7 @@ struct CurveJob : TraceJob {
   uint32_t *d_ios, *d_prog[2];   // (chain programs: <= 64 levels of 64 micro-operations)
   int* d_err;
   unsigned int* d_cnt;
-  u64 *pre, *terms, *scan[2];  int* err_pre;                        // carve_scan()
+  u64 *pre, *terms, *scan[2], *carry;  int* err_pre;                // carve_scan()
   size_t np = 0;  u64* jp;  uint32_t* prod;  unsigned char* inf;    // carve_products()
   u64* h_out = nullptr;                                             // ready()
   CurveJob(sbn_prover* P, size_t K) : TraceJob(P, K, 8 * (4 * E + 1)) {   // u32 words per instance: x and offset (2E Fq each) + exp_val
@@ -294,8 +298,12 @@ struct CurveJob : TraceJob {
     d_err = (int*)take(1);
     d_cnt = take_histograms();
   }
-  // chain offsets: the partial sums of every instance, e_k x_k, the two scan buffers, the flags of the preliminary chains (never read)
-  void carve_scan() { pre = take(12 * E * tg::CT_LANES * K); terms = take(12 * E * K); scan[0] = take(12 * E * K); scan[1] = take(12 * E * K); err_pre = (int*)take(1); }
+  // chain offsets: the partial sums of every instance, e_k x_k, the two scan buffers, the flags of the preliminary chains (never read),
+  // one carry per block of a list of more than CS_LANES instances
+  void carve_scan() {
+    pre = take(12 * E * tg::CT_LANES * K); terms = take(12 * E * K); scan[0] = take(12 * E * K); scan[1] = take(12 * E * K); err_pre = (int*)take(1);
+    carry = take(12 * E * (K / tg::CS_LANES + 1));
+  }
   // un-offset of `count` outputs: the Jacobian products between the two passes of a lane, the affine products ([count][16E] u32), their infinity flags
   void carve_products(size_t count) { np = count; jp = take(12 * E * np); prod = (uint32_t*)take(8 * E * np); inf = (unsigned char*)take(np / 8 + 1); }
   // after the last take().  Pinned staging as the driver lays it out: `in_words` u64 words go up, the outputs + error word land
@@ -347,7 +355,12 @@ struct CurveJob : TraceJob {
   int chain_scan(size_t M = 0, const uint32_t* d_head_of = nullptr) {
     if (int rc = launch_chains(err_pre)) return rc;
     hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, pre, terms);
-    if (d_head_of) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, M, d_head_of, terms, scan[0], scan[1], d_err);
+    if (K > (size_t)tg::CS_LANES) {   // in blocks of CS_LANES instances: three kernels, ordered by their boundaries
+      const size_t real = d_head_of ? M : K;
+      hipLaunchKernelGGL(tg::chain_block_scan_kernel<E>, blocks(real, tg::CS_LANES), dim3(tg::CS_LANES), 0, st, d_ios, real, d_head_of, terms, scan[0], scan[1]);
+      hipLaunchKernelGGL(tg::chain_block_carry_kernel<E>, dim3(1), dim3(64), 0, st, real, d_head_of, scan[1], carry);
+      hipLaunchKernelGGL(tg::chain_block_tail_kernel<E>, blocks((K + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, K, real, d_head_of, scan[1], carry, scan[0], d_err);
+    } else if (d_head_of) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, M, d_head_of, terms, scan[0], scan[1], d_err);
     else hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, terms, scan[0], scan[1], d_err);
     mark("chain_offsets");
     return 0;
@@ -416,7 +429,6 @@ static int curve_trace_explicit(sbn_prover* P, const uint32_t* ios, size_t K, ui
 // outputs.  Only chain_mode 1 and 2 come here, as to the two drivers below.
 template <int E>
 static int curve_trace_chained(sbn_prover* P, const ChainedIn& ch, size_t K, uint64_t* pi_out) {
-  if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a chained list has at most %d instances", tg::CS_LANES);
   if (int rc = chain_terms_check_curve(E, ch.terms, K, ch.start)) return rc;
   const std::vector<uint32_t> prelim = preliminary_list(ch, K, 16 * E, 8, ch.start);
   HIPC(hipSetDevice(P->device));
@@ -476,7 +488,6 @@ static int curve_trace_scalar_muls(sbn_prover* P, const ScalarMulIn& sm, size_t 
 // their flags behind the list
 template <int E>
 static int curve_trace_segmented(sbn_prover* P, const BatchIn& mb, size_t K, uint64_t* pi_out) {
-  if (K > (size_t)tg::CS_LANES) return fail(SBN_ERR_UNSUPPORTED, "a segmented list has at most %d instances", tg::CS_LANES);
   if (int rc = msm_batch_check_inputs(P->air.kind, mb.terms, mb.lengths, mb.segments, mb.starts, mb.start_count, mb.M)) return rc;
   const size_t S = mb.segments;
   std::vector<uint32_t> aux, seg_head, seg_len;
@@ -749,7 +760,7 @@ static int trace_gate(sbn_prover* P, size_t num_io, bool* device_chains) {
   if (!is_exp_air(kind)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation covers the Exp tables (use sbn_generate_trace_g1_op + sbn_prover_load_trace)");
   if (num_io != P->air.num_io) return fail(SBN_ERR_BAD_ARG, "prover was created for %u instances, got %zu", P->air.num_io, num_io);
   if (P->n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
-  if (!is_fq12(kind) && (P->n < 65536 || P->n > 262144)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables covers 2^16 .. 2^18 rows");
+  if (!is_fq12(kind) && !u16_device_witness_covers(P->n)) return fail(SBN_ERR_UNSUPPORTED, "device witness generation of the u16-range-check tables %s", U16_DEVICE_WITNESS_ROWS);
   *device_chains = kind != SBN_AIR_FQ_EXP && (is_fq12(kind) ? !P->set.fq12_host_chain : P->chain_mode != 0);
   return 0;
 }
@@ -765,11 +776,12 @@ static int trace_from_host_list(sbn_prover* P, size_t num_io, uint64_t* pi_out, 
 
 // ---- the derived columns of a row-major load (trace_load.hip; include/sbn.h sbn_prover_load_trace_rows, main-row mode) --------------
 // The main columns [0, num_main) are resident; everything behind them is a function of those and of the shape, written by the
-// kernels the generators above end with.  The same gate as trace_gate: the u16 tables at 2^16 .. 2^18 rows, the Fq12 kinds at any.
+// kernels the generators above end with.  The same gate as trace_gate (u16_device_witness_covers, host_common.hpp): the u16 tables
+// from 2^16 rows up, the Fq12 kinds at any height.
 int derived_columns_covered(const AirShape& as, size_t n) {
   if (!is_exp_air(as.kind)) return fail(SBN_ERR_UNSUPPORTED, "main-row mode covers the five Exp tables (hand in whole rows)");
-  if (!is_fq12(as.kind) && (n < 65536 || n > 262144))
-    return fail(SBN_ERR_UNSUPPORTED, "main-row mode of the u16-range-check tables covers 2^16 .. 2^18 rows on the device (use sbn_trace_from_rows_host + sbn_prover_load_trace)");
+  if (!is_fq12(as.kind) && !u16_device_witness_covers(n))
+    return fail(SBN_ERR_UNSUPPORTED, "main-row mode of the u16-range-check tables %s on the device (use sbn_trace_from_rows_host + sbn_prover_load_trace)", U16_DEVICE_WITNESS_ROWS);
   return 0;
 }
 int launch_derived_columns(sbn_prover* P) {

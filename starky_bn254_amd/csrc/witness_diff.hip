@@ -163,8 +163,8 @@ extern "C" int sbn_prover_diff_witness(sbn_prover* P, const uint32_t* ios, size_
   if (int rc = diag_refuse_split(P, "the witness diff", true)) return rc;
   const size_t n = P->n, C = P->air.ncols, num_main = (size_t)exp_shape(P->air).num_main;
   const bool fq12 = kind == SBN_AIR_FQ12_EXP || kind == SBN_AIR_FQ12_EXP_U64;
-  if (!fq12 && (n < 65536 || n > 262144))
-    return fail(SBN_ERR_UNSUPPORTED, "the device witness of the u16-range-check tables covers 2^16 .. 2^18 rows, this context has %zu (sbn_diff_witness_host takes any height)", n);
+  if (!fq12 && !u16_device_witness_covers(n))
+    return fail(SBN_ERR_UNSUPPORTED, "the device witness of the u16-range-check tables %s, this context has %zu (sbn_diff_witness_host takes any height)", U16_DEVICE_WITNESS_ROWS, n);
   if (n != exp_rows_per_instance(kind) * num_io) return fail(SBN_ERR_BAD_ARG, "degree_bits does not match the rows per instance");
   if (P->pi.size() != P->air.npi) return fail(SBN_ERR_BAD_ARG, "the loaded trace carries %zu public inputs, the table has %zu", P->pi.size(), P->air.npi);
   float* const times = P->diag_ms[DIAG_WITDIFF];
