@@ -49,6 +49,25 @@ def header(words):
     return tuple(int(x) for x in words[1:12])
 
 
+def check_header(words, degree_bits, row):
+    """The proof's header carries the row: cap height, arity, query rounds, and the FRI shape fri_shape() derives from it."""
+    h = header(words)
+    assert (h[0], h[5], h[8], h[10]) == (degree_bits, row[0], row[2], row[4]) and (h[7], h[9]) == fri_shape(degree_bits, row), (h, row)
+
+
+def difference(got, want, permute):
+    """None where the two proofs are equal word for word; else a sentence that names the first differing word and, through the
+    parity kit, the first stage that differs (permute: the oracle's Poseidon permutation)."""
+    if np.array_equal(got, want):
+        return None
+    import parity_kit as K
+    k = min(len(want), len(got))
+    diff = np.nonzero(np.asarray(got[:k]) != np.asarray(want[:k]))[0]
+    stage = K.first_difference(K.stage_digests(got, permute), K.stage_digests(want, permute)) if len(got) == len(want) else None
+    return (f"{len(got)} / {len(want)} words, first differing word {int(diff[0]) if diff.size else k}, sections at {section_words(want)}, "
+            f"first differing stage {stage}")
+
+
 def section_words(words):
     """One word index inside each section of a proof (layout: include/sbn.h): a cap, an opening, the final polynomial and -- where
     the proof has FRI layers -- the first evaluation of the first query's first FRI step."""

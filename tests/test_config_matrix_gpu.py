@@ -51,15 +51,11 @@ def check_against_oracle(gpu, O, stark, kind, num_io, trace, pi, case, prover=No
     t0 = time.time()
     want, _ = O.prove(kind, num_io, trace, pi, config=row + (times_x,))
     oracle_s = time.time() - t0
-    h = M.header(p1.words)
-    assert (h[0], h[5], h[8], h[10]) == (bits, row[0], row[2], row[4]) and (h[7], h[9]) == M.fri_shape(bits, row)
-    if not np.array_equal(p1.words, want):   # name the first word and, through the parity kit, the first stage that differs
-        import parity_kit as K
-        k = min(len(want), len(p1.words))
-        diff = np.nonzero(p1.words[:k] != want[:k])[0]
-        stage = K.first_difference(K.stage_digests(p1.words, O.poseidon_permute), K.stage_digests(want, O.poseidon_permute)) if len(p1.words) == len(want) else None
-        pytest.fail(f"{M.case_id(case)}: device proof differs from the oracle's: {len(p1.words)} / {len(want)} words, first differing word "
-                    f"{int(diff[0]) if diff.size else k}, sections at {M.section_words(want)}, first differing stage {stage}")
+    M.check_header(p1.words, bits, row)
+    what = M.difference(p1.words, want, O.poseidon_permute)   # names the first word and the first stage that differs
+    if what is not None:
+        pytest.fail(f"{M.case_id(case)}: device proof differs from the oracle's: {what}")
+    assert np.array_equal(p1.words, want)
     assert np.array_equal(p1.words, p2.words)
     assert O.verify(kind, num_io, p1.words, config=row + (times_x,)) == (0, "")
     gpu.verify_stark_proof(stark, p1, cfg)
