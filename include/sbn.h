@@ -791,6 +791,70 @@ int sbn_msm_batch_check(int32_t kind, size_t num_io, const uint64_t* const* publ
                         const uint32_t* terms /*optional*/, const uint32_t* starts, size_t start_count, uint32_t* finals_out, uint32_t* sums_out,
                         uint8_t* infinity_out);
 
+/* Complete sums ---------------------------------------------------------------------------------------- */
+/* Batches of short MSMs on G1_EXP / G2_EXP in which the LIBRARY picks the start of every segment, so that no valid curve input is
+ * refused and the caller gets the sums e_k x_k back.  The Exp tables add with incomplete affine formulas: a list is refused when
+ * an addition of the table's walk meets B[t] = +-2^t x, or when an offset or a final is the point at infinity, and "the remedy is
+ * another start" (above).  With the generator as the default start the everyday inputs fail: m G + r H with odd m, sk G, a list that
+ * holds -G.  Here the starts come from a fixed table of SBN_START_CANDIDATES points of the table's curve with no chosen relation to
+ * the generator (sbn_start_candidate).  G1: x = 2, 3, 4, ... in ascending order, kept where x^3 + 3 is a non-zero square mod p, y the
+ * smaller root as an integer, the first eight.  Twist: x = k + i (c0 = k, c1 = 1), k = 0, 1, 2, ..., kept where x^3 + 3 / (9 + i) is a
+ * non-zero square in Fq2, y the root whose (c1, c0) integer pair is lexicographically smaller, the first eight; these need not lie in
+ * the order-r subgroup (an offset need not).  One definition for every entry point below; kind, terms, lengths, T, W and the units
+ * are as in "Batches of short MSMs":
+ *   term_infinity  [M] bytes or NULL: a term with term_infinity[g] != 0 is the point at infinity, the identity of an aggregation.
+ *                  Its words in `terms` are NOT read or validated; the effective term is (generator, exponent 0), an instance whose
+ *                  walk has no addition and whose product is the identity;
+ *   terms_out      [M][T] u32: the effective terms;
+ *   starts_out     [segments][W] u32 and choice_out [segments] bytes: the start of segment s is candidate choice[s], the SMALLEST
+ *                  j < SBN_START_CANDIDATES for which the segment, started from candidate j, has no bad event: an offset or a final
+ *                  at infinity, or an addition of the table's walk with B = +-A.  With S_{g-1} the sum of the segment's terms
+ *                  before instance g, the bad starts are (+-2^t - k) x_g - S_{g-1} over the set bits t of e_g (k = the value of the
+ *                  bits below t) and -S_g: they depend on the segment's own terms only, so the choice of a segment is a pure
+ *                  function of its terms and no segment moves another.
+ * On success ios_out, finals_out, sums_out and infinity_out are, word for word, what sbn_msm_batch_instances(kind, terms_out,
+ * lengths, segments, starts_out, segments, num_io, ...) returns, and that call succeeds (pads copy row M - 1, offset included); so
+ * sbn_msm_batch_check(..., terms = terms_out, starts = starts_out, start_count = segments) checks the unit proofs unchanged.  A
+ * segment whose sum is the point at infinity is not an error (an all-masked segment is one: flag 1, sum words zero, final = start).
+ * Every output pointer is optional.
+ * Refused, in this order: SBN_ERR_UNSUPPORTED for a kind that is no Exp table, and for the three field tables (their offset one is
+ * always legal, nothing there is incomplete); the SBN_ERR_BAD_ARG refusals of sbn_msm_batch_instances for the arguments (null terms
+ * or lengths, segments = 0, a zero length, num_io = 0) and for the values of the terms that are not masked (a coordinate >= p, an x
+ * off the table's curve), with the same wording, naming the instance and its segment; SBN_ERR_WITNESS when all eight candidates fail
+ * for some segment, naming the smallest such segment, the count of such segments and the instance at which candidate 7 failed.
+ * Eight independent points must each hit a bad set of a few hundred points per instance among about 2^254: honest inputs cannot exhaust
+ * the table; inputs crafted from the published candidates can, and their remedy is sbn_msm_batch_instances with starts of the
+ * caller's own. */
+#define SBN_START_CANDIDATES 8
+int sbn_start_candidate(int32_t kind, uint32_t j, uint32_t* out /* [16E] */);   /* refusals as sbn_curve_generator; j >= 8: SBN_ERR_BAD_ARG */
+/* The derivation on the host pool, no device: the terms and their prefix sums once; candidate 0 on every segment, ALL failing
+ * segments collected in one pass (a per-instance status of the table's walk), only those re-derived with the next candidate.
+ * num_io is not checked against any table. */
+int sbn_msm_batch_instances_complete(int32_t kind, const uint32_t* terms, const uint8_t* term_infinity /* [M] or NULL */, const uint64_t* lengths,
+                                     size_t segments, size_t num_io, uint32_t* ios_out, uint32_t* terms_out /* [M][T] */,
+                                     uint32_t* starts_out /* [segments][W] */, uint8_t* choice_out /* [segments] */, uint32_t* finals_out,
+                                     uint32_t* sums_out, uint8_t* infinity_out);
+/* One unit on a prover of the table, M <= num_io: on success the loaded trace, the public inputs and ios_out are those of
+ * sbn_prover_generate_trace on the list above; a failing call leaves NO trace loaded.  Where the table's chains run on the device
+ * (SBN_TRACEGEN_DEVICE_CHAIN = 1 or 2) the derivation runs there too, on the segmented path of sbn_prover_generate_trace_msm_batch:
+ * the start of segment s is candidate choice[s] (an index per segment goes up, not start words), every choice 0 at first; behind
+ * the scan and the rebase of the B chains a kernel writes a status word per segment that has a bad event, the host reads the
+ * status words back, moves the failing segments to their next candidate and launches start, scan, rebase and status again -- at
+ * most eight rounds, and a second one only when a segment failed.  The terms e_k x_k, their partial sums and the A chains enter no
+ * start and are computed once.  With every choice 0 the call is the explicit call plus the status kernel and one readback.  The
+ * kernels of the explicit-start calls are unchanged (they keep their single error word).  Placement 0 derives on the host pool
+ * and takes the explicit path, and a list that exhausts the candidates is worded by the host derivation.  The words are the same
+ * in every placement. */
+int sbn_prover_generate_trace_msm_batch_complete(sbn_prover* p, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths,
+                                                 size_t segments, uint64_t* pi_out, uint32_t* terms_out, uint32_t* starts_out, uint8_t* choice_out,
+                                                 uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, uint32_t* ios_out);
+/* Any M, as units of the batch prover's table: the list is derived once on the host pool, then the units go through the unit loop
+ * of sbn_batch_prover_prove_ios.  Failure rule as sbn_batch_prover_prove_msm_batch; guards apply as to every sbn_batch_prover_prove_*
+ * call. */
+int sbn_batch_prover_prove_msm_batch_complete(sbn_batch_prover* b, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths,
+                                              size_t segments, sbn_proof** proofs_out, uint32_t* terms_out, uint32_t* starts_out, uint8_t* choice_out,
+                                              uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, uint32_t* ios_out);
+
 /* Field powers --------------------------------------------------------------------------------------- */
 /* Powers and POWER TOWERS on the three field Exp tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64: the caller wants x^e itself.  A field
  * table needs no offset trick (its offset is multiplicative: every instance here carries offset = 1, word 0 = 1 and the rest 0), but

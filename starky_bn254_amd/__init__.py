@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     prove, prove_cache_configure, prove_cache_stats, first_non_canonical, verify_stark_proof, commit_values, eval_constraints_host, poseidon_permute_batch, poseidon_permute_coop_batch, poseidon_permute_host, field_mul_batch, bn254_fq_batch, chain_instances, msm_num_units, msm_instances, msm_check_links, verify_msm, lib, lib_path, EXPORTS,
     G2_COFACTOR, generator, scalar_mul_instances, scalar_mul_check, mul_by_cofactor_check, verify_scalar_muls, verify_mul_by_cofactor,
     msm_batch_instances, msm_batch_check, verify_msms,
+    START_CANDIDATES, start_candidate, msm_batch_instances_complete,
     BN_P, BN_X, FQ_INVERSE_EXP, FQ_LEGENDRE_EXP, FQ_SQRT_EXP, bn_x, power_instances, power_check, verify_powers, verify_bn_x_powers, fq_sqrt_flags,
     prover_memory_plan, lde_rows, LDE_STORAGE,
     TRACE_REDUCE, ColumnTable, prove_columns, gather_columns, reduce_words,

@@ -45,6 +45,7 @@ EXPORTS = [
     "sbn_curve_generator", "sbn_g2_cofactor", "sbn_scalar_mul_instances", "sbn_prover_generate_trace_scalar_muls",
     "sbn_batch_prover_prove_scalar_muls", "sbn_scalar_mul_check", "sbn_batch_prover_prove_mul_by_cofactor", "sbn_mul_by_cofactor_check",
     "sbn_msm_batch_instances", "sbn_prover_generate_trace_msm_batch", "sbn_batch_prover_prove_msm_batch", "sbn_msm_batch_check",
+    "sbn_start_candidate", "sbn_msm_batch_instances_complete", "sbn_prover_generate_trace_msm_batch_complete", "sbn_batch_prover_prove_msm_batch_complete",
     "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_coop_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
@@ -243,6 +244,10 @@ def lib():
         L.sbn_prover_generate_trace_msm_batch.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp]
         L.sbn_batch_prover_prove_msm_batch.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(vp), vp, vp, vp, vp]
         L.sbn_msm_batch_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, vp, sz, vp, vp, sz, vp, vp, vp]
+        L.sbn_start_candidate.argtypes = [C.c_int32, C.c_uint32, vp]
+        L.sbn_msm_batch_instances_complete.argtypes = [C.c_int32, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.sbn_prover_generate_trace_msm_batch_complete.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sbn_batch_prover_prove_msm_batch_complete.argtypes = [vp, vp, vp, vp, sz, C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp]
         L.sbn_bn_x.argtypes = [vp]
         L.sbn_power_instances.argtypes = [C.c_int32, vp, vp, sz, sz, sz, sz, vp, vp]
         L.sbn_prover_generate_trace_powers.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
@@ -847,6 +852,55 @@ def msm_batch_check(stark, public_inputs_per_unit, lengths, starts=None, terms=N
     _check(lib().sbn_msm_batch_check(stark.kind, stark.num_io, ptrs, n, _ptr(lengths), len(lengths), _ptr(terms), _ptr(starts),
                                      starts.shape[0] if starts is not None else 1, _ptr(finals), _ptr(sums), _ptr(infinity)))
     return finals, sums, infinity
+
+
+# ---- complete sums: the library picks the start of every segment (include/sbn.h, "Complete sums") ------------------------------
+START_CANDIDATES = 8   # SBN_START_CANDIDATES
+
+
+def start_candidate(stark, j):
+    """Start candidate j < START_CANDIDATES of the curve table `stark` (sbn_start_candidate): a fixed point of the table's curve
+    with no chosen relation to the generator, as the x words of an `ios` row."""
+    if not 0 <= int(j) < 2 ** 32:
+        raise SbnError(-1, f"start candidate {j}: there are {START_CANDIDATES}")
+    out = np.zeros(_curve_words(stark), dtype=np.uint32)
+    _check(lib().sbn_start_candidate(stark.kind, int(j), _ptr(out)))
+    return out
+
+
+def _complete_args(stark, terms, lengths, term_infinity):
+    """terms, lengths as msm_batch_instances takes them; term_infinity (M,) bytes or None: a non-zero entry makes that term the
+    point at infinity (its words are not read).  Returns (terms, lengths, term_infinity, xw, ew)."""
+    if stark.kind not in (AIR_G1_EXP, AIR_G2_EXP):
+        raise SbnError(-7, "complete sums cover the curve tables G1ExpStark and G2ExpStark")
+    terms, lengths, _, xw, ew, _ = _msm_batch_args(stark, terms, lengths, None)
+    if term_infinity is not None:
+        term_infinity = np.ascontiguousarray(term_infinity, dtype=np.uint8).reshape(-1)
+        if term_infinity.shape[0] != terms.shape[0]:
+            raise SbnError(-1, f"term_infinity must hold one byte per term ({terms.shape[0]})")
+    return terms, lengths, term_infinity, xw, ew
+
+
+def _complete_outputs(M, segments, xw, ew):
+    """(terms_eff, starts, choice, finals, sums, infinity)"""
+    return (np.zeros((M, xw + ew), dtype=np.uint32), np.zeros((segments, xw), dtype=np.uint32), np.zeros(segments, dtype=np.uint8),
+            np.zeros((segments, xw), dtype=np.uint32), np.zeros((segments, xw), dtype=np.uint32), np.zeros(segments, dtype=np.uint8))
+
+
+def msm_batch_instances_complete(stark, terms, lengths, term_infinity=None):
+    """msm_batch_instances on the two curve tables with the start of every segment picked by the library, so that no valid input
+    is refused (sbn_msm_batch_instances_complete).  Returns (ios, terms_eff, starts, choice, finals, sums, infinity): terms_eff are
+    the terms with (generator, exponent 0) for the masked ones, starts[s] = start_candidate(stark, choice[s]), and the rest is what
+    msm_batch_instances(stark, terms_eff, lengths, starts) returns.  No device needed."""
+    terms, lengths, term_infinity, xw, ew = _complete_args(stark, terms, lengths, term_infinity)
+    if stark.num_io < 1:
+        raise SbnError(-1, "the table has no instances")
+    units = msm_num_units(terms.shape[0], stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * xw + ew), dtype=np.uint32)
+    eff, starts, choice, finals, sums, infinity = _complete_outputs(terms.shape[0], len(lengths), xw, ew)
+    _check(lib().sbn_msm_batch_instances_complete(stark.kind, _ptr(terms), _ptr(term_infinity), _ptr(lengths), len(lengths), stark.num_io, _ptr(ios),
+                                                  _ptr(eff), _ptr(starts), _ptr(choice), _ptr(finals), _ptr(sums), _ptr(infinity)))
+    return ios, eff, starts, choice, finals, sums, infinity
 
 
 # ---- field powers and power towers (include/sbn.h, "Field powers") -------------------------------------------------------------
@@ -1667,6 +1721,18 @@ class Prover:
                                                          _ptr(ios)))
         return pi, finals, sums, infinity, ios
 
+    def generate_trace_msms_complete(self, terms, lengths, term_infinity=None):
+        """generate_trace on the one-unit list msm_batch_instances_complete(stark, terms, lengths, term_infinity) gives (M <=
+        num_io, the rest padded); returns (public inputs, terms_eff, starts, choice, finals, sums, infinity, ios).  A failing call
+        leaves no trace loaded."""
+        terms, lengths, term_infinity, xw, ew = _complete_args(self.stark, terms, lengths, term_infinity)
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        ios = np.zeros((self.stark.num_io, 2 * xw + ew), dtype=np.uint32)
+        eff, starts, choice, finals, sums, infinity = _complete_outputs(terms.shape[0], len(lengths), xw, ew)
+        _check(lib().sbn_prover_generate_trace_msm_batch_complete(self._h, _ptr(terms), _ptr(term_infinity), _ptr(lengths), len(lengths), _ptr(pi), _ptr(eff),
+                                                                  _ptr(starts), _ptr(choice), _ptr(finals), _ptr(sums), _ptr(infinity), _ptr(ios)))
+        return pi, eff, starts, choice, finals, sums, infinity, ios
+
     def generate_trace_powers(self, bases, exps, depth=1):
         """generate_trace on the one-unit list power_instances(stark, bases, exps, depth) gives (count * depth <= num_io, the
         rest padded), the towers linked and walked on the device where the table's chains run there; returns (public inputs,
@@ -1929,6 +1995,36 @@ class BatchProver:
         _check(lib().sbn_batch_prover_prove_msm_batch(self._h, _ptr(terms), _ptr(lengths), len(lengths), _ptr(starts),
                                                       starts.shape[0] if starts is not None else 1, out, _ptr(finals), _ptr(sums), _ptr(infinity), _ptr(ios)))
         return self._proofs(out, len(ios)), finals, sums, infinity, ios
+
+    def prove_msms_complete(self, terms, lengths, term_infinity=None):
+        """A batch of short MSMs of any total length with the starts picked by the library (arguments as
+        msm_batch_instances_complete; sbn_batch_prover_prove_msm_batch_complete).  Returns (proofs, terms_eff, starts, choice,
+        finals, sums, infinity, ios); verify with verify_msms(stark, cfg, proofs, lengths, starts=starts, terms=terms_eff)."""
+        terms, lengths, term_infinity, xw, ew = _complete_args(self.stark, terms, lengths, term_infinity)
+        ios, out = self._unit_buffers(terms.shape[0], 2 * xw + ew)
+        eff, starts, choice, finals, sums, infinity = _complete_outputs(terms.shape[0], len(lengths), xw, ew)
+        _check(lib().sbn_batch_prover_prove_msm_batch_complete(self._h, _ptr(terms), _ptr(term_infinity), _ptr(lengths), len(lengths), out, _ptr(eff),
+                                                               _ptr(starts), _ptr(choice), _ptr(finals), _ptr(sums), _ptr(infinity), _ptr(ios)))
+        return self._proofs(out, len(ios)), eff, starts, choice, finals, sums, infinity, ios
+
+    def prove_scalar_muls_complete(self, points, scalars, point_infinity=None):
+        """Independent scalar multiplications e_k x_k of any count as complete sums of length 1 (points (count, 16E), scalars
+        (count, 8) or one shared scalar, as prove_scalar_muls takes them; point_infinity (count,) bytes or None).  Returns (proofs,
+        products, infinity, terms_eff, starts); verify with verify_msms(stark, cfg, proofs, np.ones(count), starts=starts,
+        terms=terms_eff)."""
+        points, scalars, _, w = _scalar_mul_args(self.stark, points, scalars, None)
+        count = points.shape[0]
+        terms = np.concatenate([points, np.broadcast_to(scalars, (count, 8))], axis=1)
+        proofs, eff, starts, _, _, sums, infinity, _ = self.prove_msms_complete(terms, np.ones(count, dtype=np.uint64), point_infinity)
+        return proofs, sums, infinity, eff, starts
+
+    def prove_msm_complete(self, terms, term_infinity=None):
+        """One sum of e_k x_k over all the terms, a complete sum of one segment.  Returns (proofs, sum, infinity, terms_eff, start):
+        sum (16E,) uint32 with infinity = 1 and zero words when it is the point at infinity; verify with verify_msms(stark, cfg,
+        proofs, [M], starts=start, terms=terms_eff)."""
+        terms = np.ascontiguousarray(terms, dtype=np.uint32)
+        proofs, eff, starts, _, _, sums, infinity, _ = self.prove_msms_complete(terms, np.array([terms.shape[0]], dtype=np.uint64), term_infinity)
+        return proofs, sums[0], int(infinity[0]), eff, starts
 
     def prove_powers(self, bases, exps, depth=1):
         """Powers / power towers of any count (arguments as power_instances) proved as units of the table, the last one padded

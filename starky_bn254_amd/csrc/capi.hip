@@ -336,6 +336,25 @@ int sbn_batch_prover_prove_msm_batch(sbn_batch_prover* B, const uint32_t* terms,
   });
 }
 
+// Complete sums of any total length (include/sbn.h, "Complete sums"): the effective terms, the choice of every segment's start and
+// the list are derived once on the host pool, then the units take the explicit-list path.
+int sbn_batch_prover_prove_msm_batch_complete(sbn_batch_prover* B, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths, size_t segments,
+                                              sbn_proof** proofs_out, uint32_t* terms_out, uint32_t* starts_out, uint8_t* choice_out, uint32_t* finals_out,
+                                              uint32_t* sums_out, uint8_t* infinity_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  size_t M = 0;   // (as above: a refused list has no unit count)
+  const int bad = msm_batch_complete_args(B->kind, terms, lengths, segments, B->num_io, &M);
+  const size_t units = sbn_msm_num_units(M, B->num_io);
+  return prove_derived_units(B, units, ios_out, proofs_out, [&](uint32_t* ios) {
+    if (bad) return bad;
+    std::vector<uint32_t> own;
+    uint32_t* eff = terms_out;
+    if (!eff) { own.resize(exp_io_words(B->kind) * M); eff = own.data(); }   // (an ios row is wider than a term)
+    if (int rc = msm_batch_effective_terms(B->kind, terms, term_infinity, lengths, segments, M, eff)) return rc;
+    return msm_batch_complete_choose(B->kind, eff, lengths, segments, M, units * B->num_io, ios, starts_out, choice_out, finals_out, sums_out, infinity_out);
+  });
+}
+
 int sbn_batch_prover_prove_mul_by_cofactor(sbn_batch_prover* B, const uint32_t* points, size_t count, sbn_proof** proofs_out, uint32_t* cleared_out,
                                            uint8_t* infinity_out, uint32_t* ios_out) {
   if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");

@@ -205,6 +205,7 @@ int chain_terms_check_curve(int E, const uint32_t* terms, size_t K, const uint32
 // (-offset) for K affine outputs ([K][16E] u32; flag 1 and zero words = infinity)
 const uint32_t* curve_generator_words(int E);
 const uint32_t* g2_cofactor_words();
+const uint32_t* curve_start_candidate_words(int E, unsigned j);   // sbn_start_candidate, j < SBN_START_CANDIDATES
 int scalar_mul_check_points(int E, const uint32_t* points, size_t count, const uint32_t* offset);
 void scalar_mul_explicit_list(int E, const uint32_t* points, const uint32_t* scalars, size_t scalar_count, size_t count, size_t total,
                               const uint32_t* offset, uint32_t* ios);
@@ -225,6 +226,16 @@ bool segmented_derive(int kind, const uint32_t* terms, const uint64_t* lengths, 
                       size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, ListRefusal* why);
 int msm_batch_derive(int kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count, size_t M,
                      size_t total, uint32_t* ios, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out);
+// msm_batch.hip, the complete sums (include/sbn.h, "Complete sums"; G1_EXP / G2_EXP only).  msm_batch_complete_args: the refusals of
+// the kind and the arguments, *M_out as above.  msm_batch_effective_terms: terms_eff [M][T] = the caller's terms with (generator,
+// exponent 0) where term_infinity says so (those words are not read), then the refusals of the values.  msm_batch_complete_choose:
+// per segment the smallest start candidate the table's walk takes (every failing segment of a candidate found in one pass), the
+// list of `total` >= M rows, and what msm_batch_derive gives on (terms_eff, starts_out); SBN_ERR_WITNESS when a segment exhausts the
+// candidates.  Every output pointer is optional.
+int msm_batch_complete_args(int kind, const void* terms, const uint64_t* lengths, size_t segments, size_t num_io, size_t* M_out);
+int msm_batch_effective_terms(int kind, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths, size_t segments, size_t M, uint32_t* terms_eff);
+int msm_batch_complete_choose(int kind, const uint32_t* terms_eff, const uint64_t* lengths, size_t segments, size_t M, size_t total, uint32_t* ios,
+                              uint32_t* starts_out, uint8_t* choice_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out);
 // prover.hip: device memory the context allocated, in bytes (the one-shot cache of capi.hip counts it against its budget)
 size_t prover_device_bytes(const sbn_prover* p);
 // prover.hip: the device sbn_set_device / sbn_set_thread_device selected for the calling thread (else the process default)

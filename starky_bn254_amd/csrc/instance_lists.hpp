@@ -77,6 +77,24 @@ template <int E> size_t walk_curve_list(const uint32_t* ios, size_t K) {
   }
   return WALKS;
 }
+// The per-instance form of that walk (the complete sums need every failing segment of a pass, not the first instance): bad[k] = 1
+// where the table cannot walk instance k, 0 elsewhere; false when a pass fails and no instance of it does (walk_curve_list's UNNAMED).
+template <int E> bool walk_status(const uint32_t* ios, size_t K, uint8_t* bad) {
+  const size_t CH = 512, IOW = curve_layout(E).IOW();
+  std::vector<u64> chains(2 * 257 * 12 * E * (K < CH ? K : CH));
+  memset(bad, 0, K);
+  for (size_t at = 0; at < K; at += CH) {
+    const size_t k = K - at < CH ? K - at : CH, cw = 257 * 12 * E * k;
+    if (!tracegen_host_chains(E, ios + IOW * at, k, chains.data(), chains.data() + cw)) continue;
+    std::atomic<size_t> found(0);
+    host_parallel_for(k, [&](size_t i) {
+      std::vector<u64> ja(257 * 12 * E), jb(257 * 12 * E);
+      if (exp_chains<E>(ios + IOW * (at + i), 0, ja.data(), jb.data()) != 0) { bad[at + i] = 1; found++; }
+    });
+    if (!found.load()) return false;
+  }
+  return true;
+}
 static constexpr const char* UNNAMED_WALK_TEXT = "degenerate affine operation (x1 == x2 or y == 0)";
 
 // The public inputs of the unit proofs of one list, as the link checks read them: instance g is row g % num_io of unit g / num_io.

@@ -1291,6 +1291,43 @@ __global__ void __launch_bounds__(CS_LANES) chain_seg_scan_kernel(uint32_t* ios,
       }
   }
 }
+// ---- complete sums (sbn_prover_generate_trace_msm_batch_complete): the start of segment s is start candidate choice[s] -----------------
+// The scan kernels above and below read the start of a segment from the offset words of its head row, and chain_rebase_kernel
+// builds B[t] = offset + I[t-1] with the complete addition, so the B chain is right whether or not the TABLE can walk it.  Two
+// small kernels turn that into a per-segment verdict without touching the kernels of the explicit-start calls:
+//   chain_seg_start_kernel   one lane per (segment, word): the offset words of the head row of segment s <- candidate choice[s];
+//   chain_seg_status_kernel  one lane per (real instance, step t <= 256), behind the rebase: a bad event of the table's walk is
+//                            B[t] at infinity (a zero Z: the step behind B[s] = -A[s], or for t = 256 an output, i.e. the next offset
+//                            or the final, at infinity) or, at a set bit, B[t] = +-A[t] (X2 Z1^2 = X1 Z2^2) -- the refusals of
+//                            affine_lambda_kernel.  A lane that meets one ORs a bit into the status word of its instance's segment
+//                            (seg_of[k]); a clean list stores nothing, and no lane reads a status word.
+// The host clears the status words, reads them back behind the kernel, moves the failing segments to their next candidate and runs
+// start, scan, rebase and status again; the terms e_k x_k and the partial sums I[t] enter no start and are computed once.
+template <int E>
+__global__ void chain_seg_start_kernel(uint32_t* ios, size_t S, const uint32_t* __restrict__ seg_head, const uint32_t* __restrict__ choice,
+                                       const uint32_t* __restrict__ candidates) {
+  const size_t W = 16 * E, IOW = 2 * W + 8;
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= S * W) return;
+  const size_t s = i / W, w = i % W;
+  ios[IOW * seg_head[s] + W + w] = candidates[W * choice[s] + w];
+}
+template <int E>
+__global__ void chain_seg_status_kernel(const uint32_t* __restrict__ ios, size_t M, const u64* __restrict__ ja, const u64* __restrict__ jb,
+                                        const uint32_t* __restrict__ seg_of, int* __restrict__ status) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= M * 257) return;
+  const size_t k = i / 257; const int t = (int)(i % 257);
+  const Co<E> Z2 = ldc<E>(jb + jac_at<E>(k, t, 2));
+  bool bad = czero<E>(Z2);
+  if (!bad && t < 256 && ((ios[8 * (4 * E + 1) * k + 32 * E + (t >> 5)] >> (t & 31)) & 1)) {
+    const Co<E> Z1 = ldc<E>(ja + jac_at<E>(k, t, 2));
+    const Co<E> D = csub(cmul(ldc<E>(jb + jac_at<E>(k, t, 0)), cmul(Z1, Z1)), cmul(ldc<E>(ja + jac_at<E>(k, t, 0)), cmul(Z2, Z2)));
+    bad = czero<E>(Z1) || czero<E>(D);
+  }
+  if (bad) atomicOr(status + seg_of[k], 1);
+}
+
 // ---- lists of more than CS_LANES instances: the same scan in blocks of CS_LANES, chained and segmented alike --------------------------
 // `head` is null for a chained list (one segment: every head is 0, M = K).  Three kernels; what one stores another reads only behind
 // the kernel boundary between them, and no workgroup waits for another one.

@@ -145,6 +145,85 @@ bool derive(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L,
   return true;
 }
 
+// ---- the complete sums: the library picks the start of every segment -------------------------------------------------------------
+// offset[g] = H + P[g] with P[g] = the sum of the segment's terms before g, which no start enters: the terms and their prefix sums
+// are computed once, a candidate H costs one complete addition per instance (and one for the final) of the segments still open.
+// Candidate j is tried on every open segment in one pass -- the offsets, one inversion for their affine forms, the table's walk of
+// the rows with a per-instance status -- and only the segments with a bad event (an offset or the final at infinity, an instance
+// the table cannot walk) stay open for candidate j + 1.  A segment's bad set depends on its own terms alone, so the choice of one
+// segment never moves another.  The sum is P of the whole segment: final + (-start) in canonical affine words.
+template <int E>
+int complete_curve(const PiLayout& t, const uint32_t* terms, size_t M, const Layout& L, size_t segments, size_t total, uint32_t* ios,
+                   uint32_t* starts_out, uint8_t* choice_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out) {
+  const size_t T = t.T(), IOW = t.IOW(), W = t.xw, NONE = (size_t)-1;
+  std::vector<Jac<E>> term(M), pre(M), tot(segments);
+  host_parallel_for(M, [&](size_t g) { term[g] = scalar_mul_jac<E>(ld_point<E>(terms + T * g), terms + T * g + W); });
+  host_parallel_for(segments, [&](size_t s) {
+    Jac<E> acc = jac_infinity<E>();
+    for (size_t g = L.head[s]; g < L.head[s + 1]; g++) { pre[g] = acc; acc = jac_add_complete<E>(acc, term[g]); }
+    tot[s] = acc;
+  });
+  for (size_t g = 0; g < M; g++) {
+    memcpy(ios + IOW * g, terms + T * g, W * sizeof(uint32_t));
+    memcpy(ios + IOW * g + 2 * W, terms + T * g + W, t.ew * sizeof(uint32_t));
+  }
+  std::vector<size_t> open(segments), bad_at(segments, NONE);
+  for (size_t s = 0; s < segments; s++) open[s] = s;
+  for (unsigned j = 0; j < SBN_START_CANDIDATES && !open.empty(); j++) {
+    const uint32_t* hw = curve_start_candidate_words(E, j);
+    const Jac<E> H = ld_point<E>(hw);
+    // slot[i]: the offsets of open segment i, then its final
+    std::vector<size_t> slot(open.size() + 1, 0);
+    for (size_t i = 0; i < open.size(); i++) slot[i + 1] = slot[i] + (L.head[open[i] + 1] - L.head[open[i]]) + 1;
+    std::vector<Jac<E>> pts(slot.back());
+    host_parallel_for(open.size(), [&](size_t i) {
+      const size_t s = open[i], h = L.head[s], len = L.head[s + 1] - h;
+      for (size_t q = 0; q < len; q++) pts[slot[i] + q] = jac_add_complete<E>(H, pre[h + q]);
+      pts[slot[i] + len] = jac_add_complete<E>(H, tot[s]);
+    });
+    std::vector<uint32_t> aff(W * pts.size());
+    std::vector<uint8_t> inf(pts.size());
+    affine_or_infinity<E>(pts, aff.data(), inf.data());   // one inversion for every Z
+    // the rows whose offset the table can hold, packed for the walk
+    std::vector<uint32_t> rows;
+    rows.reserve(IOW * (pts.size() - open.size()));
+    for (size_t i = 0; i < open.size(); i++) {
+      const size_t h = L.head[open[i]], len = slot[i + 1] - slot[i] - 1;
+      for (size_t q = 0; q < len; q++) {
+        if (inf[slot[i] + q]) continue;
+        uint32_t* io = ios + IOW * (h + q);
+        memcpy(io + W, aff.data() + W * (slot[i] + q), W * sizeof(uint32_t));
+        rows.insert(rows.end(), io, io + IOW);
+      }
+    }
+    std::vector<uint8_t> unwalkable(rows.size() / IOW + 1);
+    if (!walk_status<E>(rows.data(), rows.size() / IOW, unwalkable.data())) return fail(SBN_ERR_WITNESS, UNNAMED_WALK_TEXT);
+    std::vector<size_t> still;
+    size_t r = 0;
+    for (size_t i = 0; i < open.size(); i++) {
+      const size_t s = open[i], h = L.head[s], len = slot[i + 1] - slot[i] - 1;
+      size_t first = NONE;
+      for (size_t q = 0; q < len; q++) {
+        const bool bad = inf[slot[i] + q] ? true : unwalkable[r++] != 0;
+        if (bad && first == NONE) first = h + q;
+      }
+      if (first == NONE && inf[slot[i] + len]) first = h + len - 1;   // the output of the segment's last instance
+      if (first != NONE) { bad_at[s] = first; still.push_back(s); continue; }
+      if (choice_out) choice_out[s] = (uint8_t)j;
+      if (starts_out) memcpy(starts_out + W * s, hw, W * sizeof(uint32_t));
+      if (finals_out) memcpy(finals_out + W * s, aff.data() + W * (slot[i] + len), W * sizeof(uint32_t));
+    }
+    open.swap(still);
+  }
+  if (!open.empty())
+    return fail(SBN_ERR_WITNESS, "segment %zu: every one of the %d start candidates meets a degenerate affine operation or a point at infinity in the table's walk "
+                "(%zu segment%s in this state; candidate %d fails at instance %zu): such a list is crafted, call sbn_msm_batch_instances with starts of your own",
+                open[0], SBN_START_CANDIDATES, open.size(), open.size() == 1 ? "" : "s", SBN_START_CANDIDATES - 1, bad_at[open[0]]);
+  affine_or_infinity<E>(tot, sums_out, infinity_out);
+  pad_rows(ios, IOW, M, total);
+  return SBN_OK;
+}
+
 // ---- sbn_msm_batch_check on the curves: the outputs are points, and final + (-start) per segment -------------------------------------
 template <int E>
 int check_curve_outputs(const PiLayout& t, const std::vector<uint32_t>& outs, size_t M, const Layout& L, size_t segments, const uint32_t* starts, size_t start_count,
@@ -216,7 +295,50 @@ int msm_batch_derive(int kind, const uint32_t* terms, const uint64_t* lengths, s
     default: return fail(SBN_ERR_WITNESS, UNNAMED_WALK_TEXT);
   }
 }
+
+int msm_batch_complete_args(int kind, const void* terms, const uint64_t* lengths, size_t segments, size_t num_io, size_t* M_out) {
+  PiLayout t;
+  if (pi_layout(kind, t) && !t.E)
+    return fail(SBN_ERR_UNSUPPORTED, "complete sums cover the curve tables G1_EXP and G2_EXP (a field table's offset one is always legal: sbn_msm_batch_instances)");
+  const uint32_t* starts = nullptr;
+  size_t start_count = 1;
+  return msm_batch_check_args(kind, terms, lengths, segments, &starts, &start_count, num_io, nullptr, nullptr, M_out);
+}
+
+int msm_batch_effective_terms(int kind, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths, size_t segments, size_t M, uint32_t* terms_eff) {
+  const PiLayout t = pi_layout(kind);
+  const size_t T = t.T();
+  for (size_t g = 0; g < M; g++) {
+    if (term_infinity && term_infinity[g]) {   // the identity: a point of the curve with exponent 0, its walk has no addition
+      memcpy(terms_eff + T * g, curve_generator_words(t.E), t.xw * sizeof(uint32_t));
+      memset(terms_eff + T * g + t.xw, 0, t.ew * sizeof(uint32_t));
+    } else memcpy(terms_eff + T * g, terms + T * g, T * sizeof(uint32_t));
+  }
+  return check_inputs(t, terms_eff, M, Layout(lengths, segments, M), nullptr, 0);
+}
+
+int msm_batch_complete_choose(int kind, const uint32_t* terms_eff, const uint64_t* lengths, size_t segments, size_t M, size_t total, uint32_t* ios,
+                              uint32_t* starts_out, uint8_t* choice_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out) {
+  const PiLayout t = pi_layout(kind);
+  const Layout L(lengths, segments, M);
+  std::vector<uint32_t> own;
+  if (!ios) { own.resize(t.IOW() * total); ios = own.data(); }
+  return t.E == 1 ? complete_curve<1>(t, terms_eff, M, L, segments, total, ios, starts_out, choice_out, finals_out, sums_out, infinity_out)
+                  : complete_curve<2>(t, terms_eff, M, L, segments, total, ios, starts_out, choice_out, finals_out, sums_out, infinity_out);
+}
 }  // namespace sbn
+
+extern "C" int sbn_msm_batch_instances_complete(int32_t kind, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths, size_t segments, size_t num_io,
+                                                uint32_t* ios_out, uint32_t* terms_out, uint32_t* starts_out, uint8_t* choice_out, uint32_t* finals_out,
+                                                uint32_t* sums_out, uint8_t* infinity_out) {
+  size_t M = 0;
+  if (int rc = msm_batch_complete_args((int)kind, terms, lengths, segments, num_io, &M)) return rc;
+  std::vector<uint32_t> own;
+  if (!terms_out) { own.resize(pi_layout((int)kind).T() * M); terms_out = own.data(); }
+  if (int rc = msm_batch_effective_terms((int)kind, terms, term_infinity, lengths, segments, M, terms_out)) return rc;
+  return msm_batch_complete_choose((int)kind, terms_out, lengths, segments, M, sbn_msm_num_units(M, num_io) * num_io, ios_out, starts_out, choice_out, finals_out,
+                                   sums_out, infinity_out);
+}
 
 extern "C" int sbn_msm_batch_instances(int32_t kind, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count,
                                        size_t num_io, uint32_t* ios_out, uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out) {

@@ -153,6 +153,9 @@ struct PowerIn { const uint32_t* bases; const uint32_t* exps; size_t exp_count, 
 struct BatchIn {
   const uint32_t* terms; const uint64_t* lengths; size_t segments; const uint32_t* starts; size_t start_count, M;
   uint32_t* finals_out; uint32_t* sums_out; uint8_t* infinity_out; uint32_t* ios_out;
+  // complete sums (null: the starts are the caller's): choice[s] in, every entry 0 with `starts` = candidate 0 for every segment;
+  // out: the candidate segment s starts from, its words in starts_out[s]
+  uint8_t* choice = nullptr; uint32_t* starts_out = nullptr;
 };
 // the preliminary list of a segmented one (a chained list is one segment): row g carries x and exponent of instance min(g, M - 1)
 // and `offset_of(segment)` as its offset (xw words each, ew of the exponent); head_of[g] = the head of the segment of that
@@ -353,16 +356,41 @@ struct CurveJob : TraceJob {
   // preliminary list and the partial sums of every instance, then a scan over the list, or over M instances in segments with
   // head d_head_of[k], writes the offsets into d_ios
   int chain_scan(size_t M = 0, const uint32_t* d_head_of = nullptr) {
+    if (int rc = chain_terms()) return rc;
+    scan_offsets(M, d_head_of, d_err);
+    mark("chain_offsets");
+    return 0;
+  }
+  // its two halves: what no start enters (the A chains, the partial sums of every instance and the terms e_k x_k), and the scan from
+  // the starts in the offset words of the head rows, an offset at infinity flagged in `errw`
+  int chain_terms() {
     if (int rc = launch_chains(err_pre)) return rc;
     hipLaunchKernelGGL(tg::chain_prefix_kernel<E>, dim3((unsigned)K), dim3(tg::CT_LANES), 0, st, d_ios, K, ja, pre, terms);
+    return 0;
+  }
+  void scan_offsets(size_t M, const uint32_t* d_head_of, int* errw) {
     if (K > (size_t)tg::CS_LANES) {   // in blocks of CS_LANES instances: three kernels, ordered by their boundaries
       const size_t real = d_head_of ? M : K;
       hipLaunchKernelGGL(tg::chain_block_scan_kernel<E>, blocks(real, tg::CS_LANES), dim3(tg::CS_LANES), 0, st, d_ios, real, d_head_of, terms, scan[0], scan[1]);
       hipLaunchKernelGGL(tg::chain_block_carry_kernel<E>, dim3(1), dim3(64), 0, st, real, d_head_of, scan[1], carry);
-      hipLaunchKernelGGL(tg::chain_block_tail_kernel<E>, blocks((K + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, K, real, d_head_of, scan[1], carry, scan[0], d_err);
-    } else if (d_head_of) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, M, d_head_of, terms, scan[0], scan[1], d_err);
-    else hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, terms, scan[0], scan[1], d_err);
-    mark("chain_offsets");
+      hipLaunchKernelGGL(tg::chain_block_tail_kernel<E>, blocks((K + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, st, d_ios, K, real, d_head_of, scan[1], carry, scan[0], errw);
+    } else if (d_head_of) hipLaunchKernelGGL(tg::chain_seg_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, M, d_head_of, terms, scan[0], scan[1], errw);
+    else hipLaunchKernelGGL(tg::chain_scan_kernel<E>, dim3(1), dim3(tg::CS_LANES), 0, st, d_ios, K, terms, scan[0], scan[1], errw);
+  }
+  // complete sums, one round: the failing segments of the round before start from their next candidate (d_choice: one index per
+  // segment), the scan and the rebase run again, and every segment with a bad event of the table's walk gets a status word; the
+  // words come back to h_status and the stream drains.  The offset-at-infinity flag of the scan goes to the word nobody reads
+  // (err_pre): the status kernel finds that event as the output at infinity of the instance before.
+  int choice_round(bool restart, size_t M, size_t S, const uint32_t* d_head_of, const uint32_t* d_seg_head, const uint32_t* d_seg_of, const uint32_t* d_choice,
+                   const uint32_t* d_candidates, int* d_status, int* h_status) {
+    HIPC(hipMemsetAsync(d_status, 0, S * sizeof(int), st));
+    if (restart) hipLaunchKernelGGL(tg::chain_seg_start_kernel<E>, blocks(S * PW, 256), dim3(256), 0, st, d_ios, S, d_seg_head, d_choice, d_candidates);
+    scan_offsets(M, d_head_of, err_pre);
+    hipLaunchKernelGGL(tg::chain_rebase_kernel<E>, blocks(K * 257, 64), dim3(64), 0, st, d_ios, K, pre, jb);
+    hipLaunchKernelGGL(tg::chain_seg_status_kernel<E>, blocks(M * 257, 256), dim3(256), 0, st, d_ios, M, ja, jb, d_seg_of, d_status);
+    HIPC(hipMemcpyAsync(h_status, d_status, S * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    HIPC(hipGetLastError());
     return 0;
   }
   void rebase() {   // the chain of b onto the derived offsets; A is in ja already
@@ -485,36 +513,67 @@ static int curve_trace_scalar_muls(sbn_prover* P, const ScalarMulIn& sm, size_t 
 
 // segmented: x, the start of its segment, exp_val of every instance go up with three index arrays (aux: the head of every lane's
 // segment [K], then tail and head per segment); the derived list comes back behind the outputs, the sums final + (-start) and
-// their flags behind the list
+// their flags behind the list.  Complete sums (mb.choice): three more arrays behind those (the segment of every instance [K], the
+// start candidates [8][16E], the choice of every segment [S]); the offsets are derived in rounds (CurveJob::choice_round) until no
+// segment reports a bad event, then the stages run on as for the caller's starts.
 template <int E>
 static int curve_trace_segmented(sbn_prover* P, const BatchIn& mb, size_t K, uint64_t* pi_out) {
   if (int rc = msm_batch_check_inputs(P->air.kind, mb.terms, mb.lengths, mb.segments, mb.starts, mb.start_count, mb.M)) return rc;
-  const size_t S = mb.segments;
+  const size_t S = mb.segments, W = 16 * E;
+  const bool pick = mb.choice != nullptr;
   std::vector<uint32_t> aux, seg_head, seg_len;
-  const std::vector<uint32_t> prelim = preliminary_list(mb.terms, mb.lengths, S, mb.M, K, 16 * E, 8, [&](size_t s) { return mb.starts + (mb.start_count == 1 ? 0 : 16 * E * s); },
+  const std::vector<uint32_t> prelim = preliminary_list(mb.terms, mb.lengths, S, mb.M, K, W, 8, [&](size_t s) { return mb.starts + (mb.start_count == 1 ? 0 : W * s); },
                                                         seg_head, seg_len, &aux);
   for (size_t s = 0; s < S; s++) aux.push_back(seg_head[s] + seg_len[s] - 1);
   aux.insert(aux.end(), seg_head.begin(), seg_head.end());
+  const size_t seg_of_at = aux.size(), cand_at = seg_of_at + K, choice_at = cand_at + SBN_START_CANDIDATES * W;
+  if (pick) {
+    aux.resize(choice_at + S, 0);
+    for (size_t s = 0; s < S; s++) for (size_t g = seg_head[s]; g < seg_head[s] + seg_len[s]; g++) aux[seg_of_at + g] = (uint32_t)s;
+    for (unsigned j = 0; j < SBN_START_CANDIDATES; j++) memcpy(&aux[cand_at + W * j], curve_start_candidate_words(E, j), W * sizeof(uint32_t));
+  }
   HIPC(hipSetDevice(P->device));
   CurveJob<E> J(P, K);
   J.carve_scan();
   J.carve_products(S);
   uint32_t* d_aux = (uint32_t*)J.take(aux.size() / 2 + 1);
-  if (int rc = J.ready(J.list_words, J.list_words + 8 * E * S + (S + 7) / 8)) return rc;
+  int* d_status = pick ? (int*)J.take(S / 2 + 1) : nullptr;
+  if (int rc = J.ready(J.list_words, J.list_words + 8 * E * S + (S + 7) / 8 + (pick ? S / 2 + 1 : 0))) return rc;
   const uint32_t* ios = (const uint32_t*)J.h_back();
   u64* const h_sums = J.h_back() + J.list_words;
   if (int rc = J.upload_list(prelim.data())) return rc;
   HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
-  if (int rc = J.chain_scan(mb.M, d_aux)) return rc;
+  if (!pick) { if (int rc = J.chain_scan(mb.M, d_aux)) return rc; }
+  else {
+    int* h_status = (int*)(h_sums + 8 * E * S + (S + 7) / 8);
+    if (int rc = J.chain_terms()) return rc;
+    for (bool restart = false;; restart = true) {
+      if (restart) HIPC(hipMemcpyAsync(d_aux + choice_at, &aux[choice_at], S * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+      if (int rc = J.choice_round(restart, mb.M, S, d_aux, d_aux + K + S, d_aux + seg_of_at, d_aux + choice_at, d_aux + cand_at, d_status, h_status)) return rc;
+      bool failed = false, exhausted = false;
+      for (size_t s = 0; s < S; s++)
+        if (h_status[s]) { failed = true; if (++aux[choice_at + s] == SBN_START_CANDIDATES) exhausted = true; }
+      if (!failed) break;
+      if (exhausted) {   // the host derivation words the refusal: the segment, how many there are, the instance candidate 7 fails at
+        if (int why = msm_batch_complete_choose(P->air.kind, mb.terms, mb.lengths, S, mb.M, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return why;
+        return fail(SBN_ERR_WITNESS, "the device refuses every start candidate of a segment the host derivation takes");
+      }
+    }
+    J.mark("chain_offsets");
+    for (size_t s = 0; s < S; s++) {
+      mb.choice[s] = (uint8_t)aux[choice_at + s];
+      memcpy(mb.starts_out + W * s, curve_start_candidate_words(E, aux[choice_at + s]), W * sizeof(uint32_t));
+    }
+  }
   J.common_columns();
-  J.rebase();
+  if (!pick) J.rebase();   // (the rounds of the complete sums end with the rebase of the chosen starts)
   J.affine_lambda();
   J.un_offset(d_aux + K, d_aux + K + S);   // final_s + (-start_s): indexed by the tail and the head of every segment
   if (int rc = J.witness_and_range_check()) return rc;
   if (int rc = J.download_list(J.h_back())) return rc;
   if (int rc = J.download_products(h_sums)) return rc;
   const int rc = J.publish(ios, pi_out, mb.ios_out);
-  if (rc == SBN_ERR_WITNESS && (J.error_word() & (tg::TG_ERR_INFINITY | tg::TG_ERR_DEGENERATE))) {
+  if (rc == SBN_ERR_WITNESS && !pick && (J.error_word() & (tg::TG_ERR_INFINITY | tg::TG_ERR_DEGENERATE))) {
     // the kernels report an error word only: the host derivation names the instance and its segment (error path)
     std::vector<uint32_t> named(J.IOW * K);
     if (int why = msm_batch_derive(P->air.kind, mb.terms, mb.lengths, S, mb.starts, mb.start_count, mb.M, K, named.data(), nullptr, nullptr, nullptr)) return why;
@@ -876,6 +935,39 @@ extern "C" int sbn_prover_generate_trace_msm_batch(sbn_prover* P, const uint32_t
   const BatchIn mb{terms, lengths, segments, starts, start_count, M, finals_out, sums_out, infinity_out, ios_out};
   if (is_fq12(kind)) return fq12_trace_segmented(P, mb, num_io, pi_out);
   return kind == SBN_AIR_G1_EXP ? curve_trace_segmented<1>(P, mb, num_io, pi_out) : curve_trace_segmented<2>(P, mb, num_io, pi_out);
+}
+
+// sbn_prover_generate_trace on the one-unit list sbn_msm_batch_instances_complete derives from (terms, term_infinity, lengths).  Where
+// the chains run on the device the segmented driver above derives the list there, every segment from candidate 0 first, in rounds
+// until no segment reports a bad event.  Placement 0 and a list that exhausts the candidates derive on the host pool.
+extern "C" int sbn_prover_generate_trace_msm_batch_complete(sbn_prover* P, const uint32_t* terms, const uint8_t* term_infinity, const uint64_t* lengths,
+                                                            size_t segments, uint64_t* pi_out, uint32_t* terms_out, uint32_t* starts_out, uint8_t* choice_out,
+                                                            uint32_t* finals_out, uint32_t* sums_out, uint8_t* infinity_out, uint32_t* ios_out) {
+  if (int rc = unload(P)) return rc;
+  const int kind = P->air.kind;
+  const size_t num_io = P->air.num_io;
+  size_t M = 0;
+  if (int rc = msm_batch_complete_args(kind, terms, lengths, segments, num_io, &M)) return rc;
+  if (M > num_io) return fail(SBN_ERR_BAD_ARG, "%zu segments of %zu instances do not fit one unit of %zu instances", segments, M, num_io);
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  const size_t W = pi_layout(kind).xw, T = pi_layout(kind).T();
+  std::vector<uint32_t> own_terms, own_starts;
+  std::vector<uint8_t> own_choice;
+  if (!terms_out) { own_terms.resize(T * M); terms_out = own_terms.data(); }
+  if (!starts_out) { own_starts.resize(W * segments); starts_out = own_starts.data(); }
+  if (!choice_out) { own_choice.resize(segments); choice_out = own_choice.data(); }
+  if (int rc = msm_batch_effective_terms(kind, terms, term_infinity, lengths, segments, M, terms_out)) return rc;
+  if (!device_chains)
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) {
+      return msm_batch_complete_choose(kind, terms_out, lengths, segments, M, num_io, ios, starts_out, choice_out, finals_out, sums_out, infinity_out);
+    });
+  const int E = kind == SBN_AIR_G1_EXP ? 1 : 2;
+  for (size_t s = 0; s < segments; s++) memcpy(starts_out + W * s, curve_start_candidate_words(E, 0), W * sizeof(uint32_t));
+  memset(choice_out, 0, segments);
+  BatchIn mb{terms_out, lengths, segments, starts_out, segments, M, finals_out, sums_out, infinity_out, ios_out};
+  mb.choice = choice_out; mb.starts_out = starts_out;
+  return E == 1 ? curve_trace_segmented<1>(P, mb, num_io, pi_out) : curve_trace_segmented<2>(P, mb, num_io, pi_out);
 }
 
 // sbn_prover_generate_trace on the one-unit list sbn_power_instances derives from (bases, exps, depth)
