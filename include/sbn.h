@@ -909,6 +909,72 @@ int sbn_batch_prover_prove_powers(sbn_batch_prover* b, const uint32_t* bases, co
 int sbn_power_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units, size_t count, size_t depth,
                     const uint32_t* bases, const uint32_t* exps, size_t exp_count, uint32_t* powers_out);
 
+/* Field programs ------------------------------------------------------------------------------------- */
+/* The general form of the linked lists above, on the three field Exp tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64 (an instance is
+ * output = offset * x^e): a PROGRAM is a list of instances whose x and offset are each a literal or the OUTPUT of an earlier
+ * instance.  A chained list is the program offset[k+1] = output[k], a tower the program x[l] = output[l-1]; with general links the
+ * same table states a product of two earlier results (x = a, offset = b, e = 1), a Frobenius map (e = p), an exponent longer than
+ * the exponent field by Horner (acc = acc^(2^B) * x^limb), and a check f * f_inv = 1 by reading the output.  Curve tables are out
+ * of scope: a curve output is offset + e x, so an output used as x drags its start along.
+ * One definition for every entry point below.  W = 8 (FQ_EXP) or 96 (the Fq12 tables) u32 words per field element and ew = 8 u32
+ * words per exponent (2, low word first, for FQ12_EXP_U64), the word shapes of `ios` and of the field powers:
+ *   nodes  [count]: node g is instance g of the list.  x and offset are an index into `values` (a literal), or SBN_NODE_OUTPUT | j,
+ *          the output of node j, j < g; offset may also be SBN_NODE_ONE, the field's one.  exp is an index into `exps`.
+ *   values [n_values][W] u32, exps [n_exps][ew] u32: exponents are used as they are, never reduced.
+ * A literal and an earlier output may each be used any number of times, in either position, and the same node may supply both x
+ * and offset of one node.  With units = sbn_msm_num_units(count, num_io) the explicit list has units * num_io rows: row g < count is
+ * (x, offset, exponent of node g) with every link resolved to its words, row g >= count a copy of row count - 1 (the resize rule,
+ * as sbn_msm_instances).  Links may cross unit boundaries.  Outputs follow the table's own walk: 0^0 = 1, and a zero base or a zero
+ * offset are legal.  outs_out: [count][W] u32, ios_out: [units * num_io][24 | 200 | 194] u32; both optional.
+ * Refused, in this order:
+ *   1. SBN_ERR_UNSUPPORTED for a curve table or a kind that is no Exp table;
+ *   2. SBN_ERR_BAD_ARG for a null nodes, values or exps, count = 0 or num_io = 0, and count, n_values or n_exps of 2^31 - 1 or more;
+ *   3. node by node, naming the node and the field, SBN_ERR_BAD_ARG for a link with j >= g, then a literal index >= n_values, then
+ *      SBN_NODE_ONE as x, then an exponent index >= n_exps;
+ *   4. for the literals, then the exponents, THAT SOME NODE USES, in index order: SBN_ERR_BAD_ARG for a coefficient >= p and
+ *      SBN_ERR_NON_CANONICAL for a u64 exponent that is no canonical field element (>= 2^64 - 2^32 + 1).
+ * An unused literal is not read, and no call adds a value refusal that sbn_prover_generate_trace would not make on the explicit list. */
+typedef struct sbn_program_node { uint32_t x, offset, exp; } sbn_program_node;
+#define SBN_NODE_OUTPUT 0x80000000u  /* x / offset = SBN_NODE_OUTPUT | j : the output of node j, j < this node's index */
+#define SBN_NODE_ONE    0x7fffffffu  /* offset only: the field's one */
+/* The schedule of a program, which drives the host pool and the device alike: level_out[g] (optional, [count]) = 0 for a node
+ * without links, otherwise 1 + the largest level of the nodes it links to; *depth_out (optional) = 1 + the largest level.  The nodes
+ * of one level are independent.  Structure only: refuses a null nodes, count = 0 or >= 2^31 - 1, a link with j >= g and
+ * SBN_NODE_ONE as x (SBN_ERR_BAD_ARG, naming the node and the field). */
+int sbn_program_levels(const sbn_program_node* nodes, size_t count, uint32_t* level_out, uint32_t* depth_out);
+/* The explicit list and the outputs on the host pool, no device: level by level, the nodes of a level side by side.  num_io is not
+ * checked against any table (this only shapes a list). */
+int sbn_program_instances(int32_t kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                          const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out);
+/* One unit on a prover of the table: count <= the table's num_io (SBN_ERR_BAD_ARG otherwise, after refusals 1 and 2), the rest of
+ * the unit is padded.  On success the loaded trace, the public inputs and ios_out ([num_io][words per instance]) are, word for word,
+ * those of sbn_prover_generate_trace on the list of sbn_program_instances; sizes and the failure rule as there (a failing call
+ * leaves NO trace loaded).  On the Fq12 tables, whose chains run on the device, the host uploads the list with the literals, ones
+ * and exponents in place and the node table; one launch per level runs one workgroup per node of that level, which reads a linked
+ * operand from the outputs an EARLIER launch wrote, stores its words into its own row of the list and walks the chain.  Links cross
+ * kernel boundaries only: no launch reads what it stored.  The pads are filled on the device and the derived list and the outputs
+ * come back in the one download of the instance outputs.  FQ_EXP (chains on the host pool) and an Fq12 prover created under
+ * SBN_FQ12_HOST_CHAIN derive on the host pool and take the explicit path.  The words are the same in every placement. */
+int sbn_prover_generate_trace_program(sbn_prover* p, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                      const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out);
+/* Any count, as units of the batch prover's table (units as above): proofs_out[units] in unit order, word for word what
+ * sbn_batch_prover_prove_ios gives on the list of sbn_program_instances, which is derived once on the host pool (so no context
+ * waits for another).  Failure rule as sbn_batch_prover_prove_powers: a refused list leaves the batch prover usable and every
+ * proofs_out entry null; guards apply as to every sbn_batch_prover_prove_* call. */
+int sbn_batch_prover_prove_program(sbn_batch_prover* b, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                   const uint32_t* exps, size_t n_exps, sbn_proof** proofs_out, uint32_t* outs_out, uint32_t* ios_out);
+/* The twin of sbn_power_check, on the public inputs of the unit proofs (host, no device; it verifies NO proof): what a circuit
+ * states with `connect` calls.  After refusals 1 to 3 and a null public_inputs (SBN_ERR_BAD_ARG) it checks, in instance order:
+ * units == sbn_msm_num_units(count, num_io); x and offset of a literal node equal the caller's words (SBN_NODE_ONE: one); x or
+ * offset of a linked node equals the OUTPUT public inputs of node j, across unit boundaries; the exponent is the caller's; every
+ * output limb is in range (16 bits in the Fq12 tables, 32 in FQ_EXP) and every output coefficient is < p; every pad instance equals
+ * instance count - 1 in x, offset, exponent and output.  SBN_OK and outs_out (optional, [count][W]) = the outputs, or
+ * SBN_ERR_VERIFY_FAILED with sbn_last_error naming the first instance, the field (x, offset, exponent, output) and, for a link, the
+ * node it should equal. */
+int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
+                      const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                      const uint32_t* exps, size_t n_exps, uint32_t* outs_out);
+
 /* One oversized trace split over the GPUs of a node (BASELINE config "Single Fq12 exponentiation proof, trace height
  * 2^18, 8xMI355X with RCCL FRI fold"; reference workload src/fields/fq12/exp.rs:638-696).  One rank per GPU (one process
  * each, or the threads of one process with sbn_local_comm_create); every rank calls the same functions with the same

@@ -34,6 +34,18 @@ pub struct sbn_prover_options {
     pub lde_storage: u32,
 }
 
+/// include/sbn.h `sbn_program_node` ("Field programs"): x / offset an index into `values`, or `SBN_NODE_OUTPUT | j` for the output of
+/// node j (j below the node's own index); offset may be `SBN_NODE_ONE`; exp an index into `exps`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct sbn_program_node {
+    pub x: u32,
+    pub offset: u32,
+    pub exp: u32,
+}
+pub const SBN_NODE_OUTPUT: u32 = 0x8000_0000;
+pub const SBN_NODE_ONE: u32 = 0x7fff_ffff;
+
 /// the modes of sbn_prover_set_guard / sbn_batch_prover_set_guard / sbn_prove_set_guard
 pub const SBN_GUARD_OFF: u32 = 0;
 pub const SBN_GUARD_DEVICE: u32 = 1;
@@ -212,6 +224,11 @@ extern "C" {
     pub fn sbn_prover_generate_trace_powers(p: *mut sbn_prover, bases: *const u32, exps: *const u32, exp_count: usize, count: usize, depth: usize, pi_out: *mut u64, powers_out: *mut u32, ios_out: *mut u32) -> i32;
     pub fn sbn_batch_prover_prove_powers(b: *mut sbn_batch_prover, bases: *const u32, exps: *const u32, exp_count: usize, count: usize, depth: usize, proofs_out: *mut *mut sbn_proof, powers_out: *mut u32, ios_out: *mut u32) -> i32;
     pub fn sbn_power_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, count: usize, depth: usize, bases: *const u32, exps: *const u32, exp_count: usize, powers_out: *mut u32) -> i32;
+    pub fn sbn_program_levels(nodes: *const sbn_program_node, count: usize, level_out: *mut u32, depth_out: *mut u32) -> i32;
+    pub fn sbn_program_instances(kind: i32, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, num_io: usize, ios_out: *mut u32, outs_out: *mut u32) -> i32;
+    pub fn sbn_prover_generate_trace_program(p: *mut sbn_prover, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, pi_out: *mut u64, outs_out: *mut u32, ios_out: *mut u32) -> i32;
+    pub fn sbn_batch_prover_prove_program(b: *mut sbn_batch_prover, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, proofs_out: *mut *mut sbn_proof, outs_out: *mut u32, ios_out: *mut u32) -> i32;
+    pub fn sbn_program_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, outs_out: *mut u32) -> i32;
 
     pub fn sbn_proof_num_words(p: *const sbn_proof) -> usize;
     pub fn sbn_proof_words(p: *const sbn_proof) -> *const u64;

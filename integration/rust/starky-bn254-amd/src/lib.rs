@@ -784,6 +784,34 @@ pub fn prove_mul_by_cofactor<S: SbnTable>(stark: &S, config: &StarkConfig, degre
     prove_scalar_muls(stark, config, degree_bits, inflight, points, count, &cofactor, None)
 }
 
+/// A field program (include/sbn.h, "Field programs") proved as units of a field Exp table (`FqExpStark`, `Fq12ExpStark`,
+/// `Fq12ExpU64Stark`): node g is instance g, its x and offset each a literal of `values` (`n_values` rows), `SBN_NODE_OUTPUT | j` for
+/// the output of an earlier node, or (offset only) `SBN_NODE_ONE`; its exponent a row of `exps` (`n_exps` rows).  The list is derived
+/// once on the host pool, cut into units and padded.  Returns the unit proofs as canonical words, in unit order, and the outputs
+/// (`nodes.len()` rows in the word shape of a literal).
+pub fn prove_program<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: usize, inflight: usize, nodes: &[ffi::sbn_program_node], values: &[u32], n_values: usize, exps: &[u32], n_exps: usize) -> Result<(Vec<Vec<u64>>, Vec<u32>)> {
+    let a = air(stark);
+    let cfg = to_sbn_config(config)?;
+    let units = unsafe { ffi::sbn_msm_num_units(nodes.len(), a.num_io as usize) };
+    ensure!(units > 0 && n_values > 0 && n_exps > 0 && values.len() % n_values == 0 && exps.len() % n_exps == 0, "no node, or values / exps are not n_values / n_exps rows");
+    let mut b = ptr::null_mut();
+    check(unsafe { ffi::sbn_batch_prover_create(&a, &cfg, degree_bits as u32, inflight as u32, &mut b) }, "sbn_batch_prover_create")?;
+    let mut raw = vec![ptr::null_mut(); units];
+    let mut outs = vec![0u32; values.len() / n_values * nodes.len()];
+    let rc = unsafe { ffi::sbn_batch_prover_prove_program(b, nodes.as_ptr(), nodes.len(), values.as_ptr(), n_values, exps.as_ptr(), n_exps, raw.as_mut_ptr(), outs.as_mut_ptr(), ptr::null_mut()) };
+    unsafe { ffi::sbn_batch_prover_destroy(b) };
+    check(rc, "sbn_batch_prover_prove_program")?;
+    let proofs = raw
+        .into_iter()
+        .map(|p| {
+            let words = unsafe { std::slice::from_raw_parts(ffi::sbn_proof_words(p), ffi::sbn_proof_num_words(p)) }.to_vec();
+            unsafe { ffi::sbn_proof_free(p) };
+            words
+        })
+        .collect();
+    Ok((proofs, outs))
+}
+
 /// The library's host verifier on canonical proof words (what `verify_stark_proof` above ends in).
 pub fn verify_stark_proof_words<S: SbnTable>(stark: &S, words: &[u64], config: &StarkConfig) -> Result<()> {
     let a = air(stark);

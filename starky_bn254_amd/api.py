@@ -47,6 +47,7 @@ EXPORTS = [
     "sbn_msm_batch_instances", "sbn_prover_generate_trace_msm_batch", "sbn_batch_prover_prove_msm_batch", "sbn_msm_batch_check",
     "sbn_start_candidate", "sbn_msm_batch_instances_complete", "sbn_prover_generate_trace_msm_batch_complete", "sbn_batch_prover_prove_msm_batch_complete",
     "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
+    "sbn_program_levels", "sbn_program_instances", "sbn_prover_generate_trace_program", "sbn_batch_prover_prove_program", "sbn_program_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_coop_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
@@ -253,6 +254,11 @@ def lib():
         L.sbn_prover_generate_trace_powers.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp]
         L.sbn_batch_prover_prove_powers.argtypes = [vp, vp, vp, sz, sz, sz, C.POINTER(vp), vp, vp]
         L.sbn_power_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, sz, sz, vp, vp, sz, vp]
+        L.sbn_program_levels.argtypes = [vp, sz, vp, vp]
+        L.sbn_program_instances.argtypes = [C.c_int32, vp, sz, vp, sz, vp, sz, sz, vp, vp]
+        L.sbn_prover_generate_trace_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]
+        L.sbn_batch_prover_prove_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp), vp, vp]
+        L.sbn_program_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, vp, sz, vp, sz, vp, sz, vp]
         L.sbn_prove.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, u32, vp, sz, C.POINTER(vp)]
         L.sbn_proof_num_words.restype = sz
         L.sbn_proof_num_words.argtypes = [vp]
@@ -980,6 +986,145 @@ def power_check(stark, public_inputs_per_unit, bases, exps, depth=1):
     powers = np.zeros((count, depth, w), dtype=np.uint32)
     _check(lib().sbn_power_check(stark.kind, stark.num_io, ptrs, n, count, depth, _ptr(bases), _ptr(exps), exps.shape[0], _ptr(powers)))
     return powers
+
+
+# ---- field programs (include/sbn.h, "Field programs") ---------------------------------------------------------------------------
+NODE_OUTPUT = 0x80000000    # x / offset = NODE_OUTPUT | j: the output of node j, j < this node's index
+NODE_ONE = 0x7FFFFFFF       # offset only: the field's one
+
+
+def _program_args(stark, nodes, values, exps):
+    """nodes (count, 3) uint32 = (x, offset, exp) per node; values (n_values, W) uint32, or Python ints for FqExpStark; exps
+    (n_exps, ew) uint32 or a list of Python ints (little-endian u32 limbs)."""
+    w, ew = _power_words(stark)
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+    if w == 8 and not isinstance(values, np.ndarray) and len(values) and all(isinstance(v, int) for v in values):
+        values = [_int_limbs(v, 8) for v in values]
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    if not isinstance(exps, np.ndarray) and len(exps) and all(isinstance(e, int) for e in exps):
+        exps = [_int_limbs(e, ew) for e in exps]
+    exps = np.ascontiguousarray(exps, dtype=np.uint32)
+    if nodes.ndim != 2 or nodes.shape[1] != 3 or values.ndim != 2 or values.shape[1] != w or exps.ndim != 2 or exps.shape[1] != ew:
+        raise SbnError(-1, f"nodes must be [count][3], values [n_values][{w}] and exps [n_exps][{ew}] u32")
+    return nodes, values, exps, w, ew
+
+
+def program_levels(nodes):
+    """The schedule of a program (sbn_program_levels): (level, depth), level[g] = 0 for a node without links, otherwise 1 + the
+    largest level of the nodes it links to; depth = 1 + the largest level.  Structure only; no device needed."""
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+    if nodes.ndim != 2 or nodes.shape[1] != 3:
+        raise SbnError(-1, "nodes must be [count][3] u32")
+    level = np.zeros(nodes.shape[0], dtype=np.uint32)
+    depth = C.c_uint32(0)
+    _check(lib().sbn_program_levels(_ptr(nodes), nodes.shape[0], _ptr(level), C.addressof(depth)))
+    return level, int(depth.value)
+
+
+def program_instances(stark, nodes, values, exps):
+    """A program as instances of the field Exp table `stark` (sbn_program_instances): node g is instance g, x and offset each a
+    literal of `values` or NODE_OUTPUT | j, the output of an earlier node (offset also NODE_ONE), the exponent an entry of `exps`;
+    the last unit is padded with copies of the last instance.  Returns (ios_units, outs): (units, num_io, words per instance)
+    uint32 as BatchProver.prove_ios takes it and the outputs (count, W) uint32.  Exponents are never reduced.  No device needed."""
+    nodes, values, exps, w, ew = _program_args(stark, nodes, values, exps)
+    count = nodes.shape[0]
+    if stark.num_io < 1:
+        raise SbnError(-1, "the table has no instances")
+    units = msm_num_units(count, stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * w + ew), dtype=np.uint32)
+    outs = np.zeros((count, w), dtype=np.uint32)
+    _check(lib().sbn_program_instances(stark.kind, _ptr(nodes), count, _ptr(values), values.shape[0], _ptr(exps), exps.shape[0], stark.num_io,
+                                       _ptr(ios), _ptr(outs)))
+    return ios, outs
+
+
+def program_check(stark, public_inputs_per_unit, nodes, values, exps):
+    """The check of a program (sbn_program_check) on the public inputs of its unit proofs: literals, ones and exponents are the
+    caller's, a linked x or offset equals the output of the node it links to (across units), the pads repeat the last instance,
+    every output is a field element.  Returns the outputs (count, W); raises SbnError(-6) naming the first instance and field
+    that breaks.  Verifies NO proof: verify_program does both."""
+    nodes, values, exps, w, ew = _program_args(stark, nodes, values, exps)
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
+    outs = np.zeros((nodes.shape[0], w), dtype=np.uint32)
+    _check(lib().sbn_program_check(stark.kind, stark.num_io, ptrs, n, _ptr(nodes), nodes.shape[0], _ptr(values), values.shape[0],
+                                   _ptr(exps), exps.shape[0], _ptr(outs)))
+    return outs
+
+
+class Program:
+    """A small builder of programs for the field Exp table `stark`.  value(v) and pow / mul / pow_big return handles; a handle or a
+    literal (W uint32 words; a Python int for FqExpStark) is accepted wherever an operand is.  Equal literals share one slot of
+    `values`, equal exponents one slot of `exps`.  arrays() gives (nodes, values, exps) as program_instances,
+    Prover.generate_trace_program, BatchProver.prove_program and verify_program take them; a node handle h is node h.node."""
+
+    class Handle:
+        __slots__ = ("ref", "node")
+
+        def __init__(self, ref, node=None):
+            self.ref, self.node = ref, node
+
+    def __init__(self, stark):
+        self.stark = stark
+        self.w, self.ew = _power_words(stark)
+        self.limb_bits = 32 * self.ew - 1   # Horner limbs of pow_big: 2^limb_bits is itself a legal exponent (255, or 63 for the u64 table)
+        self._values, self._value_slot, self._exps, self._exp_slot, self._nodes = [], {}, [], {}, []
+
+    def value(self, v):
+        """A literal: W uint32 words (a Python int for FqExpStark).  Equal literals share one slot."""
+        if isinstance(v, Program.Handle):
+            return v
+        words = _int_limbs(v, 8) if self.w == 8 and isinstance(v, int) else [int(t) for t in np.asarray(v).reshape(-1)]
+        if len(words) != self.w:
+            raise SbnError(-1, f"a literal has {self.w} u32 words")
+        key = tuple(words)
+        if key not in self._value_slot:
+            self._value_slot[key] = len(self._values)
+            self._values.append(words)
+        return Program.Handle(self._value_slot[key])
+
+    def _exp(self, e):
+        key = tuple(_int_limbs(int(e), self.ew)) if isinstance(e, (int, np.integer)) else tuple(int(t) for t in np.asarray(e).reshape(-1))
+        if len(key) != self.ew:
+            raise SbnError(-1, f"an exponent has {self.ew} u32 words")
+        if key not in self._exp_slot:
+            self._exp_slot[key] = len(self._exps)
+            self._exps.append(list(key))
+        return self._exp_slot[key]
+
+    def pow(self, x, e, offset=None):
+        """The node offset * x^e (offset None: one); e a Python int that fits the exponent field, or its ew words."""
+        x = self.value(x)
+        off = NODE_ONE if offset is None else self.value(offset).ref
+        self._nodes.append((x.ref, off, self._exp(e)))
+        g = len(self._nodes) - 1
+        return Program.Handle(NODE_OUTPUT | g, g)
+
+    def mul(self, a, b):
+        """The product a * b: pow(a, 1, offset=b)."""
+        return self.pow(a, 1, offset=b)
+
+    def pow_big(self, x, e):
+        """x^e for a Python int e >= 0 of any length, by Horner over limbs of limb_bits bits, most significant first: the first
+        limb is one node, every further limb two (acc^(2^limb_bits), then x^limb with offset = acc).  A zero limb still emits
+        its nodes, so the node count depends on the bit length of e alone."""
+        e = int(e)
+        if e < 0:
+            raise SbnError(-1, "the exponent must be >= 0")
+        x = self.value(x)
+        b = self.limb_bits
+        limbs = [(e >> (b * i)) & ((1 << b) - 1) for i in range(max(1, -(-e.bit_length() // b)))]
+        acc = self.pow(x, limbs[-1])
+        for limb in reversed(limbs[:-1]):
+            acc = self.pow(x, limb, offset=self.pow(acc, 1 << b))
+        return acc
+
+    def __len__(self):
+        return len(self._nodes)
+
+    def arrays(self):
+        """(nodes (count, 3), values (n_values, W), exps (n_exps, ew)), uint32."""
+        return (np.array(self._nodes, dtype=np.uint32).reshape(-1, 3), np.array(self._values, dtype=np.uint32).reshape(-1, self.w),
+                np.array(self._exps, dtype=np.uint32).reshape(-1, self.ew))
 
 
 def fq_sqrt_flags(xs, roots):
@@ -1745,6 +1890,18 @@ class Prover:
         _check(lib().sbn_prover_generate_trace_powers(self._h, _ptr(bases), _ptr(exps), exps.shape[0], count, depth, _ptr(pi), _ptr(powers), _ptr(ios)))
         return pi, powers, ios
 
+    def generate_trace_program(self, nodes, values, exps):
+        """generate_trace on the one-unit list program_instances(stark, nodes, values, exps) gives (count <= num_io, the rest
+        padded), the links resolved on the device, one launch per level, where the table's chains run there; returns (public
+        inputs, outs, ios).  A failing call leaves no trace loaded."""
+        nodes, values, exps, w, ew = _program_args(self.stark, nodes, values, exps)
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        outs = np.zeros((nodes.shape[0], w), dtype=np.uint32)
+        ios = np.zeros((self.stark.num_io, 2 * w + ew), dtype=np.uint32)
+        _check(lib().sbn_prover_generate_trace_program(self._h, _ptr(nodes), nodes.shape[0], _ptr(values), values.shape[0], _ptr(exps), exps.shape[0],
+                                                       _ptr(pi), _ptr(outs), _ptr(ios)))
+        return pi, outs, ios
+
     def read_trace(self):
         trace = np.zeros((self.stark.num_columns, 1 << self.degree_bits), dtype=np.uint64)
         _check(lib().sbn_prover_read_trace(self._h, _ptr(trace)))
@@ -2044,6 +2201,17 @@ class BatchProver:
             raise SbnError(-1, "the BN-parameter powers are a call of Fq12ExpU64Stark")
         return self.prove_powers(fs, BN_X, depth=3)
 
+    def prove_program(self, nodes, values, exps):
+        """A program of any count (arguments as program_instances) proved as units of the table, the last one padded
+        (sbn_batch_prover_prove_program).  Returns (proofs, outs, ios)."""
+        nodes, values, exps, w, ew = _program_args(self.stark, nodes, values, exps)
+        count = nodes.shape[0]
+        ios, out = self._unit_buffers(count, 2 * w + ew)
+        outs = np.zeros((count, w), dtype=np.uint32)
+        _check(lib().sbn_batch_prover_prove_program(self._h, _ptr(nodes), count, _ptr(values), values.shape[0], _ptr(exps), exps.shape[0],
+                                                    out, _ptr(outs), _ptr(ios)))
+        return self._proofs(out, len(ios)), outs, ios
+
     def close(self):
         if self._h:
             lib().sbn_batch_prover_destroy(self._h)
@@ -2176,6 +2344,15 @@ def verify_powers(stark, config, proofs, bases, exps, depth=1, verifier=None):
     proofs = list(proofs)
     _verify_units(stark, config, proofs, verifier)
     return power_check(stark, [p.public_inputs() for p in proofs], bases, exps, depth)
+
+
+def verify_program(stark, config, proofs, nodes, values, exps, verifier=None):
+    """Verifies the unit proofs of BatchProver.prove_program (host verifier, or a Verifier of the table in batches) and then runs
+    program_check on their public inputs.  Returns the outputs (count, W); raises SbnError when a unit is rejected (naming the
+    unit) or the check fails (naming the instance and field)."""
+    proofs = list(proofs)
+    _verify_units(stark, config, proofs, verifier)
+    return program_check(stark, [p.public_inputs() for p in proofs], nodes, values, exps)
 
 
 def verify_bn_x_powers(stark, config, proofs, fs, verifier=None):

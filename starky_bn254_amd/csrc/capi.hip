@@ -323,6 +323,17 @@ int sbn_batch_prover_prove_powers(sbn_batch_prover* B, const uint32_t* bases, co
   });
 }
 
+// Field programs of any count (include/sbn.h, "Field programs"; csrc/program.hip): every link is resolved with the list, so a link
+// across a unit boundary needs no context to wait for another.
+int sbn_batch_prover_prove_program(sbn_batch_prover* B, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                   const uint32_t* exps, size_t n_exps, sbn_proof** proofs_out, uint32_t* outs_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const bool fits = count && count < 0x7fffffffu;   // (what does not fit has no unit count: sbn_program_instances refuses it)
+  return prove_derived_units(B, fits ? sbn_msm_num_units(count, B->num_io) : 0, ios_out, proofs_out, [&](uint32_t* ios) {
+    return sbn_program_instances(B->kind, nodes, count, values, n_values, exps, n_exps, B->num_io, ios, outs_out);
+  });
+}
+
 // Batches of short MSMs of any total length (include/sbn.h, "Batches of short MSMs"; csrc/msm_batch.hip): a segment that straddles
 // two units needs no context to wait for another.
 int sbn_batch_prover_prove_msm_batch(sbn_batch_prover* B, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count,

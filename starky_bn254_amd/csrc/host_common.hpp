@@ -213,6 +213,14 @@ int scalar_mul_name_degenerate(int E, const uint32_t* ios, size_t K);
 void scalar_mul_unoffset_host(int E, const uint32_t* outputs, const uint32_t* offset, size_t K, uint32_t* products, uint8_t* infinity);
 // powers.hip: the refusals of the bases and exponents of a field Exp table, naming the tower
 int power_check_inputs(int kind, const uint32_t* bases, const uint32_t* exps, size_t exp_count, size_t count);
+// program.hip (include/sbn.h, "Field programs"): refusals 1 to 4 of the header in its order, and the schedule: level[g], and the
+// nodes sorted by level (order; the nodes of level l are order[level_start[l] .. level_start[l + 1]), in node order)
+struct ProgramPlan {
+  std::vector<uint32_t> level, order, level_start;
+  size_t depth() const { return level_start.size() - 1; }
+};
+int program_plan(int kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values, const uint32_t* exps, size_t n_exps,
+                 size_t num_io, ProgramPlan& plan);
 // msm_batch.hip (segmented chained lists; a chained list is one segment): the argument refusals in the header's order (a null
 // `*starts` becomes the generator / one with *start_count = 1; *M_out = the sum of the lengths); the refusals of the values, naming
 // the global instance and its segment; the derivation of `total` >= M rows of ios (rows past M repeat row M - 1), the finals and on

@@ -1502,6 +1502,54 @@ __global__ void __launch_bounds__(256) fq12_tower_pad_kernel(uint32_t* ios, size
   for (size_t i = threadIdx.x; i < 48; i += blockDim.x) outs[48 * g + i] = outs[48 * src + i];
 }
 
+// ---- field programs (sbn_prover_generate_trace_program): x and offset of an instance = a literal or the output of an earlier one ----
+// The host sorts the nodes by level (level 0: no link; otherwise 1 + the largest level linked to), so the nodes of one level are
+// independent and every node they link to lies in an EARLIER level.  ONE LAUNCH PER LEVEL, one workgroup per node of that level,
+// with the lane roles, the LDS layout and the step of fq12_chain_kernel; the new part is the head.  The twelve coefficient lanes of
+// A (x) and of B (offset) look their operand up in the node table: a link (bit 31) reads the standard-form output of node j from
+// `outs`, which an earlier LAUNCH wrote, stores those words into the x or offset words of the node's own `ios` row (for the row,
+// flag and download kernels that follow) and enters the chain from those very registers; a literal, or one, loads from `ios`, where
+// the host put it.  Links cross kernel boundaries only: a workgroup writes outs[k] of its own node and reads outs[j] of nodes of
+// earlier levels, so nothing a launch stores to global memory is read again inside it -- no flag, no spin, no fence, no scope
+// question (the rule of fq12_tower_kernel above); the barriers order LDS only.  The price is one launch boundary per level, beside
+// chains of 64 to 256 dependent steps.  fq12_tower_pad_kernel fills the pads behind the last level.
+//   nodes: [count][3] = (x, offset, exp) of include/sbn.h's sbn_program_node; order: the node of workgroup blockIdx.x of this launch
+//   (every entry < count <= K and every link j < its node: program_plan, program.hip, refuses anything else before a launch)
+__global__ void __launch_bounds__(320) fq12_program_level_kernel(uint32_t* ios, size_t iow, int steps, const uint32_t* __restrict__ nodes,
+                                                                 const uint32_t* __restrict__ order, u64* __restrict__ ca, u64* __restrict__ cb, u64* outs) {
+  __shared__ Fq A[12], B[12], PA[144], PB[144];
+  const size_t k = order[blockIdx.x];
+  uint32_t* io = ios + iow * k;
+  const int tid = threadIdx.x, c = tid % 12;
+  const bool is_a = tid < 12, is_b = tid >= 12 && tid < 24;
+  if (is_a || is_b) {
+    const uint32_t src = nodes[3 * k + (is_a ? 0 : 1)];
+    uint32_t* w8 = io + (is_a ? 0 : 96) + 8 * c;
+    u64 t4[4];
+    if (src & 0x80000000u) {   // the link: output of node j (an earlier launch) -> x / offset of this node
+      const u64* o = outs + ((size_t)(src & 0x7fffffffu) * 12 + c) * 4;
+      for (int i = 0; i < 4; i++) t4[i] = o[i];
+      for (int w = 0; w < 8; w++) w8[w] = (uint32_t)(t4[w >> 1] >> (32 * (w & 1)));
+    } else u32x8_to_u64x4(w8, t4);
+    (is_a ? A : B)[c] = to_m(t4);
+  }
+  __syncthreads();
+  for (int t = 0;; t++) {
+    if (is_a || is_b) from_m((is_a ? A : B)[c], (is_a ? ca : cb) + ((k * (size_t)(steps + 1) + t) * 12 + c) * 4);
+    if (t == steps) { if (is_b) from_m(B[c], outs + (k * 12 + c) * 4); break; }
+    const bool bit = (io[192 + (t >> 5)] >> (t & 31)) & 1;            // uniform over the workgroup
+    if (tid < 144) PA[tid] = mmul(A[tid / 12], A[tid % 12]);
+    else if (tid < 288 && bit) PB[tid - 144] = mmul(A[(tid - 144) / 12], B[(tid - 144) % 12]);
+    __syncthreads();
+    Fq nv;
+    if (is_a) nv = fq12_fold_coeff(PA, c);
+    else if (is_b && bit) nv = fq12_fold_coeff(PB, c);
+    __syncthreads();                                                   // every product has been read, A / B may change
+    if (is_a) A[c] = nv; else if (is_b && bit) B[c] = nv;
+    __syncthreads();
+  }
+}
+
 // ---- parity hook (sbn_bn254_fq_batch, tracegen_device.hip): the field helpers above on standard-form operands, 4 words per element --------------
 enum { FQB_MUL = 0, FQB_ADD = 1, FQB_SUB = 2, FQB_INV = 3, FQB_BATCH_INV = 4, FQB_FQ2_INV = 5 };
 // Item i of op: element i, or group i of TG_INV_BATCH elements for FQB_BATCH_INV.  FQB_INV is finv_fermat on the device and inv_std on

@@ -147,6 +147,11 @@ struct ScalarMulIn { const uint32_t* points; const uint32_t* scalars; size_t sca
 // its x from `bases`, level l from the output of level l - 1, derived on the device (kernels_tracegen.cuh, "power towers").
 struct PowerIn { const uint32_t* bases; const uint32_t* exps; size_t exp_count, count, depth; uint32_t* powers_out; uint32_t* ios_out; };
 
+// sbn_prover_generate_trace_program: `count` nodes on an Fq12 table whose chains run on the device; x and offset of a node are a
+// literal of `values`, one, or the output of an earlier node, resolved on the device level by level (kernels_tracegen.cuh, "field
+// programs").
+struct ProgramIn { const sbn_program_node* nodes; size_t count; const uint32_t* values; const uint32_t* exps; uint32_t* outs_out; uint32_t* ios_out; };
+
 // sbn_prover_generate_trace_msm_batch: one unit of `segments` chained lists, M real instances and num_io - M pads; the offsets are
 // derived on the device from the terms, the heads and the starts (kernels_tracegen.cuh, "segmented chained lists"), the finals
 // are the instance outputs at the segment tails and, on the curves, the sums final + (-start) are computed there too.
@@ -766,6 +771,41 @@ static int fq12_trace_towers(sbn_prover* P, const PowerIn& pw, size_t K, uint64_
   return rc;
 }
 
+// programs: the literals, ones and exponents of every node go up in place (zeros where a link will be resolved; a pad row repeats
+// row count - 1) with the node table and the nodes sorted by level; one launch per level, one workgroup per node of that level,
+// resolves the links from the outputs of earlier launches and walks the chains (kernels_tracegen.cuh, "field programs"), the pads
+// are filled behind them, and the outputs come back together with the derived list in one download, as for the towers
+static int fq12_trace_program(sbn_prover* P, const ProgramIn& pr, const ProgramPlan& plan, size_t K, uint64_t* pi_out) {
+  Fq12Job J(P, K);
+  const size_t IOW = J.IOW, ew = IOW - 192, M = pr.count;   // M real instances; rows [M, K) are pads
+  std::vector<uint32_t> prelim(IOW * K, 0u), aux(4 * M);    // aux: the node table [M][3], then the order [M]
+  for (size_t g = 0; g < K; g++) {
+    const sbn_program_node& nd = pr.nodes[g < M ? g : M - 1];
+    uint32_t* io = prelim.data() + IOW * g;
+    if (!(nd.x & SBN_NODE_OUTPUT)) memcpy(io, pr.values + 96 * nd.x, 96 * sizeof(uint32_t));
+    if (nd.offset == SBN_NODE_ONE) io[96] = 1;
+    else if (!(nd.offset & SBN_NODE_OUTPUT)) memcpy(io + 96, pr.values + 96 * nd.offset, 96 * sizeof(uint32_t));
+    memcpy(io + 192, pr.exps + ew * nd.exp, ew * sizeof(uint32_t));
+  }
+  for (size_t g = 0; g < M; g++) { aux[3 * g] = pr.nodes[g].x; aux[3 * g + 1] = pr.nodes[g].offset; aux[3 * g + 2] = pr.nodes[g].exp; }
+  memcpy(aux.data() + 3 * M, plan.order.data(), M * sizeof(uint32_t));
+  uint32_t* d_aux = (uint32_t*)J.take(aux.size() / 2 + 1);
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+  J.common_columns();
+  for (size_t l = 0; l < plan.depth(); l++)   // the kernel boundary between two levels is the link: level l reads what levels < l stored
+    hipLaunchKernelGGL(tg::fq12_program_level_kernel, dim3((unsigned)(plan.level_start[l + 1] - plan.level_start[l])), dim3(320), 0, J.st, J.d_ios, IOW, J.steps,
+                       d_aux, d_aux + 3 * M + plan.level_start[l], J.ca, J.cb, J.d_outs);
+  J.mark("program_levels");
+  if (M < K) hipLaunchKernelGGL(tg::fq12_tower_pad_kernel, dim3((unsigned)(K - M)), dim3(256), 0, J.st, J.d_ios, IOW, M, K, (size_t)(J.steps + 1) * 48, J.ca, J.cb, J.d_outs);
+  J.mark("program_pads");
+  if (int rc = J.witness_and_range_check(K * 48 + (IOW * K + 1) / 2)) return rc;
+  const int rc = J.publish((const uint32_t*)(J.h_outs.data() + K * 48), J.h_outs.data(), 48, pi_out, pr.ios_out);
+  if (rc == SBN_OK && pr.outs_out)   // [count][96] u32 = the outputs of the M real instances, standard form
+    for (size_t i = 0; i < 48 * M; i++) { pr.outs_out[2 * i] = (uint32_t)J.h_outs[i]; pr.outs_out[2 * i + 1] = (uint32_t)(J.h_outs[i] >> 32); }
+  return rc;
+}
+
 // FqExpStark: chains on host threads (512 Montgomery products per instance), rows and the u16 range check on the device.
 static int fq_trace_explicit(sbn_prover* P, const uint32_t* ios, size_t K, uint64_t* pi_out) {
   const size_t IOW = 24;
@@ -986,6 +1026,25 @@ extern "C" int sbn_prover_generate_trace_powers(sbn_prover* P, const uint32_t* b
     return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) { return sbn_power_instances(kind, bases, exps, exp_count, count, depth, num_io, ios, powers_out); });
   const PowerIn pw{bases, exps, exp_count, count, depth, powers_out, ios_out};
   return fq12_trace_towers(P, pw, num_io, pi_out);
+}
+
+// sbn_prover_generate_trace on the one-unit list sbn_program_instances derives from (nodes, values, exps)
+extern "C" int sbn_prover_generate_trace_program(sbn_prover* P, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                                 const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out) {
+  if (int rc = unload(P)) return rc;
+  const int kind = P->air.kind;
+  if (!pi_layout(kind).field()) return fail(SBN_ERR_UNSUPPORTED, "field programs cover the field tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64");
+  if (!nodes || !values || !exps || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no node");
+  const size_t num_io = P->air.num_io;
+  if (count > num_io) return fail(SBN_ERR_BAD_ARG, "a program of %zu nodes does not fit one unit of %zu instances", count, num_io);
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  if (!device_chains)
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) { return sbn_program_instances(kind, nodes, count, values, n_values, exps, n_exps, num_io, ios, outs_out); });
+  ProgramPlan plan;
+  if (int rc = program_plan(kind, nodes, count, values, n_values, exps, n_exps, num_io, plan)) return rc;
+  const ProgramIn pr{nodes, count, values, exps, outs_out, ios_out};
+  return fq12_trace_program(P, pr, plan, num_io, pi_out);
 }
 
 extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
