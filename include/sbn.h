@@ -975,6 +975,83 @@ int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* const* public
                       const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
                       const uint32_t* exps, size_t n_exps, uint32_t* outs_out);
 
+/* Curve programs ------------------------------------------------------------------------------------- */
+/* What the field programs above are to the field tables, on the curve tables G1_EXP and G2_EXP (an instance is output = offset +
+ * e x): a program is a list of instances whose x and offset are each a literal point or the OUTPUT of an earlier instance.  A
+ * curve output is no bare product: it carries the start it was accumulated from, so an output used as x drags a multiple of the
+ * start along.  The library does the bookkeeping: beside every output it keeps the BLIND the output carries, a function of the
+ * start, the exponents and the shape of the program alone, and hands back the VALUE output + (-blind) the caller means.  With it
+ * the tables state a multiple of a result, e2 (e1 P) (the subgroup check r (h P) = O of a point just cleared of its cofactor, a
+ * scalar applied to the sum of an MSM), a combination a S1 + b S2 of two earlier results (the random linear combination of a batch
+ * verification, C - y G of a KZG opening, the merge of MSM segments derived side by side) and any DAG of such sums.
+ * One definition for every entry point below.  E = 1 (G1_EXP) or 2 (G2_EXP), W = 16E u32 words per point (x.c0 [x.c1] y.c0 [y.c1],
+ * eight words each, as in `ios`):
+ *   nodes  [count] sbn_program_node: node g is instance g of the list.  x is an index into `points` or SBN_NODE_OUTPUT | j, j < g;
+ *          offset is an index into `points`, SBN_NODE_OUTPUT | j, or SBN_NODE_START, the start the library picks; exp is an index
+ *          into `exps`.  SBN_NODE_ONE is illegal in both fields.
+ *   points [n_points][W] u32, exps [n_exps][8] u32: 256-bit exponents, used as they are, never reduced.
+ * out_g = offset_g + e_g x_g as points, and every output is carried as out_g = v_g + T_g, the value and the blind:
+ *     operand               v      T
+ *     literal point P       P      O
+ *     SBN_NODE_START        O      S
+ *     SBN_NODE_OUTPUT | j   v_j    T_j
+ *   v_g = v_off + e_g v_x,  T_g = T_off + e_g T_x.  A value may be the point at infinity; a node with no SBN_NODE_START anywhere
+ *   under it has T = O and value = out.
+ * S = sbn_start_candidate(kind, choice) with ONE choice for the whole program (a blind is a function of S, so two starts in one
+ * program would need a blind per start and node): the smallest j < SBN_START_CANDIDATES for which no node has a bad event of the
+ * complete sums -- an offset or an output at infinity, or an addition of the table's walk with B = +-A.  The events at a node
+ * whose operands hold no start are the caller's: no candidate mends them.
+ * Returned (every output pointer optional): *choice_out; outs_out [count][W], the table outputs; values_out [count][W] with
+ * infinity_out [count] bytes, values[g] = out_g + (-T_g) by the complete addition (a value at infinity is no error: flag 1, words
+ * zero); ios_out [units * num_io][2W + 8], the explicit list with every link resolved, units = sbn_msm_num_units(count, num_io),
+ * rows >= count copies of row count - 1.  Links may cross units.
+ * Refused, in this order:
+ *   1. SBN_ERR_UNSUPPORTED for any kind but G1_EXP / G2_EXP;
+ *   2. SBN_ERR_BAD_ARG for a null nodes, points or exps, count = 0 or num_io = 0, and count, n_points or n_exps of 2^31 - 1 or more;
+ *   3. node by node, naming the node and the field, SBN_ERR_BAD_ARG for a link with j >= g, then a literal index >= n_points, then
+ *      SBN_NODE_ONE, then SBN_NODE_START as x, then an exponent index >= n_exps;
+ *   4. for the literals THAT SOME NODE USES, in index order: SBN_ERR_BAD_ARG for a coordinate >= p, then (again in index order) for
+ *      a point off the table's curve.  An unused literal is not read;
+ *   5. SBN_ERR_WITNESS when all eight candidates fail, naming the first node at which candidate 7 failed and, when that node holds
+ *      no start, that no candidate can mend it. */
+#define SBN_NODE_START 0x7ffffffeu  /* offset only (curve programs): the start the library picks */
+/* The derivation on the host pool, no device: level by level (sbn_program_levels), the nodes of a level side by side, the blinds
+ * beside the outputs; candidate 0 first, after a bad event the whole program again from the next candidate; then the table's own
+ * walk of the list.  num_io is not checked against any table. */
+int sbn_curve_program_instances(int32_t kind, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,
+                                const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out,
+                                uint32_t* values_out, uint8_t* infinity_out, uint8_t* choice_out);
+/* One unit on a prover of the table: count <= the table's num_io (SBN_ERR_BAD_ARG otherwise, after refusals 1 and 2), the rest of
+ * the unit is padded.  On success the loaded trace, the public inputs and ios_out ([num_io][2W + 8]) are, word for word, those of
+ * sbn_prover_generate_trace on the list of sbn_curve_program_instances; a failing call leaves NO trace loaded.  Where the table's
+ * chains run on the device (SBN_TRACEGEN_DEVICE_CHAIN = 1 or 2) the links are resolved there from candidate 0: one launch per level
+ * walks the chains of that level's nodes (one lane or one wave per node), reading a linked operand from the affine outputs an
+ * EARLIER launch left, and a status kernel behind it writes those affine outputs and ONE status word when a node of the level has
+ * a bad event.  The host derives the blinds meanwhile, reads the word after the last level and uploads the negated blinds; the
+ * values are computed on the device and come back with the outputs and the derived list.  A bad event sends the call to the host
+ * derivation, which walks the candidates, and to the explicit path; so does placement 0.  The words are the same in every placement. */
+int sbn_prover_generate_trace_curve_program(sbn_prover* p, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,
+                                            const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* values_out,
+                                            uint8_t* infinity_out, uint8_t* choice_out, uint32_t* ios_out);
+/* Any count, as units of the batch prover's table: proofs_out[units] in unit order, word for word what sbn_batch_prover_prove_ios
+ * gives on the list of sbn_curve_program_instances, which is derived once on the host pool.  Failure rule and guards as
+ * sbn_batch_prover_prove_program. */
+int sbn_batch_prover_prove_curve_program(sbn_batch_prover* b, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,
+                                         const uint32_t* exps, size_t n_exps, sbn_proof** proofs_out, uint32_t* outs_out, uint32_t* values_out,
+                                         uint8_t* infinity_out, uint8_t* choice_out, uint32_t* ios_out);
+/* The check on the public inputs of the unit proofs (host, no device; it verifies NO proof).  After refusals 1 to 3, a null
+ * public_inputs and choice >= SBN_START_CANDIDATES (SBN_ERR_BAD_ARG) it checks units == sbn_msm_num_units(count, num_io) and then,
+ * in instance order: x and offset of a literal operand equal the caller's words; an SBN_NODE_START offset equals candidate
+ * `choice`; a linked x or offset equals the OUTPUT public inputs of node j, across unit boundaries; the exponent is the caller's;
+ * every output limb is in range, every output coordinate < p and every output a point of the curve; every pad instance equals
+ * instance count - 1.  Then the blinds are recomputed from `choice` and the exponents alone: outs_out (optional) = the outputs,
+ * values_out / infinity_out (optional) = out + (-T).  SBN_ERR_VERIFY_FAILED with sbn_last_error naming the first instance, the field
+ * (x, offset, exponent, output) and, for a link, the node it should equal. */
+int sbn_curve_program_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
+                            const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,
+                            const uint32_t* exps, size_t n_exps, uint32_t choice, uint32_t* outs_out, uint32_t* values_out,
+                            uint8_t* infinity_out);
+
 /* One oversized trace split over the GPUs of a node (BASELINE config "Single Fq12 exponentiation proof, trace height
  * 2^18, 8xMI355X with RCCL FRI fold"; reference workload src/fields/fq12/exp.rs:638-696).  One rank per GPU (one process
  * each, or the threads of one process with sbn_local_comm_create); every rank calls the same functions with the same

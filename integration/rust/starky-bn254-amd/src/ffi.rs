@@ -45,6 +45,8 @@ pub struct sbn_program_node {
 }
 pub const SBN_NODE_OUTPUT: u32 = 0x8000_0000;
 pub const SBN_NODE_ONE: u32 = 0x7fff_ffff;
+/// include/sbn.h "Curve programs": offset only, the start the library picks (one per program)
+pub const SBN_NODE_START: u32 = 0x7fff_fffe;
 
 /// the modes of sbn_prover_set_guard / sbn_batch_prover_set_guard / sbn_prove_set_guard
 pub const SBN_GUARD_OFF: u32 = 0;
@@ -229,6 +231,10 @@ extern "C" {
     pub fn sbn_prover_generate_trace_program(p: *mut sbn_prover, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, pi_out: *mut u64, outs_out: *mut u32, ios_out: *mut u32) -> i32;
     pub fn sbn_batch_prover_prove_program(b: *mut sbn_batch_prover, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, proofs_out: *mut *mut sbn_proof, outs_out: *mut u32, ios_out: *mut u32) -> i32;
     pub fn sbn_program_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, nodes: *const sbn_program_node, count: usize, values: *const u32, n_values: usize, exps: *const u32, n_exps: usize, outs_out: *mut u32) -> i32;
+    pub fn sbn_curve_program_instances(kind: i32, nodes: *const sbn_program_node, count: usize, points: *const u32, n_points: usize, exps: *const u32, n_exps: usize, num_io: usize, ios_out: *mut u32, outs_out: *mut u32, values_out: *mut u32, infinity_out: *mut u8, choice_out: *mut u8) -> i32;
+    pub fn sbn_prover_generate_trace_curve_program(p: *mut sbn_prover, nodes: *const sbn_program_node, count: usize, points: *const u32, n_points: usize, exps: *const u32, n_exps: usize, pi_out: *mut u64, outs_out: *mut u32, values_out: *mut u32, infinity_out: *mut u8, choice_out: *mut u8, ios_out: *mut u32) -> i32;
+    pub fn sbn_batch_prover_prove_curve_program(b: *mut sbn_batch_prover, nodes: *const sbn_program_node, count: usize, points: *const u32, n_points: usize, exps: *const u32, n_exps: usize, proofs_out: *mut *mut sbn_proof, outs_out: *mut u32, values_out: *mut u32, infinity_out: *mut u8, choice_out: *mut u8, ios_out: *mut u32) -> i32;
+    pub fn sbn_curve_program_check(kind: i32, num_io: usize, public_inputs: *const *const u64, units: usize, nodes: *const sbn_program_node, count: usize, points: *const u32, n_points: usize, exps: *const u32, n_exps: usize, choice: u32, outs_out: *mut u32, values_out: *mut u32, infinity_out: *mut u8) -> i32;
 
     pub fn sbn_proof_num_words(p: *const sbn_proof) -> usize;
     pub fn sbn_proof_words(p: *const sbn_proof) -> *const u64;

@@ -812,6 +812,39 @@ pub fn prove_program<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: 
     Ok((proofs, outs))
 }
 
+/// A curve program (include/sbn.h, "Curve programs") proved as units of a curve Exp table (`G1ExpStark`, `G2ExpStark`): node g is
+/// instance g = offset + e x, its x a literal of `points` (`n_points` rows) or `SBN_NODE_OUTPUT | j` for the output of an earlier node,
+/// its offset a literal, an earlier output or `SBN_NODE_START`, the start the library picks; its exponent a row of `exps` (`n_exps` rows
+/// of eight u32 words).  The list is derived once on the host pool, cut into units and padded.  Returns the unit proofs as canonical
+/// words in unit order, the values output + (-blind) (`nodes.len()` rows in the word shape of a point), their infinity flags and the
+/// start candidate chosen, which `sbn_curve_program_check` takes.
+pub fn prove_curve_program<S: SbnTable>(stark: &S, config: &StarkConfig, degree_bits: usize, inflight: usize, nodes: &[ffi::sbn_program_node], points: &[u32], n_points: usize, exps: &[u32], n_exps: usize) -> Result<(Vec<Vec<u64>>, Vec<u32>, Vec<u8>, u8)> {
+    let a = air(stark);
+    let cfg = to_sbn_config(config)?;
+    let units = unsafe { ffi::sbn_msm_num_units(nodes.len(), a.num_io as usize) };
+    ensure!(units > 0 && n_points > 0 && n_exps > 0 && points.len() % n_points == 0 && exps.len() == 8 * n_exps, "no node, or points / exps are not n_points / n_exps rows");
+    let mut b = ptr::null_mut();
+    check(unsafe { ffi::sbn_batch_prover_create(&a, &cfg, degree_bits as u32, inflight as u32, &mut b) }, "sbn_batch_prover_create")?;
+    let mut raw = vec![ptr::null_mut(); units];
+    let mut values = vec![0u32; points.len() / n_points * nodes.len()];
+    let mut infinity = vec![0u8; nodes.len()];
+    let mut choice = 0u8;
+    let rc = unsafe {
+        ffi::sbn_batch_prover_prove_curve_program(b, nodes.as_ptr(), nodes.len(), points.as_ptr(), n_points, exps.as_ptr(), n_exps, raw.as_mut_ptr(), ptr::null_mut(), values.as_mut_ptr(), infinity.as_mut_ptr(), &mut choice, ptr::null_mut())
+    };
+    unsafe { ffi::sbn_batch_prover_destroy(b) };
+    check(rc, "sbn_batch_prover_prove_curve_program")?;
+    let proofs = raw
+        .into_iter()
+        .map(|p| {
+            let words = unsafe { std::slice::from_raw_parts(ffi::sbn_proof_words(p), ffi::sbn_proof_num_words(p)) }.to_vec();
+            unsafe { ffi::sbn_proof_free(p) };
+            words
+        })
+        .collect();
+    Ok((proofs, values, infinity, choice))
+}
+
 /// The library's host verifier on canonical proof words (what `verify_stark_proof` above ends in).
 pub fn verify_stark_proof_words<S: SbnTable>(stark: &S, words: &[u64], config: &StarkConfig) -> Result<()> {
     let a = air(stark);

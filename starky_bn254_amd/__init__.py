@@ -15,6 +15,7 @@ from .api import (  # noqa: F401
     START_CANDIDATES, start_candidate, msm_batch_instances_complete,
     BN_P, BN_X, FQ_INVERSE_EXP, FQ_LEGENDRE_EXP, FQ_SQRT_EXP, bn_x, power_instances, power_check, verify_powers, verify_bn_x_powers, fq_sqrt_flags,
     NODE_OUTPUT, NODE_ONE, Program, program_levels, program_instances, program_check, verify_program,
+    NODE_START, CurveProgram, curve_program_instances, curve_program_check, verify_curve_program,
     prover_memory_plan, lde_rows, LDE_STORAGE,
     TRACE_REDUCE, ColumnTable, prove_columns, gather_columns, reduce_words,
     RowTable, trace_from_rows_host, prove_rows,

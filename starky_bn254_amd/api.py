@@ -48,6 +48,7 @@ EXPORTS = [
     "sbn_start_candidate", "sbn_msm_batch_instances_complete", "sbn_prover_generate_trace_msm_batch_complete", "sbn_batch_prover_prove_msm_batch_complete",
     "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
     "sbn_program_levels", "sbn_program_instances", "sbn_prover_generate_trace_program", "sbn_batch_prover_prove_program", "sbn_program_check",
+    "sbn_curve_program_instances", "sbn_prover_generate_trace_curve_program", "sbn_batch_prover_prove_curve_program", "sbn_curve_program_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_coop_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
     "sbn_eval_constraints_host", "sbn_host_curve_chains", "sbn_split_exchange_bytes", "sbn_split_prover_create", "sbn_split_prover_destroy", "sbn_split_prover_generate_trace",
@@ -259,6 +260,10 @@ def lib():
         L.sbn_prover_generate_trace_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]
         L.sbn_batch_prover_prove_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp), vp, vp]
         L.sbn_program_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, vp, sz, vp, sz, vp, sz, vp]
+        L.sbn_curve_program_instances.argtypes = [C.c_int32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.sbn_prover_generate_trace_curve_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.sbn_batch_prover_prove_curve_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp), vp, vp, vp, vp, vp]
+        L.sbn_curve_program_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, vp, sz, vp, sz, vp, sz, u32, vp, vp, vp]
         L.sbn_prove.argtypes = [C.POINTER(_AirDesc), C.POINTER(_Config), vp, u32, vp, sz, C.POINTER(vp)]
         L.sbn_proof_num_words.restype = sz
         L.sbn_proof_num_words.argtypes = [vp]
@@ -1127,6 +1132,131 @@ class Program:
                 np.array(self._exps, dtype=np.uint32).reshape(-1, self.ew))
 
 
+# ---- curve programs (include/sbn.h, "Curve programs") ---------------------------------------------------------------------------
+NODE_START = 0x7FFFFFFE     # offset only, curve programs: the start the library picks (one per program)
+
+
+def _curve_program_args(stark, nodes, points, exps):
+    """nodes (count, 3) uint32 = (x, offset, exp) per node; points (n_points, W) uint32; exps (n_exps, 8) uint32 or a list of Python
+    ints (256 bits, never reduced)."""
+    if getattr(stark, "kind", None) not in (AIR_G1_EXP, AIR_G2_EXP):
+        raise SbnError(-7, "curve programs cover the curve tables G1ExpStark and G2ExpStark")
+    w = _curve_words(stark)
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+    points = np.ascontiguousarray(points, dtype=np.uint32)
+    if not isinstance(exps, np.ndarray) and len(exps) and all(isinstance(e, int) for e in exps):
+        exps = [_int_limbs(e, 8) for e in exps]
+    exps = np.ascontiguousarray(exps, dtype=np.uint32)
+    if nodes.ndim != 2 or nodes.shape[1] != 3 or points.ndim != 2 or points.shape[1] != w or exps.ndim != 2 or exps.shape[1] != 8:
+        raise SbnError(-1, f"nodes must be [count][3], points [n_points][{w}] and exps [n_exps][8] u32")
+    return nodes, points, exps, w
+
+
+def _curve_program_outputs(count, w):
+    """(outs, values, infinity, choice)"""
+    return np.zeros((count, w), dtype=np.uint32), np.zeros((count, w), dtype=np.uint32), np.zeros(count, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+
+
+def curve_program_instances(stark, nodes, points, exps):
+    """A program as instances of the curve table `stark` (sbn_curve_program_instances): node g is instance g = offset + e x, x a
+    literal of `points` or NODE_OUTPUT | j, offset a literal, NODE_OUTPUT | j or NODE_START, the start the library picks (the
+    smallest start_candidate from which no node has a bad event).  Returns (ios_units, outs, values, infinity, choice): the explicit
+    padded list as BatchProver.prove_ios takes it, the table outputs (count, W), the values out + (-blind) with their flags (1: the
+    point at infinity, words zero) and the candidate chosen.  No device needed."""
+    nodes, points, exps, w = _curve_program_args(stark, nodes, points, exps)
+    count = nodes.shape[0]
+    if stark.num_io < 1:
+        raise SbnError(-1, "the table has no instances")
+    units = msm_num_units(count, stark.num_io)
+    ios = np.zeros((units, stark.num_io, 2 * w + 8), dtype=np.uint32)
+    outs, values, infinity, choice = _curve_program_outputs(count, w)
+    _check(lib().sbn_curve_program_instances(stark.kind, _ptr(nodes), count, _ptr(points), points.shape[0], _ptr(exps), exps.shape[0], stark.num_io,
+                                             _ptr(ios), _ptr(outs), _ptr(values), _ptr(infinity), _ptr(choice)))
+    return ios, outs, values, infinity, int(choice[0])
+
+
+def curve_program_check(stark, public_inputs_per_unit, nodes, points, exps, choice):
+    """The check of a curve program (sbn_curve_program_check) on the public inputs of its unit proofs: literals and exponents are
+    the caller's, a NODE_START offset is start candidate `choice`, a linked x or offset equals the output of the node it links to
+    (across units), the pads repeat the last instance, every output is a point of the curve.  Returns (outs, values, infinity), the
+    values from the blinds recomputed from `choice` and the exponents; raises SbnError(-6) naming the first instance and field that
+    breaks.  Verifies NO proof: verify_curve_program does both."""
+    nodes, points, exps, w = _curve_program_args(stark, nodes, points, exps)
+    pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
+    outs, values, infinity, _ = _curve_program_outputs(nodes.shape[0], w)
+    if not 0 <= int(choice) < 2 ** 32:
+        raise SbnError(-1, f"choice {choice}: there are {START_CANDIDATES} start candidates")
+    _check(lib().sbn_curve_program_check(stark.kind, stark.num_io, ptrs, n, _ptr(nodes), nodes.shape[0], _ptr(points), points.shape[0],
+                                         _ptr(exps), exps.shape[0], int(choice), _ptr(outs), _ptr(values), _ptr(infinity)))
+    return outs, values, infinity
+
+
+class CurveProgram:
+    """A small builder of programs for the curve table `stark`.  point(P) and mul / add / lincomb return handles; a handle or a
+    literal point (W uint32 words) is accepted wherever an operand is.  Equal literals share one slot of `points`, equal exponents
+    one slot of `exps`.  arrays() gives (nodes, points, exps) as curve_program_instances, Prover.generate_trace_curve_program,
+    BatchProver.prove_curve_program and verify_curve_program take them; a node handle h is node h.node, and values[h.node] of those
+    calls is the point the handle stands for."""
+
+    START = Program.Handle(NODE_START)
+
+    def __init__(self, stark):
+        self.stark = stark
+        self.w = _curve_words(stark)
+        self._points, self._point_slot, self._exps, self._exp_slot, self._nodes = [], {}, [], {}, []
+
+    def point(self, p):
+        """A literal point: W uint32 words.  Equal literals share one slot."""
+        if isinstance(p, Program.Handle):
+            return p
+        key = tuple(int(t) for t in np.asarray(p).reshape(-1))
+        if len(key) != self.w:
+            raise SbnError(-1, f"a point has {self.w} u32 words")
+        if key not in self._point_slot:
+            self._point_slot[key] = len(self._points)
+            self._points.append(list(key))
+        return Program.Handle(self._point_slot[key])
+
+    def _exp(self, e):
+        key = tuple(_int_limbs(int(e), 8)) if isinstance(e, (int, np.integer)) else tuple(int(t) for t in np.asarray(e).reshape(-1))
+        if len(key) != 8:
+            raise SbnError(-1, "an exponent has 8 u32 words")
+        if key not in self._exp_slot:
+            self._exp_slot[key] = len(self._exps)
+            self._exps.append(list(key))
+        return self._exp_slot[key]
+
+    def mul(self, x, e, offset=START):
+        """The node offset + e x (offset START: the value of the node is e x); e a Python int below 2^256, or its 8 words."""
+        x = self.point(x)
+        if x.ref == NODE_START:
+            raise SbnError(-1, "START is an offset, not an x")
+        self._nodes.append((x.ref, self.point(offset).ref, self._exp(e)))
+        g = len(self._nodes) - 1
+        return Program.Handle(NODE_OUTPUT | g, g)
+
+    def add(self, a, b):
+        """The sum a + b: mul(b, 1, offset=a)."""
+        return self.mul(b, 1, offset=a)
+
+    def lincomb(self, terms):
+        """The sum of e x over terms = [(e, x), ...], one node per term, each continuing from the one before it."""
+        acc = CurveProgram.START
+        for e, x in terms:
+            acc = self.mul(x, e, offset=acc)
+        if acc is CurveProgram.START:
+            raise SbnError(-1, "no term")
+        return acc
+
+    def __len__(self):
+        return len(self._nodes)
+
+    def arrays(self):
+        """(nodes (count, 3), points (n_points, W), exps (n_exps, 8)), uint32."""
+        return (np.array(self._nodes, dtype=np.uint32).reshape(-1, 3), np.array(self._points, dtype=np.uint32).reshape(-1, self.w),
+                np.array(self._exps, dtype=np.uint32).reshape(-1, 8))
+
+
 def fq_sqrt_flags(xs, roots):
     """Per element, whether root^2 == x in Fq: what a caller of FqExpStark with FQ_SQRT_EXP checks, because x^((p+1)/4) is a square
     root only when x is a square (a non-residue gives a root of -x: not an error, the flag is False).  xs, roots: Python ints or
@@ -1902,6 +2032,19 @@ class Prover:
                                                        _ptr(pi), _ptr(outs), _ptr(ios)))
         return pi, outs, ios
 
+    def generate_trace_curve_program(self, nodes, points, exps):
+        """generate_trace on the one-unit list curve_program_instances(stark, nodes, points, exps) gives (count <= num_io, the rest
+        padded); where the table's chains run on the device the links are resolved there, one launch per level, from start
+        candidate 0, and a bad event falls back to the host derivation.  Returns (public inputs, outs, values, infinity, choice,
+        ios).  A failing call leaves no trace loaded."""
+        nodes, points, exps, w = _curve_program_args(self.stark, nodes, points, exps)
+        pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
+        outs, values, infinity, choice = _curve_program_outputs(nodes.shape[0], w)
+        ios = np.zeros((self.stark.num_io, 2 * w + 8), dtype=np.uint32)
+        _check(lib().sbn_prover_generate_trace_curve_program(self._h, _ptr(nodes), nodes.shape[0], _ptr(points), points.shape[0], _ptr(exps), exps.shape[0],
+                                                             _ptr(pi), _ptr(outs), _ptr(values), _ptr(infinity), _ptr(choice), _ptr(ios)))
+        return pi, outs, values, infinity, int(choice[0]), ios
+
     def read_trace(self):
         trace = np.zeros((self.stark.num_columns, 1 << self.degree_bits), dtype=np.uint64)
         _check(lib().sbn_prover_read_trace(self._h, _ptr(trace)))
@@ -2212,6 +2355,17 @@ class BatchProver:
                                                     out, _ptr(outs), _ptr(ios)))
         return self._proofs(out, len(ios)), outs, ios
 
+    def prove_curve_program(self, nodes, points, exps):
+        """A curve program of any count (arguments as curve_program_instances) proved as units of the table, the last one padded
+        (sbn_batch_prover_prove_curve_program).  Returns (proofs, outs, values, infinity, choice, ios)."""
+        nodes, points, exps, w = _curve_program_args(self.stark, nodes, points, exps)
+        count = nodes.shape[0]
+        ios, out = self._unit_buffers(count, 2 * w + 8)
+        outs, values, infinity, choice = _curve_program_outputs(count, w)
+        _check(lib().sbn_batch_prover_prove_curve_program(self._h, _ptr(nodes), count, _ptr(points), points.shape[0], _ptr(exps), exps.shape[0],
+                                                          out, _ptr(outs), _ptr(values), _ptr(infinity), _ptr(choice), _ptr(ios)))
+        return self._proofs(out, len(ios)), outs, values, infinity, int(choice[0]), ios
+
     def close(self):
         if self._h:
             lib().sbn_batch_prover_destroy(self._h)
@@ -2353,6 +2507,16 @@ def verify_program(stark, config, proofs, nodes, values, exps, verifier=None):
     proofs = list(proofs)
     _verify_units(stark, config, proofs, verifier)
     return program_check(stark, [p.public_inputs() for p in proofs], nodes, values, exps)
+
+
+def verify_curve_program(stark, config, proofs, nodes, points, exps, choice, verifier=None):
+    """Verifies the unit proofs of BatchProver.prove_curve_program (host verifier, or a Verifier of the table in batches) and then
+    runs curve_program_check on their public inputs.  Returns (values, infinity); raises SbnError when a unit is rejected (naming
+    the unit) or the check fails (naming the instance and field)."""
+    proofs = list(proofs)
+    _verify_units(stark, config, proofs, verifier)
+    _, values, infinity = curve_program_check(stark, [p.public_inputs() for p in proofs], nodes, points, exps, choice)
+    return values, infinity
 
 
 def verify_bn_x_powers(stark, config, proofs, fs, verifier=None):

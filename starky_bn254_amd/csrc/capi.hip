@@ -334,6 +334,18 @@ int sbn_batch_prover_prove_program(sbn_batch_prover* B, const sbn_program_node* 
   });
 }
 
+// Curve programs of any count (include/sbn.h, "Curve programs"; csrc/curve_program.hip): the start, every link, the outputs and the
+// values are derived with the list.
+int sbn_batch_prover_prove_curve_program(sbn_batch_prover* B, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,
+                                         const uint32_t* exps, size_t n_exps, sbn_proof** proofs_out, uint32_t* outs_out, uint32_t* values_out,
+                                         uint8_t* infinity_out, uint8_t* choice_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const bool fits = count && count < 0x7fffffffu && exp_io_words(B->kind);   // (what does not fit has no unit count: sbn_curve_program_instances refuses it)
+  return prove_derived_units(B, fits ? sbn_msm_num_units(count, B->num_io) : 0, ios_out, proofs_out, [&](uint32_t* ios) {
+    return sbn_curve_program_instances(B->kind, nodes, count, points, n_points, exps, n_exps, B->num_io, ios, outs_out, values_out, infinity_out, choice_out);
+  });
+}
+
 // Batches of short MSMs of any total length (include/sbn.h, "Batches of short MSMs"; csrc/msm_batch.hip): a segment that straddles
 // two units needs no context to wait for another.
 int sbn_batch_prover_prove_msm_batch(sbn_batch_prover* B, const uint32_t* terms, const uint64_t* lengths, size_t segments, const uint32_t* starts, size_t start_count,

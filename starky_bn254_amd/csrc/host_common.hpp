@@ -221,6 +221,13 @@ struct ProgramPlan {
 };
 int program_plan(int kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values, const uint32_t* exps, size_t n_exps,
                  size_t num_io, ProgramPlan& plan);
+// curve_program.hip (include/sbn.h, "Curve programs"): refusals 1 to 4 of the header in its order and the schedule of
+// sbn_program_levels as a ProgramPlan; the negated blinds -T_g of the nodes from candidate `choice` ([count][16E] u32 affine words,
+// zero where flag[g] = 1: T_g is the point at infinity), level by level on the host pool
+int curve_program_plan(int kind, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points, const uint32_t* exps, size_t n_exps,
+                       size_t num_io, ProgramPlan& plan);
+void curve_program_neg_blinds(int E, const ProgramPlan& plan, const sbn_program_node* nodes, const uint32_t* exps, unsigned choice, uint32_t* neg_blinds,
+                              uint8_t* flag);
 // msm_batch.hip (segmented chained lists; a chained list is one segment): the argument refusals in the header's order (a null
 // `*starts` becomes the generator / one with *start_count = 1; *M_out = the sum of the lengths); the refusals of the values, naming
 // the global instance and its segment; the derivation of `total` >= M rows of ios (rows past M repeat row M - 1), the finals and on

@@ -1550,6 +1550,197 @@ __global__ void __launch_bounds__(320) fq12_program_level_kernel(uint32_t* ios, 
   }
 }
 
+// ---- curve programs (sbn_prover_generate_trace_curve_program): x and offset of an instance = a literal point, the start, or the ------
+// ---- output of an earlier instance --------------------------------------------------------------------------------------------------
+// The field programs above on G1 / G2 (E = 1 / 2).  The host sorts the nodes by level, so the nodes of one level are independent
+// and every node they link to lies in an EARLIER level.  Per level TWO launches, ordered by their kernel boundary:
+//   curve_program_level_kernel       one LANE per node of the level (placement 1), the chain step of chain_kernel / exp_chains;
+//   curve_program_level_coop_kernel  one WAVE per node of the level (placement 2), the chain step of chain_coop_kernel;
+//     both copied, not shared, so the code objects of the explicit-list kernels stay as they are.  The new part is the head: an
+//     operand whose node word has bit 31 set is the affine output of node j, which an earlier LAUNCH left in `outs` ([K][16E]
+//     u32, the word order of a point in `ios`); its words go into the x or offset words of the node's own `ios` row (for the row,
+//     flag and download kernels that follow) and enter the chain from those registers.  A literal, or the start, loads from
+//     `ios`, where the host put it.  The chain's own degenerate flags go to a word nobody reads: the status kernel finds them.
+//   curve_program_status_kernel      one lane per (node of the level, step t <= 256), the verdict of chain_seg_status_kernel: a bad
+//     event of the table's walk is B[t] at infinity or, at a set bit, B[t] = +-A[t].  A lane that meets one ORs into the ONE status
+//     word; a clean level stores nothing there.  The lane of t = 256 also turns B[256] into its affine form (one Fermat chain) and
+//     writes outs[k] -- zeros for an output at infinity, which the status word reports.
+// Links cross kernel boundaries only: a launch writes ja / jb / the ios row / outs of its OWN nodes and reads outs[j] of nodes of
+// earlier levels, and the status kernel reads the chains the launch in front of it stored.  Nothing a launch stores to global
+// memory is read again inside it -- no flag, no spin, no fence (the rule of fq12_program_level_kernel).  A node with a bad event
+// leaves garbage behind it; the arithmetic is total (no index depends on a value) and the host drops everything when the status
+// word is set.  The pads are nodes of the level of node count - 1 (the host repeats its node words), so they need no kernel.
+//   nodes: [K][3] = (x, offset, exp) of include/sbn.h's sbn_program_node; order: the node of item i of this launch (every entry
+//   < K and every link j < its node: curve_program_plan, curve_program.hip, refuses anything else before a launch)
+template <int E>
+__device__ __forceinline__ Co<E> program_operand(uint32_t* io8, uint32_t src, const uint32_t* outs, int w) {   // coordinate w (0: x, 1: y) of one operand
+  Co<E> r; u64 t4[4];
+#pragma unroll   // (r.c[q] under a rolled loop is an indexed stack object: scratch)
+  for (int q = 0; q < E; q++) {
+    uint32_t* dst = io8 + 8 * (w * E + q);
+    if (src & 0x80000000u) {
+      const uint32_t* o = outs + 16 * E * (size_t)(src & 0x7fffffffu) + 8 * (w * E + q);
+      for (int i = 0; i < 4; i++) {
+        const uint32_t lo = o[2 * i], hi = o[2 * i + 1];
+        dst[2 * i] = lo; dst[2 * i + 1] = hi;
+        t4[i] = (u64)lo | ((u64)hi << 32);
+      }
+    } else u32x8_to_u64x4(dst, t4);
+    r.c[q] = to_m(t4);
+  }
+  return r;
+}
+template <int E>
+__global__ void __launch_bounds__(64) curve_program_level_kernel(uint32_t* ios, const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ order, size_t count,
+                                                                 u64* __restrict__ ja, u64* __restrict__ jb, const uint32_t* outs, int* __restrict__ err) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const size_t k = order[i];
+  uint32_t* io = ios + 8 * (4 * E + 1) * k;
+  Jac<E> a, b;
+  a.X = program_operand<E>(io, nodes[3 * k], outs, 0); a.Y = program_operand<E>(io, nodes[3 * k], outs, 1);
+  b.X = program_operand<E>(io + 16 * E, nodes[3 * k + 1], outs, 0); b.Y = program_operand<E>(io + 16 * E, nodes[3 * k + 1], outs, 1);
+  a.Z = cone<E>(); b.Z = cone<E>();
+  const uint32_t* e = io + 32 * E;
+  int bad = 0;
+  for (int t = 0;; t++) {   // exp_chains (bn254w.cuh) from here on
+    stc<E>(ja + jac_at<E>(k, t, 0), a.X); stc<E>(ja + jac_at<E>(k, t, 1), a.Y); stc<E>(ja + jac_at<E>(k, t, 2), a.Z);
+    stc<E>(jb + jac_at<E>(k, t, 0), b.X); stc<E>(jb + jac_at<E>(k, t, 1), b.Y); stc<E>(jb + jac_at<E>(k, t, 2), b.Z);
+    if (t == 256) break;
+    const bool bit = (e[t >> 5] >> (t & 31)) & 1;
+    if (bit) { bool deg; b = jac_add<E>(b, a, &deg); if (deg) bad |= TG_ERR_DEGENERATE; }
+    if (czero<E>(a.Y)) bad |= TG_ERR_DEGENERATE;
+    a = jac_double<E>(a);
+  }
+  if (bad) atomicOr(err, bad);
+}
+template <int E>
+__global__ void __launch_bounds__(CP_LANES) curve_program_level_coop_kernel(uint32_t* ios, const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ order,
+                                                                            u64* __restrict__ ja, u64* __restrict__ jb, const uint32_t* outs, int* __restrict__ err,
+                                                                            ChainProgDev cp) {
+  __shared__ Fq V[CP_MAX_SLOTS];
+  __shared__ uint32_t prog[2][24 * CP_LANES];
+  const size_t k = order[blockIdx.x];
+  const int lane = threadIdx.x;
+  for (int b = 0; b < 2; b++) for (int lv = 0; lv < cp.levels[b]; lv++) prog[b][lv * CP_LANES + lane] = cp.ops[b][lv * CP_LANES + lane];
+  uint32_t* io = ios + 8 * (4 * E + 1) * k;
+  if (lane < 4 * E) {   // lane = (operand, coordinate, component): x.x x.y offset.x offset.y, E each, as in the io words
+    const uint32_t src = nodes[3 * k + lane / (2 * E)];
+    uint32_t* w8 = io + 8 * lane;
+    u64 t4[4];
+    if (src & 0x80000000u) {   // the link: affine output of node j (an earlier launch) -> x / offset of this node
+      const uint32_t* o = outs + 16 * E * (size_t)(src & 0x7fffffffu) + 8 * (lane % (2 * E));
+      uint32_t v[8];
+      for (int i = 0; i < 8; i++) v[i] = o[i];
+      for (int i = 0; i < 8; i++) w8[i] = v[i];
+      for (int i = 0; i < 4; i++) t4[i] = (u64)v[2 * i] | ((u64)v[2 * i + 1] << 32);
+    } else u32x8_to_u64x4(w8, t4);
+    V[cp.in_slot[lane]] = to_m(t4);
+  }
+  if (lane >= 32 && lane < 34) V[cp.one_slot[lane - 32]] = fq_one();
+  if (E == 2 && lane >= 40 && lane < 42) V[cp.zero_slot[lane - 40]] = Fq{{0, 0, 0, 0}};
+  __syncthreads();
+  // the exponent words, before the walk: the row is this workgroup's own and only its operand words were written above
+  const uint32_t* e = io + 32 * E;
+  for (int t = 0;; t++) {   // chain_coop_kernel from here on
+    if (lane < 6 * E) {
+      const int which = lane / (3 * E), cc = (lane % (3 * E)) / E, q = lane % E;
+      const Fq v = V[cp.coord[lane]];
+      u64* dst = (which ? jb : ja) + jac_at<E>(k, t, cc) + 4 * q;
+      for (int i = 0; i < 4; i++) dst[i] = v.l[i];
+    }
+    if (t == 256) break;
+    const int bit = (e[t >> 5] >> (t & 31)) & 1;
+    const uint32_t* ops = prog[bit];
+    const int nl = cp.levels[bit];
+    for (int lv = 0; lv < nl; lv++) {
+      const uint32_t op = ops[lv * CP_LANES + lane];
+      const int kind = op & 255, d = (op >> 8) & 255, a = (op >> 16) & 255, b = op >> 24;
+      if (kind == CP_MUL) V[d] = mmul(V[a], V[b]);
+      else if (kind == CP_ADD) V[d] = fadd(V[a], V[b]);
+      else if (kind == CP_SUB) V[d] = fsub(V[a], V[b]);
+      else if (kind == CP_COPY) V[d] = V[a];
+      else if (kind == CP_CHK1) { if (fzero(V[a])) atomicOr(err, TG_ERR_DEGENERATE); }
+      else if (kind == CP_CHK2) { if (fzero(V[a]) && fzero(V[b])) atomicOr(err, TG_ERR_DEGENERATE); }
+      __syncthreads();
+    }
+  }
+}
+template <int E>
+__global__ void __launch_bounds__(256) curve_program_status_kernel(const uint32_t* __restrict__ ios, const uint32_t* __restrict__ order, size_t count,
+                                                                   const u64* __restrict__ ja, const u64* __restrict__ jb, uint32_t* __restrict__ outs,
+                                                                   int* __restrict__ status) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= count * 257) return;
+  const size_t k = order[i / 257]; const int t = (int)(i % 257);
+  const Co<E> Z2 = ldc<E>(jb + jac_at<E>(k, t, 2));
+  bool bad = czero<E>(Z2);
+  if (!bad && t < 256 && ((ios[8 * (4 * E + 1) * k + 32 * E + (t >> 5)] >> (t & 31)) & 1)) {
+    const Co<E> Z1 = ldc<E>(ja + jac_at<E>(k, t, 2));
+    const Co<E> D = csub(cmul(ldc<E>(jb + jac_at<E>(k, t, 0)), cmul(Z1, Z1)), cmul(ldc<E>(ja + jac_at<E>(k, t, 0)), cmul(Z2, Z2)));
+    bad = czero<E>(Z1) || czero<E>(D);
+  }
+  if (bad) atomicOr(status, 1);
+  if (t != 256) return;
+  Co<E> v[2];
+  if (bad) { v[0] = Z2; v[1] = Z2; }   // the point at infinity has no affine form: zeros, and the status word says so
+  else {
+    const Co<E> zi = cinv_from_norm(Z2, finv_fermat(cnorm(Z2))), zi2 = cmul(zi, zi);
+    v[0] = cmul(ldc<E>(jb + jac_at<E>(k, 256, 0)), zi2); v[1] = cmul(ldc<E>(jb + jac_at<E>(k, 256, 1)), cmul(zi2, zi));
+  }
+  for (int c = 0; c < 2; c++)
+    for (int q = 0; q < E; q++) {
+      u64 s[4]; from_m(v[c].c[q], s);
+      for (int w = 0; w < 8; w++) outs[16 * E * k + 8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+    }
+}
+// values[i] = out_i + (-T_i), i < K real nodes, behind affine_lambda_kernel: scalar_mul_unoffset_kernel with the subtrahend from
+// `neg_blinds` ([K][16E] u32 affine words of -T_i, uploaded by the host; blind_inf[i] = 1: T_i is the point at infinity and the
+// value is the output itself) instead of the instance's own offset words.  Outputs, `jp`, the batched inversion and the flags as there.
+template <int E>
+__global__ void curve_program_values_kernel(size_t K, const u64* __restrict__ outs, const uint32_t* __restrict__ neg_blinds, const unsigned char* __restrict__ blind_inf,
+                                            u64* __restrict__ jp, uint32_t* __restrict__ values, unsigned char* __restrict__ infinity) {
+  const size_t W = 16 * E;
+  const size_t L = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
+  if (L >= NL) return;
+  Fq nrm[TG_INV_BATCH];
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = L + (size_t)j * NL;
+    nrm[j] = fq_one();
+    if (i >= K) continue;
+    Jac<E> o, m; u64 t4[4];
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        const u64* src = outs + W * i + 8 * (c * E + q);
+        for (int h = 0; h < 4; h++) t4[h] = (src[2 * h] & 0xffffffffULL) | (src[2 * h + 1] << 32);
+        (c ? o.Y : o.X).c[q] = to_m(t4);
+        u32x8_to_u64x4(neg_blinds + W * i + 8 * (c * E + q), t4);
+        (c ? m.Y : m.X).c[q] = to_m(t4);
+      }
+    o.Z = cone<E>(); m.Z = o.Z;
+    const Jac<E> r = blind_inf[i] ? o : jac_add_complete<E>(o, m);
+    st_jac<E>(jp + 12 * E * i, r);
+    if (!czero<E>(r.Z)) nrm[j] = cnorm(r.Z);
+  }
+  batch_inverse(nrm);
+  for (int j = 0; j < TG_INV_BATCH; j++) {
+    const size_t i = L + (size_t)j * NL;
+    if (i >= K) continue;
+    const Jac<E> p = ld_jac<E>(jp + 12 * E * i);
+    const bool inf = czero<E>(p.Z);
+    Co<E> v[2];
+    if (inf) { v[0] = p.Z; v[1] = p.Z; }   // the point at infinity: zero words and its flag
+    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
+    for (int c = 0; c < 2; c++)
+      for (int q = 0; q < E; q++) {
+        u64 s[4]; from_m(v[c].c[q], s);
+        for (int w = 0; w < 8; w++) values[W * i + 8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+      }
+    infinity[i] = inf ? 1 : 0;
+  }
+}
+
 // ---- parity hook (sbn_bn254_fq_batch, tracegen_device.hip): the field helpers above on standard-form operands, 4 words per element --------------
 enum { FQB_MUL = 0, FQB_ADD = 1, FQB_SUB = 2, FQB_INV = 3, FQB_BATCH_INV = 4, FQB_FQ2_INV = 5 };
 // Item i of op: element i, or group i of TG_INV_BATCH elements for FQB_BATCH_INV.  FQB_INV is finv_fermat on the device and inv_std on

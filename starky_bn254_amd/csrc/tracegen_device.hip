@@ -152,6 +152,14 @@ struct PowerIn { const uint32_t* bases; const uint32_t* exps; size_t exp_count, 
 // programs").
 struct ProgramIn { const sbn_program_node* nodes; size_t count; const uint32_t* values; const uint32_t* exps; uint32_t* outs_out; uint32_t* ios_out; };
 
+// sbn_prover_generate_trace_curve_program: `count` nodes on a curve table whose chains run on the device; x and offset of a node
+// are a literal of `points`, the start (candidate 0), or the output of an earlier node, resolved on the device level by level
+// (kernels_tracegen.cuh, "curve programs"); the values output + (-blind) are computed there from the blinds the host derives.
+struct CurveProgramIn {
+  const sbn_program_node* nodes; size_t count; const uint32_t* points; const uint32_t* exps;
+  uint32_t* outs_out; uint32_t* values_out; uint8_t* infinity_out; uint32_t* ios_out;
+};
+
 // sbn_prover_generate_trace_msm_batch: one unit of `segments` chained lists, M real instances and num_io - M pads; the offsets are
 // derived on the device from the terms, the heads and the starts (kernels_tracegen.cuh, "segmented chained lists"), the finals
 // are the instance outputs at the segment tails and, on the curves, the sums final + (-start) are computed there too.
@@ -334,19 +342,24 @@ struct CurveJob : TraceJob {
   // 1 = one lane per instance (tg::chain_kernel, 13 ms), 0 = host_chains()
   int launch_chains(int* errw) {
     if (P->chain_mode == 2) {
-      static const ChainProgram prog = build_chain_program(E);
-      if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
       tg::ChainProgDev cp{};
-      for (int b = 0; b < 2; b++) {
-        HIPC(hipMemcpyAsync(d_prog[b], prog.ops[b].data(), prog.ops[b].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        cp.ops[b] = d_prog[b]; cp.levels[b] = prog.levels[b];
-      }
-      for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) cp.in_slot[v * E + q] = (unsigned char)((v < 2 ? v : v + 1) * E + q);   // a.X a.Y | b.X b.Y
-      cp.one_slot[0] = (unsigned char)(2 * E); cp.one_slot[1] = (unsigned char)(5 * E);
-      cp.zero_slot[0] = (unsigned char)(2 * E + 1); cp.zero_slot[1] = (unsigned char)(5 * E + 1);
-      for (int i = 0; i < 6 * E; i++) cp.coord[i] = (unsigned char)i;
+      if (int rc = upload_chain_program(cp)) return rc;
       hipLaunchKernelGGL(tg::chain_coop_kernel<E>, dim3((unsigned)K), dim3(tg::CP_LANES), 0, st, d_ios, K, ja, jb, errw, cp);
     } else hipLaunchKernelGGL(tg::chain_kernel<E>, blocks(K, 64), dim3(64), 0, st, d_ios, K, ja, jb, errw);
+    return 0;
+  }
+  // the chain step as levels of micro-operations (build_chain_program) in d_prog, and the slots the one-wave kernels read and write
+  int upload_chain_program(tg::ChainProgDev& cp) {
+    static const ChainProgram prog = build_chain_program(E);
+    if (prog.levels[0] <= 0 || prog.levels[0] > 24 || prog.levels[1] > 24) return fail(SBN_ERR_UNSUPPORTED, "internal: chain program does not fit");
+    for (int b = 0; b < 2; b++) {
+      HIPC(hipMemcpyAsync(d_prog[b], prog.ops[b].data(), prog.ops[b].size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      cp.ops[b] = d_prog[b]; cp.levels[b] = prog.levels[b];
+    }
+    for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) cp.in_slot[v * E + q] = (unsigned char)((v < 2 ? v : v + 1) * E + q);   // a.X a.Y | b.X b.Y
+    cp.one_slot[0] = (unsigned char)(2 * E); cp.one_slot[1] = (unsigned char)(5 * E);
+    cp.zero_slot[0] = (unsigned char)(2 * E + 1); cp.zero_slot[1] = (unsigned char)(5 * E + 1);
+    for (int i = 0; i < 6 * E; i++) cp.coord[i] = (unsigned char)i;
     return 0;
   }
   // host threads while the device writes the input-independent columns, then a pinned upload
@@ -587,6 +600,83 @@ static int curve_trace_segmented(sbn_prover* P, const BatchIn& mb, size_t K, uin
     for (size_t s = 0; s < S; s++) for (int i = 0; i < 16 * E; i++) mb.finals_out[16 * E * s + i] = (uint32_t)J.h_out[16 * E * aux[K + s] + i];
   if (rc == SBN_OK && mb.sums_out) memcpy(mb.sums_out, h_sums, 16 * E * S * sizeof(uint32_t));
   if (rc == SBN_OK && mb.infinity_out) memcpy(mb.infinity_out, h_sums + 8 * E * S, S);
+  return rc;
+}
+
+// programs: the literals, the start (candidate 0) and the exponents of every node go up in place (zeros where a link will be
+// resolved; a pad row repeats the node words of node count - 1 and runs as one more node of its level) with the node table and
+// the nodes sorted by level; per level one launch walks the chains and a status kernel behind it writes the affine outputs the
+// next level links to and the one status word (kernels_tracegen.cuh, "curve programs").  The host derives the negated blinds
+// while the levels run, reads the status word and uploads them; the values out + (-blind) are computed where the scalar
+// multiplications compute their products, and outputs, values and the derived list come back in the one download.
+// *fallback (with SBN_OK, nothing loaded): a node has a bad event under candidate 0; the caller derives on the host pool.
+template <int E>
+static int curve_trace_program(sbn_prover* P, const CurveProgramIn& pr, const ProgramPlan& plan, size_t K, uint64_t* pi_out, bool* fallback) {
+  const size_t W = 16 * E, IOW = 2 * W + 8, M = pr.count, depth = plan.depth();
+  const uint32_t* sw = curve_start_candidate_words(E, 0);
+  std::vector<uint32_t> prelim(IOW * K, 0u), aux(4 * K), start(depth + 1, 0);   // aux: the node table [K][3], then the order [K]
+  for (size_t g = 0; g < K; g++) {
+    const sbn_program_node& nd = pr.nodes[g < M ? g : M - 1];
+    uint32_t* io = prelim.data() + IOW * g;
+    if (!(nd.x & SBN_NODE_OUTPUT)) memcpy(io, pr.points + W * nd.x, W * sizeof(uint32_t));
+    if (nd.offset == SBN_NODE_START) memcpy(io + W, sw, W * sizeof(uint32_t));
+    else if (!(nd.offset & SBN_NODE_OUTPUT)) memcpy(io + W, pr.points + W * nd.offset, W * sizeof(uint32_t));
+    memcpy(io + 2 * W, pr.exps + 8 * nd.exp, 8 * sizeof(uint32_t));
+    aux[3 * g] = nd.x; aux[3 * g + 1] = nd.offset; aux[3 * g + 2] = nd.exp;
+    start[plan.level[g < M ? g : M - 1] + 1]++;
+  }
+  for (size_t l = 0; l < depth; l++) start[l + 1] += start[l];   // the counting sort of curve_program_plan again, the pads included
+  {
+    std::vector<uint32_t> next(start.begin(), start.end() - 1);
+    for (size_t g = 0; g < K; g++) aux[3 * K + next[plan.level[g < M ? g : M - 1]]++] = (uint32_t)g;
+  }
+  HIPC(hipSetDevice(P->device));
+  CurveJob<E> J(P, K);
+  J.carve_products(M);
+  uint32_t* d_aux = (uint32_t*)J.take(2 * K + 1);
+  uint32_t* d_pout = (uint32_t*)J.take(8 * E * K + 1);       // the affine outputs the links read: [K][16E] u32
+  uint32_t* d_neg = (uint32_t*)J.take(8 * E * M + 1);        // -T of every node, and whether T is the point at infinity
+  unsigned char* d_tinf = (unsigned char*)J.take(M / 8 + 1);
+  int* d_status = (int*)J.take(1);                           // [0]: the status word; [1]: the chains' own flags, which nobody reads
+  const size_t blind_words = 8 * E * M + (M + 7) / 8;        // pinned, u64 words: the list, then -T and its flags go up; the
+  if (int rc = J.ready(J.list_words + blind_words, J.list_words + blind_words + 1)) return rc;   // list, the values and their flags, the status word come back
+  uint32_t* h_neg = (uint32_t*)(P->h_io + J.list_words);
+  uint8_t* h_tinf = (uint8_t*)(P->h_io + J.list_words + 8 * E * M);
+  const uint32_t* ios = (const uint32_t*)J.h_back();
+  u64* const h_vals = J.h_back() + J.list_words;
+  int* const h_status = (int*)(h_vals + blind_words);
+  if (int rc = J.upload_list(prelim.data())) return rc;
+  HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+  HIPC(hipMemsetAsync(d_status, 0, 2 * sizeof(int), J.st));
+  tg::ChainProgDev cp{};
+  if (P->chain_mode == 2) if (int rc = J.upload_chain_program(cp)) return rc;
+  for (size_t l = 0; l < depth; l++) {   // the kernel boundary between two levels is the link: level l reads what levels < l stored
+    const size_t cnt = start[l + 1] - start[l];
+    const uint32_t* d_order = d_aux + 3 * K + start[l];
+    if (P->chain_mode == 2) hipLaunchKernelGGL(tg::curve_program_level_coop_kernel<E>, dim3((unsigned)cnt), dim3(tg::CP_LANES), 0, J.st, J.d_ios, d_aux, d_order, J.ja, J.jb, d_pout, d_status + 1, cp);
+    else hipLaunchKernelGGL(tg::curve_program_level_kernel<E>, blocks(cnt, 64), dim3(64), 0, J.st, J.d_ios, d_aux, d_order, cnt, J.ja, J.jb, d_pout, d_status + 1);
+    hipLaunchKernelGGL(tg::curve_program_status_kernel<E>, blocks(cnt * 257, 256), dim3(256), 0, J.st, J.d_ios, d_order, cnt, J.ja, J.jb, d_pout, d_status);
+  }
+  J.mark("curve_program_levels");
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h_status, d_status, sizeof(int), hipMemcpyDeviceToHost, J.st));
+  curve_program_neg_blinds(E, plan, pr.nodes, pr.exps, 0, h_neg, h_tinf);   // on the host pool, while the levels run
+  HIPC(hipStreamSynchronize(J.st));
+  if (*h_status) { *fallback = true; return J.end(); }
+  HIPC(hipMemcpyAsync(d_neg, h_neg, W * M * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
+  HIPC(hipMemcpyAsync(d_tinf, h_tinf, M, hipMemcpyHostToDevice, J.st));
+  J.common_columns();
+  J.affine_lambda();
+  hipLaunchKernelGGL(tg::curve_program_values_kernel<E>, blocks((M + tg::TG_INV_BATCH - 1) / tg::TG_INV_BATCH, 64), dim3(64), 0, J.st, M, J.d_out, d_neg, d_tinf, J.jp, J.prod, J.inf);
+  J.mark("curve_program_values");
+  if (int rc = J.witness_and_range_check()) return rc;
+  if (int rc = J.download_list(J.h_back())) return rc;
+  if (int rc = J.download_products(h_vals)) return rc;
+  const int rc = J.publish(ios, pi_out, pr.ios_out);
+  if (rc == SBN_OK && pr.outs_out)   // the instance outputs: one u32 limb per u64 word
+    for (size_t i = 0; i < W * M; i++) pr.outs_out[i] = (uint32_t)J.h_out[i];
+  if (rc == SBN_OK && pr.values_out) memcpy(pr.values_out, h_vals, W * M * sizeof(uint32_t));
+  if (rc == SBN_OK && pr.infinity_out) memcpy(pr.infinity_out, h_vals + 8 * E * M, M);
   return rc;
 }
 
@@ -1047,7 +1137,38 @@ extern "C" int sbn_prover_generate_trace_program(sbn_prover* P, const sbn_progra
   return fq12_trace_program(P, pr, plan, num_io, pi_out);
 }
 
-extern "C" int sbn_bn254_fq_batch(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
+// sbn_prover_generate_trace on the one-unit list sbn_curve_program_instances derives from (nodes, points, exps).  Where the chains
+// run on the device the links are resolved there from candidate 0; a bad event there, like placement 0, derives on the host pool,
+// which walks the candidates and words the refusal of a program that exhausts them.
+extern "C" int sbn_prover_generate_trace_curve_program(sbn_prover* P, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,
+                                                       const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* values_out,
+                                                       uint8_t* infinity_out, uint8_t* choice_out, uint32_t* ios_out) {
+  if (int rc = unload(P)) return rc;
+  const int kind = P->air.kind;
+  if (kind != SBN_AIR_G1_EXP && kind != SBN_AIR_G2_EXP) return fail(SBN_ERR_UNSUPPORTED, "curve programs cover the curve tables G1_EXP and G2_EXP");
+  if (!nodes || !points || !exps || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no node");
+  const size_t num_io = P->air.num_io;
+  if (count > num_io) return fail(SBN_ERR_BAD_ARG, "a program of %zu nodes does not fit one unit of %zu instances", count, num_io);
+  bool device_chains;
+  if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
+  const auto on_host = [&] {
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) {
+      return sbn_curve_program_instances(kind, nodes, count, points, n_points, exps, n_exps, num_io, ios, outs_out, values_out, infinity_out, choice_out);
+    });
+  };
+  if (!device_chains) return on_host();
+  ProgramPlan plan;
+  if (int rc = curve_program_plan(kind, nodes, count, points, n_points, exps, n_exps, num_io, plan)) return rc;
+  const CurveProgramIn pr{nodes, count, points, exps, outs_out, values_out, infinity_out, ios_out};
+  bool fallback = false;
+  const int rc = kind == SBN_AIR_G1_EXP ? curve_trace_program<1>(P, pr, plan, num_io, pi_out, &fallback) : curve_trace_program<2>(P, pr, plan, num_io, pi_out, &fallback);
+  if (rc != SBN_OK) return rc;
+  if (fallback) return on_host();
+  if (choice_out) *choice_out = 0;
+  return SBN_OK;
+}
+
+extern "C" int sbn_bn254_fq_batch(int op,const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count, int on_device) {
   using namespace tg;
   if (op < FQB_MUL || op > FQB_FQ2_INV) return fail(SBN_ERR_BAD_ARG, "unknown op %d", op);
   const bool binary = op == FQB_MUL || op == FQB_ADD || op == FQB_SUB || op == FQB_FQ2_INV;
