@@ -431,13 +431,9 @@ template <int E> GL_HD void stc(u64* p, const Co<E>& v) { for (int q = 0; q < E;
 // io: x.x x.y offset.x offset.y (E x 8 u32 each) exp_val (8 u32).  A[t] = 2^t x (t = 0..256), B[0] = offset,
 // B[t+1] = bit_t ? B[t] + A[t] : B[t]   (g1/exp.rs:165-230, g2/exp.rs:180-246: even rows add-if-bit, odd rows double),
 // all in Jacobian coordinates and Montgomery form, so no step needs an inversion.  Returns TG_ERR_* flags.
-template <int E> GL_HD int exp_chains(const uint32_t* io, size_t k, u64* ja, u64* jb) {
-  u64 t4[4];
-  Jac<E> a, b;
-  Co<E>* dst[4] = {&a.X, &a.Y, &b.X, &b.Y};
-  for (int v = 0; v < 4; v++) for (int q = 0; q < E; q++) { u32x8_to_u64x4(io + 8 * (v * E + q), t4); dst[v]->c[q] = to_m(t4); }
-  a.Z = cone<E>(); b.Z = cone<E>();
-  const uint32_t* e = io + 32 * E;
+// exp_chains_from: the walk from A[0] = a, B[0] = b (Z = 1) under the exponent words e, a and b walked in place; exp_chains loads
+// both from the io words.  (tg::curve_program_level_kernel, whose operands come from earlier outputs, carries this loop itself.)
+template <int E> GL_HD int exp_chains_from(Jac<E>& a, Jac<E>& b, const uint32_t* e, size_t k, u64* ja, u64* jb) {
   int bad = 0;
   for (int t = 0;; t++) {
     stc<E>(ja + jac_at<E>(k, t, 0), a.X); stc<E>(ja + jac_at<E>(k, t, 1), a.Y); stc<E>(ja + jac_at<E>(k, t, 2), a.Z);
@@ -449,6 +445,18 @@ template <int E> GL_HD int exp_chains(const uint32_t* io, size_t k, u64* ja, u64
     a = jac_double<E>(a);
   }
   return bad;
+}
+template <int E> GL_HD int exp_chains(const uint32_t* io, size_t k, u64* ja, u64* jb) {
+  u64 t4[4];
+  Jac<E> a, b;
+  for (int q = 0; q < E; q++) {
+    u32x8_to_u64x4(io + 8 * q, t4); a.X.c[q] = to_m(t4);
+    u32x8_to_u64x4(io + 8 * (E + q), t4); a.Y.c[q] = to_m(t4);
+    u32x8_to_u64x4(io + 8 * (2 * E + q), t4); b.X.c[q] = to_m(t4);
+    u32x8_to_u64x4(io + 8 * (3 * E + q), t4); b.Y.c[q] = to_m(t4);
+  }
+  a.Z = cone<E>(); b.Z = cone<E>();
+  return exp_chains_from<E>(a, b, io + 32 * E, k, ja, jb);
 }
 
 }  // namespace bnw

@@ -11,6 +11,7 @@
 //    blinds from the choice and the exponents and returns the values.  It verifies no proof.
 // Host code only: no kernel is launched from this unit (tracegen_device.hip holds the device form).
 #include "instance_lists.hpp"
+#include <cstdio>
 
 using namespace sbn;
 
@@ -20,8 +21,6 @@ using namespace sbn::curve_host;
 
 constexpr size_t INDEX_LIMIT = 0x7fffffffu;   // count, n_points and n_exps stay below the sentinels: an index never reads as one
 constexpr size_t NONE = (size_t)-1;
-inline bool linked(uint32_t v) { return (v & SBN_NODE_OUTPUT) != 0; }
-inline uint32_t link_of(uint32_t v) { return v & ~SBN_NODE_OUTPUT; }
 inline bool literal(uint32_t v) { return !linked(v) && v != SBN_NODE_START && v != SBN_NODE_ONE; }
 
 // refusals 1 and 2
@@ -70,17 +69,11 @@ template <int E> int check_used_points(const sbn_program_node* nodes, size_t cou
   return SBN_OK;
 }
 
-// the schedule: sbn_program_levels, then a stable counting sort by level (node order inside a level)
+// the schedule: sbn_program_levels, then fill_plan's sort by level
 int schedule(const sbn_program_node* nodes, size_t count, ProgramPlan& plan) {
   plan.level.resize(count);
-  uint32_t depth = 0;
-  if (int rc = sbn_program_levels(nodes, count, plan.level.data(), &depth)) return rc;
-  plan.level_start.assign((size_t)depth + 1, 0);
-  for (size_t g = 0; g < count; g++) plan.level_start[plan.level[g] + 1]++;
-  for (size_t l = 0; l < depth; l++) plan.level_start[l + 1] += plan.level_start[l];
-  plan.order.resize(count);
-  std::vector<uint32_t> next(plan.level_start.begin(), plan.level_start.end() - 1);
-  for (size_t g = 0; g < count; g++) plan.order[next[plan.level[g]]++] = (uint32_t)g;
+  if (int rc = sbn_program_levels(nodes, count, plan.level.data(), nullptr)) return rc;
+  fill_plan(plan.level.data(), count, count, plan);
   return SBN_OK;
 }
 
@@ -245,26 +238,18 @@ extern "C" int sbn_curve_program_check(int32_t kind, size_t num_io, const uint64
   const PiLayout& L = U.L;
   const uint32_t* sw = curve_start_candidate_words(L.E, choice);
   std::vector<uint32_t> outs(L.xw * count);
-  for (size_t g = 0; g < U.rows(); g++) {
-    if (g >= count) { if (int rc = U.pad(g, count - 1)) return rc; continue; }
-    const uint32_t op[2] = {nodes[g].x, nodes[g].offset};
-    const size_t at[2] = {U.oX, U.oOff};
-    static const char* const field[2] = {"x", "offset"};
-    for (int f = 0; f < 2; f++) {
-      if (linked(op[f])) {
-        if (!same(U.inst(g) + at[f], U.inst(link_of(op[f])) + U.oOut, L.W))
-          return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the output of node %u", g, field[f], link_of(op[f]));
-      } else if (op[f] == SBN_NODE_START) {
-        if (!U.value_is(g, at[f], sw)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from start candidate %u", g, field[f], choice);
-      } else if (!U.value_is(g, at[f], points + L.xw * op[f]))
-        return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the caller's literal %u", g, field[f], op[f]);
-    }
-    if (!U.exp_is(g, exps + L.ew * nodes[g].exp)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: exponent differs from the caller's", g);
-    size_t limb;
-    if (!U.output(g, outs.data() + L.xw * g, &limb)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output limb %zu is out of range", g, limb);
-    const int fault = L.E == 1 ? output_fault<1>(outs.data() + L.xw * g) : output_fault<2>(outs.data() + L.xw * g);
-    if (fault) return fail(SBN_ERR_VERIFY_FAILED, fault == 1 ? "instance %zu: output has a coordinate >= p" : "instance %zu: output is not a point of the curve", g);
-  }
+  char not_start[48];
+  snprintf(not_start, sizeof not_start, "differs from start candidate %u", choice);
+  const int links = check_program_links(U, nodes, count, points, exps,
+    [&](uint32_t op, const char** what) -> const uint32_t* { *what = not_start; return op == SBN_NODE_START ? sw : nullptr; },
+    [&](size_t g) {
+      size_t limb;
+      if (!U.output(g, outs.data() + L.xw * g, &limb)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output limb %zu is out of range", g, limb);
+      const int fault = L.E == 1 ? output_fault<1>(outs.data() + L.xw * g) : output_fault<2>(outs.data() + L.xw * g);
+      if (fault) return fail(SBN_ERR_VERIFY_FAILED, fault == 1 ? "instance %zu: output has a coordinate >= p" : "instance %zu: output is not a point of the curve", g);
+      return (int)SBN_OK;
+    });
+  if (links != SBN_OK) return links;
   if (values_out || infinity_out) {
     ProgramPlan plan;
     if (int rc = schedule(nodes, count, plan)) return rc;

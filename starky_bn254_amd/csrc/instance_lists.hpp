@@ -1,7 +1,8 @@
 // What the five units that turn application inputs into an explicit `ios` list share (chain_instances.hip, msm.hip, scalar_mul.hip,
 // powers.hip, msm_batch.hip): the search for the first offending instance on the host pool, the refusals of a curve list, the
-// field tables' square-and-multiply, the pad rule, the table's own walk of an explicit curve list, and the reader of the per-unit
-// public inputs behind the four *_check calls.  Host code only.  (The word counts of a table: PiLayout, host_common.hpp.)
+// field tables' square-and-multiply, the pad rule, the table's own walk of an explicit curve list, the reader of the per-unit
+// public inputs behind the *_check calls, and what the two program units (program.hip, curve_program.hip) share: the link words,
+// the schedule of a levelled program and the link checks.  Host code only.  (The word counts of a table: PiLayout, host_common.hpp.)
 #pragma once
 #include "curve_host.hpp"
 #include <vector>
@@ -124,6 +125,54 @@ struct UnitInputs {
   // the output of instance g as the L.xw u32 words of a value; false and *limb = the first limb wider than its slot: no output of the table
   bool output(size_t g, uint32_t* w, size_t* limb) const { return value_from_pi(L, inst(g) + oOut, w, limb); }
 };
+
+// ---- programs (program.hip, curve_program.hip, and their device drivers in tracegen_device.hip) ------------------------------------
+inline bool linked(uint32_t v) { return (v & SBN_NODE_OUTPUT) != 0; }
+inline uint32_t link_of(uint32_t v) { return v & ~SBN_NODE_OUTPUT; }
+
+// The schedule from level[count] (sbn_program_levels): a stable counting sort, so plan.order lists the nodes of level l in node
+// order at [level_start[l], level_start[l + 1]).  rows > count: rows [count, rows) are pads, scheduled as further nodes of the level
+// of node count - 1 (the device walks a pad of a curve program as one more node).  plan.level is the caller's.
+inline void fill_plan(const uint32_t* level, size_t count, size_t rows, ProgramPlan& plan) {
+  const auto at = [&](size_t g) { return level[g < count ? g : count - 1]; };
+  uint32_t depth = 0;
+  for (size_t g = 0; g < count; g++) if (level[g] + 1 > depth) depth = level[g] + 1;
+  plan.level_start.assign((size_t)depth + 1, 0);
+  for (size_t g = 0; g < rows; g++) plan.level_start[at(g) + 1]++;
+  for (size_t l = 0; l < depth; l++) plan.level_start[l + 1] += plan.level_start[l];
+  plan.order.resize(rows);
+  std::vector<uint32_t> next(plan.level_start.begin(), plan.level_start.end() - 1);
+  for (size_t g = 0; g < rows; g++) plan.order[next[at(g)]++] = (uint32_t)g;
+}
+
+// The link checks behind sbn_program_check and sbn_curve_program_check, in instance order: a pad is instance count - 1 again; x and
+// offset equal the output of the node they link to, or the words of their literal in `literals`, or what sentinel(op, what) returns
+// for an operand that is neither (one, the start; null: op is a literal index), `what` the tail of its refusal; the exponent is the
+// caller's; judge_output(g) has the last word on the output of instance g.
+template <typename Sentinel, typename Judge>
+int check_program_links(const UnitInputs& U, const sbn_program_node* nodes, size_t count, const uint32_t* literals, const uint32_t* exps, Sentinel sentinel,
+                        Judge judge_output) {
+  const PiLayout& L = U.L;
+  for (size_t g = 0; g < U.rows(); g++) {
+    if (g >= count) { if (int rc = U.pad(g, count - 1)) return rc; continue; }
+    const uint32_t op[2] = {nodes[g].x, nodes[g].offset};
+    const size_t at[2] = {U.oX, U.oOff};
+    static const char* const field[2] = {"x", "offset"};
+    for (int f = 0; f < 2; f++) {
+      const char* what = nullptr;
+      if (linked(op[f])) {
+        if (!same(U.inst(g) + at[f], U.inst(link_of(op[f])) + U.oOut, L.W))
+          return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the output of node %u", g, field[f], link_of(op[f]));
+      } else if (const uint32_t* w = sentinel(op[f], &what)) {
+        if (!U.value_is(g, at[f], w)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s %s", g, field[f], what);
+      } else if (!U.value_is(g, at[f], literals + L.xw * op[f]))
+        return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the caller's literal %u", g, field[f], op[f]);
+    }
+    if (!U.exp_is(g, exps + L.ew * nodes[g].exp)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: exponent differs from the caller's", g);
+    if (int rc = judge_output(g)) return rc;
+  }
+  return SBN_OK;
+}
 
 }  // namespace curve_host
 }  // namespace sbn

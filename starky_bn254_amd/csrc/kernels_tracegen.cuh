@@ -1027,6 +1027,27 @@ __global__ void __launch_bounds__(RC_THREADS) __attribute__((amdgpu_waves_per_eu
 // Sums in a group do not depend on the bracketing, so the offsets equal sbn_chain_instances' word for word.
 template <int E> __device__ __forceinline__ Jac<E> ld_jac(const u64* p) { Jac<E> r; r.X = ldc<E>(p); r.Y = ldc<E>(p + 4 * E); r.Z = ldc<E>(p + 8 * E); return r; }
 template <int E> __device__ __forceinline__ void st_jac(u64* p, const Jac<E>& v) { stc<E>(p, v.X); stc<E>(p + 4 * E, v.Y); stc<E>(p + 8 * E, v.Z); }
+// Out of Jacobian and Montgomery form, for every kernel that leaves an affine point in u32 words (the word order of a point in `ios`):
+//   affine_or_zero   x, y of p from ni = 1 / norm(Z) (batch_inverse, finv_fermat); the point at infinity has none: zeros, true;
+//   st_affine_words  x then y, E coordinates of eight standard-form u32 words each, to dst[0 .. 16E);
+//   ld_affine_words  the way back: x, y of the affine point in the 16E u32 words at w, Montgomery form.
+template <int E> __device__ __forceinline__ bool affine_or_zero(const Jac<E>& p, const Fq& ni, Co<E> (&v)[2]) {
+  if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; return true; }
+  const Co<E> zi = cinv_from_norm(p.Z, ni), zi2 = cmul(zi, zi);
+  v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi));
+  return false;
+}
+template <int E> __device__ __forceinline__ void ld_affine_words(const uint32_t* w, Co<E>& X, Co<E>& Y) {
+  u64 t4[4];
+  for (int q = 0; q < E; q++) { u32x8_to_u64x4(w + 8 * q, t4); X.c[q] = to_m(t4); u32x8_to_u64x4(w + 8 * (E + q), t4); Y.c[q] = to_m(t4); }
+}
+template <int E> __device__ __forceinline__ void st_affine_words(uint32_t* dst, const Co<E> (&v)[2]) {
+  for (int c = 0; c < 2; c++)
+    for (int q = 0; q < E; q++) {
+      u64 s[4]; from_m(v[c].c[q], s);
+      for (int w = 0; w < 8; w++) dst[8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
+    }
+}
 static constexpr int CT_LANES = 256;   // one lane per step of an instance
 template <int E>
 __global__ void __launch_bounds__(CT_LANES) chain_prefix_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ ja, u64* __restrict__ pre, u64* __restrict__ terms) {
@@ -1051,8 +1072,8 @@ __global__ void chain_rebase_kernel(const uint32_t* __restrict__ ios, size_t K, 
   if (i >= K * 257) return;
   const size_t k = i / 257; const int t = (int)(i % 257);
   const uint32_t* io = ios + 8 * (4 * E + 1) * k;
-  Jac<E> b; u64 t4[4];
-  for (int q = 0; q < E; q++) { u32x8_to_u64x4(io + 8 * (2 * E + q), t4); b.X.c[q] = to_m(t4); u32x8_to_u64x4(io + 8 * (3 * E + q), t4); b.Y.c[q] = to_m(t4); }
+  Jac<E> b;
+  ld_affine_words<E>(io + 16 * E, b.X, b.Y);
   b.Z = cone<E>();
   if (t) b = jac_add_complete<E>(b, ld_jac<E>(pre + 12 * E * (k * CT_LANES + (size_t)(t - 1))));
   st_jac<E>(jb + jac_at<E>(k, t, 0), b);
@@ -1069,8 +1090,7 @@ __global__ void __launch_bounds__(CS_LANES) chain_scan_kernel(uint32_t* ios, siz
   Jac<E> cur = jac_infinity<E>();
   if (k < K) {
     if (k == 0) {   // start: the offset every instance of the preliminary list carries
-      u64 t4[4];
-      for (int q = 0; q < E; q++) { u32x8_to_u64x4(ios + 8 * (2 * E + q), t4); cur.X.c[q] = to_m(t4); u32x8_to_u64x4(ios + 8 * (3 * E + q), t4); cur.Y.c[q] = to_m(t4); }
+      ld_affine_words<E>(ios + 16 * E, cur.X, cur.Y);
       cur.Z = cone<E>();
     } else cur = ld_jac<E>(terms + 12 * E * (k - 1));
   }
@@ -1101,13 +1121,8 @@ __global__ void __launch_bounds__(CS_LANES) chain_scan_kernel(uint32_t* ios, siz
     if (i >= K) continue;
     const Jac<E> p = ld_jac<E>(sum + 12 * E * i);
     Co<E> v[2];
-    if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
-    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
-    for (int c = 0; c < 2; c++)
-      for (int q = 0; q < E; q++) {
-        u64 s[4]; from_m(v[c].c[q], s);
-        for (int w = 0; w < 8; w++) ios[IOW * i + 8 * ((2 + c) * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
-      }
+    affine_or_zero<E>(p, nrm[j], v);   // at infinity: zeros, the call is refused (TG_ERR_INFINITY)
+    st_affine_words<E>(ios + IOW * i + 16 * E, v);
   }
 }
 
@@ -1139,11 +1154,13 @@ __global__ void scalar_mul_list_kernel(const uint32_t* __restrict__ cin, size_t 
   const uint32_t* off = scal + 8 * SC;
   ios[i] = w < W ? cin[W * k + w] : (w < 2 * W ? off[w - W] : scal[(SC == 1 ? 0 : 8 * k) + (w - 2 * W)]);
 }
-template <int E>
-__global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ outs, u64* __restrict__ jp,
-                                           uint32_t* __restrict__ products, unsigned char* __restrict__ infinity,
-                                           const uint32_t* __restrict__ out_at = nullptr, const uint32_t* __restrict__ off_at = nullptr) {
-  const size_t W = 16 * E, IOW = 2 * W + 8;
+// What scalar_mul_unoffset_kernel and curve_program_values_kernel ("curve programs" below) share: dst[i] = output of instance
+// out_at[i] (null: i) + the subtrahend of item i, which `load(i, m)` leaves in m.X, m.Y already negated (false: there is none, the
+// value is the output itself), then the batched inversion and the affine words with their infinity flags.
+template <int E, typename Load>
+__device__ __forceinline__ void unoffset_store(size_t K, const u64* __restrict__ outs, const uint32_t* __restrict__ out_at, u64* __restrict__ jp,
+                                               uint32_t* __restrict__ dst, unsigned char* __restrict__ infinity, Load load) {
+  const size_t W = 16 * E;
   const size_t L = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
   if (L >= NL) return;
@@ -1153,18 +1170,15 @@ __global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, siz
     nrm[j] = fq_one();
     if (i >= K) continue;
     Jac<E> o, m; u64 t4[4];
-    const size_t io = out_at ? out_at[i] : i, im = off_at ? off_at[i] : i;   // (segmented lists: the tail and the head of segment i)
+    const size_t io = out_at ? out_at[i] : i;
     for (int c = 0; c < 2; c++)
       for (int q = 0; q < E; q++) {
         const u64* src = outs + W * io + 8 * (c * E + q);
         for (int h = 0; h < 4; h++) t4[h] = (src[2 * h] & 0xffffffffULL) | (src[2 * h + 1] << 32);
         (c ? o.Y : o.X).c[q] = to_m(t4);
-        u32x8_to_u64x4(ios + IOW * im + W + 8 * (c * E + q), t4);
-        (c ? m.Y : m.X).c[q] = to_m(t4);
       }
     o.Z = cone<E>(); m.Z = o.Z;
-    m.Y = csub(csub(m.Y, m.Y), m.Y);   // -offset
-    const Jac<E> r = jac_add_complete<E>(o, m);
+    const Jac<E> r = load(i, m) ? jac_add_complete<E>(o, m) : o;
     st_jac<E>(jp + 12 * E * i, r);
     if (!czero<E>(r.Z)) nrm[j] = cnorm(r.Z);
   }
@@ -1172,18 +1186,22 @@ __global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, siz
   for (int j = 0; j < TG_INV_BATCH; j++) {
     const size_t i = L + (size_t)j * NL;
     if (i >= K) continue;
-    const Jac<E> p = ld_jac<E>(jp + 12 * E * i);
-    const bool inf = czero<E>(p.Z);
     Co<E> v[2];
-    if (inf) { v[0] = p.Z; v[1] = p.Z; }   // the point at infinity: zero words and its flag
-    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
-    for (int c = 0; c < 2; c++)
-      for (int q = 0; q < E; q++) {
-        u64 s[4]; from_m(v[c].c[q], s);
-        for (int w = 0; w < 8; w++) products[W * i + 8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
-      }
+    const bool inf = affine_or_zero<E>(ld_jac<E>(jp + 12 * E * i), nrm[j], v);   // the point at infinity: zero words and its flag
+    st_affine_words<E>(dst + W * i, v);
     infinity[i] = inf ? 1 : 0;
   }
+}
+template <int E>
+__global__ void scalar_mul_unoffset_kernel(const uint32_t* __restrict__ ios, size_t K, const u64* __restrict__ outs, u64* __restrict__ jp,
+                                           uint32_t* __restrict__ products, unsigned char* __restrict__ infinity,
+                                           const uint32_t* __restrict__ out_at = nullptr, const uint32_t* __restrict__ off_at = nullptr) {
+  unoffset_store<E>(K, outs, out_at, jp, products, infinity, [&](size_t i, Jac<E>& m) {
+    const size_t im = off_at ? off_at[i] : i;   // (segmented lists: out_at / off_at = the tail and the head of segment i)
+    ld_affine_words<E>(ios + (2 * 16 * E + 8) * im + 16 * E, m.X, m.Y);
+    m.Y = csub(csub(m.Y, m.Y), m.Y);   // -offset
+    return true;
+  });
 }
 
 // outs: [K][12][4] = x_k^e_k in standard form (fq12_chain_kernel on offsets of one); start: 12 coefficients of 8 u32 limbs
@@ -1250,8 +1268,7 @@ __global__ void __launch_bounds__(CS_LANES) chain_seg_scan_kernel(uint32_t* ios,
   if (k < M) {
     hd = head[k];
     if (hd == k) {   // a head: the start of its segment, in the offset words of its preliminary row
-      u64 t4[4];
-      for (int q = 0; q < E; q++) { u32x8_to_u64x4(ios + IOW * k + 8 * (2 * E + q), t4); cur.X.c[q] = to_m(t4); u32x8_to_u64x4(ios + IOW * k + 8 * (3 * E + q), t4); cur.Y.c[q] = to_m(t4); }
+      ld_affine_words<E>(ios + IOW * k + 16 * E, cur.X, cur.Y);
       cur.Z = cone<E>();
     } else cur = ld_jac<E>(terms + 12 * E * (k - 1));   // (hd < k here, so k >= 1)
   }
@@ -1282,13 +1299,8 @@ __global__ void __launch_bounds__(CS_LANES) chain_seg_scan_kernel(uint32_t* ios,
     if (i >= K) continue;
     const Jac<E> p = ld_jac<E>(sum + 12 * E * (i < M ? i : M - 1));   // a pad row carries the offset of row M - 1
     Co<E> v[2];
-    if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
-    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
-    for (int c = 0; c < 2; c++)
-      for (int q = 0; q < E; q++) {
-        u64 s[4]; from_m(v[c].c[q], s);
-        for (int w = 0; w < 8; w++) ios[IOW * i + 8 * ((2 + c) * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
-      }
+    affine_or_zero<E>(p, nrm[j], v);   // at infinity: zeros, the call is refused (TG_ERR_INFINITY)
+    st_affine_words<E>(ios + IOW * i + 16 * E, v);
   }
 }
 // ---- complete sums (sbn_prover_generate_trace_msm_batch_complete): the start of segment s is start candidate choice[s] -----------------
@@ -1312,20 +1324,23 @@ __global__ void chain_seg_start_kernel(uint32_t* ios, size_t S, const uint32_t* 
   const size_t s = i / W, w = i % W;
   ios[IOW * seg_head[s] + W + w] = candidates[W * choice[s] + w];
 }
+// the verdict on step t <= 256 of instance k, for this kernel and for curve_program_status_kernel ("curve programs" below)
+template <int E>
+__device__ __forceinline__ bool walk_bad_event(const uint32_t* __restrict__ ios, const u64* __restrict__ ja, const u64* __restrict__ jb, size_t k, int t) {
+  const Co<E> Z2 = ldc<E>(jb + jac_at<E>(k, t, 2));
+  if (czero<E>(Z2)) return true;
+  if (t == 256 || !((ios[8 * (4 * E + 1) * k + 32 * E + (t >> 5)] >> (t & 31)) & 1)) return false;
+  const Co<E> Z1 = ldc<E>(ja + jac_at<E>(k, t, 2));
+  const Co<E> D = csub(cmul(ldc<E>(jb + jac_at<E>(k, t, 0)), cmul(Z1, Z1)), cmul(ldc<E>(ja + jac_at<E>(k, t, 0)), cmul(Z2, Z2)));
+  return czero<E>(Z1) || czero<E>(D);
+}
 template <int E>
 __global__ void chain_seg_status_kernel(const uint32_t* __restrict__ ios, size_t M, const u64* __restrict__ ja, const u64* __restrict__ jb,
                                         const uint32_t* __restrict__ seg_of, int* __restrict__ status) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= M * 257) return;
-  const size_t k = i / 257; const int t = (int)(i % 257);
-  const Co<E> Z2 = ldc<E>(jb + jac_at<E>(k, t, 2));
-  bool bad = czero<E>(Z2);
-  if (!bad && t < 256 && ((ios[8 * (4 * E + 1) * k + 32 * E + (t >> 5)] >> (t & 31)) & 1)) {
-    const Co<E> Z1 = ldc<E>(ja + jac_at<E>(k, t, 2));
-    const Co<E> D = csub(cmul(ldc<E>(jb + jac_at<E>(k, t, 0)), cmul(Z1, Z1)), cmul(ldc<E>(ja + jac_at<E>(k, t, 0)), cmul(Z2, Z2)));
-    bad = czero<E>(Z1) || czero<E>(D);
-  }
-  if (bad) atomicOr(status + seg_of[k], 1);
+  const size_t k = i / 257;
+  if (walk_bad_event<E>(ios, ja, jb, k, (int)(i % 257))) atomicOr(status + seg_of[k], 1);
 }
 
 // ---- lists of more than CS_LANES instances: the same scan in blocks of CS_LANES, chained and segmented alike --------------------------
@@ -1355,8 +1370,7 @@ __global__ void __launch_bounds__(CS_LANES) chain_block_scan_kernel(const uint32
     const size_t hd = head ? head[k] : 0;
     lo = hd > first ? hd : first;
     if (hd == k) {   // a head: the start of its segment, in the offset words of its preliminary row
-      u64 t4[4];
-      for (int q = 0; q < E; q++) { u32x8_to_u64x4(ios + IOW * k + 8 * (2 * E + q), t4); cur.X.c[q] = to_m(t4); u32x8_to_u64x4(ios + IOW * k + 8 * (3 * E + q), t4); cur.Y.c[q] = to_m(t4); }
+      ld_affine_words<E>(ios + IOW * k + 16 * E, cur.X, cur.Y);
       cur.Z = cone<E>();
     } else cur = ld_jac<E>(terms + 12 * E * (k - 1));   // (hd < k here, so k >= 1)
   }
@@ -1406,13 +1420,8 @@ __global__ void chain_block_tail_kernel(uint32_t* ios, size_t K, size_t M, const
     if (i >= K) continue;
     const Jac<E> p = ld_jac<E>(sum + 12 * E * i);
     Co<E> v[2];
-    if (czero<E>(p.Z)) { v[0] = p.Z; v[1] = p.Z; }   // no affine form: zeros, the call is refused (TG_ERR_INFINITY)
-    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
-    for (int c = 0; c < 2; c++)
-      for (int q = 0; q < E; q++) {
-        u64 s[4]; from_m(v[c].c[q], s);
-        for (int w = 0; w < 8; w++) ios[IOW * i + 8 * ((2 + c) * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
-      }
+    affine_or_zero<E>(p, nrm[j], v);   // at infinity: zeros, the call is refused (TG_ERR_INFINITY)
+    st_affine_words<E>(ios + IOW * i + 16 * E, v);
   }
 }
 // seg_head / seg_len: [segments] (blockIdx.x = segment; the host has checked head + len <= M <= K); starts: [SC][96] u32, SC = 1
@@ -1505,7 +1514,8 @@ __global__ void __launch_bounds__(256) fq12_tower_pad_kernel(uint32_t* ios, size
 // ---- field programs (sbn_prover_generate_trace_program): x and offset of an instance = a literal or the output of an earlier one ----
 // The host sorts the nodes by level (level 0: no link; otherwise 1 + the largest level linked to), so the nodes of one level are
 // independent and every node they link to lies in an EARLIER level.  ONE LAUNCH PER LEVEL, one workgroup per node of that level,
-// with the lane roles, the LDS layout and the step of fq12_chain_kernel; the new part is the head.  The twelve coefficient lanes of
+// with the lane roles, the LDS layout and the step of fq12_chain_kernel (spelled out in each of the three kernels: one shared
+// function cost the two one-level kernels two VGPRs and 0.7 % of their time); the new part is the head.  The twelve coefficient lanes of
 // A (x) and of B (offset) look their operand up in the node table: a link (bit 31) reads the standard-form output of node j from
 // `outs`, which an earlier LAUNCH wrote, stores those words into the x or offset words of the node's own `ios` row (for the row,
 // flag and download kernels that follow) and enters the chain from those very registers; a literal, or one, loads from `ios`, where
@@ -1554,14 +1564,15 @@ __global__ void __launch_bounds__(320) fq12_program_level_kernel(uint32_t* ios, 
 // ---- output of an earlier instance --------------------------------------------------------------------------------------------------
 // The field programs above on G1 / G2 (E = 1 / 2).  The host sorts the nodes by level, so the nodes of one level are independent
 // and every node they link to lies in an EARLIER level.  Per level TWO launches, ordered by their kernel boundary:
-//   curve_program_level_kernel       one LANE per node of the level (placement 1), the chain step of chain_kernel / exp_chains;
-//   curve_program_level_coop_kernel  one WAVE per node of the level (placement 2), the chain step of chain_coop_kernel;
-//     both copied, not shared, so the code objects of the explicit-list kernels stay as they are.  The new part is the head: an
+//   curve_program_level_kernel       one LANE per node of the level (placement 1), the chain step of chain_kernel / exp_chains, copied:
+//     calling bnw::exp_chains_from instead cost the 16-level G2 program 3 % of its time;
+//   curve_program_level_coop_kernel  one WAVE per node of the level (placement 2), the chain step of chain_coop_kernel, copied:
+//     shared as one function it cost the explicit G1 list 0.8 % of its time.  The new part of both is the head: an
 //     operand whose node word has bit 31 set is the affine output of node j, which an earlier LAUNCH left in `outs` ([K][16E]
 //     u32, the word order of a point in `ios`); its words go into the x or offset words of the node's own `ios` row (for the row,
 //     flag and download kernels that follow) and enter the chain from those registers.  A literal, or the start, loads from
 //     `ios`, where the host put it.  The chain's own degenerate flags go to a word nobody reads: the status kernel finds them.
-//   curve_program_status_kernel      one lane per (node of the level, step t <= 256), the verdict of chain_seg_status_kernel: a bad
+//   curve_program_status_kernel      one lane per (node of the level, step t <= 256), the verdict of chain_seg_status_kernel (walk_bad_event): a bad
 //     event of the table's walk is B[t] at infinity or, at a set bit, B[t] = +-A[t].  A lane that meets one ORs into the ONE status
 //     word; a clean level stores nothing there.  The lane of t = 256 also turns B[256] into its affine form (one Fermat chain) and
 //     writes outs[k] -- zeros for an output at infinity, which the status word reports.
@@ -1673,72 +1684,28 @@ __global__ void __launch_bounds__(256) curve_program_status_kernel(const uint32_
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= count * 257) return;
   const size_t k = order[i / 257]; const int t = (int)(i % 257);
-  const Co<E> Z2 = ldc<E>(jb + jac_at<E>(k, t, 2));
-  bool bad = czero<E>(Z2);
-  if (!bad && t < 256 && ((ios[8 * (4 * E + 1) * k + 32 * E + (t >> 5)] >> (t & 31)) & 1)) {
-    const Co<E> Z1 = ldc<E>(ja + jac_at<E>(k, t, 2));
-    const Co<E> D = csub(cmul(ldc<E>(jb + jac_at<E>(k, t, 0)), cmul(Z1, Z1)), cmul(ldc<E>(ja + jac_at<E>(k, t, 0)), cmul(Z2, Z2)));
-    bad = czero<E>(Z1) || czero<E>(D);
-  }
+  const bool bad = walk_bad_event<E>(ios, ja, jb, k, t);
   if (bad) atomicOr(status, 1);
   if (t != 256) return;
+  const Co<E> Z2 = ldc<E>(jb + jac_at<E>(k, 256, 2));
   Co<E> v[2];
   if (bad) { v[0] = Z2; v[1] = Z2; }   // the point at infinity has no affine form: zeros, and the status word says so
   else {
     const Co<E> zi = cinv_from_norm(Z2, finv_fermat(cnorm(Z2))), zi2 = cmul(zi, zi);
     v[0] = cmul(ldc<E>(jb + jac_at<E>(k, 256, 0)), zi2); v[1] = cmul(ldc<E>(jb + jac_at<E>(k, 256, 1)), cmul(zi2, zi));
   }
-  for (int c = 0; c < 2; c++)
-    for (int q = 0; q < E; q++) {
-      u64 s[4]; from_m(v[c].c[q], s);
-      for (int w = 0; w < 8; w++) outs[16 * E * k + 8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
-    }
+  st_affine_words<E>(outs + 16 * E * k, v);
 }
-// values[i] = out_i + (-T_i), i < K real nodes, behind affine_lambda_kernel: scalar_mul_unoffset_kernel with the subtrahend from
+// values[i] = out_i + (-T_i), i < K real nodes, behind affine_lambda_kernel: the unoffset_store of scalar_mul_unoffset_kernel with the subtrahend from
 // `neg_blinds` ([K][16E] u32 affine words of -T_i, uploaded by the host; blind_inf[i] = 1: T_i is the point at infinity and the
 // value is the output itself) instead of the instance's own offset words.  Outputs, `jp`, the batched inversion and the flags as there.
 template <int E>
 __global__ void curve_program_values_kernel(size_t K, const u64* __restrict__ outs, const uint32_t* __restrict__ neg_blinds, const unsigned char* __restrict__ blind_inf,
                                             u64* __restrict__ jp, uint32_t* __restrict__ values, unsigned char* __restrict__ infinity) {
-  const size_t W = 16 * E;
-  const size_t L = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  const size_t NL = (K + TG_INV_BATCH - 1) / TG_INV_BATCH;
-  if (L >= NL) return;
-  Fq nrm[TG_INV_BATCH];
-  for (int j = 0; j < TG_INV_BATCH; j++) {
-    const size_t i = L + (size_t)j * NL;
-    nrm[j] = fq_one();
-    if (i >= K) continue;
-    Jac<E> o, m; u64 t4[4];
-    for (int c = 0; c < 2; c++)
-      for (int q = 0; q < E; q++) {
-        const u64* src = outs + W * i + 8 * (c * E + q);
-        for (int h = 0; h < 4; h++) t4[h] = (src[2 * h] & 0xffffffffULL) | (src[2 * h + 1] << 32);
-        (c ? o.Y : o.X).c[q] = to_m(t4);
-        u32x8_to_u64x4(neg_blinds + W * i + 8 * (c * E + q), t4);
-        (c ? m.Y : m.X).c[q] = to_m(t4);
-      }
-    o.Z = cone<E>(); m.Z = o.Z;
-    const Jac<E> r = blind_inf[i] ? o : jac_add_complete<E>(o, m);
-    st_jac<E>(jp + 12 * E * i, r);
-    if (!czero<E>(r.Z)) nrm[j] = cnorm(r.Z);
-  }
-  batch_inverse(nrm);
-  for (int j = 0; j < TG_INV_BATCH; j++) {
-    const size_t i = L + (size_t)j * NL;
-    if (i >= K) continue;
-    const Jac<E> p = ld_jac<E>(jp + 12 * E * i);
-    const bool inf = czero<E>(p.Z);
-    Co<E> v[2];
-    if (inf) { v[0] = p.Z; v[1] = p.Z; }   // the point at infinity: zero words and its flag
-    else { const Co<E> zi = cinv_from_norm(p.Z, nrm[j]), zi2 = cmul(zi, zi); v[0] = cmul(p.X, zi2); v[1] = cmul(p.Y, cmul(zi2, zi)); }
-    for (int c = 0; c < 2; c++)
-      for (int q = 0; q < E; q++) {
-        u64 s[4]; from_m(v[c].c[q], s);
-        for (int w = 0; w < 8; w++) values[W * i + 8 * (c * E + q) + w] = (uint32_t)(s[w >> 1] >> (32 * (w & 1)));
-      }
-    infinity[i] = inf ? 1 : 0;
-  }
+  unoffset_store<E>(K, outs, nullptr, jp, values, infinity, [&](size_t i, Jac<E>& m) {
+    ld_affine_words<E>(neg_blinds + 16 * E * i, m.X, m.Y);
+    return !blind_inf[i];
+  });
 }
 
 // ---- parity hook (sbn_bn254_fq_batch, tracegen_device.hip): the field helpers above on standard-form operands, 4 words per element --------------

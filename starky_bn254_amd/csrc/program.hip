@@ -19,8 +19,6 @@ using namespace bnw;
 using namespace sbn::curve_host;
 
 constexpr size_t INDEX_LIMIT = 0x7fffffffu;   // count, n_values and n_exps stay below SBN_NODE_ONE: an index never reads as a link or as one
-inline bool linked(uint32_t v) { return (v & SBN_NODE_OUTPUT) != 0; }
-inline uint32_t link_of(uint32_t v) { return v & ~SBN_NODE_OUTPUT; }
 
 // Refusal 3 of the header, node by node; no_bound: structure only (sbn_program_levels knows no n_values and no n_exps).  Fills
 // level[count] (optional) and *depth.
@@ -109,15 +107,9 @@ int program_plan(int kind, const sbn_program_node* nodes, size_t count, const ui
                  size_t num_io, ProgramPlan& plan) {
   if (int rc = check_args(kind, nodes, values, exps, count, n_values, n_exps, num_io)) return rc;
   plan.level.resize(count);
-  uint32_t depth = 0;
-  if (int rc = walk_nodes(nodes, count, n_values, n_exps, false, plan.level.data(), &depth)) return rc;
+  if (int rc = walk_nodes(nodes, count, n_values, n_exps, false, plan.level.data(), nullptr)) return rc;
   if (int rc = check_used_values(kind, nodes, count, values, n_values, exps, n_exps)) return rc;
-  plan.level_start.assign((size_t)depth + 1, 0);   // a counting sort by level, stable: node order inside a level
-  for (size_t g = 0; g < count; g++) plan.level_start[plan.level[g] + 1]++;
-  for (size_t l = 0; l < depth; l++) plan.level_start[l + 1] += plan.level_start[l];
-  plan.order.resize(count);
-  std::vector<uint32_t> next(plan.level_start.begin(), plan.level_start.end() - 1);
-  for (size_t g = 0; g < count; g++) plan.order[next[plan.level[g]]++] = (uint32_t)g;
+  fill_plan(plan.level.data(), count, count, plan);
   return SBN_OK;
 }
 }  // namespace sbn
@@ -152,26 +144,13 @@ extern "C" int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* co
   const PiLayout& L = U.L;
   const uint32_t one[96] = {1};
   std::vector<uint32_t> out(L.xw);
-  for (size_t g = 0; g < U.rows(); g++) {
-    if (g >= count) { if (int rc = U.pad(g, count - 1)) return rc; continue; }
-    const uint32_t op[2] = {nodes[g].x, nodes[g].offset};
-    const size_t at[2] = {U.oX, U.oOff};
-    static const char* const field[2] = {"x", "offset"};
-    for (int f = 0; f < 2; f++) {
-      if (linked(op[f])) {
-        if (!same(U.inst(g) + at[f], U.inst(link_of(op[f])) + U.oOut, L.W))
-          return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the output of node %u", g, field[f], link_of(op[f]));
-      } else if (op[f] == SBN_NODE_ONE) {
-        if (!U.value_is(g, at[f], one)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s is not one", g, field[f]);
-      } else if (!U.value_is(g, at[f], values + L.xw * op[f]))
-        return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the caller's literal %u", g, field[f], op[f]);
-    }
-    if (!U.exp_is(g, exps + L.ew * nodes[g].exp)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: exponent differs from the caller's", g);
-    // a limb wider than its slot, or a coefficient >= p, is no output of the table
-    size_t limb;
-    if (!U.output(g, out.data(), &limb)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output limb %zu is out of range", g, limb);
-    if (!below_p(out.data(), L.values())) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output has a coefficient >= p", g);
-    if (outs_out) memcpy(outs_out + L.xw * g, out.data(), L.xw * sizeof(uint32_t));
-  }
-  return SBN_OK;
+  return check_program_links(U, nodes, count, values, exps,
+    [&](uint32_t op, const char** what) -> const uint32_t* { *what = "is not one"; return op == SBN_NODE_ONE ? one : nullptr; },
+    [&](size_t g) {   // a limb wider than its slot, or a coefficient >= p, is no output of the table
+      size_t limb;
+      if (!U.output(g, out.data(), &limb)) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output limb %zu is out of range", g, limb);
+      if (!below_p(out.data(), L.values())) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output has a coefficient >= p", g);
+      if (outs_out) memcpy(outs_out + L.xw * g, out.data(), L.xw * sizeof(uint32_t));
+      return (int)SBN_OK;
+    });
 }

@@ -199,6 +199,24 @@ static std::vector<uint32_t> preliminary_list(const ChainedIn& ch, size_t K, siz
   std::vector<uint32_t> head, len;
   return preliminary_list(ch.terms, &length, 1, K, K, xw, ew, [&](size_t) { return offset; }, head, len);
 }
+// the preliminary list of a program: row g carries the literals and the exponent of node min(g, M - 1) in place, `special_words` (one,
+// the start) where its offset is `special`, and zeros where the device will resolve a link; aux = the node table [K][3], then `order`
+static std::vector<uint32_t> program_prelim(const sbn_program_node* nodes, size_t M, size_t K, size_t xw, size_t ew, const uint32_t* literals, const uint32_t* exps,
+                                            uint32_t special, const uint32_t* special_words, const std::vector<uint32_t>& order, std::vector<uint32_t>& aux) {
+  std::vector<uint32_t> ios((2 * xw + ew) * K, 0u);
+  aux.resize(3 * K);
+  for (size_t g = 0; g < K; g++) {
+    const sbn_program_node& nd = nodes[g < M ? g : M - 1];
+    uint32_t* io = ios.data() + (2 * xw + ew) * g;
+    if (!curve_host::linked(nd.x)) memcpy(io, literals + xw * nd.x, xw * sizeof(uint32_t));
+    if (nd.offset == special) memcpy(io + xw, special_words, xw * sizeof(uint32_t));
+    else if (!curve_host::linked(nd.offset)) memcpy(io + xw, literals + xw * nd.offset, xw * sizeof(uint32_t));
+    memcpy(io + 2 * xw, exps + ew * nd.exp, ew * sizeof(uint32_t));
+    aux[3 * g] = nd.x; aux[3 * g + 1] = nd.offset; aux[3 * g + 2] = nd.exp;
+  }
+  aux.insert(aux.end(), order.begin(), order.end());
+  return ios;
+}
 
 // ---- the stages -----------------------------------------------------------------------------------------------------------------
 // One sbn_prover_generate_trace* call: the scratch carver, the launches every table has, the SBN_TRACE_TIMING marks and the tail.
@@ -612,24 +630,12 @@ static int curve_trace_segmented(sbn_prover* P, const BatchIn& mb, size_t K, uin
 // *fallback (with SBN_OK, nothing loaded): a node has a bad event under candidate 0; the caller derives on the host pool.
 template <int E>
 static int curve_trace_program(sbn_prover* P, const CurveProgramIn& pr, const ProgramPlan& plan, size_t K, uint64_t* pi_out, bool* fallback) {
-  const size_t W = 16 * E, IOW = 2 * W + 8, M = pr.count, depth = plan.depth();
-  const uint32_t* sw = curve_start_candidate_words(E, 0);
-  std::vector<uint32_t> prelim(IOW * K, 0u), aux(4 * K), start(depth + 1, 0);   // aux: the node table [K][3], then the order [K]
-  for (size_t g = 0; g < K; g++) {
-    const sbn_program_node& nd = pr.nodes[g < M ? g : M - 1];
-    uint32_t* io = prelim.data() + IOW * g;
-    if (!(nd.x & SBN_NODE_OUTPUT)) memcpy(io, pr.points + W * nd.x, W * sizeof(uint32_t));
-    if (nd.offset == SBN_NODE_START) memcpy(io + W, sw, W * sizeof(uint32_t));
-    else if (!(nd.offset & SBN_NODE_OUTPUT)) memcpy(io + W, pr.points + W * nd.offset, W * sizeof(uint32_t));
-    memcpy(io + 2 * W, pr.exps + 8 * nd.exp, 8 * sizeof(uint32_t));
-    aux[3 * g] = nd.x; aux[3 * g + 1] = nd.offset; aux[3 * g + 2] = nd.exp;
-    start[plan.level[g < M ? g : M - 1] + 1]++;
-  }
-  for (size_t l = 0; l < depth; l++) start[l + 1] += start[l];   // the counting sort of curve_program_plan again, the pads included
-  {
-    std::vector<uint32_t> next(start.begin(), start.end() - 1);
-    for (size_t g = 0; g < K; g++) aux[3 * K + next[plan.level[g < M ? g : M - 1]]++] = (uint32_t)g;
-  }
+  const size_t W = 16 * E, M = pr.count;
+  ProgramPlan rows;   // the schedule of all K rows: a pad runs as one more node of the level of node M - 1
+  curve_host::fill_plan(plan.level.data(), M, K, rows);
+  const std::vector<uint32_t>& start = rows.level_start;
+  std::vector<uint32_t> aux;   // the node table [K][3], then the order [K]
+  const std::vector<uint32_t> prelim = program_prelim(pr.nodes, M, K, W, 8, pr.points, pr.exps, SBN_NODE_START, curve_start_candidate_words(E, 0), rows.order, aux);
   HIPC(hipSetDevice(P->device));
   CurveJob<E> J(P, K);
   J.carve_products(M);
@@ -650,7 +656,7 @@ static int curve_trace_program(sbn_prover* P, const CurveProgramIn& pr, const Pr
   HIPC(hipMemsetAsync(d_status, 0, 2 * sizeof(int), J.st));
   tg::ChainProgDev cp{};
   if (P->chain_mode == 2) if (int rc = J.upload_chain_program(cp)) return rc;
-  for (size_t l = 0; l < depth; l++) {   // the kernel boundary between two levels is the link: level l reads what levels < l stored
+  for (size_t l = 0; l < rows.depth(); l++) {   // the kernel boundary between two levels is the link: level l reads what levels < l stored
     const size_t cnt = start[l + 1] - start[l];
     const uint32_t* d_order = d_aux + 3 * K + start[l];
     if (P->chain_mode == 2) hipLaunchKernelGGL(tg::curve_program_level_coop_kernel<E>, dim3((unsigned)cnt), dim3(tg::CP_LANES), 0, J.st, J.d_ios, d_aux, d_order, J.ja, J.jb, d_pout, d_status + 1, cp);
@@ -867,25 +873,17 @@ static int fq12_trace_towers(sbn_prover* P, const PowerIn& pw, size_t K, uint64_
 // are filled behind them, and the outputs come back together with the derived list in one download, as for the towers
 static int fq12_trace_program(sbn_prover* P, const ProgramIn& pr, const ProgramPlan& plan, size_t K, uint64_t* pi_out) {
   Fq12Job J(P, K);
-  const size_t IOW = J.IOW, ew = IOW - 192, M = pr.count;   // M real instances; rows [M, K) are pads
-  std::vector<uint32_t> prelim(IOW * K, 0u), aux(4 * M);    // aux: the node table [M][3], then the order [M]
-  for (size_t g = 0; g < K; g++) {
-    const sbn_program_node& nd = pr.nodes[g < M ? g : M - 1];
-    uint32_t* io = prelim.data() + IOW * g;
-    if (!(nd.x & SBN_NODE_OUTPUT)) memcpy(io, pr.values + 96 * nd.x, 96 * sizeof(uint32_t));
-    if (nd.offset == SBN_NODE_ONE) io[96] = 1;
-    else if (!(nd.offset & SBN_NODE_OUTPUT)) memcpy(io + 96, pr.values + 96 * nd.offset, 96 * sizeof(uint32_t));
-    memcpy(io + 192, pr.exps + ew * nd.exp, ew * sizeof(uint32_t));
-  }
-  for (size_t g = 0; g < M; g++) { aux[3 * g] = pr.nodes[g].x; aux[3 * g + 1] = pr.nodes[g].offset; aux[3 * g + 2] = pr.nodes[g].exp; }
-  memcpy(aux.data() + 3 * M, plan.order.data(), M * sizeof(uint32_t));
+  const size_t IOW = J.IOW, M = pr.count;   // M real instances; rows [M, K) are pads
+  const uint32_t one[96] = {1};
+  std::vector<uint32_t> aux;                // the node table [K][3], then the order [M]: the pads are filled, not walked
+  const std::vector<uint32_t> prelim = program_prelim(pr.nodes, M, K, 96, IOW - 192, pr.values, pr.exps, SBN_NODE_ONE, one, plan.order, aux);
   uint32_t* d_aux = (uint32_t*)J.take(aux.size() / 2 + 1);
   if (int rc = J.upload_list(prelim.data())) return rc;
   HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
   J.common_columns();
   for (size_t l = 0; l < plan.depth(); l++)   // the kernel boundary between two levels is the link: level l reads what levels < l stored
     hipLaunchKernelGGL(tg::fq12_program_level_kernel, dim3((unsigned)(plan.level_start[l + 1] - plan.level_start[l])), dim3(320), 0, J.st, J.d_ios, IOW, J.steps,
-                       d_aux, d_aux + 3 * M + plan.level_start[l], J.ca, J.cb, J.d_outs);
+                       d_aux, d_aux + 3 * K + plan.level_start[l], J.ca, J.cb, J.d_outs);
   J.mark("program_levels");
   if (M < K) hipLaunchKernelGGL(tg::fq12_tower_pad_kernel, dim3((unsigned)(K - M)), dim3(256), 0, J.st, J.d_ios, IOW, M, K, (size_t)(J.steps + 1) * 48, J.ca, J.cb, J.d_outs);
   J.mark("program_pads");
