@@ -975,6 +975,70 @@ int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* const* public
                       const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
                       const uint32_t* exps, size_t n_exps, uint32_t* outs_out);
 
+/* Mapped links and the final exponentiation ---------------------------------------------------------- */
+/* On the Fq12 tables a link of a field program may carry a FROBENIUS MAP: the operand is frob(output of node j, m) = (output of
+ * node j)^(p^m), m in 0 .. 11.  The map is linear, so a consuming circuit computes it natively on the public inputs it connects,
+ * and a program need not spend an instance with exponent p (which the u64 table cannot even state) on it.  In the flat basis of
+ * the tables (the coefficient of w^k is a_k = c[k] + c[k+6] i, w^6 = xi = 9 + i) coefficient k of frob(f, m) is
+ * conj^m(a_k) * G[m][k] with G[m][k] = xi^(k (p^m - 1) / 6) in Fq2 (csrc/fq12_frobenius_consts.hpp, written by
+ * tools/gen_fq12_frobenius.py).  m = 0 is the identity, m = 6 the conjugate (G[6][k] = (-1)^k), and p^12 is the identity: maps
+ * compose by adding mod 12.
+ * The two host helpers (no device): sbn_fq12_frobenius, and sbn_fq12_inverse (f^-1 = fbar / (f fbar) with fbar the product of
+ * frob(f, 1 .. 11) and one inversion in Fq).  Both refuse a null pointer, m > 11 and a coefficient >= p, and the inverse refuses
+ * zero, with SBN_ERR_BAD_ARG.  in and out may be the same array. */
+int sbn_fq12_frobenius(const uint32_t in[96], uint32_t m, uint32_t out[96]);
+int sbn_fq12_inverse(const uint32_t in[96], uint32_t out[96]);
+/* A mapped program is a field program whose nodes carry a fourth word:
+ *   maps: bits 0..7 = the map of x, bits 8..15 = the map of offset, each 0 .. 11; bits 16..31 zero.
+ * Each sbn_program_m_* call takes the arguments and gives the outputs of its twin above, and every statement made there holds
+ * with these changes:
+ *   - A node's operand with map m is frob(output of node j, m).  The explicit list holds the MAPPED words in the x / offset fields
+ *     of the row; pads copy row count - 1 as before; the schedule is unchanged (a map adds no level).
+ *   - With every maps == 0 each call gives, word for word, what its twin gives: list, outputs, trace, public inputs, proofs.
+ *   - Refusal 3 grows: node by node, after the existing checks of that node and naming the node and the field,
+ *     SBN_ERR_BAD_ARG for bits 16..31 set, then SBN_ERR_BAD_ARG for a map above 11, then SBN_ERR_BAD_ARG for a non-zero map on an
+ *     operand that is no link (a literal or SBN_NODE_ONE: the caller maps a literal itself, sbn_fq12_frobenius), then, on FQ_EXP,
+ *     SBN_ERR_UNSUPPORTED for any non-zero map (the map is an Fq12 notion; sbn_program_m_levels knows no table and skips this one).
+ *   - sbn_program_m_check is the `connect` calls of a consuming circuit: a mapped operand must equal frob(OUTPUT public inputs of
+ *     node j, m), computed natively by the check, across unit boundaries; everything else as in sbn_program_check.  A failure names
+ *     the instance, the field, the node it should equal and the map ("... differs from frob_m of the output of node j").
+ *   - sbn_prover_generate_trace_program_m, where the chains run on the device: in front of the launch of every level that has a
+ *     mapped operand a small launch (one workgroup per mapped operand) reads the output an EARLIER level wrote, applies the map and
+ *     stores the mapped words into the x / offset words of the node's own row; the level launch then loads that operand as it
+ *     loads a literal.  Links still cross kernel boundaries only.  FQ_EXP and an Fq12 prover created under SBN_FQ12_HOST_CHAIN
+ *     derive on the host pool.  The words are the same in every placement.
+ *
+ * THE FINAL EXPONENTIATION f -> f^((p^12 - 1) / r) of a BN254 pairing is 16 nodes on FQ12_EXP_U64; every exponent is 1, the BN
+ * parameter x (sbn_bn_x) or one of 2, 6, 12, 18, 30, 36.  The literals are f, conj(f) = frob(f, 6) and f_inv = f^-1
+ * (sbn_fq12_inverse); node n below is "output = offset * x^e", frob_m(n) a mapped link, conj = frob_6, e the easy-part result:
+ *    0   f * f_inv^1                  must equal one: the check that f_inv is the inverse
+ *    1   conj(f) * f_inv^1            = f^(p^6 - 1)
+ *    2   frob_2(n1) * n1^1            = e = f^((p^6 - 1)(p^2 + 1)), the easy part
+ *    3   1 * e^x      4   1 * n3^x      5   1 * n4^x        fx, fx2, fx3
+ *    6   frob_1(e) * frob_2(e)^1      7   n6 * frob_3(e)^1  y0
+ *    8   n3 * frob_1(n4)^1            fx * frob(fx2)
+ *    9   n5 * frob_1(n5)^1            fx3 * frob(fx3)
+ *   10   n7 * conj(e)^2
+ *   11   n10 * frob_2(n4)^6
+ *   12   n11 * frob_7(n3)^12          frob_7 = conj o frob_1
+ *   13   n12 * conj(n8)^18
+ *   14   n13 * conj(n4)^30
+ *   15   n14 * conj(n9)^36            = f^((p^12 - 1) / r), the result
+ * since (p^4 - p^2 + 1) / r = l0 + l1 p + l2 p^2 + p^3 with l2 = 6x^2 + 1, l1 = -36x^3 - 18x^2 - 12x + 1,
+ * l0 = -36x^3 - 30x^2 - 18x - 2, and the inverse of an easy-part result is its conjugate.  One unit of Fq12ExpU64Stark(16). */
+typedef struct sbn_program_node_m { uint32_t x, offset, exp, maps; } sbn_program_node_m;
+#define SBN_FINAL_EXP_NODES 16
+int sbn_program_m_levels(const sbn_program_node_m* nodes, size_t count, uint32_t* level_out, uint32_t* depth_out);
+int sbn_program_m_instances(int32_t kind, const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                            const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out);
+int sbn_prover_generate_trace_program_m(sbn_prover* p, const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                        const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out);
+int sbn_batch_prover_prove_program_m(sbn_batch_prover* b, const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                     const uint32_t* exps, size_t n_exps, sbn_proof** proofs_out, uint32_t* outs_out, uint32_t* ios_out);
+int sbn_program_m_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
+                        const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                        const uint32_t* exps, size_t n_exps, uint32_t* outs_out);
+
 /* Curve programs ------------------------------------------------------------------------------------- */
 /* What the field programs above are to the field tables, on the curve tables G1_EXP and G2_EXP (an instance is output = offset +
  * e x): a program is a list of instances whose x and offset are each a literal point or the OUTPUT of an earlier instance.  A

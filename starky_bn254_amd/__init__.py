@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     G2_COFACTOR, generator, scalar_mul_instances, scalar_mul_check, mul_by_cofactor_check, verify_scalar_muls, verify_mul_by_cofactor,
     msm_batch_instances, msm_batch_check, verify_msms,
     START_CANDIDATES, start_candidate, msm_batch_instances_complete,
-    BN_P, BN_X, FQ_INVERSE_EXP, FQ_LEGENDRE_EXP, FQ_SQRT_EXP, bn_x, power_instances, power_check, verify_powers, verify_bn_x_powers, fq_sqrt_flags,
+    BN_P, BN_X, FQ_INVERSE_EXP, FQ_LEGENDRE_EXP, FQ_SQRT_EXP, bn_x, power_instances, power_check, verify_powers, verify_bn_x_powers, FINAL_EXP_NODES, fq12_frobenius, fq12_conjugate, fq12_inverse, final_exponentiation, verify_final_exponentiations, fq_sqrt_flags,
     NODE_OUTPUT, NODE_ONE, Program, program_levels, program_instances, program_check, verify_program,
     NODE_START, CurveProgram, curve_program_instances, curve_program_check, verify_curve_program,
     prover_memory_plan, lde_rows, LDE_STORAGE,

@@ -48,6 +48,8 @@ EXPORTS = [
     "sbn_start_candidate", "sbn_msm_batch_instances_complete", "sbn_prover_generate_trace_msm_batch_complete", "sbn_batch_prover_prove_msm_batch_complete",
     "sbn_bn_x", "sbn_power_instances", "sbn_prover_generate_trace_powers", "sbn_batch_prover_prove_powers", "sbn_power_check",
     "sbn_program_levels", "sbn_program_instances", "sbn_prover_generate_trace_program", "sbn_batch_prover_prove_program", "sbn_program_check",
+    "sbn_fq12_frobenius", "sbn_fq12_inverse",
+    "sbn_program_m_levels", "sbn_program_m_instances", "sbn_prover_generate_trace_program_m", "sbn_batch_prover_prove_program_m", "sbn_program_m_check",
     "sbn_curve_program_instances", "sbn_prover_generate_trace_curve_program", "sbn_batch_prover_prove_curve_program", "sbn_curve_program_check",
     "sbn_prove", "sbn_prove_cache_configure", "sbn_prove_cache_stats", "sbn_first_non_canonical", "sbn_proof_num_words", "sbn_proof_words", "sbn_proof_serialize", "sbn_proof_degree_bits",
     "sbn_proof_free", "sbn_verify", "sbn_commit_values", "sbn_poseidon_permute_batch", "sbn_poseidon_permute_coop_batch", "sbn_poseidon_permute_host", "sbn_field_mul_batch", "sbn_bn254_fq_batch",
@@ -260,6 +262,13 @@ def lib():
         L.sbn_prover_generate_trace_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]
         L.sbn_batch_prover_prove_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp), vp, vp]
         L.sbn_program_check.argtypes = [C.c_int32, sz, C.POINTER(vp), sz, vp, sz, vp, sz, vp, sz, vp]
+        L.sbn_fq12_frobenius.argtypes = [vp, u32, vp]
+        L.sbn_fq12_inverse.argtypes = [vp, vp]
+        L.sbn_program_m_levels.argtypes = L.sbn_program_levels.argtypes
+        L.sbn_program_m_instances.argtypes = L.sbn_program_instances.argtypes
+        L.sbn_prover_generate_trace_program_m.argtypes = L.sbn_prover_generate_trace_program.argtypes
+        L.sbn_batch_prover_prove_program_m.argtypes = L.sbn_batch_prover_prove_program.argtypes
+        L.sbn_program_m_check.argtypes = L.sbn_program_check.argtypes
         L.sbn_curve_program_instances.argtypes = [C.c_int32, vp, sz, vp, sz, vp, sz, sz, vp, vp, vp, vp, vp]
         L.sbn_prover_generate_trace_curve_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp]
         L.sbn_batch_prover_prove_curve_program.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp), vp, vp, vp, vp, vp]
@@ -999,7 +1008,8 @@ NODE_ONE = 0x7FFFFFFF       # offset only: the field's one
 
 
 def _program_args(stark, nodes, values, exps):
-    """nodes (count, 3) uint32 = (x, offset, exp) per node; values (n_values, W) uint32, or Python ints for FqExpStark; exps
+    """nodes (count, 3) uint32 = (x, offset, exp) per node, or (count, 4) with the maps of a mapped program as the fourth word
+    (_program_fn picks the call); values (n_values, W) uint32, or Python ints for FqExpStark; exps
     (n_exps, ew) uint32 or a list of Python ints (little-endian u32 limbs)."""
     w, ew = _power_words(stark)
     nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
@@ -1009,20 +1019,27 @@ def _program_args(stark, nodes, values, exps):
     if not isinstance(exps, np.ndarray) and len(exps) and all(isinstance(e, int) for e in exps):
         exps = [_int_limbs(e, ew) for e in exps]
     exps = np.ascontiguousarray(exps, dtype=np.uint32)
-    if nodes.ndim != 2 or nodes.shape[1] != 3 or values.ndim != 2 or values.shape[1] != w or exps.ndim != 2 or exps.shape[1] != ew:
-        raise SbnError(-1, f"nodes must be [count][3], values [n_values][{w}] and exps [n_exps][{ew}] u32")
+    if nodes.ndim != 2 or nodes.shape[1] not in (3, 4) or values.ndim != 2 or values.shape[1] != w or exps.ndim != 2 or exps.shape[1] != ew:
+        raise SbnError(-1, f"nodes must be [count][3] (or [count][4] with maps), values [n_values][{w}] and exps [n_exps][{ew}] u32")
     return nodes, values, exps, w, ew
+
+
+def _program_fn(nodes, name):
+    """The C call `name` for a node table: (count, 4) nodes, which carry maps, take its sbn_*program_m* twin."""
+    if nodes.shape[1] == 4:
+        name = name + "_m" if name.endswith("_program") else name.replace("sbn_program_", "sbn_program_m_")
+    return getattr(lib(), name)
 
 
 def program_levels(nodes):
     """The schedule of a program (sbn_program_levels): (level, depth), level[g] = 0 for a node without links, otherwise 1 + the
     largest level of the nodes it links to; depth = 1 + the largest level.  Structure only; no device needed."""
     nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
-    if nodes.ndim != 2 or nodes.shape[1] != 3:
-        raise SbnError(-1, "nodes must be [count][3] u32")
+    if nodes.ndim != 2 or nodes.shape[1] not in (3, 4):
+        raise SbnError(-1, "nodes must be [count][3] u32 (or [count][4] with maps)")
     level = np.zeros(nodes.shape[0], dtype=np.uint32)
     depth = C.c_uint32(0)
-    _check(lib().sbn_program_levels(_ptr(nodes), nodes.shape[0], _ptr(level), C.addressof(depth)))
+    _check(_program_fn(nodes, "sbn_program_levels")(_ptr(nodes), nodes.shape[0], _ptr(level), C.addressof(depth)))
     return level, int(depth.value)
 
 
@@ -1038,7 +1055,7 @@ def program_instances(stark, nodes, values, exps):
     units = msm_num_units(count, stark.num_io)
     ios = np.zeros((units, stark.num_io, 2 * w + ew), dtype=np.uint32)
     outs = np.zeros((count, w), dtype=np.uint32)
-    _check(lib().sbn_program_instances(stark.kind, _ptr(nodes), count, _ptr(values), values.shape[0], _ptr(exps), exps.shape[0], stark.num_io,
+    _check(_program_fn(nodes, "sbn_program_instances")(stark.kind, _ptr(nodes), count, _ptr(values), values.shape[0], _ptr(exps), exps.shape[0], stark.num_io,
                                        _ptr(ios), _ptr(outs)))
     return ios, outs
 
@@ -1051,7 +1068,7 @@ def program_check(stark, public_inputs_per_unit, nodes, values, exps):
     nodes, values, exps, w, ew = _program_args(stark, nodes, values, exps)
     pis, ptrs, n = _unit_public_inputs(stark, public_inputs_per_unit)
     outs = np.zeros((nodes.shape[0], w), dtype=np.uint32)
-    _check(lib().sbn_program_check(stark.kind, stark.num_io, ptrs, n, _ptr(nodes), nodes.shape[0], _ptr(values), values.shape[0],
+    _check(_program_fn(nodes, "sbn_program_check")(stark.kind, stark.num_io, ptrs, n, _ptr(nodes), nodes.shape[0], _ptr(values), values.shape[0],
                                    _ptr(exps), exps.shape[0], _ptr(outs)))
     return outs
 
@@ -1060,13 +1077,15 @@ class Program:
     """A small builder of programs for the field Exp table `stark`.  value(v) and pow / mul / pow_big return handles; a handle or a
     literal (W uint32 words; a Python int for FqExpStark) is accepted wherever an operand is.  Equal literals share one slot of
     `values`, equal exponents one slot of `exps`.  arrays() gives (nodes, values, exps) as program_instances,
-    Prover.generate_trace_program, BatchProver.prove_program and verify_program take them; a node handle h is node h.node."""
+    Prover.generate_trace_program, BatchProver.prove_program and verify_program take them; a node handle h is node h.node.
+    On the Fq12 tables frobenius(h, m) and conj(h) give the handle of h^(p^m): a mapped link (include/sbn.h, "Mapped links and the
+    final exponentiation") when h is a node, a new literal when h is one."""
 
     class Handle:
-        __slots__ = ("ref", "node")
+        __slots__ = ("ref", "node", "map")
 
-        def __init__(self, ref, node=None):
-            self.ref, self.node = ref, node
+        def __init__(self, ref, node=None, map=0):
+            self.ref, self.node, self.map = ref, node, map
 
     def __init__(self, stark):
         self.stark = stark
@@ -1099,10 +1118,26 @@ class Program:
     def pow(self, x, e, offset=None):
         """The node offset * x^e (offset None: one); e a Python int that fits the exponent field, or its ew words."""
         x = self.value(x)
-        off = NODE_ONE if offset is None else self.value(offset).ref
-        self._nodes.append((x.ref, off, self._exp(e)))
+        off = Program.Handle(NODE_ONE) if offset is None else self.value(offset)
+        self._nodes.append((x.ref, off.ref, self._exp(e), x.map | (off.map << 8)))
         g = len(self._nodes) - 1
         return Program.Handle(NODE_OUTPUT | g, g)
+
+    def frobenius(self, h, m):
+        """h^(p^m), the Frobenius map m of an Fq12 operand; maps compose mod 12.  On a node handle the map rides on the link (it costs
+        no node); on a literal it is applied here (fq12_frobenius) and the result interned as a literal."""
+        if self.w != 96:
+            raise SbnError(-7, "a Frobenius map is an Fq12 notion: Fq12ExpStark and Fq12ExpU64Stark")
+        h, m = self.value(h), int(m) % 12
+        if h.ref & NODE_OUTPUT:
+            return Program.Handle(h.ref, h.node, (h.map + m) % 12)
+        if h.ref == NODE_ONE or m == 0:
+            return h
+        return self.value(fq12_frobenius(self._values[h.ref], m))
+
+    def conj(self, h):
+        """The conjugate h^(p^6)."""
+        return self.frobenius(h, 6)
 
     def mul(self, a, b):
         """The product a * b: pow(a, 1, offset=b)."""
@@ -1127,9 +1162,110 @@ class Program:
         return len(self._nodes)
 
     def arrays(self):
-        """(nodes (count, 3), values (n_values, W), exps (n_exps, ew)), uint32."""
-        return (np.array(self._nodes, dtype=np.uint32).reshape(-1, 3), np.array(self._values, dtype=np.uint32).reshape(-1, self.w),
-                np.array(self._exps, dtype=np.uint32).reshape(-1, self.ew))
+        """(nodes (count, 3), values (n_values, W), exps (n_exps, ew)), uint32; nodes (count, 4), the maps as the fourth word, when
+        some link carries a map."""
+        nodes = np.array(self._nodes, dtype=np.uint32).reshape(-1, 4)
+        if not nodes[:, 3].any():
+            nodes = np.ascontiguousarray(nodes[:, :3])
+        return (nodes, np.array(self._values, dtype=np.uint32).reshape(-1, self.w), np.array(self._exps, dtype=np.uint32).reshape(-1, self.ew))
+
+
+# ---- mapped links and the final exponentiation (include/sbn.h, "Mapped links and the final exponentiation") -----------------------
+FINAL_EXP_NODES = 16        # SBN_FINAL_EXP_NODES
+_FQ12_ONE = np.array([1] + [0] * 95, dtype=np.uint32)
+
+
+def _fq12_words(f):
+    f = np.ascontiguousarray(f, dtype=np.uint32).reshape(-1)
+    if f.shape[0] != 96:
+        raise SbnError(-1, "an Fq12 element has 96 u32 words")
+    return f
+
+
+def fq12_frobenius(f, m):
+    """f^(p^m) for an Fq12 element in the flat basis (96 u32 words), m in 0 .. 11 (sbn_fq12_frobenius).  No device needed."""
+    f, out = _fq12_words(f), np.zeros(96, dtype=np.uint32)
+    if not 0 <= int(m) <= 0xFFFFFFFF:
+        raise SbnError(-1, "a Frobenius map is 0 .. 11")
+    _check(lib().sbn_fq12_frobenius(_ptr(f), int(m), _ptr(out)))
+    return out
+
+
+def fq12_conjugate(f):
+    """The conjugate f^(p^6)."""
+    return fq12_frobenius(f, 6)
+
+
+def fq12_inverse(f):
+    """f^-1 in Fq12 (sbn_fq12_inverse); zero is refused.  No device needed."""
+    f, out = _fq12_words(f), np.zeros(96, dtype=np.uint32)
+    _check(lib().sbn_fq12_inverse(_ptr(f), _ptr(out)))
+    return out
+
+
+def final_exponentiation(pg, f, f_inv=None):
+    """Appends the FINAL_EXP_NODES = 16 nodes of the final exponentiation f -> f^((p^12 - 1) / r) to the program `pg` on
+    Fq12ExpU64Stark, by the node table of include/sbn.h.  f: 96 u32 words; f_inv (default fq12_inverse(f)) is a claim the first node
+    checks.  Returns (check, result) handles: the output of `check` must be one, the output of `result` is the value."""
+    if getattr(pg.stark, "kind", None) != AIR_FQ12_EXP_U64:
+        raise SbnError(-1, "the final exponentiation is a program of Fq12ExpU64Stark")
+    f = _fq12_words(f)
+    fi = pg.value(fq12_inverse(f) if f_inv is None else _fq12_words(f_inv))
+    fv, F, cj = pg.value(f), pg.frobenius, pg.conj
+    check = pg.pow(fi, 1, offset=fv)                        # 0
+    n1 = pg.pow(fi, 1, offset=cj(fv))                       # 1
+    e = pg.pow(n1, 1, offset=F(n1, 2))                      # 2: the easy part
+    fx = pg.pow(e, BN_X)                                    # 3
+    fx2 = pg.pow(fx, BN_X)                                  # 4
+    fx3 = pg.pow(fx2, BN_X)                                 # 5
+    n6 = pg.pow(F(e, 2), 1, offset=F(e, 1))                 # 6
+    n7 = pg.pow(F(e, 3), 1, offset=n6)                      # 7
+    n8 = pg.pow(F(fx2, 1), 1, offset=fx)                    # 8
+    n9 = pg.pow(F(fx3, 1), 1, offset=fx3)                   # 9
+    acc = pg.pow(cj(e), 2, offset=n7)                       # 10
+    acc = pg.pow(F(fx2, 2), 6, offset=acc)                  # 11
+    acc = pg.pow(F(fx, 7), 12, offset=acc)                  # 12
+    acc = pg.pow(cj(n8), 18, offset=acc)                    # 13
+    acc = pg.pow(cj(fx2), 30, offset=acc)                   # 14
+    return check, pg.pow(cj(n9), 36, offset=acc)            # 15
+
+
+def _final_exp_program(stark, fs, f_invs):
+    fs = np.ascontiguousarray(fs, dtype=np.uint32).reshape(-1, 96)
+    if f_invs is not None:
+        f_invs = np.ascontiguousarray(f_invs, dtype=np.uint32).reshape(-1, 96)
+        if f_invs.shape[0] != fs.shape[0]:
+            raise SbnError(-1, "one f_inv per f")
+    pg = Program(stark)
+    for t in range(fs.shape[0]):
+        final_exponentiation(pg, fs[t], None if f_invs is None else f_invs[t])
+    return pg.arrays()
+
+
+def verify_final_exponentiations(stark, config, proofs, fs, verifier=None):
+    """Verifies the unit proofs of BatchProver.prove_final_exponentiations (host verifier, or a Verifier of the table in batches),
+    reads the inverse of input t from the x public inputs of node 16 t, runs program_check on the program rebuilt from `fs` and
+    those inverses, and requires the output of every node 16 t to be one.  Returns the results (count, 96); raises SbnError
+    naming the unit, the instance and field, or the input whose inverse is none."""
+    proofs = list(proofs)
+    fs = np.ascontiguousarray(fs, dtype=np.uint32).reshape(-1, 96)
+    _verify_units(stark, config, proofs, verifier)
+    pis = [np.asarray(p.public_inputs(), dtype=np.uint64) for p in proofs]
+    if len(pis) != msm_num_units(FINAL_EXP_NODES * fs.shape[0], stark.num_io):
+        raise SbnError(-6, f"{len(pis)} units given, {fs.shape[0]} final exponentiations have {msm_num_units(FINAL_EXP_NODES * fs.shape[0], stark.num_io)}")
+    f_invs = np.zeros_like(fs)
+    for t in range(fs.shape[0]):
+        g = FINAL_EXP_NODES * t
+        x = pis[g // stark.num_io].reshape(stark.num_io, -1)[g % stark.num_io, :192]   # 16-bit limbs, low first
+        if (x >> np.uint64(16)).any():
+            raise SbnError(-6, f"input {t}: an x limb of instance {g} is out of range")
+        f_invs[t] = (x[0::2] | (x[1::2] << np.uint64(16))).astype(np.uint32)
+    nodes, values, exps = _final_exp_program(stark, fs, f_invs)
+    outs = program_check(stark, pis, nodes, values, exps)
+    for t in range(fs.shape[0]):
+        if not np.array_equal(outs[FINAL_EXP_NODES * t], _FQ12_ONE):
+            raise SbnError(-6, f"input {t}: f * f_inv is not one (the output of node {FINAL_EXP_NODES * t}), so the x of that node is no inverse of f")
+    return outs[FINAL_EXP_NODES - 1::FINAL_EXP_NODES].copy()
 
 
 # ---- curve programs (include/sbn.h, "Curve programs") ---------------------------------------------------------------------------
@@ -2028,7 +2164,7 @@ class Prover:
         pi = np.zeros(self.stark.num_public_inputs, dtype=np.uint64)
         outs = np.zeros((nodes.shape[0], w), dtype=np.uint32)
         ios = np.zeros((self.stark.num_io, 2 * w + ew), dtype=np.uint32)
-        _check(lib().sbn_prover_generate_trace_program(self._h, _ptr(nodes), nodes.shape[0], _ptr(values), values.shape[0], _ptr(exps), exps.shape[0],
+        _check(_program_fn(nodes, "sbn_prover_generate_trace_program")(self._h, _ptr(nodes), nodes.shape[0], _ptr(values), values.shape[0], _ptr(exps), exps.shape[0],
                                                        _ptr(pi), _ptr(outs), _ptr(ios)))
         return pi, outs, ios
 
@@ -2351,9 +2487,17 @@ class BatchProver:
         count = nodes.shape[0]
         ios, out = self._unit_buffers(count, 2 * w + ew)
         outs = np.zeros((count, w), dtype=np.uint32)
-        _check(lib().sbn_batch_prover_prove_program(self._h, _ptr(nodes), count, _ptr(values), values.shape[0], _ptr(exps), exps.shape[0],
+        _check(_program_fn(nodes, "sbn_batch_prover_prove_program")(self._h, _ptr(nodes), count, _ptr(values), values.shape[0], _ptr(exps), exps.shape[0],
                                                     out, _ptr(outs), _ptr(ios)))
         return self._proofs(out, len(ios)), outs, ios
+
+    def prove_final_exponentiations(self, fs, f_invs=None):
+        """The final exponentiations f^((p^12 - 1) / r) of fs ((count, 96) uint32) as one program of 16 * count nodes through
+        prove_program (final_exponentiation; links never leave their own 16 nodes); f_invs default to fq12_inverse.  Returns
+        (proofs, results, ios), results (count, 96).  A Fq12ExpU64Stark batch prover only."""
+        nodes, values, exps = _final_exp_program(self.stark, fs, f_invs)
+        proofs, outs, ios = self.prove_program(nodes, values, exps)
+        return proofs, outs[FINAL_EXP_NODES - 1::FINAL_EXP_NODES].copy(), ios
 
     def prove_curve_program(self, nodes, points, exps):
         """A curve program of any count (arguments as curve_program_instances) proved as units of the table, the last one padded

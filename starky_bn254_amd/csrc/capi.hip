@@ -334,6 +334,17 @@ int sbn_batch_prover_prove_program(sbn_batch_prover* B, const sbn_program_node* 
   });
 }
 
+// Mapped programs of any count (include/sbn.h, "Mapped links and the final exponentiation"): the list holds the mapped words, so the
+// units go through the same loop.
+int sbn_batch_prover_prove_program_m(sbn_batch_prover* B, const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                     const uint32_t* exps, size_t n_exps, sbn_proof** proofs_out, uint32_t* outs_out, uint32_t* ios_out) {
+  if (!B || !proofs_out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  const bool fits = count && count < 0x7fffffffu;   // (as above: sbn_program_m_instances refuses what does not fit)
+  return prove_derived_units(B, fits ? sbn_msm_num_units(count, B->num_io) : 0, ios_out, proofs_out, [&](uint32_t* ios) {
+    return sbn_program_m_instances(B->kind, nodes, count, values, n_values, exps, n_exps, B->num_io, ios, outs_out);
+  });
+}
+
 // Curve programs of any count (include/sbn.h, "Curve programs"; csrc/curve_program.hip): the start, every link, the outputs and the
 // values are derived with the list.
 int sbn_batch_prover_prove_curve_program(sbn_batch_prover* B, const sbn_program_node* nodes, size_t count, const uint32_t* points, size_t n_points,

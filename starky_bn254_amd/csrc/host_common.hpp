@@ -220,7 +220,10 @@ struct ProgramPlan {
   size_t depth() const { return level_start.size() - 1; }
 };
 int program_plan(int kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values, const uint32_t* exps, size_t n_exps,
-                 size_t num_io, ProgramPlan& plan);
+                 size_t num_io, ProgramPlan& plan, const uint32_t* maps = nullptr);
+// sbn_program_instances / sbn_program_m_instances: maps (optional, [count]) = the fourth word of every sbn_program_node_m
+int program_instances(int kind, const sbn_program_node* nodes, const uint32_t* maps, size_t count, const uint32_t* values, size_t n_values,
+                      const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out);
 // curve_program.hip (include/sbn.h, "Curve programs"): refusals 1 to 4 of the header in its order and the schedule of
 // sbn_program_levels as a ProgramPlan; the negated blinds -T_g of the nodes from candidate `choice` ([count][16E] u32 affine words,
 // zero where flag[g] = 1: T_g is the point at infinity), level by level on the host pool

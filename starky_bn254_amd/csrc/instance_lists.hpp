@@ -49,6 +49,28 @@ template <int N> void field_power(const Fq* x, const uint32_t* e, int bits, Fq* 
   memcpy(out, b, sizeof b);
 }
 
+// The Frobenius maps of Fq12 in the flat basis (include/sbn.h, "Mapped links and the final exponentiation"): out = in^(p^m), m < 12.
+// Coefficient k of w^k is a_k = c[k] + c[k+6] i; it becomes conj^m(a_k) * G[m][k], G[m][k] = (9 + i)^(k (p^m - 1) / 6) the table of
+// tools/gen_fq12_frobenius.py.  Montgomery form in and out; out may be in.
+inline void fq12_frobenius_m(const Fq* in, unsigned m, Fq* out) {
+  static const u64 G[12][6][2][4] = {
+#include "fq12_frobenius_consts.hpp"
+  };
+  for (int k = 0; k < 6; k++) {
+    const Fq re = in[k], im = (m & 1) ? fsub(Fq{{0, 0, 0, 0}}, in[k + 6]) : in[k + 6];
+    const Fq g0 = to_m(G[m][k][0]), g1 = to_m(G[m][k][1]);
+    out[k] = fsub(mmul(re, g0), mmul(im, g1));
+    out[k + 6] = fadd(mmul(re, g1), mmul(im, g0));
+  }
+}
+// the same on the u32 words of an element (every coefficient < p)
+inline void fq12_frobenius_words(const uint32_t* in, unsigned m, uint32_t* out) {
+  Fq v[12];
+  field_load<12>(in, v);
+  fq12_frobenius_m(v, m, v);
+  field_store<12>(v, out);
+}
+
 // rows [M, total) <- row M - 1: the reference's resize rule (src/curves/g1/circuit.rs:273-277), a pad row is the last row again
 inline void pad_rows(uint32_t* ios, size_t IOW, size_t M, size_t total) {
   for (size_t g = M; g < total; g++) memcpy(ios + IOW * g, ios + IOW * (M - 1), IOW * sizeof(uint32_t));
@@ -129,6 +151,13 @@ struct UnitInputs {
 // ---- programs (program.hip, curve_program.hip, and their device drivers in tracegen_device.hip) ------------------------------------
 inline bool linked(uint32_t v) { return (v & SBN_NODE_OUTPUT) != 0; }
 inline uint32_t link_of(uint32_t v) { return v & ~SBN_NODE_OUTPUT; }
+// mapped programs: maps[g] = the map of x (bits 0..7) | the map of offset << 8 of node g; a null table is all zeros
+inline unsigned map_of(const uint32_t* maps, size_t g, int f) { return maps ? (maps[g] >> (8 * f)) & 0xffu : 0u; }
+// the unmapped twin of a mapped node table, and its maps
+inline void split_nodes(const sbn_program_node_m* nodes, size_t count, std::vector<sbn_program_node>& plain, std::vector<uint32_t>& maps) {
+  plain.resize(count); maps.resize(count);
+  for (size_t g = 0; g < count; g++) { plain[g] = sbn_program_node{nodes[g].x, nodes[g].offset, nodes[g].exp}; maps[g] = nodes[g].maps; }
+}
 
 // The schedule from level[count] (sbn_program_levels): a stable counting sort, so plan.order lists the nodes of level l in node
 // order at [level_start[l], level_start[l + 1]).  rows > count: rows [count, rows) are pads, scheduled as further nodes of the level
@@ -148,11 +177,14 @@ inline void fill_plan(const uint32_t* level, size_t count, size_t rows, ProgramP
 // The link checks behind sbn_program_check and sbn_curve_program_check, in instance order: a pad is instance count - 1 again; x and
 // offset equal the output of the node they link to, or the words of their literal in `literals`, or what sentinel(op, what) returns
 // for an operand that is neither (one, the start; null: op is a literal index), `what` the tail of its refusal; the exponent is the
-// caller's; judge_output(g) has the last word on the output of instance g.
+// caller's; judge_output(g) has the last word on the output of instance g.  maps (optional, field programs on Fq12): a linked
+// operand with map m equals frob(output of node j, m), computed here from the OUTPUT public inputs of node j (instance order:
+// judge_output(j) has accepted them).
 template <typename Sentinel, typename Judge>
 int check_program_links(const UnitInputs& U, const sbn_program_node* nodes, size_t count, const uint32_t* literals, const uint32_t* exps, Sentinel sentinel,
-                        Judge judge_output) {
+                        Judge judge_output, const uint32_t* maps = nullptr) {
   const PiLayout& L = U.L;
+  std::vector<uint32_t> mapped(maps ? L.xw : 0);
   for (size_t g = 0; g < U.rows(); g++) {
     if (g >= count) { if (int rc = U.pad(g, count - 1)) return rc; continue; }
     const uint32_t op[2] = {nodes[g].x, nodes[g].offset};
@@ -160,7 +192,14 @@ int check_program_links(const UnitInputs& U, const sbn_program_node* nodes, size
     static const char* const field[2] = {"x", "offset"};
     for (int f = 0; f < 2; f++) {
       const char* what = nullptr;
-      if (linked(op[f])) {
+      if (const unsigned m = linked(op[f]) ? map_of(maps, g, f) : 0u) {
+        size_t limb;
+        if (!U.output(link_of(op[f]), mapped.data(), &limb))
+          return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s is frob_%u of the output of node %u, whose limb %zu is out of range", g, field[f], m, link_of(op[f]), limb);
+        fq12_frobenius_words(mapped.data(), m, mapped.data());
+        if (!U.value_is(g, at[f], mapped.data()))
+          return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from frob_%u of the output of node %u", g, field[f], m, link_of(op[f]));
+      } else if (linked(op[f])) {
         if (!same(U.inst(g) + at[f], U.inst(link_of(op[f])) + U.oOut, L.W))
           return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: %s differs from the output of node %u", g, field[f], link_of(op[f]));
       } else if (const uint32_t* w = sentinel(op[f], &what)) {

@@ -1560,6 +1560,45 @@ __global__ void __launch_bounds__(320) fq12_program_level_kernel(uint32_t* ios, 
   }
 }
 
+// ---- mapped links (sbn_prover_generate_trace_program_m): x / offset of an instance = frob(output of an earlier one, m) -------------
+// A pre-pass in FRONT of the level launch of every level that has a mapped operand; fq12_program_level_kernel above stays as it is.
+// One workgroup per (node of the level, mapped operand): the twelve coefficient lanes read the standard-form output of node j from
+// `outs`, which the launch of an EARLIER level wrote, apply f -> f^(p^m) in the flat basis -- coefficient k of w^k is the Fq2
+// element a_k = c[k] + c[k+6] i and becomes conj^m(a_k) * G[m][k] (include/sbn.h, "Mapped links"): lanes k and k + 6 exchange their
+// halves over LDS and each folds its half of the Fq2 product -- and store the mapped words into the x / offset words of the node's
+// own `ios` row.  The host has marked that operand as a literal in the device copy of the node table, so the level launch behind
+// this one loads it as it loads a literal.  The rule of the level kernel is kept: this launch reads what launches of earlier
+// levels stored and stores what only later launches read -- no flag, no spin, no fence; the barrier orders LDS only.
+//   tbl: [gridDim.x][4] = (node k, 0: x / 1: offset, node j, map m); k < K, j < k, 1 <= m <= 11 (program_plan refuses the rest)
+__device__ const u64 FQ12_FROBENIUS_G[12][6][2][4] = {
+#include "fq12_frobenius_consts.hpp"
+};
+__global__ void __launch_bounds__(64) fq12_program_map_kernel(uint32_t* ios, size_t iow, const uint32_t* __restrict__ tbl, const u64* __restrict__ outs) {
+  __shared__ Fq V[12];
+  const uint32_t* e = tbl + 4 * (size_t)blockIdx.x;
+  const uint32_t m = e[3];
+  const int c = threadIdx.x;
+  Fq own;
+  if (c < 12) {
+    u64 t4[4];
+    const u64* o = outs + ((size_t)e[2] * 12 + c) * 4;
+    for (int i = 0; i < 4; i++) t4[i] = o[i];
+    own = to_m(t4);
+    if (c >= 6 && (m & 1)) own = fsub(Fq{{0, 0, 0, 0}}, own);   // conj^m: the imaginary half changes sign for an odd m
+    V[c] = own;
+  }
+  __syncthreads();
+  if (c < 12) {
+    const int k = c % 6;
+    const Fq other = V[c < 6 ? c + 6 : c - 6];
+    const Fq a = mmul(own, to_m(FQ12_FROBENIUS_G[m][k][0])), b = mmul(other, to_m(FQ12_FROBENIUS_G[m][k][1]));
+    u64 s4[4];
+    from_m(c < 6 ? fsub(a, b) : fadd(a, b), s4);   // re = re g0 - im g1, im = im g0 + re g1
+    uint32_t* w8 = ios + iow * e[0] + 96 * e[1] + 8 * c;
+    for (int w = 0; w < 8; w++) w8[w] = (uint32_t)(s4[w >> 1] >> (32 * (w & 1)));
+  }
+}
+
 // ---- curve programs (sbn_prover_generate_trace_curve_program): x and offset of an instance = a literal point, the start, or the ------
 // ---- output of an earlier instance --------------------------------------------------------------------------------------------------
 // The field programs above on G1 / G2 (E = 1 / 2).  The host sorts the nodes by level, so the nodes of one level are independent

@@ -8,7 +8,10 @@
 //    (kernels_tracegen.cuh, "field programs");
 //  * sbn_program_instances builds the explicit, padded, unit-cut list and the outputs on the host pool by the table's own walk;
 //  * sbn_program_check reads the public inputs of the unit proofs and states the links a circuit would `connect`.  It verifies no
-//    proof.
+//    proof;
+//  * the sbn_program_m_* twins take nodes with a fourth word, the Frobenius maps of x and offset (include/sbn.h, "Mapped links and
+//    the final exponentiation"): an entry point splits them into the unmapped nodes and a vector of maps, and everything behind it
+//    takes (nodes, maps), maps null for the unmapped calls; sbn_fq12_frobenius and sbn_fq12_inverse are the host helpers.
 // Host code only: no kernel is launched from this unit (tracegen_device.hip holds the device form).
 #include "instance_lists.hpp"
 
@@ -21,8 +24,9 @@ using namespace sbn::curve_host;
 constexpr size_t INDEX_LIMIT = 0x7fffffffu;   // count, n_values and n_exps stay below SBN_NODE_ONE: an index never reads as a link or as one
 
 // Refusal 3 of the header, node by node; no_bound: structure only (sbn_program_levels knows no n_values and no n_exps).  Fills
-// level[count] (optional) and *depth.
-int walk_nodes(const sbn_program_node* nodes, size_t count, size_t n_values, size_t n_exps, bool no_bound, uint32_t* level, uint32_t* depth) {
+// level[count] (optional) and *depth.  maps (optional, [count]): the added refusals of a mapped program, node by node behind the
+// existing ones of that node; fq: the table is FQ_EXP, which takes no map (sbn_program_m_levels knows no table: false).
+int walk_nodes(const sbn_program_node* nodes, const uint32_t* maps, bool fq, size_t count, size_t n_values, size_t n_exps, bool no_bound, uint32_t* level, uint32_t* depth) {
   std::vector<uint32_t> own;
   if (!level) { own.resize(count); level = own.data(); }
   uint32_t deepest = 0;
@@ -37,6 +41,13 @@ int walk_nodes(const sbn_program_node* nodes, size_t count, size_t n_values, siz
           return fail(SBN_ERR_BAD_ARG, "node %zu: %s is literal %u of %zu", g, field[f], op[f], n_values);
     if (op[0] == SBN_NODE_ONE) return fail(SBN_ERR_BAD_ARG, "node %zu: x is SBN_NODE_ONE, which only an offset may be", g);
     if (!no_bound && nodes[g].exp >= n_exps) return fail(SBN_ERR_BAD_ARG, "node %zu: exponent is index %u of %zu", g, nodes[g].exp, n_exps);
+    if (maps && maps[g]) {
+      if (maps[g] >> 16) return fail(SBN_ERR_BAD_ARG, "node %zu: maps has bits 16..31 set (0x%08x)", g, maps[g]);
+      for (int f = 0; f < 2; f++) if (map_of(maps, g, f) > 11) return fail(SBN_ERR_BAD_ARG, "node %zu: the map of %s is %u, a Frobenius map is 0 .. 11", g, field[f], map_of(maps, g, f));
+      for (int f = 0; f < 2; f++)
+        if (map_of(maps, g, f) && !linked(op[f])) return fail(SBN_ERR_BAD_ARG, "node %zu: %s carries map %u and is no link (the caller maps a literal itself)", g, field[f], map_of(maps, g, f));
+      if (fq) return fail(SBN_ERR_UNSUPPORTED, "node %zu: %s carries map %u, and a Frobenius map is an Fq12 notion (FQ_EXP takes none)", g, field[map_of(maps, g, 0) ? 0 : 1], map_of(maps, g, map_of(maps, g, 0) ? 0 : 1));
+    }
     uint32_t l = 0;
     for (int f = 0; f < 2; f++) if (linked(op[f]) && level[link_of(op[f])] + 1 > l) l = level[link_of(op[f])] + 1;
     level[g] = l;
@@ -73,7 +84,7 @@ int check_used_values(int kind, const sbn_program_node* nodes, size_t count, con
 
 // the nodes, level by level; out: [count][N] Montgomery outputs; rows [0, count) of ios (optional) and outs (optional, [count][8N])
 template <int N>
-void run_levels(const PiLayout& t, const ProgramPlan& plan, const sbn_program_node* nodes, const uint32_t* values, const uint32_t* exps, uint32_t* ios, uint32_t* outs) {
+void run_levels(const PiLayout& t, const ProgramPlan& plan, const sbn_program_node* nodes, const uint32_t* maps, const uint32_t* values, const uint32_t* exps, uint32_t* ios, uint32_t* outs) {
   const size_t W = t.xw, ew = t.ew, IOW = t.IOW();
   std::vector<Fq> out(plan.order.size() * N);
   for (size_t l = 0; l < plan.depth(); l++) {
@@ -88,6 +99,10 @@ void run_levels(const PiLayout& t, const ProgramPlan& plan, const sbn_program_no
       if (linked(nd.offset)) memcpy(off, out.data() + (size_t)N * link_of(nd.offset), sizeof off);
       else if (nd.offset == SBN_NODE_ONE) { for (int c = 0; c < N; c++) off[c] = Fq{{0, 0, 0, 0}}; off[0] = fq_one(); }
       else field_load<N>(values + W * nd.offset, off);
+      if (N == 12) {   // a mapped link (walk_nodes: only a link carries a map, and only on the Fq12 tables)
+        if (const unsigned m = map_of(maps, g, 0)) fq12_frobenius_m(x, m, x);
+        if (const unsigned m = map_of(maps, g, 1)) fq12_frobenius_m(off, m, off);
+      }
       if (ios) {
         uint32_t* io = ios + IOW * g;
         field_store<N>(x, io);
@@ -104,10 +119,10 @@ void run_levels(const PiLayout& t, const ProgramPlan& plan, const sbn_program_no
 
 namespace sbn {
 int program_plan(int kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values, const uint32_t* exps, size_t n_exps,
-                 size_t num_io, ProgramPlan& plan) {
+                 size_t num_io, ProgramPlan& plan, const uint32_t* maps) {
   if (int rc = check_args(kind, nodes, values, exps, count, n_values, n_exps, num_io)) return rc;
   plan.level.resize(count);
-  if (int rc = walk_nodes(nodes, count, n_values, n_exps, false, plan.level.data(), nullptr)) return rc;
+  if (int rc = walk_nodes(nodes, maps, kind == SBN_AIR_FQ_EXP, count, n_values, n_exps, false, plan.level.data(), nullptr)) return rc;
   if (int rc = check_used_values(kind, nodes, count, values, n_values, exps, n_exps)) return rc;
   fill_plan(plan.level.data(), count, count, plan);
   return SBN_OK;
@@ -117,25 +132,52 @@ int program_plan(int kind, const sbn_program_node* nodes, size_t count, const ui
 extern "C" int sbn_program_levels(const sbn_program_node* nodes, size_t count, uint32_t* level_out, uint32_t* depth_out) {
   if (!nodes || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no node");
   if (count >= INDEX_LIMIT) return fail(SBN_ERR_BAD_ARG, "count must be below 2^31 - 1");
-  return walk_nodes(nodes, count, 0, 0, true, level_out, depth_out);
+  return walk_nodes(nodes, nullptr, false, count, 0, 0, true, level_out, depth_out);
+}
+extern "C" int sbn_program_m_levels(const sbn_program_node_m* nodes, size_t count, uint32_t* level_out, uint32_t* depth_out) {
+  if (!nodes || count == 0) return fail(SBN_ERR_BAD_ARG, "null argument or no node");
+  if (count >= INDEX_LIMIT) return fail(SBN_ERR_BAD_ARG, "count must be below 2^31 - 1");
+  std::vector<sbn_program_node> plain; std::vector<uint32_t> maps;
+  split_nodes(nodes, count, plain, maps);
+  return walk_nodes(plain.data(), maps.data(), false, count, 0, 0, true, level_out, depth_out);
 }
 
-extern "C" int sbn_program_instances(int32_t kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
-                                     const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out) {
+namespace sbn {
+int program_instances(int kind, const sbn_program_node* nodes, const uint32_t* maps, size_t count, const uint32_t* values, size_t n_values,
+                      const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out) {
   ProgramPlan plan;
-  if (int rc = program_plan((int)kind, nodes, count, values, n_values, exps, n_exps, num_io, plan)) return rc;
-  const PiLayout t = pi_layout((int)kind);
-  if (t.values() == 1) run_levels<1>(t, plan, nodes, values, exps, ios_out, outs_out);
-  else run_levels<12>(t, plan, nodes, values, exps, ios_out, outs_out);
+  if (int rc = program_plan(kind, nodes, count, values, n_values, exps, n_exps, num_io, plan, maps)) return rc;
+  const PiLayout t = pi_layout(kind);
+  if (t.values() == 1) run_levels<1>(t, plan, nodes, maps, values, exps, ios_out, outs_out);
+  else run_levels<12>(t, plan, nodes, maps, values, exps, ios_out, outs_out);
   if (ios_out) pad_rows(ios_out, t.IOW(), count, sbn_msm_num_units(count, num_io) * num_io);
   return SBN_OK;
 }
+}  // namespace sbn
 
-extern "C" int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
-                                 const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
-                                 const uint32_t* exps, size_t n_exps, uint32_t* outs_out) {
+extern "C" int sbn_program_instances(int32_t kind, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                     const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out) {
+  return program_instances((int)kind, nodes, nullptr, count, values, n_values, exps, n_exps, num_io, ios_out, outs_out);
+}
+// The unmapped twin of a mapped node table for the two calls below.  A table that refusal 2 turns away (null, empty, too long) is
+// not split: it goes on as it is, null or not, and is refused there before a node is read.
+static const sbn_program_node* split_or_pass(const sbn_program_node_m* nodes, size_t count, std::vector<sbn_program_node>& plain, std::vector<uint32_t>& maps) {
+  if (!nodes || count == 0 || count >= INDEX_LIMIT) return (const sbn_program_node*)nodes;
+  split_nodes(nodes, count, plain, maps);
+  return plain.data();
+}
+extern "C" int sbn_program_m_instances(int32_t kind, const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                       const uint32_t* exps, size_t n_exps, size_t num_io, uint32_t* ios_out, uint32_t* outs_out) {
+  std::vector<sbn_program_node> plain; std::vector<uint32_t> maps;
+  const sbn_program_node* twin = split_or_pass(nodes, count, plain, maps);
+  return program_instances((int)kind, twin, maps.data(), count, values, n_values, exps, n_exps, num_io, ios_out, outs_out);
+}
+
+static int program_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
+                         const sbn_program_node* nodes, const uint32_t* maps, size_t count, const uint32_t* values, size_t n_values,
+                         const uint32_t* exps, size_t n_exps, uint32_t* outs_out) {
   if (int rc = check_args(kind, nodes, values, exps, count, n_values, n_exps, num_io)) return rc;
-  if (int rc = walk_nodes(nodes, count, n_values, n_exps, false, nullptr, nullptr)) return rc;
+  if (int rc = walk_nodes(nodes, maps, kind == SBN_AIR_FQ_EXP, count, n_values, n_exps, false, nullptr, nullptr)) return rc;
   if (!public_inputs) return fail(SBN_ERR_BAD_ARG, "null argument");
   if (units != sbn_msm_num_units(count, num_io))
     return fail(SBN_ERR_VERIFY_FAILED, "%zu units given, a program of %zu nodes in tables of %zu has %zu units", units, count, num_io, sbn_msm_num_units(count, num_io));
@@ -152,5 +194,43 @@ extern "C" int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* co
       if (!below_p(out.data(), L.values())) return fail(SBN_ERR_VERIFY_FAILED, "instance %zu: output has a coefficient >= p", g);
       if (outs_out) memcpy(outs_out + L.xw * g, out.data(), L.xw * sizeof(uint32_t));
       return (int)SBN_OK;
-    });
+    }, maps);
+}
+extern "C" int sbn_program_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
+                                 const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                 const uint32_t* exps, size_t n_exps, uint32_t* outs_out) {
+  return program_check(kind, num_io, public_inputs, units, nodes, nullptr, count, values, n_values, exps, n_exps, outs_out);
+}
+extern "C" int sbn_program_m_check(int32_t kind, size_t num_io, const uint64_t* const* public_inputs, size_t units,
+                                   const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                   const uint32_t* exps, size_t n_exps, uint32_t* outs_out) {
+  std::vector<sbn_program_node> plain; std::vector<uint32_t> maps;
+  const sbn_program_node* twin = split_or_pass(nodes, count, plain, maps);
+  return program_check(kind, num_io, public_inputs, units, twin, maps.data(), count, values, n_values, exps, n_exps, outs_out);
+}
+
+// ---- the two host helpers of the mapped links ---------------------------------------------------------------------------------------
+extern "C" int sbn_fq12_frobenius(const uint32_t in[96], uint32_t m, uint32_t out[96]) {
+  if (!in || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (m > 11) return fail(SBN_ERR_BAD_ARG, "a Frobenius map is 0 .. 11, got %u", m);
+  if (!below_p(in, 12)) return fail(SBN_ERR_BAD_ARG, "coefficient >= p");
+  fq12_frobenius_words(in, m, out);
+  return SBN_OK;
+}
+// f^-1 = fbar / (f fbar), fbar = frob(f, 1) ... frob(f, 11): f fbar is the norm of f, an element of Fq, non-zero unless f is
+extern "C" int sbn_fq12_inverse(const uint32_t in[96], uint32_t out[96]) {
+  if (!in || !out) return fail(SBN_ERR_BAD_ARG, "null argument");
+  if (!below_p(in, 12)) return fail(SBN_ERR_BAD_ARG, "coefficient >= p");
+  Fq f[12], fbar[12], t[12];
+  field_load<12>(in, f);
+  bool zero = true;
+  for (int c = 0; c < 12; c++) zero = zero && fzero(f[c]);
+  if (zero) return fail(SBN_ERR_BAD_ARG, "zero has no inverse");
+  fq12_frobenius_m(f, 1, fbar);
+  for (unsigned m = 2; m < 12; m++) { fq12_frobenius_m(f, m, t); field_mul<12>(fbar, t, fbar); }
+  field_mul<12>(f, fbar, t);   // the norm: t[0], every other coefficient zero
+  const Fq ni = fq_inv_m(t[0]);
+  for (int c = 0; c < 12; c++) fbar[c] = mmul(fbar[c], ni);
+  field_store<12>(fbar, out);
+  return SBN_OK;
 }

@@ -149,8 +149,9 @@ struct PowerIn { const uint32_t* bases; const uint32_t* exps; size_t exp_count, 
 
 // sbn_prover_generate_trace_program: `count` nodes on an Fq12 table whose chains run on the device; x and offset of a node are a
 // literal of `values`, one, or the output of an earlier node, resolved on the device level by level (kernels_tracegen.cuh, "field
-// programs").
-struct ProgramIn { const sbn_program_node* nodes; size_t count; const uint32_t* values; const uint32_t* exps; uint32_t* outs_out; uint32_t* ios_out; };
+// programs").  maps (optional, [count]): the Frobenius maps of the links of a mapped program, applied on the device too
+// (kernels_tracegen.cuh, "mapped links").
+struct ProgramIn { const sbn_program_node* nodes; const uint32_t* maps; size_t count; const uint32_t* values; const uint32_t* exps; uint32_t* outs_out; uint32_t* ios_out; };
 
 // sbn_prover_generate_trace_curve_program: `count` nodes on a curve table whose chains run on the device; x and offset of a node
 // are a literal of `points`, the start (candidate 0), or the output of an earlier node, resolved on the device level by level
@@ -870,20 +871,39 @@ static int fq12_trace_towers(sbn_prover* P, const PowerIn& pw, size_t K, uint64_
 // programs: the literals, ones and exponents of every node go up in place (zeros where a link will be resolved; a pad row repeats
 // row count - 1) with the node table and the nodes sorted by level; one launch per level, one workgroup per node of that level,
 // resolves the links from the outputs of earlier launches and walks the chains (kernels_tracegen.cuh, "field programs"), the pads
-// are filled behind them, and the outputs come back together with the derived list in one download, as for the towers
+// are filled behind them, and the outputs come back together with the derived list in one download, as for the towers.  A mapped
+// operand (pr.maps) goes into the table of the pre-pass of its level -- (node, field, source node, map), level by level -- and is a
+// literal (zero words, bit 31 clear) in the device copy of the node table: the pre-pass launched in front of that level's launch
+// writes the mapped words into the node's row, and the level kernel, unchanged, loads them from there.
 static int fq12_trace_program(sbn_prover* P, const ProgramIn& pr, const ProgramPlan& plan, size_t K, uint64_t* pi_out) {
   Fq12Job J(P, K);
   const size_t IOW = J.IOW, M = pr.count;   // M real instances; rows [M, K) are pads
   const uint32_t one[96] = {1};
   std::vector<uint32_t> aux;                // the node table [K][3], then the order [M]: the pads are filled, not walked
   const std::vector<uint32_t> prelim = program_prelim(pr.nodes, M, K, 96, IOW - 192, pr.values, pr.exps, SBN_NODE_ONE, one, plan.order, aux);
+  const size_t map_at = aux.size();         // behind them the table of the pre-passes, [4] per mapped operand, level by level
+  std::vector<size_t> map_start(plan.depth() + 1, 0);
+  for (size_t l = 0; l < plan.depth() && pr.maps; l++) {
+    for (size_t i = plan.level_start[l]; i < plan.level_start[l + 1]; i++) {
+      const uint32_t g = plan.order[i], op[2] = {pr.nodes[g].x, pr.nodes[g].offset};
+      for (uint32_t f = 0; f < 2; f++)
+        if (const unsigned m = curve_host::map_of(pr.maps, g, (int)f)) {
+          aux.insert(aux.end(), {g, f, curve_host::link_of(op[f]), (uint32_t)m});
+          for (size_t r = g; r < (g + 1 == M ? K : g + 1); r++) aux[3 * r + f] = 0;   // (a pad repeats the table row of node M - 1; nothing walks it)
+        }
+    }
+    map_start[l + 1] = (aux.size() - map_at) / 4;
+  }
   uint32_t* d_aux = (uint32_t*)J.take(aux.size() / 2 + 1);
   if (int rc = J.upload_list(prelim.data())) return rc;
   HIPC(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, J.st));
   J.common_columns();
-  for (size_t l = 0; l < plan.depth(); l++)   // the kernel boundary between two levels is the link: level l reads what levels < l stored
+  for (size_t l = 0; l < plan.depth(); l++) {   // the kernel boundary between two levels is the link: level l reads what levels < l stored
+    if (pr.maps && map_start[l + 1] > map_start[l])
+      hipLaunchKernelGGL(tg::fq12_program_map_kernel, dim3((unsigned)(map_start[l + 1] - map_start[l])), dim3(64), 0, J.st, J.d_ios, IOW, d_aux + map_at + 4 * map_start[l], J.d_outs);
     hipLaunchKernelGGL(tg::fq12_program_level_kernel, dim3((unsigned)(plan.level_start[l + 1] - plan.level_start[l])), dim3(320), 0, J.st, J.d_ios, IOW, J.steps,
                        d_aux, d_aux + 3 * K + plan.level_start[l], J.ca, J.cb, J.d_outs);
+  }
   J.mark("program_levels");
   if (M < K) hipLaunchKernelGGL(tg::fq12_tower_pad_kernel, dim3((unsigned)(K - M)), dim3(256), 0, J.st, J.d_ios, IOW, M, K, (size_t)(J.steps + 1) * 48, J.ca, J.cb, J.d_outs);
   J.mark("program_pads");
@@ -1116,9 +1136,10 @@ extern "C" int sbn_prover_generate_trace_powers(sbn_prover* P, const uint32_t* b
   return fq12_trace_towers(P, pw, num_io, pi_out);
 }
 
-// sbn_prover_generate_trace on the one-unit list sbn_program_instances derives from (nodes, values, exps)
-extern "C" int sbn_prover_generate_trace_program(sbn_prover* P, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
-                                                 const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out) {
+// sbn_prover_generate_trace on the one-unit list sbn_program_instances derives from (nodes, values, exps); maps (optional, [count]):
+// the list of sbn_program_m_instances
+static int generate_trace_program(sbn_prover* P, const sbn_program_node* nodes, const uint32_t* maps, size_t count, const uint32_t* values, size_t n_values,
+                                  const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out) {
   if (int rc = unload(P)) return rc;
   const int kind = P->air.kind;
   if (!pi_layout(kind).field()) return fail(SBN_ERR_UNSUPPORTED, "field programs cover the field tables FQ_EXP, FQ12_EXP and FQ12_EXP_U64");
@@ -1128,11 +1149,22 @@ extern "C" int sbn_prover_generate_trace_program(sbn_prover* P, const sbn_progra
   bool device_chains;
   if (int rc = trace_gate(P, num_io, &device_chains)) return rc;
   if (!device_chains)
-    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) { return sbn_program_instances(kind, nodes, count, values, n_values, exps, n_exps, num_io, ios, outs_out); });
+    return trace_from_host_list(P, num_io, pi_out, ios_out, [&](uint32_t* ios) { return program_instances(kind, nodes, maps, count, values, n_values, exps, n_exps, num_io, ios, outs_out); });
   ProgramPlan plan;
-  if (int rc = program_plan(kind, nodes, count, values, n_values, exps, n_exps, num_io, plan)) return rc;
-  const ProgramIn pr{nodes, count, values, exps, outs_out, ios_out};
+  if (int rc = program_plan(kind, nodes, count, values, n_values, exps, n_exps, num_io, plan, maps)) return rc;
+  const ProgramIn pr{nodes, maps, count, values, exps, outs_out, ios_out};
   return fq12_trace_program(P, pr, plan, num_io, pi_out);
+}
+extern "C" int sbn_prover_generate_trace_program(sbn_prover* P, const sbn_program_node* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                                 const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out) {
+  return generate_trace_program(P, nodes, nullptr, count, values, n_values, exps, n_exps, pi_out, outs_out, ios_out);
+}
+// (a table that does not fit the unit is refused before a node is read, so only one that fits is split)
+extern "C" int sbn_prover_generate_trace_program_m(sbn_prover* P, const sbn_program_node_m* nodes, size_t count, const uint32_t* values, size_t n_values,
+                                                   const uint32_t* exps, size_t n_exps, uint64_t* pi_out, uint32_t* outs_out, uint32_t* ios_out) {
+  std::vector<sbn_program_node> plain; std::vector<uint32_t> maps;
+  if (P && nodes && count && count <= P->air.num_io) curve_host::split_nodes(nodes, count, plain, maps);
+  return generate_trace_program(P, plain.empty() ? (const sbn_program_node*)nodes : plain.data(), maps.data(), count, values, n_values, exps, n_exps, pi_out, outs_out, ios_out);
 }
 
 // sbn_prover_generate_trace on the one-unit list sbn_curve_program_instances derives from (nodes, points, exps).  Where the chains
